@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fixed-theta GP fits per second, n = 16384, d = 32, squared exponential.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either the driver's `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
      or plain `python bench.py --gpus N`, which re-launches itself under torch.distributed.run with N ranks on
      127.0.0.1; either way the line is only printed when the world size IS N and the RCCL communicator inside the
@@ -18,7 +18,12 @@ candidates r, r + N, ... through `egx_sweep_likelihood` (include/egx_gp.h), whos
 in LOCK-STEP groups (egx_gp_set_lockstep: one launch sequence per group of eight, grid.z = candidate; a handle of this
 size factors left-looking over its panel groups, kernels_chol.hip launch_potrf), two groups in flight.  The training set is resident in HBM before the timed region starts.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the Cholesky trailing update, FP64 MFMA
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step` = milliseconds per timed step) with the checksum of the timed candidates; `--dump-outputs DIR`
+also writes what the timed path returned in its last step (DIR/likelihood.npy, DIR/status.npy, float64).  Every side
+measurement below runs only with `--full`, after the timed region.
+
+With `--full`: `roofline` is for the dominant kernel (the Cholesky trailing update, FP64 MFMA
 bound), measured in a separate leg with ONE fit in flight; `cpu_baseline` is the blas-feature-shaped CPU path
 (oracle/cpu_baseline.py: OpenMP correlation build + LAPACK dpotrf) MEASURED at the full size in its own process on the
 GPU box's host -- one fit at its best thread count (latency mode) -- and `cpu_baseline_concurrent` as many such fits
@@ -566,6 +571,204 @@ def run_kernel_alone_leg(args, gpu):
                    "potrf_ms_with_lookahead_off).  What the kernel does with the chip to itself"}
 
 
+def single_fit_legs(args, egx, torch, x, y, base, gpu, lockstep, world, fits, elapsed):
+    """--full, rank 0, after the timed region: ONE fit in flight on its own handle (stage times, `roofline_single_matrix`),
+    one lock-step group alone (`roofline`), the kernel-alone and vendor yardsticks, the hbm roofline of the correlation
+    build and, at N = 1, the one-shot handle costs (`pcie_inclusive`).  Returns the keys they add to the line."""
+    n, d = args.n, args.d
+    # ---- roofline leg (not part of `value`): ONE fit in flight on its own handle, so the HIP-event duration of
+    # every update-kernel launch on its stream is not overlapped by another candidate's kernels
+    gp = egx.GpHandle(x, y, mean=0, corr=0, device=gpu, n_workspaces=1)
+    t_fit, tim0 = [], []
+    for j in range(4):  # the product's schedule: what a lone fit costs
+        tf0 = time.perf_counter()
+        gp.finalize(base * (1.0 + 0.01 * j))
+        t_fit.append(time.perf_counter() - tf0)
+        tim0.append(gp.timings())
+    t_fit, tim0 = t_fit[1:], tim0[1:]
+    # ... and the same fits with the look-ahead columns' update back IN FRONT of the trailing update on the main stream
+    # (in the product it runs beside it on a side stream and overlaps the HIP events around it): clean per-launch durations
+    prev_side = egx.set_tuning("lur_side", 0)
+    tim1 = []
+    for j in range(3):
+        gp.finalize(base * (1.0 + 0.01 * (4 + j)))
+        tim1.append(gp.timings())
+    egx.set_tuning("lur_side", prev_side)
+    potrf_ms = float(np.mean([t["potrf_ms"] for t in tim0]))
+    corr_ms = float(np.mean([t["corr_build_ms"] for t in tim0]))
+    solve_ms = float(np.mean([t["solve_ms"] for t in tim0]))
+    host_ms = float(np.mean([t["host_ms"] for t in tim0]))
+    flops = tim1[0]["potrf_flops"]
+    tflops = flops / (potrf_ms * 1e-3) / 1e12
+    syrk_ms = float(np.mean([t["potrf_syrk_ms"] for t in tim1]))
+    syrk_flops = float(np.mean([t["syrk_flops"] for t in tim1]))
+    syrk_launches = int(tim1[0]["syrk_launches"])
+    syrk_tflops = syrk_flops / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
+    # ---- ONE lock-step group alone (the unit the timed region keeps two of in flight): its whole factorisation rate.
+    # (No per-launch figure for the batched launches: inside a group the rest-of-group update runs on a side stream and
+    # overlaps the HIP events around the trailing update -- 47.7 TFLOP/s "per launch" beside 58.8 for the whole group.)
+    gl = max(1, min(lockstep, 8))
+    grp, roof_group = None, None
+    if gl > 1:
+        gq = egx.GpHandle(x, y, mean=0, corr=0, device=gpu, n_workspaces=gl)
+        gq.set_lockstep(gl)
+
+        def group_batch(j):
+            gq.likelihood_batch(np.stack([base * (1.0 + 0.01 * (j * gl + c)) for c in range(gl)]))
+            return gq.timings()
+        timg = [group_batch(j) for j in range(4)]
+        g_potrf = float(np.mean([t["potrf_ms"] for t in timg[1:]]))
+        grp = {"matrices": gl, "potrf_ms_all_matrices": g_potrf, "cholesky_tflops": gl * flops / (g_potrf * 1e-3) / 1e12,
+               "frac_of_fp64_peak": gl * flops / (g_potrf * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS}
+        # ---- the launch the timed region issues: the dominant update of a lock-step group (grid.z = gl matrices).  A
+        # handle of this shape factors LEFT-looking over its panel groups (round 4): the long update of the next group's
+        # columns is alone on its stream, HIP events bracket it cleanly, the previous group's chain shares the chip as in
+        # the product.  (A right-looking handle -- EGX_POTRF_LEFT=0 -- runs the look-ahead columns' update beside the
+        # trailing update on a side stream; lur_side = 0 puts it back in front for this leg.)
+        try:
+            prev = egx.set_tuning("lur_side", 0)  # (right-looking handles only: the left-looking schedule has no LUr)
+            timq = [group_batch(10 + j) for j in range(3)][1:]
+            egx.set_tuning("lur_side", prev)
+            ms8 = float(np.mean([t["potrf_syrk_ms"] for t in timq]))
+            fl8 = float(np.mean([t["syrk_flops"] for t in timq]))
+            nl8 = int(timq[0]["syrk_launches"])
+            if ms8 > 0 and nl8 > 0:
+                roof_group = {"tflops": fl8 / (ms8 * 1e-3) / 1e12, "launches": nl8, "launch_ms_avg": ms8 / nl8,
+                              "flops_per_launch_avg": fl8 / nl8, "share_of_potrf_flops": fl8 / (gl * flops),
+                              "potrf_ms_all_matrices_serialised": float(np.mean([t["potrf_ms"] for t in timq]))}
+        except Exception as e:  # noqa: BLE001 - falls back to the single-matrix figure below
+            sys.stderr.write(f"bench.py: group roofline leg failed: {e}\n")
+        gq.close()
+    traffic, pmc = measured_traffic(n, d)
+    # the same counters for the launch `roofline` describes (8 matrices, left-looking long update): committed summary
+    # (an OFFLINE measurement: attached only while it still describes this build -- the kernel's source text has the hash
+    #  the summary was taken with and the live launch shape is the measured one; otherwise `traffic` is null)
+    ll_pmc, ll_stale = None, None
+    import glob
+    ll_found = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_pmc_lockstep_group_left_looking_summary.json")))
+    ll_path = ll_found[-1] if ll_found else ""  # the latest round's measurement
+    if (n, d) == (16384, 32) and ll_path:
+        with open(ll_path) as f:
+            ll_pmc = json.load(f)
+        sig = stream_kernel_signature()
+        if sig != ll_pmc.get("kernel_source_sha256"):
+            ll_stale = f"k_gemm_stream source changed since the counters were taken ({sig[:12]} != recorded)"
+        elif roof_group is not None and (roof_group["launches"] != ll_pmc.get("launches_per_factorisation") or
+                                         abs(roof_group["flops_per_launch_avg"] / ll_pmc["algorithmic_flops_per_launch"] - 1.0) > 1e-6):
+            ll_stale = "the live launch shape (launches per factorisation / flops per launch) is not the measured one"
+        if ll_stale:
+            sys.stderr.write(f"bench.py: roofline.traffic not attached: {ll_stale}\n")
+            ll_pmc = None
+    out = {
+        "cholesky_tflops_per_gpu_in_timed_region": fits * flops / elapsed / 1e12 / world,
+        "stage_ms_single_fit": {"corr_build": corr_ms, "potrf_fused_fwd_solve": potrf_ms, "gamma_solve": solve_ms,
+                                "host_gls": host_ms},
+        "single_fit_in_flight_fits_per_s": 1.0 / float(np.mean(t_fit)),
+        "cholesky_tflops_single_fit": tflops,
+        "roofline": (None if roof_group is None else {
+            "bound": "mfma", "achieved": roof_group["tflops"], "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": roof_group["tflops"] / FP64_MFMA_PEAK_TFLOPS,
+            "traffic": (ll_pmc["corrected_traffic_bytes_per_launch"] if ll_pmc and gl == 8 else None),
+            "traffic_algorithmic_bytes": (ll_pmc["algorithmic_bytes_per_launch"] if ll_pmc and gl == 8 else None),
+            "launch_shape": f"{gl} matrices per launch (grid.z): the launch the timed region issues for a lock-step group",
+            "kernel": "k_gemm_stream<LOWER, TAG 1>: the LONG left-looking update of a lock-step group's next 1024 columns "
+                      "(C -= L[:, 0:g) L[cols, 0:g)^T with K = every column before the previous group, 128x256 tiles; a "
+                      "handle with n >= 14336 and a lock-step width of 8 factors left-looking over its groups of four "
+                      "256-wide panels, kernels_chol.hip launch_potrf): "
+                      f"{100.0 * roof_group['share_of_potrf_flops']:.0f} % of the factorisations' n^3/3 flops",
+            "share_of_potrf_flops": roof_group["share_of_potrf_flops"],
+            "launches_per_group": roof_group["launches"], "launch_ms_avg": roof_group["launch_ms_avg"],
+            "flops_per_launch_avg": roof_group["flops_per_launch_avg"],
+            "how": "algorithmic flops (matrices * 2 * K * (rows * 1024 - 1024 * 1023 / 2) per launch) / HIP-event durations "
+                   "around every such launch on the stream it is launched on; ONE lock-step group in flight; the chain of "
+                   "the previous group (diagonal blocks, panel solves, in-group updates) shares the chip with it as in "
+                   "the product.  Reproduce: rocprofv3 --kernel-trace --stats -- python tools/group_roofline.py, row "
+                   "'left-looking long update' of tools/rocpd_stats.py (profiles/r04_group_roofline_kernel_stats.txt)",
+            "traffic_stale": ll_stale,
+            "traffic_source": (None if not ll_pmc else {
+                "measured": "OFFLINE, not in this run; attached because the kernel source hash and the live launch shape match "
+                            "the measurement",
+                "kernel_source_sha256": ll_pmc.get("kernel_source_sha256"),
+                "file": "profiles/" + os.path.basename(ll_path) + " (from ..._pass1-3.json: separate rocprofv3 --pmc passes of "
+                        "tools/group_roofline.py, tools/gpu_pmc.sh group + tools/pmc_group_summary.py, offline)",
+                "fetch_size_bytes_per_launch_raw": ll_pmc["fetch_bytes_per_launch"],
+                "write_size_bytes_per_launch_raw": ll_pmc["write_bytes_per_launch"],
+                "correction": ll_pmc["correction"], "l2_hit_rate": ll_pmc["l2_hit_rate"],
+                "mfma_busy_frac": ll_pmc["mfma_busy_frac"],
+                "note": "3.8x the algorithmic bytes: each 128-row block of the factor is fetched by the four column tiles "
+                        "that use it on four different XCDs; 13.9 GB in 11 ms = 1.3 TB/s of fabric traffic (mostly "
+                        "Infinity-Cache hits), far from the bound -- and both walks that share those rows inside one XCD's "
+                        "L2 were slower (profiles/r04_run2_stream_walk_*, r04_run18_*)"})}),
+        "roofline_single_matrix": {"bound": "mfma", "achieved": syrk_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": syrk_tflops / FP64_MFMA_PEAK_TFLOPS,
+                     "traffic": traffic,
+                     "launch_shape": "ONE matrix per launch (a lone right-looking fit; the definition of rounds 1 to 3), with the "
+                                     "look-ahead columns' update serialised in front of it for this leg (lur_side = 0; the "
+                                     "product runs it beside the trailing update).  The timed region launches left-looking "
+                                     "updates for lock-step groups of eight: `roofline`",
+                     "kernel": "k_gemm_stream<LOWER> (Cholesky trailing update C -= P P^T, 128x256 tiles, once per group "
+                               "of four 256-wide panels, K = 1024, at this size; the launches with >= 512 tiles: "
+                               f"{100.0 * syrk_flops / flops:.0f} % of the factorisation's n^3/3 flops)",
+                     "share_of_potrf_flops": syrk_flops / flops,
+                     "launches_per_fit": syrk_launches, "launch_ms_avg": syrk_ms / max(1, syrk_launches),
+                     "flops_per_launch_avg": syrk_flops / max(1, syrk_launches),
+                     "how": "algorithmic flops (2*K*ncols*(ncols+1)/2 per launch, K = group width) / HIP-event durations around every "
+                            "launch on the stream it is launched on, one fit in flight (separate leg after the timed "
+                            "region; in the timed region the candidates in flight overlap and share the GPU)",
+                     "traffic_measured": "offline: separate rocprofv3 --pmc passes (tools/gpu_pmc.sh lone), committed under "
+                                         "profiles/ and READ here, not measured by this run",
+                     "traffic_source": (None if pmc is None else
+                                        {"file": os.path.relpath(PMC_SUMMARY, ROOT),
+                                         "fetch_bytes_per_launch_raw": pmc["fetch_bytes_per_launch"],
+                                         "write_bytes_per_launch_raw": pmc["write_bytes_per_launch"],
+                                         "c_read_bytes_per_launch_algorithmic": pmc["c_read_bytes_per_launch"],
+                                         "correction": "gfx950 FETCH_SIZE counts 16 B/lane reads at half: traffic = "
+                                                       "WRITE + C_read + 2 * (FETCH - C_read)"})},
+        "lockstep_group_alone": grp,
+        "roofline_kernel_alone": (run_kernel_alone_leg(args, gpu) if world == 1 and not args.no_extra_configs else None),
+        "vendor_yardstick": (vendor_yardstick(torch, gpu) if world == 1 and not args.no_extra_configs else None),
+        "corr_build_gbps": tim1[0]["corr_bytes"] / (corr_ms * 1e-3) / 1e9,
+        "corr_build_roofline": {"bound": "hbm", "achieved": tim1[0]["corr_bytes"] / (corr_ms * 1e-3) / 1e9,
+                                "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                "frac": tim1[0]["corr_bytes"] / (corr_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                "traffic": (None if pmc is None or "k_corr_sym" not in pmc else
+                                            pmc["k_corr_sym"].get("write_size_bytes_per_launch_raw", 0.0)
+                                            + pmc["k_corr_sym"].get("fetch_size_bytes_per_launch_raw", 0.0)),
+                                "note": "K1 is bound by FP64 VALU issue at d = 32 (3 d + ~25 ops per pair), not by "
+                                        "its 1.08 GB of writes: DESIGN.md section 4"},
+    }
+    if out["roofline"] is None:  # (a lock-step width of one: the single-matrix launches are the timed region's)
+        out["roofline"] = out["roofline_single_matrix"]
+    gp.close()
+    if world == 1:
+        # the boundary hands over HOST buffers: one-shot call sequences create -> fit -> read the scalars -> destroy,
+        # as the reference's one-shot `fit` is used (a model per expert / per EGO iteration) -- never `value`.
+        # `first_handle_in_process`: nothing pooled (2 GiB device allocation, stream / event creation, the first
+        # factorisation on untouched memory); `pooled`: the resources a destroyed handle of this shape left behind
+        def one_shot():
+            tc0 = time.perf_counter()
+            hc = egx.GpHandle(x, y, mean=0, corr=0, device=gpu, n_workspaces=1)
+            tc1 = time.perf_counter()
+            hc.finalize(base)
+            hc.fitted_scalars()
+            tc2 = time.perf_counter()
+            hc.close()
+            tc3 = time.perf_counter()
+            return {"create_alloc_upload_s": tc1 - tc0, "fit_and_download_s": tc2 - tc1, "destroy_s": tc3 - tc2,
+                    "fits_per_s": 1.0 / (tc3 - tc0)}
+        egx.trim()
+        first = one_shot()
+        pooled = [one_shot() for _ in range(4)][1:]
+        pooled_med = sorted(pooled, key=lambda r: r["fits_per_s"])[len(pooled) // 2]
+        out["pcie_inclusive"] = {"first_handle_in_process": first, "pooled": pooled_med,
+                                 "fits_per_s_cold_handle": pooled_med["fits_per_s"],
+                                 "pool": egx.pool_stats(),
+                                 "note": "x, y (4 MiB) cross PCIe once per handle; every further fit on the handle "
+                                         "moves (p + 2) n doubles back (0.4 MB); destroyed handles leave their "
+                                         "device resources in the library's pool (egx_trim frees it)"}
+    return out
+
+
 def spawn_ranks(n_ranks):
     """`python bench.py --gpus N` without a launcher: run N ranks of this script under torch.distributed.run on
     127.0.0.1 (one process per GPU, algorithm.rs:928-945's rayon workers at node scale) and pass its exit code on."""
@@ -624,8 +827,17 @@ def dry_launch(args, rank, world):
     return 0 if ok else 1
 
 
+def dump_outputs(dirname, lkh, status):
+    """--dump-outputs: what egx_sweep_likelihood handed its caller in the last timed step, one row per candidate of that
+    step -- the reduced likelihoods and the status codes (egx_status, as float64).  The candidates are drawn from fixed
+    seeds, so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "likelihood.npy"), np.asarray(lkh, dtype=np.float64))
+    np.save(os.path.join(dirname, "status.npy"), np.asarray(status, dtype=np.float64))
+
+
 # ---- the printed line: numbers first, <= 7 KB (the driver keeps the last 8 KB of stdout) -------------------------------------
-DETAILS_FILE = os.path.join("profiles", "bench_last_run_details.json")
+DETAILS_FILE = os.path.join("bench_out", "bench_last_run_details.json")  # (--full; kept out of git)
 _DROP_KEYS = {"metric_note", "thread_settings_tried", "settings_tried", "traffic_source", "how", "kernel", "launch_shape", "note",
               "note_numa", "traffic_measured", "query", "first_handle_in_process", "rccl_version", "pool", "traffic_stale",
               "extra_rows_note", "flops_per_launch_avg", "likelihood_checksum_ok_rows", "correction", "what", "reading", "threads",
@@ -663,12 +875,15 @@ def _compact(o, key=None):
     return o
 
 
-def compact_line(out, limit=7000):
-    """The full record goes to profiles/bench_last_run_details.json (and gpurun_out/ when it exists); the printed line keeps
-    the contract's keys, `roofline`, `cpu_baseline` and the numbers of every leg, without the prose and the settings tables."""
+def compact_line(out, limit=7000, details=True):
+    """With `details`, the full record goes to DETAILS_FILE (and to a copy in the run's output folder when one exists); the
+    printed line keeps the contract's keys, `roofline`, `cpu_baseline` and the numbers of every leg, without the prose and
+    the settings tables."""
+    if details:
+        os.makedirs(os.path.join(ROOT, os.path.dirname(DETAILS_FILE)), exist_ok=True)
     for path in (os.path.join(ROOT, DETAILS_FILE), os.path.join(ROOT, "gpurun_out", "bench_last_run_details.json")):
         try:
-            if os.path.isdir(os.path.dirname(path)):
+            if details and os.path.isdir(os.path.dirname(path)):
                 with open(path, "w") as f:
                     json.dump(out, f, indent=1)
         except OSError:
@@ -679,7 +894,8 @@ def compact_line(out, limit=7000):
     cb = line.get("cpu_baseline")
     if isinstance(cb, dict) and isinstance(cb.get("sample"), str):
         cb["sample"] = cb["sample"][:160]
-    line["details"] = DETAILS_FILE
+    if details:
+        line["details"] = DETAILS_FILE
     for k in _DROP_ORDER:
         if len(json.dumps(line, separators=(",", ":"))) <= limit:
             break
@@ -694,7 +910,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--npoints", dest="n", type=int, default=16384)
     ap.add_argument("--dim", dest="d", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every side measurement too: roofline legs, one-shot handle costs, "
+                         "other configurations, the tuned-fit and 512-row sweep legs, the N = 8 rank emulation, the CPU "
+                         "baselines; the full record goes to " + DETAILS_FILE)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/likelihood.npy and DIR/status.npy "
+                         "(float64, one row per candidate of that step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--in-flight", type=int, default=16,
                     help="candidates in flight per GPU (correlation-matrix workspaces of the sweep handle, 2 GiB each at "
                          "n = 16384): 2 lock-step groups of 8, factored left-looking (round 4; in flight / width -> fits/s: "
@@ -708,7 +931,8 @@ def main():
                     help="internal: the roofline launches of one fit with the look-ahead OFF (run as a child process with "
                          "EGX_LOOK_MIN set, the library reads its knobs once); prints one JSON object")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the bounded side measurements of BASELINE configs 3 / 5 and d = 64 (other_configs in the line)")
+                    help="with --full: skip the bounded side measurements of BASELINE configs 3 / 5 and d = 64 (other_configs "
+                         "in the line)")
     ap.add_argument("--lockstep", type=int, default=0,
                     help="candidates factored in lock-step by one launch sequence (0 = library default: 8 from 16 in flight on, else 4)")
     ap.add_argument("--assignment", choices=("static", "dynamic"), default="static",
@@ -721,6 +945,8 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="CPU rehearsal of the launch path: gloo + a stub evaluator, no GPU, no performance number")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.kernel_alone_leg:
         sys.exit(kernel_alone_leg(args))
@@ -874,14 +1100,14 @@ def main():
     # every rank (it is a collective): expert e on rank e mod N, smooth recombination of predict_var on 100 000 points
     # through egx_moe_predict_valvar and the sweep's communicator.  Never part of `value`; any failure becomes a string.
     moe_sharded = None
-    if world > 1 and not args.no_extra_configs and use_lib:
+    if args.full and world > 1 and not args.no_extra_configs and use_lib:
         try:
             moe_sharded = moe_sharded_leg(egx, workload, sw, rank, world, gpu)
         except Exception as e:  # noqa: BLE001 - reported in the line, must not take the headline number down
             moe_sharded = {"error": f"{type(e).__name__}: {e}"[:300]}
     # the tuned fit with its starts sharded over the ranks (every N, also 1): bounded, after the timed region, collective
     tuned = None
-    if not args.no_extra_configs and use_lib:
+    if args.full and not args.no_extra_configs and use_lib:
         try:
             tuned = tuned_fit_leg(egx, sw, d, world)
         except Exception as e:  # noqa: BLE001
@@ -890,7 +1116,7 @@ def main():
     # through the same collective, after the timed region (most rows give R ~ I and a few are not positive definite: it is
     # a parity / coverage figure -- tests/test_gpu_configs.py pins 33 of its rows -- never `value`)
     config4 = None
-    if not args.no_extra_configs and (n, d) == (16384, 32):
+    if args.full and not args.no_extra_configs and (n, d) == (16384, 32):
         try:
             c4 = egx.theta_sweep_candidates(512, d)
             barrier()
@@ -914,7 +1140,7 @@ def main():
     # and the all-gather after every step.  This rank drives exactly that through the same collective entry point; the implied
     # 8-GPU figure is 8 x its rate (candidates are independent, X and y replicated: nothing else is shared between ranks).
     n8_emulation = None
-    if world == 1 and use_lib and not args.no_extra_configs and nb >= 24:
+    if args.full and world == 1 and use_lib and not args.no_extra_configs and nb >= 24:
         try:
             share = nb // 8
             c8 = cands[:12 * share].reshape(12, share, d)
@@ -940,90 +1166,10 @@ def main():
         sys.exit(4)
 
     if rank == 0:
-        # ---- roofline leg (not part of `value`): ONE fit in flight on its own handle, so the HIP-event duration of
-        # every update-kernel launch on its stream is not overlapped by another candidate's kernels
-        gp = egx.GpHandle(x, y, mean=0, corr=0, device=gpu, n_workspaces=1)
-        t_fit, tim0 = [], []
-        for j in range(4):  # the product's schedule: what a lone fit costs
-            tf0 = time.perf_counter()
-            gp.finalize(base * (1.0 + 0.01 * j))
-            t_fit.append(time.perf_counter() - tf0)
-            tim0.append(gp.timings())
-        t_fit, tim0 = t_fit[1:], tim0[1:]
-        # ... and the same fits with the look-ahead columns' update back IN FRONT of the trailing update on the main stream
-        # (in the product it runs beside it on a side stream and overlaps the HIP events around it): clean per-launch durations
-        prev_side = egx.set_tuning("lur_side", 0)
-        tim1 = []
-        for j in range(3):
-            gp.finalize(base * (1.0 + 0.01 * (4 + j)))
-            tim1.append(gp.timings())
-        egx.set_tuning("lur_side", prev_side)
+        if args.dump_outputs:
+            last = slice((args.warmup + args.steps - 1) * nb, (args.warmup + args.steps) * nb)
+            dump_outputs(args.dump_outputs, lkhs[last], stats[last])
         fits = args.steps * nb
-        potrf_ms = float(np.mean([t["potrf_ms"] for t in tim0]))
-        corr_ms = float(np.mean([t["corr_build_ms"] for t in tim0]))
-        solve_ms = float(np.mean([t["solve_ms"] for t in tim0]))
-        host_ms = float(np.mean([t["host_ms"] for t in tim0]))
-        flops = tim1[0]["potrf_flops"]
-        tflops = flops / (potrf_ms * 1e-3) / 1e12
-        syrk_ms = float(np.mean([t["potrf_syrk_ms"] for t in tim1]))
-        syrk_flops = float(np.mean([t["syrk_flops"] for t in tim1]))
-        syrk_launches = int(tim1[0]["syrk_launches"])
-        syrk_tflops = syrk_flops / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
-        # ---- ONE lock-step group alone (the unit the timed region keeps two of in flight): its whole factorisation rate.
-        # (No per-launch figure for the batched launches: inside a group the rest-of-group update runs on a side stream and
-        # overlaps the HIP events around the trailing update -- 47.7 TFLOP/s "per launch" beside 58.8 for the whole group.)
-        gl = max(1, min(lockstep, 8))
-        grp, roof_group = None, None
-        if gl > 1:
-            gq = egx.GpHandle(x, y, mean=0, corr=0, device=gpu, n_workspaces=gl)
-            gq.set_lockstep(gl)
-
-            def group_batch(j):
-                gq.likelihood_batch(np.stack([base * (1.0 + 0.01 * (j * gl + c)) for c in range(gl)]))
-                return gq.timings()
-            timg = [group_batch(j) for j in range(4)]
-            g_potrf = float(np.mean([t["potrf_ms"] for t in timg[1:]]))
-            grp = {"matrices": gl, "potrf_ms_all_matrices": g_potrf, "cholesky_tflops": gl * flops / (g_potrf * 1e-3) / 1e12,
-                   "frac_of_fp64_peak": gl * flops / (g_potrf * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS}
-            # ---- the launch the timed region issues: the dominant update of a lock-step group (grid.z = gl matrices).  A
-            # handle of this shape factors LEFT-looking over its panel groups (round 4): the long update of the next group's
-            # columns is alone on its stream, HIP events bracket it cleanly, the previous group's chain shares the chip as in
-            # the product.  (A right-looking handle -- EGX_POTRF_LEFT=0 -- runs the look-ahead columns' update beside the
-            # trailing update on a side stream; lur_side = 0 puts it back in front for this leg.)
-            try:
-                prev = egx.set_tuning("lur_side", 0)  # (right-looking handles only: the left-looking schedule has no LUr)
-                timq = [group_batch(10 + j) for j in range(3)][1:]
-                egx.set_tuning("lur_side", prev)
-                ms8 = float(np.mean([t["potrf_syrk_ms"] for t in timq]))
-                fl8 = float(np.mean([t["syrk_flops"] for t in timq]))
-                nl8 = int(timq[0]["syrk_launches"])
-                if ms8 > 0 and nl8 > 0:
-                    roof_group = {"tflops": fl8 / (ms8 * 1e-3) / 1e12, "launches": nl8, "launch_ms_avg": ms8 / nl8,
-                                  "flops_per_launch_avg": fl8 / nl8, "share_of_potrf_flops": fl8 / (gl * flops),
-                                  "potrf_ms_all_matrices_serialised": float(np.mean([t["potrf_ms"] for t in timq]))}
-            except Exception as e:  # noqa: BLE001 - falls back to the single-matrix figure below
-                sys.stderr.write(f"bench.py: group roofline leg failed: {e}\n")
-            gq.close()
-        traffic, pmc = measured_traffic(n, d)
-        # the same counters for the launch `roofline` describes (8 matrices, left-looking long update): committed summary
-        # (an OFFLINE measurement: attached only while it still describes this build -- the kernel's source text has the hash
-        #  the summary was taken with and the live launch shape is the measured one; otherwise `traffic` is null)
-        ll_pmc, ll_stale = None, None
-        import glob
-        ll_found = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_pmc_lockstep_group_left_looking_summary.json")))
-        ll_path = ll_found[-1] if ll_found else ""  # the latest round's measurement
-        if (n, d) == (16384, 32) and ll_path:
-            with open(ll_path) as f:
-                ll_pmc = json.load(f)
-            sig = stream_kernel_signature()
-            if sig != ll_pmc.get("kernel_source_sha256"):
-                ll_stale = f"k_gemm_stream source changed since the counters were taken ({sig[:12]} != recorded)"
-            elif roof_group is not None and (roof_group["launches"] != ll_pmc.get("launches_per_factorisation") or
-                                             abs(roof_group["flops_per_launch_avg"] / ll_pmc["algorithmic_flops_per_launch"] - 1.0) > 1e-6):
-                ll_stale = "the live launch shape (launches per factorisation / flops per launch) is not the measured one"
-            if ll_stale:
-                sys.stderr.write(f"bench.py: roofline.traffic not attached: {ll_stale}\n")
-                ll_pmc = None
         ok = stats[args.warmup * nb:] == 0
         out = {
             "metric": "gp_fixed_theta_fits_per_sec", "value": fits / elapsed, "unit": "fits/s",
@@ -1052,115 +1198,12 @@ def main():
                                   "evaluation_seconds_per_rank": eval_seconds,
                                   "imbalance_max_over_mean": (max(eval_seconds) / (sum(eval_seconds) / len(eval_seconds))
                                                               if sum(eval_seconds) > 0 else None)},
-            "cholesky_tflops_per_gpu_in_timed_region": fits * flops / elapsed / 1e12 / world,
-            "stage_ms_single_fit": {"corr_build": corr_ms, "potrf_fused_fwd_solve": potrf_ms, "gamma_solve": solve_ms,
-                                    "host_gls": host_ms},
-            "single_fit_in_flight_fits_per_s": 1.0 / float(np.mean(t_fit)),
-            "cholesky_tflops_single_fit": tflops,
-            "roofline": (None if roof_group is None else {
-                "bound": "mfma", "achieved": roof_group["tflops"], "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": roof_group["tflops"] / FP64_MFMA_PEAK_TFLOPS,
-                "traffic": (ll_pmc["corrected_traffic_bytes_per_launch"] if ll_pmc and gl == 8 else None),
-                "traffic_algorithmic_bytes": (ll_pmc["algorithmic_bytes_per_launch"] if ll_pmc and gl == 8 else None),
-                "launch_shape": f"{gl} matrices per launch (grid.z): the launch the timed region issues for a lock-step group",
-                "kernel": "k_gemm_stream<LOWER, TAG 1>: the LONG left-looking update of a lock-step group's next 1024 columns "
-                          "(C -= L[:, 0:g) L[cols, 0:g)^T with K = every column before the previous group, 128x256 tiles; a "
-                          "handle with n >= 14336 and a lock-step width of 8 factors left-looking over its groups of four "
-                          "256-wide panels, kernels_chol.hip launch_potrf): "
-                          f"{100.0 * roof_group['share_of_potrf_flops']:.0f} % of the factorisations' n^3/3 flops",
-                "share_of_potrf_flops": roof_group["share_of_potrf_flops"],
-                "launches_per_group": roof_group["launches"], "launch_ms_avg": roof_group["launch_ms_avg"],
-                "flops_per_launch_avg": roof_group["flops_per_launch_avg"],
-                "how": "algorithmic flops (matrices * 2 * K * (rows * 1024 - 1024 * 1023 / 2) per launch) / HIP-event durations "
-                       "around every such launch on the stream it is launched on; ONE lock-step group in flight; the chain of "
-                       "the previous group (diagonal blocks, panel solves, in-group updates) shares the chip with it as in "
-                       "the product.  Reproduce: rocprofv3 --kernel-trace --stats -- python tools/group_roofline.py, row "
-                       "'left-looking long update' of tools/rocpd_stats.py (profiles/r04_group_roofline_kernel_stats.txt)",
-                "traffic_stale": ll_stale,
-                "traffic_source": (None if not ll_pmc else {
-                    "measured": "OFFLINE, not in this run; attached because the kernel source hash and the live launch shape match "
-                                "the measurement",
-                    "kernel_source_sha256": ll_pmc.get("kernel_source_sha256"),
-                    "file": "profiles/" + os.path.basename(ll_path) + " (from ..._pass1-3.json: separate rocprofv3 --pmc passes of "
-                            "tools/group_roofline.py, tools/gpu_pmc.sh group + tools/pmc_group_summary.py, offline)",
-                    "fetch_size_bytes_per_launch_raw": ll_pmc["fetch_bytes_per_launch"],
-                    "write_size_bytes_per_launch_raw": ll_pmc["write_bytes_per_launch"],
-                    "correction": ll_pmc["correction"], "l2_hit_rate": ll_pmc["l2_hit_rate"],
-                    "mfma_busy_frac": ll_pmc["mfma_busy_frac"],
-                    "note": "3.8x the algorithmic bytes: each 128-row block of the factor is fetched by the four column tiles "
-                            "that use it on four different XCDs; 13.9 GB in 11 ms = 1.3 TB/s of fabric traffic (mostly "
-                            "Infinity-Cache hits), far from the bound -- and both walks that share those rows inside one XCD's "
-                            "L2 were slower (profiles/r04_run2_stream_walk_*, r04_run18_*)"})}),
-            "roofline_single_matrix": {"bound": "mfma", "achieved": syrk_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": syrk_tflops / FP64_MFMA_PEAK_TFLOPS,
-                         "traffic": traffic,
-                         "launch_shape": "ONE matrix per launch (a lone right-looking fit; the definition of rounds 1 to 3), with the "
-                                         "look-ahead columns' update serialised in front of it for this leg (lur_side = 0; the "
-                                         "product runs it beside the trailing update).  The timed region launches left-looking "
-                                         "updates for lock-step groups of eight: `roofline`",
-                         "kernel": "k_gemm_stream<LOWER> (Cholesky trailing update C -= P P^T, 128x256 tiles, once per group "
-                                   "of four 256-wide panels, K = 1024, at this size; the launches with >= 512 tiles: "
-                                   f"{100.0 * syrk_flops / flops:.0f} % of the factorisation's n^3/3 flops)",
-                         "share_of_potrf_flops": syrk_flops / flops,
-                         "launches_per_fit": syrk_launches, "launch_ms_avg": syrk_ms / max(1, syrk_launches),
-                         "flops_per_launch_avg": syrk_flops / max(1, syrk_launches),
-                         "how": "algorithmic flops (2*K*ncols*(ncols+1)/2 per launch, K = group width) / HIP-event durations around every "
-                                "launch on the stream it is launched on, one fit in flight (separate leg after the timed "
-                                "region; in the timed region the candidates in flight overlap and share the GPU)",
-                         "traffic_measured": "offline: separate rocprofv3 --pmc passes (tools/gpu_pmc.sh lone), committed under "
-                                             "profiles/ and READ here, not measured by this run",
-                         "traffic_source": (None if pmc is None else
-                                            {"file": os.path.relpath(PMC_SUMMARY, ROOT),
-                                             "fetch_bytes_per_launch_raw": pmc["fetch_bytes_per_launch"],
-                                             "write_bytes_per_launch_raw": pmc["write_bytes_per_launch"],
-                                             "c_read_bytes_per_launch_algorithmic": pmc["c_read_bytes_per_launch"],
-                                             "correction": "gfx950 FETCH_SIZE counts 16 B/lane reads at half: traffic = "
-                                                           "WRITE + C_read + 2 * (FETCH - C_read)"})},
-            "lockstep_group_alone": grp,
-            "roofline_kernel_alone": (run_kernel_alone_leg(args, gpu) if world == 1 and not args.no_extra_configs else None),
-            "vendor_yardstick": (vendor_yardstick(torch, gpu) if world == 1 and not args.no_extra_configs else None),
-            "corr_build_gbps": tim1[0]["corr_bytes"] / (corr_ms * 1e-3) / 1e9,
-            "corr_build_roofline": {"bound": "hbm", "achieved": tim1[0]["corr_bytes"] / (corr_ms * 1e-3) / 1e9,
-                                    "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                    "frac": tim1[0]["corr_bytes"] / (corr_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                    "traffic": (None if pmc is None or "k_corr_sym" not in pmc else
-                                                pmc["k_corr_sym"].get("write_size_bytes_per_launch_raw", 0.0)
-                                                + pmc["k_corr_sym"].get("fetch_size_bytes_per_launch_raw", 0.0)),
-                                    "note": "K1 is bound by FP64 VALU issue at d = 32 (3 d + ~25 ops per pair), not by "
-                                            "its 1.08 GB of writes: DESIGN.md section 4"},
             "candidates_ok": int(ok.sum()), "candidates_failed": int((~ok).sum()),
             "likelihood_checksum": float(np.sum(lkhs[args.warmup * nb:][ok])),
         }
-        if out["roofline"] is None:  # (a lock-step width of one: the single-matrix launches are the timed region's)
-            out["roofline"] = out["roofline_single_matrix"]
-        gp.close()
-        if world == 1:
-            # the boundary hands over HOST buffers: one-shot call sequences create -> fit -> read the scalars -> destroy,
-            # as the reference's one-shot `fit` is used (a model per expert / per EGO iteration) -- never `value`.
-            # `first_handle_in_process`: nothing pooled (2 GiB device allocation, stream / event creation, the first
-            # factorisation on untouched memory); `pooled`: the resources a destroyed handle of this shape left behind
-            def one_shot():
-                tc0 = time.perf_counter()
-                hc = egx.GpHandle(x, y, mean=0, corr=0, device=gpu, n_workspaces=1)
-                tc1 = time.perf_counter()
-                hc.finalize(base)
-                hc.fitted_scalars()
-                tc2 = time.perf_counter()
-                hc.close()
-                tc3 = time.perf_counter()
-                return {"create_alloc_upload_s": tc1 - tc0, "fit_and_download_s": tc2 - tc1, "destroy_s": tc3 - tc2,
-                        "fits_per_s": 1.0 / (tc3 - tc0)}
-            egx.trim()
-            first = one_shot()
-            pooled = [one_shot() for _ in range(4)][1:]
-            pooled_med = sorted(pooled, key=lambda r: r["fits_per_s"])[len(pooled) // 2]
-            out["pcie_inclusive"] = {"first_handle_in_process": first, "pooled": pooled_med,
-                                     "fits_per_s_cold_handle": pooled_med["fits_per_s"],
-                                     "pool": egx.pool_stats(),
-                                     "note": "x, y (4 MiB) cross PCIe once per handle; every further fit on the handle "
-                                             "moves (p + 2) n doubles back (0.4 MB); destroyed handles leave their "
-                                             "device resources in the library's pool (egx_trim frees it)"}
-        if world == 1 and not args.no_extra_configs:
+        if args.full:
+            out.update(single_fit_legs(args, egx, torch, x, y, base, gpu, lockstep, world, fits, elapsed))
+        if args.full and world == 1 and not args.no_extra_configs:
             out["other_configs"] = other_configs(egx, workload, gpu)
         if moe_sharded is not None:
             out["other_configs"] = {"config5_mixture_8_experts_sharded": moe_sharded}
@@ -1170,7 +1213,7 @@ def main():
             out.setdefault("other_configs", {})["config4_sweep_512"] = config4
         if n8_emulation is not None:
             out["n8_rank_emulation"] = n8_emulation
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             torch.cuda.synchronize()
             cb = cpu_baseline(n, d)
             hp = host_fp64_peak()
@@ -1197,7 +1240,7 @@ def main():
             rs = cpu_baseline_reference_shaped(n, d)
             if rs is not None:
                 out["cpu_baseline_reference_shaped"] = rs
-        print(compact_line(out), flush=True)
+        print(compact_line(out, details=args.full), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -35,6 +35,12 @@ def test_bench_single_rank_dry_launch():
     assert rec["n_gpus"] == 1
 
 
+def test_bench_refuses_a_run_without_timed_steps():
+    out = _run(["--gpus", "1", "--dry-launch", "--steps", "0"])
+    assert out.returncode == 2 and "--steps" in out.stderr
+    assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
 def test_bench_refuses_a_mislabelled_world():
     out = _run(["--gpus", "8", "--dry-launch"], env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert out.returncode == 2 and "refusing" in out.stderr

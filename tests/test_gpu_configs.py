@@ -552,7 +552,7 @@ def test_bench_gpus_2_rehearsal_on_one_gpu():
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--sweep-batch", "10", "--in-flight", "4", "--npoints", "2048", "--dim", "6", "--no-cpu-baseline",
-                          "--assignment", "dynamic"], cwd=root, env=env, capture_output=True, text=True, timeout=500)
+                          "--assignment", "dynamic", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -598,6 +598,41 @@ def test_bench_gpus_2_falls_back_to_torch_collective(how):
     assert fb["n_gpus"] == 2 and fb["candidates_ok"] == 20 and len(fb["rank_seconds"]) == 2
     assert fb["last_step_balance"]["candidates_per_rank"] == [5, 5]
     assert fb["likelihood_checksum"] == lib["likelihood_checksum"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_what_its_last_step_computed(egx, tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline keys and none of the --full legs; --dump-outputs writes the
+    last timed step's likelihoods and statuses, which are what likelihood_batch gives for the same seeded candidates."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "EGX_SWEEP_TRANSPORT"):
+        env.pop(k, None)
+    steps, warmup, nb, n, d = 3, 1, 8, 2048, 6
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                          str(warmup), "--sweep-batch", str(nb), "--in-flight", "4", "--npoints", str(n), "--dim", str(d),
+                          "--dump-outputs", str(tmp_path / "dump")], cwd=root, env=env, capture_output=True, text=True,
+                         timeout=280)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "gp_fixed_theta_fits_per_sec" and rec["unit"] == "fits/s" and rec["dtype"] == "f64"
+    assert rec["higher_is_better"] is True and rec["steps"] == steps and rec["ms_per_step"] > 0
+    assert rec["value"] == pytest.approx(nb * 1e3 / rec["ms_per_step"], rel=1e-3)
+    assert not {"roofline", "other_configs", "cpu_baseline", "pcie_inclusive", "details"} & set(rec)
+    lk = np.load(tmp_path / "dump" / "likelihood.npy")
+    st = np.load(tmp_path / "dump" / "status.npy")
+    assert lk.dtype == np.float64 and st.dtype == np.float64 and lk.shape == st.shape == (nb,)
+    x, y = _data(n, d, 42)
+    cands = egx.workload.default_theta(d) * 10.0 ** np.random.default_rng(1234).uniform(-0.15, 0.15,
+                                                                                          size=((steps + warmup) * nb, d))
+    with egx.GpHandle(x, y, n_workspaces=4) as h:
+        want_lk, want_st = h.likelihood_batch(cands[-nb:])
+    np.testing.assert_array_equal(st, want_st)
+    np.testing.assert_allclose(lk, want_lk, rtol=LK_RTOL)
 
 
 @pytest.mark.parametrize("k,nx,hf", [(1, 3, 1.0), (2, 1, 1.0), (3, 2, 0.99), (8, 16, 0.9), (8, 16, 0.3), (4, 64, 1.0)])

@@ -290,15 +290,17 @@ def test_arbiter_agrees_with_numpy_oracle_where_the_problem_is_well_posed(ARB, k
 
 
 def test_arbiter_fixture_is_what_the_arbiter_computes(golden_dir, ARB):
-    """tests/golden/arbiter.json was generated by this code: the control case reproduces bit for bit (the arithmetic is
-    x87 long double in a fixed order per row -- OpenMP only splits rows), and on it LAPACK and the arbiter agree; the
+    """tests/golden/arbiter.json was generated by this code: the control case reproduces (the arithmetic is x87 long
+    double in a fixed order per row -- OpenMP only splits rows -- but the x87 transcendental instructions behind expl /
+    log10l are not correctly rounded and differ in their last bits between CPU models, so on another host the value is
+    a few double ulps away: 1e-14 relative, 400x closer than LAPACK), and on it LAPACK and the arbiter agree; the
     recorded LAPACK errors of the ill-posed cases are what this container's numpy gives, to within the BLAS build."""
     fx = _load(golden_dir, "arbiter.json")
     c = fx["control_n2048_d8_matern52"]
     x = O.lhs_classic(c["n"], c["d"], c["seed"])
     y = O.griewank(x)
     r = ARB.likelihood(x, y, np.array(c["theta"]), corr=c["corr"])
-    assert r["status"] == 0 and r["likelihood"] == c["truth_likelihood"]
+    assert r["status"] == 0 and abs(r["likelihood"] - c["truth_likelihood"]) <= 1e-14 * abs(c["truth_likelihood"])
     assert c["lapack_rel_error"] < 1e-10
     # the ill-posed cases: LAPACK is 1e-9 .. 1e-5 away from the extended-precision value, and not consistently
     assert 1e-7 < fx["config2_n4096_d8_sqexp"]["lapack_rel_error"] < 1e-4

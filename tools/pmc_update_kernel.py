@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise the separate rocprofv3 --pmc passes of `bench.py --steps 1` for the chip-filling trailing-update launches
+"""Summarise the separate rocprofv3 --pmc passes of `bench.py --full --steps 1` for the chip-filling trailing-update launches
 (k_gemm_stream / k_gemm_nt_sub<128x256> with >= 512 tiles) into profiles/r02_pmc_update_kernel.json, the file bench.py's
 `roofline.traffic` is read from.  FETCH_SIZE / WRITE_SIZE are reported in KiB-like units of 1 KB by rocprofv3 (round 1:
 1.144e8 "KB" over 140 launches); raw per-launch BYTES are stored here, the gfx950 16 B/lane correction is applied by
