@@ -21,6 +21,9 @@ TEST_LIB_PATH = os.path.join(_HERE, "lib", "_dev", "libegx_gp_hip_testhooks.so")
 #: tools/long_update_attribution.py) -- built by hand, never by build(), never the default
 TRACE_LIB_PATH = os.path.join(_HERE, "lib", "_dev", "libegx_gp_hip_trace.so")
 
+# sampling methods (egx_sample_method)
+SAMPLE_CHOLESKY, SAMPLE_PSD = 0, 1
+
 # return codes / status values (egx_rc, egx_status)
 SUCCESS, ERR_INVALID_VALUE, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_FITTED, ERR_LINALG, ERR_LIKELIHOOD, ERR_UNSUPPORTED, ERR_PEER = range(9)
 STATUS_OK, STATUS_NOT_POSITIVE_DEFINITE, STATUS_ILL_CONDITIONED_FT, STATUS_ILL_CONDITIONED_F, STATUS_NAN_THETA, STATUS_RANK_FAILED = range(6)
@@ -97,6 +100,10 @@ SIGNATURES = [
     ("egx_gp_predict_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_var_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_valvar_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    ("egx_gp_predict_covariance", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
+    ("egx_gp_sample", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, c_double_p, c_double_p,
+                                  c_double_p]),
+    ("egx_random_normals", C.c_int32, [C.c_int32, C.c_uint64, C.c_int64, C.c_int64, c_double_p]),
     ("egx_gp_get_inner", C.c_int32, [C.c_void_p, C.POINTER(InnerView)]),
     ("egx_gp_set_inner", C.c_int32, [C.c_void_p, C.POINTER(InnerView)]),
     ("egx_corr_matrix", C.c_int32, [C.c_int32, c_double_p, C.c_int64, C.c_int64, c_double_p, C.c_double, c_double_p]),
@@ -171,6 +178,10 @@ class LikelihoodComputationError(EgxError):
 
 class PeerError(EgxError):
     """A collective call in which another rank failed or did not answer (EGX_ERR_PEER)."""
+
+
+class SampleError(EgxError, ValueError):
+    """MoeError::SampleError (crates/moe/src/errors.rs:30): a mixture of several clusters cannot be sampled."""
 
 
 _ERR = {ERR_INVALID_VALUE: InvalidValueError, ERR_NO_DEVICE: NoDeviceError, ERR_NOT_FITTED: NotFittedError,

@@ -121,6 +121,22 @@ int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, in
                       int nout, int64_t ld, const GradBatch &batch, int prescaled = 0);
 // z (n) <- W y, W upper triangular row-major
 int launch_uptri_gemv(hipStream_t s, const double *W, int64_t ld, int n, const double *y, double *z);
+// posterior covariance of the m queries (k-major xqT, m_pad a multiple of 64): S (m_pad x m_pad, lds) = sigma2 (K(xq, xq) + G)
+// + tau I on the leading m x m block (K without nugget; G lower tiles read at i >= j only: S exactly symmetric), identity
+// rows / columns beyond m
+int launch_cov_assemble(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, int d, const double *coef, int hcols,
+                        const double *G, int64_t ldg, int m, double sigma2, double tau, double *S, int64_t lds);
+
+// ---- kernels_sample.hip -----------------------------------------------------
+// U / Uneg (m_pad x ldu, zero padded beyond p and below m) = +- Rq^-T (sl[q] - f(x_q))^T per query: the u of predict_var;
+// fidx (2 p ints) names the coordinates of regression column l (-1: 1.0), R = ft_qr_r (p x p row-major) on the device
+int launch_sample_u(hipStream_t s, const double *sl, int p, const double *xqT, int64_t ldq, const int *fidx, const double *R,
+                    int m, int m_pad, double *U, double *Uneg, int64_t ldu);
+// Z[i * si + j * sj] (i < m, j < nt) = the normals of philox.h for `seed`
+int launch_normals(hipStream_t s, uint64_t seed, int64_t m, int64_t nt, double *Z, int64_t si, int64_t sj);
+// T (m_pad x nt_pad, ldt) = mean 1^T + L Zt^T, L lower triangular with a zero strict upper triangle, Zt (nt_pad x m_pad, ldz)
+int launch_trmm_mean(hipStream_t s, const double *L, int64_t ldl, int m_pad, const double *Zt, int64_t ldz, int nt_pad,
+                     const double *mean, double *T, int64_t ldt);
 
 // ---- kernels_chol.hip -------------------------------------------------------
 // In-place blocked right-looking Cholesky of the leading n_pad x n_pad block (lower), applied to

@@ -1271,4 +1271,70 @@ int launch_uptri_gemv(hipStream_t s, const double *W, int64_t ld, int n, const d
     return EGX_SUCCESS;
 }
 
+// Posterior covariance of m query points (GaussianProcess::_compute_covariance, algorithm.rs:310-326), one 64 x 64 tile of
+// the lower triangle per workgroup: S[i][j] = S[j][i] = sigma2 (k(x_i, x_j) + G[i][j]) + tau [i == j] for i >= j, both < m,
+// with k the handle's correlation WITHOUT nugget (k(x, x) = 1) and G = -rt^T rt + u^T u (the Gram kernels' lower tiles, read
+// at i >= j only: the result is exactly symmetric); rows and columns m .. m_pad - 1 become those of the identity, so that
+// launch_potrf factors S as it stands.  Each unordered pair is evaluated once and stored twice.
+template <int CORR, bool PRE>
+__global__ __launch_bounds__(256) void k_cov_assemble(const double *__restrict__ xqT, int64_t ldq, int d,
+                                                      const double *__restrict__ coef, int hcols, const double *__restrict__ G,
+                                                      int64_t ldg, int m, double sigma2, double tau, double *__restrict__ S,
+                                                      int64_t lds) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int t = blockIdx.x;
+    int bx = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while (bx * (bx + 1) / 2 > t) bx--;
+    while ((bx + 1) * (bx + 2) / 2 <= t) bx++;
+    const int by = t - bx * (bx + 1) / 2;
+    const int dc = d < kCorrDC ? d : kCorrDC;
+    double *xi = sm, *xj = sm + dc * 64;
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    PairAcc<CORR> acc[4][4];
+    for (int c0 = 0; c0 < d; c0 += dc) {
+        const int dn = (d - c0 < dc) ? (d - c0) : dc;
+        if (c0) __syncthreads();
+        stage_slab(xi, xqT + (int64_t)c0 * ldq, ldq, bx * 64, dn, tid, PRE ? coef + c0 : nullptr);
+        stage_slab(xj, xqT + (int64_t)c0 * ldq, ldq, by * 64, dn, tid, PRE ? coef + c0 : nullptr);
+        __syncthreads();
+        tile_pairs_acc<CORR, PRE>(xi, xj, coef + (int64_t)c0 * hcols, hcols, dn, ty, tx, acc);
+    }
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int i = bx * 64 + ty * 4 + a, j = by * 64 + tx * 4 + b;
+            if (j > i) continue;  // (diagonal tiles) the pair comes as (j, i)
+            double v;
+            if (i < m) {
+                v = sigma2 * (acc[a][b].value() + G[(int64_t)i * ldg + j]);
+                if (i == j) v += tau;
+            } else {
+                v = (i == j) ? 1.0 : 0.0;
+            }
+            S[(int64_t)i * lds + j] = v;
+            S[(int64_t)j * lds + i] = v;
+        }
+}
+
+int launch_cov_assemble(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, int d, const double *coef, int hcols,
+                        const double *G, int64_t ldg, int m, double sigma2, double tau, double *S, int64_t lds) {
+    if (m_pad % 64 || m > m_pad) {
+        set_error("cov_assemble: m_pad must be a multiple of 64 and >= m");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int nb = m_pad / 64;
+    const dim3 grid((unsigned)(nb * (nb + 1) / 2));
+    const size_t lds_bytes = (size_t)2 * (d < kCorrDC ? d : kCorrDC) * 64 * sizeof(double);
+    if (hcols == 1) {
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_cov_assemble<C_, true>), grid, dim3(256), lds_bytes, s, xqT, ldq, d, coef,
+                                                   hcols, G, ldg, m, sigma2, tau, S, lds));
+    } else {
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_cov_assemble<C_, false>), grid, dim3(256), lds_bytes, s, xqT, ldq, d, coef,
+                                                   hcols, G, ldg, m, sigma2, tau, S, lds));
+    }
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
 }  // namespace egx

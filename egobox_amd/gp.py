@@ -349,6 +349,39 @@ class GpHandle:
         L.check(self._lib.egx_gp_predict_valvar_gradients(self._h, L.dptr(x), x.shape[0], L.dptr(gy), L.dptr(gv)))
         return gy, gv
 
+    # -- posterior covariance and trajectories (algorithm.rs:310-326, 383-395, 1153-1193)
+    def predict_covariance(self, x):
+        """(m, m) posterior covariance sigma2 (K(x, x) - rt^T rt + u^T u) in original units (egx_gp_predict_covariance)."""
+        x = self._q(x)
+        m = x.shape[0]
+        out = np.empty((m, m))
+        L.check(self._lib.egx_gp_predict_covariance(self._h, L.dptr(x), m, L.dptr(out)))
+        return out
+
+    def sample(self, x, n_traj, method="psd", seed=None, z=None, return_tau=False):
+        """(m, n_traj) trajectories predict(x) 1^T + F Z (egx_gp_sample).  method "cholesky": F = chol(Sigma), LinalgError when
+        Sigma is not positive definite; "psd": F = chol(Sigma + tau I), tau from max(1e-9, 1e-12 max diag) up by tens.
+        z: (m, n_traj) normals of the caller, else the library's stream for `seed` (None: a random seed).
+        return_tau: also return the tau used."""
+        x = self._q(x)
+        m, n_traj = x.shape[0], int(n_traj)
+        meth = {"cholesky": L.SAMPLE_CHOLESKY, "psd": L.SAMPLE_PSD}.get(method, method)
+        if not isinstance(meth, int):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"unknown sampling method {method!r}")
+        if seed is None:
+            seed = int(np.random.default_rng().integers(0, 2 ** 63))
+        zp = None
+        if z is not None:
+            z = L.as_f64(z, 2)
+            if z.shape != (m, n_traj):
+                raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"z must be ({m}, {n_traj}), got {z.shape}")
+            zp = L.dptr(z)
+        out = np.empty((m, n_traj))
+        tau = C.c_double()
+        L.check(self._lib.egx_gp_sample(self._h, L.dptr(x), m, n_traj, int(meth), int(seed) & (2 ** 64 - 1), zp, L.dptr(out),
+                                        C.byref(tau)))
+        return (out, tau.value) if return_tau else out
+
     # -- state
     def inner(self, with_chol=False):
         n, d, p, h = self.n, self.d, self.p, self.h
@@ -776,6 +809,27 @@ class GaussianProcess:
     def predict_valvar_gradients(self, x):
         """algorithm.rs:711-727 -> ((m, nx), (m, nx))."""
         return self._h.predict_valvar_gradients(x)
+
+    def predict_covariance(self, x):
+        """_compute_covariance (algorithm.rs:310-326): (m, m) posterior covariance at x, original units."""
+        return self._h.predict_covariance(x)
+
+    def sample_chol(self, x, n_traj, seed=None):
+        """algorithm.rs:383: (m, n_traj) trajectories mean(x) + L Z, L the plain Cholesky factor of the posterior covariance;
+        LinalgError when it is not positive definite (the reference panics)."""
+        return self._h.sample(x, n_traj, "cholesky", seed)
+
+    def sample_eig(self, x, n_traj, seed=None):
+        """algorithm.rs:388-390, with a DELIBERATE DEVIATION: no eigendecomposition.  The reference factors the covariance by
+        eigh and zeroes the eigenvalues below 1e-9 (Sigma_+); here the factor is the Cholesky factor of Sigma + tau I, tau =
+        max(1e-9, 1e-12 max_i Sigma_ii), times 10 after each failed factorisation (at most six times, then LinalgError).  The
+        covariance sampled differs from Sigma_+ by at most tau + max(1e-9, |lambda_min(Sigma)|) in 2-norm.  The draws are
+        not the reference's either way (its stream is Rust's ndarray-rand)."""
+        return self._h.sample(x, n_traj, "psd", seed)
+
+    def sample(self, x, n_traj, seed=None):
+        """algorithm.rs:393-395: alias of `sample_eig` (see there for the deviation)."""
+        return self.sample_eig(x, n_traj, seed)
 
     def inner_params(self, with_chol=False):
         if self._inner is None or (with_chol and "r_chol" not in self._inner):

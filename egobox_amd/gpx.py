@@ -134,6 +134,13 @@ class Gpx:
         """python/src/gp_mix.rs `predict_var_gradients`: (m, nx) derivatives of the variance."""
         return self._experts[0].predict_var_gradients(x)
 
+    def sample(self, x, n_traj):
+        """python/src/gp_mix.rs `sample` -> GpMixture::sample (crates/moe/src/algorithm.rs:550-558): (m, n_traj) trajectories of
+        the single expert (GaussianProcess.sample); more than one cluster is the reference's SampleError."""
+        if len(self._experts) != 1:
+            raise G.L.SampleError(G.L.ERR_INVALID_VALUE, f"Can not sample when several clusters {len(self._experts)}")
+        return self._experts[0].sample(x, n_traj)
+
     def thetas(self):
         return np.stack([e.theta() for e in self._experts])
 

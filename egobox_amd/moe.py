@@ -262,6 +262,16 @@ class GpMixture:
     def predict(self, x):
         return self.predict_valvar(x, True, False)[0]
 
+    def sample(self, x, n_traj):
+        """GpMixture::sample (crates/moe/src/algorithm.rs:550-558): (m, n_traj) trajectories of the single expert
+        (GaussianProcess.sample); a mixture of several clusters raises the reference's SampleError."""
+        if self.gmx.n_clusters != 1:
+            from ._lib import ERR_INVALID_VALUE, SampleError
+            raise SampleError(ERR_INVALID_VALUE, f"Can not sample when several clusters {self.gmx.n_clusters}")
+        if self.experts[0] is None:
+            raise ValueError("the single expert lives on another rank")
+        return self.experts[0].sample(x, n_traj)
+
     def predict_var(self, x):
         return self.predict_valvar(x, False, True)[1]
 

@@ -299,6 +299,32 @@ int32_t egx_gp_predict_var_gradients(egx_gp *gp, const double *xq, int64_t m, do
 int32_t egx_gp_predict_valvar_gradients(egx_gp *gp, const double *xq, int64_t m, double *grad_y /*m*d*/,
                                         double *grad_var /*m*d*/);
 
+/* ---- posterior covariance and trajectories (GpSurrogateExt::sample, crates/moe/src/surrogates.rs:66-81;
+ * GaussianProcess::_compute_covariance algorithm.rs:310-326, sample_chol / sample_eig / sample :383-395, helper
+ * sample :1153-1193).  xq is (m x d) in ORIGINAL units; every array is host memory, row-major.
+ *
+ * egx_gp_predict_covariance: cov (m x m) = sigma2 (K(xq, xq) - rt^T rt + u^T u), K without nugget (diagonal 1), rt / u those
+ * of predict_var: the diagonal is predict_var before its clamp at 0.  Exactly symmetric.
+ *
+ * egx_gp_sample: traj (m x n_traj) = predict(xq) 1^T + F Z, F the lower Cholesky factor of
+ *   EGX_SAMPLE_CHOLESKY  cov itself (sample_chol); EGX_ERR_LINALG, naming the 1-based pivot, when it is not positive definite
+ *   EGX_SAMPLE_PSD       cov + tau I (sample / sample_eig), tau0 = max(1e-9, 1e-12 max_i cov_ii), times 10 after every failed
+ *                        factorisation, at most six retries, then EGX_ERR_LINALG.
+ * DEVIATION from the reference's sample_eig: no eigendecomposition.  The reference samples with the eigenvalues below 1e-9
+ * clipped to 0 (Sigma_+); the covariance sampled here, F F^T = Sigma + tau I, differs from Sigma_+ by at most
+ * tau + max(1e-9, |lambda_min(Sigma)|) in 2-norm.  The tau used is written to *tau_out (0 for EGX_SAMPLE_CHOLESKY; may be NULL).
+ * z: (m x n_traj) normals supplied by the caller (with z = I, n_traj = m, traj - predict(xq) is F), or NULL: the library's
+ * stream, egx_random_normals(seed).  m = 0 or n_traj = 0 succeeds and does nothing; serialised per handle like predict*. */
+typedef enum { EGX_SAMPLE_CHOLESKY = 0, EGX_SAMPLE_PSD = 1 } egx_sample_method;
+int32_t egx_gp_predict_covariance(egx_gp *gp, const double *xq, int64_t m, double *cov /*m*m*/);
+int32_t egx_gp_sample(egx_gp *gp, const double *xq, int64_t m, int64_t n_traj, int32_t method, uint64_t seed,
+                      const double *z /*m*n_traj or NULL*/, double *traj /*m*n_traj*/, double *tau_out /*1 or NULL*/);
+/* The normals egx_gp_sample draws for `seed` when z is NULL, (m x n_traj), computed on `device` (-1: the current one):
+ * Philox4x64-10 with numpy.random.Philox's constants, key (seed, 0); Z[i, j] is normal (i mod 4) of the block with counter
+ * (i / 4, j, 0, 0), by Box-Muller over u = ((w >> 11) + 0.5) 2^-53 -- it depends on (seed, i, j) only
+ * (egobox_amd/csrc/philox.h). */
+int32_t egx_random_normals(int32_t device, uint64_t seed, int64_t m, int64_t n_traj, double *z /*m*n_traj*/);
+
 /* ---- fitted state download (GpInnerParams algorithm.rs:47-60 + accessors
  * theta()/variance()/likelihood() :413-431), for serde parity.  Any pointer may
  * be NULL (skipped).  r_chol is (n x n) lower with zero upper triangle;

@@ -151,6 +151,23 @@ class GaussianProcess {
         check(egx_gp_predict_valvar_gradients(h_.get(), x, m, gy.data(), gv.data()));
         return {std::move(gy), std::move(gv)};
     }
+    // _compute_covariance, algorithm.rs:310-326 -> (m x m) row-major
+    std::vector<double> predict_covariance(const double *x, int64_t m) const {
+        std::vector<double> c((size_t)(m * m));
+        check(egx_gp_predict_covariance(h_.get(), x, m, c.data()));
+        return c;
+    }
+    // sample (EGX_SAMPLE_PSD: Cholesky of Sigma + tau I, the deviation from sample_eig documented in egx_gp.h) / sample_chol
+    // (EGX_SAMPLE_CHOLESKY), algorithm.rs:383-395 -> (m x n_traj) row-major; z (m x n_traj) or nullptr: the stream of `seed`
+    std::vector<double> sample(const double *x, int64_t m, int64_t n_traj, egx_sample_method method = EGX_SAMPLE_PSD,
+                               uint64_t seed = 0, const double *z = nullptr, double *tau = nullptr) const {
+        std::vector<double> t((size_t)(m * n_traj));
+        check(egx_gp_sample(h_.get(), x, m, n_traj, method, seed, z, t.data(), tau));
+        return t;
+    }
+    std::vector<double> sample_chol(const double *x, int64_t m, int64_t n_traj, uint64_t seed = 0) const {
+        return sample(x, m, n_traj, EGX_SAMPLE_CHOLESKY, seed);
+    }
     // reduced likelihood at k candidate thetas (k x theta_len row-major) -> (values, status per candidate): the evaluations
     // the reference's multistart closures make (algorithm.rs:880-897, 928-945), factored in lock-step groups on the GPU
     std::pair<std::vector<double>, std::vector<int32_t>> likelihood_batch(const double *thetas, int64_t k, int64_t theta_len) {
