@@ -341,11 +341,7 @@ int likelihood_grad_batch_core(egx_gp *gp, const double *thetas, int64_t k, int6
                     sl.pre[j] = sl.hcols == 1 ? 1 : 0;
                     for (double cj : sl.coefs[j])
                         if (!(cj > 0.0) || !std::isfinite(cj)) sl.pre[j] = 0;
-                    if (!res.rho_on_device) {  // host GLS: rho goes back (zero padded)
-                        std::memset(w.h_vec, 0, sizeof(double) * gp->n_pad);
-                        std::memcpy(w.h_vec, res.rho.data(), sizeof(double) * gp->n);
-                        EGX_HIP_CHECK(hipMemcpyAsync(w.d_rhs, w.h_vec, sizeof(double) * gp->n_pad, hipMemcpyHostToDevice, st));
-                    }
+                    EGX_RC(upload_rho(gp, w, res, st));
                 }
                 // maximal runs of consecutive candidates with a gradient (and the same form of the trace kernel): each run is one
                 // lock-step launch sequence

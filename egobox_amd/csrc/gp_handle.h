@@ -89,11 +89,10 @@ struct Workspace {
     double *h_rows = nullptr;  // pinned: q x n_pad solved RHS rows (ft^T, yt^T)
     double *h_diag = nullptr;  // pinned: n
     double *h_vec = nullptr;   // pinned: n_pad
-    bool block_inv_ready = false;  // dW holds the inverse blocks of the factor now in M (launched ahead of the host's GLS: finalize)
     int *h_info = nullptr;     // pinned: [0] the factorisation's info, [1..8] the abort word + diagnostics of its chain launches
     // theta-gradient scratch (lazy, gp_fit.hip): the workgroups' partial sums, the reduced sums, their pinned copy
     double *d_gpart = nullptr, *d_gout = nullptr, *h_gout = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     GemmTrace trace;
 };
 
@@ -223,7 +222,8 @@ int finish_eval(egx_gp *gp, Workspace &w, EvalResult &out, int keep);  // 0 scal
 void record_timings(egx_gp *gp, Workspace &w, double host_ms, double solve_ms);
 bool has_nan(const double *theta, int64_t len);
 int eval_one(egx_gp *gp, int widx, const double *theta, int64_t theta_len, EvalResult &res, bool keep);
-int backward_solve(egx_gp *gp, Workspace &w);
+// the host GLS's rho into w.d_rhs, zero padded, on stream st (the device GLS leaves it there itself)
+int upload_rho(egx_gp *gp, Workspace &w, const EvalResult &res, hipStream_t st);
 int do_finalize(egx_gp *gp, const double *theta, int64_t theta_len);
 // Where a batch takes its candidates from: the sequence 0 .. k-1 (nullptr), a rank's static shard or the node-wide
 // counter of a dynamic sweep (sweep.hip).  pull() hands out up to `want` candidate indices, 0 = exhausted.

@@ -365,7 +365,6 @@ static void pool_give(egx_gp *gp) {
         w.eval_stream = w.stream;
         w.trace.used = 0;
         w.gls_enqueued = false;
-        w.block_inv_ready = false;
         w.retried = false;
         w.retry_W = nullptr;
         w.sync_lead = nullptr;
@@ -970,136 +969,124 @@ int eval_one(egx_gp *gp, int widx, const double *theta, int64_t theta_len, EvalR
     return EGX_SUCCESS;
 }
 
-// w.d_vec <- C^-T w.d_rhs  (block inverses are rebuilt: the factor in w.M has just changed)
-static int ensure_block_inverse_buffer(egx_gp *gp, Workspace &w) {
-    if (!w.dW) EGX_HIP_CHECK(dev_malloc(&w.dW, sizeof(double) * block_inverse_doubles(gp->n_pad)));
-    return EGX_SUCCESS;
-}
-// The inverse blocks only need the factor, not the host's half of the likelihood: a fit launches them right behind the
-// evaluation, so that they run while the host waits for the read-back and does its GLS (84 us off a fit's critical path)
-static int prelaunch_block_inverse(egx_gp *gp, Workspace &w, hipStream_t st) {
-    EGX_RC(ensure_block_inverse_buffer(gp, w));
-    EGX_RC(launch_block_inverse(st, w.M, gp->ld, gp->n_pad, w.dinv, w.dW));
-    w.block_inv_ready = true;
-    return EGX_SUCCESS;
-}
-int backward_solve(egx_gp *gp, Workspace &w) {
-    if (!w.block_inv_ready) EGX_RC(prelaunch_block_inverse(gp, w, w.stream));
-    w.block_inv_ready = false;
-    EGX_RC(launch_trsv_t(w.stream, w.M, gp->ld, gp->n_pad, w.dW, w.d_rhs, w.d_vec));
-    return EGX_SUCCESS;
-}
+// the longest run of models that one call evaluates in lock-step (multi_run_len)
+constexpr int kMaxRun = 12;
+static_assert(kMaxRun <= SolveBatchPtrs::kMax && kMaxRun <= EvalBatchPtrs::kMax, "a run must fit one batched launch");
 
-// second half of a fit at fixed theta, behind the evaluation that was enqueued on workspace 0, in two steps so that several
-// models' tails overlap (egx_gp_finalize_multi): (1) the host half of the likelihood, then gamma = C^-T rho and the fitted
-// state's device copies ENQUEUED on the model's own stream; (2) wait for them, take over the fitted state
-struct FinalizeTail {
+// The host halves (finish_eval) of a run of `len` models evaluated by enqueue_eval_members.  On the host-GLS route (the
+// log-determinant over the diagonal, GLS: ~0.1 ms per model at n = 8192, no HIP launches) they run side by side on host threads;
+// the device-GLS route (p > 1 trend columns) issues launches: one after the other.
+struct HostHalf {
     EvalResult res;
+    int rc = EGX_SUCCESS;
+    std::string err;  // (the error text is per thread)
     std::chrono::steady_clock::time_point t0, t1;
 };
-static int finalize_tail_enqueue(egx_gp *gp, const std::vector<double> &coef, int hcols, FinalizeTail &ft) {
-    Workspace &w = gp->ws[0];
-    EvalResult &res = ft.res;
-    ft.t0 = std::chrono::steady_clock::now();
-    EGX_RC(finish_eval(gp, w, res, 1));
-    ft.t1 = std::chrono::steady_clock::now();
-    if (res.status == EGX_STATUS_NOT_POSITIVE_DEFINITE) {
+static void host_halves(egx_gp *const *gps, int len, int keep, HostHalf *hh) {
+    auto run = [&](int j) {
+        hh[j].t0 = std::chrono::steady_clock::now();
+        hh[j].rc = finish_eval(gps[j], gps[j]->ws[0], hh[j].res, keep);
+        hh[j].t1 = std::chrono::steady_clock::now();
+        if (hh[j].rc != EGX_SUCCESS) hh[j].err = last_error_string();
+    };
+    if (len == 1 || gps[0]->gls_device) {
+        for (int j = 0; j < len; j++) run(j);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int j = 1; j < len; j++)
+        pool.emplace_back([&, j] {
+            if (hipSetDevice(gps[j]->device) == hipSuccess) run(j);
+            else hh[j].rc = EGX_ERR_HIP, hh[j].err = "hipSetDevice failed in a host-half worker";
+        });
+    run(0);
+    for (auto &t : pool) t.join();
+}
+
+// Whatever way a run's evaluation is left, no work stays in flight on the lead's stream that writes into the members' pinned
+// buffers, and no member's eval_stream points at a stream of a handle that may be destroyed first.  (synced: the run ended
+// in a synchronisation of that stream: no second one, 30 us of a fit's host time)
+struct RunGuard {
+    egx_gp *const *gps;
+    int len;
+    bool synced = false;
+    ~RunGuard() {
+        if (!synced) {
+            (void)hipStreamSynchronize(gps[0]->ws[0].stream);
+            (void)hipGetLastError();
+        }
+        for (int j = 0; j < len; j++) gps[j]->ws[0].eval_stream = gps[j]->ws[0].stream;
+    }
+};
+
+// the error of a fit whose host half ended in `status`
+static int status_error(int status, const Workspace &w) {
+    if (status == EGX_STATUS_OK) return EGX_SUCCESS;
+    if (status == EGX_STATUS_NOT_POSITIVE_DEFINITE) {
         set_error("LinalgError: matrix is not positive definite (pivot " + std::to_string(*w.h_info) + ")");
         return EGX_ERR_LINALG;
     }
-    if (res.status == EGX_STATUS_ILL_CONDITIONED_F) {
-        set_error("LikelihoodComputation computation error: F is too ill conditioned. Poor combination of "
-                  "regression model and observations.");
-        return EGX_ERR_LIKELIHOOD;
-    }
-    if (res.status == EGX_STATUS_ILL_CONDITIONED_FT) {
-        set_error("LikelihoodComputation computation error: ft is too ill conditioned, try another theta again");
-        return EGX_ERR_LIKELIHOOD;
-    }
-    // gamma = C^-T rho   (algorithm.rs:1034)
-    const int n = gp->n, n_pad = gp->n_pad;
-    if (!res.rho_on_device) {
-        std::memset(w.h_vec, 0, sizeof(double) * n_pad);
-        std::memcpy(w.h_vec, res.rho.data(), sizeof(double) * n);
-        EGX_HIP_CHECK(hipMemcpyAsync(w.d_rhs, w.h_vec, sizeof(double) * n_pad, hipMemcpyHostToDevice, w.stream));
-    }
-    EGX_HIP_CHECK(hipEventRecord(w.ev[4], w.stream));
-    EGX_RC(backward_solve(gp, w));
-    EGX_HIP_CHECK(hipMemcpyAsync(gp->d_gamma, w.d_vec, sizeof(double) * n_pad, hipMemcpyDeviceToDevice, w.stream));
-    EGX_HIP_CHECK(hipMemcpyAsync(w.h_vec, w.d_vec, sizeof(double) * n_pad, hipMemcpyDeviceToHost, w.stream));
-    EGX_HIP_CHECK(hipMemcpyAsync(gp->d_fit_coef, w.d_coef, sizeof(double) * coef.size(), hipMemcpyDeviceToDevice,
-                                 w.stream));
-    if (hcols == 1) EGX_RC(launch_scale_rows(w.stream, gp->d_xT, gp->n_pad, gp->d, gp->d_fit_coef, dev_xs_fit(gp)));
+    set_error(status == EGX_STATUS_ILL_CONDITIONED_F
+                  ? "LikelihoodComputation computation error: F is too ill conditioned. Poor combination of regression model and "
+                    "observations."
+                  : "LikelihoodComputation computation error: ft is too ill conditioned, try another theta again");
+    return EGX_ERR_LIKELIHOOD;
+}
+
+int upload_rho(egx_gp *gp, Workspace &w, const EvalResult &res, hipStream_t st) {
+    if (res.rho_on_device) return EGX_SUCCESS;
+    std::memset(w.h_vec, 0, sizeof(double) * gp->n_pad);
+    std::memcpy(w.h_vec, res.rho.data(), sizeof(double) * gp->n);
+    EGX_HIP_CHECK(hipMemcpyAsync(w.d_rhs, w.h_vec, sizeof(double) * gp->n_pad, hipMemcpyHostToDevice, st));
     return EGX_SUCCESS;
 }
-// ... of the members of a group that were evaluated in lock-step (egx_gp_finalize_multi): the host halves one after the other,
-// then ONE launch sequence for all back-substitutions (launch_trsv_t_batch: 64 launches instead of 64 per model -- the
-// command processor serialises such ~5 us launches however many streams or host threads issue them: eight n = 8192 experts
-// 36.9 -> X ms, profiles/r05_expert_group_*.txt) on the stream the evaluation ran on, and the fitted state's device copies.
-// rcs[j] / errs[j]: per-model outcome of the host half (a model that failed is left out of the launches).
-static int finalize_tails_lockstep(egx_gp *const *gps, int len, const std::vector<double> *coefs, int hcols, FinalizeTail *tails,
-                                   int *rcs, std::string *errs) {
-    hipStream_t st = gps[0]->ws[0].eval_stream;
+
+// A fit at fixed theta of a run of 1 .. kMaxRun models: a lone handle, or members of one group in consecutive slots
+// (egx_gp_finalize_multi).  On the stream of the evaluation (the lead's): the evaluation, then the inverse blocks for gamma's
+// back-substitution (they only need the factors, and run while the host waits for the read-back and does the GLS: 84 us off a
+// fit's critical path); after the host halves ONE back-substitution launch sequence for all models (launch_trsv_t_batch: 64
+// launches instead of 64 per model -- the command processor serialises such ~5 us launches however many streams or host threads
+// issue them) and the fitted state's device copies; one synchronisation, then every model takes over its fitted state.
+// A model that fails leaves the others to finish: first_rc keeps the first error of a model; the return value is an error of
+// what the run's models share.
+static int fit_run(egx_gp *const *gps, int len, const std::vector<double> *coefs, int hcols, const std::vector<double> *thfull,
+                   int &first_rc) {
+    for (int j = 0; j < len; j++) gps[j]->fitted = false;
+    RunGuard guard{gps, len};
+    EGX_RC(enqueue_eval_members(gps, len, coefs, hcols));
+    const egx_gp *lead = gps[0];
+    const hipStream_t st = lead->ws[0].eval_stream;
     SolveBatchPtrs bp;
-    int live[SolveBatchPtrs::kMax], nlive = 0;
-    // the host halves (log-determinant over the diagonal, GLS: ~0.1 ms per model at n = 8192, no HIP launches on the host-GLS
-    // route) side by side on host threads; the device-GLS route (p > 1 trend columns) issues launches: one after the other
-    std::vector<int> frc((size_t)len, EGX_SUCCESS);
-    std::vector<std::string> ferr((size_t)len);
-    auto host_half = [&](int j) {
-        FinalizeTail &ft = tails[j];
-        ft.t0 = std::chrono::steady_clock::now();
-        frc[(size_t)j] = finish_eval(gps[j], gps[j]->ws[0], ft.res, 1);
-        ft.t1 = std::chrono::steady_clock::now();
-        if (frc[(size_t)j] != EGX_SUCCESS) ferr[(size_t)j] = last_error_string();  // (the error text is per thread)
-    };
-    if (!gps[0]->gls_device) {
-        std::vector<std::thread> pool;
-        for (int j = 1; j < len; j++)
-            pool.emplace_back([&, j] {
-                if (hipSetDevice(gps[j]->device) != hipSuccess) {
-                    frc[(size_t)j] = EGX_ERR_HIP;
-                    ferr[(size_t)j] = "hipSetDevice failed in a finalize worker";
-                    return;
-                }
-                host_half(j);
-            });
-        host_half(0);
-        for (auto &t : pool) t.join();
-    } else {
-        for (int j = 0; j < len; j++) host_half(j);
+    for (int j = 0; j < len; j++) {
+        Workspace &w = gps[j]->ws[0];
+        if (!w.dW) EGX_HIP_CHECK(dev_malloc(&w.dW, sizeof(double) * block_inverse_doubles(gps[j]->n_pad)));
+        bp.M[j] = w.M, bp.dinv[j] = w.dinv, bp.dW[j] = w.dW, bp.rhs[j] = w.d_rhs, bp.vec[j] = w.d_vec;
     }
+    if (len == 1) EGX_RC(launch_block_inverse(st, bp.M[0], lead->ld, lead->n_pad, bp.dinv[0], bp.dW[0]));
+    else EGX_RC(launch_block_inverse_batch(st, bp, len, lead->ld, lead->n_pad));
+    std::vector<HostHalf> hh((size_t)len);
+    host_halves(gps, len, 1, hh.data());
+    int live[kMaxRun], nlive = 0;
     for (int j = 0; j < len; j++) {
         egx_gp *gp = gps[j];
         Workspace &w = gp->ws[0];
-        FinalizeTail &ft = tails[j];
-        int rc = frc[(size_t)j];
-        if (rc != EGX_SUCCESS) set_error(ferr[(size_t)j]);
-        if (rc == EGX_SUCCESS && ft.res.status != EGX_STATUS_OK) {
-            rc = ft.res.status == EGX_STATUS_NOT_POSITIVE_DEFINITE ? EGX_ERR_LINALG : EGX_ERR_LIKELIHOOD;
-            set_error(ft.res.status == EGX_STATUS_NOT_POSITIVE_DEFINITE
-                          ? "LinalgError: matrix is not positive definite (pivot " + std::to_string(*w.h_info) + ")"
-                          : ft.res.status == EGX_STATUS_ILL_CONDITIONED_F
-                                ? std::string("LikelihoodComputation computation error: F is too ill conditioned. Poor combination of "
-                                              "regression model and observations.")
-                                : std::string("LikelihoodComputation computation error: ft is too ill conditioned, try another theta again"));
-        }
-        rcs[j] = rc;
+        if (hh[j].rc != EGX_SUCCESS) set_error(hh[j].err);
+        const int rc = hh[j].rc != EGX_SUCCESS ? hh[j].rc : status_error(hh[j].res.status, w);
         if (rc != EGX_SUCCESS) {
-            errs[j] = last_error_string();
+            if (first_rc == EGX_SUCCESS) first_rc = rc;
             continue;
         }
-        if (!ft.res.rho_on_device) {
-            std::memset(w.h_vec, 0, sizeof(double) * gp->n_pad);
-            std::memcpy(w.h_vec, ft.res.rho.data(), sizeof(double) * gp->n);
-            EGX_HIP_CHECK(hipMemcpyAsync(w.d_rhs, w.h_vec, sizeof(double) * gp->n_pad, hipMemcpyHostToDevice, st));
-        }
+        EGX_RC(upload_rho(gp, w, hh[j].res, st));
+        // the factor came from finish_eval's separate-launch retry (synchronised there): the inverse blocks launched above are
+        // those of the aborted chain launch's factor
+        if (w.retried) EGX_RC(launch_block_inverse(st, w.M, gp->ld, gp->n_pad, w.dinv, w.dW));
         bp.M[nlive] = w.M, bp.dinv[nlive] = w.dinv, bp.dW[nlive] = w.dW, bp.rhs[nlive] = w.d_rhs, bp.vec[nlive] = w.d_vec;
         live[nlive++] = j;
     }
     if (nlive == 0) return EGX_SUCCESS;
-    egx_gp *g0 = gps[live[0]];
-    EGX_RC(launch_trsv_t_batch(st, bp, nlive, g0->ld, g0->n_pad));  // gamma = C^-T rho (algorithm.rs:1034); inverse blocks: multi_eval
+    // gamma = C^-T rho   (algorithm.rs:1034)
+    if (len == 1) EGX_RC(launch_trsv_t(st, bp.M[0], lead->ld, lead->n_pad, bp.dW[0], bp.rhs[0], bp.vec[0]));
+    else EGX_RC(launch_trsv_t_batch(st, bp, nlive, lead->ld, lead->n_pad));
     for (int q = 0; q < nlive; q++) {
         egx_gp *gp = gps[live[q]];
         Workspace &w = gp->ws[0];
@@ -1110,64 +1097,60 @@ static int finalize_tails_lockstep(egx_gp *const *gps, int len, const std::vecto
         if (hcols == 1) EGX_RC(launch_scale_rows(st, gp->d_xT, gp->n_pad, gp->d, gp->d_fit_coef, dev_xs_fit(gp)));
     }
     EGX_HIP_CHECK(hipStreamSynchronize(st));
-    return EGX_SUCCESS;
-}
-static int finalize_tail_complete(egx_gp *gp, const std::vector<double> &coef, int hcols, const std::vector<double> &thfull,
-                                  FinalizeTail &ft) {
-    Workspace &w = gp->ws[0];
-    EvalResult &res = ft.res;
-    EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
-    auto t2 = std::chrono::steady_clock::now();
-    // The one-launch back-substitution leaves NaN in gamma when one of its bounded waits ran out (kernels_chol.hip): like an
-    // aborted chain launch -- not a numerical event, the reference knows no such failure -- it is run ONCE more, launch per
-    // block, from the right-hand side it left untouched (egx_chain_stats counts it; "pipe_retry" = 0: the error at once)
-    auto finite = [&]() {
-        for (int i = 0; i < gp->n; i++)
-            if (!std::isfinite(w.h_vec[i])) return false;
-        return true;
-    };
-    if (!finite()) {
-        g_chain_aborts++;
-        bool ok = false;
-        if (g_pipe_retry.load() != 0 && w.dW != nullptr) {
-            g_chain_retries++;
-            EGX_RC(launch_trsv_t(w.stream, w.M, gp->ld, gp->n_pad, w.dW, w.d_rhs, w.d_vec, true));
-            EGX_HIP_CHECK(hipMemcpyAsync(gp->d_gamma, w.d_vec, sizeof(double) * gp->n_pad, hipMemcpyDeviceToDevice, w.stream));
-            EGX_HIP_CHECK(hipMemcpyAsync(w.h_vec, w.d_vec, sizeof(double) * gp->n_pad, hipMemcpyDeviceToHost, w.stream));
-            EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
-            ok = finite();
+    guard.synced = true;
+    const auto t2 = std::chrono::steady_clock::now();
+    for (int q = 0; q < nlive; q++) {
+        const int j = live[q];
+        egx_gp *gp = gps[j];
+        Workspace &w = gp->ws[0];
+        // The one-launch back-substitution leaves NaN in gamma when one of its bounded waits ran out (kernels_chol.hip): like an
+        // aborted chain launch -- not a numerical event, the reference knows no such failure -- it is run ONCE more, launch per
+        // block, from the right-hand side it left untouched (egx_chain_stats counts it; "pipe_retry" = 0: the error at once)
+        auto finite = [&]() {
+            for (int i = 0; i < gp->n; i++)
+                if (!std::isfinite(w.h_vec[i])) return false;
+            return true;
+        };
+        if (!finite()) {
+            g_chain_aborts++;
+            bool ok = false;
+            if (g_pipe_retry.load() != 0) {
+                g_chain_retries++;
+                EGX_RC(launch_trsv_t(w.stream, w.M, gp->ld, gp->n_pad, w.dW, w.d_rhs, w.d_vec, true));
+                EGX_HIP_CHECK(hipMemcpyAsync(gp->d_gamma, w.d_vec, sizeof(double) * gp->n_pad, hipMemcpyDeviceToDevice, w.stream));
+                EGX_HIP_CHECK(hipMemcpyAsync(w.h_vec, w.d_vec, sizeof(double) * gp->n_pad, hipMemcpyDeviceToHost, w.stream));
+                EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
+                ok = finite();
+            }
+            if (!ok) {
+                set_error("back-substitution gamma = C^-T rho: non-finite result (the launch ran into its wait bound, EGX_PIPE_TIMEOUT_MS, "
+                          "or rho is not finite)");
+                if (first_rc == EGX_SUCCESS) first_rc = EGX_ERR_HIP;
+                continue;
+            }
         }
-        if (!ok) {
-            set_error("back-substitution gamma = C^-T rho: non-finite result (the launch ran into its wait bound, EGX_PIPE_TIMEOUT_MS, "
-                      "or rho is not finite)");
-            return EGX_ERR_HIP;
+        const EvalResult &res = hh[j].res;
+        gp->gamma.assign(w.h_vec, w.h_vec + gp->n);
+        gp->theta = thfull[j];
+        gp->likelihood = res.lkh;
+        gp->sigma2 = res.sigma2n * gp->y_std * gp->y_std;  // algorithm.rs:1048
+        gp->beta = res.beta;
+        gp->ft = res.ft;
+        gp->ft_qr_r = res.ft_qr_r;
+        gp->fit_coef = coefs[j];
+        gp->fit_hcols = hcols;
+        gp->fitted = true;
+        gp->fit_epoch++;
+        gp->small_var_calls = 0;
+        if (w.eval_stream == w.stream) {  // (a model that rode in another model's launch sequence has no timings of its own)
+            float gpu = 0;
+            hipEventElapsedTime(&gpu, w.ev[0], w.ev[3]);
+            double host_ms = std::chrono::duration<double, std::milli>(hh[j].t1 - hh[j].t0).count() - gpu;
+            if (host_ms < 0) host_ms = 0;
+            record_timings(gp, w, host_ms, std::chrono::duration<double, std::milli>(t2 - hh[j].t1).count());
         }
     }
-    gp->gamma.assign(w.h_vec, w.h_vec + gp->n);
-    gp->theta = thfull;
-    gp->likelihood = res.lkh;
-    gp->sigma2 = res.sigma2n * gp->y_std * gp->y_std;  // algorithm.rs:1048
-    gp->beta = res.beta;
-    gp->ft = res.ft;
-    gp->ft_qr_r = res.ft_qr_r;
-    gp->fit_coef = coef;
-    gp->fit_hcols = hcols;
-    gp->fitted = true;
-    gp->fit_epoch++;
-    gp->small_var_calls = 0;
-    if (w.eval_stream == w.stream) {  // (a model that rode in another model's launch sequence has no timings of its own)
-        float gpu = 0;
-        hipEventElapsedTime(&gpu, w.ev[0], w.ev[3]);
-        double host_ms = std::chrono::duration<double, std::milli>(ft.t1 - ft.t0).count() - gpu;
-        if (host_ms < 0) host_ms = 0;
-        record_timings(gp, w, host_ms, std::chrono::duration<double, std::milli>(t2 - ft.t1).count());
-    }
     return EGX_SUCCESS;
-}
-static int finalize_tail(egx_gp *gp, const std::vector<double> &coef, int hcols, const std::vector<double> &thfull) {
-    FinalizeTail ft;
-    EGX_RC(finalize_tail_enqueue(gp, coef, hcols, ft));
-    return finalize_tail_complete(gp, coef, hcols, thfull, ft);
 }
 int do_finalize(egx_gp *gp, const double *theta, int64_t theta_len) {
     std::vector<double> coef, thfull;
@@ -1177,10 +1160,9 @@ int do_finalize(egx_gp *gp, const double *theta, int64_t theta_len) {
         set_error("theta contains NaN");
         return EGX_ERR_INVALID_VALUE;
     }
-    gp->fitted = false;
-    EGX_RC(enqueue_eval(gp, gp->ws[0], coef, hcols));
-    EGX_RC(prelaunch_block_inverse(gp, gp->ws[0], gp->ws[0].stream));
-    return finalize_tail(gp, coef, hcols, thfull);
+    int rc = EGX_SUCCESS;
+    EGX_RC(fit_run(&gp, 1, &coef, hcols, &thfull, rc));
+    return rc;
 }
 // Candidates pipelined over the handle's workspaces (caller holds gp->mu exclusively and has set the device).
 // The workspaces form SLOTS of gp->lockstep consecutive ones; the candidates of a slot are factored in lock-step by one
@@ -1836,7 +1818,7 @@ int32_t egx_gp_create_group(const egx_gp_config *cfg_in, const double *x, const 
 // same arithmetic alone and in a batch)
 static int multi_run_len(egx_gp *const *gps, int k, int i) {
     if (!gps[i]->group) return 1;
-    int cap = 12;
+    int cap = kMaxRun;
     if (gps[i]->sched.whole) {  // (every diagonal block of a whole-factorisation launch has a workgroup of its own)
         const int np = (gps[i]->n_pad + kNB - 1) / kNB;
         cap = std::max(1, std::min(cap, 128 / np));
@@ -1895,91 +1877,25 @@ static int multi_eval_locked(egx_gp *const *gps, int32_t k, const double *thetas
         }
         // (every member evaluates on its workspace 0 and is UN-FITTED by the call -- also by egx_gp_likelihood_multi, unlike
         //  egx_gp_likelihood, which keeps a fitted handle with spare workspaces fitted: include/egx_gp.h says so)
-        for (int j = 0; j < len; j++) gps[i + j]->fitted = false;
-        // An error between here and the members' host halves must not leave work in flight on the lead's stream that writes into
-        // the other members' pinned buffers, nor their eval_stream pointing at a stream of a handle that may be destroyed first:
-        // drain the lead's stream and hand every member its own stream back before returning.
-        auto bail = [&](int rc_in) {
-            const std::string msg = last_error_string();
-            (void)hipStreamSynchronize(gps[i]->ws[0].stream);
-            for (int j = 0; j < len; j++) gps[i + j]->ws[0].eval_stream = gps[i + j]->ws[0].stream;
-            (void)hipGetLastError();
-            set_error(msg);
-            return rc_in;
-        };
-#define EGX_RC_BAIL(call)                    \
-    do {                                     \
-        const int _rc = (call);              \
-        if (_rc) return bail(_rc);           \
-    } while (0)
-        if (len > 1) EGX_RC_BAIL(enqueue_eval_members(gps + i, len, coefs.data(), hcols));
-        else EGX_RC_BAIL(enqueue_eval(gps[i], gps[i]->ws[0], coefs[0], hcols));
-        if (finalize && len > 1 && len <= SolveBatchPtrs::kMax) {
-            // the members' inverse blocks (for gamma's back-substitution) right behind the evaluation, in lock-step: they only need
-            // the factors and run while the host waits for the read-back and does the models' GLS
-            SolveBatchPtrs ib;
+        if (finalize) {
+            EGX_RC(fit_run(gps + i, len, coefs.data(), hcols, thfull.data(), first_rc));
+        } else {
+            for (int j = 0; j < len; j++) gps[i + j]->fitted = false;
+            RunGuard guard{gps + i, len};
+            EGX_RC(enqueue_eval_members(gps + i, len, coefs.data(), hcols));
+            std::vector<HostHalf> hh((size_t)len);
+            host_halves(gps + i, len, 0, hh.data());
+            // (each host half began by synchronising the lead's stream; only one that failed may have left work on it)
+            guard.synced = std::all_of(hh.begin(), hh.end(), [](const HostHalf &x) { return x.rc == EGX_SUCCESS; });
             for (int j = 0; j < len; j++) {
-                Workspace &w = gps[i + j]->ws[0];
-                EGX_RC_BAIL(ensure_block_inverse_buffer(gps[i + j], w));
-                ib.M[j] = w.M, ib.dinv[j] = w.dinv, ib.dW[j] = w.dW, ib.rhs[j] = w.d_rhs, ib.vec[j] = w.d_vec;
-            }
-            EGX_RC_BAIL(launch_block_inverse_batch(gps[i]->ws[0].eval_stream, ib, len, gps[i]->ld, gps[i]->n_pad));
-        } else if (finalize) {
-            for (int j = 0; j < len; j++) EGX_RC_BAIL(prelaunch_block_inverse(gps[i + j], gps[i + j]->ws[0], gps[i + j]->ws[0].stream));
-        }
-        std::vector<FinalizeTail> tails((size_t)(finalize ? len : 0));
-        std::vector<int> trc((size_t)len, EGX_SUCCESS);
-        std::vector<std::string> terr((size_t)len);
-        if (finalize && len > 1 && len <= SolveBatchPtrs::kMax) {
-            EGX_RC_BAIL(finalize_tails_lockstep(gps + i, len, coefs.data(), hcols, tails.data(), trc.data(), terr.data()));
-#undef EGX_RC_BAIL
-        } else if (finalize) {
-            for (int j = 0; j < len; j++) {
-                trc[(size_t)j] = finalize_tail_enqueue(gps[i + j], coefs[(size_t)j], hcols, tails[(size_t)j]);
-                if (trc[(size_t)j] != EGX_SUCCESS) terr[(size_t)j] = last_error_string();
-            }
-        }
-        // (likelihoods only: the members' host halves side by side as well, see finalize_tails_lockstep)
-        std::vector<EvalResult> lres((size_t)(finalize ? 0 : len));
-        std::vector<int> lrc((size_t)len, EGX_SUCCESS);
-        if (!finalize) {
-            auto host_half = [&](int j) {
-                lrc[(size_t)j] = finish_eval(gps[i + j], gps[i + j]->ws[0], lres[(size_t)j], 0);
-                if (lrc[(size_t)j] != EGX_SUCCESS) terr[(size_t)j] = last_error_string();
-            };
-            if (len > 1 && !gps[i]->gls_device) {
-                std::vector<std::thread> pool;
-                for (int j = 1; j < len; j++)
-                    pool.emplace_back([&, j] {
-                        if (hipSetDevice(gps[i + j]->device) == hipSuccess) host_half(j);
-                        else lrc[(size_t)j] = EGX_ERR_HIP, terr[(size_t)j] = "hipSetDevice failed in a likelihood worker";
-                    });
-                host_half(0);
-                for (auto &t : pool) t.join();
-            } else {
-                for (int j = 0; j < len; j++) host_half(j);
-            }
-        }
-        for (int j = 0; j < len; j++) {
-            egx_gp *g = gps[i + j];
-            int rc;
-            if (finalize) {
-                rc = trc[(size_t)j];
-                if (rc == EGX_SUCCESS) rc = finalize_tail_complete(g, coefs[(size_t)j], hcols, thfull[(size_t)j], tails[(size_t)j]);
-                else {
-                    if (!terr[(size_t)j].empty()) set_error(terr[(size_t)j]);
-                    (void)hipStreamSynchronize(g->ws[0].stream);
+                if (hh[j].rc == EGX_SUCCESS) {
+                    lkh[i + j] = hh[j].res.lkh;
+                    status[i + j] = hh[j].res.status;
+                    continue;
                 }
-            } else {
-                rc = lrc[(size_t)j];
-                if (rc == EGX_SUCCESS) {
-                    if (lkh) lkh[i + j] = lres[(size_t)j].lkh;
-                    if (status) status[i + j] = lres[(size_t)j].status;
-                } else if (!terr[(size_t)j].empty()) {
-                    set_error(terr[(size_t)j]);
-                }
+                set_error(hh[j].err);
+                if (first_rc == EGX_SUCCESS) first_rc = hh[j].rc;  // (the others still finish)
             }
-            if (rc != EGX_SUCCESS && first_rc == EGX_SUCCESS) first_rc = rc;  // (the others still finish: their streams are drained)
         }
         i += len;
     }

@@ -183,6 +183,8 @@ import numpy as np
 import egobox_amd as egx
 x, y = egx.workload.make_training_set(1000, 4, 4)   # (the benchmark's well-conditioned family: chain and separate launches agree to 1e-10)
 th = egx.workload.default_theta(4) * 3.0
+xq = np.random.default_rng(5).random((64, 4))
+fit_of = lambda g: [g.inner()["gamma"].ravel().tolist(), g.predict(xq).tolist(), g.predict_var(xq).tolist()]
 out = {}
 with egx.GpHandle(x, y) as h:
     assert h.schedule()["pipelined_chain"] == 1
@@ -191,6 +193,8 @@ with egx.GpHandle(x, y) as h:
     egx.set_tuning("pipe", 0)
     with egx.GpHandle(x, y) as hs:                     # what the fallback computes: the separate-launch schedule
         sep, st = hs.likelihood(th)
+        hs.finalize(th)
+        sep_fit = fit_of(hs)
     egx.set_tuning("pipe", 1)
     egx.set_tuning("pipe_timeout_ms", 25)
     egx.set_tuning("pipe_stall", 1)                    # test build only: the diagonal role publishes into a scratch word
@@ -202,6 +206,7 @@ with egx.GpHandle(x, y) as h:
     out["fallback"] = [lk, int(st), sep, good, s1["aborted"] - s0["aborted"], s1["retried"] - s0["retried"]]
     h.finalize(th)                                     # ... also for a fit (the factor the predictions use)
     out["fit_after_fallback"] = h.fitted_scalars()[0]
+    out["fit_vs_separate"] = [fit_of(h), sep_fit]
     egx.set_tuning("pipe_retry", 0)                    # fallback disabled: the error, within the bound, not a hang
     t0 = time.perf_counter()
     try:
@@ -255,6 +260,10 @@ def test_a_hand_off_that_never_arrives_is_retried_by_separate_launches_and_an_er
     assert st == 0 and lk == sep and abs(lk - good) <= 1e-8 * abs(good)
     assert aborted == 1 and retried == 1 and out["fallback_seconds"] < 5.0
     assert abs(out["fit_after_fallback"] - good) <= 1e-8 * abs(good)
+    # gamma and the predictions of that fit are those of the separate-launch fit: the inverse blocks of the back-substitution
+    # are rebuilt from the retried factor, not kept from the aborted chain launch's
+    for got, want in zip(*out["fit_vs_separate"]):
+        np.testing.assert_array_equal(np.array(got), np.array(want))
     assert out["error"] is not None and "pipelined chain kernel" in out["error"] and out["error_seconds"] < 5.0
     assert out["again"] == [good, 0]
     assert out["potrf_resid"] < 1e-12 and out["potrf_error"] is not None
