@@ -144,6 +144,12 @@ SIGNATURES = [
                                 C.c_int64, c_int64_p]),
     ("egx_sgp_predict", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_sgp_predict_var", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
+    ("egx_sgp_predict_valvar", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    ("egx_sgp_predict_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
+    ("egx_sgp_predict_var_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
+    ("egx_sgp_predict_valvar_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    ("egx_sgp_sample", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, c_double_p, c_double_p,
+                        c_double_p]),
     ("egx_sgp_get_state", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
 ]
 

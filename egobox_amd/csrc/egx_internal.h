@@ -121,6 +121,10 @@ int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, in
                       int nout, int64_t ld, const GradBatch &batch, int prescaled = 0);
 // z (n) <- W y, W upper triangular row-major
 int launch_uptri_gemv(hipStream_t s, const double *W, int64_t ld, int n, const double *y, double *z);
+// the same for `rows` right-hand sides, rows of Y (ldr apart): Z[a] = W Y[a], or base[a] + sc * W Y[a] with base != nullptr
+// (base may be Z)
+int launch_uptri_gemv_rows(hipStream_t s, const double *W, int64_t ld, int n, const double *Y, const double *base, double sc,
+                           double *Z, int64_t ldr, int rows);
 // posterior covariance of the m queries (k-major xqT, m_pad a multiple of 64): S (m_pad x m_pad, lds) = sigma2 (K(xq, xq) + G)
 // + tau I on the leading m x m block (K without nugget; G lower tiles read at i >= j only: S exactly symmetric), identity
 // rows / columns beyond m

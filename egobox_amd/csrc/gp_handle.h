@@ -241,5 +241,20 @@ int likelihood_grad_batch_core(egx_gp *gp, const double *thetas, int64_t k, int6
 // gp_predict.hip
 int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout);
 int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv);
+// gp_sample.hip: factor sigma2 (K(x, x) + G) (+ tau I) of m queries and draw nt trajectories around `mean` (m_pad host doubles).
+// xqT is k-major (d x m_pad, m_pad = m rounded up to 128), G the (m_pad x m_pad) Gram term or nullptr, max_diag the largest
+// diagonal entry of the covariance (EGX_SAMPLE_PSD's first jitter), `what` names the covariance in error messages
+struct SampleCov {
+    int corr;
+    const double *xqT;
+    int d;
+    const double *coef;
+    int hcols;
+    const double *G;
+    double sigma2, max_diag;
+    const char *what;
+};
+int sample_draw(hipStream_t st, const SampleCov &c, int m, int nt, int method, uint64_t seed, const double *z,
+                const double *mean, double *traj, double *tau_out);
 
 }  // namespace egx

@@ -9,6 +9,7 @@
 //   6. S = L L^T by launch_potrf; EGX_SAMPLE_PSD retries with tau x 10 on a failed pivot (the device info word)
 //   7. Z: the philox.h stream (k_normals) or the caller's normals
 //   8. traj = mean 1^T + L Z (k_trmm_mean: FP64 MFMA, zero upper tiles skipped)
+// Steps 5-8 (sample_draw) also serve egx_sgp_sample, whose covariance is the prior sigma2 K(x, x) (sgp_host.hip).
 #include <cstdio>
 
 #include "gp_handle.h"
@@ -16,6 +17,65 @@
 using namespace egx;
 
 namespace egx {
+
+// steps 5-8 for a covariance sigma2 (K(x, x) + G) described by `c` (G == nullptr: no Gram term), shared by the dense
+// posterior (sample_impl) and the sparse GP's prior covariance (sgp_host.hip).  mean: m_pad doubles on the host.
+int sample_draw(hipStream_t st, const SampleCov &c, int m, int nt, int method, uint64_t seed, const double *z,
+                const double *mean, double *traj, double *tau_out) {
+    const int m_pad = (int)round_up(m, kTile), nt_pad = (int)round_up(nt, 64);
+    // EGX_SAMPLE_PSD: tau0 = max(1e-9, 1e-12 max_i Sigma_ii)
+    double tau = method == EGX_SAMPLE_PSD ? std::max(1e-9, 1e-12 * c.max_diag) : 0.0;
+    DevBuf S, dinv, info;
+    EGX_RC(S.alloc((size_t)m_pad * m_pad));
+    EGX_RC(dinv.alloc(dinv_doubles(m_pad)));
+    EGX_RC(info.alloc(1));  // one int in a double-sized slot
+    const int tries = method == EGX_SAMPLE_PSD ? 7 : 1;  // the first factorisation and at most six retries
+    int piv = 0;
+    for (int t = 0; t < tries; t++) {
+        if (t) tau *= 10.0;
+        EGX_RC(launch_cov_assemble(st, c.corr, c.xqT, m_pad, m_pad, c.d, c.coef, c.hcols, c.G, m_pad, m, c.sigma2, tau, S.p,
+                                   m_pad));
+        EGX_HIP_CHECK(hipMemsetAsync(info.p, 0, sizeof(double), st));
+        EGX_RC(launch_potrf(st, S.p, m_pad, m_pad, m_pad, dinv.p, reinterpret_cast<int *>(info.p)));
+        EGX_HIP_CHECK(hipMemcpyAsync(&piv, info.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        EGX_HIP_CHECK(hipStreamSynchronize(st));
+        if (piv == 0) break;
+    }
+    if (piv != 0) {
+        char msg[200];
+        if (method == EGX_SAMPLE_CHOLESKY)
+            std::snprintf(msg, sizeof msg, "sample_chol: the %s covariance is not positive definite (pivot %d)", c.what, piv);
+        else
+            std::snprintf(msg, sizeof msg, "sample: the %s covariance + %.3g I is not positive definite (pivot %d)", c.what, tau,
+                          piv);
+        set_error(msg);
+        return EGX_ERR_LINALG;
+    }
+    EGX_RC(launch_zero_upper(st, S.p, m_pad, m_pad));
+    // Z, transposed (nt_pad x m_pad, zero padded): the contraction operand the MFMA core reads K-contiguous
+    DevBuf Zt, dmean, T;
+    EGX_RC(Zt.alloc((size_t)nt_pad * m_pad));
+    EGX_HIP_CHECK(hipMemsetAsync(Zt.p, 0, sizeof(double) * (size_t)nt_pad * m_pad, st));
+    std::vector<double> zt;
+    if (z) {
+        zt.resize((size_t)nt * m);
+        for (int64_t i = 0; i < m; i++)
+            for (int j = 0; j < nt; j++) zt[(size_t)j * m + i] = z[(size_t)i * nt + j];
+        EGX_HIP_CHECK(hipMemcpy2DAsync(Zt.p, sizeof(double) * m_pad, zt.data(), sizeof(double) * m, sizeof(double) * m, nt,
+                                       hipMemcpyHostToDevice, st));
+    } else {
+        EGX_RC(launch_normals(st, seed, m, nt, Zt.p, 1, m_pad));
+    }
+    EGX_RC(dmean.alloc((size_t)m_pad));
+    EGX_HIP_CHECK(hipMemcpyAsync(dmean.p, mean, sizeof(double) * m_pad, hipMemcpyHostToDevice, st));
+    EGX_RC(T.alloc((size_t)m_pad * nt_pad));
+    EGX_RC(launch_trmm_mean(st, S.p, m_pad, m_pad, Zt.p, m_pad, nt_pad, dmean.p, T.p, nt_pad));
+    EGX_HIP_CHECK(hipMemcpy2DAsync(traj, sizeof(double) * nt, T.p, sizeof(double) * nt_pad, sizeof(double) * nt, m,
+                                   hipMemcpyDeviceToHost, st));
+    EGX_HIP_CHECK(hipStreamSynchronize(st));
+    if (tau_out) *tau_out = tau;
+    return EGX_SUCCESS;
+}
 
 namespace {
 
@@ -126,74 +186,24 @@ int sample_impl(egx_gp *gp, const double *xq, int64_t m, int64_t n_traj, int met
     if (m == 0 || n_traj == 0) return EGX_SUCCESS;
     EGX_RC(set_device(gp));
     // mean(x): predict in original units (algorithm.rs:1158, `mean_x`)
-    const int m_pad = (int)round_up(m, kTile), nt = (int)n_traj, nt_pad = (int)round_up(nt, 64);
+    const int m_pad = (int)round_up(m, kTile), nt = (int)n_traj;
     std::vector<double> mean((size_t)m_pad, 0.0);
     EGX_RC(predict_impl(gp, xq, m, mean.data(), nullptr));
     CovBufs b;
     EGX_RC(cov_prepare(gp, xq, (int)m, b));
     hipStream_t st = gp->ws[0].stream;
-    double tau = 0.0;
-    if (method == EGX_SAMPLE_PSD) {  // tau0 = max(1e-9, 1e-12 max_i Sigma_ii), Sigma_ii = sigma2 (1 + G_ii) as k_cov_assemble forms it
+    double max_diag = 0.0;
+    if (method == EGX_SAMPLE_PSD) {  // Sigma_ii = sigma2 (1 + G_ii) as k_cov_assemble forms it
         DevBuf dg;
         EGX_RC(dg.alloc((size_t)m));
         EGX_RC(launch_gather_diag(st, b.G.p, m_pad, (int)m, dg.p));
         std::vector<double> g((size_t)m);
         EGX_HIP_CHECK(hipMemcpyAsync(g.data(), dg.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
         EGX_HIP_CHECK(hipStreamSynchronize(st));
-        double mx = 0.0;
-        for (double v : g) mx = std::max(mx, gp->sigma2 * (1.0 + v));
-        tau = std::max(1e-9, 1e-12 * mx);
+        for (double v : g) max_diag = std::max(max_diag, gp->sigma2 * (1.0 + v));
     }
-    DevBuf S, dinv, info;
-    EGX_RC(S.alloc((size_t)m_pad * m_pad));
-    EGX_RC(dinv.alloc(dinv_doubles(m_pad)));
-    EGX_RC(info.alloc(1));  // one int in a double-sized slot
-    const int tries = method == EGX_SAMPLE_PSD ? 7 : 1;  // the first factorisation and at most six retries
-    int piv = 0;
-    for (int t = 0; t < tries; t++) {
-        if (t) tau *= 10.0;
-        EGX_RC(launch_cov_assemble(st, gp->corr, b.xqT.p, m_pad, m_pad, gp->d, gp->d_fit_coef, gp->fit_hcols, b.G.p, m_pad,
-                                   (int)m, gp->sigma2, tau, S.p, m_pad));
-        EGX_HIP_CHECK(hipMemsetAsync(info.p, 0, sizeof(double), st));
-        EGX_RC(launch_potrf(st, S.p, m_pad, m_pad, m_pad, dinv.p, reinterpret_cast<int *>(info.p)));
-        EGX_HIP_CHECK(hipMemcpyAsync(&piv, info.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        EGX_HIP_CHECK(hipStreamSynchronize(st));
-        if (piv == 0) break;
-    }
-    if (piv != 0) {
-        char msg[200];
-        if (method == EGX_SAMPLE_CHOLESKY)
-            std::snprintf(msg, sizeof msg, "sample_chol: the posterior covariance is not positive definite (pivot %d)", piv);
-        else
-            std::snprintf(msg, sizeof msg, "sample: the posterior covariance + %.3g I is not positive definite (pivot %d)", tau,
-                          piv);
-        set_error(msg);
-        return EGX_ERR_LINALG;
-    }
-    EGX_RC(launch_zero_upper(st, S.p, m_pad, m_pad));
-    // Z, transposed (nt_pad x m_pad, zero padded): the contraction operand the MFMA core reads K-contiguous
-    DevBuf Zt, dmean, T;
-    EGX_RC(Zt.alloc((size_t)nt_pad * m_pad));
-    EGX_HIP_CHECK(hipMemsetAsync(Zt.p, 0, sizeof(double) * (size_t)nt_pad * m_pad, st));
-    std::vector<double> zt;
-    if (z) {
-        zt.resize((size_t)nt * m);
-        for (int64_t i = 0; i < m; i++)
-            for (int j = 0; j < nt; j++) zt[(size_t)j * m + i] = z[(size_t)i * nt + j];
-        EGX_HIP_CHECK(hipMemcpy2DAsync(Zt.p, sizeof(double) * m_pad, zt.data(), sizeof(double) * m, sizeof(double) * m, nt,
-                                       hipMemcpyHostToDevice, st));
-    } else {
-        EGX_RC(launch_normals(st, seed, m, nt, Zt.p, 1, m_pad));
-    }
-    EGX_RC(dmean.alloc((size_t)m_pad));
-    EGX_HIP_CHECK(hipMemcpyAsync(dmean.p, mean.data(), sizeof(double) * m_pad, hipMemcpyHostToDevice, st));
-    EGX_RC(T.alloc((size_t)m_pad * nt_pad));
-    EGX_RC(launch_trmm_mean(st, S.p, m_pad, m_pad, Zt.p, m_pad, nt_pad, dmean.p, T.p, nt_pad));
-    EGX_HIP_CHECK(hipMemcpy2DAsync(traj, sizeof(double) * nt, T.p, sizeof(double) * nt_pad, sizeof(double) * nt, m,
-                                   hipMemcpyDeviceToHost, st));
-    EGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (tau_out) *tau_out = tau;
-    return EGX_SUCCESS;
+    const SampleCov c{gp->corr, b.xqT.p, gp->d, gp->d_fit_coef, gp->fit_hcols, b.G.p, gp->sigma2, max_diag, "posterior"};
+    return sample_draw(st, c, (int)m, nt, method, seed, z, mean.data(), traj, tau_out);
 }
 
 }  // namespace

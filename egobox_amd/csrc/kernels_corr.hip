@@ -617,15 +617,21 @@ __global__ void k_sum_partials(const double *__restrict__ P, int nsplit, int n_p
     y[j] = sacc;
 }
 
-__global__ __launch_bounds__(256) void k_uptri_gemv(const double *__restrict__ W, int64_t ld, int n,
-                                                    const double *__restrict__ y, double *__restrict__ z) {
+// z[a][i] = (base ? base[a][i] + sc * acc : acc), acc = sum_{k >= i} W[i][k] y[a][k], for the rows a = blockIdx.y of y / base / z
+// (ldr apart): a wave per (row of W, right-hand side).  base may be z itself (an element is read by the lane that writes it).
+__global__ __launch_bounds__(256) void k_uptri_gemv(const double *__restrict__ W, int64_t ld, int n, const double *y,
+                                                    const double *base, double sc, double *z, int64_t ldr) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= n) return;
     const double *row = W + (int64_t)i * ld;
+    y += (int64_t)blockIdx.y * ldr;
     double acc = 0.0;
     for (int k = (i & ~63) + lane; k < n; k += 64) acc = __builtin_fma((k >= i) ? row[k] : 0.0, y[k], acc);
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (lane == 0) z[i] = acc;
+    if (lane == 0) {
+        const int64_t e = (int64_t)blockIdx.y * ldr + i;
+        z[e] = base ? base[e] + sc * acc : acc;
+    }
 }
 
 __global__ void k_fill_rows(double *__restrict__ M, int64_t ld, int r0, int rows_pad, const double *__restrict__ src,
@@ -1158,7 +1164,8 @@ int launch_uptri_solve_pair(hipStream_t s, const double *W, int64_t ld, int n, i
     nsplit = (n + per - 1) / per;
     hipLaunchKernelGGL(k_uptri_gemv_t, dim3(n_pad / 64, nsplit), dim3(256), 0, s, W, ld, n, r, per, P, n_pad);
     hipLaunchKernelGGL(k_sum_partials, dim3((n_pad + 255) / 256), dim3(256), 0, s, (const double *)P, nsplit, n_pad, y);
-    hipLaunchKernelGGL(k_uptri_gemv, dim3((n + 3) / 4), dim3(256), 0, s, W, ld, n, (const double *)y, z);
+    hipLaunchKernelGGL(k_uptri_gemv, dim3((n + 3) / 4), dim3(256), 0, s, W, ld, n, (const double *)y, (const double *)nullptr, 1.0, z,
+                       (int64_t)0);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
@@ -1266,14 +1273,19 @@ int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, in
 
 // z (n) <- W y for the upper triangular W (row-major): gamma = C^-T rho through the explicit C^-T of the theta-gradient
 int launch_uptri_gemv(hipStream_t s, const double *W, int64_t ld, int n, const double *y, double *z) {
-    hipLaunchKernelGGL(k_uptri_gemv, dim3((n + 3) / 4), dim3(256), 0, s, W, ld, n, y, z);
+    return launch_uptri_gemv_rows(s, W, ld, n, y, nullptr, 1.0, z, 0, 1);
+}
+
+int launch_uptri_gemv_rows(hipStream_t s, const double *W, int64_t ld, int n, const double *Y, const double *base, double sc,
+                           double *Z, int64_t ldr, int rows) {
+    hipLaunchKernelGGL(k_uptri_gemv, dim3((n + 3) / 4, (unsigned)rows), dim3(256), 0, s, W, ld, n, Y, base, sc, Z, ldr);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
 
 // Posterior covariance of m query points (GaussianProcess::_compute_covariance, algorithm.rs:310-326), one 64 x 64 tile of
 // the lower triangle per workgroup: S[i][j] = S[j][i] = sigma2 (k(x_i, x_j) + G[i][j]) + tau [i == j] for i >= j, both < m,
-// with k the handle's correlation WITHOUT nugget (k(x, x) = 1) and G = -rt^T rt + u^T u (the Gram kernels' lower tiles, read
+// with k the handle's correlation WITHOUT nugget (k(x, x) = 1) and G = -rt^T rt + u^T u (nullptr: no such term; the Gram kernels' lower tiles, read
 // at i >= j only: the result is exactly symmetric); rows and columns m .. m_pad - 1 become those of the identity, so that
 // launch_potrf factors S as it stands.  Each unordered pair is evaluated once and stored twice.
 template <int CORR, bool PRE>
@@ -1307,7 +1319,7 @@ __global__ __launch_bounds__(256) void k_cov_assemble(const double *__restrict__
             if (j > i) continue;  // (diagonal tiles) the pair comes as (j, i)
             double v;
             if (i < m) {
-                v = sigma2 * (acc[a][b].value() + G[(int64_t)i * ldg + j]);
+                v = sigma2 * (acc[a][b].value() + (G ? G[(int64_t)i * ldg + j] : 0.0));
                 if (i == j) v += tau;
             } else {
                 v = (i == j) ? 1.0 : 0.0;

@@ -1,0 +1,49 @@
+// Internal header of the sparse-GP translation units (sgp_host.hip: handle, likelihood, fit, state; sgp_predict.hip:
+// predictions, their x-gradients, sampling).
+#pragma once
+#include <mutex>
+#include <vector>
+
+#include "gp_handle.h"
+
+struct Dev {
+    double *p = nullptr;
+    ~Dev() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        EGX_HIP_CHECK(egx::dev_malloc(&p, sizeof(double) * (n ? n : 1)));
+        return EGX_SUCCESS;
+    }
+};
+
+struct egx_sgp {
+    int device = 0, corr = 0, method = 0;
+    double nugget = 0.0;
+    int n = 0, d = 0, nz = 0, n_pad = 0, z_pad = 0, zext = 0;
+    std::vector<double> y_host;
+    double yty = 0.0;
+    hipStream_t stream = nullptr;
+    Dev xT, zT, y, coef, RT, W, G, P, Kz, A, dinv_z, dinv_a, s0, sb, diag, brow, vec, wall, tmpv;
+    int *d_info = nullptr;
+    std::mutex mu;
+    // fitted state
+    bool fitted = false;
+    std::vector<double> theta;
+    double sigma2 = 0.0, noise = 0.0, likelihood = 0.0;
+    std::vector<double> w_vec;
+    // predictions (sgp_predict.hip): the explicit inverse factors C_z^-T and L^-T (upper triangular, z_pad x z_pad) of the
+    // fitted state, built by the first gradient call after a fit, and the grow-only workspace of the query chunks
+    bool winv_ok = false;
+    egx::DevBuf Wz, Wa, q_x, q_RT, q_E, q_Ct, q_part, q_out;
+    std::vector<double> h_x, h_out;
+};
+
+
+namespace egx {
+// ---- sgp_predict.hip ----
+// any subset of mean (m), variance (m), d mean / dx (m x d), d var / dx (m x d) of the m queries; caller holds g->mu
+int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout, double *gyout, double *gvout);
+}  // namespace egx

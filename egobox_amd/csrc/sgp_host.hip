@@ -12,38 +12,19 @@
 //   A = I + G = L L^T,  b = L^-1 V (beta o y)                         launch_potrf with the right-hand side riding below A
 // The Woodbury matrix of the reference (nz x nz inverses) is never formed for predictions:
 //   kx^T Kmm^-1 kx = |U^-1 kx|^2,   kx^T U^-T (L L^T)^-1 U^-1 kx = |L^-1 U^-1 kx|^2   (two launch_trsm_rows + k_row_reduce)
+// Predictions, their x-gradients and sampling: sgp_predict.hip.
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <mutex>
 #include <vector>
 
-#include "egx_internal.h"
+#include "sgp_handle.h"
 #include "cobyla.h"
 
 using namespace egx;
 
 namespace {
-
-// outcome of one start of the multistart optimisation (objective, minimiser in log10 parameters, evaluations)
-struct StartResult {
-    double f;
-    std::vector<double> x;
-    int64_t evals;
-};
-
-struct Dev {
-    double *p = nullptr;
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        EGX_HIP_CHECK(dev_malloc(&p, sizeof(double) * (n ? n : 1)));
-        return EGX_SUCCESS;
-    }
-};
 
 // W[i][t] = scale * sb[t] * RT[t][i]  (i < nz, t < n), row z_pad: W[z_pad][t] = sb[t] * y[t]; everything else 0.
 // RT is (n_pad x z_pad) row-major, W is (zext x n_pad) row-major; 32x32 LDS transpose tiles.
@@ -96,27 +77,6 @@ struct Eval {
     int status = EGX_STATUS_OK;
 };
 
-}  // namespace
-
-struct egx_sgp {
-    int device = 0, corr = 0, method = 0;
-    double nugget = 0.0;
-    int n = 0, d = 0, nz = 0, n_pad = 0, z_pad = 0, zext = 0;
-    std::vector<double> y_host;
-    double yty = 0.0;
-    hipStream_t stream = nullptr;
-    Dev xT, zT, y, coef, RT, W, G, P, Kz, A, dinv_z, dinv_a, s0, sb, diag, brow, vec, wall, tmpv;
-    int *d_info = nullptr;
-    std::mutex mu;
-    // fitted state
-    bool fitted = false;
-    std::vector<double> theta;
-    double sigma2 = 0.0, noise = 0.0, likelihood = 0.0;
-    std::vector<double> w_vec;
-};
-
-namespace {
-
 int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, double noise, Eval &out, bool keep) {
     const int n = g->n, d = g->d, nz = g->nz, n_pad = g->n_pad, z_pad = g->z_pad, zext = g->zext;
     out = Eval();
@@ -137,6 +97,7 @@ int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, 
     hipStream_t s = g->stream;
     const double sigma = std::sqrt(sigma2);
     g->fitted = false;  // the resident factors are about to be overwritten; set again below when `keep`
+    g->winv_ok = false;  // ... and with them the cached inverse factors of the x-gradients (sgp_predict.hip)
     EGX_HIP_CHECK(hipMemcpyAsync(g->coef.p, th.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
     EGX_HIP_CHECK(hipStreamSynchronize(s));  // th is a local
     EGX_HIP_CHECK(hipMemsetAsync(g->d_info, 0, 2 * sizeof(int), s));
@@ -234,72 +195,6 @@ int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, 
         g->noise = noise;
         g->likelihood = lkh;
         g->fitted = true;
-    }
-    return EGX_SUCCESS;
-}
-
-int sgp_predict(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout) {
-    if (!g->fitted) {
-        set_error("sparse model is not fitted (call egx_sgp_finalize or egx_sgp_fit first)");
-        return EGX_ERR_NOT_FITTED;
-    }
-    if (m < 0 || (m > 0 && !xq)) {
-        set_error("bad query array");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    const int d = g->d, nz = g->nz, z_pad = g->z_pad;
-    hipStream_t s = g->stream;
-    const int64_t cap = 65536;
-    for (int64_t m0 = 0; m0 < m; m0 += cap) {
-        const int mc = (int)((m - m0 < cap) ? (m - m0) : cap);
-        const int m_pad = (int)round_up(mc, kTile);
-        std::vector<double> xt((size_t)d * m_pad, 0.0);
-        for (int a = 0; a < mc; a++)
-            for (int k = 0; k < d; k++) xt[(size_t)k * m_pad + a] = xq[(size_t)(m0 + a) * d + k];
-        Dev dq, dr, dRT, dp, dq2;
-        int rc = dq.alloc(xt.size());
-        if (rc) return rc;
-        EGX_HIP_CHECK(hipMemcpyAsync(dq.p, xt.data(), sizeof(double) * xt.size(), hipMemcpyHostToDevice, s));
-        EGX_HIP_CHECK(hipStreamSynchronize(s));
-        if (yout) {  // Kx . vec  (:237-241), R never materialised
-            std::vector<double> r(m_pad);
-            rc = dr.alloc(m_pad);
-            if (rc) return rc;
-            rc = launch_predict_mean(s, g->corr, dq.p, m_pad, m_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->vec.p, dr.p);
-            if (rc) return rc;
-            EGX_HIP_CHECK(hipMemcpyAsync(r.data(), dr.p, sizeof(double) * m_pad, hipMemcpyDeviceToHost, s));
-            EGX_HIP_CHECK(hipStreamSynchronize(s));
-            for (int a = 0; a < mc; a++) yout[m0 + a] = r[a];
-        }
-        if (vout) {  // sigma2 - kx^T inv kx, clamped, + noise  (:245-257)
-            std::vector<double> p2(m_pad), q2(m_pad);
-            rc = dRT.alloc((size_t)m_pad * z_pad);
-            if (rc) return rc;
-            rc = dp.alloc(m_pad);
-            if (rc) return rc;
-            rc = dq2.alloc(m_pad);
-            if (rc) return rc;
-            rc = launch_cross_corr(s, g->corr, dq.p, m_pad, m_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, dRT.p, z_pad);
-            if (rc) return rc;
-            rc = launch_trsm_rows(s, g->Kz.p, z_pad, z_pad, g->dinv_z.p, dRT.p, z_pad, m_pad);  // C_z^-1 r
-            if (rc) return rc;
-            rc = launch_row_reduce(s, dRT.p, z_pad, m_pad, nz, nullptr, 0, 0, dp.p, nullptr);
-            if (rc) return rc;
-            rc = launch_trsm_rows(s, g->A.p, z_pad, z_pad, g->dinv_a.p, dRT.p, z_pad, m_pad);   // L^-1 C_z^-1 r
-            if (rc) return rc;
-            rc = launch_row_reduce(s, dRT.p, z_pad, m_pad, nz, nullptr, 0, 0, dq2.p, nullptr);
-            if (rc) return rc;
-            EGX_HIP_CHECK(hipMemcpyAsync(p2.data(), dp.p, sizeof(double) * m_pad, hipMemcpyDeviceToHost, s));
-            EGX_HIP_CHECK(hipMemcpyAsync(q2.data(), dq2.p, sizeof(double) * m_pad, hipMemcpyDeviceToHost, s));
-            EGX_HIP_CHECK(hipStreamSynchronize(s));
-            // p = U^-1 kx = sigma C_z^-1 r  ->  |p|^2 = sigma2 |C_z^-1 r|^2, likewise q
-            for (int a = 0; a < mc; a++) {
-                const double quad = (g->method == 0) ? g->sigma2 * (p2[a] - q2[a]) : g->sigma2 * (p2[a] + q2[a]);
-                double var = g->sigma2 - quad;
-                if (var < 1e-15) var = 1e-15;
-                vout[m0 + a] = var + g->noise;
-            }
-        }
     }
     return EGX_SUCCESS;
 }
@@ -567,26 +462,6 @@ int32_t egx_sgp_fit(egx_sgp *g, const double *params0s, int64_t n_starts, const 
         return EGX_ERR_LINALG;
     }
     return EGX_SUCCESS;
-}
-
-int32_t egx_sgp_predict(egx_sgp *g, const double *xq, int64_t m, double *y) {
-    if (!g || (m > 0 && !y)) {
-        set_error("NULL argument");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(g->mu);
-    EGX_HIP_CHECK(hipSetDevice(g->device));
-    return sgp_predict(g, xq, m, y, nullptr);
-}
-
-int32_t egx_sgp_predict_var(egx_sgp *g, const double *xq, int64_t m, double *var) {
-    if (!g || (m > 0 && !var)) {
-        set_error("NULL argument");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(g->mu);
-    EGX_HIP_CHECK(hipSetDevice(g->device));
-    return sgp_predict(g, xq, m, nullptr, var);
 }
 
 // Fitted state: theta (d), sigma2, noise, likelihood, Woodbury vector (nz) and -- computed on the host from the two

@@ -131,6 +131,56 @@ class SgpHandle:
         L.check(self._lib.egx_sgp_predict_var(self._h, L.dptr(x), x.shape[0], L.dptr(out)))
         return out
 
+    def predict_valvar(self, x):
+        """(mean, variance) from one call (one upload, one synchronisation): the bits of `predict` and `predict_var`."""
+        x = self._q(x)
+        y, v = np.empty(x.shape[0]), np.empty(x.shape[0])
+        L.check(self._lib.egx_sgp_predict_valvar(self._h, L.dptr(x), x.shape[0], L.dptr(y), L.dptr(v)))
+        return y, v
+
+    def predict_gradients(self, x):
+        """(m, d) analytic d mean / d x (egx_sgp_predict_gradients)."""
+        x = self._q(x)
+        out = np.empty(x.shape)
+        L.check(self._lib.egx_sgp_predict_gradients(self._h, L.dptr(x), x.shape[0], L.dptr(out)))
+        return out
+
+    def predict_var_gradients(self, x):
+        """(m, d) analytic d var / d x, exactly 0 where `predict_var` clamps (egx_sgp_predict_var_gradients)."""
+        x = self._q(x)
+        out = np.empty(x.shape)
+        L.check(self._lib.egx_sgp_predict_var_gradients(self._h, L.dptr(x), x.shape[0], L.dptr(out)))
+        return out
+
+    def predict_valvar_gradients(self, x):
+        """Both analytic gradients from one K(x, z) block and one pair of forward solves."""
+        x = self._q(x)
+        gy, gv = np.empty(x.shape), np.empty(x.shape)
+        L.check(self._lib.egx_sgp_predict_valvar_gradients(self._h, L.dptr(x), x.shape[0], L.dptr(gy), L.dptr(gv)))
+        return gy, gv
+
+    def sample(self, x, n_traj, method="psd", seed=None, z=None, return_tau=False):
+        """(m, n_traj) trajectories predict(x) 1^T + F Z (egx_sgp_sample), F F^T = sigma2 r(x, x) (+ tau I): the PRIOR
+        covariance, as the reference samples its sparse GP.  Arguments and return convention of `GpHandle.sample`."""
+        x = self._q(x)
+        m, n_traj = x.shape[0], int(n_traj)
+        meth = {"cholesky": L.SAMPLE_CHOLESKY, "psd": L.SAMPLE_PSD}.get(method, method)
+        if not isinstance(meth, int):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"unknown sampling method {method!r}")
+        if seed is None:
+            seed = int(np.random.default_rng().integers(0, 2 ** 63))
+        zp = None
+        if z is not None:
+            z = L.as_f64(z, 2)
+            if z.shape != (m, n_traj):
+                raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"z must be ({m}, {n_traj}), got {z.shape}")
+            zp = L.dptr(z)
+        out = np.empty((m, n_traj))
+        tau = C.c_double()
+        L.check(self._lib.egx_sgp_sample(self._h, L.dptr(x), m, n_traj, int(meth), int(seed) & (2 ** 64 - 1), zp, L.dptr(out),
+                                         C.byref(tau)))
+        return (out, tau.value) if return_tau else out
+
     def state(self, with_inv=False):
         th, vec = np.empty(self.d), np.empty(self.nz)
         s2, nv, lk = C.c_double(), C.c_double(), C.c_double()
@@ -265,11 +315,42 @@ class SparseGaussianProcess:
         v = fn(shifted.reshape(-1, nx)).reshape(2 * nx, m)
         return ((v[0::2] - v[1::2]) / (2.0 * h)).T.copy()
 
-    def predict_gradients(self, x):
+    def predict_valvar(self, x):
+        return self._h.predict_valvar(x)
+
+    def predict_gradients(self, x, analytic=False):
+        """Default: the reference's central differences.  analytic=True: the closed form they approximate, evaluated on
+        the GPU (egx_sgp_predict_gradients) -- what a Rust shim behind `SgpSurrogate::predict_gradients` should bind."""
+        if analytic:
+            return self._h.predict_gradients(x)
         return self._central_diff(self._h.predict, x)
 
-    def predict_var_gradients(self, x):
+    def predict_var_gradients(self, x, analytic=False):
+        """As `predict_gradients`; the analytic form (egx_sgp_predict_var_gradients) is exactly 0 where the variance is
+        clamped at 1e-15, which is what the central difference of the clamped function gives there."""
+        if analytic:
+            return self._h.predict_var_gradients(x)
         return self._central_diff(self._h.predict_var, x)
+
+    def predict_valvar_gradients(self, x):
+        """(d mean / d x, d var / d x), analytic only (egx_sgp_predict_valvar_gradients): what a shim should bind for
+        `predict_valvar_gradients`."""
+        return self._h.predict_valvar_gradients(x)
+
+    def sample_chol(self, x, n_traj, seed=None):
+        """sparse_algorithm.rs:338-362 with the plain Cholesky factor: (m, n_traj) trajectories predict(x) + F Z with
+        F F^T = sigma2 r(x, x), the PRIOR covariance (no noise, no Woodbury term: the reference's definition, kept as it
+        is); LinalgError when it is not positive definite."""
+        return self._h.sample(x, n_traj, "cholesky", seed)
+
+    def sample_eig(self, x, n_traj, seed=None):
+        """As `GaussianProcess.sample_eig` (same deviation: Cholesky of the covariance + tau I, no eigendecomposition),
+        on the prior covariance of `sample_chol`."""
+        return self._h.sample(x, n_traj, "psd", seed)
+
+    def sample(self, x, n_traj, seed=None):
+        """Alias of `sample_eig`, as in the reference."""
+        return self.sample_eig(x, n_traj, seed)
 
     def theta(self):
         return self._h.state()["theta"]
@@ -351,11 +432,26 @@ class SparseGpx:
     def predict_var(self, x):
         return self._sgp.predict_var(x)
 
-    def predict_gradients(self, x):
-        return self._sgp.predict_gradients(x)
+    def predict_valvar(self, x):
+        return self._sgp.predict_valvar(x)
 
-    def predict_var_gradients(self, x):
-        return self._sgp.predict_var_gradients(x)
+    def predict_gradients(self, x, analytic=False):
+        return self._sgp.predict_gradients(x, analytic=analytic)
+
+    def predict_var_gradients(self, x, analytic=False):
+        return self._sgp.predict_var_gradients(x, analytic=analytic)
+
+    def predict_valvar_gradients(self, x):
+        return self._sgp.predict_valvar_gradients(x)
+
+    def sample(self, x, n_traj, seed=None):
+        return self._sgp.sample(x, n_traj, seed)
+
+    def sample_chol(self, x, n_traj, seed=None):
+        return self._sgp.sample_chol(x, n_traj, seed)
+
+    def sample_eig(self, x, n_traj, seed=None):
+        return self._sgp.sample_eig(x, n_traj, seed)
 
     def thetas(self):
         return self._sgp.theta()[None, :]

@@ -524,6 +524,28 @@ int32_t egx_sgp_fit(egx_sgp *sgp, const double *params0s, int64_t n_starts, cons
 /* SparseGaussianProcess::predict :237-241, predict_var :245-257 (clamp at 1e-15, + noise) */
 int32_t egx_sgp_predict(egx_sgp *sgp, const double *xq, int64_t m, double *y /*m*/);
 int32_t egx_sgp_predict_var(egx_sgp *sgp, const double *xq, int64_t m, double *var /*m*/);
+/* Mean and variance of the same points in one call: one upload, one launch sequence, one synchronisation; the same bits as
+ * the two calls above.  (The mean keeps its own kernel, which evaluates r(xq, z) on the fly: a row-dot of the K(xq, z) block
+ * formed for the variance would have to repeat that kernel's summation order to keep the bits, and was not attempted.) */
+int32_t egx_sgp_predict_valvar(egx_sgp *sgp, const double *xq, int64_t m, double *y /*m*/, double *var /*m*/);
+/* ANALYTIC x-gradients (what a SgpSurrogate shim binds for predict_gradients / predict_var_gradients /
+ * predict_valvar_gradients; the reference takes central differences of predict / predict_var, :298-336, which these are the
+ * limit of).  With kx = sigma2 r(x, z), W / vec the WoodburyData of egx_sgp_get_state:
+ *   d mean / d x_k = sigma2 sum_j vec_j d r(x, z_j) / d x_k
+ *   d var  / d x_k = -2 sigma2 sum_j (W kx)_j d r(x, z_j) / d x_k  where sigma2 - kx^T W kx >= 1e-15, and exactly 0 where
+ *                    predict_var clamps (the derivative of the clamped function, as the central difference gives there).
+ * xq (m x d) in the units of the training inputs; m = 0 succeeds and does nothing; EGX_ERR_UNSUPPORTED when 6 d > 20480. */
+int32_t egx_sgp_predict_gradients(egx_sgp *sgp, const double *xq, int64_t m, double *grad /*m*d*/);
+int32_t egx_sgp_predict_var_gradients(egx_sgp *sgp, const double *xq, int64_t m, double *grad /*m*d*/);
+int32_t egx_sgp_predict_valvar_gradients(egx_sgp *sgp, const double *xq, int64_t m, double *grad_y /*m*d*/,
+                                         double *grad_var /*m*d*/);
+/* SparseGaussianProcess::sample :338-362 AS THE REFERENCE DEFINES IT: traj (m x n_traj) = predict(xq) 1^T + F Z with
+ * F F^T = sigma2 r(xq, xq) (+ tau I): the PRIOR covariance, without the noise and without the Woodbury term.  That is a
+ * quirk of the reference, kept on purpose: the trajectories scatter around the posterior mean with the prior's spread.
+ * method, seed, z, tau_out, the normals, the EGX_SAMPLE_PSD jitter rule and the deviation from sample_eig are those of
+ * egx_gp_sample (above); nothing m x m leaves the device. */
+int32_t egx_sgp_sample(egx_sgp *sgp, const double *xq, int64_t m, int64_t n_traj, int32_t method, uint64_t seed,
+                       const double *z /*m*n_traj or NULL*/, double *traj /*m*n_traj*/, double *tau_out /*1 or NULL*/);
 /* fitted state: theta (d), sigma2, noise, likelihood, WoodburyData vec (nz) and inv (nz*nz) :32-36; NULL = skip */
 int32_t egx_sgp_get_state(egx_sgp *sgp, double *theta, double *sigma2, double *noise, double *likelihood,
                           double *w_vec, double *w_inv);

@@ -231,6 +231,72 @@ class GaussianProcess {
     int64_t d_ = 0, n_evals_ = 0;
 };
 
+// SparseGaussianProcess at given parameters, sparse_algorithm.rs:145-362 (the predict side; the multistart fit is egx_sgp_fit):
+// x (n x d), y (n), z (nz x d) row-major, raw units, zero trend.  Everything a SgpSurrogate (FullGpSurrogate) needs.
+class SparseGaussianProcess {
+  public:
+    SparseGaussianProcess(const double *x, const double *y, int64_t n, int64_t d, const double *z, int64_t nz,
+                          const egx_sgp_config *cfg = nullptr)
+        : d_(d) {
+        egx_sgp *h = nullptr;
+        check(egx_sgp_create(cfg, x, y, n, d, z, nz, &h));
+        h_.reset(h);
+    }
+    void finalize(const double *theta, int64_t theta_len, double sigma2, double noise) {
+        check(egx_sgp_finalize(h_.get(), theta, theta_len, sigma2, noise));
+    }
+    std::vector<double> predict(const double *x, int64_t m) const {
+        std::vector<double> y((size_t)m);
+        check(egx_sgp_predict(h_.get(), x, m, y.data()));
+        return y;
+    }
+    std::vector<double> predict_var(const double *x, int64_t m) const {
+        std::vector<double> v((size_t)m);
+        check(egx_sgp_predict_var(h_.get(), x, m, v.data()));
+        return v;
+    }
+    std::pair<std::vector<double>, std::vector<double>> predict_valvar(const double *x, int64_t m) const {
+        std::vector<double> y((size_t)m), v((size_t)m);
+        check(egx_sgp_predict_valvar(h_.get(), x, m, y.data(), v.data()));
+        return {std::move(y), std::move(v)};
+    }
+    // analytic (m x d) row-major gradients: the closed form the reference's central differences (:298-336) approximate
+    std::vector<double> predict_gradients(const double *x, int64_t m) const {
+        std::vector<double> g((size_t)(m * d_));
+        check(egx_sgp_predict_gradients(h_.get(), x, m, g.data()));
+        return g;
+    }
+    std::vector<double> predict_var_gradients(const double *x, int64_t m) const {
+        std::vector<double> g((size_t)(m * d_));
+        check(egx_sgp_predict_var_gradients(h_.get(), x, m, g.data()));
+        return g;
+    }
+    std::pair<std::vector<double>, std::vector<double>> predict_valvar_gradients(const double *x, int64_t m) const {
+        std::vector<double> gy((size_t)(m * d_)), gv((size_t)(m * d_));
+        check(egx_sgp_predict_valvar_gradients(h_.get(), x, m, gy.data(), gv.data()));
+        return {std::move(gy), std::move(gv)};
+    }
+    // :338-362 -> (m x n_traj) row-major around predict(x) with the PRIOR covariance sigma2 r(x, x) (the reference's definition)
+    std::vector<double> sample(const double *x, int64_t m, int64_t n_traj, egx_sample_method method = EGX_SAMPLE_PSD,
+                               uint64_t seed = 0, const double *z = nullptr, double *tau = nullptr) const {
+        std::vector<double> t((size_t)(m * n_traj));
+        check(egx_sgp_sample(h_.get(), x, m, n_traj, method, seed, z, t.data(), tau));
+        return t;
+    }
+    std::vector<double> sample_chol(const double *x, int64_t m, int64_t n_traj, uint64_t seed = 0) const {
+        return sample(x, m, n_traj, EGX_SAMPLE_CHOLESKY, seed);
+    }
+    std::pair<int64_t, int64_t> dims() const { return {d_, 1}; }
+    egx_sgp *handle() const { return h_.get(); }
+
+  private:
+    struct Deleter {
+        void operator()(egx_sgp *p) const { egx_sgp_destroy(p); }
+    };
+    std::unique_ptr<egx_sgp, Deleter> h_;
+    int64_t d_ = 0;
+};
+
 inline std::vector<GaussianProcess> GpParams::fit_group(const double *x, const double *y, int64_t n, int64_t d, int32_t k) const {
     if (tuning_.kind == ThetaTuning::Kind::Partial)
         throw InvalidValueError(EGX_ERR_INVALID_VALUE, "fit_group: ThetaTuning::Fixed or ::Full");
