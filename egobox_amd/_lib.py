@@ -25,7 +25,8 @@ TRACE_LIB_PATH = os.path.join(_HERE, "lib", "_dev", "libegx_gp_hip_trace.so")
 SAMPLE_CHOLESKY, SAMPLE_PSD = 0, 1
 
 # return codes / status values (egx_rc, egx_status)
-SUCCESS, ERR_INVALID_VALUE, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_FITTED, ERR_LINALG, ERR_LIKELIHOOD, ERR_UNSUPPORTED, ERR_PEER = range(9)
+SUCCESS, ERR_INVALID_VALUE, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_FITTED, ERR_LINALG, ERR_LIKELIHOOD, ERR_UNSUPPORTED, ERR_PEER, \
+    ERR_NO_FINITE_START = range(10)
 STATUS_OK, STATUS_NOT_POSITIVE_DEFINITE, STATUS_ILL_CONDITIONED_FT, STATUS_ILL_CONDITIONED_F, STATUS_NAN_THETA, STATUS_RANK_FAILED = range(6)
 
 c_double_p = C.POINTER(C.c_double)
@@ -46,6 +47,19 @@ class InnerView(C.Structure):
 
 class SgpConfig(C.Structure):
     _fields_ = [("corr", C.c_int32), ("method", C.c_int32), ("nugget", C.c_double), ("device", C.c_int32)]
+
+
+class InfillConfig(C.Structure):
+    _fields_ = [("criterion", C.c_int32), ("feasibility", C.c_int32), ("fmin", C.c_double), ("sigma_weight", C.c_double),
+                ("scale_ic", C.c_double), ("scale", C.c_double)]
+
+
+class InfillParts(C.Structure):
+    _fields_ = [(k, c_double_p) for k in ("mean", "var", "grad_mean", "grad_var")]
+
+
+class InfillStats(C.Structure):
+    _fields_ = [("rounds", C.c_int64), ("best_start", C.c_int64), ("evals", c_int64_p)]
 
 
 class Timings(C.Structure):
@@ -151,6 +165,16 @@ SIGNATURES = [
     ("egx_sgp_sample", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, c_double_p, c_double_p,
                         c_double_p]),
     ("egx_sgp_get_state", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("egx_infill_config_default", None, [C.POINTER(InfillConfig)]),
+    ("egx_infill_create", C.c_int32, [C.POINTER(InfillConfig), C.c_void_p, C.POINTER(C.c_void_p), c_double_p, C.c_int32,
+                                      C.POINTER(C.c_void_p)]),
+    ("egx_infill_destroy", None, [C.c_void_p]),
+    ("egx_infill_set_params", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32]),
+    ("egx_infill_get_params", C.c_int32, [C.c_void_p, C.POINTER(InfillConfig)]),
+    ("egx_infill_eval", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, C.POINTER(InfillParts)]),
+    ("egx_infill_scaling", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p]),
+    ("egx_infill_optimize", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                        c_double_p, C.POINTER(InfillStats)]),
 ]
 
 

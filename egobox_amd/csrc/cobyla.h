@@ -29,10 +29,12 @@ class CobylaBox {
 public:
     enum Status { RUNNING = 0, MAXEVAL = 1, FTOL = 2, RHOEND = 3, ROUNDOFF = 4 };
 
-    // x0, lo, hi in the caller's units; rhobeg = initial step (all coordinates), ftol_rel as nlopt_stop_ftol
+    // x0, lo, hi in the caller's units; rhobeg = initial step (all coordinates), ftol_rel / ftol_abs as nlopt_stop_ftol
+    // (ftol_abs = 0: the relative test alone, bit for bit what every caller before the infill optimiser got)
     CobylaBox(const std::vector<double> &x0, const std::vector<double> &lo, const std::vector<double> &hi, double rhobeg,
-              double ftol_rel, int64_t maxeval, double rhoend_scaled = 0.0, bool rho_doubling = true, bool clamp_eval = true)
-        : n_((int)x0.size()), scale_(rhobeg), ftol_rel_(ftol_rel), maxfun_(maxeval), rhoend_(rhoend_scaled),
+              double ftol_rel, int64_t maxeval, double rhoend_scaled = 0.0, bool rho_doubling = true, bool clamp_eval = true,
+              double ftol_abs = 0.0)
+        : n_((int)x0.size()), scale_(rhobeg), ftol_rel_(ftol_rel), ftol_abs_(ftol_abs), maxfun_(maxeval), rhoend_(rhoend_scaled),
           rho_doubling_(rho_doubling), clamp_eval_(clamp_eval) {
         const int n = n_;
         lo_.resize(n);
@@ -98,7 +100,7 @@ private:
     static constexpr double kBarrier = 1e30;
     enum Label { L_EVAL, L_AFTER_EVAL, L140, L370, L440, L550, L_DONE };
     int n_;
-    double scale_, ftol_rel_;
+    double scale_, ftol_rel_, ftol_abs_;
     int64_t maxfun_;
     double rhoend_;
     bool rho_doubling_;  // false = Powell's original radius schedule (used to validate against his Fortran code)
@@ -516,9 +518,9 @@ private:
                 // the function-value stopping test lives where rho is about to be reduced
                 {
                     const double fb = (ifull_ == 1) ? f_ : datf_[np];
-                    if (fb < minf_ && ftol_rel_ > 0.0) {
+                    if (fb < minf_ && (ftol_rel_ > 0.0 || ftol_abs_ > 0.0)) {
                         const double d = std::fabs(fb - minf_);
-                        if (std::isfinite(minf_) && (d < ftol_rel_ * (std::fabs(fb) + std::fabs(minf_)) * 0.5 || fb == minf_)) {
+                        if (std::isfinite(minf_) && (d < ftol_abs_ || d < ftol_rel_ * (std::fabs(fb) + std::fabs(minf_)) * 0.5 || fb == minf_)) {
                             finish(FTOL);
                             return;
                         }

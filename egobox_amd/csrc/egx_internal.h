@@ -142,6 +142,40 @@ int launch_normals(hipStream_t s, uint64_t seed, int64_t m, int64_t nt, double *
 int launch_trmm_mean(hipStream_t s, const double *L, int64_t ldl, int m_pad, const double *Zt, int64_t ldz, int nt_pad,
                      const double *mean, double *T, int64_t ldt);
 
+// ---- kernels_infill.hip -----------------------------------------------------
+// The host arithmetic of predict_impl / xgrad_impl as kernels over ONE tile of kTile query points of one model, and the
+// criterion of infill_math.h across the models of a point (gp_infill.hip).
+namespace infill {
+struct Params;
+}
+// raw rows (mt x d, mt <= kTile) -> normalised k-major tile xqT (d x kTile); par = x_mean (d) | x_std (d); points with a
+// non-finite coordinate are zeroed and flagged (flag: kTile ints or nullptr), the slots beyond mt are zero
+int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag);
+struct InfillTrend {
+    int p = 1, rp = 0, msplit = 1;
+    const double *xqT = nullptr;   // d x kTile
+    const int *fidx = nullptr;     // 2 p ints: the coordinates of regression column l (-1: 1.0)
+    const double *beta = nullptr;  // p
+    const double *R = nullptr, *Rt = nullptr;  // ft_qr_r and its transpose (p x p row-major)
+    const double *racc = nullptr;  // msplit x kTile partial sums of launch_predict_mean
+    const double *s0 = nullptr, *sl = nullptr;  // launch_row_reduce's outputs
+    double sigma2 = 0.0, y_mean = 0.0, y_std = 1.0;
+    double *mean = nullptr, *var = nullptr;  // kTile each
+    double *dneg = nullptr;        // kTile x rp: -D = -B^-1 A^T zero padded, or nullptr (values only)
+};
+int launch_infill_trend(hipStream_t s, const InfillTrend &t);
+// gmean / gvar (kTile x d) from launch_xgrad's partial sums (nsplit x kTile x d each), original units
+int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *out_v,
+                               const double *x_std, double *gmean, double *gvar);
+// value[i] / grad[i * d ..] of the m points of a call; model j of point i at j * mstride + i; grad may be nullptr
+int launch_infill_combine(hipStream_t s, const infill::Params &prm, int k, int d, int64_t m, int64_t mstride, const double *mean,
+                          const double *var, const double *gmean, const double *gvar, const double *tol, const int *flag,
+                          double *value, double *grad);
+// the scaling pass' terms per point, on the device with k_infill_combine's text: ei (EI value; nullptr = skipped), base (the
+// objective of prm without the feasibility factor) and fac (pofs, or logpofs for LogEI); base == nullptr skips both
+int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, int64_t m, int64_t mstride, const double *mean,
+                              const double *var, const double *tol, const int *flag, double *ei, double *base, double *fac);
+
 // ---- kernels_chol.hip -------------------------------------------------------
 // In-place blocked right-looking Cholesky of the leading n_pad x n_pad block (lower), applied to
 // all m_tot >= n_pad rows (rows >= n_pad are right-hand sides: on return they hold (C^-1 B)^T).

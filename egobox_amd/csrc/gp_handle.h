@@ -241,6 +241,8 @@ int likelihood_grad_batch_core(egx_gp *gp, const double *thetas, int64_t k, int6
 // gp_predict.hip
 int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout);
 int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv);
+// d_W <- C^-T and d_neg_invkf <- -C^-T [ft | yt] of the fitted factor, cached per fitted state (fit_epoch)
+int ensure_winv(egx_gp *gp);
 // gp_sample.hip: factor sigma2 (K(x, x) + G) (+ tau I) of m queries and draw nt trajectories around `mean` (m_pad host doubles).
 // xqT is k-major (d x m_pad, m_pad = m rounded up to 128), G the (m_pad x m_pad) Gram term or nullptr, max_diag the largest
 // diagonal entry of the covariance (EGX_SAMPLE_PSD's first jitter), `what` names the covariance in error messages

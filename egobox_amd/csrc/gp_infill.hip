@@ -1,0 +1,521 @@
+// EGO's infill criterion on fitted dense GPs (crates/ego/src/criteria/{ei,wb2}.rs, utils/{logei_helper,cstr_pof}.rs,
+// solver/solver_computations.rs:132-193, 297-475, solver/solver_infill_optim.rs:148-236): the minimised objective and its
+// x-gradient for m points in one call, from one objective model and k constraint models; the scaling pass; the lock-step
+// COBYLA multistart.
+//
+// A call walks the points in tiles of EXACTLY kTile = 128 and, per tile, the models one after the other through the launch
+// sequence of predict_impl / xgrad_impl's batched form; what those do on the host between their launches runs in the
+// kernels of kernels_infill.hip, and k_infill_combine applies infill_math.h across the models.  One upload, one launch sequence
+// per (tile, model), one combine, the copies back, ONE synchronisation: the count depends on k and on the number of tiles only.
+// Every launch of a tile has the padded batch size 128, and the splits of the training range are functions of the model
+// alone: the bits of a point do not depend on where it sits nor on its companions (tests/test_gpu_infill.py).
+#include <set>
+
+#include "gp_handle.h"
+#include "infill_math.h"
+
+using namespace egx;
+
+namespace {
+
+// per-model device copies of the small fitted state the trend kernel reads; refreshed when the model's fit_epoch moves
+struct ModelCache {
+    uint64_t epoch = ~(uint64_t)0;
+    bool valid = false;
+    DevBuf beta, R, Rt, fidx;
+};
+
+// regression column l of f(x) = fa[l] * fb[l]: (-1, -1) the constant, (j, -1) x_j, (k, j) x_j x_k (host_math.h regression_row)
+std::vector<int> regression_index(int mean, int d) {
+    std::vector<int> idx = {-1, -1};
+    if (mean >= 1)
+        for (int j = 0; j < d; j++) idx.insert(idx.end(), {j, -1});
+    if (mean >= 2)
+        for (int k = 0; k < d; k++)
+            for (int j = k; j < d; j++) idx.insert(idx.end(), {k, j});
+    return idx;
+}
+
+// the splits of the training range for a tile of 128 queries: predict_impl's / xgrad_impl's rules at m_pad = kTile
+int mean_splits(const egx_gp *gp) {
+    int msplit = (1024 + kTile / 64 - 1) / (kTile / 64);
+    if (msplit > gp->n_pad / 64) msplit = gp->n_pad / 64;
+    const int per = (gp->n_pad / 64 + msplit - 1) / msplit;
+    return (gp->n_pad / 64 + per - 1) / per;
+}
+int xgrad_splits(const egx_gp *gp) {
+    int nsplit = 512;
+    const int slabs = (gp->n + 63) / 64;
+    if (nsplit > slabs) nsplit = slabs;
+    const int per = (slabs + nsplit - 1) / nsplit;
+    return (slabs + per - 1) / per;
+}
+
+}  // namespace
+
+struct egx_infill {
+    std::mutex mu;
+    std::vector<egx_gp *> models;  // [0] the objective model, then the constraint models (borrowed)
+    std::vector<double> tol;       // k
+    infill::Params prm{};
+    int d = 0, device = 0;
+    std::unique_ptr<ModelCache[]> cache;  // one per model
+    DevBuf d_tol;
+    bool tol_on_device = false;
+    // buffers of a call (grow-only): the whole call's points and results, then the scratch of ONE (tile, model) step
+    DevBuf xraw, flag, mean, var, gmean, gvar, value, grad;
+    DevBuf xqT, racc, RT, s0, sl, Wt, dneg, out_y, out_v;
+};
+
+namespace {
+
+// The distinct models' locks (a model may serve twice, e.g. as objective and as a constraint), taken in ADDRESS order, not in
+// index order: two handles that hold the same models in opposite roles and are evaluated from two threads would otherwise
+// take the exclusive locks in opposite orders.
+struct ModelLocks {
+    std::vector<std::unique_lock<std::shared_mutex>> held;
+    explicit ModelLocks(egx_infill *h) {
+        const std::set<egx_gp *, std::less<egx_gp *>> distinct(h->models.begin(), h->models.end());
+        for (egx_gp *gp : distinct) held.emplace_back(gp->mu);
+    }
+};
+
+int refresh_cache(egx_infill *h, int j, hipStream_t st) {
+    egx_gp *gp = h->models[j];
+    ModelCache &c = h->cache[j];
+    if (c.valid && c.epoch == gp->fit_epoch) return EGX_SUCCESS;
+    const int p = gp->p;
+    const std::vector<int> idx = regression_index(gp->mean, gp->d);
+    std::vector<double> rt((size_t)p * p);
+    for (int i = 0; i < p; i++)
+        for (int l = 0; l < p; l++) rt[(size_t)i * p + l] = gp->ft_qr_r[(size_t)l * p + i];
+    EGX_RC(c.beta.alloc(p));
+    EGX_RC(c.R.alloc((size_t)p * p));
+    EGX_RC(c.Rt.alloc((size_t)p * p));
+    EGX_RC(c.fidx.alloc((idx.size() + 1) / 2));
+    EGX_HIP_CHECK(hipMemcpyAsync(c.beta.p, gp->beta.data(), sizeof(double) * p, hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipMemcpyAsync(c.R.p, gp->ft_qr_r.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipMemcpyAsync(c.Rt.p, rt.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipMemcpyAsync(c.fidx.p, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipStreamSynchronize(st));  // rt and idx are locals; once per fitted state
+    c.epoch = gp->fit_epoch;
+    c.valid = true;
+    return EGX_SUCCESS;
+}
+
+// The evaluation proper; the handle's and the models' locks are held.  value / grad / every member of parts may be nullptr.
+int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts) {
+    if (m < 0 || (m > 0 && !xq)) {
+        set_error("bad query array");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int nm = (int)h->models.size(), k = nm - 1, d = h->d;
+    for (int j = 0; j < nm; j++)
+        if (!h->models[j]->fitted) {
+            set_error("infill: model " + std::to_string(j) + " is not fitted (call egx_gp_finalize or egx_gp_fit first)");
+            return EGX_ERR_NOT_FITTED;
+        }
+    if (m == 0) return EGX_SUCCESS;
+    const bool want_g = grad || (parts && (parts->grad_mean || parts->grad_var));
+    EGX_RC(set_device(h->models[0]));
+    hipStream_t st = h->models[0]->ws[0].stream;
+    if (want_g)
+        for (int j = 0; j < nm; j++) EGX_RC(ensure_winv(h->models[j]));  // once per fitted state (synchronises the model's stream)
+    for (int j = 0; j < nm; j++) EGX_RC(refresh_cache(h, j, st));
+    if (k > 0 && !h->tol_on_device) {
+        EGX_RC(h->d_tol.alloc(k));
+        EGX_HIP_CHECK(hipMemcpyAsync(h->d_tol.p, h->tol.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+        h->tol_on_device = true;
+    }
+    const int64_t M = round_up(m, kTile);
+    int n_pad_max = 0, p_max = 0, rp_max = 0, ms_max = 0, ns_max = 0;
+    for (egx_gp *gp : h->models) {
+        n_pad_max = std::max(n_pad_max, gp->n_pad);
+        p_max = std::max(p_max, gp->p);
+        rp_max = std::max(rp_max, gp->rhs_pad);
+        ms_max = std::max(ms_max, mean_splits(gp));
+        ns_max = std::max(ns_max, xgrad_splits(gp));
+    }
+    EGX_RC(h->xraw.alloc((size_t)m * d));
+    EGX_RC(h->flag.alloc((size_t)(M + 1) / 2));
+    EGX_RC(h->mean.alloc((size_t)nm * M));
+    EGX_RC(h->var.alloc((size_t)nm * M));
+    EGX_RC(h->value.alloc((size_t)M));
+    EGX_RC(h->xqT.alloc((size_t)d * kTile));
+    EGX_RC(h->racc.alloc((size_t)ms_max * kTile));
+    EGX_RC(h->RT.alloc((size_t)kTile * n_pad_max));
+    EGX_RC(h->s0.alloc(kTile));
+    EGX_RC(h->sl.alloc((size_t)kTile * p_max));
+    if (want_g) {
+        EGX_RC(h->gmean.alloc((size_t)nm * M * d));
+        EGX_RC(h->gvar.alloc((size_t)nm * M * d));
+        EGX_RC(h->grad.alloc((size_t)M * d));
+        EGX_RC(h->Wt.alloc((size_t)n_pad_max * kTile));
+        EGX_RC(h->dneg.alloc((size_t)kTile * rp_max));
+        EGX_RC(h->out_y.alloc((size_t)ns_max * kTile * d));
+        EGX_RC(h->out_v.alloc((size_t)ns_max * kTile * d));
+    }
+    int *flag = reinterpret_cast<int *>(h->flag.p);
+    EGX_HIP_CHECK(hipMemcpyAsync(h->xraw.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st));
+    for (int64_t t0 = 0; t0 < m; t0 += kTile) {
+        const int mt = (int)std::min<int64_t>(kTile, m - t0);
+        for (int j = 0; j < nm; j++) {
+            egx_gp *gp = h->models[j];
+            Workspace &w = gp->ws[0];
+            ModelCache &c = h->cache[j];
+            const int n = gp->n, n_pad = gp->n_pad, p = gp->p, rp = gp->rhs_pad;
+            const int msplit = mean_splits(gp), nsplit = xgrad_splits(gp);
+            EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, j == 0 ? flag + t0 : nullptr));
+            // r . gamma in split partial sums (algorithm.rs:260-262), before the solve overwrites r
+            EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
+                                       gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
+                                       gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
+            // rt = C^-1 r (held transposed), sum rt^2 and ft^T rt (:337-352)
+            EGX_RC(launch_cross_corr(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
+                                     gp->fit_hcols, h->RT.p, n_pad));
+            EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, h->RT.p, n_pad, kTile));
+            EGX_RC(launch_row_reduce(st, h->RT.p, n_pad, kTile, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p, h->s0.p, h->sl.p));
+            InfillTrend tr;
+            tr.p = p, tr.rp = rp, tr.msplit = msplit;
+            tr.xqT = h->xqT.p, tr.fidx = reinterpret_cast<const int *>(c.fidx.p), tr.beta = c.beta.p, tr.R = c.R.p, tr.Rt = c.Rt.p;
+            tr.racc = h->racc.p, tr.s0 = h->s0.p, tr.sl = h->sl.p;
+            tr.sigma2 = gp->sigma2, tr.y_mean = gp->y_mean, tr.y_std = gp->y_std;
+            tr.mean = h->mean.p + (size_t)j * M + t0, tr.var = h->var.p + (size_t)j * M + t0;
+            tr.dneg = want_g ? h->dneg.p : nullptr;
+            EGX_RC(launch_infill_trend(st, tr));
+            if (!want_g) continue;
+            // -(R^-1 r + R^-1 F D)^T as an (n_pad x 128) weight matrix: xgrad_impl's two GEMMs, then the two contractions
+            EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * (size_t)n_pad * kTile, st));
+            EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_W, n_pad, h->RT.p, n_pad, n_pad, kTile, n_pad, 0, 1));
+            EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_neg_invkf, rp, h->dneg.p, rp, n_pad, kTile, rp, 0, 0));
+            EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
+                                gp->d_gamma, 0, 1, nsplit, h->out_y.p));
+            EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
+                                h->Wt.p, kTile, 0, nsplit, h->out_v.p));
+            EGX_RC(launch_infill_xgrad_finish(st, tr, d, nsplit, h->out_y.p, h->out_v.p, dev_xnorm(gp) + d,
+                                              h->gmean.p + ((size_t)j * M + t0) * d, h->gvar.p + ((size_t)j * M + t0) * d));
+        }
+    }
+    if (value)
+        EGX_RC(launch_infill_combine(st, h->prm, k, d, m, M, h->mean.p, h->var.p, want_g ? h->gmean.p : nullptr,
+                                     want_g ? h->gvar.p : nullptr, h->d_tol.p, flag, h->value.p, grad ? h->grad.p : nullptr));
+    if (value) EGX_HIP_CHECK(hipMemcpyAsync(value, h->value.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+    if (grad) EGX_HIP_CHECK(hipMemcpyAsync(grad, h->grad.p, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
+    if (parts)
+        for (int j = 0; j < nm; j++) {
+            if (parts->mean)
+                EGX_HIP_CHECK(hipMemcpyAsync(parts->mean + (size_t)j * m, h->mean.p + (size_t)j * M, sizeof(double) * (size_t)m,
+                                             hipMemcpyDeviceToHost, st));
+            if (parts->var)
+                EGX_HIP_CHECK(hipMemcpyAsync(parts->var + (size_t)j * m, h->var.p + (size_t)j * M, sizeof(double) * (size_t)m,
+                                             hipMemcpyDeviceToHost, st));
+            if (parts->grad_mean)
+                EGX_HIP_CHECK(hipMemcpyAsync(parts->grad_mean + (size_t)j * m * d, h->gmean.p + (size_t)j * M * d,
+                                             sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
+            if (parts->grad_var)
+                EGX_HIP_CHECK(hipMemcpyAsync(parts->grad_var + (size_t)j * m * d, h->gvar.p + (size_t)j * M * d,
+                                             sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
+        }
+    EGX_HIP_CHECK(hipStreamSynchronize(st));
+    return EGX_SUCCESS;
+}
+
+int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts) {
+    const int rc = eval_locked(h, xq, m, value, grad, parts);
+    if (rc) {  // nothing may still run on the handle's buffers
+        (void)hipStreamSynchronize(h->models[0]->ws[0].stream);
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
+bool params_ok(double fmin, double sigma_weight, double scale_ic, double scale) {
+    if (std::isnan(fmin) || !(sigma_weight > 0.0) || std::isnan(scale_ic) || !(scale > 0.0) || std::isinf(scale)) {
+        set_error("infill: fmin and scale_ic must not be NaN, sigma_weight and scale must be positive and finite");
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+void egx_infill_config_default(egx_infill_config *cfg) {
+    if (!cfg) return;
+    cfg->criterion = EGX_INFILL_LOG_EI;
+    cfg->feasibility = 1;
+    cfg->fmin = 0.0;
+    cfg->sigma_weight = 1.0;
+    cfg->scale_ic = 1.0;
+    cfg->scale = 1.0;
+}
+
+int32_t egx_infill_create(const egx_infill_config *cfg_in, egx_gp *obj_model, egx_gp *const *cstr_models, const double *cstr_tols,
+                          int32_t n_cstr, egx_infill **out) {
+    if (!out) {
+        set_error("out handle pointer is NULL");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    *out = nullptr;
+    egx_infill_config cfg;
+    if (cfg_in) cfg = *cfg_in; else egx_infill_config_default(&cfg);
+    if (!obj_model || n_cstr < 0 || (n_cstr > 0 && (!cstr_models || !cstr_tols))) {
+        set_error("infill: NULL model or tolerance array");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (cfg.criterion < EGX_INFILL_EI || cfg.criterion > EGX_INFILL_WB2S) {
+        set_error("infill: unknown criterion");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (!params_ok(cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale)) return EGX_ERR_INVALID_VALUE;
+    std::unique_ptr<egx_infill> h(new egx_infill);
+    h->models.push_back(obj_model);
+    for (int j = 0; j < n_cstr; j++) {
+        if (!cstr_models[j]) {
+            set_error("infill: model " + std::to_string(j + 1) + " is NULL");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (std::isnan(cstr_tols[j])) {
+            set_error("infill: tolerance " + std::to_string(j) + " is NaN");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        h->models.push_back(cstr_models[j]);
+        h->tol.push_back(cstr_tols[j]);
+    }
+    h->d = obj_model->d;
+    h->device = obj_model->device;
+    for (size_t j = 1; j < h->models.size(); j++) {
+        if (h->models[j]->d != h->d) {
+            set_error("infill: model " + std::to_string(j) + " has " + std::to_string(h->models[j]->d) + " inputs, model 0 has " +
+                      std::to_string(h->d));
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (h->models[j]->device != h->device) {
+            set_error("infill: model " + std::to_string(j) + " lives on device " + std::to_string(h->models[j]->device) +
+                      ", model 0 on device " + std::to_string(h->device));
+            return EGX_ERR_INVALID_VALUE;
+        }
+    }
+    for (size_t j = 0; j < h->models.size(); j++)
+        if (!h->models[j]->fitted) {
+            set_error("infill: model " + std::to_string(j) + " is not fitted (call egx_gp_finalize or egx_gp_fit first)");
+            return EGX_ERR_NOT_FITTED;
+        }
+    h->cache.reset(new ModelCache[h->models.size()]);
+    h->prm.kind = cfg.criterion;
+    h->prm.fmin = cfg.fmin;
+    h->prm.sigma_weight = cfg.sigma_weight;
+    h->prm.scale_ic = cfg.scale_ic;
+    h->prm.scale = cfg.scale;
+    h->prm.feasibility = cfg.feasibility != 0;
+    *out = h.release();
+    return EGX_SUCCESS;
+}
+
+void egx_infill_destroy(egx_infill *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+int32_t egx_infill_set_params(egx_infill *h, double fmin, double sigma_weight, double scale_ic, double scale, int32_t feasibility) {
+    if (!h) {
+        set_error("NULL handle");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (!params_ok(fmin, sigma_weight, scale_ic, scale)) return EGX_ERR_INVALID_VALUE;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->prm.fmin = fmin;
+    h->prm.sigma_weight = sigma_weight;
+    h->prm.scale_ic = scale_ic;
+    h->prm.scale = scale;
+    h->prm.feasibility = feasibility != 0;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_get_params(egx_infill *h, egx_infill_config *cfg) {
+    if (!h || !cfg) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    cfg->criterion = h->prm.kind;
+    cfg->feasibility = h->prm.feasibility;
+    cfg->fmin = h->prm.fmin;
+    cfg->sigma_weight = h->prm.sigma_weight;
+    cfg->scale_ic = h->prm.scale_ic;
+    cfg->scale = h->prm.scale;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_eval(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts) {
+    if (!h || (m > 0 && !value)) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    return eval_guarded(h, xq, m, value, grad, parts);
+}
+
+int32_t egx_infill_scaling(egx_infill *h, const double *pts, int64_t npts, double *scale_ic_out, double *scale_out,
+                           double *scale_cstr) {
+    if (!h || npts < 1 || !pts) {
+        set_error("infill scaling: needs a handle and at least one point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    const int nm = (int)h->models.size(), k = nm - 1;
+    // ONE values-only pass over all points (means and variances of every model stay on the device); the criterion's terms are
+    // then formed ON THE DEVICE with the text of k_infill_combine, so that what is stored is bit for bit the largest |value|
+    // egx_infill_eval returns at scale = 1 (all values finite).  The host does the NaN / inf -> 1 replacement, the last
+    // multiplication / subtraction, max and argmax.
+    std::vector<double> mean((size_t)nm * npts);
+    egx_infill_parts parts{mean.data(), nullptr, nullptr, nullptr};
+    EGX_RC(eval_guarded(h, pts, npts, nullptr, nullptr, &parts));
+    hipStream_t st = h->models[0]->ws[0].stream;
+    const int64_t M = round_up(npts, kTile);
+    const int *flag = reinterpret_cast<const int *>(h->flag.p);
+    EGX_RC(h->value.alloc((size_t)2 * M));  // [0, M): ei, then base; [M, 2M): fac
+    infill::Params prm = h->prm;
+    prm.scale = 1.0;
+    prm.feasibility = 1;
+    std::vector<double> base((size_t)npts), fac((size_t)npts);
+    auto fail = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        (void)hipGetLastError();
+        return rc;
+    };
+    double scale_ic = 1.0;
+    if (prm.kind == infill::kWB2S) {  // compute_wb2s_scale, criteria/wb2.rs:67-88 (argmax: the first maximum)
+        int rc = launch_infill_scale_terms(st, prm, k, npts, M, h->mean.p, h->var.p, h->d_tol.p, flag, h->value.p, nullptr, nullptr);
+        if (rc) return fail(rc);
+        if (hipMemcpyAsync(base.data(), h->value.p, sizeof(double) * (size_t)npts, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            set_error("infill scaling: copying the EI values back failed");
+            return fail(EGX_ERR_HIP);
+        }
+        int64_t i_max = 0;
+        for (int64_t i = 1; i < npts; i++)
+            if (base[i] > base[i_max] || std::isnan(base[i_max])) i_max = i;
+        if (std::fabs(base[i_max]) > 100.0 * infill::kEps) scale_ic = 100.0 * std::fabs(mean[i_max]) / base[i_max];
+    }
+    prm.scale_ic = scale_ic;
+    {
+        int rc = launch_infill_scale_terms(st, prm, k, npts, M, h->mean.p, h->var.p, h->d_tol.p, flag, nullptr, h->value.p,
+                                           h->value.p + M);
+        if (rc) return fail(rc);
+        if (hipMemcpyAsync(base.data(), h->value.p, sizeof(double) * (size_t)npts, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(fac.data(), h->value.p + M, sizeof(double) * (size_t)npts, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            set_error("infill scaling: copying the criterion's terms back failed");
+            return fail(EGX_ERR_HIP);
+        }
+    }
+    double scale = 0.0;  // compute_infill_obj_scale, solver_computations.rs:297-351
+    for (int64_t i = 0; i < npts; i++) {
+        double v = base[i];
+        if (std::isnan(v) || std::isinf(v)) v = 1.0;
+        if (k > 0) v = (prm.kind == infill::kLogEI) ? v - fac[i] : v * fac[i];
+        scale = std::fmax(scale, std::fabs(v));
+    }
+    if (scale < 100.0 * infill::kEps || std::isnan(scale) || std::isinf(scale)) scale = 1.0;
+    if (scale_cstr)  // compute_cstr_scales, utils/misc.rs:10-28
+        for (int j = 1; j <= k; j++) {
+            double best = -1.0;
+            for (int64_t i = 0; i < npts; i++) {
+                const double v = mean[(size_t)j * npts + i];
+                if (!std::isinf(v) && std::fabs(v) > best) best = std::fabs(v);
+            }
+            scale_cstr[j - 1] = best < 0.0 ? 1.0 : best;
+        }
+    h->prm.scale_ic = scale_ic;
+    h->prm.scale = scale;
+    if (scale_ic_out) *scale_ic_out = scale_ic;
+    if (scale_out) *scale_out = scale;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_optimize(egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start,
+                            int64_t max_eval, double *f_best, double *x_best, egx_infill_stats *stats) {
+    if (!h || !lo || !hi || !x_start || !f_best || !x_best || n_start < 1) {
+        set_error("infill optimize: NULL argument or no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int d = h->d;
+    for (int i = 0; i < d; i++)
+        if (!(lo[i] <= hi[i]) || std::isinf(lo[i]) || std::isinf(hi[i])) {
+            set_error("infill optimize: bounds must be finite with lo <= hi (coordinate " + std::to_string(i) + ")");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    for (int64_t s = 0; s < n_start; s++)
+        for (int i = 0; i < d; i++)
+            if (!std::isfinite(x_start[s * d + i])) {
+                set_error("infill optimize: start point " + std::to_string(s) + " has a non-finite coordinate");
+                return EGX_ERR_INVALID_VALUE;
+            }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    // one COBYLA per start: rhobeg 0.5, ftol_rel = ftol_abs = 1e-4 (crates/ego/src/optimizers/optimizer.rs:155-167,
+    // solver_infill_optim.rs:222-227), at most min(10 n_start d, 2000) evaluations each (:217-221)
+    if (max_eval <= 0) max_eval = std::min<int64_t>(10 * n_start * d, 2000);
+    const std::vector<double> blo(lo, lo + d), bhi(hi, hi + d);
+    std::vector<CobylaBox> mach;
+    mach.reserve((size_t)n_start);
+    for (int64_t s = 0; s < n_start; s++)
+        mach.emplace_back(std::vector<double>(x_start + s * d, x_start + (s + 1) * d), blo, bhi, 0.5, 1e-4, max_eval, 0.0, true, true,
+                          1e-4);
+    // The best EVALUATED point of every start (the first on ties), kept here and not taken from CobylaBox::best_x(): that is
+    // the pole of the final simplex, re-assembled by additions each time the pole moves, so it need not be bit for bit a point
+    // that was evaluated -- and "f_best is egx_infill_eval at x_best" is part of this call's contract.
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> fb((size_t)n_start, inf), xb((size_t)n_start * d, 0.0);
+    for (int64_t s = 0; s < n_start; s++)
+        for (int i = 0; i < d; i++) xb[s * d + i] = std::fmin(hi[i], std::fmax(lo[i], x_start[s * d + i]));
+    std::vector<double> pts, vals, x;
+    std::vector<size_t> who;
+    int64_t rounds = 0;
+    // all starts in LOCK-STEP: a round's trial points are ONE values-only evaluation
+    for (;;) {
+        pts.clear();
+        who.clear();
+        for (size_t q = 0; q < mach.size(); q++)
+            if (mach[q].ask(x)) {
+                who.push_back(q);
+                pts.insert(pts.end(), x.begin(), x.end());
+            }
+        if (who.empty()) break;
+        vals.assign(who.size(), 0.0);
+        EGX_RC(eval_guarded(h, pts.data(), (int64_t)who.size(), vals.data(), nullptr, nullptr));
+        rounds++;
+        for (size_t q = 0; q < who.size(); q++) {
+            const size_t s = who[q];
+            const double v = vals[q];
+            if (v == v && v < 1e30 && v < fb[s]) {  // beyond COBYLA's barrier a value counts as +inf (optimizer.rs:153-157 style)
+                fb[s] = v;
+                std::copy(pts.begin() + q * d, pts.begin() + (q + 1) * d, xb.begin() + s * d);
+            }
+            mach[s].tell(v);
+        }
+    }
+    int64_t best = 0;
+    for (int64_t s = 1; s < n_start; s++)
+        if (fb[s] < fb[best]) best = s;  // the first wins ties (solver_infill_optim.rs:229-236)
+    *f_best = fb[best];
+    std::copy(xb.begin() + best * d, xb.begin() + (best + 1) * d, x_best);
+    if (stats) {
+        stats->rounds = rounds;
+        stats->best_start = best;
+        if (stats->evals)
+            for (int64_t s = 0; s < n_start; s++) stats->evals[s] = mach[(size_t)s].evals();
+    }
+    if (!std::isfinite(fb[best])) {
+        set_error("infill optimize: no start ended at a finite value");
+        return EGX_ERR_NO_FINITE_START;
+    }
+    return EGX_SUCCESS;
+}
+
+}  // extern "C"

@@ -32,7 +32,6 @@ static int upload_queries(egx_gp *gp, const double *xq, int64_t m0, int m, int m
 }
 
 static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vout);
-static int ensure_winv(egx_gp *gp);
 static int small_path_buffers(egx_gp *gp);
 
 int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout) {
@@ -189,7 +188,7 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
 
 // d_W <- C^-T (upper triangular, rows of the identity through the forward block substitution) and
 // d_neg_invkf <- -C^-T [ft | yt] for the factor resident in workspace 0; cached per fitted state.
-static int ensure_winv(egx_gp *gp) {
+int ensure_winv(egx_gp *gp) {
     if (gp->winv_epoch == gp->fit_epoch && gp->d_W && gp->d_neg_invkf) return EGX_SUCCESS;
     Workspace &w = gp->ws[0];
     const int n_pad = gp->n_pad;

@@ -1,0 +1,262 @@
+// Kernels of the fused infill evaluation (gp_infill.hip): everything predict_impl / xgrad_impl do on the HOST between their
+// launches, per tile of kTile = 128 query points and per model, plus the criterion itself:
+//   k_infill_prepare   raw queries -> normalised k-major tile (algorithm.rs:254), non-finite points flagged and zeroed
+//   k_infill_trend     mean = f beta + sum of the split partial sums (algorithm.rs:260-262); A = f - ft^T rt, Rq^T u = A, Rq D = u,
+//                      var = sigma2 (1 - sum rt^2 + sum u^2) clamped at 0 (:272-278, 352-367); -D zero padded for the GEMM
+//   k_infill_xgrad_finish   reduction of launch_xgrad's split partial sums, the trend Jacobian terms, un-normalisation (:510-727)
+//   k_infill_combine   infill_math.h across the 1 + k models of a point: value and gradient of the minimised objective
+// None of them is matrix-shaped: they are latency-bound tails whose point is to keep the call free of host round trips.
+// Every reduction runs in a fixed order that depends on the model alone, and a workgroup (or thread) owns one point: a point's
+// result does not depend on its position in the tile nor on its companions.
+// The sums that predict_impl / xgrad_impl form on the host -- f beta, the split partial sums, sum u^2, the forward substitution
+// Rq^T u = A, the Jacobian terms; NOT the back substitution Rq D = u, whose updates reach an entry in descending instead of
+// ascending order -- are formed here in the HOST'S ORDER and without FMA contraction (the host build has none): a model whose
+// gamma is large against its predictions -- an ill-conditioned correlation matrix -- amplifies a reordering of the split sums
+// to 1e-5 of the mean, and a caller may compare egx_infill_eval's parts with egx_gp_predict*.
+#include "egx_internal.h"
+#pragma clang fp contract(off)
+#include "infill_math.h"
+
+namespace egx {
+
+constexpr int kInfThreads = 256;
+
+// one thread per point of the tile; xq: the tile's mt <= 128 raw rows (mt x d); par = x_mean (d) | x_std (d)
+__global__ __launch_bounds__(kTile) void k_infill_prepare(const double *__restrict__ xq, int mt, int d,
+                                                          const double *__restrict__ par, double *__restrict__ xqT,
+                                                          int *__restrict__ flag) {
+    const int a = threadIdx.x;
+    int bad = 0;
+    if (a < mt)
+        for (int j = 0; j < d; j++) bad |= !isfinite(xq[(int64_t)a * d + j]);
+    const bool live = a < mt && !bad;
+    for (int j = 0; j < d; j++) xqT[(int64_t)j * kTile + a] = live ? (xq[(int64_t)a * d + j] - par[j]) / par[d + j] : 0.0;
+    if (flag) flag[a] = bad;
+}
+
+struct TrendArgs {
+    int p, rp, msplit, want_d;
+    const double *xqT;    // d x 128 normalised tile
+    const int *fidx;      // 2 p: coordinates of regression column l (-1: 1.0)
+    const double *beta;   // p
+    const double *R;      // Rq (p x p row-major, upper)
+    const double *Rt;     // Rq^T (p x p row-major)
+    const double *racc;   // msplit x 128 partial sums r . gamma
+    const double *s0;     // 128: sum rt^2
+    const double *sl;     // 128 x p: ft^T rt
+    double sigma2, y_mean, y_std;
+    double *mean, *var;   // 128 each (this tile of this model)
+    double *dneg;         // 128 x rp: -D, zero padded (want_d)
+};
+
+// One workgroup per point (p reaches 561 for the quadratic trend at d = 32: Rq is streamed from L2 row by row).
+// LDS: s[p] (A, then u, then D), diag[p], prod[p] (f_l beta_l), part[msplit]; thread 0 adds them in predict_impl's order.
+__global__ __launch_bounds__(kInfThreads) void k_infill_trend(TrendArgs g) {
+    extern __shared__ double lds[];
+    const int p = g.p, a = blockIdx.x, t = threadIdx.x;
+    double *s = lds, *diag = lds + p, *prod = lds + 2 * p, *part = lds + 3 * p;
+    for (int l = t; l < p; l += kInfThreads) {
+        const int ia = g.fidx[2 * l], ib = g.fidx[2 * l + 1];
+        const double fa = ia < 0 ? 1.0 : g.xqT[(int64_t)ia * kTile + a];
+        const double f = ib < 0 ? fa : g.xqT[(int64_t)ib * kTile + a] * fa;
+        prod[l] = f * g.beta[l];
+        s[l] = f - g.sl[(int64_t)a * p + l];
+        diag[l] = g.R[(int64_t)l * p + l];
+    }
+    for (int sp = t; sp < g.msplit; sp += kInfThreads) part[sp] = g.racc[(int64_t)sp * kTile + a];
+    __syncthreads();
+    if (t == 0) {
+        double fb = 0.0, rg = 0.0;
+        for (int l = 0; l < p; l++) fb += prod[l];
+        for (int sp = 0; sp < g.msplit; sp++) rg += part[sp];
+        g.mean[a] = (fb + rg) * g.y_std + g.y_mean;
+    }
+    // Rq^T u = A: column by column (row i of Rq is contiguous); every s_j receives its subtractions in the order l = 0, 1, ...
+    for (int i = 0; i < p; i++) {
+        const double ui = s[i] / diag[i];
+        __syncthreads();  // every thread has read s[i]
+        if (t == 0) s[i] = ui;
+        for (int j = i + 1 + t; j < p; j += kInfThreads) s[j] -= g.R[(int64_t)i * p + j] * ui;
+        __syncthreads();
+    }
+    if (t == 0) {
+        double usq = 0.0;
+        for (int l = 0; l < p; l++) usq += s[l] * s[l];
+        const double mse = g.sigma2 * (1.0 - g.s0[a] + usq);
+        g.var[a] = mse < 0.0 ? 0.0 : mse;
+    }
+    if (!g.want_d) return;
+    __syncthreads();
+    // Rq D = u: from the last row up, column i of Rq is row i of Rq^T
+    for (int i = p - 1; i >= 0; i--) {
+        const double di = s[i] / diag[i];
+        __syncthreads();
+        if (t == 0) s[i] = di;
+        for (int j = t; j < i; j += kInfThreads) s[j] -= g.Rt[(int64_t)i * p + j] * di;
+        __syncthreads();
+    }
+    for (int l = t; l < g.rp; l += kInfThreads) g.dneg[(int64_t)a * g.rp + l] = l < p ? -s[l] : 0.0;
+}
+
+struct XgFinishArgs {
+    int d, p, rp, nsplit;
+    const double *xqT;
+    const int *fidx;
+    const double *beta;
+    const double *dneg;     // 128 x rp (-D)
+    const double *out_y;    // nsplit x 128 x d partial sums of the mean contraction
+    const double *out_v;    // ... of the variance contraction
+    const double *x_std;    // d
+    double sigma2, y_std;
+    double *gmean, *gvar;   // 128 x d each (this tile of this model)
+};
+
+// sum_l v_l d f_l / d x_k at the point's normalised coordinates (host_math.h regression_jac_dot); sign * v[l * 1]
+__device__ inline double jac_dot(const XgFinishArgs &g, int a, int k, const double *v, double sign) {
+    double acc = 0.0;
+    for (int l = 1; l < g.p; l++) {
+        const int ia = g.fidx[2 * l], ib = g.fidx[2 * l + 1];
+        if (ib < 0) {
+            if (ia == k) acc += sign * v[l];
+        } else {
+            if (ia == k) acc += sign * v[l] * g.xqT[(int64_t)ib * kTile + a];
+            if (ib == k) acc += sign * v[l] * g.xqT[(int64_t)ia * kTile + a];
+        }
+    }
+    return acc;
+}
+
+// One workgroup per point.  The partial sums of kc = kXgStage / nsplit coordinates at a time are staged in LDS by all threads;
+// thread kk then adds the splits of its coordinate in order (xgrad_impl's reduce_out).
+constexpr int kXgStage = 2048;
+__global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish(XgFinishArgs g) {
+    __shared__ double st_y[kXgStage], st_v[kXgStage];
+    const int a = blockIdx.x, t = threadIdx.x, d = g.d, ns = g.nsplit;
+    int kc = kXgStage / ns;
+    if (kc > kInfThreads) kc = kInfThreads;
+    for (int k0 = 0; k0 < d; k0 += kc) {
+        const int kn = d - k0 < kc ? d - k0 : kc;
+        __syncthreads();
+        for (int e = t; e < ns * kn; e += kInfThreads) {
+            const int sp = e / kn, kk = e - sp * kn;
+            const int64_t o = ((int64_t)sp * kTile + a) * d + k0 + kk;
+            st_y[kk * ns + sp] = g.out_y[o];
+            st_v[kk * ns + sp] = g.out_v[o];
+        }
+        __syncthreads();
+        if (t < kn) {
+            const int k = k0 + t;
+            double sy = 0.0, sv = 0.0;
+            for (int sp = 0; sp < ns; sp++) {
+                sy += st_y[t * ns + sp];
+                sv += st_v[t * ns + sp];
+            }
+            const double dfy = jac_dot(g, a, k, g.beta, 1.0);
+            const double dfv = jac_dot(g, a, k, g.dneg + (int64_t)a * g.rp, -1.0);
+            g.gmean[(int64_t)a * d + k] = (dfy + sy) * g.y_std / g.x_std[k];
+            g.gvar[(int64_t)a * d + k] = 2.0 * g.sigma2 * (dfv + sv) / g.x_std[k];
+        }
+    }
+}
+
+// one thread per point of the call; model j of point i at j * mstride + i (mean, var) and (j * mstride + i) * d (gradients)
+__global__ __launch_bounds__(kInfThreads) void k_infill_combine(infill::Params prm, int k, int d, int64_t m, int64_t mstride,
+                                                               const double *__restrict__ mean, const double *__restrict__ var,
+                                                               const double *__restrict__ gmean, const double *__restrict__ gvar,
+                                                               const double *__restrict__ tol, const int *__restrict__ flag,
+                                                               double *__restrict__ value, double *__restrict__ grad) {
+    const int64_t i = (int64_t)blockIdx.x * kInfThreads + threadIdx.x;
+    if (i >= m) return;
+    if (flag[i]) {  // NaN in the point: +inf, gradient 0 (solver_infill_optim.rs:87-90)
+        value[i] = INFINITY;
+        if (grad)
+            for (int c = 0; c < d; c++) grad[i * d + c] = 0.0;
+        return;
+    }
+    value[i] = infill::objective(prm, k, mean + i, var + i, mstride, tol);
+    if (grad)
+        infill::objective_grad(prm, k, d, mean + i, var + i, mstride, gmean + i * d, gvar + i * d, mstride * d, tol, grad + i * d, 1);
+}
+
+// The terms of the scaling pass (egx_infill_scaling), one thread per point, with the text k_infill_combine runs:
+//   ei[i]   EI(x_i) at the handle's fmin and sigma_weight (compute_wb2s_scale)                      -- when ei != nullptr
+//   base[i] the objective WITHOUT the feasibility factor, fac[i] that factor (pofs, or logpofs for LogEI; 1 / 0 without
+//           constraint models): the host replaces a NaN / infinite base by 1 and forms base * fac or base - fac, the one
+//           IEEE operation infill::objective ends with                                              -- when base != nullptr
+// A flagged (non-finite) point has base = +inf and the neutral factor.
+__global__ __launch_bounds__(kInfThreads) void k_infill_scale_terms(infill::Params prm, int k, int64_t m, int64_t mstride,
+                                                                   const double *__restrict__ mean, const double *__restrict__ var,
+                                                                   const double *__restrict__ tol, const int *__restrict__ flag,
+                                                                   double *__restrict__ ei, double *__restrict__ base,
+                                                                   double *__restrict__ fac) {
+    const int64_t i = (int64_t)blockIdx.x * kInfThreads + threadIdx.x;
+    if (i >= m) return;
+    const bool is_log = prm.kind == infill::kLogEI;
+    const bool bad = flag[i] != 0;
+    if (ei) ei[i] = bad ? 0.0 : infill::ei_value(mean[i], var[i], prm.fmin, prm.sigma_weight);
+    if (base) {
+        base[i] = bad ? INFINITY : infill::objective(prm, 0, mean + i, var + i, mstride, tol);
+        if (k == 0 || bad)
+            fac[i] = is_log ? 0.0 : 1.0;
+        else
+            fac[i] = is_log ? infill::logpofs(k, mean + i, var + i, mstride, tol) : infill::pofs(k, mean + i, var + i, mstride, tol);
+    }
+}
+
+int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, int64_t m, int64_t mstride, const double *mean,
+                              const double *var, const double *tol, const int *flag, double *ei, double *base, double *fac) {
+    if (m <= 0) return EGX_SUCCESS;
+    hipLaunchKernelGGL(k_infill_scale_terms, dim3((unsigned)((m + kInfThreads - 1) / kInfThreads)), dim3(kInfThreads), 0, s, prm, k,
+                       m, mstride, mean, var, tol, flag, ei, base, fac);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag) {
+    hipLaunchKernelGGL(k_infill_prepare, dim3(1), dim3(kTile), 0, s, xq, mt, d, par, xqT, flag);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_trend(hipStream_t s, const InfillTrend &t) {
+    const size_t lds = sizeof(double) * ((size_t)3 * t.p + (size_t)t.msplit);
+    if (lds > 65536) {
+        set_error("infill: more than 2560 regression columns");
+        return EGX_ERR_UNSUPPORTED;
+    }
+    TrendArgs g;
+    g.p = t.p, g.rp = t.rp, g.msplit = t.msplit, g.want_d = t.dneg != nullptr;
+    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.R = t.R, g.Rt = t.Rt, g.racc = t.racc, g.s0 = t.s0, g.sl = t.sl;
+    g.sigma2 = t.sigma2, g.y_mean = t.y_mean, g.y_std = t.y_std;
+    g.mean = t.mean, g.var = t.var, g.dneg = t.dneg;
+    hipLaunchKernelGGL(k_infill_trend, dim3(kTile), dim3(kInfThreads), lds, s, g);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *out_v,
+                               const double *x_std, double *gmean, double *gvar) {
+    XgFinishArgs g;
+    if (nsplit < 1 || nsplit > kXgStage) {
+        set_error("infill: split count of the x-gradient contraction out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    g.d = d, g.p = t.p, g.rp = t.rp, g.nsplit = nsplit;
+    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.dneg = t.dneg, g.out_y = out_y, g.out_v = out_v, g.x_std = x_std;
+    g.sigma2 = t.sigma2, g.y_std = t.y_std, g.gmean = gmean, g.gvar = gvar;
+    hipLaunchKernelGGL(k_infill_xgrad_finish, dim3(kTile), dim3(kInfThreads), 0, s, g);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_combine(hipStream_t s, const infill::Params &prm, int k, int d, int64_t m, int64_t mstride, const double *mean,
+                          const double *var, const double *gmean, const double *gvar, const double *tol, const int *flag,
+                          double *value, double *grad) {
+    if (m <= 0) return EGX_SUCCESS;
+    hipLaunchKernelGGL(k_infill_combine, dim3((unsigned)((m + kInfThreads - 1) / kInfThreads)), dim3(kInfThreads), 0, s, prm, k, d,
+                       m, mstride, mean, var, gmean, gvar, tol, flag, value, grad);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+}  // namespace egx

@@ -1,0 +1,154 @@
+"""EGO's infill criterion on fitted models (include/egx_gp.h `egx_infill_*`; crates/ego/src/criteria, utils/cstr_pof.rs,
+solver/solver_computations.rs:132-193, 297-475, solver/solver_infill_optim.rs:148-236): the objective the infill optimiser
+minimises and its x-gradient for many points per call, the scaling pass and the lock-step COBYLA multistart."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+
+#: criterion constants (egx_infill_criterion)
+EI, LOG_EI, WB2, WB2S = 0, 1, 2, 3
+
+
+def _gp_handle(model):
+    """The `GpHandle` behind a GpHandle, a GaussianProcess or a single-expert Gpx."""
+    from .gp import GaussianProcess, GpHandle
+    from .gpx import Gpx
+    if isinstance(model, Gpx):
+        if len(model._experts) != 1:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, "infill: mixtures with more than one cluster are not supported")
+        model = model._experts[0]
+    if isinstance(model, GaussianProcess):
+        model = model.handle
+    if not isinstance(model, GpHandle):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: expected a GpHandle, GaussianProcess or Gpx, got {type(model).__name__}")
+    return model
+
+
+class InfillObjective:
+    """`egx_infill`: one objective model, k >= 0 constraint models (kept alive by this object), a criterion and its parameters.
+
+    value / gradient are those of the MINIMISED objective: -crit / scale, times the probability of feasibility of the
+    constraint models (EI, WB2, WB2S) or minus its logarithm (LOG_EI)."""
+
+    def __init__(self, obj_model, cstr_models=(), cstr_tols=(), criterion=LOG_EI, fmin=0.0, sigma_weight=1.0, feasibility=True,
+                 scale_ic=1.0, scale=1.0):
+        lib = L.load()
+        self._lib = lib
+        self._models = [_gp_handle(obj_model)] + [_gp_handle(m) for m in cstr_models]
+        self._owners = (obj_model, tuple(cstr_models))
+        tols = L.as_f64(np.atleast_1d(np.asarray(cstr_tols, dtype=np.float64)) if len(cstr_models) else np.zeros(0), 1)
+        k = len(self._models) - 1
+        if tols.shape[0] != k:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: {k} constraint models but {tols.shape[0]} tolerances")
+        cfg = L.InfillConfig()
+        lib.egx_infill_config_default(C.byref(cfg))
+        cfg.criterion, cfg.feasibility = int(criterion), int(bool(feasibility))
+        cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale = float(fmin), float(sigma_weight), float(scale_ic), float(scale)
+        arr = (C.c_void_p * max(k, 1))(*[m._h.value for m in self._models[1:]])
+        self._h = C.c_void_p()
+        L.check(lib.egx_infill_create(C.byref(cfg), self._models[0]._h, arr if k else None, L.dptr(tols) if k else None, k,
+                                      C.byref(self._h)))
+        self.d, self.n_cstr, self.criterion = self._models[0].d, k, int(criterion)
+
+    # ---- parameters ----------------------------------------------------------------------------------------------------
+    @property
+    def params(self):
+        cfg = L.InfillConfig()
+        L.check(self._lib.egx_infill_get_params(self._h, C.byref(cfg)))
+        return dict(fmin=cfg.fmin, sigma_weight=cfg.sigma_weight, scale_ic=cfg.scale_ic, scale=cfg.scale,
+                    feasibility=bool(cfg.feasibility))
+
+    def set_params(self, fmin=None, sigma_weight=None, scale_ic=None, scale=None, feasibility=None):
+        """Change parameters between EGO iterations (None keeps the current value)."""
+        p = self.params
+        new = dict(fmin=fmin, sigma_weight=sigma_weight, scale_ic=scale_ic, scale=scale, feasibility=feasibility)
+        p.update({k: v for k, v in new.items() if v is not None})
+        L.check(self._lib.egx_infill_set_params(self._h, float(p["fmin"]), float(p["sigma_weight"]), float(p["scale_ic"]),
+                                                float(p["scale"]), int(bool(p["feasibility"]))))
+
+    # ---- evaluation ----------------------------------------------------------------------------------------------------
+    def _points(self, x):
+        x = L.as_f64(x)
+        if x.ndim == 1:
+            x = x.reshape(1, -1) if self.d > 1 or x.shape[0] == 1 else x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: points must be (m, {self.d}), got {x.shape}")
+        return np.ascontiguousarray(x)
+
+    def _eval(self, x, want_grad, want_parts):
+        x = self._points(x)
+        m, d, nm = x.shape[0], self.d, 1 + self.n_cstr
+        value = np.empty(m)
+        grad = np.empty((m, d)) if want_grad else None
+        parts, pstruct = None, None
+        if want_parts:
+            parts = dict(mean=np.empty((nm, m)), var=np.empty((nm, m)), grad_mean=np.empty((nm, m, d)), grad_var=np.empty((nm, m, d)))
+            pstruct = L.InfillParts(*[L.dptr(parts[k]) for k in ("mean", "var", "grad_mean", "grad_var")])
+        L.check(self._lib.egx_infill_eval(self._h, L.dptr(x), m, L.dptr(value), L.dptr(grad) if want_grad else None,
+                                          C.byref(pstruct) if want_parts else None))
+        return value, grad, parts
+
+    def value(self, x):
+        """(m,) values of the minimised objective at x (m, d); no gradient work."""
+        return self._eval(x, False, False)[0]
+
+    def value_and_grad(self, x):
+        """((m,), (m, d)): the minimised objective and its x-gradient; the values are bit for bit those of `value`."""
+        v, g, _ = self._eval(x, True, False)
+        return v, g
+
+    def parts(self, x):
+        """What the criterion is computed from, model-major (model 0 = objective): dict of mean (1 + k, m), var (1 + k, m),
+        grad_mean (1 + k, m, d), grad_var (1 + k, m, d), plus value (m,) and grad (m, d)."""
+        v, g, p = self._eval(x, True, True)
+        p["value"], p["grad"] = v, g
+        return p
+
+    def scaling(self, points):
+        """compute_scaling (solver_computations.rs:132-193) on `points` (npts, d): returns (scale_ic, scale, scale_cstr) and
+        stores scale_ic and scale in the object."""
+        x = self._points(points)
+        sic, sc = C.c_double(), C.c_double()
+        scs = np.empty(max(self.n_cstr, 1))
+        L.check(self._lib.egx_infill_scaling(self._h, L.dptr(x), x.shape[0], C.byref(sic), C.byref(sc), L.dptr(scs)))
+        return sic.value, sc.value, scs[:self.n_cstr].copy()
+
+    def optimize(self, xlimits, x_start, max_eval=None):
+        """The bound-constrained multistart (solver_infill_optim.rs:148-236): one COBYLA per row of x_start (n_start, d) inside
+        xlimits (d, 2), all starts in lock-step.  Returns (f, x, stats); f = +inf when no start ended at a finite value."""
+        lim = L.as_f64(xlimits, 2)
+        if lim.shape != (self.d, 2):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
+        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+        xs = self._points(x_start)
+        n_start = xs.shape[0]
+        f, xb = C.c_double(), np.empty(self.d)
+        evals = np.zeros(n_start, dtype=np.int64)
+        st = L.InfillStats(0, 0, evals.ctypes.data_as(L.c_int64_p))
+        rc = self._lib.egx_infill_optimize(self._h, L.dptr(lo), L.dptr(hi), L.dptr(xs), n_start,
+                                           0 if max_eval is None else int(max_eval), C.byref(f), L.dptr(xb), C.byref(st))
+        if rc != L.ERR_NO_FINITE_START:
+            L.check(rc)
+        stats = dict(evals=evals, rounds=int(st.rounds), best_start=int(st.best_start), finite=rc == L.SUCCESS)
+        return f.value, xb, stats
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.egx_infill_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -49,7 +49,8 @@ typedef enum {
     EGX_ERR_LINALG = 5,        /* GpError::LinalgError (not positive definite), errors.rs:19 */
     EGX_ERR_LIKELIHOOD = 6,    /* GpError::LikelihoodComputationError, errors.rs:12 */
     EGX_ERR_UNSUPPORTED = 7,
-    EGX_ERR_PEER = 8           /* collective calls: another rank failed, or did not answer in time */
+    EGX_ERR_PEER = 8,          /* collective calls: another rank failed, or did not answer in time */
+    EGX_ERR_NO_FINITE_START = 9 /* egx_infill_optimize: no start ended at a finite value (*f_best = +inf) */
 } egx_rc;
 
 /* per-evaluation status (the value channel) */
@@ -549,6 +550,81 @@ int32_t egx_sgp_sample(egx_sgp *sgp, const double *xq, int64_t m, int64_t n_traj
 /* fitted state: theta (d), sigma2, noise, likelihood, WoodburyData vec (nz) and inv (nz*nz) :32-36; NULL = skip */
 int32_t egx_sgp_get_state(egx_sgp *sgp, double *theta, double *sigma2, double *noise, double *likelihood,
                           double *w_vec, double *w_inv);
+
+/* ---- EGO's infill criterion on fitted models -------------------------------------------------------------------------
+ * What EGO asks of its surrogates, "where next?" (crates/ego/src): the objective its infill optimiser MINIMISES,
+ *   obj(x) = -crit(x) / scale                    crit: criteria/ei.rs:22-170 (EI, LogEI), criteria/wb2.rs:21-49 (WB2, WB2S)
+ *   obj(x) * pofs(x)  (EI, WB2, WB2S)  or  obj(x) - logpofs(x)  (LogEI)   with constraint models (cstr_infill = true):
+ *                                                utils/cstr_pof.rs, solver/solver_computations.rs:356-475
+ * and its x-gradient, for m points per call, from ONE objective model and n_cstr >= 0 constraint models (dense GPs, all
+ * fitted, same d, same device; n may differ).  The models are BORROWED: they must outlive the handle, and a call always reads
+ * their CURRENT fitted state.  feasibility == 0 replaces obj by -1 (0 for LogEI) and its gradient by 0 (:410-416, 441-466).
+ * The reference evaluates this one point at a time with 2 (1 + n_cstr) predict calls per evaluation; here a call is one
+ * upload, one launch sequence per 128-point tile and model, one synchronisation, and nothing is computed on the host.
+ *
+ * A point's results do not depend on its companions: value[i], grad[i, :] and the parts of point i are bit for bit the same
+ * whether the point is evaluated alone, at another position, or among others; value is bit for bit the same with and
+ * without grad.
+ *
+ * Three DEVIATIONS from the reference (egobox_amd/csrc/infill_math.h):
+ *   1. log_ei_helper (utils/logei_helper.rs) is exact on the whole line: below u = -20 the asymptotic series replaces
+ *      exp(z^2) erfc(z), which leaves double range near u = -37.6 in the reference (wrong or NaN down to u = -1e6).
+ *   2. pof_grad (cstr_pof.rs:42-43) is the derivative of Phi((tol - mu) / sigma) for every tol, not only for tol = 0.
+ *   3. the gradient uses the same sigma_weight as the value (solver_computations.rs:387-391 passes None).
+ * NaN in a point: value = +inf, gradient 0, for that point only (solver_infill_optim.rs:87-90).  m = 0 succeeds. */
+typedef struct egx_infill egx_infill;
+typedef enum { EGX_INFILL_EI = 0, EGX_INFILL_LOG_EI = 1, EGX_INFILL_WB2 = 2, EGX_INFILL_WB2S = 3 } egx_infill_criterion;
+typedef struct {
+    int32_t criterion;   /* egx_infill_criterion; default EGX_INFILL_LOG_EI */
+    int32_t feasibility; /* 0: no feasible point known yet (see above); default 1 */
+    double fmin;         /* current best objective value */
+    double sigma_weight; /* k in sigma_k = k sqrt(var) (EI, WB2, WB2S; LogEI ignores it, as the reference); default 1 */
+    double scale_ic;     /* WB2S's factor on EI (wb2.rs:29); ignored by the other criteria; default 1 */
+    double scale;        /* obj = -crit / scale; default 1 */
+} egx_infill_config;
+void egx_infill_config_default(egx_infill_config *cfg);
+/* EGX_ERR_INVALID_VALUE naming the model's index (0 = objective, 1.. = constraints) when d or the device differ;
+ * EGX_ERR_NOT_FITTED when a model is not fitted (here and in every later call). */
+int32_t egx_infill_create(const egx_infill_config *cfg, egx_gp *obj_model, egx_gp *const *cstr_models /*n_cstr*/,
+                          const double *cstr_tols /*n_cstr*/, int32_t n_cstr, egx_infill **out);
+void egx_infill_destroy(egx_infill *h);
+/* between EGO iterations, without rebuilding the handle */
+int32_t egx_infill_set_params(egx_infill *h, double fmin, double sigma_weight, double scale_ic, double scale,
+                              int32_t feasibility);
+int32_t egx_infill_get_params(egx_infill *h, egx_infill_config *cfg);
+/* what the criterion was computed FROM, model-major (model 0 = objective): any pointer may be NULL (skipped) */
+typedef struct {
+    double *mean;      /* (1 + n_cstr) * m     */
+    double *var;       /* (1 + n_cstr) * m     */
+    double *grad_mean; /* (1 + n_cstr) * m * d */
+    double *grad_var;  /* (1 + n_cstr) * m * d */
+} egx_infill_parts;
+/* xq (m x d) in ORIGINAL units.  grad == NULL skips the gradient work (unless parts asks for gradients); the cached C^-T
+ * the gradients need is built on the first gradient call after a fit -- values need the factor alone. */
+int32_t egx_infill_eval(egx_infill *h, const double *xq, int64_t m, double *value /*m*/, double *grad /*m*d or NULL*/,
+                        const egx_infill_parts *parts /*or NULL*/);
+/* compute_scaling (solver_computations.rs:132-193) on the caller's points (the reference draws min(100 d, 1000) LHS points):
+ * scale_ic = compute_wb2s_scale (wb2.rs:67-88; 1 unless the criterion is WB2S), scale = compute_infill_obj_scale (:297-351),
+ * scale_cstr[j] = compute_cstr_scales (utils/misc.rs:10-28; may be NULL).  One values-only pass over the points.  The criterion's
+ * terms are formed on the device with the text of egx_infill_eval: scale is bit for bit the largest |value| egx_infill_eval
+ * returns for these points at scale = 1 (a NaN / infinite objective counting as 1.0 before the feasibility factor).  scale_ic
+ * and scale are stored in the handle and returned (either pointer may be NULL). */
+int32_t egx_infill_scaling(egx_infill *h, const double *pts /*npts*d*/, int64_t npts, double *scale_ic, double *scale,
+                           double *scale_cstr /*n_cstr or NULL*/);
+/* The bound-constrained multistart of solver_infill_optim.rs:148-236 (no constraint models, or cstr_infill = true): one
+ * COBYLA per start (rhobeg 0.5, ftol_rel = ftol_abs = 1e-4, at most max_eval evaluations each; max_eval <= 0:
+ * min(10 n_start d, 2000)), all starts advanced in LOCK-STEP -- a round's trial points are one values-only evaluation, and
+ * every start walks bit for bit the points it walks alone.  Returns the best EVALUATED point over all starts (the first start
+ * wins ties): *f_best is bit for bit egx_infill_eval at x_best.  Values at or beyond 1e30 (COBYLA's barrier; LogEI's f64::MAX at
+ * a point of zero variance) count as +inf.  No start finite: *f_best = +inf, x_best = start 0 clamped into the box, and
+ * EGX_ERR_NO_FINITE_START.  NaN / infinite start rows or bounds, lo > hi: EGX_ERR_INVALID_VALUE. */
+typedef struct {
+    int64_t rounds;     /* lock-step rounds = evaluations of the start that ran longest */
+    int64_t best_start; /* index of the start that won */
+    int64_t *evals;     /* n_start evaluation counts, or NULL */
+} egx_infill_stats;
+int32_t egx_infill_optimize(egx_infill *h, const double *lo /*d*/, const double *hi /*d*/, const double *x_start /*n_start*d*/,
+                            int64_t n_start, int64_t max_eval, double *f_best, double *x_best /*d*/, egx_infill_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -478,6 +478,86 @@ inline std::pair<std::vector<double>, std::vector<double>> moe_predict_valvar_gr
     return {std::move(gy), std::move(gv)};
 }
 
+// EGO's infill criterion on fitted models (egx_infill_*, egx_gp.h): the objective the infill optimiser minimises and its
+// x-gradient for m points per call (crates/ego/src/criteria, utils/cstr_pof.rs, solver/solver_computations.rs:356-475), the
+// scaling pass (:132-193) and the lock-step multistart (solver_infill_optim.rs:148-236).  The models are borrowed and must
+// outlive the object.
+class InfillObjective {
+  public:
+    InfillObjective(const GaussianProcess &obj_model, const std::vector<const GaussianProcess *> &cstr_models,
+                    const std::vector<double> &cstr_tols, egx_infill_criterion criterion, double fmin, double sigma_weight = 1.0,
+                    bool feasibility = true) {
+        if (cstr_models.size() != cstr_tols.size())
+            throw InvalidValueError(EGX_ERR_INVALID_VALUE, "InfillObjective: one tolerance per constraint model");
+        egx_infill_config cfg;
+        egx_infill_config_default(&cfg);
+        cfg.criterion = criterion;
+        cfg.fmin = fmin;
+        cfg.sigma_weight = sigma_weight;
+        cfg.feasibility = feasibility ? 1 : 0;
+        std::vector<egx_gp *> hs;
+        for (const GaussianProcess *m : cstr_models) hs.push_back(m->handle());
+        egx_infill *raw = nullptr;
+        check(egx_infill_create(&cfg, obj_model.handle(), hs.data(), cstr_tols.data(), (int32_t)hs.size(), &raw));
+        h_.reset(raw);
+        d_ = obj_model.dims().first;
+        k_ = (int64_t)hs.size();
+    }
+    // InfillCriterion::value through eval_infill_obj_with_cstrs: (m) values of the minimised objective
+    std::vector<double> value(const double *x, int64_t m) const {
+        std::vector<double> v((size_t)m);
+        check(egx_infill_eval(h_.get(), x, m, v.data(), nullptr, nullptr));
+        return v;
+    }
+    // ... and eval_grad_infill_obj_with_cstrs: (m) values, (m x d) gradients
+    std::pair<std::vector<double>, std::vector<double>> value_and_grad(const double *x, int64_t m) const {
+        std::vector<double> v((size_t)m), g((size_t)(m * d_));
+        check(egx_infill_eval(h_.get(), x, m, v.data(), g.data(), nullptr));
+        return {std::move(v), std::move(g)};
+    }
+    struct Scaling {
+        double scale_ic = 1.0, scale = 1.0;
+        std::vector<double> scale_cstr;
+    };
+    Scaling scaling(const double *pts, int64_t npts) {  // compute_scaling; scale_ic and scale are stored in the object
+        Scaling s;
+        s.scale_cstr.assign((size_t)(k_ > 0 ? k_ : 1), 0.0);
+        check(egx_infill_scaling(h_.get(), pts, npts, &s.scale_ic, &s.scale, s.scale_cstr.data()));
+        s.scale_cstr.resize((size_t)k_);
+        return s;
+    }
+    void set_params(double fmin, double sigma_weight, double scale_ic, double scale, bool feasibility) {
+        check(egx_infill_set_params(h_.get(), fmin, sigma_weight, scale_ic, scale, feasibility ? 1 : 0));
+    }
+    struct Optimum {
+        double f = 0.0;
+        std::vector<double> x;
+        std::vector<int64_t> evals;
+        int64_t rounds = 0, best_start = 0;
+        bool finite = true;  // false: no start ended at a finite value (f = +inf)
+    };
+    Optimum optimize(const double *lo, const double *hi, const double *x_start, int64_t n_start, int64_t max_eval = 0) {
+        Optimum o;
+        o.x.assign((size_t)d_, 0.0);
+        o.evals.assign((size_t)n_start, 0);
+        egx_infill_stats st{0, 0, o.evals.data()};
+        const int32_t rc = egx_infill_optimize(h_.get(), lo, hi, x_start, n_start, max_eval, &o.f, o.x.data(), &st);
+        if (rc != EGX_ERR_NO_FINITE_START) check(rc);
+        o.finite = rc == EGX_SUCCESS;
+        o.rounds = st.rounds;
+        o.best_start = st.best_start;
+        return o;
+    }
+    egx_infill *handle() const { return h_.get(); }
+
+  private:
+    struct Deleter {
+        void operator()(egx_infill *p) const { egx_infill_destroy(p); }
+    };
+    std::unique_ptr<egx_infill, Deleter> h_;
+    int64_t d_ = 0, k_ = 0;
+};
+
 // device resources destroyed models left in the library's pool (a model of the same shape created next reuses them)
 inline int64_t trim() { return egx_trim(); }  // bytes freed
 struct PoolStats { int64_t cached_bytes = 0, hits = 0, misses = 0; };

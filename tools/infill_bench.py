@@ -1,0 +1,139 @@
+"""A/B of one infill evaluation: COMPOSED (what a caller does without egx_infill_*: predict_valvar + predict_valvar_gradients
+per model, the criterion's arithmetic on the host with tests/infill_oracle.py) against FUSED (egx_infill_eval).  The composed
+leg uses only entry points that exist without this feature, so it is the yardstick on any commit.
+
+One process, legs alternated (composed, fused, composed again: the two composed runs show the spread), >= 3 warm-ups per
+shape, medians.  Also: one lock-step optimize with 20 starts against 20 one-start calls.
+
+    python tools/infill_bench.py [--out profiles/infill_eval_ab.txt] [--reps 15] [--only-m21]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import egobox_amd as egx  # noqa: E402
+import infill_oracle as IO  # noqa: E402
+from egobox_amd import workload  # noqa: E402
+
+
+def build(n, d, k):
+    hs, ys = [], []
+    for j in range(1 + k):
+        x, y = workload.make_training_set(n, d, seed=100 + j)
+        if j:
+            y = y - np.quantile(y, 0.6)
+        h = egx.GpHandle(x, y)
+        h.finalize(np.full(d, 1.5))
+        hs.append(h), ys.append(y)
+    return hs, ys
+
+
+def composed(hs, tols, fmin, xq, want_grad):
+    """the caller's loop: 2 (1 + k) library calls (1 + k without gradients), then the arithmetic on the host"""
+    m, d = xq.shape
+    nm = len(hs)
+    mu, var = np.empty((nm, m)), np.empty((nm, m))
+    dmu, dvar = np.zeros((nm, m, d)), np.zeros((nm, m, d))
+    for j, h in enumerate(hs):
+        mu[j], var[j] = h.predict_valvar(xq)
+        if want_grad:
+            dmu[j], dvar[j] = h.predict_valvar_gradients(xq)
+    val = np.empty(m)
+    grad = np.empty((m, d)) if want_grad else None
+    for i in range(m):
+        val[i] = IO.objective(IO.LOG_EI, mu[:, i], var[:, i], tols, fmin, 1.0, 1.0, 1.0, True, dev=True)
+        if want_grad:
+            grad[i] = IO.dev_objective_grad(IO.LOG_EI, (mu[:, i], var[:, i], dmu[:, i], dvar[:, i]), tols, fmin, 1.0, 1.0, 1.0, True)
+    return val, grad
+
+
+def median_ms(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infill_eval_ab.txt"))
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
+    args = ap.parse_args()
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    if args.only_m21:
+        hs, ys = build(4096, 8, 2)
+        obj = egx.InfillObjective(hs[0], hs[1:], [0.0, 0.0], criterion=egx.LOG_EI, fmin=float(np.quantile(ys[0], 0.05)))
+        xq = np.random.default_rng(0).random((21, 8))
+        for _ in range(3):
+            obj.value_and_grad(xq)
+        for _ in range(10):
+            obj.value(xq)
+            obj.value_and_grad(xq)
+        return
+    emit("# infill evaluation, composed (predict_valvar + predict_valvar_gradients per model + host arithmetic) vs fused")
+    emit("# (egx_infill_eval); LogEI, k = 2 constraint models; median ms over %d calls after 3 warm-ups; legs alternated" % args.reps)
+    emit("# n d k m grad composed_a_ms fused_ms composed_b_ms composed_spread fused/composed verdict")
+    for n, d, k in ((4096, 8, 2), (8192, 16, 2)):
+        hs, ys = build(n, d, k)
+        tols = [0.0] * k
+        fmin = float(np.quantile(ys[0], 0.05))
+        obj = egx.InfillObjective(hs[0], hs[1:], tols, criterion=egx.LOG_EI, fmin=fmin)
+        rng = np.random.default_rng(1)
+        for m in (1, 21, 800):
+            xq = rng.random((m, d))
+            reps = args.reps if m < 800 else max(3, args.reps // 5)
+            for want_grad in (False, True):
+                fused = (lambda: obj.value_and_grad(xq)) if want_grad else (lambda: obj.value(xq))
+                comp = lambda: composed(hs, tols, fmin, xq, want_grad)  # noqa: E731
+                vc, gc = comp()
+                vf = fused()
+                vf, gf = vf if want_grad else (vf, None)
+                ok = np.allclose(vf, vc, rtol=1e-6, atol=1e-6) and (not want_grad or np.allclose(gf, gc, rtol=1e-4, atol=1e-5 * (1 + np.abs(gc).max())))
+                ca = median_ms(comp, reps)
+                fu = median_ms(fused, reps)
+                cb = median_ms(comp, reps)
+                spread = abs(ca - cb)
+                c = min(ca, cb)
+                verdict = "fused faster" if fu < c else ("within the spread" if fu <= max(ca, cb) else "FUSED SLOWER")
+                emit(f"{n} {d} {k} {m} {int(want_grad)} {ca:.3f} {fu:.3f} {cb:.3f} {spread:.3f} {fu / c:.3f} {verdict}"
+                     + ("" if ok else "  RESULTS DIFFER"))
+        # the multistart: 20 starts in lock-step against 20 one-start calls
+        starts = rng.random((20, d))
+        lim = np.array([[0.0, 1.0]] * d)
+        obj.scaling(rng.random((200, d)))
+        obj.optimize(lim, starts[:2], max_eval=20)  # warm-up
+        t0 = time.perf_counter()
+        f, xb, st = obj.optimize(lim, starts, max_eval=100)
+        t_lock = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        singles = [obj.optimize(lim, starts[i:i + 1], max_eval=100) for i in range(20)]
+        t_single = (time.perf_counter() - t0) * 1e3
+        same = f == min(s[0] for s in singles)
+        emit(f"# optimize n {n} d {d} k {k}: 20 starts lock-step {t_lock:.1f} ms ({st['rounds']} rounds, {int(st['evals'].sum())} evaluations), "
+             f"20 one-start calls {t_single:.1f} ms, same optimum: {same}")
+        obj.close()
+        for h in hs:
+            h.close()
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
