@@ -185,22 +185,20 @@ namespace egx {
 static int ensure_grad_scratch(egx_gp *gp, int ws_lo, int nuse) {
     const size_t sq = (size_t)gp->n_pad * gp->n_pad;
     if (gp->slab_W_count < nuse) {
-        if (gp->slab_W) (void)hipFree(gp->slab_W);
-        gp->slab_W = nullptr;
         gp->slab_W_count = 0;
-        EGX_HIP_CHECK(dev_malloc(&gp->slab_W, sizeof(double) * sq * (size_t)nuse));
+        EGX_RC(gp->slab_W.alloc(sq * (size_t)nuse));
         gp->slab_W_count = nuse;
     }
     for (int i = ws_lo; i < ws_lo + nuse; i++) {
         Workspace &w = gp->ws[i];
-        if (!w.d_gpart) EGX_HIP_CHECK(dev_malloc(&w.d_gpart, sizeof(double) * (size_t)grad_partial_doubles(gp->d)));
-        if (!w.d_gout) EGX_HIP_CHECK(dev_malloc(&w.d_gout, sizeof(double) * (size_t)(gp->d + 64)));
-        if (!w.h_gout) EGX_HIP_CHECK(hipHostMalloc(&w.h_gout, sizeof(double) * (size_t)(gp->d + 64), hipHostMallocDefault));
+        EGX_RC(w.d_gpart.alloc((size_t)grad_partial_doubles(gp->d)));
+        EGX_RC(w.d_gout.alloc((size_t)(gp->d + 64)));
+        EGX_RC(w.h_gout.alloc((size_t)(gp->d + 64)));
     }
     if (gp->has_w && !gp->d_wabs) {
         std::vector<double> wabs(gp->w_star.size());
         for (size_t e = 0; e < wabs.size(); e++) wabs[e] = std::fabs(gp->w_star[e]);
-        EGX_HIP_CHECK(dev_malloc(&gp->d_wabs, sizeof(double) * wabs.size()));
+        EGX_RC(gp->d_wabs.alloc(wabs.size()));
         EGX_HIP_CHECK(hipMemcpy(gp->d_wabs, wabs.data(), sizeof(double) * wabs.size(), hipMemcpyHostToDevice));
     }
     return EGX_SUCCESS;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "egx_internal.h"
+#include "dev_mem.h"
 #include "host_math.h"
 #include "cobyla.h"
 
@@ -28,31 +29,9 @@
 
 namespace egx {
 
-// Scoped device allocation for the temporaries of one call (freed on every exit path).
-struct DevBuf {
-    double *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    size_t cap = 0;  // doubles
-    // grow-only: a buffer declared outside a chunk loop is allocated once (a hipMalloc / hipFree pair of a 1 GiB block per
-    // 16 384 query points used to sit inside predict_var's loop)
-    int alloc(size_t n_doubles) {
-        if (n_doubles == 0) n_doubles = 1;
-        if (p && cap >= n_doubles) return EGX_SUCCESS;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        EGX_HIP_CHECK(dev_malloc(&p, sizeof(double) * n_doubles));
-        cap = n_doubles;
-        return EGX_SUCCESS;
-    }
-};
-
-struct Workspace {
+// Streams and events of a workspace.  Plain handles (the launchers take them as they are); WorkspaceHandles below owns them.
+struct WorkspaceRaw {
+    int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t eval_stream = nullptr;  // the stream the evaluation in flight was enqueued on: the workspace's own, or
                                         // the leader's when it rides in a lock-step group (finish_eval waits on it)
@@ -60,17 +39,35 @@ struct Workspace {
     // the stream + events on which C^-T rides along a factorisation (theta-gradient; PotrfInverse, egx_internal.h)
     hipStream_t inv_stream = nullptr;
     hipEvent_t ev_inv_grp = nullptr, ev_inv_done = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    GemmTrace trace;
+};
+// Move-only owner of the above: the events are destroyed with it, the four streams go to the idle list of their device as a
+// set (gp_host.hip; idle: whoever lets a workspace go has synchronised its streams)
+struct WorkspaceHandles : WorkspaceRaw {
+    WorkspaceHandles() = default;
+    WorkspaceHandles(WorkspaceHandles &&o) noexcept : WorkspaceRaw(o) { static_cast<WorkspaceRaw &>(o) = WorkspaceRaw(); }
+    WorkspaceHandles &operator=(WorkspaceHandles &&o) noexcept {
+        std::swap(static_cast<WorkspaceRaw &>(*this), static_cast<WorkspaceRaw &>(o));
+        return *this;
+    }
+    ~WorkspaceHandles() { release(); }
+    void release_streams();
+    void release();
+};
+
+struct Workspace : WorkspaceHandles {
     // M, dinv and d_info are VIEWS into the handle's slabs (egx_gp::slab_*): consecutive workspaces sit at fixed
     // strides, which is what lets a group of them be factored in lock-step by one launch sequence
     double *M = nullptr;       // (m_tot x ld): correlation matrix / factor + appended RHS rows
     double *dinv = nullptr;    // (n_pad/64) x 64 x 64 inverses of the diagonal tiles
-    double *dW = nullptr;      // (n_pad/256) x 256 x 256 transposed inverses of the diagonal blocks (lazy)
-    double *d_coef = nullptr;  // d x hcols
-    double *d_xs = nullptr;    // d x n_pad: the inputs times this candidate's coefficients (K1's scalar-row form)
-    double *d_diag = nullptr;  // n
-    double *d_vec = nullptr;   // n_pad (gamma)
-    double *d_rhs = nullptr;   // n_pad (rho, destroyed by the back-substitution)
     int *d_info = nullptr;
+    DevMem<double> dW;      // (n_pad/256) x 256 x 256 transposed inverses of the diagonal blocks (lazy)
+    DevMem<double> d_coef;  // d x hcols
+    DevMem<double> d_xs;    // d x n_pad: the inputs times this candidate's coefficients (K1's scalar-row form)
+    DevMem<double> d_diag;  // n
+    DevMem<double> d_vec;   // n_pad (gamma)
+    DevMem<double> d_rhs;   // n_pad (rho, destroyed by the back-substitution)
     const int *sync_lead = nullptr;  // hand-off words of the lead of the lock-step group this evaluation ran in (diagnostics)
     // what finish_eval needs to enqueue this evaluation once more, alone and by separate launches, when a chain launch ran into
     // its wait bound: coefficient columns and count (the coefficients themselves are still in h_coef), the C^-T buffer of the
@@ -79,21 +76,57 @@ struct Workspace {
     double *retry_W = nullptr;
     bool retried = false;
     // device-side GLS (p > 1 trend columns): Gram matrix of [ft | yt] and its factor, all (rhs_pad x rhs_pad)
-    double *d_gneg = nullptr, *d_gram = nullptr, *d_gdinv = nullptr, *d_gramP = nullptr, *d_beta = nullptr,
-           *d_part = nullptr;
-    int *d_ginfo = nullptr;
-    double *h_gram = nullptr, *h_part = nullptr, *h_beta = nullptr;  // pinned
-    int *h_ginfo = nullptr;                                          // pinned
+    DevMem<double> d_gneg, d_gram, d_gdinv, d_gramP, d_beta, d_part;
+    DevMem<int> d_ginfo;
+    PinMem<double> h_gram, h_part, h_beta;
+    PinMem<int> h_ginfo;
     bool gls_enqueued = false;  // this evaluation took the device GLS route (set by enqueue_eval)
-    double *h_coef = nullptr;  // pinned
-    double *h_rows = nullptr;  // pinned: q x n_pad solved RHS rows (ft^T, yt^T)
-    double *h_diag = nullptr;  // pinned: n
-    double *h_vec = nullptr;   // pinned: n_pad
-    int *h_info = nullptr;     // pinned: [0] the factorisation's info, [1..8] the abort word + diagnostics of its chain launches
+    PinMem<double> h_coef;
+    PinMem<double> h_rows;  // q x n_pad solved RHS rows (ft^T, yt^T)
+    PinMem<double> h_diag;  // n
+    PinMem<double> h_vec;   // n_pad
+    PinMem<int> h_info;     // [0] the factorisation's info, [1..8] the abort word + diagnostics of its chain launches
     // theta-gradient scratch (lazy, gp_fit.hip): the workgroups' partial sums, the reduced sums, their pinned copy
-    double *d_gpart = nullptr, *d_gout = nullptr, *h_gout = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    GemmTrace trace;
+    DevMem<double> d_gpart, d_gout;
+    PinMem<double> h_gout;
+    // device bytes held (what the resource pool counts): EVERY DevMem above
+    size_t device_bytes() const {
+        return dW.bytes + d_coef.bytes + d_xs.bytes + d_diag.bytes + d_vec.bytes + d_rhs.bytes + d_gneg.bytes + d_gram.bytes +
+               d_gdinv.bytes + d_gramP.bytes + d_beta.bytes + d_part.bytes + d_ginfo.bytes + d_gpart.bytes + d_gout.bytes;
+    }
+};
+
+// The three slabs of a handle or of a group: one allocation each for all workspaces' (members') matrices, tile inverses, and
+// failure flags + hand-off words
+struct Slabs {
+    DevMem<double> M, D;
+    DevMem<int> I;  // one failure flag per workspace, then (from sync_off on) stride_S hand-off words per workspace
+                    // for the pipelined chain kernel (kernels_pipe.hip; zeroed by every factorisation)
+    size_t bytes() const { return M.bytes + D.bytes + I.bytes; }
+    bool complete() const { return M.p && D.p && I.p; }
+};
+// The geometry of a shape: n training points, p trend columns, nws workspaces (members of a group) in one set of slabs
+struct SlabGeometry {
+    int n_pad = 0, rhs_pad = 0, m_tot = 0;
+    int64_t stride_M = 0, stride_D = 0, stride_S = 0, sync_off = 0;  // elements per workspace; first hand-off word in I
+    size_t doubles_M = 0, doubles_D = 0, ints_I = 0;                 // what the three slabs hold
+};
+SlabGeometry slab_geometry(int64_t n, int64_t p, int nws);  // gp_host.hip
+// Everything device-side a handle hands to the resource pool when it is destroyed, and adopts from there when one of its
+// shape is created: the training-set buffers, the slabs (none: a member of a group) and the workspaces
+struct HandleRes {
+    int device = 0;
+    DevMem<double> d_xT;    // d x n_pad (k-major normalised inputs, zero padded), then the same times the fit's coefficients
+    DevMem<double> d_rhsT;  // q x n_pad: columns of F then y (normalised), as rows
+    DevMem<double> d_gamma;  // n_pad
+    DevMem<double> d_fit_coef;  // d x hcols coefficients of the fit, then x_mean (d) | x_std (d): dev_xnorm()
+    Slabs slabs;
+    std::vector<Workspace> ws;
+    size_t device_bytes() const {
+        size_t b = d_xT.bytes + d_rhsT.bytes + d_gamma.bytes + d_fit_coef.bytes + slabs.bytes();
+        for (const auto &w : ws) b += w.device_bytes();
+        return b;
+    }
 };
 
 // outcome of one start of a multistart optimisation: objective (-likelihood), its minimiser in log10 theta, evaluations
@@ -121,16 +154,14 @@ namespace egx {
 // (crates/moe/src/algorithm.rs:167-177), an optimiser's objective and constraint surrogates -- whose matrices sit at the
 // fixed strides a lock-step launch needs, although every member has its own training set.  Freed with the last member.
 struct GroupSlabs {
+    Slabs slabs;
     int device = 0, k = 0;
-    double *M = nullptr, *D = nullptr;
-    int *I = nullptr;
-    size_t bytes_M = 0, bytes_D = 0, bytes_I = 0;
+    int64_t sync_off = 0;  // of the group's I slab
     ~GroupSlabs();  // gp_host.hip: the slabs go to the resource pool (the next group of this shape adopts them), or are freed
 };
 }  // namespace egx
 
-struct egx_gp {
-    int device = 0;
+struct egx_gp : egx::HandleRes {
     int n = 0, d = 0, p = 0, h = 0, corr = 0, mean = 0;
     double nugget = 0.0;
     int n_pad = 0, rhs_pad = 0, m_tot = 0, q = 0;
@@ -140,13 +171,9 @@ struct egx_gp {
     std::vector<double> w_star;  // d x h
     std::vector<double> x_raw, y_raw, xnorm, x_mean, x_std, ynorm, F;
     double y_mean = 0.0, y_std = 1.0;
-    double *d_xT = nullptr;    // d x n_pad (k-major normalised inputs, zero padded), then the same times the fit's coefficients
-    double *d_rhsT = nullptr;  // q x n_pad: columns of F then y (normalised), as rows
-    std::vector<egx::Workspace> ws;
-    // one allocation each for all workspaces' matrices, tile inverses and failure flags (strides in elements)
+    // VIEWS of workspace 0's part of the slabs (strides in elements): the handle's own `slabs`, or slot `group_slot` of the group's
     double *slab_M = nullptr, *slab_D = nullptr;
-    int *slab_I = nullptr;  // one failure flag per workspace, then (from sync_off on) stride_S hand-off words per workspace
-                            // for the pipelined chain kernel (kernels_pipe.hip; zeroed by every factorisation)
+    int *slab_I = nullptr;
     int64_t stride_M = 0, stride_D = 0, stride_S = 0, sync_off = 0;
     std::shared_ptr<egx::GroupSlabs> group;  // member of a group: slab_M / slab_D / slab_I are VIEWS of slot `group_slot`
     int group_slot = -1;
@@ -166,20 +193,16 @@ struct egx_gp {
     std::vector<double> beta, gamma, ft, ft_qr_r;
     std::vector<double> fit_coef;
     int fit_hcols = 1;
-    double *d_gamma = nullptr;  // n_pad
-    double *d_fit_coef = nullptr;  // d x hcols coefficients of the fit, then x_mean (d) | x_std (d): dev_xnorm()
     // theta-gradient scratch (allocated on first use, gp_fit.hip): C^-T of `slab_W_count` candidates at a fixed stride of
     // n_pad^2 doubles (lock-step), |w_star| on the device (KPLS + Matern)
-    double *slab_W = nullptr, *d_wabs = nullptr;
+    egx::DevMem<double> slab_W, d_wabs;
     int slab_W_count = 0;
     // x-gradient state (lazy, per fitted factor): d_W = C^-T of the FITTED factor and
     // -R^-1 F = -C^-T ft as an (n_pad x rhs_pad) matrix
-    double *d_W = nullptr;
-    double *d_neg_invkf = nullptr;
+    egx::DevMem<double> d_W, d_neg_invkf;
     std::vector<double> h_neg_invkf;  // host copy (n x p) for the single-point path
     // device scratch of the single-point path, allocated once (a hipMalloc per call would cost more than the kernels)
-    double *sp_R = nullptr, *sp_P = nullptr, *sp_y = nullptr, *sp_z = nullptr, *sp_wt = nullptr, *sp_out = nullptr,
-           *sp_xq = nullptr;
+    egx::DevMem<double> sp_R, sp_P, sp_y, sp_z, sp_wt, sp_out, sp_xq;
     int sp_nsplit = 0;
     int small_var_calls = 0;  // single-point predict_var calls since the fit: the third one builds W = C^-T
     uint64_t fit_epoch = 0, winv_epoch = ~(uint64_t)0;
@@ -200,8 +223,7 @@ int fit_reduce_finalize(egx_gp *gp, const double *theta_base, const std::vector<
 // x_mean (d) | x_std (d) on the device, behind the coefficients of the fit in the same allocation
 // the training inputs times the coefficients of the fit (d x n_pad, k-major; valid when fit_hcols == 1), behind d_xT in
 // the same allocation: what the scalar-row prediction kernel reads (kernels_corr.hip k_predict_mean_srow)
-// ints of slab_I for `nws` workspaces, and workspace i's hand-off words in it
-inline size_t slab_I_ints(const egx_gp *gp, int nws) { return (size_t)egx::round_up(nws, 64) + (size_t)gp->stride_S * (size_t)nws; }
+// workspace i's hand-off words in slab_I
 inline int *dev_sync(const egx_gp *gp, int i) { return gp->slab_I + gp->sync_off + (int64_t)i * gp->stride_S; }
 inline double *dev_xs_fit(const egx_gp *gp) { return gp->d_xT + (size_t)gp->d * gp->n_pad; }
 inline double *dev_xnorm(const egx_gp *gp) { return gp->d_fit_coef + (size_t)gp->d * (gp->has_w ? gp->h : 1); }

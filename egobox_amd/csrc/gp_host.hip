@@ -4,6 +4,7 @@
 // parts run in the HIP kernels of kernels_corr.hip / kernels_chol.hip.  Predictions: gp_predict.hip; optimiser drivers
 // and the theta-gradient: gp_fit.hip; sparse GP: sgp_host.hip.  There is no CPU fallback.
 #include "gp_handle.h"
+#include "resource_pool.h"
 
 namespace egx {
 
@@ -47,21 +48,6 @@ static void destroy_stream_set(StreamSet &ss) {
     if (ss.stream) (void)hipStreamDestroy(ss.stream);
     ss = StreamSet();
 }
-// the workspace's streams (idle: every caller has synchronised them) go to the free list; a partial set is destroyed
-static void give_streams(int device, Workspace &w) {
-    StreamSet ss;
-    ss.stream = w.stream, ss.inv_stream = w.inv_stream, ss.s2 = w.lk.s2, ss.s3 = w.lk.s3;
-    w.stream = w.eval_stream = w.inv_stream = nullptr;
-    w.lk.s2 = w.lk.s3 = nullptr;
-    if (ss.stream && ss.inv_stream && ss.s2 && ss.s3) {
-        std::lock_guard<std::mutex> lock(g_stream_mu);
-        if (g_stream_sets.size() < kMaxIdleStreamSets) {
-            g_stream_sets.emplace_back(device, ss);
-            return;
-        }
-    }
-    destroy_stream_set(ss);
-}
 // four streams for a workspace of `device`: an idle set, or new ones (evaluation, rider, then the two high-priority ones)
 static hipError_t take_streams(int device, Workspace &w) {
     {
@@ -103,47 +89,63 @@ static void destroy_idle_streams(int device) {
     if (have_cur) (void)hipSetDevice(cur);
 }
 
-static void free_workspace(Workspace &w, int device) {
-    // (M, dinv, d_info are views into the handle's slabs)
-    if (w.dW) hipFree(w.dW);
-    if (w.d_coef) hipFree(w.d_coef);
-    if (w.d_xs) hipFree(w.d_xs);
-    if (w.d_diag) hipFree(w.d_diag);
-    if (w.d_vec) hipFree(w.d_vec);
-    if (w.d_rhs) hipFree(w.d_rhs);
-    for (double *q : {w.d_gneg, w.d_gram, w.d_gdinv, w.d_gramP, w.d_beta, w.d_part})
-        if (q) hipFree(q);
-    if (w.d_ginfo) hipFree(w.d_ginfo);
-    for (double *q : {w.h_gram, w.h_part, w.h_beta})
-        if (q) hipHostFree(q);
-    if (w.h_ginfo) hipHostFree(w.h_ginfo);
-    if (w.h_coef) hipHostFree(w.h_coef);
-    if (w.h_rows) hipHostFree(w.h_rows);
-    if (w.h_diag) hipHostFree(w.h_diag);
-    if (w.h_vec) hipHostFree(w.h_vec);
-    if (w.h_info) hipHostFree(w.h_info);
-    if (w.d_gpart) hipFree(w.d_gpart);
-    if (w.d_gout) hipFree(w.d_gout);
-    if (w.h_gout) hipHostFree(w.h_gout);
-    for (auto &e : w.ev)
-        if (e) hipEventDestroy(e);
-    if (w.trace.ready)
-        for (int i = 0; i < GemmTrace::kMax; i++) {
-            hipEventDestroy(w.trace.e0[i]);
-            hipEventDestroy(w.trace.e1[i]);
+// the streams (idle: every caller has synchronised them) go to the free list as a set; a partial set is destroyed
+void WorkspaceHandles::release_streams() {
+    StreamSet ss;
+    ss.stream = stream, ss.inv_stream = inv_stream, ss.s2 = lk.s2, ss.s3 = lk.s3;
+    stream = eval_stream = inv_stream = nullptr;
+    lk.s2 = lk.s3 = nullptr;
+    if (ss.stream && ss.inv_stream && ss.s2 && ss.s3) {
+        std::lock_guard<std::mutex> lock(g_stream_mu);
+        if (g_stream_sets.size() < kMaxIdleStreamSets) {
+            g_stream_sets.emplace_back(device, ss);
+            return;
         }
-    for (hipEvent_t e : {w.lk.ev_lu, w.lk.ev_lur, w.lk.ev_panel, w.lk.ev_a, w.lk.ev_b})
+    }
+    destroy_stream_set(ss);
+}
+void WorkspaceHandles::release() {
+    for (auto &e : ev)
         if (e) hipEventDestroy(e);
-    if (w.ev_inv_grp) hipEventDestroy(w.ev_inv_grp);
-    if (w.ev_inv_done) hipEventDestroy(w.ev_inv_done);
-    give_streams(device, w);  // (idle: whoever frees a workspace has synchronised its streams)
-    w = Workspace();
+    if (trace.ready)
+        for (int i = 0; i < GemmTrace::kMax; i++) {
+            hipEventDestroy(trace.e0[i]);
+            hipEventDestroy(trace.e1[i]);
+        }
+    for (hipEvent_t e : {lk.ev_lu, lk.ev_lur, lk.ev_panel, lk.ev_a, lk.ev_b, ev_inv_grp, ev_inv_done})
+        if (e) hipEventDestroy(e);
+    release_streams();
+    static_cast<WorkspaceRaw &>(*this) = WorkspaceRaw();
 }
 
-static int alloc_workspace(egx_gp *gp, Workspace &w, int index) {
+SlabGeometry slab_geometry(int64_t n, int64_t p, int nws) {
+    SlabGeometry g;
+    // 256-column granularity lets every trailing update of a large fit use the 128x256 tile (N % 256 == 0)
+    g.n_pad = (int)round_up(n, n >= 4096 ? kNB : kTile);
+    g.rhs_pad = (int)round_up(p + 1, kRhsPad);
+    g.m_tot = g.n_pad + g.rhs_pad;
+    g.stride_M = (int64_t)g.m_tot * g.n_pad;
+    g.stride_D = round_up((int64_t)dinv_doubles(g.n_pad), 64);
+    g.stride_S = (int64_t)pipe_sync_ints(g.n_pad, g.m_tot);
+    g.sync_off = round_up(nws, 64);
+    g.doubles_M = (size_t)g.stride_M * nws, g.doubles_D = (size_t)g.stride_D * nws;
+    g.ints_I = (size_t)g.sync_off + (size_t)g.stride_S * nws;
+    return g;
+}
+static int alloc_slabs(Slabs &s, const SlabGeometry &g) {
+    EGX_RC(s.M.alloc(g.doubles_M));
+    EGX_RC(s.D.alloc(g.doubles_D));
+    return s.I.alloc(g.ints_I);
+}
+// workspace `index` looks at its part of the slabs whose slot 0 the handle's views name
+static void set_views(egx_gp *gp, Workspace &w, int index) {
     w.M = gp->slab_M + (int64_t)index * gp->stride_M;
     w.dinv = gp->slab_D + (int64_t)index * gp->stride_D;
     w.d_info = gp->slab_I + index;
+}
+
+static int alloc_workspace(egx_gp *gp, Workspace &w) {
+    w.device = gp->device;
     // evaluation stream, the C^-T rider's stream, the look-ahead chain's stream and the side stream of the split updates
     // (launch_potrf; the last two high priority): an idle set of the device, or new ones
     EGX_HIP_CHECK(take_streams(gp->device, w));
@@ -151,31 +153,31 @@ static int alloc_workspace(egx_gp *gp, Workspace &w, int index) {
     EGX_HIP_CHECK(hipEventCreateWithFlags(&w.ev_inv_done, hipEventDisableTiming));
     for (hipEvent_t *e : {&w.lk.ev_lu, &w.lk.ev_lur, &w.lk.ev_panel, &w.lk.ev_a, &w.lk.ev_b})
         EGX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    const int hmax = gp->has_w ? gp->h : 1;
-    EGX_HIP_CHECK(dev_malloc(&w.d_coef, sizeof(double) * (size_t)gp->d * hmax));
-    EGX_HIP_CHECK(dev_malloc(&w.d_xs, sizeof(double) * (size_t)gp->d * gp->n_pad));
-    EGX_HIP_CHECK(dev_malloc(&w.d_diag, sizeof(double) * (size_t)gp->n_pad));
-    EGX_HIP_CHECK(dev_malloc(&w.d_vec, sizeof(double) * (size_t)gp->n_pad));
-    EGX_HIP_CHECK(dev_malloc(&w.d_rhs, sizeof(double) * (size_t)gp->n_pad));
-    EGX_HIP_CHECK(hipHostMalloc(&w.h_coef, sizeof(double) * (size_t)gp->d * hmax, hipHostMallocDefault));
-    EGX_HIP_CHECK(hipHostMalloc(&w.h_rows, sizeof(double) * (size_t)gp->q * gp->n_pad, hipHostMallocDefault));
-    EGX_HIP_CHECK(hipHostMalloc(&w.h_diag, sizeof(double) * (size_t)gp->n_pad, hipHostMallocDefault));
-    EGX_HIP_CHECK(hipHostMalloc(&w.h_vec, sizeof(double) * (size_t)gp->n_pad, hipHostMallocDefault));
-    EGX_HIP_CHECK(hipHostMalloc(&w.h_info, 16 * sizeof(int), hipHostMallocDefault));
+    const size_t hmax = gp->has_w ? gp->h : 1, d = (size_t)gp->d, n_pad = (size_t)gp->n_pad;
+    EGX_RC(w.d_coef.alloc(d * hmax));
+    EGX_RC(w.d_xs.alloc(d * n_pad));
+    EGX_RC(w.d_diag.alloc(n_pad));
+    EGX_RC(w.d_vec.alloc(n_pad));
+    EGX_RC(w.d_rhs.alloc(n_pad));
+    EGX_RC(w.h_coef.alloc(d * hmax));
+    EGX_RC(w.h_rows.alloc((size_t)gp->q * n_pad));
+    EGX_RC(w.h_diag.alloc(n_pad));
+    EGX_RC(w.h_vec.alloc(n_pad));
+    EGX_RC(w.h_info.alloc(16));
     std::memset(w.h_info, 0, 16 * sizeof(int));
     if (gp->gls_device) {
-        const size_t g2 = (size_t)gp->rhs_pad * gp->rhs_pad;
-        EGX_HIP_CHECK(dev_malloc(&w.d_gneg, sizeof(double) * g2));
-        EGX_HIP_CHECK(dev_malloc(&w.d_gram, sizeof(double) * g2));
-        EGX_HIP_CHECK(dev_malloc(&w.d_gdinv, sizeof(double) * dinv_doubles(gp->rhs_pad)));
-        EGX_HIP_CHECK(dev_malloc(&w.d_gramP, sizeof(double) * gram_scratch_doubles(gp->rhs_pad, gp->n_pad)));
-        EGX_HIP_CHECK(dev_malloc(&w.d_beta, sizeof(double) * (size_t)gp->rhs_pad));
-        EGX_HIP_CHECK(dev_malloc(&w.d_part, sizeof(double) * (size_t)((gp->n_pad + 255) / 256)));
-        EGX_HIP_CHECK(dev_malloc(&w.d_ginfo, sizeof(int)));
-        EGX_HIP_CHECK(hipHostMalloc(&w.h_gram, sizeof(double) * g2, hipHostMallocDefault));
-        EGX_HIP_CHECK(hipHostMalloc(&w.h_part, sizeof(double) * (size_t)((gp->n_pad + 255) / 256), hipHostMallocDefault));
-        EGX_HIP_CHECK(hipHostMalloc(&w.h_beta, sizeof(double) * (size_t)gp->rhs_pad, hipHostMallocDefault));
-        EGX_HIP_CHECK(hipHostMalloc(&w.h_ginfo, sizeof(int), hipHostMallocDefault));
+        const size_t g = (size_t)gp->rhs_pad, nblk = (n_pad + 255) / 256;
+        EGX_RC(w.d_gneg.alloc(g * g));
+        EGX_RC(w.d_gram.alloc(g * g));
+        EGX_RC(w.d_gdinv.alloc(dinv_doubles(gp->rhs_pad)));
+        EGX_RC(w.d_gramP.alloc(gram_scratch_doubles(gp->rhs_pad, gp->n_pad)));
+        EGX_RC(w.d_beta.alloc(g));
+        EGX_RC(w.d_part.alloc(nblk));
+        EGX_RC(w.d_ginfo.alloc(1));
+        EGX_RC(w.h_gram.alloc(g * g));
+        EGX_RC(w.h_part.alloc(nblk));
+        EGX_RC(w.h_beta.alloc(g));
+        EGX_RC(w.h_ginfo.alloc(1));
     }
     for (auto &e : w.ev) EGX_HIP_CHECK(hipEventCreate(&e));
     for (int i = 0; i < GemmTrace::kMax; i++) {
@@ -191,60 +193,19 @@ static int alloc_workspace(egx_gp *gp, Workspace &w, int index) {
 // callers -- the expert loop of egobox-moe (crates/moe/src/algorithm.rs:167-177), EGO's surrogate refits -- create a new
 // model per call.  A new handle used to cost a 2 GiB hipMalloc (n = 16384), ~400 event / 3 stream creations per
 // workspace and a first factorisation at half speed on the never-touched allocation (round 2: 68 ms against 27 ms
-// resident).  Destroyed handles therefore leave everything device-side they own -- slabs, workspaces with their
-// streams / events / pinned buffers, the training-set buffers -- in a per-process pool keyed by the SHAPE of the handle;
+// resident).  Destroyed handles therefore leave everything device-side they own -- a HandleRes: slabs, workspaces with their
+// events / pinned buffers, the training-set buffers -- in a per-process pool keyed by the SHAPE of the handle;
 // the next egx_gp_create of that shape adopts it and only uploads x and y.  Bounded (EGX_POOL_MAX_GB, default 48; least
 // recently returned entries are freed first), emptied by egx_trim().  Nothing pooled is ever read before it is
 // rewritten: every evaluation rebuilds R including its identity padding, the right-hand-side rows and the flags.
+// The slabs of a destroyed GROUP (GroupSlabs: k matrices, tile inverses, flags + hand-off words of one shape) are an entry of
+// their own -- a HandleRes with nothing but slabs -- adopted by the next egx_gp_create_group whose three sizes match (round 6:
+// eight n = 8192 experts were 107 ms to create and 100 ms to destroy -- a 4.4 GB hipMalloc / hipFree and eight workspaces'
+// streams, ~400 events and pinned buffers each -- for a 33 ms fit).  Keys, order and eviction: resource_pool.h.
 // ---------------------------------------------------------------------------------------------
-struct PoolKey {
-    int device = 0, n_pad = 0, d = 0, q = 0, hmax = 1, nws = 0;
-    bool gls = false;
-    bool member = false;  // a member of a group (egx_gp_create_group): everything but the slabs, which belong to the group
-    bool operator==(const PoolKey &o) const {
-        return device == o.device && n_pad == o.n_pad && d == o.d && q == o.q && hmax == o.hmax && nws == o.nws && gls == o.gls &&
-               member == o.member;
-    }
-};
-struct PoolEntry {
-    PoolKey key;
-    double *d_xT = nullptr, *d_rhsT = nullptr, *d_gamma = nullptr, *d_fit_coef = nullptr;
-    double *slab_M = nullptr, *slab_D = nullptr;
-    int *slab_I = nullptr;
-    std::vector<Workspace> ws;
-    size_t bytes = 0;
-};
-// the slabs of a destroyed GROUP (GroupSlabs: k matrices, tile inverses, flags + hand-off words of one shape): adopted by the
-// next egx_gp_create_group whose three sizes match (round 6: eight n = 8192 experts were 107 ms to create and 100 ms to
-// destroy -- a 4.4 GB hipMalloc / hipFree and eight workspaces' streams, ~400 events and pinned buffers each -- for a 33 ms fit)
-struct SlabEntry {
-    int device = 0;
-    double *M = nullptr, *D = nullptr;
-    int *I = nullptr;
-    size_t bytes_M = 0, bytes_D = 0, bytes_I = 0;
-    size_t bytes() const { return bytes_M + bytes_D + bytes_I; }
-};
-static std::mutex g_pool_mu;
-static std::list<PoolEntry> g_pool;  // front = most recently returned
-static std::list<SlabEntry> g_slab_pool;  // front = most recently returned
-static int64_t g_pool_hits = 0, g_pool_misses = 0;
+using Pool = ResourcePool<HandleRes>;
+static Pool &g_pool = *new Pool;  // (never destroyed: what is pooled at exit is not freed behind the runtime's back)
 
-// bytes pooled on one device (the bound EGX_POOL_MAX_GB is PER DEVICE)
-static size_t pool_bytes_on(int device) {
-    size_t b = 0;
-    for (const auto &e : g_pool)
-        if (e.key.device == device) b += e.bytes;
-    for (const auto &e : g_slab_pool)
-        if (e.device == device) b += e.bytes();
-    return b;
-}
-static void free_slab_entry(SlabEntry &e) {
-    (void)hipSetDevice(e.device);
-    if (e.M) (void)hipFree(e.M);
-    if (e.D) (void)hipFree(e.D);
-    if (e.I) (void)hipFree(e.I);
-    e = SlabEntry();
-}
 static size_t pool_cap_bytes() {
     static const size_t cap = [] {
         double gb = 48.0;
@@ -253,43 +214,20 @@ static size_t pool_cap_bytes() {
     }();
     return cap;
 }
-static void free_entry(PoolEntry &e) {
-    (void)hipSetDevice(e.key.device);
-    for (auto &w : e.ws) free_workspace(w, e.key.device);
-    for (double *q : {e.d_xT, e.d_rhsT, e.d_gamma, e.d_fit_coef, e.slab_M, e.slab_D})
-        if (q) (void)hipFree(q);
-    if (e.slab_I) (void)hipFree(e.slab_I);
-    e = PoolEntry();
+// the pool's free path: entries that left the list are freed on their own device
+static void pool_free(Pool::List out) {
+    int cur = 0;
+    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+    for (auto &e : out) {
+        (void)hipSetDevice(e.key.device);
+        e.res = HandleRes();
+    }
+    if (have_cur) (void)hipSetDevice(cur);
 }
 // everything pooled on `device` (-1: on every device) is freed; returns the bytes
 static size_t pool_trim(int device) {
-    std::list<PoolEntry> out;
-    std::list<SlabEntry> out_slabs;
     size_t bytes = 0;
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        for (auto it = g_pool.begin(); it != g_pool.end();) {
-            auto next = std::next(it);
-            if (device < 0 || it->key.device == device) {
-                bytes += it->bytes;
-                out.splice(out.end(), g_pool, it);
-            }
-            it = next;
-        }
-        for (auto it = g_slab_pool.begin(); it != g_slab_pool.end();) {
-            auto next = std::next(it);
-            if (device < 0 || it->device == device) {
-                bytes += it->bytes();
-                out_slabs.splice(out_slabs.end(), g_slab_pool, it);
-            }
-            it = next;
-        }
-    }
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    for (auto &e : out) free_entry(e);
-    for (auto &e : out_slabs) free_slab_entry(e);
-    if (have_cur) (void)hipSetDevice(cur);
+    pool_free(g_pool.trim(device, &bytes));
     return bytes;
 }
 static PoolKey pool_key(const egx_gp *gp, int nws) {
@@ -304,165 +242,52 @@ static PoolKey pool_key(const egx_gp *gp, int nws) {
     k.member = gp->group != nullptr;
     return k;
 }
-// device bytes a handle of this shape hands to the pool: the slabs, the training-set buffers and every workspace's own
-// buffers (the lazily allocated ones -- block inverses, theta-gradient scratch -- counted when present)
-static size_t pooled_bytes(const egx_gp *gp, const std::vector<Workspace> &ws) {
-    const size_t n_pad = (size_t)gp->n_pad, d = (size_t)gp->d, hmax = gp->has_w ? (size_t)gp->h : 1;
-    size_t b = gp->group ? 0  // (a member of a group: the slabs are the group's, pooled on their own)
-                         : sizeof(double) * ((size_t)gp->stride_M + (size_t)gp->stride_D) * ws.size() + sizeof(int) * slab_I_ints(gp, (int)ws.size());
-    b += sizeof(double) * (2 * d * n_pad + (size_t)gp->q * n_pad + n_pad + d * hmax + 2 * d);
-    for (const auto &w : ws) {
-        b += sizeof(double) * (d * hmax + d * n_pad + 3 * n_pad);
-        if (w.dW) b += sizeof(double) * ((n_pad + kNB - 1) / kNB) * 65536;
-        if (w.d_gram) {
-            const size_t g = (size_t)gp->rhs_pad;
-            b += sizeof(double) * (2 * g * g + dinv_doubles((int)g) + gram_scratch_doubles((int)g, (int)n_pad) + g + (n_pad + 255) / 256);
-        }
-        if (w.d_gpart) b += sizeof(double) * ((size_t)grad_partial_doubles((int)d) + 64 + d);
-    }
-    return b;
+static PoolKey slabs_key(int device, const SlabGeometry &g) {
+    PoolKey k;
+    k.slabs = true;
+    k.device = device;
+    k.bytes_M = sizeof(double) * g.doubles_M, k.bytes_D = sizeof(double) * g.doubles_D, k.bytes_I = sizeof(int) * g.ints_I;
+    return k;
 }
-// adopt a pooled set of resources of this shape, if there is one
-static bool pool_take(egx_gp *gp, int nws) {
-    const PoolKey key = pool_key(gp, nws);
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    for (auto it = g_pool.begin(); it != g_pool.end(); ++it)
-        if (it->key == key) {
-            gp->d_xT = it->d_xT;
-            gp->d_rhsT = it->d_rhsT;
-            gp->d_gamma = it->d_gamma;
-            gp->d_fit_coef = it->d_fit_coef;
-            gp->slab_M = it->slab_M;
-            gp->slab_D = it->slab_D;
-            gp->slab_I = it->slab_I;
-            gp->ws = std::move(it->ws);
-            g_pool.erase(it);
-            g_pool_hits++;
-            return true;
-        }
-    g_pool_misses++;
-    return false;
-}
-// hand a dying handle's resources to the pool (or free them when the pool is disabled / they alone exceed its bound)
+// hand a dying handle's resources to the pool (or free them when the pool is disabled / they alone exceed its bound / the
+// handle's creation failed half way)
 static void pool_give(egx_gp *gp) {
-    PoolEntry e;
+    Pool::Entry e;
     e.key = pool_key(gp, (int)gp->ws.size());
-    e.d_xT = gp->d_xT;
-    e.d_rhsT = gp->d_rhsT;
-    e.d_gamma = gp->d_gamma;
-    e.d_fit_coef = gp->d_fit_coef;
-    e.slab_M = gp->slab_M;
-    e.slab_D = gp->slab_D;
-    e.slab_I = gp->slab_I;
-    e.ws = std::move(gp->ws);
-    e.bytes = pooled_bytes(gp, e.ws);
-    gp->d_xT = gp->d_rhsT = gp->d_gamma = gp->d_fit_coef = gp->slab_M = gp->slab_D = nullptr;
-    gp->slab_I = nullptr;
+    e.res = std::move(static_cast<HandleRes &>(*gp));
     gp->ws.clear();
-    bool complete = (e.key.member || (e.slab_M && e.slab_D && e.slab_I)) && e.d_xT && e.d_rhsT && e.d_gamma && e.d_fit_coef && !e.ws.empty();
-    for (auto &w : e.ws) {
+    HandleRes &r = e.res;
+    e.bytes = r.device_bytes();
+    bool complete = (e.key.member || r.slabs.complete()) && r.d_xT && r.d_rhsT && r.d_gamma && r.d_fit_coef && !r.ws.empty();
+    for (auto &w : r.ws) {
         complete = complete && w.stream && w.trace.ready && w.inv_stream && w.ev_inv_grp && w.ev_inv_done;
-        w.eval_stream = w.stream;
         w.trace.used = 0;
         w.gls_enqueued = false;
         w.retried = false;
         w.retry_W = nullptr;
         w.sync_lead = nullptr;
-        if (e.key.member) w.M = w.dinv = nullptr, w.d_info = nullptr;  // (views of a group's slabs: set again by the adopting member)
-    }
-    const size_t cap = pool_cap_bytes();
-    if (!complete || e.bytes > cap) {  // a handle whose creation failed half way, or a pool too small for it
-        free_entry(e);
-        return;
+        w.M = w.dinv = nullptr, w.d_info = nullptr;  // (views: set again by the adopting handle)
     }
     // the pooled workspaces keep everything but their streams: those are idle now and may serve a handle of any shape (the last
     // workspace's set goes first, so that a handle which adopts this entry next finds every set where it was)
-    for (size_t i = e.ws.size(); i-- > 0;) give_streams(e.key.device, e.ws[i]);
-    std::list<PoolEntry> evicted;
-    std::list<SlabEntry> evicted_slabs;
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        const int dev = e.key.device;
-        g_pool.push_front(std::move(e));
-        // least recently returned entries OF THIS DEVICE go first (the newcomer itself stays), groups' slabs before them
-        while (pool_bytes_on(dev) > cap) {
-            auto sv = g_slab_pool.end();
-            for (auto it = g_slab_pool.begin(); it != g_slab_pool.end(); ++it)
-                if (it->device == dev) sv = it;
-            if (sv != g_slab_pool.end()) {
-                evicted_slabs.splice(evicted_slabs.begin(), g_slab_pool, sv);
-                continue;
-            }
-            auto victim = g_pool.end();
-            for (auto it = std::next(g_pool.begin()); it != g_pool.end(); ++it)
-                if (it->key.device == dev) victim = it;
-            if (victim == g_pool.end()) break;
-            evicted.splice(evicted.begin(), g_pool, victim);
-        }
-    }
-    for (auto &v : evicted) free_entry(v);
-    for (auto &v : evicted_slabs) free_slab_entry(v);
-}
-// a group's slabs: adopt pooled ones of exactly these sizes, or allocate
-static int group_slabs_take(GroupSlabs &g) {
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        for (auto it = g_slab_pool.begin(); it != g_slab_pool.end(); ++it)
-            if (it->device == g.device && it->bytes_M == g.bytes_M && it->bytes_D == g.bytes_D && it->bytes_I == g.bytes_I) {
-                g.M = it->M, g.D = it->D, g.I = it->I;
-                g_slab_pool.erase(it);
-                g_pool_hits++;
-                return EGX_SUCCESS;
-            }
-        g_pool_misses++;
-    }
-    EGX_HIP_CHECK(dev_malloc_bytes(reinterpret_cast<void **>(&g.M), g.bytes_M));
-    EGX_HIP_CHECK(dev_malloc_bytes(reinterpret_cast<void **>(&g.D), g.bytes_D));
-    EGX_HIP_CHECK(dev_malloc_bytes(reinterpret_cast<void **>(&g.I), g.bytes_I));
-    return EGX_SUCCESS;
+    if (complete && e.bytes <= pool_cap_bytes())
+        for (size_t i = r.ws.size(); i-- > 0;) r.ws[i].release_streams();
+    pool_free(g_pool.give(std::move(e), complete, pool_cap_bytes()));
 }
 }  // namespace egx
 // the last member of a group is gone: its slabs go to the pool (least recently returned slabs of the device make room), or
 // are freed when the pool is disabled, they alone exceed its bound, or the group was never completely allocated
 egx::GroupSlabs::~GroupSlabs() {
     using namespace egx;
-    SlabEntry e;
-    e.device = device, e.M = M, e.D = D, e.I = I, e.bytes_M = bytes_M, e.bytes_D = bytes_D, e.bytes_I = bytes_I;
-    M = D = nullptr, I = nullptr;
-    const size_t cap = pool_cap_bytes();
-    if (!(e.M && e.D && e.I) || e.bytes() > cap) {
-        int cur = 0;
-        const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-        free_slab_entry(e);
-        if (have_cur) (void)hipSetDevice(cur);
-        return;
-    }
-    std::list<PoolEntry> evicted;
-    std::list<SlabEntry> evicted_slabs;
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        const int dev = e.device;
-        g_slab_pool.push_front(e);
-        while (pool_bytes_on(dev) > cap) {
-            auto sv = g_slab_pool.end();
-            for (auto it = std::next(g_slab_pool.begin()); it != g_slab_pool.end(); ++it)
-                if (it->device == dev) sv = it;
-            if (sv != g_slab_pool.end()) {
-                evicted_slabs.splice(evicted_slabs.begin(), g_slab_pool, sv);
-                continue;
-            }
-            auto victim = g_pool.end();
-            for (auto it = g_pool.begin(); it != g_pool.end(); ++it)
-                if (it->key.device == dev) victim = it;
-            if (victim == g_pool.end()) break;
-            evicted.splice(evicted.begin(), g_pool, victim);
-        }
-    }
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    for (auto &v : evicted) free_entry(v);
-    for (auto &v : evicted_slabs) free_slab_entry(v);
-    if (have_cur) (void)hipSetDevice(cur);
+    Pool::Entry e;
+    e.key.slabs = true;
+    e.key.device = device;
+    e.key.bytes_M = slabs.M.bytes, e.key.bytes_D = slabs.D.bytes, e.key.bytes_I = slabs.I.bytes;
+    e.bytes = slabs.bytes();
+    e.res.device = device;
+    e.res.slabs = std::move(slabs);
+    const bool complete = e.res.slabs.complete();
+    pool_free(g_pool.give(std::move(e), complete, pool_cap_bytes()));
 }
 namespace egx {
 
@@ -806,7 +631,7 @@ int finish_eval(egx_gp *gp, Workspace &w, EvalResult &out, int keep) {
         g_chain_retries++;
         egx_gp *owner = gp;
         Workspace *wp = &w;
-        const std::vector<double> coef(w.h_coef, w.h_coef + w.retry_ncoef);
+        const std::vector<double> coef(w.h_coef.p, w.h_coef.p + w.retry_ncoef);
         EGX_RC(enqueue_eval_core(&owner, &wp, 1, &coef, w.retry_hcols, w.retry_W, true));
         EGX_HIP_CHECK(hipStreamSynchronize(w.eval_stream));
     }
@@ -1059,7 +884,7 @@ static int fit_run(egx_gp *const *gps, int len, const std::vector<double> *coefs
     SolveBatchPtrs bp;
     for (int j = 0; j < len; j++) {
         Workspace &w = gps[j]->ws[0];
-        if (!w.dW) EGX_HIP_CHECK(dev_malloc(&w.dW, sizeof(double) * block_inverse_doubles(gps[j]->n_pad)));
+        EGX_RC(w.dW.alloc(block_inverse_doubles(gps[j]->n_pad)));
         bp.M[j] = w.M, bp.dinv[j] = w.dinv, bp.dW[j] = w.dW, bp.rhs[j] = w.d_rhs, bp.vec[j] = w.d_vec;
     }
     if (len == 1) EGX_RC(launch_block_inverse(st, bp.M[0], lead->ld, lead->n_pad, bp.dinv[0], bp.dW[0]));
@@ -1130,7 +955,7 @@ static int fit_run(egx_gp *const *gps, int len, const std::vector<double> *coefs
             }
         }
         const EvalResult &res = hh[j].res;
-        gp->gamma.assign(w.h_vec, w.h_vec + gp->n);
+        gp->gamma.assign(w.h_vec.p, w.h_vec.p + gp->n);
         gp->theta = thfull[j];
         gp->likelihood = res.lkh;
         gp->sigma2 = res.sigma2n * gp->y_std * gp->y_std;  // algorithm.rs:1048
@@ -1309,15 +1134,7 @@ int32_t egx_set_tuning(const char *knob, int32_t value, int32_t *previous) {
 }
 
 void egx_pool_stats(int64_t *cached_bytes, int64_t *hits, int64_t *misses) {
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    if (cached_bytes) {
-        size_t b = 0;
-        for (const auto &e : g_pool) b += e.bytes;
-        for (const auto &e : g_slab_pool) b += e.bytes();
-        *cached_bytes = (int64_t)b;
-    }
-    if (hits) *hits = g_pool_hits;
-    if (misses) *misses = g_pool_misses;
+    g_pool.stats(cached_bytes, hits, misses);
 }
 
 void egx_gp_config_default(egx_gp_config *cfg) {
@@ -1352,16 +1169,27 @@ int32_t egx_regression_basis(int32_t mean, const double *x, int64_t n, int64_t d
     return EGX_SUCCESS;
 }
 
-// set by egx_gp_create_group around the creation of its members: the member takes slot `slot` of these slabs
-struct GroupCtx {
-    std::shared_ptr<GroupSlabs> slabs;
-    int slot = 0;
-    int64_t sync_off = 0;
-};
-static thread_local GroupCtx *t_group_ctx = nullptr;
+}  // extern "C"
 
-int32_t egx_gp_create(const egx_gp_config *cfg_in, const double *x, const double *y, int64_t n, int64_t d,
-                      egx_gp **out) {
+// a member of a group takes slot `slot` of the group's slabs
+struct GroupSlot {
+    std::shared_ptr<GroupSlabs> group;
+    int slot = 0;
+};
+// nothing of this handle may still run when its resources change hands
+static hipError_t sync_streams(egx_gp *gp) {
+    hipError_t e = hipSuccess;
+    for (auto &w : gp->ws)
+        for (hipStream_t st : {w.stream, w.lk.s2, w.lk.s3, w.inv_stream})
+            if (st) {
+                const hipError_t r = hipStreamSynchronize(st);
+                if (e == hipSuccess) e = r;
+            }
+    return e;
+}
+
+static int create_handle(const egx_gp_config *cfg_in, const double *x, const double *y, int64_t n, int64_t d, const GroupSlot *slot,
+                         egx_gp **out) {
     if (!out) {
         set_error("out handle pointer is NULL");
         return EGX_ERR_INVALID_VALUE;
@@ -1429,7 +1257,8 @@ int32_t egx_gp_create(const egx_gp_config *cfg_in, const double *x, const double
         set_error("device ordinal out of range");
         return EGX_ERR_INVALID_VALUE;
     }
-    egx_gp *gp = new egx_gp();
+    std::unique_ptr<egx_gp, decltype(&egx_gp_destroy)> owner(new egx_gp(), &egx_gp_destroy);  // (a failed creation unwinds through destroy)
+    egx_gp *gp = owner.get();
     gp->device = dev;
     gp->n = (int)n;
     gp->d = (int)d;
@@ -1445,11 +1274,12 @@ int32_t egx_gp_create(const egx_gp_config *cfg_in, const double *x, const double
         const char *e = std::getenv("EGX_GLS_DEVICE");  // 0 = always the host Householder route (A/B, debugging)
         gp->gls_device = gp->p >= 2 && !(e && e[0] == '0');
     }
-    // 256-column granularity lets every trailing update of a large fit use the 128x256 tile (N % 256 == 0)
-    gp->n_pad = (int)round_up(n, n >= 4096 ? kNB : kTile);
-    gp->rhs_pad = (int)round_up(gp->q, kRhsPad);
-    gp->m_tot = gp->n_pad + gp->rhs_pad;
+    // all workspaces' matrices / tile inverses / failure flags at fixed strides in one allocation each (lock-step batches)
+    const int nws = slot ? 1 : (cfg.n_workspaces < 1 ? 1 : cfg.n_workspaces);
+    const SlabGeometry geo = slab_geometry(n, p, nws);
+    gp->n_pad = geo.n_pad, gp->rhs_pad = geo.rhs_pad, gp->m_tot = geo.m_tot;
     gp->ld = gp->n_pad;
+    gp->stride_M = geo.stride_M, gp->stride_D = geo.stride_D, gp->stride_S = geo.stride_S, gp->sync_off = geo.sync_off;
     gp->x_raw.assign(x, x + n * d);
     gp->y_raw.assign(y, y + n);
     gp->xnorm.resize(n * d);
@@ -1461,16 +1291,8 @@ int32_t egx_gp_create(const egx_gp_config *cfg_in, const double *x, const double
     gp->F.resize(n * p);
     for (int64_t i = 0; i < n; i++) hm::regression_row(gp->mean, &gp->xnorm[i * d], d, &gp->F[i * p]);  // :866
 
-    auto fail = [&](int rc) {
-        egx_gp_destroy(gp);
-        return rc;
-    };
-    if (hipSetDevice(dev) != hipSuccess) {
-        set_error("hipSetDevice failed");
-        return fail(EGX_ERR_HIP);
-    }
-    int rc = chol_init();
-    if (rc) return fail(rc);
+    EGX_HIP_CHECK(hipSetDevice(dev));
+    EGX_RC(chol_init());
     // k-major, zero padded copies
     std::vector<double> xT((size_t)d * gp->n_pad, 0.0), rhsT((size_t)gp->q * gp->n_pad, 0.0);
     for (int64_t i0 = 0; i0 < n; i0 += 64) {  // 64-point blocks: the d write streams stay within a few cache lines each
@@ -1483,99 +1305,64 @@ int32_t egx_gp_create(const egx_gp_config *cfg_in, const double *x, const double
     for (int64_t l = 0; l < p; l++)
         for (int64_t i = 0; i < n; i++) rhsT[(size_t)l * gp->n_pad + i] = gp->F[i * p + l];
     for (int64_t i = 0; i < n; i++) rhsT[(size_t)p * gp->n_pad + i] = gp->ynorm[i];
-#define EGX_HIPF(expr)                                                            \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess) {                                                   \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));         \
-            (void)hipGetLastError();                                              \
-            return fail(EGX_ERR_HIP);                                             \
-        }                                                                         \
-    } while (0)
-    int nws = cfg.n_workspaces < 1 ? 1 : cfg.n_workspaces;
-    // all workspaces' matrices / tile inverses / failure flags at fixed strides in one allocation each (lock-step batches)
-    gp->stride_M = (int64_t)gp->m_tot * gp->ld;
-    gp->stride_D = round_up((int64_t)dinv_doubles(gp->n_pad), 64);
-    gp->stride_S = (int64_t)pipe_sync_ints(gp->n_pad, gp->m_tot);
-    gp->sync_off = round_up(nws, 64);
-    if (t_group_ctx) {
-        // member of a group (egx_gp_create_group): ONE workspace whose matrix, tile inverses, flag and hand-off words are slot
-        // `slot` of the group's slabs -- the members' matrices sit at the strides a lock-step launch needs
-        GroupCtx &g = *t_group_ctx;
-        nws = 1;
-        gp->group = g.slabs;
-        gp->group_slot = g.slot;
-        // (a destroyed member of a group of this shape left its workspace -- streams, events, pinned buffers -- and its
-        //  training-set buffers in the pool: adopt them; the slab views are this group's)
-        const bool pooled = pool_take(gp, 1);
-        gp->slab_M = g.slabs->M + (int64_t)g.slot * gp->stride_M;
-        gp->slab_D = g.slabs->D + (int64_t)g.slot * gp->stride_D;
-        gp->slab_I = g.slabs->I + g.slot;
-        gp->sync_off = g.sync_off + (int64_t)g.slot * gp->stride_S - g.slot;  // dev_sync(gp, 0) = the slot's words
-        if (pooled) {
-            Workspace &w = gp->ws[0];
-            w.M = gp->slab_M, w.dinv = gp->slab_D, w.d_info = gp->slab_I;
-            EGX_HIPF(take_streams(gp->device, w));  // (pooled workspaces are kept without streams)
-        } else {
-            EGX_HIPF(dev_malloc(&gp->d_xT, sizeof(double) * 2 * xT.size()));
-            EGX_HIPF(dev_malloc(&gp->d_rhsT, sizeof(double) * rhsT.size()));
-            EGX_HIPF(dev_malloc(&gp->d_gamma, sizeof(double) * gp->n_pad));
-            EGX_HIPF(dev_malloc(&gp->d_fit_coef, sizeof(double) * ((size_t)d * (gp->has_w ? gp->h : 1) + 2 * (size_t)d)));
-            gp->ws.resize(1);
-            rc = alloc_workspace(gp, gp->ws[0], 0);
-            if (rc) return fail(rc);
-        }
-    } else if (pool_take(gp, nws)) {  // a destroyed handle of this shape left its resources behind; its streams went to the free list
-        for (auto &w : gp->ws) EGX_HIPF(take_streams(gp->device, w));
-    } else {  // allocate
-        EGX_HIPF(dev_malloc(&gp->d_xT, sizeof(double) * 2 * xT.size()));  // + dev_xs_fit()
-        EGX_HIPF(dev_malloc(&gp->d_rhsT, sizeof(double) * rhsT.size()));
-        EGX_HIPF(dev_malloc(&gp->d_gamma, sizeof(double) * gp->n_pad));
-        EGX_HIPF(dev_malloc(&gp->d_fit_coef, sizeof(double) * ((size_t)d * (gp->has_w ? gp->h : 1) + 2 * (size_t)d)));
-        EGX_HIPF(dev_malloc(&gp->slab_M, sizeof(double) * (size_t)gp->stride_M * nws));
-        EGX_HIPF(dev_malloc(&gp->slab_D, sizeof(double) * (size_t)gp->stride_D * nws));
-        EGX_HIPF(dev_malloc(&gp->slab_I, sizeof(int) * slab_I_ints(gp, nws)));
-        gp->ws.resize(nws);
-        for (int i = 0; i < nws; i++) {
-            rc = alloc_workspace(gp, gp->ws[i], i);
-            if (rc) return fail(rc);
-        }
+    if (slot) {  // (before the pool is asked: a member's resources are keyed apart from a lone handle's)
+        gp->group = slot->group;
+        gp->group_slot = slot->slot;
     }
-    EGX_HIPF(hipMemcpy(gp->d_xT, xT.data(), sizeof(double) * xT.size(), hipMemcpyHostToDevice));
-    EGX_HIPF(hipMemcpy(gp->d_rhsT, rhsT.data(), sizeof(double) * rhsT.size(), hipMemcpyHostToDevice));
+    // a destroyed handle of this shape left its resources behind (without streams: those went to the idle list); a member of a
+    // group adopts a destroyed member's workspace and training-set buffers, the slabs are its group's
+    HandleRes pooled;
+    if (g_pool.take(pool_key(gp, nws), pooled)) {
+        static_cast<HandleRes &>(*gp) = std::move(pooled);
+        for (auto &w : gp->ws) EGX_HIP_CHECK(take_streams(gp->device, w));
+    } else {
+        EGX_RC(gp->d_xT.alloc(2 * xT.size()));  // + dev_xs_fit()
+        EGX_RC(gp->d_rhsT.alloc(rhsT.size()));
+        EGX_RC(gp->d_gamma.alloc((size_t)gp->n_pad));
+        EGX_RC(gp->d_fit_coef.alloc((size_t)d * (gp->has_w ? gp->h : 1) + 2 * (size_t)d));
+        if (!slot) EGX_RC(alloc_slabs(gp->slabs, geo));
+        gp->ws.resize((size_t)nws);
+        for (auto &w : gp->ws) EGX_RC(alloc_workspace(gp, w));
+    }
+    if (slot) {
+        // ONE workspace whose matrix, tile inverses, flag and hand-off words are slot `slot` of the group's slabs -- the members'
+        // matrices sit at the strides a lock-step launch needs
+        const GroupSlabs &g = *slot->group;
+        gp->slab_M = g.slabs.M + (int64_t)slot->slot * gp->stride_M;
+        gp->slab_D = g.slabs.D + (int64_t)slot->slot * gp->stride_D;
+        gp->slab_I = g.slabs.I + slot->slot;
+        gp->sync_off = g.sync_off + (int64_t)slot->slot * gp->stride_S - slot->slot;  // dev_sync(gp, 0) = the slot's words
+    } else {
+        gp->slab_M = gp->slabs.M, gp->slab_D = gp->slabs.D, gp->slab_I = gp->slabs.I;
+    }
+    for (int i = 0; i < nws; i++) set_views(gp, gp->ws[(size_t)i], i);
+    EGX_HIP_CHECK(hipMemcpy(gp->d_xT, xT.data(), sizeof(double) * xT.size(), hipMemcpyHostToDevice));
+    EGX_HIP_CHECK(hipMemcpy(gp->d_rhsT, rhsT.data(), sizeof(double) * rhsT.size(), hipMemcpyHostToDevice));
     {  // normalisation parameters for the query-side kernel (gp_predict.hip upload_queries)
         std::vector<double> par(gp->x_mean);
         par.insert(par.end(), gp->x_std.begin(), gp->x_std.end());
-        EGX_HIPF(hipMemcpy(dev_xnorm(gp), par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));
+        EGX_HIP_CHECK(hipMemcpy(dev_xnorm(gp), par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));
     }
     gp->lockstep = default_lockstep(nws, gp->n_pad);  // candidates of a likelihood batch factored in lock-step: egx_gp_set_lockstep
     gp->sched = schedule_for(gp->n_pad, gp->lockstep, nws);
-    if (t_group_ctx) gp->sched.flow = gp->sched.flow_tail = 0;  // (members of a group are factored in lock-step: the flow launch takes one matrix)
-    rc = pipe_prepare(gp->n_pad, gp->m_tot, gp->sched);  // the chain launches' task lists: not inside the first evaluation
-    if (rc) return fail(rc);
-    *out = gp;
+    if (slot) gp->sched.flow = gp->sched.flow_tail = 0;  // (members of a group are factored in lock-step: the flow launch takes one matrix)
+    EGX_RC(pipe_prepare(gp->n_pad, gp->m_tot, gp->sched));  // the chain launches' task lists: not inside the first evaluation
+    *out = owner.release();
     return EGX_SUCCESS;
+}
+
+extern "C" {
+
+int32_t egx_gp_create(const egx_gp_config *cfg, const double *x, const double *y, int64_t n, int64_t d, egx_gp **out) {
+    return create_handle(cfg, x, y, n, d, nullptr, out);
 }
 
 void egx_gp_destroy(egx_gp *gp) {
     if (!gp) return;
     hipSetDevice(gp->device);
-    // nothing of this handle may still run when its resources change hands
-    for (auto &w : gp->ws) {
-        if (w.stream) (void)hipStreamSynchronize(w.stream);
-        if (w.lk.s2) (void)hipStreamSynchronize(w.lk.s2);
-        if (w.lk.s3) (void)hipStreamSynchronize(w.lk.s3);
-        if (w.inv_stream) (void)hipStreamSynchronize(w.inv_stream);
-    }
+    (void)sync_streams(gp);
     (void)hipGetLastError();
-    if (gp->group) gp->slab_M = gp->slab_D = nullptr, gp->slab_I = nullptr;  // (views of the group's slabs: freed with the last member)
     pool_give(gp);
-    if (gp->d_W) hipFree(gp->d_W);
-    if (gp->d_neg_invkf) hipFree(gp->d_neg_invkf);
-    for (double *q : {gp->sp_R, gp->sp_P, gp->sp_y, gp->sp_z, gp->sp_wt, gp->sp_out, gp->sp_xq})
-        if (q) hipFree(q);
-    if (gp->slab_W) hipFree(gp->slab_W);
-    if (gp->d_wabs) hipFree(gp->d_wabs);
     delete gp;
 }
 
@@ -1672,55 +1459,29 @@ int32_t egx_gp_shrink(egx_gp *gp, int32_t n_keep) {
     std::unique_lock<std::shared_mutex> lock(gp->mu);
     EGX_RC(set_device(gp));
     const int nws = (int)gp->ws.size();
-    for (auto &w : gp->ws) {  // nothing of this handle may still run
-        if (w.stream) EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
-        if (w.lk.s2) EGX_HIP_CHECK(hipStreamSynchronize(w.lk.s2));
-        if (w.lk.s3) EGX_HIP_CHECK(hipStreamSynchronize(w.lk.s3));
-        if (w.inv_stream) EGX_HIP_CHECK(hipStreamSynchronize(w.inv_stream));
-    }
-    if (gp->slab_W) {  // the theta-gradient's C^-T buffers are scratch between calls
-        (void)hipFree(gp->slab_W);
-        gp->slab_W = nullptr;
-        gp->slab_W_count = 0;
-    }
+    EGX_HIP_CHECK(sync_streams(gp));
+    gp->slab_W.reset();  // the theta-gradient's C^-T buffers are scratch between calls
+    gp->slab_W_count = 0;
     if (n_keep >= nws) return EGX_SUCCESS;
     // the first n_keep workspaces sit at the front of the slabs: smaller slabs, one device-to-device copy each
-    double *nM = nullptr, *nD = nullptr;
-    int *nI = nullptr;
-    if (dev_malloc(&nM, sizeof(double) * (size_t)gp->stride_M * n_keep) != hipSuccess ||
-        dev_malloc(&nD, sizeof(double) * (size_t)gp->stride_D * n_keep) != hipSuccess ||
-        dev_malloc(&nI, sizeof(int) * slab_I_ints(gp, n_keep)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (nM) (void)hipFree(nM);
-        if (nD) (void)hipFree(nD);
-        if (nI) (void)hipFree(nI);
+    const SlabGeometry geo = slab_geometry(gp->n, gp->p, n_keep);
+    Slabs smaller;
+    if (alloc_slabs(smaller, geo) != EGX_SUCCESS) {
         set_error("egx_gp_shrink: no memory for the smaller slabs (the handle is unchanged)");
         return EGX_ERR_HIP;
     }
-    hipError_t ce = hipMemcpy(nM, gp->slab_M, sizeof(double) * (size_t)gp->stride_M * n_keep, hipMemcpyDeviceToDevice);
-    if (ce == hipSuccess) ce = hipMemcpy(nD, gp->slab_D, sizeof(double) * (size_t)gp->stride_D * n_keep, hipMemcpyDeviceToDevice);
-    if (ce == hipSuccess) ce = hipMemcpy(nI, gp->slab_I, sizeof(int) * (size_t)n_keep, hipMemcpyDeviceToDevice);
+    hipError_t ce = hipMemcpy(smaller.M, gp->slabs.M, smaller.M.bytes, hipMemcpyDeviceToDevice);
+    if (ce == hipSuccess) ce = hipMemcpy(smaller.D, gp->slabs.D, smaller.D.bytes, hipMemcpyDeviceToDevice);
+    if (ce == hipSuccess) ce = hipMemcpy(smaller.I, gp->slabs.I, sizeof(int) * (size_t)n_keep, hipMemcpyDeviceToDevice);
     if (ce != hipSuccess) {  // the handle keeps its slabs, the new ones go back
-        (void)hipFree(nM);
-        (void)hipFree(nD);
-        (void)hipFree(nI);
         set_error(std::string("egx_gp_shrink: copying the kept workspaces failed (the handle is unchanged): ") + hipGetErrorString(ce));
         return EGX_ERR_HIP;
     }
-    (void)hipFree(gp->slab_M);
-    (void)hipFree(gp->slab_D);
-    (void)hipFree(gp->slab_I);
-    gp->slab_M = nM;
-    gp->slab_D = nD;
-    gp->slab_I = nI;
+    gp->slabs = std::move(smaller);
+    gp->slab_M = gp->slabs.M, gp->slab_D = gp->slabs.D, gp->slab_I = gp->slabs.I;
     gp->sync_off = round_up(n_keep, 64);  // (the hand-off words need no copy: every factorisation zeroes its own)
-    for (int i = n_keep; i < nws; i++) free_workspace(gp->ws[i], gp->device);
     gp->ws.resize((size_t)n_keep);
-    for (int i = 0; i < n_keep; i++) {
-        gp->ws[i].M = gp->slab_M + (int64_t)i * gp->stride_M;
-        gp->ws[i].dinv = gp->slab_D + (int64_t)i * gp->stride_D;
-        gp->ws[i].d_info = gp->slab_I + i;
-    }
+    for (int i = 0; i < n_keep; i++) set_views(gp, gp->ws[(size_t)i], i);
     {
         std::lock_guard<std::mutex> pl(gp->pool_mu);
         gp->ws_busy.assign((size_t)n_keep, 0);
@@ -1780,31 +1541,25 @@ int32_t egx_gp_create_group(const egx_gp_config *cfg_in, const double *x, const 
     int dev = cfg.device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
     EGX_HIP_CHECK(hipSetDevice(dev));
-    // the members' geometry (the formulas of egx_gp_create)
     if (cfg.mean < 0 || cfg.mean > 2) {
         set_error("unknown regression model");
         return EGX_ERR_INVALID_VALUE;
     }
-    const int64_t p = hm::regression_ncols(cfg.mean, d);
-    const int n_pad = (int)round_up(n, n >= 4096 ? kNB : kTile);
-    const int m_tot = n_pad + (int)round_up(p + 1, kRhsPad);
-    const int64_t sM = (int64_t)m_tot * n_pad, sD = round_up((int64_t)dinv_doubles(n_pad), 64), sS = (int64_t)pipe_sync_ints(n_pad, m_tot);
-    GroupCtx ctx;
-    ctx.slabs = std::make_shared<GroupSlabs>();
-    ctx.slabs->device = dev;
-    ctx.slabs->k = k;
-    ctx.sync_off = round_up(k, 64);
-    ctx.slabs->bytes_M = sizeof(double) * (size_t)sM * k;
-    ctx.slabs->bytes_D = sizeof(double) * (size_t)sD * k;
-    ctx.slabs->bytes_I = sizeof(int) * ((size_t)ctx.sync_off + (size_t)sS * k);
-    EGX_RC(group_slabs_take(*ctx.slabs));
+    // the group's slabs: pooled ones of exactly these sizes, or new ones
+    const SlabGeometry geo = slab_geometry(n, hm::regression_ncols(cfg.mean, d), k);
+    GroupSlot slot;
+    slot.group = std::make_shared<GroupSlabs>();
+    slot.group->device = dev;
+    slot.group->k = k;
+    slot.group->sync_off = geo.sync_off;
+    HandleRes pooled;
+    if (g_pool.take(slabs_key(dev, geo), pooled))
+        slot.group->slabs = std::move(pooled.slabs);
+    else
+        EGX_RC(alloc_slabs(slot.group->slabs, geo));
     int rc = EGX_SUCCESS;
-    for (int32_t j = 0; j < k && rc == EGX_SUCCESS; j++) {
-        ctx.slot = j;
-        t_group_ctx = &ctx;
-        rc = egx_gp_create(&cfg, x + (size_t)j * n * d, y + (size_t)j * n, n, d, &out[j]);
-        t_group_ctx = nullptr;
-    }
+    for (slot.slot = 0; slot.slot < k && rc == EGX_SUCCESS; slot.slot++)
+        rc = create_handle(&cfg, x + (size_t)slot.slot * n * d, y + (size_t)slot.slot * n, n, d, &slot, &out[slot.slot]);
     if (rc != EGX_SUCCESS)
         for (int32_t j = 0; j < k; j++) {
             if (out[j]) egx_gp_destroy(out[j]);

@@ -65,9 +65,8 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
             }
             (void)hipGetLastError();
             if (gp->winv_epoch != gp->fit_epoch) {  // give a half-built cache back
-                if (gp->d_W) (void)hipFree(gp->d_W);
-                if (gp->d_neg_invkf) (void)hipFree(gp->d_neg_invkf);
-                gp->d_W = gp->d_neg_invkf = nullptr;
+                gp->d_W.reset();
+                gp->d_neg_invkf.reset();
             }
             gp->winv_fail_epoch = gp->fit_epoch;
         }
@@ -193,8 +192,8 @@ int ensure_winv(egx_gp *gp) {
     Workspace &w = gp->ws[0];
     const int n_pad = gp->n_pad;
     const size_t sq = (size_t)n_pad * n_pad;
-    if (!gp->d_W) EGX_HIP_CHECK(dev_malloc(&gp->d_W, sizeof(double) * sq));
-    if (!gp->d_neg_invkf) EGX_HIP_CHECK(dev_malloc(&gp->d_neg_invkf, sizeof(double) * (size_t)n_pad * gp->rhs_pad));
+    EGX_RC(gp->d_W.alloc(sq));
+    EGX_RC(gp->d_neg_invkf.alloc((size_t)n_pad * gp->rhs_pad));
     // the rows of the identity, written on the device as far as the solve and the readers of W touch them (everything
     // on and above the diagonal 128-tiles): no host round trip, no 2 GiB memset
     EGX_RC(launch_identity_rows(w.stream, gp->d_W, n_pad, n_pad));
@@ -218,20 +217,19 @@ int ensure_winv(egx_gp *gp) {
 // Small batches (EGO's infill optimiser asks for one point at a time): per query two memory-bound passes over the cached
 // W = C^-T instead of the batched block solves, then the x-gradient contraction with a per-training-point weight VECTOR.
 static int small_path_buffers(egx_gp *gp) {
-    if (gp->sp_R) return EGX_SUCCESS;
+    if (gp->sp_xq) return EGX_SUCCESS;  // (the last one allocated)
     const int n = gp->n, n_pad = gp->n_pad, d = gp->d;
     int nsplit = (n + 63) / 64;
     if (nsplit > 512) nsplit = 512;
     const int slabs = (n + 63) / 64, per = (slabs + nsplit - 1) / nsplit;
     gp->sp_nsplit = (slabs + per - 1) / per;
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_R, sizeof(double) * (size_t)kTile * n_pad));
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_P, sizeof(double) * (size_t)32 * n_pad));
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_y, sizeof(double) * n_pad));
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_z, sizeof(double) * n_pad));
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_wt, sizeof(double) * n_pad));
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_out, sizeof(double) * (size_t)gp->sp_nsplit * kTile * d));
-    EGX_HIP_CHECK(dev_malloc(&gp->sp_xq, sizeof(double) * (size_t)d * kTile));
-    return EGX_SUCCESS;
+    EGX_RC(gp->sp_R.alloc((size_t)kTile * n_pad));
+    EGX_RC(gp->sp_P.alloc((size_t)32 * n_pad));
+    EGX_RC(gp->sp_y.alloc((size_t)n_pad));
+    EGX_RC(gp->sp_z.alloc((size_t)n_pad));
+    EGX_RC(gp->sp_wt.alloc((size_t)n_pad));
+    EGX_RC(gp->sp_out.alloc((size_t)gp->sp_nsplit * kTile * d));
+    return gp->sp_xq.alloc((size_t)d * kTile);
 }
 
 // normalised query a of xq, k-major with the other 127 slots zero, into the cached device slab; xn (d) on the host

@@ -33,6 +33,7 @@
 // 16x16x4 instruction per SIMD): the matrix core is used because one instruction carries 2048
 // flops with two 8-byte operands per lane, which keeps LDS and issue pressure negligible.
 #include "egx_internal.h"
+#include "dev_mem.h"
 #include "potf2_blocks.h"
 #include "mfma_gemm_core.h"
 
@@ -476,13 +477,14 @@ __global__ __launch_bounds__(512, 2) void k_gemm_stream(double *__restrict__ C, 
 // mode 1: start recording into a fresh device buffer of `cap` records; mode 0: stop, copy the records taken (at most cap) to
 // `out` (kStraceWords words each) and return their number
 extern "C" long long egx_dev_stream_trace(int mode, long long *out, long long cap) {
-    static long long *dbuf = nullptr;
+    static auto &owned = *new egx::DevMem<long long>;  // (never destroyed)
     static long long dcap = 0;
-    long long *null = nullptr;
+    long long *null = nullptr, *dbuf = owned.p;
     if (mode == 1) {
-        if (dbuf) (void)hipFree(dbuf);
+        owned.reset();
         dcap = cap;
-        if (hipMalloc(&dbuf, sizeof(long long) * (16 + egx::kStraceWords * cap)) != hipSuccess) return -1;
+        if (owned.alloc((size_t)(16 + egx::kStraceWords * cap)) != EGX_SUCCESS) return -1;
+        dbuf = owned.p;
         (void)hipMemset(dbuf, 0, sizeof(long long) * (16 + egx::kStraceWords * cap));
         (void)hipMemcpy(dbuf + 1, &cap, sizeof(long long), hipMemcpyHostToDevice);
         if (hipMemcpyToSymbol(HIP_SYMBOL(egx::g_strace), &dbuf, sizeof(dbuf)) != hipSuccess) return -2;
@@ -496,8 +498,7 @@ extern "C" long long egx_dev_stream_trace(int mode, long long *out, long long ca
     if (taken > dcap) taken = dcap;
     if (taken > cap) taken = cap;
     if (out && taken > 0) (void)hipMemcpy(out, dbuf + 16, sizeof(long long) * egx::kStraceWords * taken, hipMemcpyDeviceToHost);
-    (void)hipFree(dbuf);
-    dbuf = nullptr;
+    owned.reset();
     return taken;
 }
 namespace egx {
@@ -1834,18 +1835,13 @@ int mfma_probe(double *max_abs_err) {
             hA[i * 16 + j] = 1.0 + i * 0.37 - j * 0.11 + (i * j % 5) * 0.013;
             hB[i * 16 + j] = -0.5 + i * 0.29 + j * j * 0.017 - (i % 3) * 0.21;
         }
-    double *dA, *dB, *dC;
-    EGX_HIP_CHECK(hipMalloc(&dA, sizeof hA));
-    EGX_HIP_CHECK(hipMalloc(&dB, sizeof hB));
-    EGX_HIP_CHECK(hipMalloc(&dC, sizeof hC));
+    DevBuf dA, dB, dC;
+    if (dA.alloc(256) || dB.alloc(256) || dC.alloc(256)) return EGX_ERR_HIP;
     EGX_HIP_CHECK(hipMemcpy(dA, hA, sizeof hA, hipMemcpyHostToDevice));
     EGX_HIP_CHECK(hipMemcpy(dB, hB, sizeof hB, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mfma_probe, dim3(1), dim3(64), 0, 0, dA, dB, dC);
+    hipLaunchKernelGGL(k_mfma_probe, dim3(1), dim3(64), 0, 0, dA.p, dB.p, dC.p);
     EGX_HIP_CHECK(hipGetLastError());
     EGX_HIP_CHECK(hipMemcpy(hC, dC, sizeof hC, hipMemcpyDeviceToHost));
-    hipFree(dA);
-    hipFree(dB);
-    hipFree(dC);
     double worst = 0.0;
     for (int i = 0; i < 16; i++)
         for (int j = 0; j < 16; j++) {

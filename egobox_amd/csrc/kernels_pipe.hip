@@ -45,6 +45,7 @@
 // group of ONE panel gives the same bits as the separate launches, tools/pipe_check.hip); FINE / COARSE add their K = 256
 // products in an order of their own (fixed: a matrix gets the same bits alone and in a lock-step batch, on any grid size).
 #include "egx_internal.h"
+#include "dev_mem.h"
 #include "mfma_gemm_core.h"
 #include "potf2_blocks.h"
 #include "pipe_tasks.h"
@@ -1272,12 +1273,23 @@ bool pipe_fits(int nz, int np) {
 // (the task list of a launch and its order: pipe_tasks.h, host-testable)
 // A plan = the task list of one (device, shape, group) on the device.  Built when a handle is created (pipe_prepare: no
 // allocation and no copy inside the first launch), kept for the life of the process or until egx_trim (pipe_release_plans).
-struct PipePlan {
+struct PipePlan {  // (what a launch takes: views of the owned lists below)
     PipeTask *d_tasks = nullptr;
     int ntasks = 0;
 };
+struct FlowPlan {
+    PipeTask *d_tasks = nullptr;
+    int *d_coff = nullptr;
+    int ntasks = 0;
+};
+struct OwnedPlan {
+    DevMem<PipeTask> tasks;
+    DevMem<int> coff;  // flow launches only
+    int ntasks = 0;
+};
 static std::mutex g_plan_mu;
-static std::map<std::tuple<int, int, int, int, int, int>, PipePlan> g_plans;
+// (never destroyed: what is left at exit is not freed behind the runtime's back)
+static auto &g_plans = *new std::map<std::tuple<int, int, int, int, int, int>, OwnedPlan>;
 
 static int pipe_plan_get(int dev, int n_pad, int m_tot, int g0, int np, int rt, PipePlan &out) {
     std::lock_guard<std::mutex> lock(g_plan_mu);
@@ -1285,30 +1297,21 @@ static int pipe_plan_get(int dev, int n_pad, int m_tot, int g0, int np, int rt, 
     auto it = g_plans.find(key);
     if (it == g_plans.end()) {
         const std::vector<PipeTask> tasks = pipe_tasks(n_pad, m_tot, g0, np, rt, kPipeLookAhead);
-        PipePlan pl;
+        OwnedPlan pl;
         pl.ntasks = (int)tasks.size();
         if (pl.ntasks > 0) {
-            EGX_HIP_CHECK(dev_malloc(&pl.d_tasks, sizeof(PipeTask) * tasks.size()));
+            EGX_RC_PIPE(pl.tasks.alloc(tasks.size()));
             // (synchronous: the source is a temporary.  Handles prepare their plans at creation, so this is not on a launch path
             //  except for callers without a handle -- egx_potrf, the tools -- and after egx_trim)
-            const hipError_t e = hipMemcpy(pl.d_tasks, tasks.data(), sizeof(PipeTask) * tasks.size(), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(pl.d_tasks);
-                EGX_HIP_CHECK(e);
-            }
+            EGX_HIP_CHECK(hipMemcpy(pl.tasks, tasks.data(), sizeof(PipeTask) * tasks.size(), hipMemcpyHostToDevice));
         }
-        it = g_plans.emplace(key, pl).first;
+        it = g_plans.emplace(key, std::move(pl)).first;
     }
-    out = it->second;
+    out.d_tasks = it->second.tasks, out.ntasks = it->second.ntasks;
     return EGX_SUCCESS;
 }
 // ---- flow launch (pipe_flow.h): the critical lists of all stages, one after the other, and where each stage starts
-struct FlowPlan {
-    PipeTask *d_tasks = nullptr;
-    int *d_coff = nullptr;
-    int ntasks = 0;
-};
-static std::map<std::tuple<int, int, int>, FlowPlan> g_flow_plans;  // (device, n_pad, m_tot); under g_plan_mu
+static auto &g_flow_plans = *new std::map<std::tuple<int, int, int>, OwnedPlan>;  // (device, n_pad, m_tot); under g_plan_mu
 static int flow_plan_get(int dev, int n_pad, int m_tot, FlowPlan &out) {
     std::lock_guard<std::mutex> lock(g_plan_mu);
     const auto key = std::make_tuple(dev, n_pad, m_tot);
@@ -1323,20 +1326,15 @@ static int flow_plan_get(int dev, int n_pad, int m_tot, FlowPlan &out) {
             tasks.insert(tasks.end(), st.begin(), st.end());
         }
         coff[(size_t)NP] = (int)tasks.size();
-        FlowPlan pl;
+        OwnedPlan pl;
         pl.ntasks = (int)tasks.size();
-        EGX_HIP_CHECK(dev_malloc(&pl.d_tasks, sizeof(PipeTask) * (tasks.size() + 1)));
-        hipError_t e = dev_malloc(&pl.d_coff, sizeof(int) * coff.size());
-        if (e == hipSuccess) e = hipMemcpy(pl.d_tasks, tasks.data(), sizeof(PipeTask) * tasks.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(pl.d_coff, coff.data(), sizeof(int) * coff.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(pl.d_tasks);
-            if (pl.d_coff) (void)hipFree(pl.d_coff);
-            EGX_HIP_CHECK(e);
-        }
-        it = g_flow_plans.emplace(key, pl).first;
+        EGX_RC_PIPE(pl.tasks.alloc(tasks.size() + 1));
+        EGX_RC_PIPE(pl.coff.alloc(coff.size()));
+        EGX_HIP_CHECK(hipMemcpy(pl.tasks, tasks.data(), sizeof(PipeTask) * tasks.size(), hipMemcpyHostToDevice));
+        EGX_HIP_CHECK(hipMemcpy(pl.coff, coff.data(), sizeof(int) * coff.size(), hipMemcpyHostToDevice));
+        it = g_flow_plans.emplace(key, std::move(pl)).first;
     }
-    out = it->second;
+    out.d_tasks = it->second.tasks, out.d_coff = it->second.coff, out.ntasks = it->second.ntasks;
     return EGX_SUCCESS;
 }
 // the plans a handle of this shape and schedule will launch, on the current device (egx_gp_create / egx_gp_set_lockstep)
@@ -1369,27 +1367,20 @@ size_t pipe_release_plans() {
     int cur = 0;
     const bool have_cur = hipGetDevice(&cur) == hipSuccess;
     int synced = -1;
-    for (auto &kv : g_plans) {
-        const int dev = std::get<0>(kv.first);
-        if (!kv.second.d_tasks) continue;
-        if (dev != synced) {
-            if (hipSetDevice(dev) != hipSuccess) continue;
+    auto sync_once = [&](int dev) {
+        if (dev != synced && hipSetDevice(dev) == hipSuccess) {
             (void)hipDeviceSynchronize();
             synced = dev;
         }
-        (void)hipFree(kv.second.d_tasks);
+    };
+    for (auto &kv : g_plans) {
+        if (!kv.second.tasks) continue;
+        sync_once(std::get<0>(kv.first));
         bytes += sizeof(PipeTask) * (size_t)kv.second.ntasks;
     }
     g_plans.clear();
     for (auto &kv : g_flow_plans) {
-        const int dev = std::get<0>(kv.first);
-        if (dev != synced) {
-            if (hipSetDevice(dev) != hipSuccess) continue;
-            (void)hipDeviceSynchronize();
-            synced = dev;
-        }
-        if (kv.second.d_tasks) (void)hipFree(kv.second.d_tasks);
-        if (kv.second.d_coff) (void)hipFree(kv.second.d_coff);
+        sync_once(std::get<0>(kv.first));
         bytes += sizeof(PipeTask) * (size_t)kv.second.ntasks;
     }
     g_flow_plans.clear();

@@ -6,19 +6,6 @@
 
 #include "gp_handle.h"
 
-struct Dev {
-    double *p = nullptr;
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        EGX_HIP_CHECK(egx::dev_malloc(&p, sizeof(double) * (n ? n : 1)));
-        return EGX_SUCCESS;
-    }
-};
-
 struct egx_sgp {
     int device = 0, corr = 0, method = 0;
     double nugget = 0.0;
@@ -26,8 +13,8 @@ struct egx_sgp {
     std::vector<double> y_host;
     double yty = 0.0;
     hipStream_t stream = nullptr;
-    Dev xT, zT, y, coef, RT, W, G, P, Kz, A, dinv_z, dinv_a, s0, sb, diag, brow, vec, wall, tmpv;
-    int *d_info = nullptr;
+    egx::DevBuf xT, zT, y, coef, RT, W, G, P, Kz, A, dinv_z, dinv_a, s0, sb, diag, brow, vec, wall, tmpv;
+    egx::DevMem<int> d_info;
     std::mutex mu;
     // fitted state
     bool fitted = false;

@@ -214,7 +214,6 @@ void egx_sgp_config_default(egx_sgp_config *cfg) {
 void egx_sgp_destroy(egx_sgp *g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
-    if (g->d_info) (void)hipFree(g->d_info);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -323,7 +322,7 @@ int32_t egx_sgp_create(const egx_sgp_config *cfg_in, const double *x, const doub
     SGP_TRY(g->vec.alloc(zp));
     SGP_TRY(g->tmpv.alloc(zp));
     SGP_TRY(g->wall.alloc(block_inverse_doubles(zp)));
-    SGP_HIP(dev_malloc(&g->d_info, 2 * sizeof(int)));
+    SGP_TRY(g->d_info.alloc(2));
     SGP_HIP(hipMemcpy(g->xT.p, xT.data(), sizeof(double) * xT.size(), hipMemcpyHostToDevice));
     SGP_HIP(hipMemcpy(g->zT.p, zT.data(), sizeof(double) * zT.size(), hipMemcpyHostToDevice));
     SGP_HIP(hipMemcpy(g->y.p, yp.data(), sizeof(double) * np, hipMemcpyHostToDevice));

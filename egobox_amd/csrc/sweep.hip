@@ -105,8 +105,8 @@ struct egx_sweep {
     hipStream_t stream = nullptr;
     // staging of the all-gather, allocated once: kChunk doubles per rank
     static constexpr int64_t kChunk = 262144;  // 2 MiB per rank: a 100 000-point mean + variance pair goes in one piece
-    double *d_send = nullptr, *d_recv = nullptr;
-    double *h_send = nullptr, *h_recv = nullptr;  // pinned
+    egx::DevMem<double> d_send, d_recv;
+    egx::PinMem<double> h_send, h_recv;
     std::mutex mu;
     int64_t n_allgathers = 0;
     // dynamic assignment
@@ -393,12 +393,9 @@ int32_t egx_sweep_create(const egx_gp_config *cfg_in, const double *x, const dou
         return fail(EGX_ERR_HIP);
     }
     {   // staging of the collective: allocated here, never inside a collective call
-        const size_t one = sizeof(double) * (size_t)egx_sweep::kChunk;
-        if (dev_malloc(&sw->d_send, one) != hipSuccess || dev_malloc(&sw->d_recv, one * world) != hipSuccess ||
-            hipHostMalloc(&sw->h_send, one, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(&sw->h_recv, one * world, hipHostMallocDefault) != hipSuccess) {
+        const size_t one = (size_t)egx_sweep::kChunk;
+        if (sw->d_send.alloc(one) || sw->d_recv.alloc(one * world) || sw->h_send.alloc(one) || sw->h_recv.alloc(one * world)) {
             set_error("egx_sweep_create: staging buffers");
-            (void)hipGetLastError();
             return fail(EGX_ERR_HIP);
         }
     }
@@ -470,10 +467,6 @@ void egx_sweep_destroy(egx_sweep *sw) {
     if (!sw) return;
     if (sw->gp) hipSetDevice(sw->gp->device);
     if (sw->comm) rccl().CommDestroy(sw->comm);
-    if (sw->d_send) hipFree(sw->d_send);
-    if (sw->d_recv) hipFree(sw->d_recv);
-    if (sw->h_send) hipHostFree(sw->h_send);
-    if (sw->h_recv) hipHostFree(sw->h_recv);
     if (sw->stream) hipStreamDestroy(sw->stream);
     if (sw->counters) {
         if (sw->counters_shared) {
