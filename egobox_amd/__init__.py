@@ -5,7 +5,7 @@ if the library has not been built, and model construction fails with NoDeviceErr
 no CPU or PyTorch fallback for the compute path.
 """
 from . import _lib
-from ._lib import (EgxError, InvalidValueError, LikelihoodComputationError, LinalgError, NoDeviceError,
+from ._lib import (ClusteringError, EgxError, InvalidValueError, LikelihoodComputationError, LinalgError, NoDeviceError,
                    NotFittedError, PeerError, SampleError)
 
 _lib.load()  # fail loudly at import when the HIP library is missing
@@ -19,6 +19,7 @@ from .multistart import prepare_multistart, theta_sweep_candidates  # noqa: E402
 from .sgp import (Inducings, ParamTuning, SgpHandle, SgpParams, SparseGaussianProcess, SparseGpMix, SparseGpx,  # noqa: E402
                   SparseMethod)
 from . import infill, moe, workload  # noqa: E402
+from .moe import GaussianMixture, GpMixture, GpMixtureParams  # noqa: E402
 from .infill import EI, LOG_EI, WB2, WB2S, InfillObjective  # noqa: E402
 from .sweep import Sweep, best_candidate, rendezvous_sweep, shard_indices, sweep_likelihood  # noqa: E402
 

@@ -54,6 +54,11 @@ class InfillConfig(C.Structure):
                 ("scale_ic", C.c_double), ("scale", C.c_double)]
 
 
+class GmmConfig(C.Structure):
+    _fields_ = [("n_clusters", C.c_int32), ("n_runs", C.c_int32), ("max_iter", C.c_int32), ("device", C.c_int32),
+                ("tol", C.c_double), ("reg_covar", C.c_double)]
+
+
 class InfillParts(C.Structure):
     _fields_ = [(k, c_double_p) for k in ("mean", "var", "grad_mean", "grad_var")]
 
@@ -142,6 +147,9 @@ SIGNATURES = [
                                            c_double_p, C.c_int64, c_double_p]),
     ("egx_gmx_predict_probas_derivatives", C.c_int32, [C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64,
                                                        C.c_double, c_double_p, C.c_int64, c_double_p]),
+    ("egx_gmm_config_default", None, [C.POINTER(GmmConfig)]),
+    ("egx_gmm_fit", C.c_int32, [C.POINTER(GmmConfig), c_double_p, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
     ("egx_moe_predict_valvar_gradients", C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p, C.c_int64, C.c_int64,
                                                      c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int32,
                                                      c_double_p, c_double_p]),
@@ -212,6 +220,11 @@ class PeerError(EgxError):
 
 class SampleError(EgxError, ValueError):
     """MoeError::SampleError (crates/moe/src/errors.rs:30): a mixture of several clusters cannot be sampled."""
+
+
+class ClusteringError(EgxError, ValueError):
+    """MoeError::ClusteringError (crates/moe/src/errors.rs): no usable clustering -- every restart of the mixture's
+    training failed, or a cluster is left with fewer than three points."""
 
 
 _ERR = {ERR_INVALID_VALUE: InvalidValueError, ERR_NO_DEVICE: NoDeviceError, ERR_NOT_FITTED: NotFittedError,

@@ -176,6 +176,36 @@ int launch_infill_combine(hipStream_t s, const infill::Params &prm, int k, int d
 int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, int64_t m, int64_t mstride, const double *mean,
                               const double *var, const double *tol, const int *flag, double *ei, double *base, double *fac);
 
+// ---- kernels_gmm.hip --------------------------------------------------------
+// EM of a Gaussian mixture for R restarts in lock-step over one (n x D) data set (egx_gmm_fit).  DP = D rounded up to a
+// multiple of 4; every per-cluster array on the device is padded to it with zeros.
+constexpr int kGmmTileRows = 256;   // rows per workgroup of the E-step
+constexpr int kGmmBlockAcc = 21;    // doubles per 4 x 4 moment block: 16 second moments, 4 first moments, sum of responsibilities
+constexpr int kGmmMaxDim = 36;      // D <= DP <= 36
+constexpr int kGmmMaxClusters = 16;
+constexpr int kGmmMaxBlocks = (kGmmMaxDim / 4) * (kGmmMaxDim / 4 + 1) / 2;
+struct GmmLaunch {
+    const double *data = nullptr;  // n x D row-major
+    int64_t n = 0;
+    int D = 0, DP = 0, k = 0, R = 0;
+    int T = 0;        // tiles of kGmmTileRows rows
+    int rsplit = 1;   // workgroups per tile; workgroup y serves the restarts y, y + rsplit, ..
+    int init = 0;     // iteration 0: one-hot responsibilities on the nearest mean
+    const int *active = nullptr;           // R: 0 = frozen, both kernels skip it
+    double *means = nullptr;               // R x k x DP
+    double *prec = nullptr;                // R x k x DP x DP, upper triangular precisions_chol
+    double *cst = nullptr;                 // R x k: -D/2 ln 2 pi + sum ln diag P + ln w
+    double *weights = nullptr;             // R x k
+    double *covs = nullptr;                // R x k x D x D (not padded)
+    double *part = nullptr;                // T x R x k x gmm_part_len(DP): the tiles' partial moments
+    double *lpn_part = nullptr;            // T x R: the tiles' sums of log-prob-norm
+    double *lbst = nullptr;                // R lower bounds | R failure flags (non-zero: failed)
+};
+inline size_t gmm_part_len(int DP) { return (size_t)(DP / 4) * (DP / 4 + 1) / 2 * kGmmBlockAcc; }
+size_t gmm_estep_lds_bytes(int DP, int k);
+int launch_gmm_estep(hipStream_t s, const GmmLaunch &g);
+int launch_gmm_mstep(hipStream_t s, const GmmLaunch &g, double reg_covar);
+
 // ---- kernels_chol.hip -------------------------------------------------------
 // In-place blocked right-looking Cholesky of the leading n_pad x n_pad block (lower), applied to
 // all m_tot >= n_pad rows (rows >= n_pad are right-hand sides: on return they hold (C^-1 B)^T).

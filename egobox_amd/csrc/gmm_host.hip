@@ -1,0 +1,192 @@
+// egx_gmm_fit: trains the Gaussian mixture of a mixture of experts on the GPU -- what egobox-moe asks of linfa-clustering with
+// GaussianMixtureModel::params(n_clusters).n_runs(20).fit(..) (crates/moe/src/algorithm.rs:120-123, clustering.rs:126-130).
+// The n_runs restarts are independent EM problems of one shape over the SAME data: they advance in lock-step, one E-step
+// launch and one M-step launch per iteration for all of them (kernels_gmm.hip), the host reads the R lower bounds back and
+// freezes the restarts that stopped.  A restart computes the same bits alone and in any batch.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "dev_mem.h"
+#include "egx_internal.h"
+#include "gp_handle.h"
+
+using egx::set_error;
+
+namespace {
+
+bool all_finite(const double *p, size_t len) {
+    for (size_t i = 0; i < len; i++)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+void egx_gmm_config_default(egx_gmm_config *cfg) {
+    if (!cfg) return;
+    cfg->n_clusters = 1;
+    cfg->n_runs = 20;  // crates/moe/src/algorithm.rs:121
+    cfg->max_iter = 100;
+    cfg->device = -1;
+    cfg->tol = 1e-3;
+    cfg->reg_covar = 1e-6;
+}
+
+int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim, const double *init_means,
+                    double *weights, double *means, double *covariances, double *lower_bounds, int32_t *n_iters,
+                    int32_t *statuses, int32_t *best_run, double *all_weights, double *all_means, double *all_covariances) {
+    if (!cfg || !data || !init_means || !weights || !means || !covariances || !lower_bounds || !n_iters || !statuses || !best_run) {
+        set_error("egx_gmm_fit: NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int k = cfg->n_clusters, R = cfg->n_runs, D = dim;
+    if (k < 1 || D < 1 || n < k || R < 1 || cfg->max_iter < 1 || !(cfg->tol >= 0.0) || !(cfg->reg_covar >= 0.0) ||
+        !std::isfinite(cfg->reg_covar)) {
+        set_error("egx_gmm_fit: n >= n_clusters >= 1, dim >= 1, n_runs >= 1, max_iter >= 1, tol >= 0 and reg_covar >= 0 expected");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int DP = (D + 3) / 4 * 4;
+    if (DP > egx::kGmmMaxDim || k > egx::kGmmMaxClusters) {
+        set_error("egx_gmm_fit: dim <= 36 and n_clusters <= 16 expected (got dim " + std::to_string(D) + ", n_clusters " +
+                  std::to_string(k) + ")");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int64_t T64 = (n + egx::kGmmTileRows - 1) / egx::kGmmTileRows;
+    const size_t len = egx::gmm_part_len(DP);
+    const size_t part_doubles = (size_t)T64 * R * k * len;
+    if (T64 > (1 << 22) || part_doubles > ((size_t)1 << 29)) {  // (4 GiB of partial moments)
+        set_error("egx_gmm_fit: n * n_runs * n_clusters * dim^2 beyond the workspace limit of 4 GiB");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (!all_finite(data, (size_t)n * D) || !all_finite(init_means, (size_t)R * k * D)) {
+        set_error("egx_gmm_fit: data and init_means must be finite");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        set_error("egx_gmm_fit: no HIP device");
+        return EGX_ERR_NO_DEVICE;
+    }
+    int device = cfg->device;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;  // the calling thread's current device
+    if (device >= ndev) {
+        set_error("egx_gmm_fit: device out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    EGX_HIP_CHECK(hipSetDevice(device));
+
+    const size_t rk = (size_t)R * k;
+    egx::DevBuf d_data, d_means, d_prec, d_cst, d_w, d_cov, d_part, d_lpn, d_lbst;
+    egx::DevMem<int> d_active;
+    EGX_RC(d_data.alloc((size_t)n * D));
+    EGX_RC(d_means.alloc(rk * DP));
+    EGX_RC(d_prec.alloc(rk * DP * DP));
+    EGX_RC(d_cst.alloc(rk));
+    EGX_RC(d_w.alloc(rk));
+    EGX_RC(d_cov.alloc(rk * D * D));
+    EGX_RC(d_part.alloc(part_doubles));
+    EGX_RC(d_lpn.alloc((size_t)T64 * R));
+    EGX_RC(d_lbst.alloc(2 * (size_t)R));
+    EGX_RC(d_active.alloc(R));
+    std::vector<double> h_means(rk * DP, 0.0);
+    for (size_t i = 0; i < rk; i++)
+        for (int j = 0; j < D; j++) h_means[i * DP + j] = init_means[i * D + j];
+    EGX_HIP_CHECK(hipMemcpy(d_data.p, data, sizeof(double) * (size_t)n * D, hipMemcpyHostToDevice));
+    EGX_HIP_CHECK(hipMemcpy(d_means.p, h_means.data(), sizeof(double) * h_means.size(), hipMemcpyHostToDevice));
+    EGX_HIP_CHECK(hipMemset(d_prec.p, 0, sizeof(double) * rk * DP * DP));
+    EGX_HIP_CHECK(hipMemset(d_cst.p, 0, sizeof(double) * rk));
+    EGX_HIP_CHECK(hipMemset(d_lbst.p, 0, sizeof(double) * 2 * R));
+
+    egx::GmmLaunch g;
+    g.data = d_data.p;
+    g.n = n;
+    g.D = D;
+    g.DP = DP;
+    g.k = k;
+    g.R = R;
+    g.T = (int)T64;
+    // enough workgroups to fill the chip when the data has few tiles: the restarts are dealt over grid.y (a restart's
+    // arithmetic does not depend on the deal)
+    g.rsplit = (int)std::min<int64_t>(R, std::max<int64_t>(1, (1024 + T64 - 1) / T64));
+    g.active = d_active.p;
+    g.means = d_means.p;
+    g.prec = d_prec.p;
+    g.cst = d_cst.p;
+    g.weights = d_w.p;
+    g.covs = d_cov.p;
+    g.part = d_part.p;
+    g.lpn_part = d_lpn.p;
+    g.lbst = d_lbst.p;
+
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<int> active(R, 1);
+    std::vector<double> h_lbst(2 * (size_t)R), prev(R, -std::numeric_limits<double>::infinity());
+    int n_active = R;
+    for (int r = 0; r < R; r++) {
+        statuses[r] = 1;
+        n_iters[r] = 0;
+        lower_bounds[r] = nan;
+    }
+    for (int it = 0; it <= cfg->max_iter && n_active > 0; it++) {
+        g.init = it == 0;
+        EGX_HIP_CHECK(hipMemcpy(d_active.p, active.data(), sizeof(int) * R, hipMemcpyHostToDevice));
+        EGX_RC(egx::launch_gmm_estep(nullptr, g));
+        EGX_RC(egx::launch_gmm_mstep(nullptr, g, cfg->reg_covar));
+        EGX_HIP_CHECK(hipMemcpy(h_lbst.data(), d_lbst.p, sizeof(double) * 2 * R, hipMemcpyDeviceToHost));
+        for (int r = 0; r < R; r++) {
+            if (!active[r]) continue;
+            n_iters[r] = it;
+            const double lb = h_lbst[r];
+            bool stop = false;
+            if (h_lbst[(size_t)R + r] != 0.0 || (it > 0 && !std::isfinite(lb))) {
+                statuses[r] = 2;
+                lower_bounds[r] = nan;
+                stop = true;
+            } else if (it > 0) {
+                lower_bounds[r] = lb;
+                if (std::fabs(lb - prev[r]) < cfg->tol) {
+                    statuses[r] = 0;
+                    stop = true;
+                }
+                prev[r] = lb;
+            }
+            if (stop) {
+                active[r] = 0;
+                n_active--;
+            }
+        }
+    }
+    int best = -1;
+    for (int r = 0; r < R; r++)
+        if (statuses[r] != 2 && (best < 0 || lower_bounds[r] > lower_bounds[best])) best = r;
+    *best_run = best;
+    std::vector<double> h_w(rk), h_cov(rk * D * D);
+    EGX_HIP_CHECK(hipMemcpy(h_w.data(), d_w.p, sizeof(double) * rk, hipMemcpyDeviceToHost));
+    EGX_HIP_CHECK(hipMemcpy(h_means.data(), d_means.p, sizeof(double) * h_means.size(), hipMemcpyDeviceToHost));
+    EGX_HIP_CHECK(hipMemcpy(h_cov.data(), d_cov.p, sizeof(double) * h_cov.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < rk; i++) {
+        if (all_weights) all_weights[i] = h_w[i];
+        if (all_means)
+            for (int j = 0; j < D; j++) all_means[i * D + j] = h_means[i * DP + j];
+    }
+    if (all_covariances) std::copy(h_cov.begin(), h_cov.end(), all_covariances);
+    if (best < 0) {
+        set_error("egx_gmm_fit: every restart failed (a covariance that is not positive definite, or a value that is not finite)");
+        return EGX_ERR_LINALG;
+    }
+    for (int c = 0; c < k; c++) {
+        const size_t i = (size_t)best * k + c;
+        weights[c] = h_w[i];
+        for (int j = 0; j < D; j++) means[(size_t)c * D + j] = h_means[i * DP + j];
+        std::copy(h_cov.begin() + i * D * D, h_cov.begin() + (i + 1) * D * D, covariances + (size_t)c * D * D);
+    }
+    return EGX_SUCCESS;
+}
+
+}  // extern "C"

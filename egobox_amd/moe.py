@@ -1,12 +1,20 @@
-"""Predict-side mixture-of-experts recombination around the GPU GP experts ("next").
+"""Mixture of experts around the GPU GP experts: training (clustering + expert fits) and predict-side recombination.
 
-Mirrors what egobox-moe does AFTER its clustering has chosen and trained the experts:
+Training mirrors egobox-moe's `GpMixture::params().n_clusters(k).fit(..)`:
+  GpMixtureParams / .fit (train, train_on_clusters) crates/moe/src/parameters.rs, crates/moe/src/algorithm.rs:72-205
+  optimize_heaviside_factor, check_number_of_points crates/moe/src/algorithm.rs:353-405
+  extract_part, sort_by_cluster                     crates/moe/src/algorithm.rs:1111-1121, clustering.rs:33-56
+  GaussianMixture.fit                               GaussianMixtureModel::params(k).n_runs(20).fit, algorithm.rs:120-123
+The Gaussian mixture is trained inside libegx_gp_hip.so (egx_gmm_fit: full-covariance EM, the restarts in lock-step on the
+GPU); the experts go through `GpMixture.fit_experts`, clusters of equal size in lock-step.  Not here: NbClusters::Auto, expert
+selection by cross-validation over several specs, sparse-GP experts, a k-means initialisation.
+
+Prediction mirrors what egobox-moe does with the trained mixture:
   GaussianMixture.predict_probas / predict        crates/moe/src/gaussian_mixture.rs:114-121, 231-283, 305-316
   GpMixture.predict_smooth / predict_var_smooth   crates/moe/src/algorithm.rs:411-423, 670-685, 789-809
   GpMixture.predict_hard  / predict_var_hard      crates/moe/src/algorithm.rs:879-935
   GpMixture.predict_(var_)gradients smooth / hard crates/moe/src/algorithm.rs:691-783, 942-1010;
   GaussianMixture.predict_probas_derivatives      crates/moe/src/gaussian_mixture.rs:127-170
-Clustering itself (GMM fitting, expert selection by cross-validation) stays in egobox-moe.
 
 Differences that matter on a GPU: the reference's hard recombination calls the expert ONCE PER ROW with a
 1 x nx batch (each a full n^2 triangular solve for the variance); here queries are routed once and every
@@ -18,9 +26,12 @@ egx_gmx_predict_probas(_derivatives)); the numpy forms below serve duck-typed ex
 """
 from __future__ import annotations
 
+import copy
 import math
 
 import numpy as np
+
+from ._lib import ERR_INVALID_VALUE, ERR_LINALG, ClusteringError, InvalidValueError
 
 
 class GaussianMixture:
@@ -39,6 +50,63 @@ class GaussianMixture:
             c = np.linalg.cholesky(self.covariances[i])
             self.precisions_chol[i] = np.linalg.solve(c, np.eye(nx)).T
         self.set_heaviside_factor(heaviside_factor)
+
+    @classmethod
+    def fit(cls, data, n_clusters, n_runs=20, seed=42, max_iter=100, tol=1e-3, reg_covar=1e-6, init_means=None, device=-1):
+        """Train a full-covariance mixture on `data` (n, dim) by EM with `n_runs` restarts in lock-step on the GPU
+        (egx_gmm_fit; GaussianMixtureModel::params(n_clusters).n_runs(20).fit, crates/moe/src/algorithm.rs:120-123) and
+        keep the restart with the greatest lower bound.  `init_means` (n_runs, n_clusters, dim) are the restarts' initial
+        means; by default restart r starts from n_clusters distinct rows of `data` drawn by numpy.random.default_rng(seed)
+        (not the reference's Xoshiro256Plus stream).  The result carries lower_bound_, n_iter_, and per restart
+        lower_bounds_, n_iters_, statuses_ (0 converged, 1 stopped at max_iter, 2 failed) and best_run_."""
+        from . import _lib as L
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 2:
+            raise InvalidValueError(ERR_INVALID_VALUE, f"data must be (n, dim), got shape {data.shape}")
+        data = np.ascontiguousarray(data)
+        n, dim = data.shape
+        k, n_runs = int(n_clusters), int(n_runs)
+        if k < 1 or k > n or n_runs < 1:
+            raise InvalidValueError(ERR_INVALID_VALUE, f"n >= n_clusters >= 1 and n_runs >= 1 expected (n {n}, n_clusters {k}, "
+                                                       f"n_runs {n_runs})")
+        if init_means is None:
+            rng = np.random.default_rng(seed)
+            init_means = np.stack([data[rng.choice(n, size=k, replace=False)] for _ in range(n_runs)])
+        init_means = np.ascontiguousarray(init_means, dtype=np.float64)
+        if init_means.shape != (n_runs, k, dim):
+            raise InvalidValueError(ERR_INVALID_VALUE, f"init_means must be (n_runs, n_clusters, dim) = {(n_runs, k, dim)}, "
+                                                       f"got {init_means.shape}")
+        lib = L.load()
+        cfg = L.GmmConfig()
+        lib.egx_gmm_config_default(cfg)
+        cfg.n_clusters, cfg.n_runs, cfg.max_iter, cfg.device = k, n_runs, int(max_iter), int(device)
+        cfg.tol, cfg.reg_covar = float(tol), float(reg_covar)
+        weights, means, covs = np.empty(k), np.empty((k, dim)), np.empty((k, dim, dim))
+        lbs = np.empty(n_runs)
+        n_iters, statuses = np.zeros(n_runs, dtype=np.int32), np.zeros(n_runs, dtype=np.int32)
+        best = L.C.c_int32(-1)
+        all_w, all_m, all_c = np.empty((n_runs, k)), np.empty((n_runs, k, dim)), np.empty((n_runs, k, dim, dim))
+        rc = lib.egx_gmm_fit(cfg, L.dptr(data), n, dim, L.dptr(init_means), L.dptr(weights), L.dptr(means), L.dptr(covs),
+                             L.dptr(lbs), n_iters.ctypes.data_as(L.c_int32_p), statuses.ctypes.data_as(L.c_int32_p),
+                             L.C.byref(best), L.dptr(all_w), L.dptr(all_m), L.dptr(all_c))
+        if rc == ERR_LINALG:
+            raise ClusteringError(rc, lib.egx_last_error().decode("utf-8", "replace"))
+        L.check(rc)
+        gm = cls(weights, means, covs)
+        gm.best_run_ = int(best.value)
+        gm.lower_bounds_, gm.n_iters_, gm.statuses_ = lbs, n_iters, statuses
+        gm.lower_bound_, gm.n_iter_ = float(lbs[gm.best_run_]), int(n_iters[gm.best_run_])
+        gm.all_weights_, gm.all_means_, gm.all_covariances_ = all_w, all_m, all_c
+        return gm
+
+    def marginal(self, nx, heaviside_factor=1.0):
+        """The mixture of the first nx coordinates (crates/moe/src/algorithm.rs:126-134: a mixture trained on [x, y] serves
+        the x-space); the training record (lower_bound_, ...) is carried over."""
+        gmx = GaussianMixture(self.weights, self.means[:, :nx], self.covariances[:, :nx, :nx], heaviside_factor)
+        for name in ("best_run_", "lower_bounds_", "n_iters_", "statuses_", "lower_bound_", "n_iter_"):
+            if hasattr(self, name):
+                setattr(gmx, name, getattr(self, name))
+        return gmx
 
     def set_heaviside_factor(self, f):
         """gaussian_mixture.rs:105-110: refresh the log-determinants."""
@@ -122,8 +190,216 @@ class GaussianMixture:
         return (uprime * v[:, None, None] - u[:, :, None] * vprime[:, None, :]) / (v * v)[:, None, None]
 
 
+def extract_part(data, quantile):
+    """crates/moe/src/algorithm.rs:1111-1121: one row out of `quantile` (rows 0, quantile, 2 quantile, ..) and the rest."""
+    data = np.asarray(data)
+    idx = np.arange(data.shape[0])
+    return data[idx % quantile == 0], data[idx % quantile != 0]
+
+
+def sort_by_cluster(n_clusters, data, clustering):
+    """crates/moe/src/clustering.rs:33-56: the rows of `data` per cluster, in their order."""
+    data, clustering = np.asarray(data), np.asarray(clustering)
+    return [data[clustering == c] for c in range(n_clusters)]
+
+
+def check_number_of_points(clusters, dim, mean):
+    """crates/moe/src/algorithm.rs:381-405, as written there: `cluster.len()` counts the ELEMENTS of the (rows, nx + 1)
+    array.  `mean` is the regression model (ConstantMean / LinearMean / QuadraticMean)."""
+    if len(clusters) > 1:
+        need = {2: (dim + 1) * (dim + 2) // 2, 1: dim + 1}.get(mean.code, 1)
+        for c in clusters:
+            if np.asarray(c).size < need:
+                raise ClusteringError(ERR_INVALID_VALUE,
+                                      f"Not enough points in training set. Need {need} points, got {np.asarray(c).size}")
+
+
+def check_three_points(clusters):
+    """crates/moe/src/algorithm.rs:168-173."""
+    if len(clusters) > 1:
+        for c in clusters:
+            if np.asarray(c).shape[0] < 3:
+                raise ClusteringError(ERR_INVALID_VALUE,
+                                      f"Not enough points in cluster, requires at least 3, got {np.asarray(c).shape[0]}")
+
+
+HEAVISIDE_GRID = np.linspace(0.1, 2.1, 20)
+
+
+def heaviside_errors(experts, gmx, xtest, ytest, **kw):
+    """The error of every grid factor, crates/moe/src/algorithm.rs:363-369: ||pred - y||_2 / ||x_test||_2 with the smooth
+    recombination of the trained experts under a copy of `gmx` that carries the factor."""
+    xtest = np.atleast_2d(np.asarray(xtest, dtype=np.float64))
+    ytest = np.asarray(ytest, dtype=np.float64).ravel()
+    errors = np.empty(HEAVISIDE_GRID.size)
+    for i, f in enumerate(HEAVISIDE_GRID):
+        gmx2 = copy.copy(gmx).set_heaviside_factor(f)
+        pred = GpMixture(experts, gmx2, "smooth", **kw).predict(xtest)
+        errors[i] = math.sqrt(np.sum((pred - ytest) ** 2)) / math.sqrt(np.sum(xtest * xtest))
+    return errors
+
+
+def optimize_heaviside_factor(experts, gmx, xtest, ytest, recombination="smooth", **kw):
+    """crates/moe/src/algorithm.rs:353-378: the grid factor of the smallest error (the first among equals), 1 when every
+    error is below 1e-6, when the recombination is hard or with one cluster."""
+    if recombination == "hard" or gmx.n_clusters == 1:
+        return 1.0
+    errors = heaviside_errors(experts, gmx, xtest, ytest, **kw)
+    if errors.max() < 1e-6:
+        return 1.0
+    return float(HEAVISIDE_GRID[int(np.argmin(errors))])
+
+
+class GpMixtureParams:
+    """Builder of a trained mixture of experts, crates/moe/src/parameters.rs (defaults :142-159, 246-253): setters return
+    self, `.fit(x, y)` trains the Gaussian mixture on [x, y] on the GPU and one GP expert per cluster."""
+
+    def __init__(self):
+        from . import gp as G
+        self._n_clusters = 1
+        self._recombination, self._heaviside_factor = "smooth", 1.0  # parameters.rs:249
+        self._mean, self._corr = G.ConstantMean(), G.SquaredExponentialCorr()
+        self._theta_tunings = [G.ThetaTuning.default()]
+        self._kpls_dim = None
+        self._n_start = 10
+        self._max_eval = G.GP_COBYLA_MAX_EVAL
+        self._gmx = None
+        self._seed = 42
+        self._device = -1
+        self._n_runs = 20  # algorithm.rs:121
+
+    def n_clusters(self, n_clusters):
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
+            raise NotImplementedError("n_clusters must be a number: NbClusters::Auto (find_best_number_of_clusters) is not "
+                                      "implemented")
+        if n_clusters < 1:
+            raise InvalidValueError(ERR_INVALID_VALUE, f"n_clusters must be at least 1, got {n_clusters}")
+        self._n_clusters = int(n_clusters)
+        return self
+
+    def recombination(self, mode, heaviside_factor=None):
+        """"hard", or "smooth" with its heaviside factor; smooth without one (the reference's Smooth(None)) chooses the
+        factor on one row out of five held back from the training (algorithm.rs:106-113, 179-193)."""
+        mode = str(getattr(mode, "name", mode)).lower()
+        if mode not in ("hard", "smooth"):
+            raise InvalidValueError(ERR_INVALID_VALUE, "recombination must be 'hard' or 'smooth'")
+        if heaviside_factor is not None and not float(heaviside_factor) > 0.0:
+            raise InvalidValueError(ERR_INVALID_VALUE, "heaviside_factor must be positive")
+        self._recombination = mode
+        self._heaviside_factor = None if heaviside_factor is None else float(heaviside_factor)
+        return self
+
+    def regression_spec(self, spec):
+        """One RegressionSpec flag (or a mean object); several at once ask for the cross-validated expert selection of
+        find_best_expert (algorithm.rs:209-347), which is not implemented."""
+        from . import gpx
+        self._mean = gpx._single(spec, gpx._REGR, "regression_spec") if isinstance(spec, (int, gpx.RegressionSpec)) else spec
+        return self
+
+    def correlation_spec(self, spec):
+        from . import gpx
+        self._corr = gpx._single(spec, gpx._CORR, "correlation_spec") if isinstance(spec, (int, gpx.CorrelationSpec)) else spec
+        return self
+
+    def theta_tunings(self, theta_tunings):
+        """One tuning for every expert, or one per cluster (algorithm.rs:297-302)."""
+        self._theta_tunings = list(theta_tunings)
+        if not self._theta_tunings:
+            raise InvalidValueError(ERR_INVALID_VALUE, "at least one theta tuning expected")
+        return self
+
+    def n_start(self, n_start):
+        self._n_start = int(n_start)
+        return self
+
+    def max_eval(self, max_eval):
+        self._max_eval = int(max_eval)
+        return self
+
+    def kpls_dim(self, kpls_dim):
+        self._kpls_dim = kpls_dim
+        return self
+
+    def gmx(self, gmx):
+        """A ready mixture of the x-space instead of a trained one (the reference's .gmx(), algorithm.rs:116-117)."""
+        self._gmx = gmx
+        return self
+
+    def seed(self, seed):
+        self._seed = seed
+        return self
+
+    def device(self, device):
+        self._device = int(device)
+        return self
+
+    def n_runs(self, n_runs):
+        """Extension: the restarts of the mixture's EM (the reference fixes 20, algorithm.rs:121)."""
+        self._n_runs = int(n_runs)
+        return self
+
+    def _expert_params(self, nc):
+        from . import gp as G
+        tt = self._theta_tunings
+        if len(tt) != 1 and len(tt) != self._n_clusters:
+            raise InvalidValueError(ERR_INVALID_VALUE, f"theta_tunings: 1 or n_clusters ({self._n_clusters}) expected, "
+                                                       f"got {len(tt)}")
+        return G.GpParams(self._mean, self._corr).theta_tuning(tt[0] if len(tt) == 1 else tt[nc]).n_start(self._n_start) \
+            .max_eval(self._max_eval).kpls_dim(self._kpls_dim).device(self._device)
+
+    def fit(self, x, y):
+        """GpMixtureValidParams::train, crates/moe/src/algorithm.rs:72-140."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if x.ndim != 2 or y.shape[0] != x.shape[0]:
+            raise InvalidValueError(ERR_INVALID_VALUE, f"x (n, nx) and y (n,) expected, got {x.shape} and {y.shape}")
+        n, nx = x.shape
+        k = self._n_clusters
+        if k > n:
+            raise InvalidValueError(ERR_INVALID_VALUE, f"n_clusters ({k}) exceeds the number of training points ({n})")
+        self._expert_params(0)
+        data = np.column_stack([x, y])
+        smooth_none = self._recombination == "smooth" and self._heaviside_factor is None and k > 1
+        if self._gmx is not None:
+            gmx = self._gmx
+        else:
+            training = extract_part(data, 5)[1] if smooth_none else data
+            gmm = GaussianMixture.fit(training, k, n_runs=self._n_runs, seed=self._seed, device=self._device)
+            gmx = gmm.marginal(nx, self._heaviside_factor if self._heaviside_factor is not None else 1.0)
+        return self._train_on_clusters(x, y, data, gmx, smooth_none)
+
+    def _train_on_clusters(self, x, y, data, gmx, smooth_none):
+        """train_on_clusters, crates/moe/src/algorithm.rs:144-205."""
+        nx = x.shape[1]
+        clusters = sort_by_cluster(gmx.n_clusters, data, gmx.predict(x))
+        check_number_of_points(clusters, nx, self._mean)
+        check_three_points(clusters)
+        cxs, cys = [c[:, :nx] for c in clusters], [c[:, nx] for c in clusters]
+        if len(self._theta_tunings) == 1 and self._kpls_dim is None:
+            moe = GpMixture.fit_experts(self._expert_params(0), cxs, cys, gmx, self._recombination)
+        else:  # a tuning per cluster, or the PLS rotations of each cluster's own data: one fit per expert
+            moe = GpMixture([self._expert_params(i).fit(cxs[i], cys[i]) for i in range(len(clusters))], gmx,
+                            self._recombination)
+        if smooth_none:
+            test = extract_part(data, 5)[0]
+            factor = optimize_heaviside_factor(moe.experts, gmx, test[:, :nx], test[:, nx], self._recombination)
+            final = copy.copy(self).recombination("smooth", factor).fit(x, y)  # on ALL data, algorithm.rs:188-193
+            final.heaviside_stage_ = moe  # the mixture the factor was chosen on (its gmx saw four rows out of five)
+            return final
+        moe.training_data = (x, y)
+        moe.params_ = self
+        return moe
+
+
 class GpMixture:
-    """Experts + mixture, predict side only.  `experts[i]` is None for experts that live on another rank."""
+    """Experts + mixture.  `GpMixture.params()` builds and trains one; the constructor takes trained experts (`experts[i]` is
+    None for experts that live on another rank)."""
+
+    @staticmethod
+    def params():
+        return GpMixtureParams()
 
     def __init__(self, experts, gmx, recombination="hard", rank=0, world=1, device=None, sweep=None):
         """`sweep`: the rank's `egobox_amd.Sweep` (its RCCL communicator carries the recombination's one all-gather
@@ -142,7 +418,7 @@ class GpMixture:
     def fit_experts(cls, params, cluster_xs, cluster_ys, gmx, recombination="hard", **kw):
         """The expert loop of egobox-moe (crates/moe/src/algorithm.rs:167-177: one GP per cluster, fitted one after the other)
         with the experts of EQUAL training-set size fitted in lock-step: `params` is a `GpParams` with ThetaTuning.Fixed,
-        cluster_xs[i] / cluster_ys[i] the training set of cluster i (the clustering itself is out of this package's scope).
+        cluster_xs[i] / cluster_ys[i] the training set of cluster i (`GpMixtureParams.fit` clusters and calls this).
         Clusters of one size go through `GpParams.fit_group` (one launch sequence for all of them), the others through
         `fit`; every expert is bit for bit what `fit` alone gives."""
         k = len(cluster_xs)

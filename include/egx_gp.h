@@ -454,6 +454,30 @@ int32_t egx_gmx_precisions_chol(const double *covariances, int64_t k, int64_t d,
 int32_t egx_gmx_predict_probas(int32_t device, const double *weights, const double *means, const double *precisions_chol,
                                int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m, double *probas);
 
+/* Training of that mixture: full-covariance EM on data (n x dim, row-major; egobox-moe passes the joined [x, y]) with
+ * n_runs restarts in lock-step on the GPU -- GaussianMixtureModel::params(n_clusters).n_runs(20).fit(..), crates/moe/src/
+ * algorithm.rs:120-123 and clustering.rs:126-130.  Restart r starts from init_means[r] (k x dim): iteration 0 assigns every
+ * row to its nearest initial mean (squared Euclidean distance, ties to the lowest cluster) and runs the M-step on these
+ * one-hot responsibilities; every later iteration is an E-step and an M-step (nk = sum resp + 10 eps, weights = nk / sum nk,
+ * covariance = weighted scatter about the new mean + reg_covar I), its lower bound the mean log-prob-norm of the E-step.  A
+ * restart stops when |lb - lb_prev| < tol (status 0) or after max_iter iterations (status 1, still a candidate); a
+ * covariance that is not positive definite or a value that is not finite fails that restart alone (status 2, excluded, its
+ * lower bound NaN).  The result is the restart with the greatest final lower bound (the lowest index among equals).  A
+ * restart computes the same bits alone and in any batch.  dim <= 36 and n_clusters <= 16, beyond: EGX_ERR_INVALID_VALUE, as
+ * for n < n_clusters, a value of data / init_means that is not finite, n_runs < 1 (all checked before the device is
+ * touched).  EGX_ERR_LINALG when every restart failed (the per-restart outputs are filled).  The all_* outputs (every
+ * restart's parameters; those of a failed restart are not meaningful) may be NULL. */
+typedef struct {
+    int32_t n_clusters, n_runs, max_iter, device; /* device < 0: the calling thread's current device */
+    double tol, reg_covar;
+} egx_gmm_config;
+void egx_gmm_config_default(egx_gmm_config *cfg); /* n_clusters 1, n_runs 20, max_iter 100, tol 1e-3, reg_covar 1e-6, device -1 */
+int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim,
+                    const double *init_means /*n_runs*k*dim*/, double *weights /*k*/, double *means /*k*dim*/,
+                    double *covariances /*k*dim*dim*/, double *lower_bounds /*n_runs*/, int32_t *n_iters /*n_runs*/,
+                    int32_t *statuses /*n_runs*/, int32_t *best_run, double *all_weights /*n_runs*k*/,
+                    double *all_means /*n_runs*k*dim*/, double *all_covariances /*n_runs*k*dim*dim*/);
+
 /* d p_c(x) / d x of those responsibilities: GaussianMixture::predict_probas_derivatives (gaussian_mixture.rs:127-170),
  * dprobas is (m x k x d) row-major; on the device, one lane per point (needs 3 d + k <= 320). */
 int32_t egx_gmx_predict_probas_derivatives(int32_t device, const double *weights, const double *means,

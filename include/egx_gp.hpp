@@ -478,6 +478,39 @@ inline std::pair<std::vector<double>, std::vector<double>> moe_predict_valvar_gr
     return {std::move(gy), std::move(gv)};
 }
 
+// GaussianMixtureModel::params(n_clusters).n_runs(n_runs).fit(data) (crates/moe/src/algorithm.rs:120-123) through egx_gmm_fit:
+// full-covariance EM on data (n x dim row-major), restart r from init_means[r] (n_clusters x dim), the restarts in lock-step
+// on the GPU.  LinalgError when every restart failed.
+struct GmmFit {
+    std::vector<double> weights, means, covariances;  // the best restart: (k), (k x dim), (k x dim x dim)
+    std::vector<double> lower_bounds;                 // per restart (NaN: failed)
+    std::vector<int32_t> n_iters, statuses;           // per restart; 0 converged, 1 stopped at max_iter, 2 failed
+    int32_t best_run = -1;
+};
+inline GmmFit gmm_fit(const double *data, int64_t n, int32_t dim, int32_t n_clusters, const std::vector<double> &init_means,
+                      const egx_gmm_config *config = nullptr) {
+    egx_gmm_config cfg;
+    if (config)
+        cfg = *config;
+    else
+        egx_gmm_config_default(&cfg);
+    cfg.n_clusters = n_clusters;
+    const size_t per = (size_t)(n_clusters > 0 ? n_clusters : 1) * (size_t)(dim > 0 ? dim : 1);
+    cfg.n_runs = (int32_t)(init_means.size() / per);
+    if (cfg.n_runs < 1 || (size_t)cfg.n_runs * per != init_means.size())
+        throw InvalidValueError(EGX_ERR_INVALID_VALUE, "gmm_fit: init_means must hold n_runs x n_clusters x dim values");
+    GmmFit f;
+    f.weights.resize((size_t)n_clusters);
+    f.means.resize(per);
+    f.covariances.resize(per * (size_t)dim);
+    f.lower_bounds.resize((size_t)cfg.n_runs);
+    f.n_iters.resize((size_t)cfg.n_runs);
+    f.statuses.resize((size_t)cfg.n_runs);
+    check(egx_gmm_fit(&cfg, data, n, dim, init_means.data(), f.weights.data(), f.means.data(), f.covariances.data(),
+                      f.lower_bounds.data(), f.n_iters.data(), f.statuses.data(), &f.best_run, nullptr, nullptr, nullptr));
+    return f;
+}
+
 // EGO's infill criterion on fitted models (egx_infill_*, egx_gp.h): the objective the infill optimiser minimises and its
 // x-gradient for m points per call (crates/ego/src/criteria, utils/cstr_pof.rs, solver/solver_computations.rs:356-475), the
 // scaling pass (:132-193) and the lock-step multistart (solver_infill_optim.rs:148-236).  The models are borrowed and must
