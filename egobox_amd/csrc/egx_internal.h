@@ -40,6 +40,10 @@ constexpr int kRhsPad = 128;    // rows appended below R for the fused forward s
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
+// The widest lock-step launch: candidates of a slot (egx_gp_set_lockstep clamps the width to it), models of a run
+// (egx_gp_finalize_multi).  It sizes the pointer blocks that such a launch takes by value: EvalBatchPtrs, SolveBatchPtrs, GradBatch
+constexpr int kLockstepMax = 16;
+
 // ---- kernels_corr.hip -------------------------------------------------------
 // coef is (d x hcols) row-major: per-dimension scale (w = I: hcols = 1, coef[j] = theta_j;
 // KPLS: sq-exp/abs-exp collapse to hcols = 1, Matern keeps theta_l*|w_jl|).
@@ -80,12 +84,11 @@ int launch_fill_rows(hipStream_t s, double *M, int64_t ld, int r0, int rows_pad,
 int launch_gather_diag(hipStream_t s, const double *M, int64_t ld, int n, double *out);
 // per-candidate pointers of a lock-step batch, passed by value to the batched front-end / tail kernels (kernels_corr.hip)
 struct EvalBatchPtrs {
-    static constexpr int kMax = 16;  // the widest lock-step batch (egx_gp_set_lockstep)
-    const double *xT[kMax], *coef[kMax], *rhsT[kMax];
-    double *xs[kMax], *M[kMax];
-    double *h_diag[kMax], *h_rows[kMax];  // pinned host memory, written by the device
-    int *h_info[kMax];
-    const int *d_info[kMax];
+    const double *xT[kLockstepMax], *coef[kLockstepMax], *rhsT[kLockstepMax];
+    double *xs[kLockstepMax], *M[kLockstepMax];
+    double *h_diag[kLockstepMax], *h_rows[kLockstepMax];  // pinned host memory, written by the device
+    int *h_info[kLockstepMax];
+    const int *d_info[kLockstepMax];
 };
 int launch_eval_front_batch(hipStream_t s, int corr, const EvalBatchPtrs &b, int count, int64_t ldx, int n, int d, int hcols,
                             double nugget, int64_t ld, int n_pad, int rhs_pad, int q);
@@ -105,16 +108,15 @@ int launch_zero_upper(hipStream_t s, double *M, int64_t ld, int n);
 // hcols == 1: output o = input dimension o (nout = d; w = I: coef = theta);
 // hcols  > 1 (KPLS + Matern): output o = theta_o, d log R / d theta_o = sum_j wabs[j][o] (d log m / dt)(coef[j][o] a_j) a_j
 // Deterministic (fixed reduction order): a candidate's result does not depend on the batch it runs in.
-constexpr int kGradMaxBatch = 16;
 struct GradBatch {
     int count = 1;
-    const double *xs[kGradMaxBatch];     // d x ldx: the inputs times the candidate's coefficients (prescaled form only)
-    const double *coef[kGradMaxBatch];   // d x hcols
-    const double *gamma[kGradMaxBatch];  // n_pad
-    const double *rneg[kGradMaxBatch];   // -R^-1, lower triangle, leading dimension ld
-    double inv_s2[kGradMaxBatch];        // 1 / sigma2 (normalised units)
-    double *part[kGradMaxBatch];         // grad_partial_doubles(nout) doubles of scratch
-    double *out[kGradMaxBatch];          // nout
+    const double *xs[kLockstepMax];     // d x ldx: the inputs times the candidate's coefficients (prescaled form only)
+    const double *coef[kLockstepMax];   // d x hcols
+    const double *gamma[kLockstepMax];  // n_pad
+    const double *rneg[kLockstepMax];   // -R^-1, lower triangle, leading dimension ld
+    double inv_s2[kLockstepMax];        // 1 / sigma2 (normalised units)
+    double *part[kLockstepMax];         // grad_partial_doubles(nout) doubles of scratch
+    double *out[kLockstepMax];          // nout
 };
 int grad_partial_doubles(int nout);
 int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, int d, int hcols, const double *wabs,
@@ -294,24 +296,32 @@ int launch_syrk_uptri_neg(hipStream_t s, double *C, int64_t ldc, const double *W
 // dinv <- inverses of the 64x64 diagonal tiles of a given lower factor (model load path)
 int launch_diag_tile_inverses(hipStream_t s, const double *M, int64_t ld, int n_pad, double *dinv);
 // Wall ((n_pad/256) x 256 x 256) <- transposed inverses of the 256x256 diagonal blocks of the factor
-// per-model pointers of a lock-step back-substitution (egx_gp_finalize_multi), by value in the kernel arguments
+// per-model pointers of a back-substitution, by value in the kernel arguments: the models of a run in lock-step
+// (egx_gp_finalize_multi; blockIdx.y = model), or ONE factor -- a lone model is a batch of one
 struct SolveBatchPtrs {
-    static constexpr int kMax = 16;
-    const double *M[kMax], *dinv[kMax];
-    double *dW[kMax], *rhs[kMax], *vec[kMax];
+    const double *M[kLockstepMax], *dinv[kLockstepMax];
+    double *dW[kLockstepMax], *rhs[kLockstepMax], *vec[kLockstepMax];
 };
 // the buffer of the 256 x 256 inverse blocks (launch_block_inverse: Wall / dW) carries, behind the blocks, the start ticket and
 // the exchange buffer of the one-launch back-substitution (k_trsv_t_fused): allocate block_inverse_doubles(n_pad) doubles
 inline size_t trsv_tail_doubles(int n_pad) { return 4 + (size_t)n_pad; }
 inline size_t block_inverse_doubles(int n_pad) { return (size_t)((n_pad + kNB - 1) / kNB) * 65536 + trsv_tail_doubles(n_pad); }
 long long pipe_timeout_ticks();  // EGX_PIPE_TIMEOUT_MS in ticks of the 100-MHz wall clock (kernels_pipe.hip)
-int launch_block_inverse_batch(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad);
-int launch_trsv_t_batch(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad);
-int launch_block_inverse(hipStream_t s, const double *M, int64_t ld, int n_pad, const double *dinv, double *Wall);
-// xout (n_pad) <- C^-T v   (needs launch_block_inverse first).  One launch (k_trsv_t_fused; v is left alone) unless
-// per_block or "trsv_fused" = 0: then one launch per 256-column block, and v is destroyed
-int launch_trsv_t(hipStream_t s, const double *M, int64_t ld, int n_pad, const double *Wall, double *v,
-                  double *xout, bool per_block = false);
+// dW[j] <- the 256 x 256 inverse blocks of factor j (M[j], dinv[j]), j < count
+int launch_block_inverse(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad);
+// vec[j] (n_pad) <- C_j^-T rhs[j]   (needs launch_block_inverse first).  One launch (k_trsv_t_fused; rhs is left alone) unless
+// per_block or "trsv_fused" = 0: then one launch per 256-column block, and rhs is destroyed
+int launch_trsv_t(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad, bool per_block = false);
+// ... of one factor
+inline int launch_block_inverse(hipStream_t s, const double *M, int64_t ld, int n_pad, const double *dinv, double *Wall) {
+    const SolveBatchPtrs b{{M}, {dinv}, {Wall}, {}, {}};
+    return launch_block_inverse(s, b, 1, ld, n_pad);
+}
+inline int launch_trsv_t(hipStream_t s, const double *M, int64_t ld, int n_pad, double *Wall, double *v, double *xout,
+                         bool per_block = false) {
+    const SolveBatchPtrs b{{M}, {}, {Wall}, {v}, {xout}};
+    return launch_trsv_t(s, b, 1, ld, n_pad, per_block);
+}
 // C (M x N, ldc) -= A (M x K, lda) * B (N x K, ldb)^T ; lower != 0 skips tiles strictly above the diagonal
 // ktri != 0 (with lower): A and B are upper triangular, the K loop of tile (bx, by) starts at row bx*tile
 // info != nullptr: device flag of the enclosing factorisation; the kernel returns at once when it is non-zero

@@ -235,7 +235,7 @@ static int enqueue_grad_run(egx_gp *gp, hipStream_t st, int w0, int count, int s
         gb.part[j] = w.d_gpart;
         gb.out[j] = w.d_gout;
     }
-    for (int j = count; j < kGradMaxBatch; j++) {
+    for (int j = count; j < kLockstepMax; j++) {
         gb.xs[j] = gb.coef[j] = gb.gamma[j] = gb.rneg[j] = nullptr;
         gb.inv_s2[j] = 0.0;
         gb.part[j] = gb.out[j] = nullptr;
@@ -276,118 +276,94 @@ static void grad_chain_rule(const egx_gp *gp, const double *gsum, int hcols, con
     }
 }
 
-// likelihood + gradient of the rows of thetas (k x theta_len): lkh[c], grad[c * h ..], status[c].  Caller holds gp->mu
-// exclusively and has set the device.  A fitted model keeps workspace 0 as long as another workspace exists.
+// likelihood + gradient of the rows of thetas (k x theta_len) that `src` hands out: lkh[c], grad[c * h ..], status[c].  Caller
+// holds gp->mu exclusively and has set the device.  A fitted model keeps workspace 0 as long as another workspace exists.
+// The two-phase client of the slot pipeline (slot_pipeline.h): a slot's candidates are enqueued as a likelihood batch's are
+// (C^-T riding along, into the slot's buffers of slab_W), phase 1 ends with the host halves of the likelihoods and enqueues the
+// gradient stages, phase 2 ends with the chain rule.  It uses min(workspaces, k) workspaces: that many C^-T buffers.
 int likelihood_grad_batch_core(egx_gp *gp, const double *thetas, int64_t k, int64_t theta_len, double *lkh, double *grad,
-                               int32_t *status) {
+                               int32_t *status, CandidateSource *src) {
     if (k <= 0) return EGX_SUCCESS;
     const int h = gp->h;
     const int ws_lo = (gp->fitted && gp->ws.size() > 1) ? 1 : 0;
-    const int nws = (int)gp->ws.size() - ws_lo;
-    const int nuse = (int)std::min<int64_t>(nws, k);
-    int B = gp->lockstep < 1 ? 1 : gp->lockstep;
-    B = std::min(std::min(B, nuse), kGradMaxBatch);
-    const int nslots = (nuse + B - 1) / B;
+    const int nuse = (int)std::min<int64_t>((int64_t)gp->ws.size() - ws_lo, k);
+    const SlotGeometry g = slot_geometry(ws_lo, nuse, gp->lockstep, kLockstepMax);
     EGX_RC(ensure_grad_scratch(gp, ws_lo, nuse));
     if (ws_lo == 0) gp->fitted = false;
     struct Slot {
-        int phase = 0;  // 0 idle, 1 likelihood in flight, 2 gradient in flight
         std::vector<int64_t> cand;
         std::vector<std::vector<double>> coefs, thfull;
         std::vector<char> ok, pre;  // ok: has a gradient; pre: eligible for the prescaled trace kernel
         int hcols = 1;
     };
-    std::vector<Slot> slots(nslots);
+    std::vector<Slot> slots(g.nslots);
     for (auto &sl : slots) {
-        sl.coefs.resize(B);
-        sl.thfull.resize(B);
+        sl.coefs.resize(g.width);
+        sl.thfull.resize(g.width);
     }
-    auto slot_cap = [&](int i) { return std::min(B, nuse - i * B); };
-    int64_t next = 0;
-    int busy = 0;
-    auto run = [&]() -> int {
-        for (int i = 0;; i = (i + 1) % nslots) {
-            Slot &sl = slots[i];
-            const int w0 = ws_lo + i * B;
-            hipStream_t st = gp->ws[w0].stream;
-            if (sl.phase == 2) {
-                EGX_HIP_CHECK(hipStreamSynchronize(st));
-                for (size_t j = 0; j < sl.cand.size(); j++)
-                    if (sl.ok[j])
-                        grad_chain_rule(gp, gp->ws[w0 + (int)j].h_gout, sl.hcols, sl.coefs[j], sl.thfull[j], grad + sl.cand[j] * h);
-                sl.cand.clear();
-                sl.phase = 0;
-                busy--;
-            } else if (sl.phase == 1) {
-                // host half of the likelihoods (GLS, sigma2), then the gradient stages for the candidates that have one
-                const int cnt = (int)sl.cand.size();
-                std::vector<double> inv_s2(cnt, 0.0);
-                sl.ok.assign(cnt, 0);
-                sl.pre.assign(cnt, 0);
-                for (int j = 0; j < cnt; j++) {
-                    Workspace &w = gp->ws[w0 + j];
-                    EvalResult res;
-                    EGX_RC(finish_eval(gp, w, res, 2));
-                    const int64_t c = sl.cand[j];
-                    lkh[c] = res.lkh;
-                    status[c] = res.status;
-                    if (res.status != EGX_STATUS_OK || !(res.sigma2n > 0.0) || !std::isfinite(res.lkh)) continue;
-                    sl.ok[j] = 1;
-                    inv_s2[j] = 1.0 / res.sigma2n;
-                    // the prescaled form divides by the coefficient once per output: a candidate's OWN coefficients decide
-                    // (never its companions': the kernel choice must not depend on the batch)
-                    sl.pre[j] = sl.hcols == 1 ? 1 : 0;
-                    for (double cj : sl.coefs[j])
-                        if (!(cj > 0.0) || !std::isfinite(cj)) sl.pre[j] = 0;
-                    EGX_RC(upload_rho(gp, w, res, st));
-                }
-                // maximal runs of consecutive candidates with a gradient (and the same form of the trace kernel): each run is one
-                // lock-step launch sequence
-                for (int j = 0; j < cnt;) {
-                    if (!sl.ok[j]) {
-                        j++;
-                        continue;
-                    }
-                    int e = j;
-                    while (e < cnt && sl.ok[e] && sl.pre[e] == sl.pre[j]) e++;
-                    EGX_RC(enqueue_grad_run(gp, st, w0 + j, e - j, i * B + j, inv_s2.data() + j, sl.hcols, sl.pre[j]));
-                    j = e;
-                }
-                sl.phase = 2;
+    auto admit = [&](int i, int j, int64_t c, bool &valid) -> int {
+        Slot &sl = slots[i];
+        const double *th = thetas + c * theta_len;
+        EGX_RC(make_coef(gp, th, theta_len, sl.coefs[j], sl.hcols, &sl.thfull[j]));
+        for (int l = 0; l < h; l++) grad[c * h + l] = 0.0;
+        valid = !has_nan(th, theta_len);  // (a NaN theta is answered at once, algorithm.rs:885-891)
+        if (valid) sl.cand.push_back(c);
+        else lkh[c] = -std::numeric_limits<double>::infinity(), status[c] = EGX_STATUS_NAN_THETA;
+        return EGX_SUCCESS;
+    };
+    auto enqueue = [&](int i, int count) -> int {
+        return enqueue_eval_group(gp, g.first_ws(i), count, slots[i].coefs.data(), slots[i].hcols,
+                                  gp->slab_W + (int64_t)(i * g.width) * gp->n_pad * gp->n_pad);
+    };
+    auto advance = [&](int i, int phase, bool &idle) -> int {
+        Slot &sl = slots[i];
+        const int w0 = g.first_ws(i);
+        hipStream_t st = gp->ws[w0].stream;
+        const int cnt = (int)sl.cand.size();
+        idle = phase == 2;
+        if (phase == 2) {
+            EGX_HIP_CHECK(hipStreamSynchronize(st));
+            for (int j = 0; j < cnt; j++)
+                if (sl.ok[j]) grad_chain_rule(gp, gp->ws[w0 + j].h_gout, sl.hcols, sl.coefs[j], sl.thfull[j], grad + sl.cand[j] * h);
+            sl.cand.clear();
+            return EGX_SUCCESS;
+        }
+        // host half of the likelihoods (GLS, sigma2), then the gradient stages for the candidates that have one
+        std::vector<double> inv_s2(cnt, 0.0);
+        sl.ok.assign(cnt, 0);
+        sl.pre.assign(cnt, 0);
+        for (int j = 0; j < cnt; j++) {
+            Workspace &w = gp->ws[w0 + j];
+            EvalResult res;
+            EGX_RC(finish_eval(gp, w, res, 2));
+            const int64_t c = sl.cand[j];
+            lkh[c] = res.lkh;
+            status[c] = res.status;
+            if (res.status != EGX_STATUS_OK || !(res.sigma2n > 0.0) || !std::isfinite(res.lkh)) continue;
+            sl.ok[j] = 1;
+            inv_s2[j] = 1.0 / res.sigma2n;
+            // the prescaled form divides by the coefficient once per output: a candidate's OWN coefficients decide
+            // (never its companions': the kernel choice must not depend on the batch)
+            sl.pre[j] = sl.hcols == 1 ? 1 : 0;
+            for (double cj : sl.coefs[j])
+                if (!(cj > 0.0) || !std::isfinite(cj)) sl.pre[j] = 0;
+            EGX_RC(upload_rho(gp, w, res, st));
+        }
+        // maximal runs of consecutive candidates with a gradient (and the same form of the trace kernel): each run is one
+        // lock-step launch sequence
+        for (int j = 0; j < cnt;) {
+            if (!sl.ok[j]) {
+                j++;
                 continue;
             }
-            // idle: the next candidates (NaN thetas are answered at once, algorithm.rs:885-891)
-            while (next < k && (int)sl.cand.size() < slot_cap(i)) {
-                const int64_t c = next++;
-                const double *th = thetas + c * theta_len;
-                const size_t j = sl.cand.size();
-                EGX_RC(make_coef(gp, th, theta_len, sl.coefs[j], sl.hcols, &sl.thfull[j]));
-                for (int l = 0; l < h; l++) grad[c * h + l] = 0.0;
-                if (has_nan(th, theta_len)) {
-                    lkh[c] = -std::numeric_limits<double>::infinity();
-                    status[c] = EGX_STATUS_NAN_THETA;
-                    continue;
-                }
-                sl.cand.push_back(c);
-            }
-            if (!sl.cand.empty()) {
-                EGX_RC(enqueue_eval_group(gp, w0, (int)sl.cand.size(), sl.coefs.data(), sl.hcols,
-                                          gp->slab_W + (int64_t)(i * B) * gp->n_pad * gp->n_pad));
-                sl.phase = 1;
-                busy++;
-            }
-            if (next >= k && busy == 0) return EGX_SUCCESS;
+            int e = j;
+            while (e < cnt && sl.ok[e] && sl.pre[e] == sl.pre[j]) e++;
+            EGX_RC(enqueue_grad_run(gp, st, w0 + j, e - j, i * g.width + j, inv_s2.data() + j, sl.hcols, sl.pre[j]));
+            j = e;
         }
+        return EGX_SUCCESS;
     };
-    const int rc = run();
-    if (rc) {  // leave no work behind that still writes into the workspaces
-        const std::string msg = last_error_string();
-        for (int i = 0; i < nslots; i++)
-            if (slots[i].phase != 0) (void)hipStreamSynchronize(gp->ws[ws_lo + i * B].stream);
-        (void)hipGetLastError();
-        set_error(msg);
-    }
-    return rc;
+    return run_slots(gp, g, src, k, admit, enqueue, advance);
 }
 }  // namespace egx
 

@@ -18,6 +18,7 @@
 
 #include "egx_internal.h"
 #include "dev_mem.h"
+#include "slot_pipeline.h"
 #include "host_math.h"
 #include "cobyla.h"
 
@@ -65,7 +66,6 @@ struct Workspace : WorkspaceHandles {
     DevMem<double> dW;      // (n_pad/256) x 256 x 256 transposed inverses of the diagonal blocks (lazy)
     DevMem<double> d_coef;  // d x hcols
     DevMem<double> d_xs;    // d x n_pad: the inputs times this candidate's coefficients (K1's scalar-row form)
-    DevMem<double> d_diag;  // n
     DevMem<double> d_vec;   // n_pad (gamma)
     DevMem<double> d_rhs;   // n_pad (rho, destroyed by the back-substitution)
     const int *sync_lead = nullptr;  // hand-off words of the lead of the lock-step group this evaluation ran in (diagnostics)
@@ -91,7 +91,7 @@ struct Workspace : WorkspaceHandles {
     PinMem<double> h_gout;
     // device bytes held (what the resource pool counts): EVERY DevMem above
     size_t device_bytes() const {
-        return dW.bytes + d_coef.bytes + d_xs.bytes + d_diag.bytes + d_vec.bytes + d_rhs.bytes + d_gneg.bytes + d_gram.bytes +
+        return dW.bytes + d_coef.bytes + d_xs.bytes + d_vec.bytes + d_rhs.bytes + d_gneg.bytes + d_gram.bytes +
                d_gdinv.bytes + d_gramP.bytes + d_beta.bytes + d_part.bytes + d_ginfo.bytes + d_gpart.bytes + d_gout.bytes;
     }
 };
@@ -247,19 +247,29 @@ int eval_one(egx_gp *gp, int widx, const double *theta, int64_t theta_len, EvalR
 // the host GLS's rho into w.d_rhs, zero padded, on stream st (the device GLS leaves it there itself)
 int upload_rho(egx_gp *gp, Workspace &w, const EvalResult &res, hipStream_t st);
 int do_finalize(egx_gp *gp, const double *theta, int64_t theta_len);
-// Where a batch takes its candidates from: the sequence 0 .. k-1 (nullptr), a rank's static shard or the node-wide
-// counter of a dynamic sweep (sweep.hip).  pull() hands out up to `want` candidate indices, 0 = exhausted.
-struct CandidateSource {
-    virtual int pull(int want, int64_t *out) = 0;
-    virtual ~CandidateSource() = default;
-};
+// The slot pipeline (slot_pipeline.h) over the workspaces of a handle: what both batch cores below run.  Candidates come
+// from `src` (nullptr: the sequence 0 .. k-1; a rank's static shard or the node-wide counter of a dynamic sweep, sweep.hip);
+// slot i synchronises the stream of its first workspace; a source's index out of range is the error it always was.
+// (The synchronisations after an error set no error text: the first error's stays.)
+template <class Admit, class Enqueue, class Advance>
+int run_slots(egx_gp *gp, const SlotGeometry &g, CandidateSource *src, int64_t k, Admit &&admit, Enqueue &&enqueue, Advance &&advance) {
+    SequentialSource seq(k);
+    const int rc = run_slot_pipeline(g, src ? *src : static_cast<CandidateSource &>(seq), k, admit, enqueue, advance,
+                                     [&](int i) { (void)hipStreamSynchronize(gp->ws[g.first_ws(i)].stream); });
+    if (rc) (void)hipGetLastError();
+    if (rc == kSlotBadIndex) {
+        set_error("likelihood batch: the candidate source returned an index out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    return rc;
+}
 // Evaluates the candidates `src` hands out (rows of thetas, k x theta_len) pipelined over the handle's workspaces;
 // results go to lkh[c] / status[c] of the candidate's own index, evaluated[c] (optional, k chars) is set for them.
 int likelihood_batch_core(egx_gp *gp, const double *thetas, int64_t k, int64_t theta_len, double *lkh, int32_t *status,
                           CandidateSource *src = nullptr, char *evaluated = nullptr);
-// likelihood + dL/dtheta of k candidates, pipelined over the workspaces in lock-step slots (gp_fit.hip)
+// likelihood + dL/dtheta of the candidates `src` hands out, pipelined over the workspaces in lock-step slots (gp_fit.hip)
 int likelihood_grad_batch_core(egx_gp *gp, const double *thetas, int64_t k, int64_t theta_len, double *lkh, double *grad,
-                               int32_t *status);
+                               int32_t *status, CandidateSource *src = nullptr);
 // gp_predict.hip
 int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout);
 int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv);

@@ -156,7 +156,6 @@ static int alloc_workspace(egx_gp *gp, Workspace &w) {
     const size_t hmax = gp->has_w ? gp->h : 1, d = (size_t)gp->d, n_pad = (size_t)gp->n_pad;
     EGX_RC(w.d_coef.alloc(d * hmax));
     EGX_RC(w.d_xs.alloc(d * n_pad));
-    EGX_RC(w.d_diag.alloc(n_pad));
     EGX_RC(w.d_vec.alloc(n_pad));
     EGX_RC(w.d_rhs.alloc(n_pad));
     EGX_RC(w.h_coef.alloc(d * hmax));
@@ -347,13 +346,18 @@ int make_coef(const egx_gp *gp, const double *theta, int64_t theta_len, std::vec
 
 // GPU half of `count` likelihood evaluations on the consecutive workspaces w0 ..: R assembly + RHS rows per candidate,
 // ONE factorisation launch sequence for all of them (lock-step batch, kernels_chol.hip) with fused forward solves,
-// diagonal gather, async download of (diag C, ft^T, yt^T, info) per candidate.  All asynchronous on the streams of
-// workspace w0; every member's eval_stream is set to it.
+// ONE tail launch that writes (diag C, ft^T, yt^T, info) of every candidate into its pinned host buffers.  All asynchronous
+// on the streams of workspace w0; every member's eval_stream is set to it.  There is one path: 1 <= count <= kLockstepMax (what
+// the kernels' pointer blocks hold; egx_gp_set_lockstep clamps the width to it), a lone candidate is a batch of one.
 // core: evaluation j uses the training set of owners[j] and the workspace wss[j]; the workspaces are consecutive slots of ONE
 // slab (a handle's, or a group's: egx_gp_create_group), the launches run on the streams of the first
 // separate: the chain by separate launches whatever the handle's schedule says (finish_eval's retry of an aborted chain launch)
 static int enqueue_eval_core(egx_gp *const *owners, Workspace *const *wss, int count, const std::vector<double> *coefs, int hcols,
                              double *W0, bool separate = false) {
+    if (count < 1 || count > kLockstepMax) {
+        set_error("enqueue_eval: a lock-step launch takes 1 .. " + std::to_string(kLockstepMax) + " candidates, got " + std::to_string(count));
+        return EGX_ERR_INVALID_VALUE;
+    }
     egx_gp *gp = owners[0];
     Workspace &lead = *wss[0];
     hipStream_t st = lead.stream;
@@ -376,19 +380,16 @@ static int enqueue_eval_core(egx_gp *const *owners, Workspace *const *wss, int c
     EGX_HIP_CHECK(hipMemsetAsync(lead.d_info, 0, sizeof(int) * (size_t)count, st));
     EGX_HIP_CHECK(hipEventRecord(lead.ev[0], st));
     // the candidates' pointers for the batched front-end and tail launches (by value in the kernel arguments)
-    EvalBatchPtrs bp;
     // (a lone candidate takes the same route: its tail is then one launch instead of a gather + four copies -- 30 us of a
     //  0.12-0.4 ms evaluation at n = 128 ... 1024)
-    const bool batched = count >= 1 && count <= EvalBatchPtrs::kMax;
-    if (batched)
-        for (int j = 0; j < count; j++) {
-            Workspace &w = *wss[j];
-            bp.xT[j] = owners[j]->d_xT, bp.coef[j] = w.d_coef, bp.rhsT[j] = owners[j]->d_rhsT, bp.xs[j] = w.d_xs, bp.M[j] = w.M;
-            bp.h_diag[j] = w.h_diag, bp.h_rows[j] = w.h_rows, bp.h_info[j] = w.h_info, bp.d_info[j] = w.d_info;
-        }
-    int front = batched ? launch_eval_front_batch(st, gp->corr, bp, count, gp->n_pad, gp->n, gp->d, hcols, gp->nugget, gp->ld,
-                                                  gp->n_pad, gp->rhs_pad, gp->q)
-                        : EGX_ERR_UNSUPPORTED;
+    EvalBatchPtrs bp;
+    for (int j = 0; j < count; j++) {
+        Workspace &w = *wss[j];
+        bp.xT[j] = owners[j]->d_xT, bp.coef[j] = w.d_coef, bp.rhsT[j] = owners[j]->d_rhsT, bp.xs[j] = w.d_xs, bp.M[j] = w.M;
+        bp.h_diag[j] = w.h_diag, bp.h_rows[j] = w.h_rows, bp.h_info[j] = w.h_info, bp.d_info[j] = w.d_info;
+    }
+    const int front = launch_eval_front_batch(st, gp->corr, bp, count, gp->n_pad, gp->n, gp->d, hcols, gp->nugget, gp->ld, gp->n_pad,
+                                              gp->rhs_pad, gp->q);
     if (front != EGX_SUCCESS && front != EGX_ERR_UNSUPPORTED) return front;
     if (front == EGX_ERR_UNSUPPORTED)  // Matern with KPLS weights (hcols > 1) or d > 64: launch by launch
         for (int j = 0; j < count; j++) {
@@ -425,14 +426,10 @@ static int enqueue_eval_core(egx_gp *const *owners, Workspace *const *wss, int c
                         &lead.trace, &pb, W0 ? &inv : nullptr));
     EGX_HIP_CHECK(hipEventRecord(lead.ev[2], st));
     // what the host needs back: ONE launch writes every candidate's diagonal, solved right-hand-side rows, info and hand-off
-    // diagnostics straight into its pinned host buffers (k_eval_tail); beyond 16 candidates (never today): a gather + copies each
-    if (batched) EGX_RC(launch_eval_tail(st, bp, count, gp->ld, gp->n, gp->n_pad, gp->q, gp->gls_device ? 0 : 1, pb.sync));
+    // diagnostics straight into its pinned host buffers (k_eval_tail), whichever front end built the matrices
+    EGX_RC(launch_eval_tail(st, bp, count, gp->ld, gp->n, gp->n_pad, gp->q, gp->gls_device ? 0 : 1, pb.sync));
     for (int j = 0; j < count; j++) {
         Workspace &w = *wss[j];
-        if (!batched) {
-            EGX_RC(launch_gather_diag(st, w.M, gp->ld, gp->n, w.d_diag));
-            EGX_HIP_CHECK(hipMemcpyAsync(w.h_diag, w.d_diag, sizeof(double) * gp->n, hipMemcpyDeviceToHost, st));
-        }
         w.gls_enqueued = gp->gls_device;
         if (gp->gls_device) {
             // p > 1: ft never leaves the device.  Gram matrix of the solved rows [ft | yt] (split-K MFMA, fixed-order
@@ -445,17 +442,8 @@ static int enqueue_eval_core(egx_gp *const *owners, Workspace *const *wss, int c
             EGX_RC(launch_potrf(st, w.d_gram, g, g, g, w.d_gdinv, w.d_ginfo));
             EGX_HIP_CHECK(hipMemcpyAsync(w.h_gram, w.d_gram, sizeof(double) * (size_t)g * g, hipMemcpyDeviceToHost, st));
             EGX_HIP_CHECK(hipMemcpyAsync(w.h_ginfo, w.d_ginfo, sizeof(int), hipMemcpyDeviceToHost, st));
-        } else if (!batched) {
-            EGX_HIP_CHECK(hipMemcpyAsync(w.h_rows, w.M + (size_t)gp->n_pad * gp->ld,
-                                         sizeof(double) * (size_t)gp->q * gp->n_pad, hipMemcpyDeviceToHost, st));
         }
         w.sync_lead = pb.sync;  // word 0 of the LEAD's hand-off words: non-zero iff a bounded wait inside a chain launch ran out
-        if (batched) continue;
-        EGX_HIP_CHECK(hipMemcpyAsync(w.h_info, w.d_info, sizeof(int), hipMemcpyDeviceToHost, st));
-        if (pb.sync)
-            EGX_HIP_CHECK(hipMemcpyAsync(w.h_info + 1, pb.sync, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
-        else  // (a handle whose schedule has no chain launches never touches its hand-off words)
-            w.h_info[1] = 0;
     }
     EGX_HIP_CHECK(hipEventRecord(lead.ev[3], st));
     return EGX_SUCCESS;
@@ -796,7 +784,7 @@ int eval_one(egx_gp *gp, int widx, const double *theta, int64_t theta_len, EvalR
 
 // the longest run of models that one call evaluates in lock-step (multi_run_len)
 constexpr int kMaxRun = 12;
-static_assert(kMaxRun <= SolveBatchPtrs::kMax && kMaxRun <= EvalBatchPtrs::kMax, "a run must fit one batched launch");
+static_assert(kMaxRun <= kLockstepMax, "a run must fit one lock-step launch");
 
 // The host halves (finish_eval) of a run of `len` models evaluated by enqueue_eval_members.  On the host-GLS route (the
 // log-determinant over the diagonal, GLS: ~0.1 ms per model at n = 8192, no HIP launches) they run side by side on host threads;
@@ -869,9 +857,10 @@ int upload_rho(egx_gp *gp, Workspace &w, const EvalResult &res, hipStream_t st) 
 // A fit at fixed theta of a run of 1 .. kMaxRun models: a lone handle, or members of one group in consecutive slots
 // (egx_gp_finalize_multi).  On the stream of the evaluation (the lead's): the evaluation, then the inverse blocks for gamma's
 // back-substitution (they only need the factors, and run while the host waits for the read-back and does the GLS: 84 us off a
-// fit's critical path); after the host halves ONE back-substitution launch sequence for all models (launch_trsv_t_batch: 64
+// fit's critical path); after the host halves ONE back-substitution launch sequence for all models (launch_trsv_t: 64
 // launches instead of 64 per model -- the command processor serialises such ~5 us launches however many streams or host threads
 // issue them) and the fitted state's device copies; one synchronisation, then every model takes over its fitted state.
+// A lone model is a run of one: the same launchers, the same kernels (blockIdx.y = model).
 // A model that fails leaves the others to finish: first_rc keeps the first error of a model; the return value is an error of
 // what the run's models share.
 static int fit_run(egx_gp *const *gps, int len, const std::vector<double> *coefs, int hcols, const std::vector<double> *thfull,
@@ -887,8 +876,7 @@ static int fit_run(egx_gp *const *gps, int len, const std::vector<double> *coefs
         EGX_RC(w.dW.alloc(block_inverse_doubles(gps[j]->n_pad)));
         bp.M[j] = w.M, bp.dinv[j] = w.dinv, bp.dW[j] = w.dW, bp.rhs[j] = w.d_rhs, bp.vec[j] = w.d_vec;
     }
-    if (len == 1) EGX_RC(launch_block_inverse(st, bp.M[0], lead->ld, lead->n_pad, bp.dinv[0], bp.dW[0]));
-    else EGX_RC(launch_block_inverse_batch(st, bp, len, lead->ld, lead->n_pad));
+    EGX_RC(launch_block_inverse(st, bp, len, lead->ld, lead->n_pad));
     std::vector<HostHalf> hh((size_t)len);
     host_halves(gps, len, 1, hh.data());
     int live[kMaxRun], nlive = 0;
@@ -910,8 +898,7 @@ static int fit_run(egx_gp *const *gps, int len, const std::vector<double> *coefs
     }
     if (nlive == 0) return EGX_SUCCESS;
     // gamma = C^-T rho   (algorithm.rs:1034)
-    if (len == 1) EGX_RC(launch_trsv_t(st, bp.M[0], lead->ld, lead->n_pad, bp.dW[0], bp.rhs[0], bp.vec[0]));
-    else EGX_RC(launch_trsv_t_batch(st, bp, nlive, lead->ld, lead->n_pad));
+    EGX_RC(launch_trsv_t(st, bp, nlive, lead->ld, lead->n_pad));
     for (int q = 0; q < nlive; q++) {
         egx_gp *gp = gps[live[q]];
         Workspace &w = gp->ws[0];
@@ -989,91 +976,45 @@ int do_finalize(egx_gp *gp, const double *theta, int64_t theta_len) {
     EGX_RC(fit_run(&gp, 1, &coef, hcols, &thfull, rc));
     return rc;
 }
-// Candidates pipelined over the handle's workspaces (caller holds gp->mu exclusively and has set the device).
-// The workspaces form SLOTS of gp->lockstep consecutive ones; the candidates of a slot are factored in lock-step by one
-// launch sequence (enqueue_eval_group), different slots run on their own stream sets, so that the exposed serial parts
-// of one slot (first group's chain, the last ~3000 columns) overlap the trailing updates of the other.  A slot whose
-// candidates have been read back takes the next ones the source hands out.
+// Candidates pipelined over the handle's workspaces (caller holds gp->mu exclusively and has set the device): the one-phase
+// client of the slot pipeline.  Slots of gp->lockstep consecutive workspaces, ALL of the handle's; the candidates of a slot
+// are factored in lock-step by one launch sequence (enqueue_eval_group); a slot whose candidates have been read back
+// (finish_eval) takes the next ones the source hands out.  NaN thetas are answered at once (algorithm.rs:885-891).
 int likelihood_batch_core(egx_gp *gp, const double *thetas, int64_t k, int64_t theta_len, double *lkh, int32_t *status,
                           CandidateSource *src, char *evaluated) {
-    struct Sequential final : CandidateSource {
-        int64_t k, next = 0;
-        explicit Sequential(int64_t k_) : k(k_) {}
-        int pull(int want, int64_t *out) override {
-            int got = 0;
-            while (got < want && next < k) out[got++] = next++;
-            return got;
-        }
-    } seq(k);
-    if (!src) src = &seq;
     // a fitted model keeps its factor (workspace 0) as long as another workspace exists
     const int ws_lo = (gp->fitted && gp->ws.size() > 1) ? 1 : 0;
-    const int nws = (int)gp->ws.size() - ws_lo;
-    const int B = gp->lockstep < nws ? (gp->lockstep < 1 ? 1 : gp->lockstep) : nws;
-    const int nslots = (nws + B - 1) / B;  // the last slot may hold fewer workspaces (11 starts: 4 + 4 + 3)
-    auto slot_cap = [&](int i) { return std::min(B, nws - i * B); };
-    std::vector<std::vector<int64_t>> cand(nslots);  // candidates in flight on slot i (workspaces ws_lo + i B ...)
-    bool exhausted = false;
-    int busy = 0;
-    // next candidate with a usable theta (NaN thetas are answered at once, algorithm.rs:885-891)
-    auto next_valid = [&](int64_t &c, std::vector<double> &coef, int &hcols) -> int {
-        while (!exhausted) {
-            if (src->pull(1, &c) == 0) {
-                exhausted = true;
-                break;
-            }
-            if (c < 0 || c >= k) {
-                set_error("likelihood batch: the candidate source returned an index out of range");
-                return EGX_ERR_INVALID_VALUE;
-            }
-            const double *th = thetas + c * theta_len;
-            EGX_RC(make_coef(gp, th, theta_len, coef, hcols, nullptr));
-            if (evaluated) evaluated[c] = 1;
-            if (!has_nan(th, theta_len)) return EGX_SUCCESS;
-            lkh[c] = -std::numeric_limits<double>::infinity();
-            status[c] = EGX_STATUS_NAN_THETA;
-        }
-        c = -1;
+    const SlotGeometry g = slot_geometry(ws_lo, (int)gp->ws.size() - ws_lo, gp->lockstep, kLockstepMax);
+    std::vector<std::vector<int64_t>> cand(g.nslots);  // candidates in flight on slot i
+    std::vector<std::vector<double>> coefs(g.width);   // of the slot being filled (enqueue_eval_core copies them)
+    int hcols = 1;
+    auto admit = [&](int i, int j, int64_t c, bool &valid) -> int {
+        const double *th = thetas + c * theta_len;
+        EGX_RC(make_coef(gp, th, theta_len, coefs[j], hcols, nullptr));
+        if (evaluated) evaluated[c] = 1;
+        valid = !has_nan(th, theta_len);
+        if (valid) cand[i].push_back(c);
+        else lkh[c] = -std::numeric_limits<double>::infinity(), status[c] = EGX_STATUS_NAN_THETA;
         return EGX_SUCCESS;
     };
-    auto run = [&]() -> int {
-        std::vector<std::vector<double>> coefs(B);
-        for (int i = 0;; i = (i + 1) % nslots) {
-            const int w0 = ws_lo + i * B;
-            if (!cand[i].empty()) {
-                for (size_t j = 0; j < cand[i].size(); j++) {
-                    EvalResult res;
-                    EGX_RC(finish_eval(gp, gp->ws[w0 + (int)j], res, 0));
-                    lkh[cand[i][j]] = res.lkh;
-                    status[cand[i][j]] = res.status;
-                }
-                if (w0 == 0) record_timings(gp, gp->ws[0], 0.0, 0.0);
-                cand[i].clear();
-                busy--;
-            }
-            int hcols = 1;
-            while (!exhausted && (int)cand[i].size() < slot_cap(i)) {
-                int64_t c;
-                EGX_RC(next_valid(c, coefs[cand[i].size()], hcols));
-                if (c >= 0) cand[i].push_back(c);
-            }
-            if (!cand[i].empty()) {
-                if (w0 == 0) gp->fitted = false;
-                EGX_RC(enqueue_eval_group(gp, w0, (int)cand[i].size(), coefs.data(), hcols));
-                busy++;
-            }
-            if (exhausted && busy == 0) return EGX_SUCCESS;
-        }
+    auto enqueue = [&](int i, int count) -> int {
+        if (g.first_ws(i) == 0) gp->fitted = false;
+        return enqueue_eval_group(gp, g.first_ws(i), count, coefs.data(), hcols);
     };
-    const int rc = run();
-    if (rc) {  // leave no work behind that still writes into the workspaces
-        const std::string msg = last_error_string();
-        for (int i = 0; i < nslots; i++)
-            if (!cand[i].empty()) (void)hipStreamSynchronize(gp->ws[ws_lo + i * B].stream);
-        (void)hipGetLastError();
-        set_error(msg);
-    }
-    return rc;
+    auto advance = [&](int i, int, bool &idle) -> int {
+        const int w0 = g.first_ws(i);
+        for (size_t j = 0; j < cand[i].size(); j++) {
+            EvalResult res;
+            EGX_RC(finish_eval(gp, gp->ws[w0 + (int)j], res, 0));
+            lkh[cand[i][j]] = res.lkh;
+            status[cand[i][j]] = res.status;
+        }
+        if (w0 == 0) record_timings(gp, gp->ws[0], 0.0, 0.0);
+        cand[i].clear();
+        idle = true;
+        return EGX_SUCCESS;
+    };
+    return run_slots(gp, g, src, k, admit, enqueue, advance);
 }
 }  // namespace egx
 
@@ -1442,7 +1383,8 @@ int32_t egx_gp_set_lockstep(egx_gp *gp, int32_t width) {
     }
     std::unique_lock<std::shared_mutex> lock(gp->mu);
     const int nws = (int)gp->ws.size();
-    gp->lockstep = width == 0 ? default_lockstep(nws, gp->n_pad) : (width > nws ? nws : width);
+    // (a wider request gives slots of kLockstepMax: lockstep, the schedule and PotrfBatch::seqs describe what actually runs)
+    gp->lockstep = width == 0 ? default_lockstep(nws, gp->n_pad) : std::min(width, std::min(nws, kLockstepMax));
     gp->sched = schedule_for(gp->n_pad, gp->lockstep, nws);
     if (gp->group) gp->sched.flow = gp->sched.flow_tail = 0;
     EGX_RC(set_device(gp));

@@ -816,14 +816,10 @@ __device__ __forceinline__ void block_inv256_body(const double *__restrict__ M, 
             __syncthreads();
         }
 }
-__global__ __launch_bounds__(512, 2) void k_block_inv256(const double *__restrict__ M, int64_t ld, int n_pad,
-                                                         const double *__restrict__ dinv, double *__restrict__ Wall) {
-    block_inv256_body(M, ld, n_pad, dinv, Wall);
-}
-// ... of several models at once (blockIdx.y = model; egx_gp_finalize_multi): the back-substitutions of eight experts are
-// 8 x 65 launches of ~5 us that the command processor serialises however many streams and host threads issue them -- in
-// lock-step they are 65 (profiles/r05_expert_group_*.txt)
-__global__ __launch_bounds__(512, 2) void k_block_inv256_batch(SolveBatchPtrs b, int64_t ld, int n_pad) {
+// blockIdx.y = model (this and the kernels below; a lone model is a batch of one).  Several models at once
+// (egx_gp_finalize_multi): the back-substitutions of eight experts are 8 x 65 launches of ~5 us that the command processor
+// serialises however many streams and host threads issue them -- in lock-step they are 65 (profiles/r05_expert_group_*.txt)
+__global__ __launch_bounds__(512, 2) void k_block_inv256(SolveBatchPtrs b, int64_t ld, int n_pad) {
     block_inv256_body(b.M[blockIdx.y], ld, n_pad, b.dinv[blockIdx.y], b.dW[blockIdx.y]);
 }
 
@@ -852,11 +848,7 @@ __device__ __forceinline__ void trsv_w_body(const double *__restrict__ W, int nb
         }
     }
 }
-__global__ __launch_bounds__(256) void k_trsv_w(const double *__restrict__ W, int nbk, const double *__restrict__ v,
-                                                double *__restrict__ xout) {
-    trsv_w_body(W, nbk, v, xout);
-}
-__global__ __launch_bounds__(256) void k_trsv_w_batch(SolveBatchPtrs b, int blk, int k0, int nbk) {
+__global__ __launch_bounds__(256) void k_trsv_w(SolveBatchPtrs b, int blk, int k0, int nbk) {
     const int z = blockIdx.y;
     trsv_w_body(b.dW[z] + (int64_t)blk * 65536, nbk, b.rhs[z] + k0, b.vec[z] + k0);
 }
@@ -882,11 +874,7 @@ __device__ __forceinline__ void gemv_t_update_body(const double *__restrict__ Mr
     __syncthreads();
     if (g == 0) v[j] -= ((red[0][jl] + red[1][jl]) + red[2][jl]) + red[3][jl];
 }
-__global__ __launch_bounds__(256) void k_gemv_t_update(const double *__restrict__ Mrow, int64_t ld, int nbk,
-                                                       const double *__restrict__ x, double *__restrict__ v) {
-    gemv_t_update_body(Mrow, ld, nbk, x, v);
-}
-__global__ __launch_bounds__(256) void k_gemv_t_update_batch(SolveBatchPtrs b, int64_t ld, int k0, int nbk) {
+__global__ __launch_bounds__(256) void k_gemv_t_update(SolveBatchPtrs b, int64_t ld, int k0, int nbk) {
     const int z = blockIdx.y;
     gemv_t_update_body(b.M[z] + (int64_t)k0 * ld, ld, nbk, b.vec[z] + k0, b.rhs[z]);
 }
@@ -895,7 +883,7 @@ __global__ __launch_bounds__(256) void k_gemv_t_update_batch(SolveBatchPtrs b, i
 // MFMA layout probe: C(16x16) = A(16x16) B(16x16) with asymmetric operands.
 // ---------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------
-// gamma = C^-T rho as ONE launch (round 6; launch_trsv_t / launch_trsv_t_batch): the block back-substitution above is
+// gamma = C^-T rho as ONE launch (round 6; launch_trsv_t): the block back-substitution above is
 // 2 n / 256 launches of ~5 us in a row -- 0.81 ms of a 29.6-ms fit at n = 16384, 0.16 of 1.7 ms at n = 4096 -- for 1.07 GB of
 // factor that stream in 0.2 ms.  Here one workgroup per 64 COLUMNS of the right-hand side (a segment) keeps that piece of
 // rho in registers, takes the blocks' solutions x_b in order b = last ... as they appear (its 256 x 64 piece of L fetched
@@ -990,11 +978,7 @@ __device__ __forceinline__ void trsv_fused_body(const double *__restrict__ M, in
         if (lane == 0 && row0 + u < nbk) __hip_atomic_store(x + k0 + row0 + u, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-__global__ __launch_bounds__(256) void k_trsv_t_fused(const double *__restrict__ M, int64_t ld, int n_pad, const double *__restrict__ Wall,
-                                                      const double *__restrict__ rhs, double *x, double *tail, long long limit, int stall) {
-    trsv_fused_body(M, ld, n_pad, Wall, rhs, x, tail, limit, stall);
-}
-__global__ __launch_bounds__(256) void k_trsv_t_fused_batch(SolveBatchPtrs b, int64_t ld, int n_pad, long long limit, int stall) {
+__global__ __launch_bounds__(256) void k_trsv_t_fused(SolveBatchPtrs b, int64_t ld, int n_pad, long long limit, int stall) {
     const int z = blockIdx.y;
     trsv_fused_body(b.M[z], ld, n_pad, b.dW[z], b.rhs[z], b.vec[z], b.dW[z] + (int64_t)((n_pad + kNB - 1) / kNB) * 65536, limit, stall);
 }
@@ -1761,59 +1745,25 @@ int launch_diag_tile_inverses(hipStream_t s, const double *M, int64_t ld, int n_
     return EGX_SUCCESS;
 }
 
-int launch_block_inverse(hipStream_t s, const double *M, int64_t ld, int n_pad, const double *dinv, double *Wall) {
+// dW[j] <- the 256 x 256 inverse blocks of factor j;  vec[j] (n_pad) <- C_j^-T rhs[j]   for `count` models of one shape in
+// lock-step (blockIdx.y = model); a lone factor is a batch of one (the inline overloads of egx_internal.h)
+int launch_block_inverse(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad) {
     int rc = chol_init();
     if (rc) return rc;
     constexpr int lds = GemmShape<64, 64, 16, 32, 512>::LDS_BYTES;
-    hipLaunchKernelGGL(k_block_inv256, dim3((n_pad + kNB - 1) / kNB), dim3(512), lds, s, M, ld, n_pad, dinv, Wall);
+    hipLaunchKernelGGL(k_block_inv256, dim3((unsigned)((n_pad + kNB - 1) / kNB), (unsigned)count), dim3(512), lds, s, b, ld, n_pad);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
-
-int launch_trsv_t(hipStream_t s, const double *M, int64_t ld, int n_pad, const double *Wall, double *v,
-                  double *xout, bool per_block) {
-    // the one-launch form leaves v alone; the launch-per-block form updates it in place above the current block
+int launch_trsv_t(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad, bool per_block) {
+    // the one-launch form leaves rhs alone; the launch-per-block form updates it in place above the current block
     const int nblocks = (n_pad + kNB - 1) / kNB;
     if (!per_block && g_trsv_fused.load() != 0 && n_pad % 64 == 0) {  // one launch (k_trsv_t_fused); its hand-off words sit behind the inverse blocks
-        double *tail = const_cast<double *>(Wall) + (int64_t)nblocks * 65536;
-        EGX_HIP_CHECK(hipMemsetAsync(tail, 0xFF, sizeof(double) * trsv_tail_doubles(n_pad), s));
-        EGX_HIP_CHECK(hipMemsetAsync(xout, 0xFF, sizeof(double) * (size_t)n_pad, s));
-        hipLaunchKernelGGL(k_trsv_t_fused, dim3((unsigned)(n_pad / 64)), dim3(256), 0, s, M, ld, n_pad, Wall, (const double *)v, xout, tail,
-                           pipe_timeout_ticks(), EGX_TRSV_STALL);
-        EGX_HIP_CHECK(hipGetLastError());
-        return EGX_SUCCESS;
-    }
-    for (int b = nblocks - 1; b >= 0; b--) {
-        const int k0 = b * kNB;
-        const int nbk = (n_pad - k0 < kNB) ? (n_pad - k0) : kNB;
-        hipLaunchKernelGGL(k_trsv_w, dim3(8), dim3(256), 0, s, Wall + (int64_t)b * 65536, nbk,
-                           (const double *)(v + k0), xout + k0);
-        if (k0 > 0)
-            hipLaunchKernelGGL(k_gemv_t_update, dim3(k0 / 64), dim3(256), 0, s, M + (int64_t)k0 * ld, ld, nbk,
-                               (const double *)(xout + k0), v);
-    }
-    EGX_HIP_CHECK(hipGetLastError());
-    return EGX_SUCCESS;
-}
-
-// launch_block_inverse / launch_trsv_t for `count` models of one shape in lock-step (blockIdx.y = model):
-// dW[j] <- the 256 x 256 inverse blocks of factor j;  vec[j] (n_pad) <- C_j^-T rhs[j]
-int launch_block_inverse_batch(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad) {
-    int rc = chol_init();
-    if (rc) return rc;
-    constexpr int lds = GemmShape<64, 64, 16, 32, 512>::LDS_BYTES;
-    hipLaunchKernelGGL(k_block_inv256_batch, dim3((unsigned)((n_pad + kNB - 1) / kNB), (unsigned)count), dim3(512), lds, s, b, ld, n_pad);
-    EGX_HIP_CHECK(hipGetLastError());
-    return EGX_SUCCESS;
-}
-int launch_trsv_t_batch(hipStream_t s, const SolveBatchPtrs &b, int count, int64_t ld, int n_pad) {
-    const int nblocks = (n_pad + kNB - 1) / kNB;
-    if (g_trsv_fused.load() != 0 && n_pad % 64 == 0) {
         for (int z = 0; z < count; z++) {
             EGX_HIP_CHECK(hipMemsetAsync(b.dW[z] + (int64_t)nblocks * 65536, 0xFF, sizeof(double) * trsv_tail_doubles(n_pad), s));
             EGX_HIP_CHECK(hipMemsetAsync(b.vec[z], 0xFF, sizeof(double) * (size_t)n_pad, s));
         }
-        hipLaunchKernelGGL(k_trsv_t_fused_batch, dim3((unsigned)(n_pad / 64), (unsigned)count), dim3(256), 0, s, b, ld, n_pad,
+        hipLaunchKernelGGL(k_trsv_t_fused, dim3((unsigned)(n_pad / 64), (unsigned)count), dim3(256), 0, s, b, ld, n_pad,
                            pipe_timeout_ticks(), EGX_TRSV_STALL);
         EGX_HIP_CHECK(hipGetLastError());
         return EGX_SUCCESS;
@@ -1821,8 +1771,8 @@ int launch_trsv_t_batch(hipStream_t s, const SolveBatchPtrs &b, int count, int64
     for (int blk = nblocks - 1; blk >= 0; blk--) {
         const int k0 = blk * kNB;
         const int nbk = (n_pad - k0 < kNB) ? (n_pad - k0) : kNB;
-        hipLaunchKernelGGL(k_trsv_w_batch, dim3(8, (unsigned)count), dim3(256), 0, s, b, blk, k0, nbk);
-        if (k0 > 0) hipLaunchKernelGGL(k_gemv_t_update_batch, dim3((unsigned)(k0 / 64), (unsigned)count), dim3(256), 0, s, b, ld, k0, nbk);
+        hipLaunchKernelGGL(k_trsv_w, dim3(8, (unsigned)count), dim3(256), 0, s, b, blk, k0, nbk);
+        if (k0 > 0) hipLaunchKernelGGL(k_gemv_t_update, dim3((unsigned)(k0 / 64), (unsigned)count), dim3(256), 0, s, b, ld, k0, nbk);
     }
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;

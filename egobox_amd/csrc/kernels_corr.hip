@@ -1181,7 +1181,7 @@ int launch_fill_rows(hipStream_t s, double *M, int64_t ld, int r0, int rows_pad,
 // falls back to launch_corr_sym / launch_fill_rows per candidate otherwise): returns EGX_ERR_UNSUPPORTED without launching
 int launch_eval_front_batch(hipStream_t s, int corr, const EvalBatchPtrs &b, int count, int64_t ldx, int n, int d, int hcols,
                             double nugget, int64_t ld, int n_pad, int rhs_pad, int q) {
-    if (hcols != 1 || d > kCorrDC || count < 1 || count > EvalBatchPtrs::kMax) return EGX_ERR_UNSUPPORTED;
+    if (hcols != 1 || d > kCorrDC || count < 1 || count > kLockstepMax) return EGX_ERR_UNSUPPORTED;
     const int nt2 = n_pad / 128;
     const dim3 grid((unsigned)(4 * (nt2 * (nt2 + 1) / 2)), (unsigned)count);
     const size_t lds = (size_t)d * 64 * sizeof(double);
@@ -1239,7 +1239,7 @@ int grad_partial_doubles(int nout) { return kGradMaxWG * (int)round_up(nout, 32)
 // prescaled != 0 (hcols == 1, every coefficient > 0): batch.xs[z] holds candidate z's inputs times its coefficients
 int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, int d, int hcols, const double *wabs,
                       int nout, int64_t ld, const GradBatch &batch, int prescaled) {
-    if (batch.count < 1 || batch.count > kGradMaxBatch) {
+    if (batch.count < 1 || batch.count > kLockstepMax) {
         set_error("grad_accum: batch count out of range");
         return EGX_ERR_INVALID_VALUE;
     }

@@ -217,7 +217,8 @@ class GpHandle:
     # -- likelihood
     def set_lockstep(self, width):
         """Candidates of `likelihood_batch` factored in lock-step by one launch sequence (egx_gp_set_lockstep);
-        0 = the library's default, 1 = one stream set per candidate."""
+        0 = the library's default, 1 = one stream set per candidate.  The width is clamped to min(n_workspaces, 16) -- the
+        most one launch takes; a wider request gives slots of 16 -- and the width in force is returned."""
         L.check(self._lib.egx_gp_set_lockstep(self._h, int(width)))
         return self._lib.egx_gp_get_lockstep(self._h)
 

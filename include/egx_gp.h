@@ -179,7 +179,9 @@ int32_t egx_gp_likelihood_batch(egx_gp *gp, const double *thetas, int64_t k, int
  * schedule; the serial chain of the factorisation then costs its latency once per group and every launch has `width`
  * times the tiles.  1 = every candidate on its own stream set (round 2's pipeline); 0 = the default
  * (min(n_workspaces, 12) below a padded n of 14336 -- one slot: the serial chain is what such an evaluation waits for --,
- * from there on 4, and 8 from 16 workspaces on); at most n_workspaces.  A candidate's result does
+ * from there on 4, and 8 from 16 workspaces on).  The width is CLAMPED to min(n_workspaces, 16) -- 16 candidates are the
+ * most one launch takes; a wider request gives slots of 16 -- and egx_gp_get_lockstep / egx_gp_get_schedule report the
+ * width in force.  A candidate's result does
  * not depend on its companions or on how many of them share its launch (same kernels, same arithmetic: bit-identical);
  * it does not depend on the width either, with ONE exception: a handle with a padded n >= 14336 and a width >= 8 factors
  * LEFT-looking over its panel groups (two long-K updates per tile of the factor instead of one per earlier group), a

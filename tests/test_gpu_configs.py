@@ -988,6 +988,74 @@ def test_theta_gradient_batch_is_bit_identical_to_single_candidates(egx, n, d, c
     assert len(ok) >= 5 and all(np.all(np.isfinite(g[c])) and np.abs(g[c]).max() > 0 for c in ok)
 
 
+@pytest.mark.parametrize("corr,d,kpls", [
+    (3, 6, 2),     # Matern 5/2 with KPLS weights: two coefficient columns per dimension (hcols > 1)
+    (0, 70, 0),    # squared exponential, more input dimensions than the scalar-row kernels stage (64)
+])
+def test_fallback_front_end_in_lock_step_is_bit_identical_to_single_candidates(egx, corr, d, kpls):
+    """The shapes the batched front end refuses -- Matern with KPLS weights, d > 64 -- build their matrices launch by launch
+    (launch_corr_sym, launch_fill_rows) and then share the slot's ONE tail launch: in slots of four (7 candidates, one a NaN
+    theta that takes no slot: 4 + 2) every candidate gets the bits of a slot of one, and likelihood_grad_batch the bits of
+    likelihood_grad."""
+    n = 300
+    x, y = _data(n, d, 17)
+    rng = np.random.default_rng(60 + corr)
+    w = None
+    if kpls:
+        w = rng.standard_normal((d, kpls))
+        w /= np.linalg.norm(w, axis=0)
+        base = np.array([1.8, 2.8])
+    else:
+        base = egx.workload.default_theta(d) * 3.0
+    thetas = base * 10.0 ** rng.uniform(-0.15, 0.15, (7, base.size))
+    thetas[3, 0] = np.nan
+    with egx.GpHandle(x, y, corr=corr, w_star=w, n_workspaces=4) as h:
+        assert h.set_lockstep(1) == 1
+        ref_lk, ref_st = h.likelihood_batch(thetas)
+        single = [h.likelihood_grad(t) for t in thetas]
+        assert h.set_lockstep(4) == 4
+        lk, st = h.likelihood_batch(thetas)
+        lkg, g, stg = h.likelihood_grad_batch(thetas)
+    ok = np.arange(7) != 3
+    assert ref_st[3] == egx._lib.STATUS_NAN_THETA and np.all(ref_st[ok] == 0)
+    np.testing.assert_array_equal(st, ref_st)
+    np.testing.assert_array_equal(lk, ref_lk)      # bit identical (-inf for the NaN theta in both)
+    np.testing.assert_array_equal(stg, ref_st)
+    np.testing.assert_array_equal(lkg, ref_lk)
+    for c in range(7):
+        assert single[c][2] == ref_st[c] and (single[c][0] == ref_lk[c])
+        np.testing.assert_array_equal(g[c], single[c][1])
+    assert all(np.all(np.isfinite(g[c])) and np.abs(g[c]).max() > 0 for c in range(7) if ok[c]) and np.all(g[3] == 0.0)
+
+
+def test_lockstep_width_is_clamped_to_what_one_launch_takes(egx):
+    """egx_gp_set_lockstep clamps the width to min(n_workspaces, 16): a request for 20 on 20 workspaces gives slots of 16 + 4,
+    the handle reports what runs (width and schedule as after a request for 16), and 40 candidates -- 16 + 4, 16 + 4 -- get the
+    bits of slots of one, likelihoods and theta-gradients."""
+    n, d = 200, 3
+    x, y = _data(n, d, 5)
+    rng = np.random.default_rng(12)
+    thetas = 4.0 * 10.0 ** rng.uniform(-0.2, 0.2, (40, d))  # (short correlation lengths: every R well conditioned)
+    with egx.GpHandle(x, y, corr=0, n_workspaces=20) as h:
+        assert h.set_lockstep(1) == 1
+        ref_lk, ref_st = h.likelihood_batch(thetas)
+        ref_lkg, ref_g, ref_stg = h.likelihood_grad_batch(thetas)
+        assert h.set_lockstep(16) == 16
+        sched16 = h.schedule()
+        assert h.set_lockstep(20) == 16
+        assert h.schedule() == sched16
+        lk, st = h.likelihood_batch(thetas)
+        lkg, g, stg = h.likelihood_grad_batch(thetas)
+    assert np.all(ref_st == 0) and np.all(ref_stg == 0)
+    np.testing.assert_array_equal(st, ref_st)
+    np.testing.assert_array_equal(lk, ref_lk)
+    np.testing.assert_array_equal(stg, ref_stg)
+    np.testing.assert_array_equal(lkg, ref_lkg)
+    np.testing.assert_array_equal(g, ref_g)
+    np.testing.assert_array_equal(lkg, lk)
+    assert np.all(np.isfinite(g)) and np.all(np.abs(g).max(axis=1) > 0)
+
+
 def test_theta_gradient_batch_matches_oracle_and_keeps_a_fitted_model(egx, O):
     """The batch against the oracle's closed form (gp_oracle.likelihood_grad), on a FITTED handle: with more than one
     workspace the fit stays in workspace 0 and predictions are unchanged afterwards."""
