@@ -63,6 +63,11 @@ class InfillParts(C.Structure):
     _fields_ = [(k, c_double_p) for k in ("mean", "var", "grad_mean", "grad_var")]
 
 
+class InfillSurrogate(C.Structure):
+    _fields_ = [("experts", C.POINTER(C.c_void_p)), ("n_experts", C.c_int32), ("weights", c_double_p), ("means", c_double_p),
+                ("precisions_chol", c_double_p), ("heaviside_factor", C.c_double), ("smooth", C.c_int32)]
+
+
 class InfillStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("best_start", C.c_int64), ("evals", c_int64_p)]
 
@@ -183,6 +188,10 @@ SIGNATURES = [
     ("egx_infill_scaling", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p]),
     ("egx_infill_optimize", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
                                         c_double_p, C.POINTER(InfillStats)]),
+    ("egx_infill_create_mix", C.c_int32, [C.POINTER(InfillConfig), C.POINTER(InfillSurrogate), c_double_p, C.c_int32,
+                                          C.POINTER(C.c_void_p)]),
+    ("egx_infill_eval_experts", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                            c_double_p, c_double_p, c_double_p]),
 ]
 
 

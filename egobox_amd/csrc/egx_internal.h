@@ -169,6 +169,23 @@ int launch_infill_trend(hipStream_t s, const InfillTrend &t);
 // gmean / gvar (kTile x d) from launch_xgrad's partial sums (nsplit x kTile x d each), original units
 int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *out_v,
                                const double *x_std, double *gmean, double *gvar);
+// A surrogate with k >= 2 experts, one tile: the mixture's responsibilities at the tile's raw points and the recombination of
+// the experts' tables (expert c of point a at c * estride + a, gradients at (c * estride + a) * d) into the surrogate's slot.
+struct InfillMix {
+    int mt = 0, d = 0, k = 0;
+    bool smooth = true, want_g = false;
+    const double *xq = nullptr;    // the tile's mt raw rows
+    const int *flag = nullptr;     // the tile's kTile flags
+    const double *means = nullptr, *precs = nullptr, *par = nullptr;  // k x d, k x d x d scaled factors, k (gmx_point.h)
+    const double *emean = nullptr, *evar = nullptr, *egmean = nullptr, *egvar = nullptr;
+    int64_t estride = 0;
+    double *mean = nullptr, *var = nullptr, *gmean = nullptr, *gvar = nullptr;  // the surrogate's tile
+    double *dp = nullptr;          // kTile x k x d scratch for d p / d x: needed by smooth gradients, else optional
+    double *probas = nullptr;      // kTile x k copy of the responsibilities, or nullptr
+};
+constexpr size_t kInfillMixMaxLds = 160 * 1024;
+size_t infill_mix_lds_bytes(int d, int k);  // 64 lanes x (3 (d | 1) + 2 (k | 1)) doubles
+int launch_infill_mix(hipStream_t s, const InfillMix &g);
 // value[i] / grad[i * d ..] of the m points of a call; model j of point i at j * mstride + i; grad may be nullptr
 int launch_infill_combine(hipStream_t s, const infill::Params &prm, int k, int d, int64_t m, int64_t mstride, const double *mean,
                           const double *var, const double *gmean, const double *gvar, const double *tol, const int *flag,

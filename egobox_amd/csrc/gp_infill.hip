@@ -9,8 +9,16 @@
 // per (tile, model), one combine, the copies back, ONE synchronisation: the count depends on k and on the number of tiles only.
 // Every launch of a tile has the padded batch size 128, and the splits of the training range are functions of the model
 // alone: the bits of a point do not depend on where it sits nor on its companions (tests/test_gpu_infill.py).
+//
+// A SURROGATE -- the objective, a constraint -- is one dense GP or a mixture of k experts with its Gaussian mixture
+// (egx_infill_create_mix; GpMixture, crates/moe/src/algorithm.rs).  The walk is tile -> surrogate -> expert through the same
+// sequence; a lone expert writes the surrogate's slot of the tables, the experts of a mixture write the expert tables and ONE
+// k_infill_mix launch per (tile, surrogate) recombines them into the slot (smooth: the weighted sums; hard: the expert of the
+// first maximum of the responsibilities -- every expert still evaluates the whole tile, so that every launch keeps the padded
+// batch of 128).  Locks, caches, checks and scratch sizes run over the flat list of all experts.
 #include <set>
 
+#include "gmx_point.h"
 #include "gp_handle.h"
 #include "infill_math.h"
 
@@ -51,12 +59,24 @@ int xgrad_splits(const egx_gp *gp) {
     return (slabs + per - 1) / per;
 }
 
+// models[first .. first + k) are the surrogate's experts; with k >= 2 they own the slots [eslot, eslot + k) of the expert tables
+struct Surrogate {
+    int first = 0, k = 1, eslot = -1;
+    bool smooth = true;
+    std::vector<double> gmx;  // means (k d) | scaled precision factors (k d d) | par (k), as k_gmx_probas reads them
+    DevBuf d_gmx;             // uploaded on the first evaluation
+    bool on_device = false;
+};
+
 }  // namespace
 
 struct egx_infill {
     std::mutex mu;
-    std::vector<egx_gp *> models;  // [0] the objective model, then the constraint models (borrowed)
-    std::vector<double> tol;       // k
+    std::vector<egx_gp *> models;  // every expert of every surrogate, surrogate by surrogate (borrowed)
+    std::vector<Surrogate> surr;   // [0] the objective, then the constraints
+    bool mix_api = false;          // created by egx_infill_create_mix: messages name surrogate and expert
+    int n_eslots = 0, k_max = 1;
+    std::vector<double> tol;       // one per constraint
     infill::Params prm{};
     int d = 0, device = 0;
     std::unique_ptr<ModelCache[]> cache;  // one per model
@@ -65,6 +85,8 @@ struct egx_infill {
     // buffers of a call (grow-only): the whole call's points and results, then the scratch of ONE (tile, model) step
     DevBuf xraw, flag, mean, var, gmean, gvar, value, grad;
     DevBuf xqT, racc, RT, s0, sl, Wt, dneg, out_y, out_v;
+    // the experts of the mixtures: their tables (slot-major like mean / var), d p / d x of one tile, the diagnostics of a call
+    DevBuf emean, evar, egmean, egvar, dprob, dg_probas, dg_dprobas;
 };
 
 namespace {
@@ -78,6 +100,49 @@ struct ModelLocks {
         const std::set<egx_gp *, std::less<egx_gp *>> distinct(h->models.begin(), h->models.end());
         for (egx_gp *gp : distinct) held.emplace_back(gp->mu);
     }
+};
+
+// "model j" for a handle of egx_infill_create, "surrogate j expert e" for one of egx_infill_create_mix
+std::string who(const egx_infill *h, int idx) {
+    if (!h->mix_api) return "model " + std::to_string(idx);
+    for (size_t j = 0; j < h->surr.size(); j++)
+        if (idx < h->surr[j].first + h->surr[j].k)
+            return "surrogate " + std::to_string(j) + " expert " + std::to_string(idx - h->surr[j].first);
+    return "model " + std::to_string(idx);
+}
+
+int check_fitted(const egx_infill *h) {
+    for (size_t e = 0; e < h->models.size(); e++)
+        if (!h->models[e]->fitted) {
+            set_error("infill: " + who(h, (int)e) + " is not fitted (call egx_gp_finalize or egx_gp_fit first)");
+            return EGX_ERR_NOT_FITTED;
+        }
+    return EGX_SUCCESS;
+}
+
+// same d, same device as expert 0 of the objective
+int check_shapes(egx_infill *h) {
+    h->d = h->models[0]->d;
+    h->device = h->models[0]->device;
+    for (size_t e = 1; e < h->models.size(); e++) {
+        if (h->models[e]->d != h->d) {
+            set_error("infill: " + who(h, (int)e) + " has " + std::to_string(h->models[e]->d) + " inputs, " + who(h, 0) + " has " +
+                      std::to_string(h->d));
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (h->models[e]->device != h->device) {
+            set_error("infill: " + who(h, (int)e) + " lives on device " + std::to_string(h->models[e]->device) + ", " + who(h, 0) +
+                      " on device " + std::to_string(h->device));
+            return EGX_ERR_INVALID_VALUE;
+        }
+    }
+    return EGX_SUCCESS;
+}
+
+// what egx_infill_eval_experts asks for: the parts of surrogate j's experts and its responsibilities (host pointers, any nullptr)
+struct ExpertDiag {
+    int j = 0;
+    double *mean = nullptr, *var = nullptr, *gmean = nullptr, *gvar = nullptr, *probas = nullptr, *dprobas = nullptr;
 };
 
 int refresh_cache(egx_infill *h, int j, hipStream_t st) {
@@ -103,25 +168,69 @@ int refresh_cache(egx_infill *h, int j, hipStream_t st) {
     return EGX_SUCCESS;
 }
 
+// One expert's launch sequence for one tile: mean / var (and gmean / gvar when want_g) point at the tile's kTile entries of the
+// table the expert writes; flag: the tile's flags, written by the first expert of the call only (else nullptr).
+int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *var, double *gmean,
+                double *gvar, int *flag) {
+    const int d = h->d;
+    egx_gp *gp = h->models[j];
+    Workspace &w = gp->ws[0];
+    ModelCache &c = h->cache[j];
+    const int n = gp->n, n_pad = gp->n_pad, p = gp->p, rp = gp->rhs_pad;
+    const int msplit = mean_splits(gp), nsplit = xgrad_splits(gp);
+    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag));
+    // r . gamma in split partial sums (algorithm.rs:260-262), before the solve overwrites r
+    EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
+                               gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
+                               gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
+    // rt = C^-1 r (held transposed), sum rt^2 and ft^T rt (:337-352)
+    EGX_RC(launch_cross_corr(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
+                             gp->fit_hcols, h->RT.p, n_pad));
+    EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, h->RT.p, n_pad, kTile));
+    EGX_RC(launch_row_reduce(st, h->RT.p, n_pad, kTile, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p, h->s0.p, h->sl.p));
+    InfillTrend tr;
+    tr.p = p, tr.rp = rp, tr.msplit = msplit;
+    tr.xqT = h->xqT.p, tr.fidx = reinterpret_cast<const int *>(c.fidx.p), tr.beta = c.beta.p, tr.R = c.R.p, tr.Rt = c.Rt.p;
+    tr.racc = h->racc.p, tr.s0 = h->s0.p, tr.sl = h->sl.p;
+    tr.sigma2 = gp->sigma2, tr.y_mean = gp->y_mean, tr.y_std = gp->y_std;
+    tr.mean = mean, tr.var = var;
+    tr.dneg = want_g ? h->dneg.p : nullptr;
+    EGX_RC(launch_infill_trend(st, tr));
+    if (!want_g) return EGX_SUCCESS;
+    // -(R^-1 r + R^-1 F D)^T as an (n_pad x 128) weight matrix: xgrad_impl's two GEMMs, then the two contractions
+    EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * (size_t)n_pad * kTile, st));
+    EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_W, n_pad, h->RT.p, n_pad, n_pad, kTile, n_pad, 0, 1));
+    EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_neg_invkf, rp, h->dneg.p, rp, n_pad, kTile, rp, 0, 0));
+    EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
+                        gp->d_gamma, 0, 1, nsplit, h->out_y.p));
+    EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
+                        h->Wt.p, kTile, 0, nsplit, h->out_v.p));
+    return launch_infill_xgrad_finish(st, tr, d, nsplit, h->out_y.p, h->out_v.p, dev_xnorm(gp) + d, gmean, gvar);
+}
+
 // The evaluation proper; the handle's and the models' locks are held.  value / grad / every member of parts may be nullptr.
-int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts) {
+int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
+                const ExpertDiag *diag = nullptr) {
     if (m < 0 || (m > 0 && !xq)) {
         set_error("bad query array");
         return EGX_ERR_INVALID_VALUE;
     }
-    const int nm = (int)h->models.size(), k = nm - 1, d = h->d;
-    for (int j = 0; j < nm; j++)
-        if (!h->models[j]->fitted) {
-            set_error("infill: model " + std::to_string(j) + " is not fitted (call egx_gp_finalize or egx_gp_fit first)");
-            return EGX_ERR_NOT_FITTED;
-        }
+    const int ne = (int)h->models.size(), nm = (int)h->surr.size(), k = nm - 1, d = h->d;
+    EGX_RC(check_fitted(h));
     if (m == 0) return EGX_SUCCESS;
-    const bool want_g = grad || (parts && (parts->grad_mean || parts->grad_var));
+    const bool want_g = grad || (parts && (parts->grad_mean || parts->grad_var)) ||
+                        (diag && (diag->gmean || diag->gvar || diag->dprobas));
     EGX_RC(set_device(h->models[0]));
     hipStream_t st = h->models[0]->ws[0].stream;
     if (want_g)
-        for (int j = 0; j < nm; j++) EGX_RC(ensure_winv(h->models[j]));  // once per fitted state (synchronises the model's stream)
-    for (int j = 0; j < nm; j++) EGX_RC(refresh_cache(h, j, st));
+        for (int e = 0; e < ne; e++) EGX_RC(ensure_winv(h->models[e]));  // once per fitted state (synchronises the model's stream)
+    for (int e = 0; e < ne; e++) EGX_RC(refresh_cache(h, e, st));
+    for (Surrogate &sg : h->surr)
+        if (sg.k >= 2 && !sg.on_device) {
+            EGX_RC(sg.d_gmx.alloc(sg.gmx.size()));
+            EGX_HIP_CHECK(hipMemcpyAsync(sg.d_gmx.p, sg.gmx.data(), sizeof(double) * sg.gmx.size(), hipMemcpyHostToDevice, st));
+            sg.on_device = true;
+        }
     if (k > 0 && !h->tol_on_device) {
         EGX_RC(h->d_tol.alloc(k));
         EGX_HIP_CHECK(hipMemcpyAsync(h->d_tol.p, h->tol.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
@@ -155,45 +264,54 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
         EGX_RC(h->out_y.alloc((size_t)ns_max * kTile * d));
         EGX_RC(h->out_v.alloc((size_t)ns_max * kTile * d));
     }
+    const int ns = h->n_eslots;
+    const Surrogate *dsg = diag ? &h->surr[diag->j] : nullptr;
+    const bool diag_mix = dsg && dsg->k >= 2;
+    if (ns > 0) {
+        EGX_RC(h->emean.alloc((size_t)ns * M));
+        EGX_RC(h->evar.alloc((size_t)ns * M));
+        if (want_g) {
+            EGX_RC(h->egmean.alloc((size_t)ns * M * d));
+            EGX_RC(h->egvar.alloc((size_t)ns * M * d));
+            EGX_RC(h->dprob.alloc((size_t)kTile * h->k_max * d));
+        }
+    }
+    if (diag_mix) {
+        EGX_RC(h->dg_probas.alloc((size_t)M * dsg->k));
+        if (diag->dprobas) EGX_RC(h->dg_dprobas.alloc((size_t)M * dsg->k * d));
+    }
     int *flag = reinterpret_cast<int *>(h->flag.p);
     EGX_HIP_CHECK(hipMemcpyAsync(h->xraw.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st));
     for (int64_t t0 = 0; t0 < m; t0 += kTile) {
         const int mt = (int)std::min<int64_t>(kTile, m - t0);
-        for (int j = 0; j < nm; j++) {
-            egx_gp *gp = h->models[j];
-            Workspace &w = gp->ws[0];
-            ModelCache &c = h->cache[j];
-            const int n = gp->n, n_pad = gp->n_pad, p = gp->p, rp = gp->rhs_pad;
-            const int msplit = mean_splits(gp), nsplit = xgrad_splits(gp);
-            EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, j == 0 ? flag + t0 : nullptr));
-            // r . gamma in split partial sums (algorithm.rs:260-262), before the solve overwrites r
-            EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
-                                       gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
-                                       gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
-            // rt = C^-1 r (held transposed), sum rt^2 and ft^T rt (:337-352)
-            EGX_RC(launch_cross_corr(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
-                                     gp->fit_hcols, h->RT.p, n_pad));
-            EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, h->RT.p, n_pad, kTile));
-            EGX_RC(launch_row_reduce(st, h->RT.p, n_pad, kTile, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p, h->s0.p, h->sl.p));
-            InfillTrend tr;
-            tr.p = p, tr.rp = rp, tr.msplit = msplit;
-            tr.xqT = h->xqT.p, tr.fidx = reinterpret_cast<const int *>(c.fidx.p), tr.beta = c.beta.p, tr.R = c.R.p, tr.Rt = c.Rt.p;
-            tr.racc = h->racc.p, tr.s0 = h->s0.p, tr.sl = h->sl.p;
-            tr.sigma2 = gp->sigma2, tr.y_mean = gp->y_mean, tr.y_std = gp->y_std;
-            tr.mean = h->mean.p + (size_t)j * M + t0, tr.var = h->var.p + (size_t)j * M + t0;
-            tr.dneg = want_g ? h->dneg.p : nullptr;
-            EGX_RC(launch_infill_trend(st, tr));
-            if (!want_g) continue;
-            // -(R^-1 r + R^-1 F D)^T as an (n_pad x 128) weight matrix: xgrad_impl's two GEMMs, then the two contractions
-            EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * (size_t)n_pad * kTile, st));
-            EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_W, n_pad, h->RT.p, n_pad, n_pad, kTile, n_pad, 0, 1));
-            EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_neg_invkf, rp, h->dneg.p, rp, n_pad, kTile, rp, 0, 0));
-            EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                                gp->d_gamma, 0, 1, nsplit, h->out_y.p));
-            EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                                h->Wt.p, kTile, 0, nsplit, h->out_v.p));
-            EGX_RC(launch_infill_xgrad_finish(st, tr, d, nsplit, h->out_y.p, h->out_v.p, dev_xnorm(gp) + d,
-                                              h->gmean.p + ((size_t)j * M + t0) * d, h->gvar.p + ((size_t)j * M + t0) * d));
+        for (int js = 0; js < nm; js++) {
+            const Surrogate &sg = h->surr[js];
+            const bool lone = sg.k < 2;  // a lone expert writes the surrogate's slot, the experts of a mixture their own tables
+            for (int e = 0; e < sg.k; e++) {
+                const size_t row = (lone ? (size_t)js : (size_t)(sg.eslot + e)) * M + t0;
+                EGX_RC(expert_tile(h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
+                                   (lone ? h->var.p : h->evar.p) + row, want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr,
+                                   want_g ? (lone ? h->gvar.p : h->egvar.p) + row * d : nullptr,
+                                   sg.first + e == 0 ? flag + t0 : nullptr));
+            }
+            if (lone) continue;
+            InfillMix mx;
+            mx.mt = mt, mx.d = d, mx.k = sg.k, mx.smooth = sg.smooth, mx.want_g = want_g;
+            mx.xq = h->xraw.p + (size_t)t0 * d, mx.flag = flag + t0;
+            mx.means = sg.d_gmx.p, mx.precs = sg.d_gmx.p + (size_t)sg.k * d, mx.par = mx.precs + (size_t)sg.k * d * d;
+            mx.emean = h->emean.p + (size_t)sg.eslot * M + t0, mx.evar = h->evar.p + (size_t)sg.eslot * M + t0;
+            mx.estride = M;
+            mx.mean = h->mean.p + (size_t)js * M + t0, mx.var = h->var.p + (size_t)js * M + t0;
+            if (want_g) {
+                mx.egmean = h->egmean.p + ((size_t)sg.eslot * M + t0) * d, mx.egvar = h->egvar.p + ((size_t)sg.eslot * M + t0) * d;
+                mx.gmean = h->gmean.p + ((size_t)js * M + t0) * d, mx.gvar = h->gvar.p + ((size_t)js * M + t0) * d;
+                if (sg.smooth) mx.dp = h->dprob.p;
+            }
+            if (diag_mix && dsg == &sg) {
+                mx.probas = h->dg_probas.p + (size_t)t0 * sg.k;
+                if (diag->dprobas) mx.dp = h->dg_dprobas.p + (size_t)t0 * sg.k * d;
+            }
+            EGX_RC(launch_infill_mix(st, mx));
         }
     }
     if (value)
@@ -216,12 +334,38 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
                 EGX_HIP_CHECK(hipMemcpyAsync(parts->grad_var + (size_t)j * m * d, h->gvar.p + (size_t)j * M * d,
                                              sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
         }
+    if (diag) {  // expert c of the surrogate: its slot of the expert tables, or (a lone expert) the surrogate's own slot
+        auto back = [&](double *dst, const double *tab_e, const double *tab_s, size_t per) {
+            if (!dst) return hipSuccess;
+            for (int c = 0; c < dsg->k; c++) {
+                const double *src = diag_mix ? tab_e + (size_t)(dsg->eslot + c) * M * per : tab_s + (size_t)diag->j * M * per;
+                const hipError_t e = hipMemcpyAsync(dst + (size_t)c * m * per, src, sizeof(double) * (size_t)m * per,
+                                                    hipMemcpyDeviceToHost, st);
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        };
+        EGX_HIP_CHECK(back(diag->mean, h->emean.p, h->mean.p, 1));
+        EGX_HIP_CHECK(back(diag->var, h->evar.p, h->var.p, 1));
+        EGX_HIP_CHECK(back(diag->gmean, h->egmean.p, h->gmean.p, (size_t)d));
+        EGX_HIP_CHECK(back(diag->gvar, h->egvar.p, h->gvar.p, (size_t)d));
+        if (diag_mix && diag->probas)
+            EGX_HIP_CHECK(hipMemcpyAsync(diag->probas, h->dg_probas.p, sizeof(double) * (size_t)m * dsg->k, hipMemcpyDeviceToHost, st));
+        if (diag_mix && diag->dprobas)
+            EGX_HIP_CHECK(hipMemcpyAsync(diag->dprobas, h->dg_dprobas.p, sizeof(double) * (size_t)m * dsg->k * d,
+                                         hipMemcpyDeviceToHost, st));
+    }
     EGX_HIP_CHECK(hipStreamSynchronize(st));
+    if (diag && !diag_mix) {  // one cluster: the responsibilities are ones (gaussian_mixture.rs:115-116)
+        if (diag->probas) std::fill(diag->probas, diag->probas + m, 1.0);
+        if (diag->dprobas) std::fill(diag->dprobas, diag->dprobas + (size_t)m * d, 0.0);
+    }
     return EGX_SUCCESS;
 }
 
-int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts) {
-    const int rc = eval_locked(h, xq, m, value, grad, parts);
+int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
+                 const ExpertDiag *diag = nullptr) {
+    const int rc = eval_locked(h, xq, m, value, grad, parts, diag);
     if (rc) {  // nothing may still run on the handle's buffers
         (void)hipStreamSynchronize(h->models[0]->ws[0].stream);
         (void)hipGetLastError();
@@ -235,6 +379,28 @@ bool params_ok(double fmin, double sigma_weight, double scale_ic, double scale) 
         return false;
     }
     return true;
+}
+
+int config_ok(const egx_infill_config &cfg) {
+    if (cfg.criterion < EGX_INFILL_EI || cfg.criterion > EGX_INFILL_WB2S) {
+        set_error("infill: unknown criterion");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    return params_ok(cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale) ? EGX_SUCCESS : EGX_ERR_INVALID_VALUE;
+}
+
+// the checks over all experts, the caches, the criterion's parameters
+int finish_create(egx_infill *h, const egx_infill_config &cfg) {
+    EGX_RC(check_shapes(h));
+    EGX_RC(check_fitted(h));
+    h->cache.reset(new ModelCache[h->models.size()]);
+    h->prm.kind = cfg.criterion;
+    h->prm.fmin = cfg.fmin;
+    h->prm.sigma_weight = cfg.sigma_weight;
+    h->prm.scale_ic = cfg.scale_ic;
+    h->prm.scale = cfg.scale;
+    h->prm.feasibility = cfg.feasibility != 0;
+    return EGX_SUCCESS;
 }
 
 }  // namespace
@@ -264,11 +430,7 @@ int32_t egx_infill_create(const egx_infill_config *cfg_in, egx_gp *obj_model, eg
         set_error("infill: NULL model or tolerance array");
         return EGX_ERR_INVALID_VALUE;
     }
-    if (cfg.criterion < EGX_INFILL_EI || cfg.criterion > EGX_INFILL_WB2S) {
-        set_error("infill: unknown criterion");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (!params_ok(cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale)) return EGX_ERR_INVALID_VALUE;
+    EGX_RC(config_ok(cfg));
     std::unique_ptr<egx_infill> h(new egx_infill);
     h->models.push_back(obj_model);
     for (int j = 0; j < n_cstr; j++) {
@@ -283,34 +445,113 @@ int32_t egx_infill_create(const egx_infill_config *cfg_in, egx_gp *obj_model, eg
         h->models.push_back(cstr_models[j]);
         h->tol.push_back(cstr_tols[j]);
     }
-    h->d = obj_model->d;
-    h->device = obj_model->device;
-    for (size_t j = 1; j < h->models.size(); j++) {
-        if (h->models[j]->d != h->d) {
-            set_error("infill: model " + std::to_string(j) + " has " + std::to_string(h->models[j]->d) + " inputs, model 0 has " +
-                      std::to_string(h->d));
-            return EGX_ERR_INVALID_VALUE;
-        }
-        if (h->models[j]->device != h->device) {
-            set_error("infill: model " + std::to_string(j) + " lives on device " + std::to_string(h->models[j]->device) +
-                      ", model 0 on device " + std::to_string(h->device));
-            return EGX_ERR_INVALID_VALUE;
-        }
+    for (size_t j = 0; j < h->models.size(); j++) {  // every surrogate a lone expert
+        h->surr.emplace_back();
+        h->surr.back().first = (int)j;
     }
-    for (size_t j = 0; j < h->models.size(); j++)
-        if (!h->models[j]->fitted) {
-            set_error("infill: model " + std::to_string(j) + " is not fitted (call egx_gp_finalize or egx_gp_fit first)");
-            return EGX_ERR_NOT_FITTED;
-        }
-    h->cache.reset(new ModelCache[h->models.size()]);
-    h->prm.kind = cfg.criterion;
-    h->prm.fmin = cfg.fmin;
-    h->prm.sigma_weight = cfg.sigma_weight;
-    h->prm.scale_ic = cfg.scale_ic;
-    h->prm.scale = cfg.scale;
-    h->prm.feasibility = cfg.feasibility != 0;
+    EGX_RC(finish_create(h.get(), cfg));
     *out = h.release();
     return EGX_SUCCESS;
+}
+
+int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_surrogate *surrogates, const double *cstr_tols,
+                              int32_t n_cstr, egx_infill **out) {
+    if (!out) {
+        set_error("out handle pointer is NULL");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    *out = nullptr;
+    egx_infill_config cfg;
+    if (cfg_in) cfg = *cfg_in; else egx_infill_config_default(&cfg);
+    if (!surrogates || n_cstr < 0 || (n_cstr > 0 && !cstr_tols)) {
+        set_error("infill: NULL surrogate or tolerance array");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    EGX_RC(config_ok(cfg));
+    std::unique_ptr<egx_infill> h(new egx_infill);
+    h->mix_api = true;
+    for (int j = 0; j <= n_cstr; j++) {
+        const egx_infill_surrogate &sv = surrogates[j];
+        const std::string name = "infill: surrogate " + std::to_string(j);
+        if (sv.n_experts < 1 || !sv.experts) {
+            set_error(name + " needs at least one expert");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (j > 0 && std::isnan(cstr_tols[j - 1])) {
+            set_error("infill: tolerance " + std::to_string(j - 1) + " is NaN");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        h->surr.emplace_back();
+        Surrogate &sg = h->surr.back();
+        sg.first = (int)h->models.size(), sg.k = sv.n_experts, sg.smooth = sv.smooth != 0;
+        for (int e = 0; e < sv.n_experts; e++) {
+            if (!sv.experts[e]) {
+                set_error(name + " expert " + std::to_string(e) + " is NULL");
+                return EGX_ERR_INVALID_VALUE;
+            }
+            h->models.push_back(sv.experts[e]);
+        }
+        if (j > 0) h->tol.push_back(cstr_tols[j - 1]);
+        if (sg.k < 2) continue;  // one cluster: the responsibilities are ones, the mixture is not read
+        const int64_t kk = sg.k, d = sv.experts[0]->d;
+        if (!sv.weights || !sv.means || !sv.precisions_chol) {
+            set_error(name + ": NULL weights, means or precisions_chol");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (!(sv.heaviside_factor > 0.0) || std::isinf(sv.heaviside_factor)) {
+            set_error(name + ": heaviside_factor must be positive and finite");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        bool finite = true, positive = true;
+        for (int64_t i = 0; i < kk; i++) finite &= std::isfinite(sv.weights[i]), positive &= sv.weights[i] > 0.0;
+        for (int64_t i = 0; i < kk * d; i++) finite &= std::isfinite(sv.means[i]);
+        for (int64_t i = 0; i < kk * d * d; i++) finite &= std::isfinite(sv.precisions_chol[i]);
+        if (!finite) {
+            set_error(name + ": non-finite weight, mean or precision factor");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (!positive) {
+            set_error(name + ": weights must be positive");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (infill_mix_lds_bytes((int)d, (int)kk) > kInfillMixMaxLds) {
+            set_error(name + ": 3 (d | 1) + 2 (k | 1) exceeds 320 doubles of LDS scratch per point (d " + std::to_string(d) + ", k " +
+                      std::to_string(kk) + ")");
+            return EGX_ERR_UNSUPPORTED;
+        }
+        sg.gmx.resize((size_t)(kk * d + kk * d * d + kk));
+        std::copy(sv.means, sv.means + kk * d, sg.gmx.begin());
+        gmx_scaled_factors(sv.weights, sv.precisions_chol, kk, d, sv.heaviside_factor, sg.gmx.data() + kk * d,
+                           sg.gmx.data() + kk * d + kk * d * d);
+        for (int64_t c = 0; c < kk; c++)
+            if (!std::isfinite(sg.gmx[(size_t)(kk * d + kk * d * d + c)])) {
+                set_error(name + ": cluster " + std::to_string(c) + " has no positive diagonal in its precision factor");
+                return EGX_ERR_INVALID_VALUE;
+            }
+        sg.eslot = h->n_eslots;
+        h->n_eslots += sg.k;
+        h->k_max = std::max(h->k_max, sg.k);
+    }
+    EGX_RC(finish_create(h.get(), cfg));
+    *out = h.release();
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_eval_experts(egx_infill *h, int32_t j, const double *xq, int64_t m, double *mean, double *var, double *grad_mean,
+                                double *grad_var, double *probas, double *dprobas) {
+    if (!h) {
+        set_error("NULL handle");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (j < 0 || j >= (int32_t)h->surr.size()) {
+        set_error("infill: surrogate " + std::to_string(j) + " out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    ExpertDiag dg;
+    dg.j = j, dg.mean = mean, dg.var = var, dg.gmean = grad_mean, dg.gvar = grad_var, dg.probas = probas, dg.dprobas = dprobas;
+    return eval_guarded(h, xq, m, nullptr, nullptr, nullptr, &dg);
 }
 
 void egx_infill_destroy(egx_infill *h) {
@@ -367,7 +608,7 @@ int32_t egx_infill_scaling(egx_infill *h, const double *pts, int64_t npts, doubl
     }
     std::lock_guard<std::mutex> lock(h->mu);
     ModelLocks locks(h);
-    const int nm = (int)h->models.size(), k = nm - 1;
+    const int nm = (int)h->surr.size(), k = nm - 1;
     // ONE values-only pass over all points (means and variances of every model stay on the device); the criterion's terms are
     // then formed ON THE DEVICE with the text of k_infill_combine, so that what is stored is bit for bit the largest |value|
     // egx_infill_eval returns at scale = 1 (all values finite).  The host does the NaN / inf -> 1 replacement, the last

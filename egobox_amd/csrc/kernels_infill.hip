@@ -4,6 +4,8 @@
 //   k_infill_trend     mean = f beta + sum of the split partial sums (algorithm.rs:260-262); A = f - ft^T rt, Rq^T u = A, Rq D = u,
 //                      var = sigma2 (1 - sum rt^2 + sum u^2) clamped at 0 (:272-278, 352-367); -D zero padded for the GEMM
 //   k_infill_xgrad_finish   reduction of launch_xgrad's split partial sums, the trend Jacobian terms, un-normalisation (:510-727)
+//   k_infill_mix       a surrogate with several experts: the responsibilities of its Gaussian mixture at the point (gmx_point.h)
+//                      and infill_mix_math.h across the experts, into the surrogate's slot of the tables k_infill_combine reads
 //   k_infill_combine   infill_math.h across the 1 + k models of a point: value and gradient of the minimised objective
 // None of them is matrix-shaped: they are latency-bound tails whose point is to keep the call free of host round trips.
 // Every reduction runs in a fixed order that depends on the model alone, and a workgroup (or thread) owns one point: a point's
@@ -16,6 +18,8 @@
 #include "egx_internal.h"
 #pragma clang fp contract(off)
 #include "infill_math.h"
+#include "infill_mix_math.h"
+#include "gmx_point.h"
 
 namespace egx {
 
@@ -159,6 +163,44 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish(XgFinishArg
     }
 }
 
+// A surrogate that is a mixture of k >= 2 experts, after the experts' sequences have written their tables for the tile: one
+// lane per point, 64-lane workgroups (kTile / 64 of them).  The lane's raw coordinates (a flagged point: zeros, as the experts
+// got), its responsibilities p and the scratch of the derivative (z, v': d each; u: k) live in LDS rows of odd stride; the
+// mixture's means, scaled precision factors and par are read at wave-uniform addresses.  Expert c of point a: emean / evar at
+// c * estride + a, egmean / egvar at (c * estride + a) * d.  dp (kTile x k x d): d p_c / d x, computed when not nullptr (smooth
+// gradients need it); probas (kTile x k): a copy of p for egx_infill_eval_experts, or nullptr.
+__global__ __launch_bounds__(64) void k_infill_mix(const double *__restrict__ xq, const int *__restrict__ flag, int mt, int d, int k,
+                                                  int smooth, int want_g, const double *__restrict__ means,
+                                                  const double *__restrict__ precs, const double *__restrict__ par,
+                                                  const double *__restrict__ emean, const double *__restrict__ evar,
+                                                  const double *__restrict__ egmean, const double *__restrict__ egvar,
+                                                  int64_t estride, double *__restrict__ mean, double *__restrict__ var,
+                                                  double *__restrict__ gmean, double *__restrict__ gvar, double *__restrict__ dp,
+                                                  double *__restrict__ probas) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int q0 = blockIdx.x * 64, lane = threadIdx.x, ds = d | 1, ks = k | 1;
+    const int rows = mt - q0 < 64 ? mt - q0 : 64;
+    if (rows <= 0) return;
+    double *xs = sm, *ps = xs + 64 * ds, *zs = ps + 64 * ks, *vps = zs + 64 * ds, *us = vps + 64 * ds;
+    for (int e = lane; e < rows * d; e += 64) {
+        const int i = e / d, j = e - i * d;
+        xs[i * ds + j] = flag[q0 + i] ? 0.0 : xq[(int64_t)q0 * d + e];
+    }
+    __syncthreads();
+    if (lane >= rows) return;
+    const int64_t a = q0 + lane;
+    const double *x = xs + lane * ds;
+    double *p = ps + lane * ks, *dpa = dp ? dp + a * k * d : nullptr;
+    gmx_probas_point(x, d, k, means, precs, par, p);
+    if (probas)
+        for (int c = 0; c < k; c++) probas[a * k + c] = p[c];
+    if (dpa) gmx_probas_deriv_point(x, zs + lane * ds, vps + lane * ds, us + lane * ks, d, k, means, precs, par, dpa);
+    infill::mix_value(smooth != 0, k, p, 1, emean + a, evar + a, estride, mean + a, var + a);
+    if (want_g)
+        infill::mix_grad(smooth != 0, k, d, p, 1, dpa, d, emean + a, evar + a, estride, egmean + a * d, egvar + a * d, estride * d,
+                         gmean + a * d, gvar + a * d);
+}
+
 // one thread per point of the call; model j of point i at j * mstride + i (mean, var) and (j * mstride + i) * d (gradients)
 __global__ __launch_bounds__(kInfThreads) void k_infill_combine(infill::Params prm, int k, int d, int64_t m, int64_t mstride,
                                                                const double *__restrict__ mean, const double *__restrict__ var,
@@ -245,6 +287,24 @@ int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int n
     g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.dneg = t.dneg, g.out_y = out_y, g.out_v = out_v, g.x_std = x_std;
     g.sigma2 = t.sigma2, g.y_std = t.y_std, g.gmean = gmean, g.gvar = gvar;
     hipLaunchKernelGGL(k_infill_xgrad_finish, dim3(kTile), dim3(kInfThreads), 0, s, g);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+size_t infill_mix_lds_bytes(int d, int k) { return sizeof(double) * 64 * (size_t)(3 * (d | 1) + 2 * (k | 1)); }
+
+int launch_infill_mix(hipStream_t s, const InfillMix &g) {
+    const size_t lds = infill_mix_lds_bytes(g.d, g.k);
+    if (g.k < 2 || g.mt < 1 || g.mt > kTile || lds > kInfillMixMaxLds || (g.smooth && g.want_g && !g.dp)) {
+        set_error("infill: bad arguments of the mixture recombination");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (lds > 64 * 1024)
+        EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_infill_mix), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds));
+    hipLaunchKernelGGL(k_infill_mix, dim3(kTile / 64), dim3(64), lds, s, g.xq, g.flag, g.mt, g.d, g.k, g.smooth ? 1 : 0,
+                       g.want_g ? 1 : 0, g.means, g.precs, g.par, g.emean, g.evar, g.egmean, g.egvar, g.estride, g.mean, g.var,
+                       g.gmean, g.gvar, g.dp, g.probas);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

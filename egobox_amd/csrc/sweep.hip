@@ -18,6 +18,7 @@
 // RCCL is bound at run time (dlopen of librccl.so.1 on the first sweep call): libegx_gp_hip.so itself keeps
 // libamdhip64 as its only link-time dependency, and single-GPU users never load the collective library.
 #include "gp_handle.h"
+#include "gmx_point.h"
 #include "sweep_shard.h"
 
 #include <dlfcn.h>
@@ -262,23 +263,7 @@ __global__ __launch_bounds__(64) void k_gmx_probas(const double *__restrict__ xq
     }
     __syncthreads();
     if (lane >= rows) return;
-    const double *x = sm + lane * ds;
-    double *out = probas + (q0 + lane) * k;
-    double s = 0.0;
-    for (int c = 0; c < k; c++) {
-        const double *mu = means + (size_t)c * d, *P = precs + (size_t)c * d * d;
-        double q = 0.0;
-        for (int j = 0; j < d; j++) {
-            double acc = 0.0;
-            for (int i = 0; i < d; i++) acc = __builtin_fma(x[i] - mu[i], P[(size_t)i * d + j], acc);
-            q = __builtin_fma(acc, acc, q);
-        }
-        const double wlp = par[c] - 0.5 * q;
-        out[c] = wlp;
-        s += (wlp <= -307.0) ? 0.0 : exp(wlp);
-    }
-    const double norm = (fabs(s) < 2.220446049250313e-16) ? 0.0 : log(s);
-    for (int c = 0; c < k; c++) out[c] = exp(out[c] - norm);
+    gmx_probas_point(sm + lane * ds, d, k, means, precs, par, probas + (q0 + lane) * k);
 }
 
 // GaussianMixture::predict_probas_derivatives (crates/moe/src/gaussian_mixture.rs:127-170), one lane per point:
@@ -301,34 +286,8 @@ __global__ __launch_bounds__(64) void k_gmx_probas_deriv(const double *__restric
     }
     __syncthreads();
     if (lane >= rows) return;
-    const double *x = xs + lane * ds;
-    double *z = zs + lane * ds, *vp = vps + lane * ds, *u = us + lane * ks;
-    double *o = out + (q0 + lane) * (int64_t)k * d;
-    for (int l = 0; l < d; l++) vp[l] = 0.0;
-    double v = 0.0;
-    for (int c = 0; c < k; c++) {
-        const double *mu = means + (size_t)c * d, *P = precs + (size_t)c * d * d;
-        double q = 0.0;
-        for (int j = 0; j < d; j++) {
-            double acc = 0.0;
-            for (int i = 0; i < d; i++) acc = __builtin_fma(x[i] - mu[i], P[(size_t)i * d + j], acc);
-            z[j] = acc;
-            q = __builtin_fma(acc, acc, q);
-        }
-        const double uc = exp(par[c] - 0.5 * q);  // w_c pdf_c(x)  (:136-139: no MIN_10_EXP guard on this path)
-        u[c] = uc;
-        v += uc;
-        for (int l = 0; l < d; l++) {
-            double acc = 0.0;
-            for (int j = 0; j < d; j++) acc = __builtin_fma(z[j], P[(size_t)l * d + j], acc);
-            const double up = -acc * uc;
-            o[(int64_t)c * d + l] = up;
-            vp[l] += up;
-        }
-    }
-    const double v2 = v * v;
-    for (int c = 0; c < k; c++)
-        for (int l = 0; l < d; l++) o[(int64_t)c * d + l] = (o[(int64_t)c * d + l] * v - u[c] * vp[l]) / v2;
+    gmx_probas_deriv_point(xs + lane * ds, zs + lane * ds, vps + lane * ds, us + lane * ks, d, k, means, precs, par,
+                           out + (q0 + lane) * (int64_t)k * d);
 }
 }  // namespace egx
 
@@ -929,15 +888,8 @@ int32_t egx_gmx_predict_probas(int32_t device, const double *weights, const doub
     }
     EGX_HIP_CHECK(hipSetDevice(device));
     // scaled factors and the per-cluster constant (:105-110, 253-283): precs = P * hf^-0.5, log det = sum log diag(precs)
-    const double factor = std::pow(heaviside_factor, -0.5);
     std::vector<double> precs((size_t)k * d * d), par(k);
-    const double cst = (double)d * std::log(2.0 * M_PI);
-    for (int64_t c = 0; c < k; c++) {
-        double ld = 0.0;
-        for (int64_t i = 0; i < d * d; i++) precs[(size_t)c * d * d + i] = precisions_chol[(size_t)c * d * d + i] * factor;
-        for (int64_t i = 0; i < d; i++) ld += std::log(precs[(size_t)c * d * d + i * d + i]);
-        par[c] = (-0.5 * cst + ld) + std::log(weights[c]);
-    }
+    egx::gmx_scaled_factors(weights, precisions_chol, k, d, heaviside_factor, precs.data(), par.data());
     egx::DevBuf d_x, d_mu, d_p, d_par, d_out;
     EGX_RC(d_x.alloc((size_t)m * d));
     EGX_RC(d_mu.alloc((size_t)k * d));
@@ -986,15 +938,8 @@ int32_t egx_gmx_predict_probas_derivatives(int32_t device, const double *weights
         return EGX_ERR_INVALID_VALUE;
     }
     EGX_HIP_CHECK(hipSetDevice(device));
-    const double factor = std::pow(heaviside_factor, -0.5);
     std::vector<double> precs((size_t)k * d * d), par(k);
-    const double cst = (double)d * std::log(2.0 * M_PI);
-    for (int64_t c = 0; c < k; c++) {
-        double ld = 0.0;
-        for (int64_t i = 0; i < d * d; i++) precs[(size_t)c * d * d + i] = precisions_chol[(size_t)c * d * d + i] * factor;
-        for (int64_t i = 0; i < d; i++) ld += std::log(precs[(size_t)c * d * d + i * d + i]);
-        par[c] = (-0.5 * cst + ld) + std::log(weights[c]);
-    }
+    egx::gmx_scaled_factors(weights, precisions_chol, k, d, heaviside_factor, precs.data(), par.data());
     egx::DevBuf d_x, d_mu, d_p, d_par, d_out;
     EGX_RC(d_x.alloc((size_t)m * d));
     EGX_RC(d_mu.alloc((size_t)k * d));

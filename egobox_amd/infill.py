@@ -28,8 +28,32 @@ def _gp_handle(model):
     return model
 
 
+def _surrogate(model, j):
+    """(expert handles, GaussianMixture or None, smooth) of surrogate j: a `GpMixture` of any number of clusters, or a single
+    model (one expert, no mixture)."""
+    from .moe import GaussianMixture, GpMixture
+    if not isinstance(model, GpMixture):
+        return [_gp_handle(model)], None, True
+    name = f"infill: surrogate {j}"
+    if model.world != 1:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{name}: a GpMixture spread over {model.world} ranks is not supported")
+    if not isinstance(model.gmx, GaussianMixture):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{name}: gmx must be a GaussianMixture, got {type(model.gmx).__name__}")
+    experts = []
+    for e, expert in enumerate(model.experts):
+        try:
+            experts.append(_gp_handle(expert))
+        except L.InvalidValueError:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{name} expert {e}: expected a library-backed GaussianProcess or "
+                                                           f"GpHandle, got {type(expert).__name__}") from None
+    return experts, model.gmx, model.recombination == "smooth"
+
+
 class InfillObjective:
     """`egx_infill`: one objective model, k >= 0 constraint models (kept alive by this object), a criterion and its parameters.
+    A model is a GpHandle, a GaussianProcess, a single-expert Gpx or a single-rank `egobox_amd.moe.GpMixture` of library-backed
+    experts (any number of clusters, smooth or hard): with a mixture among them the handle is built by egx_infill_create_mix
+    and the recombination runs on the GPU; with single models only, by egx_infill_create as before.
 
     value / gradient are those of the MINIMISED objective: -crit / scale, times the probability of feasibility of the
     constraint models (EI, WB2, WB2S) or minus its logarithm (LOG_EI)."""
@@ -38,20 +62,40 @@ class InfillObjective:
                  scale_ic=1.0, scale=1.0):
         lib = L.load()
         self._lib = lib
-        self._models = [_gp_handle(obj_model)] + [_gp_handle(m) for m in cstr_models]
+        from .moe import GpMixture
+        mixed = any(isinstance(m, GpMixture) for m in (obj_model, *cstr_models))
+        if mixed:
+            self._surrogates = [_surrogate(m, j) for j, m in enumerate((obj_model, *cstr_models))]
+            self._models = [e for experts, _, _ in self._surrogates for e in experts]
+        else:
+            self._models = [_gp_handle(obj_model)] + [_gp_handle(m) for m in cstr_models]
+            self._surrogates = [([m], None, True) for m in self._models]
         self._owners = (obj_model, tuple(cstr_models))
         tols = L.as_f64(np.atleast_1d(np.asarray(cstr_tols, dtype=np.float64)) if len(cstr_models) else np.zeros(0), 1)
-        k = len(self._models) - 1
+        k = len(self._surrogates) - 1
         if tols.shape[0] != k:
             raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: {k} constraint models but {tols.shape[0]} tolerances")
         cfg = L.InfillConfig()
         lib.egx_infill_config_default(C.byref(cfg))
         cfg.criterion, cfg.feasibility = int(criterion), int(bool(feasibility))
         cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale = float(fmin), float(sigma_weight), float(scale_ic), float(scale)
-        arr = (C.c_void_p * max(k, 1))(*[m._h.value for m in self._models[1:]])
         self._h = C.c_void_p()
-        L.check(lib.egx_infill_create(C.byref(cfg), self._models[0]._h, arr if k else None, L.dptr(tols) if k else None, k,
-                                      C.byref(self._h)))
+        if mixed:
+            keep, structs = [], (L.InfillSurrogate * (k + 1))()
+            for st, (experts, gmx, smooth) in zip(structs, self._surrogates):
+                arr = (C.c_void_p * len(experts))(*[e._h.value for e in experts])
+                st.experts, st.n_experts, st.smooth, st.heaviside_factor = arr, len(experts), int(smooth), 1.0
+                keep.append(arr)
+                if gmx is not None:
+                    w, mu, pc = L.as_f64(gmx.weights), L.as_f64(gmx.means), L.as_f64(gmx.precisions_chol)
+                    st.weights, st.means, st.precisions_chol = L.dptr(w), L.dptr(mu), L.dptr(pc)
+                    st.heaviside_factor = float(gmx.heaviside_factor)
+                    keep += [w, mu, pc]
+            L.check(lib.egx_infill_create_mix(C.byref(cfg), structs, L.dptr(tols) if k else None, k, C.byref(self._h)))
+        else:
+            arr = (C.c_void_p * max(k, 1))(*[m._h.value for m in self._models[1:]])
+            L.check(lib.egx_infill_create(C.byref(cfg), self._models[0]._h, arr if k else None, L.dptr(tols) if k else None, k,
+                                          C.byref(self._h)))
         self.d, self.n_cstr, self.criterion = self._models[0].d, k, int(criterion)
 
     # ---- parameters ----------------------------------------------------------------------------------------------------
@@ -107,6 +151,20 @@ class InfillObjective:
         v, g, p = self._eval(x, True, True)
         p["value"], p["grad"] = v, g
         return p
+
+    def expert_parts(self, j, x):
+        """What surrogate j (0 = objective) was recombined FROM (egx_infill_eval_experts): dict of the expert-major mean (k, m),
+        var (k, m), grad_mean (k, m, d), grad_var (k, m, d) of its k experts, the responsibilities probas (m, k) and their
+        x-derivatives dprobas (m, k, d)."""
+        if not 0 <= int(j) < len(self._surrogates):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: surrogate {j} out of range")
+        x = self._points(x)
+        m, d, k = x.shape[0], self.d, len(self._surrogates[int(j)][0])
+        out = dict(mean=np.empty((k, m)), var=np.empty((k, m)), grad_mean=np.empty((k, m, d)), grad_var=np.empty((k, m, d)),
+                   probas=np.empty((m, k)), dprobas=np.empty((m, k, d)))
+        L.check(self._lib.egx_infill_eval_experts(self._h, int(j), L.dptr(x), m, *[L.dptr(out[key]) for key in (
+            "mean", "var", "grad_mean", "grad_var", "probas", "dprobas")]))
+        return out
 
     def scaling(self, points):
         """compute_scaling (solver_computations.rs:132-193) on `points` (npts, d): returns (scale_ic, scale, scale_cstr) and

@@ -583,7 +583,8 @@ int32_t egx_sgp_get_state(egx_sgp *sgp, double *theta, double *sigma2, double *n
  *   obj(x) * pofs(x)  (EI, WB2, WB2S)  or  obj(x) - logpofs(x)  (LogEI)   with constraint models (cstr_infill = true):
  *                                                utils/cstr_pof.rs, solver/solver_computations.rs:356-475
  * and its x-gradient, for m points per call, from ONE objective model and n_cstr >= 0 constraint models (dense GPs, all
- * fitted, same d, same device; n may differ).  The models are BORROWED: they must outlive the handle, and a call always reads
+ * fitted, same d, same device; n may differ) -- or, through egx_infill_create_mix below, from surrogates that are mixtures
+ * of such GPs.  The models are BORROWED: they must outlive the handle, and a call always reads
  * their CURRENT fitted state.  feasibility == 0 replaces obj by -1 (0 for LogEI) and its gradient by 0 (:410-416, 441-466).
  * The reference evaluates this one point at a time with 2 (1 + n_cstr) predict calls per evaluation; here a call is one
  * upload, one launch sequence per 128-point tile and model, one synchronisation, and nothing is computed on the host.
@@ -651,6 +652,43 @@ typedef struct {
 } egx_infill_stats;
 int32_t egx_infill_optimize(egx_infill *h, const double *lo /*d*/, const double *hi /*d*/, const double *x_start /*n_start*d*/,
                             int64_t n_start, int64_t max_eval, double *f_best, double *x_best /*d*/, egx_infill_stats *stats);
+
+/* ---- ... on mixtures of experts -------------------------------------------------------------------------------------
+ * What EGO holds for its objective and every constraint is a clustered surrogate (GpMixture, crates/moe/src/algorithm.rs):
+ * one GP expert per cluster and the Gaussian mixture of the x-space that weighs them.  A handle of egx_infill_create_mix takes
+ * such SURROGATES: the experts (borrowed egx_gp*, all fitted, same d and device; n may differ) and a copy of the mixture, given
+ * as to egx_gmx_predict_probas -- weights (k), means (k x d), precisions_chol (k x d x d) and the heaviside factor.  Per
+ * 128-point tile every expert runs the launch sequence of a single model; one more launch per (tile, surrogate with k >= 2)
+ * computes the responsibilities p_e(x), their x-derivatives (the arithmetic of egx_gmx_predict_probas / _derivatives, bit for
+ * bit) and recombines the experts on the device:
+ *   smooth (:411-423, 670-685, 691-783)  mean = sum p_e mu_e, var = sum p_e^2 v_e,
+ *                                        grad mean = sum p_e grad mu_e + p'_e mu_e, grad var = sum p_e^2 grad v_e + 2 p_e p'_e v_e
+ *   hard   (:879-935, 942-1010)          the four quantities of the expert of the FIRST maximum of p_e
+ * (the experts in index order).  In hard mode every expert still evaluates every point and the kernel selects: a call costs k
+ * expert sequences per surrogate in both modes, and a point's bits stay independent of its companions.  A surrogate with ONE
+ * expert is that expert (the responsibilities are ones, gaussian_mixture.rs:115-116): its mixture is not read and may be NULL.
+ * egx_infill_eval, _scaling, _optimize, _set_params and _get_params work on such a handle unchanged; egx_infill_parts stays
+ * per SURROGATE, (1 + n_cstr) entries.  A NaN / infinite point: value +inf, gradient 0, for that point only.
+ * Checked before the device is touched, EGX_ERR_INVALID_VALUE naming the surrogate (and the expert): NULL pointers,
+ * n_experts < 1, and for k >= 2 a heaviside factor that is not positive and finite, non-finite weights / means / factors,
+ * weights that are not positive, differing d or device.  EGX_ERR_NOT_FITTED names surrogate and expert, here and in every
+ * later call.  EGX_ERR_UNSUPPORTED when 3 (d | 1) + 2 (k | 1) > 320 (the recombination keeps that many doubles of LDS per
+ * point; every mixture egx_gmm_fit can train, d <= 35 and k <= 16, fits).
+ * Out of scope: mixtures whose experts live on several ranks (egx_sweep) and sparse-GP experts (egx_sgp). */
+typedef struct {
+    egx_gp *const *experts; int32_t n_experts;       /* one per cluster, fitted, same d and device */
+    const double *weights /*k*/, *means /*k*d*/, *precisions_chol /*k*d*d*/;  /* as egx_gmx_predict_probas; may be NULL when n_experts == 1 */
+    double heaviside_factor;                          /* > 0 */
+    int32_t smooth;                                   /* 1 smooth, 0 hard */
+} egx_infill_surrogate;
+int32_t egx_infill_create_mix(const egx_infill_config *cfg, const egx_infill_surrogate *surrogates /*1 + n_cstr, [0] = objective*/,
+                              const double *cstr_tols, int32_t n_cstr, egx_infill **out);
+/* diagnostics: what surrogate j was recombined FROM; any pointer may be NULL.  Expert-major parts of its k experts, the
+ * responsibilities (bit for bit egx_gmx_predict_probas at xq) and their derivatives (... _derivatives); k = 1: ones and zeros.
+ * Works on a handle of egx_infill_create as well (every surrogate one expert). */
+int32_t egx_infill_eval_experts(egx_infill *h, int32_t j, const double *xq, int64_t m,
+                                double *mean /*k*m*/, double *var /*k*m*/, double *grad_mean /*k*m*d*/, double *grad_var /*k*m*d*/,
+                                double *probas /*m*k*/, double *dprobas /*m*k*d*/);
 
 #ifdef __cplusplus
 }

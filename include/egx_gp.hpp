@@ -515,8 +515,63 @@ inline GmmFit gmm_fit(const double *data, int64_t n, int32_t dim, int32_t n_clus
 // x-gradient for m points per call (crates/ego/src/criteria, utils/cstr_pof.rs, solver/solver_computations.rs:356-475), the
 // scaling pass (:132-193) and the lock-step multistart (solver_infill_optim.rs:148-236).  The models are borrowed and must
 // outlive the object.
+//
+// A surrogate of the mixture form (egx_infill_create_mix): the experts of a GpMixture (borrowed) and a copy of its Gaussian
+// mixture, as egx_gmx_predict_probas takes it.  One expert: the mixture is not read and may stay empty.
+struct InfillSurrogate {
+    std::vector<const GaussianProcess *> experts;  // one per cluster
+    std::vector<double> weights, means, precisions_chol;  // k, k x d, k x d x d
+    double heaviside_factor = 1.0;
+    bool smooth = true;  // false: hard recombination
+};
+
 class InfillObjective {
   public:
+    // what surrogate j was recombined from (egx_infill_eval_experts): expert-major parts, responsibilities, their derivatives
+    struct ExpertParts {
+        std::vector<double> mean, var, grad_mean, grad_var, probas, dprobas;  // k m, k m, k m d, k m d, m k, m k d
+    };
+    // surrogates[0] is the objective, the others the constraints (one tolerance each)
+    InfillObjective(const std::vector<InfillSurrogate> &surrogates, const std::vector<double> &cstr_tols,
+                    egx_infill_criterion criterion, double fmin, double sigma_weight = 1.0, bool feasibility = true) {
+        if (surrogates.empty() || surrogates.size() != cstr_tols.size() + 1)
+            throw InvalidValueError(EGX_ERR_INVALID_VALUE, "InfillObjective: an objective surrogate and one tolerance per constraint");
+        egx_infill_config cfg;
+        egx_infill_config_default(&cfg);
+        cfg.criterion = criterion;
+        cfg.fmin = fmin;
+        cfg.sigma_weight = sigma_weight;
+        cfg.feasibility = feasibility ? 1 : 0;
+        std::vector<std::vector<egx_gp *>> hs(surrogates.size());
+        std::vector<egx_infill_surrogate> raw_s(surrogates.size());
+        for (size_t j = 0; j < surrogates.size(); j++) {
+            const InfillSurrogate &sv = surrogates[j];
+            for (const GaussianProcess *e : sv.experts) hs[j].push_back(e ? e->handle() : nullptr);
+            n_experts_.push_back((int64_t)hs[j].size());
+            raw_s[j].experts = hs[j].data();
+            raw_s[j].n_experts = (int32_t)hs[j].size();
+            raw_s[j].weights = sv.weights.empty() ? nullptr : sv.weights.data();
+            raw_s[j].means = sv.means.empty() ? nullptr : sv.means.data();
+            raw_s[j].precisions_chol = sv.precisions_chol.empty() ? nullptr : sv.precisions_chol.data();
+            raw_s[j].heaviside_factor = sv.heaviside_factor;
+            raw_s[j].smooth = sv.smooth ? 1 : 0;
+        }
+        egx_infill *raw = nullptr;
+        check(egx_infill_create_mix(&cfg, raw_s.data(), cstr_tols.data(), (int32_t)cstr_tols.size(), &raw));
+        h_.reset(raw);
+        d_ = surrogates[0].experts[0]->dims().first;
+        k_ = (int64_t)cstr_tols.size();
+    }
+    ExpertParts eval_experts(int32_t j, const double *x, int64_t m) const {
+        if (j < 0 || (size_t)j >= n_experts_.size()) throw InvalidValueError(EGX_ERR_INVALID_VALUE, "InfillObjective: no such surrogate");
+        const size_t k = (size_t)n_experts_[(size_t)j], mm = (size_t)m, d = (size_t)d_;
+        ExpertParts p;
+        p.mean.resize(k * mm), p.var.resize(k * mm), p.grad_mean.resize(k * mm * d), p.grad_var.resize(k * mm * d);
+        p.probas.resize(mm * k), p.dprobas.resize(mm * k * d);
+        check(egx_infill_eval_experts(h_.get(), j, x, m, p.mean.data(), p.var.data(), p.grad_mean.data(), p.grad_var.data(),
+                                      p.probas.data(), p.dprobas.data()));
+        return p;
+    }
     InfillObjective(const GaussianProcess &obj_model, const std::vector<const GaussianProcess *> &cstr_models,
                     const std::vector<double> &cstr_tols, egx_infill_criterion criterion, double fmin, double sigma_weight = 1.0,
                     bool feasibility = true) {
@@ -535,6 +590,7 @@ class InfillObjective {
         h_.reset(raw);
         d_ = obj_model.dims().first;
         k_ = (int64_t)hs.size();
+        n_experts_.assign((size_t)k_ + 1, 1);
     }
     // InfillCriterion::value through eval_infill_obj_with_cstrs: (m) values of the minimised objective
     std::vector<double> value(const double *x, int64_t m) const {
@@ -589,6 +645,7 @@ class InfillObjective {
     };
     std::unique_ptr<egx_infill, Deleter> h_;
     int64_t d_ = 0, k_ = 0;
+    std::vector<int64_t> n_experts_;  // per surrogate
 };
 
 // device resources destroyed models left in the library's pool (a model of the same shape created next reuses them)

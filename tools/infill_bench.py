@@ -6,6 +6,13 @@ One process, legs alternated (composed, fused, composed again: the two composed 
 shape, medians.  Also: one lock-step optimize with 20 starts against 20 one-start calls.
 
     python tools/infill_bench.py [--out profiles/infill_eval_ab.txt] [--reps 15] [--only-m21]
+
+--mix runs the MIXTURE leg instead: the objective is a smooth mixture of k = 3 experts (explicit Gaussian mixture, the clusters
+overlapping in the unit box), no constraints.  Composed = GpMixture.predict_valvar + predict_valvar_gradients (the library's
+mixture entry points) with the same host arithmetic; fused = the handle of egx_infill_create_mix.  Same protocol, written to
+profiles/infill_mix_eval_ab.txt.
+
+    python tools/infill_bench.py --mix [--out profiles/infill_mix_eval_ab.txt] [--reps 15]
 """
 import argparse
 import os
@@ -54,6 +61,31 @@ def composed(hs, tols, fmin, xq, want_grad):
     return val, grad
 
 
+def build_mixture(n, d, k):
+    """k experts on their own training sets and an explicit mixture whose clusters overlap in the unit box"""
+    hs, ys = build(n, d, k - 1)  # (build shifts the outputs of all but the first; irrelevant for a timing)
+    means = np.full((k, d), 0.5)
+    means[:, 0] = (np.arange(k) + 0.5) / k
+    gmx = egx.GaussianMixture(np.full(k, 1.0 / k), means, [np.eye(d) * 0.05] * k, 0.9)
+    return egx.GpMixture([egx.GaussianProcess(h, None) for h in hs], gmx, "smooth"), hs, ys
+
+
+def composed_mixture(mix, fmin, xq, want_grad):
+    """2 mixture calls (each: responsibilities, every expert, the fold), then the arithmetic on the host"""
+    m, d = xq.shape
+    mu, var = (a[None, :] for a in mix.predict_valvar(xq))
+    dmu = dvar = np.zeros((1, m, d))
+    if want_grad:
+        dmu, dvar = (a[None, :, :] for a in mix.predict_valvar_gradients(xq))
+    val = np.empty(m)
+    grad = np.empty((m, d)) if want_grad else None
+    for i in range(m):
+        val[i] = IO.objective(IO.LOG_EI, mu[:, i], var[:, i], [], fmin, 1.0, 1.0, 1.0, True, dev=True)
+        if want_grad:
+            grad[i] = IO.dev_objective_grad(IO.LOG_EI, (mu[:, i], var[:, i], dmu[:, i], dvar[:, i]), [], fmin, 1.0, 1.0, 1.0, True)
+    return val, grad
+
+
 def median_ms(fn, reps, warm=3):
     for _ in range(warm):
         fn()
@@ -67,10 +99,13 @@ def median_ms(fn, reps, warm=3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infill_eval_ab.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--mix", action="store_true", help="the mixture leg (k = 3 experts, smooth) instead of the single-model legs")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
     def emit(s):
@@ -86,6 +121,41 @@ def main():
         for _ in range(10):
             obj.value(xq)
             obj.value_and_grad(xq)
+        return
+    if args.mix:
+        kx = 3
+        emit("# infill evaluation on a mixture surrogate, composed (GpMixture.predict_valvar + predict_valvar_gradients + host")
+        emit("# arithmetic) vs fused (egx_infill_create_mix / egx_infill_eval); LogEI, objective = smooth mixture of %d experts, no" % kx)
+        emit("# constraints; median ms over %d calls after 3 warm-ups; legs alternated" % args.reps)
+        emit("# n d experts m grad composed_a_ms fused_ms composed_b_ms composed_spread fused/composed verdict")
+        for n, d in ((2048, 8), (4096, 8)):
+            mix, hs, ys = build_mixture(n, d, kx)
+            fmin = float(np.quantile(ys[0], 0.05))
+            obj = egx.InfillObjective(mix, criterion=egx.LOG_EI, fmin=fmin)
+            rng = np.random.default_rng(1)
+            for m in (1, 21, 800):
+                xq = rng.random((m, d))
+                reps = args.reps if m < 800 else max(3, args.reps // 5)
+                for want_grad in (False, True):
+                    fused = (lambda: obj.value_and_grad(xq)) if want_grad else (lambda: obj.value(xq))
+                    comp = lambda: composed_mixture(mix, fmin, xq, want_grad)  # noqa: E731
+                    vc, gc = comp()
+                    vf = fused()
+                    vf, gf = vf if want_grad else (vf, None)
+                    ok = np.allclose(vf, vc, rtol=1e-6, atol=1e-6) and (
+                        not want_grad or np.allclose(gf, gc, rtol=1e-4, atol=1e-5 * (1 + np.abs(gc).max())))
+                    ca = median_ms(comp, reps)
+                    fu = median_ms(fused, reps)
+                    cb = median_ms(comp, reps)
+                    c = min(ca, cb)
+                    verdict = "fused faster" if fu < c else ("within the spread" if fu <= max(ca, cb) else "FUSED SLOWER")
+                    emit(f"{n} {d} {kx} {m} {int(want_grad)} {ca:.3f} {fu:.3f} {cb:.3f} {abs(ca - cb):.3f} {fu / c:.3f} {verdict}"
+                         + ("" if ok else "  RESULTS DIFFER"))
+            obj.close()
+            for h in hs:
+                h.close()
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
         return
     emit("# infill evaluation, composed (predict_valvar + predict_valvar_gradients per model + host arithmetic) vs fused")
     emit("# (egx_infill_eval); LogEI, k = 2 constraint models; median ms over %d calls after 3 warm-ups; legs alternated" % args.reps)
