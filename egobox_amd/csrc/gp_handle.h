@@ -205,7 +205,11 @@ struct egx_gp : egx::HandleRes {
     egx::DevMem<double> sp_R, sp_P, sp_y, sp_z, sp_wt, sp_out, sp_xq;
     int sp_nsplit = 0;
     int small_var_calls = 0;  // single-point predict_var calls since the fit: the third one builds W = C^-T
-    uint64_t fit_epoch = 0, winv_epoch = ~(uint64_t)0;
+    // the small fitted state the trend kernels read (ensure_trend_state): d_tbeta = beta (p), Rq = ft_qr_r and Rq^T (p x p
+    // row-major), host_math.h regression_index (2 p)
+    egx::DevMem<double> d_tbeta, d_rq, d_rqT;
+    egx::DevMem<int> d_fidx;
+    uint64_t fit_epoch = 0, winv_epoch = ~(uint64_t)0, trend_epoch = ~(uint64_t)0;
     uint64_t winv_fail_epoch = ~(uint64_t)0;  // fit for which the C^-T cache could not be built (batched path serves it)
     egx_timings timings{};
 };
@@ -275,6 +279,21 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
 int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv);
 // d_W <- C^-T and d_neg_invkf <- -C^-T [ft | yt] of the fitted factor, cached per fitted state (fit_epoch)
 int ensure_winv(egx_gp *gp);
+// d_tbeta, d_rq, d_rqT, d_fidx of the fitted state, cached likewise; uploads on `st` and waits for it when the state has moved
+int ensure_trend_state(egx_gp *gp, hipStream_t st);
+// "not fitted" / "bad query array": what every posterior entry point checks first
+int check_query(const egx_gp *gp, const double *xq, int64_t m);
+// The dense posterior's device sequence on the factor resident in workspace 0, for a k-major query block xqT (d x m_pad):
+//   posterior_solve    RT (m_pad x n_pad) = rt^T, rt = C^-1 r(x); s0 = sum rt^2; sl (m_pad x p) = ft^T rt
+//   posterior_weights  Wt (n_pad x m_pad) = -(R^-1 r)^T from RT and the cached C^-T (ensure_winv) ...
+//   posterior_weights_trend   ... then Wt -= (-R^-1 F) (-D)^T with dneg = -D (m_pad x rhs_pad, zero padded)
+int posterior_solve(egx_gp *gp, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl);
+int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt);
+int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int m_pad, double *Wt);
+// how many parts the training range is split into so that few queries still fill the chip (the caller adds the partial sums
+// in order): launch_predict_mean's over rows = n_pad, launch_xgrad's over rows = n
+int mean_splits(int rows, int m_pad);
+int xgrad_splits(int rows, int m_pad);
 // gp_sample.hip: factor sigma2 (K(x, x) + G) (+ tau I) of m queries and draw nt trajectories around `mean` (m_pad host doubles).
 // xqT is k-major (d x m_pad, m_pad = m rounded up to 128), G the (m_pad x m_pad) Gram term or nullptr, max_diag the largest
 // diagonal entry of the covariance (EGX_SAMPLE_PSD's first jitter), `what` names the covariance in error messages

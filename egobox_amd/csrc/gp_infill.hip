@@ -4,9 +4,10 @@
 // COBYLA multistart.
 //
 // A call walks the points in tiles of EXACTLY kTile = 128 and, per tile, the models one after the other through the launch
-// sequence of predict_impl / xgrad_impl's batched form; what those do on the host between their launches runs in the
-// kernels of kernels_infill.hip, and k_infill_combine applies infill_math.h across the models.  One upload, one launch sequence
-// per (tile, model), one combine, the copies back, ONE synchronisation: the count depends on k and on the number of tiles only.
+// sequence of predict_impl / xgrad_impl (posterior_solve, posterior_weights, the split rules: gp_predict.hip); what those
+// do on the host between their launches runs in the kernels of kernels_infill.hip, and k_infill_combine applies
+// infill_math.h across the models.  One upload, one launch sequence per (tile, model), one combine, the copies back, ONE
+// synchronisation: the count depends on k and on the number of tiles only.
 // Every launch of a tile has the padded batch size 128, and the splits of the training range are functions of the model
 // alone: the bits of a point do not depend on where it sits nor on its companions (tests/test_gpu_infill.py).
 //
@@ -25,39 +26,6 @@
 using namespace egx;
 
 namespace {
-
-// per-model device copies of the small fitted state the trend kernel reads; refreshed when the model's fit_epoch moves
-struct ModelCache {
-    uint64_t epoch = ~(uint64_t)0;
-    bool valid = false;
-    DevBuf beta, R, Rt, fidx;
-};
-
-// regression column l of f(x) = fa[l] * fb[l]: (-1, -1) the constant, (j, -1) x_j, (k, j) x_j x_k (host_math.h regression_row)
-std::vector<int> regression_index(int mean, int d) {
-    std::vector<int> idx = {-1, -1};
-    if (mean >= 1)
-        for (int j = 0; j < d; j++) idx.insert(idx.end(), {j, -1});
-    if (mean >= 2)
-        for (int k = 0; k < d; k++)
-            for (int j = k; j < d; j++) idx.insert(idx.end(), {k, j});
-    return idx;
-}
-
-// the splits of the training range for a tile of 128 queries: predict_impl's / xgrad_impl's rules at m_pad = kTile
-int mean_splits(const egx_gp *gp) {
-    int msplit = (1024 + kTile / 64 - 1) / (kTile / 64);
-    if (msplit > gp->n_pad / 64) msplit = gp->n_pad / 64;
-    const int per = (gp->n_pad / 64 + msplit - 1) / msplit;
-    return (gp->n_pad / 64 + per - 1) / per;
-}
-int xgrad_splits(const egx_gp *gp) {
-    int nsplit = 512;
-    const int slabs = (gp->n + 63) / 64;
-    if (nsplit > slabs) nsplit = slabs;
-    const int per = (slabs + nsplit - 1) / nsplit;
-    return (slabs + per - 1) / per;
-}
 
 // models[first .. first + k) are the surrogate's experts; with k >= 2 they own the slots [eslot, eslot + k) of the expert tables
 struct Surrogate {
@@ -79,7 +47,6 @@ struct egx_infill {
     std::vector<double> tol;       // one per constraint
     infill::Params prm{};
     int d = 0, device = 0;
-    std::unique_ptr<ModelCache[]> cache;  // one per model
     DevBuf d_tol;
     bool tol_on_device = false;
     // buffers of a call (grow-only): the whole call's points and results, then the scratch of ONE (tile, model) step
@@ -145,62 +112,33 @@ struct ExpertDiag {
     double *mean = nullptr, *var = nullptr, *gmean = nullptr, *gvar = nullptr, *probas = nullptr, *dprobas = nullptr;
 };
 
-int refresh_cache(egx_infill *h, int j, hipStream_t st) {
-    egx_gp *gp = h->models[j];
-    ModelCache &c = h->cache[j];
-    if (c.valid && c.epoch == gp->fit_epoch) return EGX_SUCCESS;
-    const int p = gp->p;
-    const std::vector<int> idx = regression_index(gp->mean, gp->d);
-    std::vector<double> rt((size_t)p * p);
-    for (int i = 0; i < p; i++)
-        for (int l = 0; l < p; l++) rt[(size_t)i * p + l] = gp->ft_qr_r[(size_t)l * p + i];
-    EGX_RC(c.beta.alloc(p));
-    EGX_RC(c.R.alloc((size_t)p * p));
-    EGX_RC(c.Rt.alloc((size_t)p * p));
-    EGX_RC(c.fidx.alloc((idx.size() + 1) / 2));
-    EGX_HIP_CHECK(hipMemcpyAsync(c.beta.p, gp->beta.data(), sizeof(double) * p, hipMemcpyHostToDevice, st));
-    EGX_HIP_CHECK(hipMemcpyAsync(c.R.p, gp->ft_qr_r.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
-    EGX_HIP_CHECK(hipMemcpyAsync(c.Rt.p, rt.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
-    EGX_HIP_CHECK(hipMemcpyAsync(c.fidx.p, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, st));
-    EGX_HIP_CHECK(hipStreamSynchronize(st));  // rt and idx are locals; once per fitted state
-    c.epoch = gp->fit_epoch;
-    c.valid = true;
-    return EGX_SUCCESS;
-}
-
 // One expert's launch sequence for one tile: mean / var (and gmean / gvar when want_g) point at the tile's kTile entries of the
 // table the expert writes; flag: the tile's flags, written by the first expert of the call only (else nullptr).
 int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *var, double *gmean,
                 double *gvar, int *flag) {
     const int d = h->d;
     egx_gp *gp = h->models[j];
-    Workspace &w = gp->ws[0];
-    ModelCache &c = h->cache[j];
-    const int n = gp->n, n_pad = gp->n_pad, p = gp->p, rp = gp->rhs_pad;
-    const int msplit = mean_splits(gp), nsplit = xgrad_splits(gp);
+    const int n = gp->n, n_pad = gp->n_pad;
+    const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
     EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag));
     // r . gamma in split partial sums (algorithm.rs:260-262), before the solve overwrites r
     EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
                                gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
                                gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
     // rt = C^-1 r (held transposed), sum rt^2 and ft^T rt (:337-352)
-    EGX_RC(launch_cross_corr(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
-                             gp->fit_hcols, h->RT.p, n_pad));
-    EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, h->RT.p, n_pad, kTile));
-    EGX_RC(launch_row_reduce(st, h->RT.p, n_pad, kTile, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p, h->s0.p, h->sl.p));
+    EGX_RC(posterior_solve(gp, st, h->xqT.p, kTile, h->RT.p, h->s0.p, h->sl.p));
     InfillTrend tr;
-    tr.p = p, tr.rp = rp, tr.msplit = msplit;
-    tr.xqT = h->xqT.p, tr.fidx = reinterpret_cast<const int *>(c.fidx.p), tr.beta = c.beta.p, tr.R = c.R.p, tr.Rt = c.Rt.p;
+    tr.p = gp->p, tr.rp = gp->rhs_pad, tr.msplit = msplit;
+    tr.xqT = h->xqT.p, tr.fidx = gp->d_fidx, tr.beta = gp->d_tbeta, tr.R = gp->d_rq, tr.Rt = gp->d_rqT;
     tr.racc = h->racc.p, tr.s0 = h->s0.p, tr.sl = h->sl.p;
     tr.sigma2 = gp->sigma2, tr.y_mean = gp->y_mean, tr.y_std = gp->y_std;
     tr.mean = mean, tr.var = var;
     tr.dneg = want_g ? h->dneg.p : nullptr;
     EGX_RC(launch_infill_trend(st, tr));
     if (!want_g) return EGX_SUCCESS;
-    // -(R^-1 r + R^-1 F D)^T as an (n_pad x 128) weight matrix: xgrad_impl's two GEMMs, then the two contractions
-    EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * (size_t)n_pad * kTile, st));
-    EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_W, n_pad, h->RT.p, n_pad, n_pad, kTile, n_pad, 0, 1));
-    EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, gp->d_neg_invkf, rp, h->dneg.p, rp, n_pad, kTile, rp, 0, 0));
+    // -(R^-1 r + R^-1 F D)^T as an (n_pad x 128) weight matrix, then the two contractions
+    EGX_RC(posterior_weights(gp, st, h->RT.p, kTile, h->Wt.p));
+    EGX_RC(posterior_weights_trend(gp, st, h->dneg.p, kTile, h->Wt.p));
     EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
                         gp->d_gamma, 0, 1, nsplit, h->out_y.p));
     EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
@@ -224,7 +162,7 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     hipStream_t st = h->models[0]->ws[0].stream;
     if (want_g)
         for (int e = 0; e < ne; e++) EGX_RC(ensure_winv(h->models[e]));  // once per fitted state (synchronises the model's stream)
-    for (int e = 0; e < ne; e++) EGX_RC(refresh_cache(h, e, st));
+    for (int e = 0; e < ne; e++) EGX_RC(ensure_trend_state(h->models[e], st));
     for (Surrogate &sg : h->surr)
         if (sg.k >= 2 && !sg.on_device) {
             EGX_RC(sg.d_gmx.alloc(sg.gmx.size()));
@@ -242,8 +180,8 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
         n_pad_max = std::max(n_pad_max, gp->n_pad);
         p_max = std::max(p_max, gp->p);
         rp_max = std::max(rp_max, gp->rhs_pad);
-        ms_max = std::max(ms_max, mean_splits(gp));
-        ns_max = std::max(ns_max, xgrad_splits(gp));
+        ms_max = std::max(ms_max, mean_splits(gp->n_pad, kTile));
+        ns_max = std::max(ns_max, xgrad_splits(gp->n, kTile));
     }
     EGX_RC(h->xraw.alloc((size_t)m * d));
     EGX_RC(h->flag.alloc((size_t)(M + 1) / 2));
@@ -389,11 +327,10 @@ int config_ok(const egx_infill_config &cfg) {
     return params_ok(cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale) ? EGX_SUCCESS : EGX_ERR_INVALID_VALUE;
 }
 
-// the checks over all experts, the caches, the criterion's parameters
+// the checks over all experts, the criterion's parameters
 int finish_create(egx_infill *h, const egx_infill_config &cfg) {
     EGX_RC(check_shapes(h));
     EGX_RC(check_fitted(h));
-    h->cache.reset(new ModelCache[h->models.size()]);
     h->prm.kind = cfg.criterion;
     h->prm.fmin = cfg.fmin;
     h->prm.sigma_weight = cfg.sigma_weight;

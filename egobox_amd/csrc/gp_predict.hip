@@ -31,10 +31,7 @@ static int upload_queries(egx_gp *gp, const double *xq, int64_t m0, int m, int m
     return EGX_SUCCESS;
 }
 
-static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vout);
-static int small_path_buffers(egx_gp *gp);
-
-int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout) {
+int check_query(const egx_gp *gp, const double *xq, int64_t m) {
     if (!gp->fitted) {
         set_error("model is not fitted (call egx_gp_finalize or egx_gp_fit first)");
         return EGX_ERR_NOT_FITTED;
@@ -43,6 +40,51 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
         set_error("bad query array");
         return EGX_ERR_INVALID_VALUE;
     }
+    return EGX_SUCCESS;
+}
+
+// few queries: split the training range so that ~1024 (mean) / ~512 (x-gradient) workgroups exist
+static int even_splits(int slabs, int want) {
+    if (want > slabs) want = slabs;
+    const int per = (slabs + want - 1) / want;
+    return (slabs + per - 1) / per;
+}
+int mean_splits(int rows, int m_pad) {
+    const int wgs = m_pad / 64;
+    return even_splits(rows / 64, wgs < 1024 ? (1024 + wgs - 1) / wgs : 1);
+}
+int xgrad_splits(int rows, int m_pad) {
+    const int wgs = m_pad / 128;
+    return even_splits((rows + 63) / 64, wgs < 512 ? (512 + wgs - 1) / wgs : 1);
+}
+
+// corr (m x n): algorithm.rs:372-380 ; rt = C^-1 corr^T: :337-350 (held transposed, row per query) ; sum rt^2 and ft^T rt
+// (:352): the factor and its tile inverses are workspace 0's, the ft^T rows live below the factor
+int posterior_solve(egx_gp *gp, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl) {
+    const Workspace &w = gp->ws[0];
+    const int n_pad = gp->n_pad;
+    EGX_RC(launch_cross_corr(st, gp->corr, xqT, m_pad, m_pad, gp->d_xT, n_pad, n_pad, gp->d, gp->d_fit_coef, gp->fit_hcols, RT,
+                             n_pad));
+    EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, RT, n_pad, m_pad));
+    return launch_row_reduce(st, RT, n_pad, m_pad, gp->n, w.M + (size_t)n_pad * gp->ld, gp->ld, gp->p, s0, sl);
+}
+// -Z^T = 0 - C^-T rt as an (n_pad x m_pad) matrix (W upper triangular: K range starts at the row tile)
+int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt) {
+    const int n_pad = gp->n_pad;
+    EGX_HIP_CHECK(hipMemsetAsync(Wt, 0, sizeof(double) * (size_t)n_pad * m_pad, st));
+    return launch_gemm_nt_sub(st, Wt, m_pad, gp->d_W, n_pad, RT, n_pad, n_pad, m_pad, n_pad, 0, 1);
+}
+// -(Z + E)^T : Wt -= (-R^-1 F) (-D)^T
+int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int m_pad, double *Wt) {
+    const int rp = gp->rhs_pad;
+    return launch_gemm_nt_sub(st, Wt, m_pad, gp->d_neg_invkf, rp, dneg, rp, gp->n_pad, m_pad, rp, 0, 0);
+}
+
+static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vout);
+static int small_path_buffers(egx_gp *gp);
+
+int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout) {
+    EGX_RC(check_query(gp, xq, m));
     EGX_RC(set_device(gp));
     if (vout && m > 0 && m <= 8 && gp->winv_fail_epoch != gp->fit_epoch) {
         // a few points at a time: EGO's inner loop (its criteria ask for value AND variance).  The cached C^-T behind
@@ -72,7 +114,7 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
         }
     }
     Workspace &w = gp->ws[0];
-    const int n = gp->n, n_pad = gp->n_pad, d = gp->d, p = gp->p;
+    const int n_pad = gp->n_pad, d = gp->d, p = gp->p;
     // chunk so that the (m_tile x n_pad) block of predict_var stays <= 1 GiB
     int64_t cap = ((int64_t)1 << 27) / n_pad / kTile * kTile;
     if (cap < kTile) cap = kTile;
@@ -98,15 +140,7 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
         sl_.m_pad = m_pad;
         hipStream_t st = sl_.stream;
         EGX_RC(upload_queries(gp, xq, m0, mc, m_pad, sl_.xn, sl_.d_xraw, sl_.d_xqT, st));
-        // few queries: split the training range so that ~1024 workgroups exist (partial sums added below)
-        int msplit = 1;
-        if (m_pad / 64 < 1024) msplit = (1024 + m_pad / 64 - 1) / (m_pad / 64);
-        if (msplit > n_pad / 64) msplit = n_pad / 64;
-        {
-            const int per = (n_pad / 64 + msplit - 1) / msplit;
-            msplit = (n_pad / 64 + per - 1) / per;
-        }
-        sl_.msplit = msplit;
+        const int msplit = sl_.msplit = mean_splits(n_pad, m_pad);  // (partial sums added below)
         if (yout) {
             EGX_RC(sl_.d_racc.alloc((size_t)msplit * m_pad));
             EGX_RC(launch_predict_mean(st, gp->corr, sl_.d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
@@ -117,13 +151,7 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
             EGX_RC(sl_.d_RT.alloc((size_t)m_pad * n_pad));
             EGX_RC(sl_.d_s0.alloc(m_pad));
             EGX_RC(sl_.d_sl.alloc((size_t)m_pad * p));
-            // corr (m x n): algorithm.rs:372-380 ; rt = C^-1 corr^T: :337-350 (held transposed, row per query)
-            EGX_RC(launch_cross_corr(st, gp->corr, sl_.d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
-                                     gp->fit_hcols, sl_.d_RT.p, n_pad));
-            EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, sl_.d_RT.p, n_pad, m_pad));
-            // sum rt^2 and ft^T rt (:352): ft^T rows live below the factor in the workspace
-            EGX_RC(launch_row_reduce(st, sl_.d_RT.p, n_pad, m_pad, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p, sl_.d_s0.p,
-                                     sl_.d_sl.p));
+            EGX_RC(posterior_solve(gp, st, sl_.d_xqT.p, m_pad, sl_.d_RT.p, sl_.d_s0.p, sl_.d_sl.p));
         }
         return EGX_SUCCESS;
     };
@@ -155,13 +183,7 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
             if (vout) {
                 // u = (Rq^T)^-1 (ft^T rt - f^T)   algorithm.rs:352-367 ; Rq^T lower triangular
                 for (int l = 0; l < p; l++) rhs[l] = sl[(size_t)a * p + l] - f[l];
-                double usq = 0.0;
-                for (int i = 0; i < p; i++) {
-                    double sacc = rhs[i];
-                    for (int l = 0; l < i; l++) sacc -= gp->ft_qr_r[(size_t)l * p + i] * u[l];
-                    u[i] = sacc / gp->ft_qr_r[(size_t)i * p + i];
-                    usq += u[i] * u[i];
-                }
+                const double usq = hm::trend_forward(gp->ft_qr_r.data(), p, rhs.data(), u.data());
                 double mse = gp->sigma2 * (1.0 - s0[a] + usq);  // algorithm.rs:272-274
                 vout[m0 + a] = (mse < 0.0) ? 0.0 : mse;         // :278
             }
@@ -211,6 +233,26 @@ int ensure_winv(egx_gp *gp) {
             for (int l = 0; l < gp->p; l++) gp->h_neg_invkf[(size_t)i * gp->p + l] = tmp[(size_t)i * gp->rhs_pad + l];
     }
     gp->winv_epoch = gp->fit_epoch;
+    return EGX_SUCCESS;
+}
+
+int ensure_trend_state(egx_gp *gp, hipStream_t st) {
+    if (gp->trend_epoch == gp->fit_epoch && gp->d_fidx) return EGX_SUCCESS;
+    const int p = gp->p;
+    const std::vector<int> idx = hm::regression_index(gp->mean, gp->d);
+    std::vector<double> rt((size_t)p * p);
+    for (int i = 0; i < p; i++)
+        for (int l = 0; l < p; l++) rt[(size_t)i * p + l] = gp->ft_qr_r[(size_t)l * p + i];
+    EGX_RC(gp->d_tbeta.alloc(p));
+    EGX_RC(gp->d_rq.alloc((size_t)p * p));
+    EGX_RC(gp->d_rqT.alloc((size_t)p * p));
+    EGX_RC(gp->d_fidx.alloc(idx.size()));
+    EGX_HIP_CHECK(hipMemcpyAsync(gp->d_tbeta, gp->beta.data(), sizeof(double) * p, hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipMemcpyAsync(gp->d_rq, gp->ft_qr_r.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipMemcpyAsync(gp->d_rqT, rt.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipMemcpyAsync(gp->d_fidx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, st));
+    EGX_HIP_CHECK(hipStreamSynchronize(st));  // rt and idx are locals; once per fitted state
+    gp->trend_epoch = gp->fit_epoch;
     return EGX_SUCCESS;
 }
 
@@ -298,16 +340,8 @@ static int xgrad_small(egx_gp *gp, const double *xq, int64_t m, double *gy, doub
                 for (int i = 0; i < n; i++) sacc += gp->ft[(size_t)i * p + l] * y[i];
                 a_vec[l] = f[l] - sacc;
             }
-            for (int i = 0; i < p; i++) {
-                double sacc = a_vec[i];
-                for (int l = 0; l < i; l++) sacc -= gp->ft_qr_r[(size_t)l * p + i] * u[l];
-                u[i] = sacc / gp->ft_qr_r[(size_t)i * p + i];
-            }
-            for (int i = p - 1; i >= 0; i--) {
-                double sacc = u[i];
-                for (int l = i + 1; l < p; l++) sacc -= gp->ft_qr_r[(size_t)i * p + l] * dd[l];
-                dd[i] = sacc / gp->ft_qr_r[(size_t)i * p + i];
-            }
+            (void)hm::trend_forward(gp->ft_qr_r.data(), p, a_vec.data(), u.data());
+            hm::trend_backward(gp->ft_qr_r.data(), p, u.data(), dd.data());
             for (int i = 0; i < n; i++) {  // -(R^-1 r + R^-1 F D)_i
                 double e = 0.0;
                 for (int l = 0; l < p; l++) e += gp->h_neg_invkf[(size_t)i * p + l] * dd[l];
@@ -327,21 +361,18 @@ static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vo
     const int n = gp->n, d = gp->d, p = gp->p;
     EGX_RC(ensure_winv(gp));
     EGX_RC(small_path_buffers(gp));
-    std::vector<double> xn, slab, y, z, f(p), u(p);
+    std::vector<double> xn, slab, y, z, f(p), rhs(p), u(p);
     for (int64_t a = 0; a < m; a++) {
         EGX_RC(small_path_query(gp, xq, a, xn, slab));
         EGX_RC(small_path_solve(gp, y, z, false));
         double s0 = 0.0;
         for (int i = 0; i < n; i++) s0 += y[i] * y[i];
         hm::regression_row(gp->mean, xn.data(), d, f.data());
-        double usq = 0.0;
         for (int i = 0; i < p; i++) {  // u = (Rq^T)^-1 (ft^T rt - f)   algorithm.rs:352-367
-            double sacc = -f[i];
-            for (int t = 0; t < n; t++) sacc += gp->ft[(size_t)t * p + i] * y[t];
-            for (int l = 0; l < i; l++) sacc -= gp->ft_qr_r[(size_t)l * p + i] * u[l];
-            u[i] = sacc / gp->ft_qr_r[(size_t)i * p + i];
-            usq += u[i] * u[i];
+            rhs[i] = -f[i];
+            for (int t = 0; t < n; t++) rhs[i] += gp->ft[(size_t)t * p + i] * y[t];
         }
+        const double usq = hm::trend_forward(gp->ft_qr_r.data(), p, rhs.data(), u.data());
         const double mse = gp->sigma2 * (1.0 - s0 + usq);
         vout[a] = (mse < 0.0) ? 0.0 : mse;
     }
@@ -355,14 +386,7 @@ static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vo
 // The reference redoes R^-1 F and chol(B) for every query point; here they are per-fit state, the per-query
 // R^-1 r = C^-T (C^-1 r) is the predict_var solve followed by one GEMM with the cached C^-T.
 int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv) {
-    if (!gp->fitted) {
-        set_error("model is not fitted (call egx_gp_finalize or egx_gp_fit first)");
-        return EGX_ERR_NOT_FITTED;
-    }
-    if (m < 0 || (m > 0 && !xq)) {
-        set_error("bad query array");
-        return EGX_ERR_INVALID_VALUE;
-    }
+    EGX_RC(check_query(gp, xq, m));
     EGX_RC(set_device(gp));
     // (the few-query kernel keeps 5 + hcols doubles per input dimension in LDS, the batched one 1 + hcols: very wide
     //  inputs take the batched form whatever m is)
@@ -379,14 +403,7 @@ int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv) 
     for (int64_t m0 = 0; m0 < m; m0 += cap) {
         const int mc = (int)((m - m0 < cap) ? (m - m0) : cap);
         const int m_pad = (int)round_up(mc, kTile);
-        // enough workgroups for small batches: split the training range (partial sums added on the host)
-        int nsplit = 1;
-        const int wgs = m_pad / 128;
-        if (wgs < 512) nsplit = (512 + wgs - 1) / wgs;
-        const int slabs = (n + 63) / 64;
-        if (nsplit > slabs) nsplit = slabs;
-        const int per = (slabs + nsplit - 1) / nsplit;
-        nsplit = (slabs + per - 1) / per;
+        const int nsplit = xgrad_splits(n, m_pad);  // (partial sums added on the host)
         EGX_RC(upload_queries(gp, xq, m0, mc, m_pad, xn, d_xraw, d_xqT, w.stream));
         const size_t out_sz = (size_t)nsplit * m_pad * d;
         EGX_RC(d_out.alloc(out_sz));
@@ -414,37 +431,22 @@ int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv) 
             EGX_RC(d_sl.alloc((size_t)m_pad * p));
             EGX_RC(d_Wt.alloc((size_t)n_pad * m_pad));
             EGX_RC(d_D.alloc((size_t)m_pad * rp));
-            EGX_RC(launch_cross_corr(w.stream, gp->corr, d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n_pad, d,
-                                     gp->d_fit_coef, gp->fit_hcols, d_RT.p, n_pad));
-            EGX_RC(launch_trsm_rows(w.stream, w.M, gp->ld, n_pad, w.dinv, d_RT.p, n_pad, m_pad));
-            EGX_RC(launch_row_reduce(w.stream, d_RT.p, n_pad, m_pad, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p,
-                                     d_s0.p, d_sl.p));
+            EGX_RC(posterior_solve(gp, w.stream, d_xqT.p, m_pad, d_RT.p, d_s0.p, d_sl.p));
             EGX_HIP_CHECK(hipMemcpyAsync(sl.data(), d_sl.p, sizeof(double) * (size_t)m_pad * p, hipMemcpyDeviceToHost,
                                          w.stream));
-            // -Z^T = 0 - C^-T rt  as an (n_pad x m_pad) matrix (W upper triangular: K range starts at the row tile)
-            EGX_HIP_CHECK(hipMemsetAsync(d_Wt.p, 0, sizeof(double) * (size_t)n_pad * m_pad, w.stream));
-            EGX_RC(launch_gemm_nt_sub(w.stream, d_Wt.p, m_pad, gp->d_W, n_pad, d_RT.p, n_pad, n_pad, m_pad, n_pad, 0, 1));
+            EGX_RC(posterior_weights(gp, w.stream, d_RT.p, m_pad, d_Wt.p));
             EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
             // D = B^-1 A^T per query (p x p work on the host), uploaded negated and zero padded to rhs_pad columns
             dneg.assign((size_t)m_pad * rp, 0.0);
             for (int a = 0; a < mc; a++) {
                 hm::regression_row(gp->mean, xn.empty() ? nullptr : &xn[(size_t)a * d], d, f.data());
                 for (int l = 0; l < p; l++) a_vec[l] = f[l] - sl[(size_t)a * p + l];
-                for (int i = 0; i < p; i++) {  // Rq^T u = A^T (Rq^T lower)
-                    double sacc = a_vec[i];
-                    for (int l = 0; l < i; l++) sacc -= gp->ft_qr_r[(size_t)l * p + i] * u[l];
-                    u[i] = sacc / gp->ft_qr_r[(size_t)i * p + i];
-                }
-                for (int i = p - 1; i >= 0; i--) {  // Rq D = u (Rq upper)
-                    double sacc = u[i];
-                    for (int l = i + 1; l < p; l++) sacc -= gp->ft_qr_r[(size_t)i * p + l] * dd[l];
-                    dd[i] = sacc / gp->ft_qr_r[(size_t)i * p + i];
-                }
+                (void)hm::trend_forward(gp->ft_qr_r.data(), p, a_vec.data(), u.data());  // Rq^T u = A^T
+                hm::trend_backward(gp->ft_qr_r.data(), p, u.data(), dd.data());          // Rq D = u
                 for (int l = 0; l < p; l++) dneg[(size_t)a * rp + l] = -dd[l];
             }
             EGX_HIP_CHECK(hipMemcpyAsync(d_D.p, dneg.data(), sizeof(double) * dneg.size(), hipMemcpyHostToDevice, w.stream));
-            // -(Z + E)^T : Wt -= (-R^-1 F) (-D)^T
-            EGX_RC(launch_gemm_nt_sub(w.stream, d_Wt.p, m_pad, gp->d_neg_invkf, rp, d_D.p, rp, n_pad, m_pad, rp, 0, 0));
+            EGX_RC(posterior_weights_trend(gp, w.stream, d_D.p, m_pad, d_Wt.p));
             EGX_RC(launch_xgrad(w.stream, gp->corr, d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n, d, gp->d_fit_coef,
                                 gp->fit_hcols, d_Wt.p, m_pad, 0, nsplit, d_out.p));
             EGX_HIP_CHECK(hipMemcpyAsync(part.data(), d_out.p, sizeof(double) * out_sz, hipMemcpyDeviceToHost, w.stream));

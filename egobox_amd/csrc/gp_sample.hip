@@ -2,8 +2,8 @@
 // GaussianProcess::_compute_covariance algorithm.rs:310-326, sample_chol / sample_eig / sample :383-395, helper :1153-1193).
 // Everything of size m x m or m x n stays on the device; the host sees the m query points, m means and the result.
 //   1. queries uploaded and normalised on the device (as predict_impl)
-//   2. RT = C^-1 K(x, xt)^T, one row per query: predict_var's cross correlation + block solve; ft^T rt by its row reduction
-//   3. U = Rq^-T (ft^T rt - f(x)) per query (kernels_sample.hip k_sample_u)
+//   2. RT = C^-1 K(x, xt)^T, one row per query, and ft^T rt: posterior_solve (gp_predict.hip)
+//   3. U = Rq^-T (ft^T rt - f(x)) per query (kernels_sample.hip k_sample_u; Rq and the column index: ensure_trend_state)
 //   4. G = -RT RT^T + U U^T, lower tiles: two calls of the trailing-update GEMM (launch_gemm_nt_sub)
 //   5. S = sigma2 (K(x, x) + G) + tau I, padded with the identity (kernels_corr.hip k_cov_assemble)
 //   6. S = L L^T by launch_potrf; EGX_SAMPLE_PSD retries with tau x 10 on a failed pivot (the device info word)
@@ -81,28 +81,17 @@ namespace {
 
 // device buffers of one covariance: the normalised queries, the solves and the Gram matrix G
 struct CovBufs {
-    DevBuf xraw, xqT, RT, s0, sl, U, Uneg, R, fidx, G;
+    DevBuf xraw, xqT, RT, s0, sl, U, Uneg, G;
     int m = 0, m_pad = 0;
 };
 
-// regression column l of f(x) = fa[l] * fb[l]: (-1, -1) the constant, (j, -1) x_j, (k, j) x_j x_k (host_math.h regression_row)
-std::vector<int> regression_index(int mean, int d) {
-    std::vector<int> idx = {-1, -1};
-    if (mean >= 1)
-        for (int j = 0; j < d; j++) idx.insert(idx.end(), {j, -1});
-    if (mean >= 2)
-        for (int k = 0; k < d; k++)
-            for (int j = k; j < d; j++) idx.insert(idx.end(), {k, j});
-    return idx;
-}
-
 // steps 1-4 on the handle's first workspace stream: leaves b.xqT (d x m_pad) and b.G (m_pad x m_pad, lower tiles)
 int cov_prepare(egx_gp *gp, const double *xq, int m, CovBufs &b) {
-    Workspace &w = gp->ws[0];
-    hipStream_t st = w.stream;
+    hipStream_t st = gp->ws[0].stream;
     const int n = gp->n, n_pad = gp->n_pad, d = gp->d, p = gp->p;
     const int m_pad = (int)round_up(m, kTile), pk = (int)round_up(p, 16);
     b.m = m, b.m_pad = m_pad;
+    EGX_RC(ensure_trend_state(gp, st));
     EGX_RC(b.xraw.alloc((size_t)m * d));
     EGX_RC(b.xqT.alloc((size_t)d * m_pad));
     EGX_HIP_CHECK(hipMemcpyAsync(b.xraw.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st));
@@ -112,41 +101,25 @@ int cov_prepare(egx_gp *gp, const double *xq, int m, CovBufs &b) {
     EGX_RC(b.RT.alloc((size_t)m_pad * n_pad));
     EGX_RC(b.s0.alloc(m_pad));
     EGX_RC(b.sl.alloc((size_t)m_pad * p));
-    EGX_RC(launch_cross_corr(st, gp->corr, b.xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef, gp->fit_hcols,
-                             b.RT.p, n_pad));
-    EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, b.RT.p, n_pad, m_pad));
-    EGX_RC(launch_row_reduce(st, b.RT.p, n_pad, m_pad, n, w.M + (size_t)n_pad * gp->ld, gp->ld, p, b.s0.p, b.sl.p));
+    EGX_RC(posterior_solve(gp, st, b.xqT.p, m_pad, b.RT.p, b.s0.p, b.sl.p));
     if (n < n_pad)
         EGX_HIP_CHECK(hipMemset2DAsync(b.RT.p + n, sizeof(double) * n_pad, 0, sizeof(double) * (n_pad - n), m_pad, st));
     // u (algorithm.rs:352-367) on the device
-    const std::vector<int> idx = regression_index(gp->mean, d);
-    EGX_RC(b.fidx.alloc((idx.size() + 1) / 2));
-    EGX_RC(b.R.alloc((size_t)p * p));
-    EGX_HIP_CHECK(hipMemcpyAsync(b.fidx.p, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, st));
-    EGX_HIP_CHECK(hipMemcpyAsync(b.R.p, gp->ft_qr_r.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice, st));
     EGX_RC(b.U.alloc((size_t)m_pad * pk));
     EGX_RC(b.Uneg.alloc((size_t)m_pad * pk));
-    EGX_RC(launch_sample_u(st, b.sl.p, p, b.xqT.p, m_pad, reinterpret_cast<const int *>(b.fidx.p), b.R.p, m, m_pad, b.U.p,
-                           b.Uneg.p, pk));
+    EGX_RC(launch_sample_u(st, b.sl.p, p, b.xqT.p, m_pad, gp->d_fidx, gp->d_rq, m, m_pad, b.U.p, b.Uneg.p, pk));
     // G = 0 - RT RT^T - (-U) U^T, lower tiles
     EGX_RC(b.G.alloc((size_t)m_pad * m_pad));
     EGX_HIP_CHECK(hipMemsetAsync(b.G.p, 0, sizeof(double) * (size_t)m_pad * m_pad, st));
     EGX_RC(launch_gemm_nt_sub(st, b.G.p, m_pad, b.RT.p, n_pad, b.RT.p, n_pad, m_pad, m_pad, n_pad, 1));
     EGX_RC(launch_gemm_nt_sub(st, b.G.p, m_pad, b.Uneg.p, pk, b.U.p, pk, m_pad, m_pad, pk, 1));
-    // (the host copies below must not overtake the uploads of idx / ft_qr_r: they are read before this returns)
+    // (xq has been read, and a caller that fails from here on frees b with nothing in flight)
     EGX_HIP_CHECK(hipStreamSynchronize(st));
     return EGX_SUCCESS;
 }
 
-int check_query(egx_gp *gp, const double *xq, int64_t m) {
-    if (!gp->fitted) {
-        set_error("model is not fitted (call egx_gp_finalize or egx_gp_fit first)");
-        return EGX_ERR_NOT_FITTED;
-    }
-    if (m < 0 || (m > 0 && !xq)) {
-        set_error("bad query array");
-        return EGX_ERR_INVALID_VALUE;
-    }
+int check_cov_query(const egx_gp *gp, const double *xq, int64_t m) {
+    EGX_RC(check_query(gp, xq, m));
     if (m > (int64_t)1 << 20) {
         set_error("covariance of more than 2^20 query points");
         return EGX_ERR_INVALID_VALUE;
@@ -155,7 +128,7 @@ int check_query(egx_gp *gp, const double *xq, int64_t m) {
 }
 
 int covariance_impl(egx_gp *gp, const double *xq, int64_t m, double *cov) {
-    EGX_RC(check_query(gp, xq, m));
+    EGX_RC(check_cov_query(gp, xq, m));
     if (m == 0) return EGX_SUCCESS;
     EGX_RC(set_device(gp));
     CovBufs b;
@@ -173,7 +146,7 @@ int covariance_impl(egx_gp *gp, const double *xq, int64_t m, double *cov) {
 
 int sample_impl(egx_gp *gp, const double *xq, int64_t m, int64_t n_traj, int method, uint64_t seed, const double *z,
                 double *traj, double *tau_out) {
-    EGX_RC(check_query(gp, xq, m));
+    EGX_RC(check_cov_query(gp, xq, m));
     if (method != EGX_SAMPLE_CHOLESKY && method != EGX_SAMPLE_PSD) {
         set_error("sample: method must be EGX_SAMPLE_CHOLESKY or EGX_SAMPLE_PSD");
         return EGX_ERR_INVALID_VALUE;

@@ -59,6 +59,39 @@ inline void regression_row(int mean, const double *x, int64_t d, double *f) {
         for (int64_t k = 0; k < d; k++)
             for (int64_t j = k; j < d; j++) f[c++] = x[j] * x[k];
 }
+// regression_row's column order for the device: column l of f(x) is the product of the coordinates idx[2 l] and idx[2 l + 1]
+// (-1: 1.0) -- (-1, -1) the constant, (j, -1) x_j, (k, j) x_j x_k (trend_column.h evaluates it)
+inline std::vector<int> regression_index(int mean, int d) {
+    std::vector<int> idx = {-1, -1};
+    if (mean >= 1)
+        for (int j = 0; j < d; j++) idx.insert(idx.end(), {j, -1});
+    if (mean >= 2)
+        for (int k = 0; k < d; k++)
+            for (int j = k; j < d; j++) idx.insert(idx.end(), {k, j});
+    return idx;
+}
+
+// The trend tail of a prediction over Rq = ft_qr_r (p x p row-major, upper; algorithm.rs:352-367).  The loop orders are part
+// of the results' bits, and kernels_infill.hip reproduces the forward one.
+// Rq^T u = rhs (Rq^T lower triangular); returns sum u^2
+inline double trend_forward(const double *rq, int64_t p, const double *rhs, double *u) {
+    double usq = 0.0;
+    for (int64_t i = 0; i < p; i++) {
+        double sacc = rhs[i];
+        for (int64_t l = 0; l < i; l++) sacc -= rq[l * p + i] * u[l];
+        u[i] = sacc / rq[i * p + i];
+        usq += u[i] * u[i];
+    }
+    return usq;
+}
+// Rq D = u
+inline void trend_backward(const double *rq, int64_t p, const double *u, double *dd) {
+    for (int64_t i = p - 1; i >= 0; i--) {
+        double sacc = u[i];
+        for (int64_t l = i + 1; l < p; l++) sacc -= rq[i * p + l] * dd[l];
+        dd[i] = sacc / rq[i * p + i];
+    }
+}
 
 // sum_i log10(d_i) for positive finite d (the log-determinant term of algorithm.rs:1039-1041) without n calls of log10:
 // the mantissas are multiplied (renormalised every 256 factors: 256 numbers in [0.5, 1) cannot underflow), the exponents added;

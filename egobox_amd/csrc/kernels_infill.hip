@@ -20,6 +20,7 @@
 #include "infill_math.h"
 #include "infill_mix_math.h"
 #include "gmx_point.h"
+#include "trend_column.h"
 
 namespace egx {
 
@@ -60,9 +61,7 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_trend(TrendArgs g) {
     const int p = g.p, a = blockIdx.x, t = threadIdx.x;
     double *s = lds, *diag = lds + p, *prod = lds + 2 * p, *part = lds + 3 * p;
     for (int l = t; l < p; l += kInfThreads) {
-        const int ia = g.fidx[2 * l], ib = g.fidx[2 * l + 1];
-        const double fa = ia < 0 ? 1.0 : g.xqT[(int64_t)ia * kTile + a];
-        const double f = ib < 0 ? fa : g.xqT[(int64_t)ib * kTile + a] * fa;
+        const double f = trend_column(g.fidx, l, g.xqT, kTile, a);
         prod[l] = f * g.beta[l];
         s[l] = f - g.sl[(int64_t)a * p + l];
         diag[l] = g.R[(int64_t)l * p + l];
@@ -119,13 +118,9 @@ struct XgFinishArgs {
 __device__ inline double jac_dot(const XgFinishArgs &g, int a, int k, const double *v, double sign) {
     double acc = 0.0;
     for (int l = 1; l < g.p; l++) {
-        const int ia = g.fidx[2 * l], ib = g.fidx[2 * l + 1];
-        if (ib < 0) {
-            if (ia == k) acc += sign * v[l];
-        } else {
-            if (ia == k) acc += sign * v[l] * g.xqT[(int64_t)ib * kTile + a];
-            if (ib == k) acc += sign * v[l] * g.xqT[(int64_t)ia * kTile + a];
-        }
+        const int ia = g.fidx[2 * l], ib = g.fidx[2 * l + 1];  // d (fa fb) / d x_k: the other factor (times 1.0 is exact)
+        if (ia == k) acc += sign * v[l] * trend_factor(g.xqT, kTile, a, ib);
+        if (ib == k) acc += sign * v[l] * trend_factor(g.xqT, kTile, a, ia);
     }
     return acc;
 }

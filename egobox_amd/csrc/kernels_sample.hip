@@ -6,13 +6,13 @@
 #include "egx_internal.h"
 #include "mfma_gemm_core.h"
 #include "philox.h"
+#include "trend_column.h"
 
 namespace egx {
 
 // One wave per query q: s = sl[q] - f(x_q) in LDS, then the forward substitution with Rq^T (Rq = ft_qr_r, p x p row-major,
 // upper) column by column: u_i = s_i / Rq_ii, s_j -= Rq_ij u_i (j > i) -- the subtractions of predict_impl's host loop, in
-// its order.  f(x) = [1, x_a, x_b x_a (a <= b)] from the normalised query (k-major xqT): column l is fa[l] * fb[l] with the
-// coordinates named by fidx (-1: 1.0), host_math.h regression_row's order.  Rows q >= m of U are zero.
+// its order.  f(x) from the normalised query (k-major xqT) by trend_column.h.  Rows q >= m of U are zero.
 __global__ __launch_bounds__(64) void k_sample_u(const double *__restrict__ sl, int p, const double *__restrict__ xqT,
                                                  int64_t ldq, const int *__restrict__ fidx, const double *__restrict__ R, int m,
                                                  double *__restrict__ U, double *__restrict__ Uneg, int64_t ldu) {
@@ -23,12 +23,7 @@ __global__ __launch_bounds__(64) void k_sample_u(const double *__restrict__ sl, 
         for (int l = lane; l < ldu; l += 64) urow[l] = nrow[l] = 0.0;
         return;
     }
-    for (int l = lane; l < p; l += 64) {
-        const int a = fidx[2 * l], b = fidx[2 * l + 1];
-        const double fa = a < 0 ? 1.0 : xqT[(int64_t)a * ldq + q];
-        const double fb = b < 0 ? 1.0 : xqT[(int64_t)b * ldq + q];
-        s[l] = sl[(int64_t)q * p + l] - (b < 0 ? fa : fb * fa);
-    }
+    for (int l = lane; l < p; l += 64) s[l] = sl[(int64_t)q * p + l] - trend_column(fidx, l, xqT, ldq, q);
     __syncthreads();
     for (int i = 0; i < p; i++) {
         const double ui = s[i] / R[(int64_t)i * p + i];

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_sgp_grad_finish(const double *__restric
 #endif
 constexpr int kSgpPointMax = EGX_SGP_POINT_MAX;
 
-int check_query(egx_sgp *g, const double *xq, int64_t m) {
+int check_sgp_query(egx_sgp *g, const double *xq, int64_t m) {
     if (!g->fitted) {
         set_error("sparse model is not fitted (call egx_sgp_finalize or egx_sgp_fit first)");
         return EGX_ERR_NOT_FITTED;
@@ -106,7 +106,7 @@ int ensure_inverse_factors(egx_sgp *g) {
 namespace egx {
 
 int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout, double *gyout, double *gvout) {
-    EGX_RC(check_query(g, xq, m));
+    EGX_RC(check_sgp_query(g, xq, m));
     const int d = g->d, nz = g->nz, z_pad = g->z_pad;
     const bool grad = gyout || gvout, solves = vout || gvout;
     if (grad && (int64_t)d * (1 + 5) > 20480) {
@@ -185,11 +185,7 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
             }
         } else if (grad) {
             // enough workgroups for small batches: split the inducing points (partial sums added by k_sgp_grad_finish)
-            const int slabs = (nz + 63) / 64, wgs = m_pad / 128;
-            int nsplit = wgs < 512 ? (512 + wgs - 1) / wgs : 1;
-            if (nsplit > slabs) nsplit = slabs;
-            const int per = (slabs + nsplit - 1) / nsplit;
-            nsplit = (slabs + per - 1) / per;
+            const int nsplit = xgrad_splits(nz, m_pad);
             EGX_RC(g->q_part.alloc((size_t)nsplit * m_pad * d));
             if (gyout) {
                 EGX_RC(launch_xgrad(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit,
@@ -253,7 +249,7 @@ namespace {
 // sigma2 r(x, x): the PRIOR covariance, without noise and without the Woodbury term.  Steps 5-8 of gp_sample.hip.
 int sgp_sample(egx_sgp *g, const double *xq, int64_t m, int64_t n_traj, int method, uint64_t seed, const double *z, double *traj,
                double *tau_out) {
-    EGX_RC(check_query(g, xq, m));
+    EGX_RC(check_sgp_query(g, xq, m));
     if (m > (int64_t)1 << 20) {
         set_error("sample: more than 2^20 query points");
         return EGX_ERR_INVALID_VALUE;

@@ -75,6 +75,72 @@ int main() {
             EXPECT(std::fabs(fd - jd[k]) < 1e-7);
         }
     }
+    // regression_index names exactly the products regression_row writes, in its column order
+    for (int mean = 0; mean < 3; mean++)
+        for (int d : {1, 3}) {
+            const int64_t p = hm::regression_ncols(mean, d);
+            std::vector<double> x(d), f(p);
+            for (auto &e : x) e = g(rng);
+            hm::regression_row(mean, x.data(), d, f.data());
+            const std::vector<int> idx = hm::regression_index(mean, d);
+            EXPECT(idx.size() == (size_t)(2 * p));
+            for (int64_t l = 0; l < p && 2 * l + 1 < (int64_t)idx.size(); l++) {
+                const int a = idx[2 * l], b = idx[2 * l + 1];
+                EXPECT(a >= -1 && a < d && b >= -1 && b < d);
+                const double fa = a < 0 ? 1.0 : x[a];
+                EXPECT((b < 0 ? fa : x[b] * fa) == f[l]);
+            }
+        }
+    // the trend tail: Rq^T u = rhs and Rq D = u over a row-major upper Rq against a dense solve (Gaussian elimination with
+    // partial pivoting in long double), p = 1 (constant trend) and p = 6 (quadratic trend at d = 2).  Rq has a diagonal in
+    // [1, 2] and off-diagonal entries of size 0.3: its condition number stays below 1e2, so 1e-13 |x|_max is a wide bound
+    // for six double-precision unknowns.
+    for (int64_t p : {hm::regression_ncols(0, 2), hm::regression_ncols(2, 2)}) {
+        EXPECT(p == 1 || p == 6);
+        std::uniform_real_distribution<double> dg(1.0, 2.0);
+        std::vector<double> rq(p * p, 0.0), rhs(p), u(p), dd(p);
+        for (int64_t i = 0; i < p; i++) {
+            rq[i * p + i] = dg(rng);
+            for (int64_t j = i + 1; j < p; j++) rq[i * p + j] = 0.3 * g(rng);
+            rhs[i] = g(rng);
+        }
+        auto dense_solve = [&](bool transposed, const std::vector<double> &b) {
+            std::vector<long double> a(p * p), x(b.begin(), b.end());
+            for (int64_t i = 0; i < p; i++)
+                for (int64_t j = 0; j < p; j++) a[i * p + j] = transposed ? rq[j * p + i] : rq[i * p + j];
+            for (int64_t k = 0; k < p; k++) {
+                int64_t piv = k;
+                for (int64_t i = k + 1; i < p; i++)
+                    if (fabsl(a[i * p + k]) > fabsl(a[piv * p + k])) piv = i;
+                for (int64_t j = 0; j < p; j++) std::swap(a[k * p + j], a[piv * p + j]);
+                std::swap(x[k], x[piv]);
+                for (int64_t i = k + 1; i < p; i++) {
+                    const long double m = a[i * p + k] / a[k * p + k];
+                    for (int64_t j = k; j < p; j++) a[i * p + j] -= m * a[k * p + j];
+                    x[i] -= m * x[k];
+                }
+            }
+            for (int64_t i = p - 1; i >= 0; i--) {
+                for (int64_t j = i + 1; j < p; j++) x[i] -= a[i * p + j] * x[j];
+                x[i] /= a[i * p + i];
+            }
+            return x;
+        };
+        const double usq = hm::trend_forward(rq.data(), p, rhs.data(), u.data());
+        hm::trend_backward(rq.data(), p, u.data(), dd.data());
+        const std::vector<long double> u_ref = dense_solve(true, rhs), d_ref = dense_solve(false, u);
+        double usq_chk = 0.0, umax = 0.0, dmax = 0.0;
+        for (int64_t i = 0; i < p; i++) {
+            usq_chk += u[i] * u[i];
+            umax = std::fmax(umax, std::fabs(u[i]));
+            dmax = std::fmax(dmax, std::fabs(dd[i]));
+        }
+        EXPECT(usq == usq_chk);
+        for (int64_t i = 0; i < p; i++) {
+            EXPECT(std::fabs(u[i] - (double)u_ref[i]) <= 1e-13 * umax);
+            EXPECT(std::fabs(dd[i] - (double)d_ref[i]) <= 1e-13 * dmax);
+        }
+    }
     // Householder QR with a positive diagonal: R^T R = A^T A, Q^T b consistent with least squares
     {
         const int64_t n = 30, p = 4;

@@ -301,3 +301,25 @@ def test_handles_and_errors(egx, O):
     gmx = egx.moe.GaussianMixture(np.full(2, 0.5), np.array([[0.0], [4.0]]), np.ones((2, 1, 1)))
     with pytest.raises(egx.SampleError):
         egx.moe.GpMixture(gpx._experts * 2, gmx).sample(xt, 2)
+
+
+# ------------------------------------------------------------------ 7. a handle finalised twice
+@pytest.mark.gpu
+def test_refinalised_handle_samples_new_state(egx):
+    """The trend state the sampling kernels read (beta, Rq, the column index) is cached on the device per fitted state: a
+    second finalize must replace it.  Linear mean (p = 3), so Rq is a matrix and depends on theta."""
+    x, y = _data(200, 2, seed=17)
+    xq = np.random.default_rng(11).random((9, 2))
+    th1, th2 = np.array([0.5, 3.0]), np.array([4.0, 0.8])
+    with egx.GpHandle(x, y, mean=1, corr=0) as h, egx.GpHandle(x, y, mean=1, corr=0) as fresh:
+        h.finalize(th1)
+        c1 = h.predict_covariance(xq)
+        s1 = h.sample(xq, 5, seed=31)
+        h.finalize(th2)
+        c2 = h.predict_covariance(xq)
+        s2 = h.sample(xq, 5, seed=31)
+        fresh.finalize(th2)
+        np.testing.assert_array_equal(c2, fresh.predict_covariance(xq))
+        np.testing.assert_array_equal(s2, fresh.sample(xq, 5, seed=31))
+        assert not np.array_equal(c2, c1)
+        assert not np.array_equal(s2, s1)
