@@ -224,6 +224,10 @@ inline size_t gmm_part_len(int DP) { return (size_t)(DP / 4) * (DP / 4 + 1) / 2 
 size_t gmm_estep_lds_bytes(int DP, int k);
 int launch_gmm_estep(hipStream_t s, const GmmLaunch &g);
 int launch_gmm_mstep(hipStream_t s, const GmmLaunch &g, double reg_covar);
+// The fitted mixture at m raw points (m x d on the device), one lane per point on the calling thread's default stream: the
+// responsibilities (out: m x k) or, deriv, their x-derivatives (m x k x d).  blk = gmx_pack's block (gmx_point.h) on the device,
+// lds = the dynamic LDS the caller has sized and bounded.
+int launch_gmx_probas(bool deriv, const double *xq, int64_t m, int d, int k, const double *blk, size_t lds, double *out);
 
 // ---- kernels_chol.hip -------------------------------------------------------
 // In-place blocked right-looking Cholesky of the leading n_pad x n_pad block (lower), applied to

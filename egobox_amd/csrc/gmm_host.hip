@@ -3,6 +3,7 @@
 // The n_runs restarts are independent EM problems of one shape over the SAME data: they advance in lock-step, one E-step
 // launch and one M-step launch per iteration for all of them (kernels_gmm.hip), the host reads the R lower bounds back and
 // freezes the restarts that stopped.  A restart computes the same bits alone and in any batch.
+// ... and the fitted mixture's predict side: egx_gmx_precisions_chol (host) and egx_gmx_predict_probas(_derivatives).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -11,6 +12,7 @@
 
 #include "dev_mem.h"
 #include "egx_internal.h"
+#include "gmx_point.h"
 #include "gp_handle.h"
 
 using egx::set_error;
@@ -21,6 +23,30 @@ bool all_finite(const double *p, size_t len) {
     for (size_t i = 0; i < len; i++)
         if (!std::isfinite(p[i])) return false;
     return true;
+}
+
+// The operands of k_gmx_probas / k_gmx_probas_deriv on `device` (< 0: the calling thread's current one): the query points and
+// gmx_pack's block [means | scaled factors | par] (gaussian_mixture.rs:105-110, 253-283), one upload each.
+int gmx_upload(const std::string &who, int32_t device, const double *weights, const double *means, const double *precisions_chol,
+               int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m, egx::DevBuf &d_x, egx::DevBuf &d_blk) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        set_error(who + ": no HIP device");
+        return EGX_ERR_NO_DEVICE;
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
+    if (device >= ndev) {
+        set_error(who + ": device out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    EGX_HIP_CHECK(hipSetDevice(device));
+    const std::vector<double> blk = egx::gmx_pack(weights, means, precisions_chol, k, d, heaviside_factor);
+    EGX_RC(d_x.alloc((size_t)m * d));
+    EGX_RC(d_blk.alloc(blk.size()));
+    EGX_HIP_CHECK(hipMemcpy(d_x.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice));
+    EGX_HIP_CHECK(hipMemcpy(d_blk.p, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
+    return EGX_SUCCESS;
 }
 
 }  // namespace
@@ -186,6 +212,93 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
         for (int j = 0; j < D; j++) means[(size_t)c * D + j] = h_means[i * DP + j];
         std::copy(h_cov.begin() + i * D * D, h_cov.begin() + (i + 1) * D * D, covariances + (size_t)c * D * D);
     }
+    return EGX_SUCCESS;
+}
+
+// ---- Gaussian mixture responsibilities ----------------------------------------------------------
+// precisions_chol[c] = (chol(cov_c)^-1)^T, crates/moe/src/gaussian_mixture.rs:182-205: d x d host arithmetic.
+int32_t egx_gmx_precisions_chol(const double *covariances, int64_t k, int64_t d, double *precisions_chol) {
+    if (!covariances || !precisions_chol || k < 1 || d < 1) {
+        set_error("egx_gmx_precisions_chol: bad arguments");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::vector<double> L((size_t)d * d), Li((size_t)d * d);
+    for (int64_t c = 0; c < k; c++) {
+        const double *A = covariances + (size_t)c * d * d;
+        std::fill(L.begin(), L.end(), 0.0);
+        for (int64_t j = 0; j < d; j++) {  // lower Cholesky factor, column by column
+            double dj = A[j * d + j];
+            for (int64_t l = 0; l < j; l++) dj -= L[j * d + l] * L[j * d + l];
+            if (!(dj > 0.0) || !std::isfinite(dj)) {
+                set_error("egx_gmx_precisions_chol: covariance " + std::to_string((long long)c) + " is not positive definite");
+                return EGX_ERR_LINALG;
+            }
+            L[j * d + j] = std::sqrt(dj);
+            for (int64_t i = j + 1; i < d; i++) {
+                double v = A[i * d + j];
+                for (int64_t l = 0; l < j; l++) v -= L[i * d + l] * L[j * d + l];
+                L[i * d + j] = v / L[j * d + j];
+            }
+        }
+        std::fill(Li.begin(), Li.end(), 0.0);  // L^-1 by forward substitution on the identity
+        for (int64_t col = 0; col < d; col++)
+            for (int64_t i = col; i < d; i++) {
+                double v = (i == col) ? 1.0 : 0.0;
+                for (int64_t l = col; l < i; l++) v -= L[i * d + l] * Li[l * d + col];
+                Li[i * d + col] = v / L[i * d + i];
+            }
+        double *out = precisions_chol + (size_t)c * d * d;
+        for (int64_t i = 0; i < d; i++)
+            for (int64_t j = 0; j < d; j++) out[i * d + j] = Li[j * d + i];  // transposed: upper triangular
+    }
+    return EGX_SUCCESS;
+}
+
+int32_t egx_gmx_predict_probas(int32_t device, const double *weights, const double *means, const double *precisions_chol,
+                               int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m, double *probas) {
+    if (!weights || !means || !precisions_chol || k < 1 || d < 1 || d > 4096 || m < 0 || (m > 0 && (!xq || !probas)) ||
+        !(heaviside_factor > 0.0)) {
+        set_error("egx_gmx_predict_probas: bad arguments");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (m == 0) return EGX_SUCCESS;
+    if (k == 1) {  // gaussian_mixture.rs:115-116
+        for (int64_t a = 0; a < m; a++) probas[a] = 1.0;
+        return EGX_SUCCESS;
+    }
+    egx::DevBuf d_x, d_blk, d_out;
+    EGX_RC(gmx_upload("egx_gmx_predict_probas", device, weights, means, precisions_chol, k, d, heaviside_factor, xq, m, d_x, d_blk));
+    EGX_RC(d_out.alloc((size_t)m * k));
+    const size_t lds = sizeof(double) * 64 * (size_t)(d | 1);
+    if (lds > 160 * 1024) {
+        set_error("egx_gmx_predict_probas: d too large for one workgroup's LDS");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    EGX_RC(egx::launch_gmx_probas(false, d_x.p, m, (int)d, (int)k, d_blk.p, lds, d_out.p));
+    EGX_HIP_CHECK(hipMemcpy(probas, d_out.p, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost));
+    return EGX_SUCCESS;
+}
+
+int32_t egx_gmx_predict_probas_derivatives(int32_t device, const double *weights, const double *means,
+                                           const double *precisions_chol, int64_t k, int64_t d, double heaviside_factor,
+                                           const double *xq, int64_t m, double *dprobas) {
+    if (!weights || !means || !precisions_chol || k < 1 || d < 1 || m < 0 || (m > 0 && (!xq || !dprobas)) ||
+        !(heaviside_factor > 0.0)) {
+        set_error("egx_gmx_predict_probas_derivatives: bad arguments");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (m == 0) return EGX_SUCCESS;
+    const size_t lds = sizeof(double) * 64 * (size_t)(3 * (d | 1) + (k | 1));
+    if (lds > 160 * 1024) {
+        set_error("egx_gmx_predict_probas_derivatives: d / k too large for one workgroup's LDS (3 d + k <= 320)");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    egx::DevBuf d_x, d_blk, d_out;
+    EGX_RC(gmx_upload("egx_gmx_predict_probas_derivatives", device, weights, means, precisions_chol, k, d, heaviside_factor, xq, m,
+                      d_x, d_blk));
+    EGX_RC(d_out.alloc((size_t)m * k * d));
+    EGX_RC(egx::launch_gmx_probas(true, d_x.p, m, (int)d, (int)k, d_blk.p, lds, d_out.p));
+    EGX_HIP_CHECK(hipMemcpy(dprobas, d_out.p, sizeof(double) * (size_t)m * k * d, hipMemcpyDeviceToHost));
     return EGX_SUCCESS;
 }
 

@@ -1,14 +1,16 @@
 // The responsibilities of a Gaussian mixture at ONE point (GaussianMixture::predict_probas / predict_probas_derivatives,
-// crates/moe/src/gaussian_mixture.rs:114-170, 231-283): the one text behind k_gmx_probas / k_gmx_probas_deriv (sweep.hip) and
-// k_infill_mix (kernels_infill.hip), and the host preparation of the operands they read.  A lane owns the point; x, z, vp and
+// crates/moe/src/gaussian_mixture.rs:114-170, 231-283): the one text behind k_gmx_probas / k_gmx_probas_deriv (kernels_gmm.hip)
+// and k_infill_mix (kernels_infill.hip), and the host preparation of the operands they read (gmx_pack).  A lane owns the point; x, z, vp and
 // u are the lane's own scratch rows, means / precs / par are read at wave-uniform addresses.
 // The bodies switch FMA contraction OFF and spell out every fused multiply-add, so that every translation unit runs the same
-// operations whatever its contraction mode: the explicit ones are those the compiler's default mode chose when the two kernels
-// of sweep.hip held this text (v' += u' and u' v - u v'), which therefore keep their bits.
+// operations whatever its contraction mode: the explicit ones are those the compiler's default mode chose when the two
+// k_gmx_* kernels held this text themselves (v' += u' and u' v - u v'), which therefore keep their bits.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace egx {
 
@@ -24,6 +26,15 @@ inline void gmx_scaled_factors(const double *weights, const double *precisions_c
         for (int64_t i = 0; i < d; i++) ld += std::log(precs[(size_t)c * d * d + i * d + i]);
         par[c] = (-0.5 * cst + ld) + std::log(weights[c]);
     }
+}
+
+// the operands of the three kernels as ONE block: [means (k d) | scaled factors (k d d) | par (k)]
+inline std::vector<double> gmx_pack(const double *weights, const double *means, const double *precisions_chol, int64_t k, int64_t d,
+                                    double heaviside_factor) {
+    std::vector<double> blk((size_t)(k * d + k * d * d + k));
+    std::copy(means, means + k * d, blk.begin());
+    gmx_scaled_factors(weights, precisions_chol, k, d, heaviside_factor, blk.data() + k * d, blk.data() + k * d + k * d * d);
+    return blk;
 }
 
 #if defined(__HIPCC__)

@@ -456,10 +456,7 @@ int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_
                       std::to_string(kk) + ")");
             return EGX_ERR_UNSUPPORTED;
         }
-        sg.gmx.resize((size_t)(kk * d + kk * d * d + kk));
-        std::copy(sv.means, sv.means + kk * d, sg.gmx.begin());
-        gmx_scaled_factors(sv.weights, sv.precisions_chol, kk, d, sv.heaviside_factor, sg.gmx.data() + kk * d,
-                           sg.gmx.data() + kk * d + kk * d * d);
+        sg.gmx = gmx_pack(sv.weights, sv.means, sv.precisions_chol, kk, d, sv.heaviside_factor);
         for (int64_t c = 0; c < kk; c++)
             if (!std::isfinite(sg.gmx[(size_t)(kk * d + kk * d * d + c)])) {
                 set_error(name + ": cluster " + std::to_string(c) + " has no positive diagonal in its precision factor");

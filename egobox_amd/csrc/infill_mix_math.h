@@ -1,7 +1,8 @@
 // Recombination of a mixture of experts at ONE point (crates/moe/src/algorithm.rs): from the responsibilities p_e, their
 // x-derivatives p'_e and every expert's (mean, variance, grad mean, grad variance) to the four quantities of the mixture.
 // Plain C++17 behind a host / device macro (as infill_math.h): g++ compiles it for the CPU suite
-// (tests/c_host/infill_mix_math_test.cpp), k_infill_mix (kernels_infill.hip) runs the same text.
+// (tests/c_host/infill_mix_math_test.cpp), k_infill_mix (kernels_infill.hip) runs the same text, and the host fold of
+// egx_moe_predict_valvar(_gradients) (moe_fold.h) takes its mean and gradient terms from here.
 //
 //   smooth  (:411-423, 670-685, 691-783), the experts in index order:
 //       mean = sum p_e mu_e                     var = sum p_e^2 v_e
@@ -31,6 +32,7 @@ EGX_MX_HD int mix_first_max(int k, const double *p, int64_t sp) {
 }
 
 EGX_MX_HD double mix_mean_term(double p, double mu) { return p * mu; }
+// (the host fold's variance term is moe::fold_var_term, (p p) v: another association, other bits -- moe_fold.h)
 EGX_MX_HD double mix_var_term(double p, double v) { return (v * p) * p; }
 EGX_MX_HD double mix_grad_mean_term(double p, double dp, double mu, double gmu) { return gmu * p + dp * mu; }
 EGX_MX_HD double mix_grad_var_term(double p, double dp, double v, double gv) { return gv * (p * p) + ((2.0 * p) * dp) * v; }

@@ -12,7 +12,11 @@
 //
 // No floating-point atomics: a restart's numbers depend on n, D, k and its own start only -- not on R, not on its place in
 // the batch, not on the run.  A frozen restart (active[r] == 0) is skipped on entry by both kernels.
+//
+// ... and the fitted mixture's predict side: k_gmx_probas / k_gmx_probas_deriv, the responsibilities and their x-derivatives
+// at m points (egx_gmx_predict_probas(_derivatives), gmm_host.hip), one lane per point with the point text of gmx_point.h.
 #include "egx_internal.h"
+#include "gmx_point.h"
 
 namespace egx {
 
@@ -302,6 +306,55 @@ int launch_gmm_estep(hipStream_t s, const GmmLaunch &g) {
 int launch_gmm_mstep(hipStream_t s, const GmmLaunch &g, double reg_covar) {
     hipLaunchKernelGGL(k_gmm_mstep, dim3((unsigned)g.k, (unsigned)g.R), dim3(256), 0, s, g.n, g.D, g.DP, g.k, g.R, g.T, g.init,
                        reg_covar, g.active, g.part, g.lpn_part, g.means, g.prec, g.cst, g.weights, g.covs, g.lbst);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+// Responsibilities of a Gaussian mixture at m points (gmx_probas_point): one lane per point, the workgroup's 64 points staged
+// in LDS (row stride d | 1: a lane walks its own row), means, scaled factors and par read as wave-uniform operands.
+__global__ __launch_bounds__(64) void k_gmx_probas(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                  const double *__restrict__ means, const double *__restrict__ precs,
+                                                  const double *__restrict__ par, double *__restrict__ probas) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int64_t q0 = (int64_t)blockIdx.x * 64;
+    const int lane = threadIdx.x, ds = d | 1;
+    const int rows = (int)((m - q0 < 64) ? (m - q0) : 64);
+    for (int e = lane; e < rows * d; e += 64) {
+        const int i = e / d, j = e - i * d;
+        sm[i * ds + j] = xq[q0 * d + e];
+    }
+    __syncthreads();
+    if (lane >= rows) return;
+    gmx_probas_point(sm + lane * ds, d, k, means, precs, par, probas + (q0 + lane) * k);
+}
+
+// ... and their x-derivatives (gmx_probas_deriv_point), one lane per point: the lane's scratch (x, z, v': d each; u: k) in LDS.
+__global__ __launch_bounds__(64) void k_gmx_probas_deriv(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                        const double *__restrict__ means, const double *__restrict__ precs,
+                                                        const double *__restrict__ par, double *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int64_t q0 = (int64_t)blockIdx.x * 64;
+    const int lane = threadIdx.x, ds = d | 1, ks = k | 1;
+    const int rows = (int)((m - q0 < 64) ? (m - q0) : 64);
+    double *xs = sm, *zs = sm + 64 * ds, *vps = zs + 64 * ds, *us = vps + 64 * ds;
+    for (int e = lane; e < rows * d; e += 64) {
+        const int i = e / d, j = e - i * d;
+        xs[i * ds + j] = xq[q0 * d + e];
+    }
+    __syncthreads();
+    if (lane >= rows) return;
+    gmx_probas_deriv_point(xs + lane * ds, zs + lane * ds, vps + lane * ds, us + lane * ks, d, k, means, precs, par,
+                           out + (q0 + lane) * (int64_t)k * d);
+}
+
+int launch_gmx_probas(bool deriv, const double *xq, int64_t m, int d, int k, const double *blk, size_t lds, double *out) {
+    const double *precs = blk + (size_t)k * d, *par = precs + (size_t)k * d * d;
+    const dim3 grid((unsigned)((m + 63) / 64));
+    if (deriv && lds > 64 * 1024)
+        EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gmx_probas_deriv),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (deriv) hipLaunchKernelGGL(k_gmx_probas_deriv, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out);
+    else hipLaunchKernelGGL(k_gmx_probas, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

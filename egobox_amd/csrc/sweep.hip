@@ -11,14 +11,13 @@
 // aborted instead of blocking for ever on a peer that died.
 //
 // Reference seam: the rayon multistart of crates/gp/src/algorithm.rs:928-945 (independent likelihood evaluations,
-// arg-min reduce :942-945) and the serial expert loop of crates/moe/src/algorithm.rs:167-177.  Evaluations at
-// different theta share nothing but the replicated (4 MiB) training set, so there is no data-path collective besides
-// this gather.
+// arg-min reduce :942-945).  Evaluations at different theta share nothing but the replicated (4 MiB) training set, so
+// there is no data-path collective besides this gather.
 //
 // RCCL is bound at run time (dlopen of librccl.so.1 on the first sweep call): libegx_gp_hip.so itself keeps
 // libamdhip64 as its only link-time dependency, and single-GPU users never load the collective library.
 #include "gp_handle.h"
-#include "gmx_point.h"
+#include "sweep_internal.h"
 #include "sweep_shard.h"
 
 #include <dlfcn.h>
@@ -99,30 +98,6 @@ struct SweepCounters {
 };
 static_assert(std::atomic<int64_t>::is_always_lock_free, "the shared counters must be plain lock-free words");
 
-struct egx_sweep {
-    egx_gp *gp = nullptr;
-    int rank = 0, world = 1;
-    ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;
-    // staging of the all-gather, allocated once: kChunk doubles per rank
-    static constexpr int64_t kChunk = 262144;  // 2 MiB per rank: a 100 000-point mean + variance pair goes in one piece
-    egx::DevMem<double> d_send, d_recv;
-    egx::PinMem<double> h_send, h_recv;
-    std::mutex mu;
-    int64_t n_allgathers = 0;
-    // dynamic assignment
-    int dynamic = 0;
-    SweepCounters *counters = nullptr;  // shared memory (world > 1) or heap (world == 1)
-    bool counters_shared = false;
-    bool shm_transport = false;  // the all-gather goes through `counters->gather` instead of RCCL (test transport)
-    int64_t shm_generation = 0;
-    std::string shm_name;
-    int64_t call_seq = 0;
-    // balance of the last call
-    std::vector<int64_t> last_per_rank;
-    double last_eval_s = 0.0;
-    double timeout_s = 1800.0;
-};
 
 namespace {
 
@@ -244,52 +219,31 @@ static int sweep_allgather_doubles(egx_sweep *sw, const double *send, int64_t co
     return EGX_SUCCESS;
 }
 
-namespace egx {
-// Responsibilities of a Gaussian mixture at m points (GaussianMixture::predict_probas, crates/moe/src/gaussian_mixture.rs:
-// 114-121, 231-283): one lane per point, the workgroup's 64 points staged in LDS (row stride d | 1: a lane walks its own
-// row), the k x d x d scaled precision factors and the means read as wave-uniform operands.  par = [log w_c + log det_c -
-// 0.5 d ln 2 pi] (k).  q_c = || (x - mu_c) P_c ||^2; weighted log probability, the sum of the exponentials above
-// f64::MIN_10_EXP, its logarithm unless the sum is below epsilon (:236-251), exp of the difference (:119).
-__global__ __launch_bounds__(64) void k_gmx_probas(const double *__restrict__ xq, int64_t m, int d, int k,
-                                                  const double *__restrict__ means, const double *__restrict__ precs,
-                                                  const double *__restrict__ par, double *__restrict__ probas) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int64_t q0 = (int64_t)blockIdx.x * 64;
-    const int lane = threadIdx.x, ds = d | 1;
-    const int rows = (int)((m - q0 < 64) ? (m - q0) : 64);
-    for (int e = lane; e < rows * d; e += 64) {
-        const int i = e / d, j = e - i * d;
-        sm[i * ds + j] = xq[q0 * d + e];
+int egx::sweep_exchange_status(egx_sweep *sw, const char *who, int local_rc, const std::string &local_msg, std::vector<double> &part,
+                               std::vector<double> &all) {
+    const int world = sw ? sw->world : 1;
+    if (sw) {
+        all.resize(part.size() * (size_t)world);
+        const int coll_rc = sweep_allgather_doubles(sw, part.data(), (int64_t)part.size(), all.data());
+        if (coll_rc) {
+            if (local_rc) set_error(local_msg + " (and the collective failed: " + last_error_string() + ")");
+            return local_rc ? local_rc : coll_rc;
+        }
+    } else {
+        all.swap(part);
     }
-    __syncthreads();
-    if (lane >= rows) return;
-    gmx_probas_point(sm + lane * ds, d, k, means, precs, par, probas + (q0 + lane) * k);
+    if (local_rc) {
+        set_error(local_msg);
+        return local_rc;
+    }
+    const SweepFailure f = sweep_first_failure(all.data(), world, all.size() / (size_t)world);
+    if (f.rank >= 0) {
+        set_error(std::string(who) + ": rank " + std::to_string(f.rank) + " failed with egx_rc " + std::to_string(f.rc));
+        return EGX_ERR_PEER;
+    }
+    return EGX_SUCCESS;
 }
 
-// GaussianMixture::predict_probas_derivatives (crates/moe/src/gaussian_mixture.rs:127-170), one lane per point:
-//   u_c = w_c pdf_c(x),  v = sum_c u_c,  deriv_c = (x - mu_c) precisions_c / hf,  u'_c = -deriv_c u_c,  v' = sum_c u'_c
-//   d p_c / d x = (u'_c v - u_c v') / v^2
-// With the scaled factor P' = precisions_chol_c hf^-1/2 (what pdfs() itself uses, :253-283): z = (x - mu_c) P' gives both the
-// quadratic form |z|^2 of the pdf and deriv_c = z P'^T (precisions = P P^T, :208-217).  Pass A writes u'_c to the output and
-// accumulates v, v'; pass B finishes the output in place.  Per-lane scratch (x, z, v': d each; u: k) lives in LDS.
-__global__ __launch_bounds__(64) void k_gmx_probas_deriv(const double *__restrict__ xq, int64_t m, int d, int k,
-                                                        const double *__restrict__ means, const double *__restrict__ precs,
-                                                        const double *__restrict__ par, double *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int64_t q0 = (int64_t)blockIdx.x * 64;
-    const int lane = threadIdx.x, ds = d | 1, ks = k | 1;
-    const int rows = (int)((m - q0 < 64) ? (m - q0) : 64);
-    double *xs = sm, *zs = sm + 64 * ds, *vps = zs + 64 * ds, *us = vps + 64 * ds;
-    for (int e = lane; e < rows * d; e += 64) {
-        const int i = e / d, j = e - i * d;
-        xs[i * ds + j] = xq[q0 * d + e];
-    }
-    __syncthreads();
-    if (lane >= rows) return;
-    gmx_probas_deriv_point(xs + lane * ds, zs + lane * ds, vps + lane * ds, us + lane * ks, d, k, means, precs, par,
-                           out + (q0 + lane) * (int64_t)k * d);
-}
-}  // namespace egx
 
 extern "C" {
 
@@ -576,189 +530,6 @@ int32_t egx_sweep_allgather(egx_sweep *sw, const double *send, int64_t count, do
     return rc;
 }
 
-// ---- mixture-of-experts recombination (BASELINE config 5: one expert per GPU) -----------------------
-// GpMixture::predict_smooth / predict_var_smooth (crates/moe/src/algorithm.rs:411-423, 670-685): val = sum_e p_e y_e,
-// var = sum_e p_e^2 v_e over ALL points; predict_hard / predict_var_hard (:879-935): every point is answered by the expert
-// of its cluster, argmax_e p_e.  The reference calls the expert once per ROW in hard mode (a full n^2 triangular solve per
-// point for the variance); here the points are routed once and every expert gets ONE batched call on its subset.
-// Multi-rank: every rank owns some of the experts, forms the partial sums of its own and ONE all-gather of the partial
-// (val, var) vectors + a sum in rank order (the same bits on every rank) replaces the reference's fold over experts.
-int32_t egx_moe_predict_valvar(egx_sweep *sw, egx_gp *const *experts, const int32_t *expert_ids, int64_t n_local,
-                               int64_t n_experts, const double *probas, const double *xq, int64_t m, int64_t d,
-                               int32_t smooth, double *val, double *var) {
-    if (n_local < 0 || n_experts < 1 || m < 0 || d < 1 || (m > 0 && (!probas || !xq)) || (n_local > 0 && (!experts || !expert_ids)) ||
-        (!val && !var)) {
-        set_error("egx_moe_predict_valvar: bad arguments");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (!sw && n_local != n_experts) {
-        set_error("egx_moe_predict_valvar: without a sweep handle (single process) every expert must be local");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (m == 0) return EGX_SUCCESS;
-    // ---- local part: failures are carried into the collective (a rank that left early would hang the others)
-    int local_rc = EGX_SUCCESS;
-    std::string local_msg;
-    std::vector<double> part((size_t)2 * m + 1, 0.0);  // [status | val (m) | var (m)]
-    double *pv = part.data() + 1, *pw = pv + m;
-    for (int64_t e = 0; e < n_local && !local_rc; e++)
-        if (!experts[e] || expert_ids[e] < 0 || expert_ids[e] >= n_experts) {
-            local_msg = "egx_moe_predict_valvar: NULL expert handle or expert id out of range";
-            local_rc = EGX_ERR_INVALID_VALUE;
-        }
-    std::vector<int32_t> cluster;
-    if (!smooth && !local_rc) {  // gmx.predict: first maximum of the responsibilities (ndarray / numpy argmax)
-        cluster.resize(m);
-        for (int64_t a = 0; a < m; a++) {
-            const double *pa = probas + a * n_experts;
-            int32_t best = 0;
-            for (int32_t j = 1; j < n_experts; j++)
-                if (pa[j] > pa[best]) best = j;
-            cluster[a] = best;
-        }
-    }
-    if (!local_rc) {
-        // experts of one rank: up to two in flight (each handle has its own streams: one's launch gaps hide in the other)
-        std::atomic<int64_t> next{0};
-        std::mutex acc_mu;
-        auto worker = [&]() {
-            std::vector<double> xs, ys, vs;
-            std::vector<int64_t> idx;
-            for (;;) {
-                const int64_t e = next.fetch_add(1);
-                if (e >= n_local) return;
-                {
-                    std::lock_guard<std::mutex> l(acc_mu);
-                    if (local_rc) return;
-                }
-                const int32_t g = expert_ids[e];
-                const double *xin = xq;
-                int64_t me = m;
-                if (!smooth) {
-                    idx.clear();
-                    for (int64_t a = 0; a < m; a++)
-                        if (cluster[a] == g) idx.push_back(a);
-                    me = (int64_t)idx.size();
-                    if (me == 0) continue;
-                    xs.resize((size_t)me * d);
-                    for (int64_t i = 0; i < me; i++) std::memcpy(&xs[(size_t)i * d], xq + idx[i] * d, sizeof(double) * d);
-                    xin = xs.data();
-                }
-                ys.resize(me);
-                vs.resize(me);
-                int rc;
-                if (val && var) rc = egx_gp_predict_valvar(experts[e], xin, me, ys.data(), vs.data());
-                else if (val) rc = egx_gp_predict(experts[e], xin, me, ys.data());
-                else rc = egx_gp_predict_var(experts[e], xin, me, vs.data());
-                std::lock_guard<std::mutex> l(acc_mu);
-                if (rc) {
-                    if (!local_rc) {
-                        local_rc = rc;
-                        local_msg = last_error_string();
-                    }
-                    return;
-                }
-                if (smooth) {
-                    for (int64_t a = 0; a < m; a++) {
-                        const double p = probas[a * n_experts + g];
-                        if (val) pv[a] += p * ys[a];
-                        if (var) pw[a] += p * p * vs[a];
-                    }
-                } else {
-                    for (int64_t i = 0; i < me; i++) {
-                        if (val) pv[idx[i]] = ys[i];
-                        if (var) pw[idx[i]] = vs[i];
-                    }
-                }
-            }
-        };
-        // (the accumulation of the smooth sums is ordered by completion, not by expert: addition of <= n_local terms per
-        //  point in a run-dependent order would not be reproducible to the bit -- so with two workers each owns its own
-        //  partial vectors and they are added in worker order below)
-        if (n_local > 1 && smooth) {
-            std::vector<double> part2((size_t)2 * m, 0.0);
-            double *pv0 = pv, *pw0 = pw;
-            // worker A takes the even local experts into part, worker B the odd ones into part2
-            auto fixed_worker = [&](int64_t first, double *tv, double *tw) {
-                std::vector<double> ys(m), vs(m);
-                for (int64_t e = first; e < n_local; e += 2) {
-                    {
-                        std::lock_guard<std::mutex> l(acc_mu);
-                        if (local_rc) return;
-                    }
-                    int rc;
-                    if (val && var) rc = egx_gp_predict_valvar(experts[e], xq, m, ys.data(), vs.data());
-                    else if (val) rc = egx_gp_predict(experts[e], xq, m, ys.data());
-                    else rc = egx_gp_predict_var(experts[e], xq, m, vs.data());
-                    if (rc) {
-                        std::lock_guard<std::mutex> l(acc_mu);
-                        if (!local_rc) {
-                            local_rc = rc;
-                            local_msg = last_error_string();
-                        }
-                        return;
-                    }
-                    const int32_t g = expert_ids[e];
-                    for (int64_t a = 0; a < m; a++) {
-                        const double p = probas[a * n_experts + g];
-                        if (val) tv[a] += p * ys[a];
-                        if (var) tw[a] += p * p * vs[a];
-                    }
-                }
-            };
-            std::thread tb(fixed_worker, (int64_t)1, part2.data(), part2.data() + m);
-            fixed_worker(0, pv0, pw0);
-            tb.join();
-            for (int64_t a = 0; a < m; a++) {
-                pv0[a] += part2[a];
-                pw0[a] += part2[(size_t)m + a];
-            }
-        } else if (n_local > 1) {
-            std::thread tb(worker);  // hard: disjoint subsets, no sums: completion order does not matter
-            worker();
-            tb.join();
-        } else {
-            worker();
-        }
-    }
-    part[0] = local_rc ? -(double)(kSweepPoison + local_rc) : 0.0;
-    // ---- the collective (multi-rank) and the sum over ranks, in rank order
-    const int world = sw ? sw->world : 1;
-    std::vector<double> all;
-    const double *src = part.data();
-    if (sw) {
-        std::lock_guard<std::mutex> lock(sw->mu);
-        all.resize(part.size() * (size_t)world);
-        (void)set_device(sw->gp);
-        const int coll_rc = sweep_allgather_doubles(sw, part.data(), (int64_t)part.size(), all.data());
-        if (coll_rc) {
-            if (local_rc) set_error(local_msg + " (and the collective failed: " + last_error_string() + ")");
-            return local_rc ? local_rc : coll_rc;
-        }
-        src = all.data();
-    }
-    if (local_rc) {
-        set_error(local_msg);
-        return local_rc;
-    }
-    for (int r = 0; r < world; r++)
-        if (src[(size_t)r * part.size()] != 0.0) {
-            set_error("egx_moe_predict_valvar: rank " + std::to_string(r) + " failed with egx_rc " +
-                      std::to_string((int)(-src[(size_t)r * part.size()]) - kSweepPoison));
-            return EGX_ERR_PEER;
-        }
-    for (int64_t a = 0; a < m; a++) {
-        double sv = 0.0, sw2 = 0.0;
-        for (int r = 0; r < world; r++) {
-            const double *pr = src + (size_t)r * part.size() + 1;
-            sv += pr[a];
-            sw2 += pr[m + a];
-        }
-        if (val) val[a] = sv;
-        if (var) var[a] = sw2;
-    }
-    return EGX_SUCCESS;
-}
 
 // ---- tuned fit over the ranks of a sweep (SURVEY 8e x 8f rank 2) --------------------------------------------------
 // GpValidParams::fit with ThetaTuning::Full (crates/gp/src/algorithm.rs:873-960): the reference runs its n_start + 1 COBYLA
@@ -787,7 +558,7 @@ int32_t egx_sweep_fit(egx_sweep *sw, const double *theta0s, int64_t n_starts, co
     // payload: [status | per start: objective, evaluations, minimiser (h)], NaN objective for the starts of other ranks
     const size_t per = (size_t)h + 2;
     std::vector<double> part(1 + (size_t)n_starts * per, std::numeric_limits<double>::quiet_NaN());
-    part[0] = local_rc ? -(double)(kSweepPoison + local_rc) : 0.0;
+    part[0] = sweep_status_word(local_rc);
     if (!local_rc)
         for (int64_t s = sw->rank; s < n_starts; s += world) {
             double *q = part.data() + 1 + (size_t)s * per;
@@ -795,25 +566,9 @@ int32_t egx_sweep_fit(egx_sweep *sw, const double *theta0s, int64_t n_starts, co
             q[1] = (double)results[(size_t)s].evals;
             for (int i = 0; i < h; i++) q[2 + i] = results[(size_t)s].x[(size_t)i];
         }
-    std::vector<double> all(part.size() * (size_t)world);
-    {
-        (void)set_device(gp);
-        const int coll_rc = sweep_allgather_doubles(sw, part.data(), (int64_t)part.size(), all.data());
-        if (coll_rc) {
-            if (local_rc) set_error(local_msg + " (and the collective failed: " + last_error_string() + ")");
-            return local_rc ? local_rc : coll_rc;
-        }
-    }
-    if (local_rc) {
-        set_error(local_msg);
-        return local_rc;
-    }
-    for (int r = 0; r < world; r++)
-        if (all[(size_t)r * part.size()] != 0.0) {
-            set_error("egx_sweep_fit: rank " + std::to_string(r) + " failed with egx_rc " +
-                      std::to_string((int)(-all[(size_t)r * part.size()]) - kSweepPoison));
-            return EGX_ERR_PEER;
-        }
+    std::vector<double> all;
+    (void)set_device(gp);
+    EGX_RC(sweep_exchange_status(sw, "egx_sweep_fit", local_rc, local_msg, part, all));
     results.assign((size_t)n_starts, StartResult{std::numeric_limits<double>::infinity(), std::vector<double>(h, 0.0), 0});
     for (int64_t s = 0; s < n_starts; s++) {
         const double *q = all.data() + (size_t)(s % world) * part.size() + 1 + (size_t)s * per;
@@ -822,300 +577,6 @@ int32_t egx_sweep_fit(egx_sweep *sw, const double *theta0s, int64_t n_starts, co
         results[(size_t)s].x.assign(q + 2, q + 2 + h);
     }
     return fit_reduce_finalize(gp, theta0s, active, theta0s, results, n_evals_out);
-}
-
-// ---- Gaussian mixture responsibilities ----------------------------------------------------------
-// precisions_chol[c] = (chol(cov_c)^-1)^T, crates/moe/src/gaussian_mixture.rs:182-205: d x d host arithmetic.
-int32_t egx_gmx_precisions_chol(const double *covariances, int64_t k, int64_t d, double *precisions_chol) {
-    if (!covariances || !precisions_chol || k < 1 || d < 1) {
-        set_error("egx_gmx_precisions_chol: bad arguments");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    std::vector<double> L((size_t)d * d), Li((size_t)d * d);
-    for (int64_t c = 0; c < k; c++) {
-        const double *A = covariances + (size_t)c * d * d;
-        std::fill(L.begin(), L.end(), 0.0);
-        for (int64_t j = 0; j < d; j++) {  // lower Cholesky factor, column by column
-            double dj = A[j * d + j];
-            for (int64_t l = 0; l < j; l++) dj -= L[j * d + l] * L[j * d + l];
-            if (!(dj > 0.0) || !std::isfinite(dj)) {
-                set_error("egx_gmx_precisions_chol: covariance " + std::to_string((long long)c) + " is not positive definite");
-                return EGX_ERR_LINALG;
-            }
-            L[j * d + j] = std::sqrt(dj);
-            for (int64_t i = j + 1; i < d; i++) {
-                double v = A[i * d + j];
-                for (int64_t l = 0; l < j; l++) v -= L[i * d + l] * L[j * d + l];
-                L[i * d + j] = v / L[j * d + j];
-            }
-        }
-        std::fill(Li.begin(), Li.end(), 0.0);  // L^-1 by forward substitution on the identity
-        for (int64_t col = 0; col < d; col++)
-            for (int64_t i = col; i < d; i++) {
-                double v = (i == col) ? 1.0 : 0.0;
-                for (int64_t l = col; l < i; l++) v -= L[i * d + l] * Li[l * d + col];
-                Li[i * d + col] = v / L[i * d + i];
-            }
-        double *out = precisions_chol + (size_t)c * d * d;
-        for (int64_t i = 0; i < d; i++)
-            for (int64_t j = 0; j < d; j++) out[i * d + j] = Li[j * d + i];  // transposed: upper triangular
-    }
-    return EGX_SUCCESS;
-}
-
-int32_t egx_gmx_predict_probas(int32_t device, const double *weights, const double *means, const double *precisions_chol,
-                               int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m, double *probas) {
-    if (!weights || !means || !precisions_chol || k < 1 || d < 1 || d > 4096 || m < 0 || (m > 0 && (!xq || !probas)) ||
-        !(heaviside_factor > 0.0)) {
-        set_error("egx_gmx_predict_probas: bad arguments");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (m == 0) return EGX_SUCCESS;
-    if (k == 1) {  // gaussian_mixture.rs:115-116
-        for (int64_t a = 0; a < m; a++) probas[a] = 1.0;
-        return EGX_SUCCESS;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        set_error("egx_gmx_predict_probas: no HIP device");
-        return EGX_ERR_NO_DEVICE;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;  // the calling thread's current device
-    if (device >= ndev) {
-        set_error("egx_gmx_predict_probas: device out of range");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    EGX_HIP_CHECK(hipSetDevice(device));
-    // scaled factors and the per-cluster constant (:105-110, 253-283): precs = P * hf^-0.5, log det = sum log diag(precs)
-    std::vector<double> precs((size_t)k * d * d), par(k);
-    egx::gmx_scaled_factors(weights, precisions_chol, k, d, heaviside_factor, precs.data(), par.data());
-    egx::DevBuf d_x, d_mu, d_p, d_par, d_out;
-    EGX_RC(d_x.alloc((size_t)m * d));
-    EGX_RC(d_mu.alloc((size_t)k * d));
-    EGX_RC(d_p.alloc(precs.size()));
-    EGX_RC(d_par.alloc(k));
-    EGX_RC(d_out.alloc((size_t)m * k));
-    EGX_HIP_CHECK(hipMemcpy(d_x.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemcpy(d_mu.p, means, sizeof(double) * (size_t)k * d, hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemcpy(d_p.p, precs.data(), sizeof(double) * precs.size(), hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemcpy(d_par.p, par.data(), sizeof(double) * k, hipMemcpyHostToDevice));
-    const size_t lds = sizeof(double) * 64 * (size_t)(d | 1);
-    if (lds > 160 * 1024) {
-        set_error("egx_gmx_predict_probas: d too large for one workgroup's LDS");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    hipLaunchKernelGGL(egx::k_gmx_probas, dim3((unsigned)((m + 63) / 64)), dim3(64), lds, 0, d_x.p, m, (int)d, (int)k, d_mu.p,
-                       d_p.p, d_par.p, d_out.p);
-    EGX_HIP_CHECK(hipGetLastError());
-    EGX_HIP_CHECK(hipMemcpy(probas, d_out.p, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost));
-    return EGX_SUCCESS;
-}
-
-int32_t egx_gmx_predict_probas_derivatives(int32_t device, const double *weights, const double *means,
-                                           const double *precisions_chol, int64_t k, int64_t d, double heaviside_factor,
-                                           const double *xq, int64_t m, double *dprobas) {
-    if (!weights || !means || !precisions_chol || k < 1 || d < 1 || m < 0 || (m > 0 && (!xq || !dprobas)) ||
-        !(heaviside_factor > 0.0)) {
-        set_error("egx_gmx_predict_probas_derivatives: bad arguments");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (m == 0) return EGX_SUCCESS;
-    const size_t lds = sizeof(double) * 64 * (size_t)(3 * (d | 1) + (k | 1));
-    if (lds > 160 * 1024) {
-        set_error("egx_gmx_predict_probas_derivatives: d / k too large for one workgroup's LDS (3 d + k <= 320)");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        set_error("egx_gmx_predict_probas_derivatives: no HIP device");
-        return EGX_ERR_NO_DEVICE;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= ndev) {
-        set_error("egx_gmx_predict_probas_derivatives: device out of range");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    EGX_HIP_CHECK(hipSetDevice(device));
-    std::vector<double> precs((size_t)k * d * d), par(k);
-    egx::gmx_scaled_factors(weights, precisions_chol, k, d, heaviside_factor, precs.data(), par.data());
-    egx::DevBuf d_x, d_mu, d_p, d_par, d_out;
-    EGX_RC(d_x.alloc((size_t)m * d));
-    EGX_RC(d_mu.alloc((size_t)k * d));
-    EGX_RC(d_p.alloc(precs.size()));
-    EGX_RC(d_par.alloc(k));
-    EGX_RC(d_out.alloc((size_t)m * k * d));
-    EGX_HIP_CHECK(hipMemcpy(d_x.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemcpy(d_mu.p, means, sizeof(double) * (size_t)k * d, hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemcpy(d_p.p, precs.data(), sizeof(double) * precs.size(), hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemcpy(d_par.p, par.data(), sizeof(double) * k, hipMemcpyHostToDevice));
-    if (lds > 64 * 1024)
-        EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&egx::k_gmx_probas_deriv),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(egx::k_gmx_probas_deriv, dim3((unsigned)((m + 63) / 64)), dim3(64), lds, 0, d_x.p, m, (int)d, (int)k,
-                       d_mu.p, d_p.p, d_par.p, d_out.p);
-    EGX_HIP_CHECK(hipGetLastError());
-    EGX_HIP_CHECK(hipMemcpy(dprobas, d_out.p, sizeof(double) * (size_t)m * k * d, hipMemcpyDeviceToHost));
-    return EGX_SUCCESS;
-}
-
-// GpMixture::predict_gradients_smooth / predict_var_gradients_smooth (crates/moe/src/algorithm.rs:691-783):
-//     d val / dx = sum_e p_e grad y_e + p'_e y_e ,   d var / dx = sum_e p_e^2 grad v_e + 2 p_e p'_e v_e
-// and predict_gradients_hard / predict_var_gradients_hard (:942-1010): the gradient of the expert of argmax_e p_e.  The
-// reference calls every expert once per ROW; here every expert gets ONE batched call per quantity on its points (all of
-// them in smooth mode, its cluster's in hard mode).  Sharded exactly like egx_moe_predict_valvar: a rank's partial
-// (m x d) sums over ITS experts -- two experts in flight, even / odd local experts into separate partial sums that are
-// added in a fixed order -- one all-gather, the sum over ranks in rank order (the same bits on every rank).
-int32_t egx_moe_predict_valvar_gradients(egx_sweep *sw, egx_gp *const *experts, const int32_t *expert_ids, int64_t n_local,
-                                         int64_t n_experts, const double *probas, const double *dprobas, const double *xq,
-                                         int64_t m, int64_t d, int32_t smooth, double *grad_val, double *grad_var) {
-    if (n_local < 0 || n_experts < 1 || m < 0 || d < 1 || (m > 0 && (!probas || !xq)) || (n_local > 0 && (!experts || !expert_ids)) ||
-        (!grad_val && !grad_var) || (smooth && n_experts > 1 && m > 0 && !dprobas)) {
-        set_error("egx_moe_predict_valvar_gradients: bad arguments (the smooth recombination of more than one expert needs dprobas)");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (!sw && n_local != n_experts) {
-        set_error("egx_moe_predict_valvar_gradients: without a sweep handle (single process) every expert must be local");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    if (m == 0) return EGX_SUCCESS;
-    const size_t md = (size_t)m * d;
-    int local_rc = EGX_SUCCESS;
-    std::string local_msg;
-    std::vector<double> part(2 * md + 1, 0.0);  // [status | grad val (m x d) | grad var (m x d)]
-    for (int64_t e = 0; e < n_local && !local_rc; e++)
-        if (!experts[e] || expert_ids[e] < 0 || expert_ids[e] >= n_experts) {
-            local_msg = "egx_moe_predict_valvar_gradients: NULL expert handle or expert id out of range";
-            local_rc = EGX_ERR_INVALID_VALUE;
-        }
-    std::vector<int32_t> cluster;
-    if (!smooth && !local_rc) {
-        cluster.resize(m);
-        for (int64_t a = 0; a < m; a++) {
-            const double *pa = probas + a * n_experts;
-            int32_t best = 0;
-            for (int32_t j = 1; j < n_experts; j++)
-                if (pa[j] > pa[best]) best = j;
-            cluster[a] = best;
-        }
-    }
-    if (!local_rc) {
-        std::mutex acc_mu;
-        // worker w takes the local experts w, w + 2, ... into its own partial sums (tv, tw)
-        auto worker = [&](int64_t first, double *tv, double *tw) {
-            std::vector<double> xs, gy, gv, ys, vs;
-            std::vector<int64_t> idx;
-            for (int64_t e = first; e < n_local; e += 2) {
-                {
-                    std::lock_guard<std::mutex> l(acc_mu);
-                    if (local_rc) return;
-                }
-                const int32_t g = expert_ids[e];
-                const double *xin = xq;
-                int64_t me = m;
-                if (!smooth) {
-                    idx.clear();
-                    for (int64_t a = 0; a < m; a++)
-                        if (cluster[a] == g) idx.push_back(a);
-                    me = (int64_t)idx.size();
-                    if (me == 0) continue;
-                    xs.resize((size_t)me * d);
-                    for (int64_t i = 0; i < me; i++) std::memcpy(&xs[(size_t)i * d], xq + idx[i] * d, sizeof(double) * d);
-                    xin = xs.data();
-                }
-                int rc = EGX_SUCCESS;
-                if (grad_val) gy.resize((size_t)me * d);
-                if (grad_var) gv.resize((size_t)me * d);
-                if (grad_val && grad_var) rc = egx_gp_predict_valvar_gradients(experts[e], xin, me, gy.data(), gv.data());
-                else if (grad_val) rc = egx_gp_predict_gradients(experts[e], xin, me, gy.data());
-                else rc = egx_gp_predict_var_gradients(experts[e], xin, me, gv.data());
-                const bool need_pp = smooth && n_experts > 1;  // the p' terms need the experts' values too
-                if (!rc && need_pp) {
-                    if (grad_val) ys.resize(me);
-                    if (grad_var) vs.resize(me);
-                    if (grad_val && grad_var) rc = egx_gp_predict_valvar(experts[e], xin, me, ys.data(), vs.data());
-                    else if (grad_val) rc = egx_gp_predict(experts[e], xin, me, ys.data());
-                    else rc = egx_gp_predict_var(experts[e], xin, me, vs.data());
-                }
-                if (rc) {
-                    std::lock_guard<std::mutex> l(acc_mu);
-                    if (!local_rc) {
-                        local_rc = rc;
-                        local_msg = last_error_string();
-                    }
-                    return;
-                }
-                if (smooth) {
-                    for (int64_t a = 0; a < m; a++) {
-                        const double p = probas[a * n_experts + g];
-                        const double *pp = need_pp ? dprobas + ((size_t)a * n_experts + g) * d : nullptr;
-                        for (int64_t j = 0; j < d; j++) {
-                            if (grad_val) tv[a * d + j] += gy[a * d + j] * p + (pp ? pp[j] * ys[a] : 0.0);
-                            if (grad_var) tw[a * d + j] += gv[a * d + j] * (p * p) + (pp ? 2.0 * p * pp[j] * vs[a] : 0.0);
-                        }
-                    }
-                } else {
-                    for (int64_t i = 0; i < me; i++) {  // disjoint rows: no sums
-                        if (grad_val) std::memcpy(tv + idx[i] * d, &gy[(size_t)i * d], sizeof(double) * d);
-                        if (grad_var) std::memcpy(tw + idx[i] * d, &gv[(size_t)i * d], sizeof(double) * d);
-                    }
-                }
-            }
-        };
-        double *pv = part.data() + 1, *pw = pv + md;
-        if (n_local > 1) {
-            std::vector<double> part2(smooth ? 2 * md : 0, 0.0);
-            // smooth: worker B accumulates into its own vectors (a fixed order of additions); hard: rows are disjoint
-            double *bv = smooth ? part2.data() : pv, *bw = smooth ? part2.data() + md : pw;
-            std::thread tb(worker, (int64_t)1, bv, bw);
-            worker(0, pv, pw);
-            tb.join();
-            if (smooth)
-                for (size_t i = 0; i < md; i++) {
-                    pv[i] += part2[i];
-                    pw[i] += part2[md + i];
-                }
-        } else {
-            worker(0, pv, pw);
-        }
-    }
-    part[0] = local_rc ? -(double)(kSweepPoison + local_rc) : 0.0;
-    const int world = sw ? sw->world : 1;
-    std::vector<double> all;
-    const double *src = part.data();
-    if (sw) {
-        std::lock_guard<std::mutex> lock(sw->mu);
-        all.resize(part.size() * (size_t)world);
-        (void)set_device(sw->gp);
-        const int coll_rc = sweep_allgather_doubles(sw, part.data(), (int64_t)part.size(), all.data());
-        if (coll_rc) {
-            if (local_rc) set_error(local_msg + " (and the collective failed: " + last_error_string() + ")");
-            return local_rc ? local_rc : coll_rc;
-        }
-        src = all.data();
-    }
-    if (local_rc) {
-        set_error(local_msg);
-        return local_rc;
-    }
-    for (int r = 0; r < world; r++)
-        if (src[(size_t)r * part.size()] != 0.0) {
-            set_error("egx_moe_predict_valvar_gradients: rank " + std::to_string(r) + " failed with egx_rc " +
-                      std::to_string((int)(-src[(size_t)r * part.size()]) - kSweepPoison));
-            return EGX_ERR_PEER;
-        }
-    for (size_t i = 0; i < md; i++) {
-        double sv = 0.0, sw2 = 0.0;
-        for (int r = 0; r < world; r++) {
-            const double *pr = src + (size_t)r * part.size() + 1;
-            sv += pr[i];
-            sw2 += pr[md + i];
-        }
-        if (grad_val) grad_val[i] = sv;
-        if (grad_var) grad_var[i] = sw2;
-    }
-    return EGX_SUCCESS;
 }
 
 }  // extern "C"

@@ -93,4 +93,21 @@ inline SweepVerdict sweep_unpack(const double *recv, int64_t k, int world, doubl
     return v;
 }
 
+// ---- ONE status word in front of a payload (egx_sweep_fit, the mixture's fold: moe_fold.h) ----
+// 0.0 for a rank whose local work succeeded, else -(kSweepPoison + egx_rc); `world` payloads of `len` doubles each
+inline double sweep_status_word(int rc) { return rc ? -(double)(kSweepPoison + rc) : 0.0; }
+struct SweepFailure {
+    int rank = -1;  // lowest rank whose status word is set (-1: none)
+    int rc = 0;     // its egx_rc
+};
+inline SweepFailure sweep_first_failure(const double *all, int world, size_t len) {
+    SweepFailure f;
+    for (int r = 0; r < world && f.rank < 0; r++)
+        if (all[(size_t)r * len] != 0.0) {
+            f.rank = r;
+            f.rc = (int)(-all[(size_t)r * len]) - kSweepPoison;
+        }
+    return f;
+}
+
 }  // namespace egx

@@ -81,6 +81,30 @@ int main() {
         const SweepVerdict v = sweep_unpack(g.data(), 4, 2, lk, st, 5);
         if (v.duplicate != 1 || v.missing != 3) { printf("duplicate / missing not detected\n"); return 1; }
     }
-    printf("OK %d (world, k, assignment, failed rank) combinations\n", checked);
+    // the status word in front of a payload (egx_sweep_fit, the mixture's fold): 0.0 for success, else -(kSweepPoison + rc),
+    // and the lowest failed rank among `world` payloads of stride `len` -- every subset of failing ranks (first, last, several)
+    int words = 0;
+    if (sweep_status_word(0) != 0.0 || std::signbit(sweep_status_word(0))) { printf("status word of success\n"); return 1; }
+    for (int world = 1; world <= 8; world++)
+        for (size_t len : {(size_t)1, (size_t)2, (size_t)131})
+            for (int rc : {1, 3, 8, 9, kSweepPoison - 1, kSweepPoison, kSweepPoison + 1, 3 * kSweepPoison})
+                for (unsigned failing = 0; failing < (1u << world); failing++) {
+                    std::vector<double> all(len * world, 7.5);  // payload values (negative ones included) are not status
+                    int lowest = -1;
+                    for (int r = 0; r < world; r++) {
+                        const bool bad = (failing >> r) & 1u;
+                        all[r * len] = sweep_status_word(bad ? rc + r : 0);  // every failed rank its own rc
+                        if (len > 1) all[r * len + 1] = -(double)(kSweepPoison + 2);
+                        if (bad && lowest < 0) lowest = r;
+                        if (bad && all[r * len] != -(double)(kSweepPoison + rc + r)) { printf("status word of rc %d\n", rc + r); return 1; }
+                    }
+                    const SweepFailure f = sweep_first_failure(all.data(), world, len);
+                    if (f.rank != lowest || (lowest >= 0 && f.rc != rc + lowest) || (lowest < 0 && f.rc != 0)) {
+                        printf("world %d len %zu rc %d failing %x: rank %d rc %d\n", world, len, rc, failing, f.rank, f.rc);
+                        return 1;
+                    }
+                    words++;
+                }
+    printf("OK %d (world, k, assignment, failed rank) combinations, %d status-word gathers\n", checked, words);
     return 0;
 }

@@ -167,3 +167,22 @@ def test_precisions_chol_through_the_c_abi():
     bad = np.array([[[1.0, 2.0], [2.0, 1.0]]])
     with pytest.raises(L.LinalgError):
         L.check(lib.egx_gmx_precisions_chol(L.dptr(bad), 1, 2, L.dptr(np.empty((1, 2, 2)))))
+
+
+@pytest.mark.parametrize("sanitizer", ["address,undefined", "thread"])
+def test_sharded_fold_with_closed_form_experts(tmp_path, sanitizer):
+    """The fold of egx_moe_predict_valvar(_gradients) (csrc/moe_fold.h) with closed-form experts, as a stand-alone program
+    (tests/c_host/moe_fold_test.cpp) under ASan + UBSan and under TSan: the order of additions, hard-mode routing, NULL
+    outputs, a failing expert, two and three simulated ranks."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "moe_fold_test"
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-pthread", "-fsanitize=" + sanitizer,
+                            os.path.join(root, "tests", "c_host", "moe_fold_test.cpp"), "-o", str(exe)],
+                           capture_output=True, text=True)
+    if build.returncode != 0 and sanitizer == "thread" and "tsan" in build.stderr:
+        pytest.skip("no ThreadSanitizer runtime to link against: " + build.stderr.strip().splitlines()[-1])
+    assert build.returncode == 0, build.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), (out.stdout, out.stderr)
