@@ -13,12 +13,13 @@ _lib.load()  # fail loudly at import when the HIP library is missing
 from .gp import (AbsoluteExponentialCorr, ConstantMean, GaussianProcess, GpHandle, GpParams, Kriging,  # noqa: E402
                  LinearMean, Matern32Corr, Matern52Corr, QuadraticMean, SquaredExponentialCorr, ThetaTuning,
                  chain_stats, corr_matrix, cross_corr, finalize_multi, fit_multi, likelihood_multi, mfma_probe, normalize, pool_stats, potrf,
-                 regression_basis, set_tuning, trim)
+                 predict_valvar_multi, regression_basis, set_tuning, trim)
 from .gpx import CorrelationSpec, GpMix, Gpx, Recombination, RegressionSpec  # noqa: E402
 from .multistart import prepare_multistart, theta_sweep_candidates  # noqa: E402
 from .sgp import (Inducings, ParamTuning, SgpHandle, SgpParams, SparseGaussianProcess, SparseGpMix, SparseGpx,  # noqa: E402
                   SparseMethod)
-from . import infill, moe, workload  # noqa: E402
+from . import cv, infill, moe, workload  # noqa: E402
+from .cv import GpMetrics, IaeAlphaPlotData, cross_validate, fold_indices  # noqa: E402
 from .moe import GaussianMixture, GpMixture, GpMixtureParams  # noqa: E402
 from .infill import EI, LOG_EI, WB2, WB2S, InfillObjective  # noqa: E402
 from .sweep import Sweep, best_candidate, rendezvous_sweep, shard_indices, sweep_likelihood  # noqa: E402

@@ -121,6 +121,7 @@ SIGNATURES = [
     ("egx_gp_predict", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_var", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_valvar", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    ("egx_gp_predict_valvar_multi", C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p]),
     ("egx_gp_predict_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_var_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_valvar_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),

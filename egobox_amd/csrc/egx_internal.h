@@ -52,19 +52,58 @@ constexpr int kLockstepMax = 16;
 int launch_corr_sym(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, int d,
                     const double *coef, int hcols, double nugget, double *M, int64_t ld, int n_pad,
                     double *xs_scratch = nullptr);
+// per-member pointers of a posterior batch, passed by value to the kernels of the posterior sequence (blockIdx.z / .y = member):
+// the members of a group predicting in lock-step (egx_gp_predict_valvar_multi), or ONE model -- a lone model is a batch of
+// one.  What a member owns alone comes as a pointer; what the caller lays out per launch (queries, partial sums, the
+// (m_pad x n_pad) blocks) sits at the fixed strides of PosteriorBatch.
+struct PosteriorBatchPtrs {
+    const double *par[kLockstepMax];    // x_mean (d) | x_std (d)                         launch_normalize_queries
+    const double *xT[kLockstepMax];     // d x ldx training inputs (prescaled form: times the fit's coefficients)
+    const double *coef[kLockstepMax];   // d x hcols
+    const double *gamma[kLockstepMax];  // n_pad                                          launch_predict_mean
+    const double *ftT[kLockstepMax];    // p rows, ldf apart                              launch_row_reduce
+};
+struct PosteriorBatch {
+    int count = 1;
+    PosteriorBatchPtrs ptrs{};
+    int64_t sq = 0, sracc = 0, sR = 0, ss0 = 0, ssl = 0;  // doubles between two members' xqT / racc / R (RT) / s0 / sl blocks
+};
 // full (m_pad x n_pad) cross correlation block, row-major into R (ld), no diagonal handling
-int launch_cross_corr(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad,
-                      const double *xT, int64_t ldx, int n_pad, int d, const double *coef,
-                      int hcols, double *R, int64_t ld);
+int launch_cross_corr(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx,
+                      int n_pad, int d, int hcols, double *R, int64_t ld);
+inline int launch_cross_corr(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad,
+                             const double *xT, int64_t ldx, int n_pad, int d, const double *coef,
+                             int hcols, double *R, int64_t ld) {
+    PosteriorBatch pb;
+    pb.ptrs.xT[0] = xT, pb.ptrs.coef[0] = coef;
+    return launch_cross_corr(s, corr, pb, xqT, ldq, m_pad, ldx, n_pad, d, hcols, R, ld);
+}
+// raw row-major queries -> normalised k-major (d x ldq, zero padded to m_pad); par = x_mean (d) | x_std (d) on the device;
+// member z reads its m raw rows at xq + z * sxq
+int launch_normalize_queries(hipStream_t s, const PosteriorBatch &pb, const double *xq, int64_t sxq, int m, int d, double *xqT,
+                             int64_t ldq, int m_pad);
+inline int launch_normalize_queries(hipStream_t s, const double *xq, int m, int d, const double *par, double *xqT, int64_t ldq,
+                                    int m_pad) {
+    PosteriorBatch pb;
+    pb.ptrs.par[0] = par;
+    return launch_normalize_queries(s, pb, xq, 0, m, d, xqT, ldq, m_pad);
+}
 // racc[split * m_pad + q] = partial sum_i k(xq, x_i) * gamma[i] over the split's training range (gamma zero padded to
 // n_pad); nsplit > 1 spreads a few queries over the chip, the caller adds the partial sums (racc: nsplit * m_pad)
-// raw row-major queries -> normalised k-major (d x ldq, zero padded to m_pad); par = x_mean (d) | x_std (d) on the device
-int launch_normalize_queries(hipStream_t s, const double *xq, int m, int d, const double *par, double *xqT, int64_t ldq,
-                             int m_pad);
-int launch_predict_mean(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad,
-                        const double *xT, int64_t ldx, int n_pad, int d, const double *coef,
-                        int hcols, const double *gamma, double *racc, int nsplit = 1,
-                        const double *xs_prescaled = nullptr);  // (d x ldx) training inputs times coef (hcols == 1): scalar-row form
+// prescaled != 0: ptrs.xT holds the (d x ldx) training inputs times coef: the scalar-row form, which exists for hcols == 1
+// and d <= 64 only -- predict_mean_prescaled says whether a shape takes it (otherwise ptrs.xT are the plain inputs)
+bool predict_mean_prescaled(int d, int hcols);
+int launch_predict_mean(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx,
+                        int n_pad, int d, int hcols, double *racc, int nsplit, int prescaled);
+inline int launch_predict_mean(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad,
+                               const double *xT, int64_t ldx, int n_pad, int d, const double *coef,
+                               int hcols, const double *gamma, double *racc, int nsplit = 1,
+                               const double *xs_prescaled = nullptr) {
+    const bool pre = xs_prescaled != nullptr && predict_mean_prescaled(d, hcols);
+    PosteriorBatch pb;
+    pb.ptrs.xT[0] = pre ? xs_prescaled : xT, pb.ptrs.coef[0] = coef, pb.ptrs.gamma[0] = gamma;
+    return launch_predict_mean(s, corr, pb, xqT, ldq, m_pad, ldx, n_pad, d, hcols, racc, nsplit, pre ? 1 : 0);
+}
 // xs[k][i] = coef[k] * xT[k][i] over a (d x ldx) k-major array
 int launch_scale_rows(hipStream_t s, const double *xT, int64_t ldx, int d, const double *coef, double *xs);
 // x-gradient contraction out[split][a][k] = sum_j w(j, a) d r(x_a, x_j) / d x_ak over the split's training range;
@@ -94,8 +133,14 @@ int launch_eval_front_batch(hipStream_t s, int corr, const EvalBatchPtrs &b, int
                             double nugget, int64_t ld, int n_pad, int rhs_pad, int q);
 int launch_eval_tail(hipStream_t s, const EvalBatchPtrs &b, int count, int64_t ld, int n, int n_pad, int q, int rows, const int *sync);
 // per-row reductions over the first n columns of rows [0, m): s0[q] = sum rt^2, sl[q*p + l] = sum rt*ft_l
-int launch_row_reduce(hipStream_t s, const double *RT, int64_t ld, int m, int n, const double *ftT,
-                      int64_t ldf, int p, double *s0, double *sl);
+int launch_row_reduce(hipStream_t s, const PosteriorBatch &pb, const double *RT, int64_t ld, int m, int n, int64_t ldf, int p,
+                      double *s0, double *sl);
+inline int launch_row_reduce(hipStream_t s, const double *RT, int64_t ld, int m, int n, const double *ftT,
+                             int64_t ldf, int p, double *s0, double *sl) {
+    PosteriorBatch pb;
+    pb.ptrs.ftT[0] = ftT;
+    return launch_row_reduce(s, pb, RT, ld, m, n, ldf, p, s0, sl);
+}
 // device-side GLS helpers: G <- -Gneg (lower, leading q x q) + identity padding; rho <- yt - ft beta with block sums of rho^2
 int launch_gram_finish(hipStream_t s, const double *Gneg, double *G, int64_t ldg, int rows, int q);
 int launch_gls_residual(hipStream_t s, const double *ftT, int64_t ld, const double *yt, const double *beta, int p, int n,

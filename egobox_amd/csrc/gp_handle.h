@@ -288,6 +288,16 @@ int check_query(const egx_gp *gp, const double *xq, int64_t m);
 //   posterior_weights  Wt (n_pad x m_pad) = -(R^-1 r)^T from RT and the cached C^-T (ensure_winv) ...
 //   posterior_weights_trend   ... then Wt -= (-R^-1 F) (-D)^T with dneg = -D (m_pad x rhs_pad, zero padded)
 int posterior_solve(egx_gp *gp, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl);
+// posterior_solve for a run of `len` models of one shape whose factors sit at one stride (members of a group in consecutive
+// slots): ONE launch sequence, the member a grid coordinate; every block at the fixed stride of its size (gp_predict.hip).
+// posterior_solve is this with len = 1.
+int posterior_solve_run(egx_gp *const *gps, int len, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl);
+// predict_impl's batched route for such a run: member j answers xq[j] (m rows) into yout[j] / vout[j]
+int predict_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m, double *const *yout, double *const *vout);
+// gp_host.hip: the run of a multi-model call that starts at gps[i] (members of one group in consecutive slots), and the
+// exclusive locks of its k distinct handles in a fixed order
+int run_len_multi(egx_gp *const *gps, int k, int i);
+int lock_multi(egx_gp *const *gps, int32_t k, std::vector<std::unique_lock<std::shared_mutex>> &locks);
 int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt);
 int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int m_pad, double *Wt);
 // how many parts the training range is split into so that few queries still fill the chip (the caller adds the partial sums

@@ -1792,6 +1792,11 @@ int32_t egx_gp_set_inner(egx_gp *gp, const egx_gp_inner_view *v) {
 }  // extern "C"
 
 namespace egx {
+int run_len_multi(egx_gp *const *gps, int k, int i) { return ::multi_run_len(gps, k, i); }
+int lock_multi(egx_gp *const *gps, int32_t k, std::vector<std::unique_lock<std::shared_mutex>> &locks) { return ::multi_lock(gps, k, locks); }
+}  // namespace egx
+
+namespace egx {
 static int upload_kmajor(const double *x, int64_t n, int64_t d, int n_pad, DevBuf &buf) {
     std::vector<double> xT((size_t)d * n_pad, 0.0);
     for (int64_t i = 0; i < n; i++)

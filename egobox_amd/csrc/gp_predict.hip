@@ -61,12 +61,36 @@ int xgrad_splits(int rows, int m_pad) {
 // corr (m x n): algorithm.rs:372-380 ; rt = C^-1 corr^T: :337-350 (held transposed, row per query) ; sum rt^2 and ft^T rt
 // (:352): the factor and its tile inverses are workspace 0's, the ft^T rows live below the factor
 int posterior_solve(egx_gp *gp, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl) {
-    const Workspace &w = gp->ws[0];
-    const int n_pad = gp->n_pad;
-    EGX_RC(launch_cross_corr(st, gp->corr, xqT, m_pad, m_pad, gp->d_xT, n_pad, n_pad, gp->d, gp->d_fit_coef, gp->fit_hcols, RT,
-                             n_pad));
-    EGX_RC(launch_trsm_rows(st, w.M, gp->ld, n_pad, w.dinv, RT, n_pad, m_pad));
-    return launch_row_reduce(st, RT, n_pad, m_pad, gp->n, w.M + (size_t)n_pad * gp->ld, gp->ld, gp->p, s0, sl);
+    return posterior_solve_run(&gp, 1, st, xqT, m_pad, RT, s0, sl);
+}
+// the members' own pointers of a posterior batch; the strides are the caller's layout
+static void posterior_batch(egx_gp *const *gps, int len, PosteriorBatch &pb) {
+    pb.count = len;
+    for (int j = 0; j < len; j++) {
+        const egx_gp *g = gps[j];
+        pb.ptrs.par[j] = dev_xnorm(g);
+        pb.ptrs.xT[j] = g->d_xT;
+        pb.ptrs.coef[j] = g->d_fit_coef;
+        pb.ptrs.gamma[j] = g->d_gamma;
+        pb.ptrs.ftT[j] = g->ws[0].M + (size_t)g->n_pad * g->ld;
+    }
+}
+// ... of a run of `len` models of one shape whose factors sit at one stride (members of a group in consecutive slots; a lone
+// model is a run of one): member j's blocks are xqT + j d m_pad, RT + j m_pad n_pad, s0 + j m_pad, sl + j m_pad p
+int posterior_solve_run(egx_gp *const *gps, int len, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl) {
+    const egx_gp *lead = gps[0];
+    const Workspace &w = lead->ws[0];
+    const int n_pad = lead->n_pad;
+    PosteriorBatch pb;
+    posterior_batch(gps, len, pb);
+    pb.sq = (int64_t)lead->d * m_pad, pb.sR = (int64_t)m_pad * n_pad, pb.ss0 = m_pad, pb.ssl = (int64_t)m_pad * lead->p;
+    TrsmBatch tb;
+    tb.count = len;
+    if (len > 1) tb.sM = gps[1]->ws[0].M - w.M, tb.sD = gps[1]->ws[0].dinv - w.dinv;
+    tb.sR = pb.sR;
+    EGX_RC(launch_cross_corr(st, lead->corr, pb, xqT, m_pad, m_pad, n_pad, n_pad, lead->d, lead->fit_hcols, RT, n_pad));
+    EGX_RC(launch_trsm_rows(st, w.M, lead->ld, n_pad, w.dinv, RT, n_pad, m_pad, 0, &tb));
+    return launch_row_reduce(st, pb, RT, n_pad, m_pad, lead->n, lead->ld, lead->p, s0, sl);
 }
 // -Z^T = 0 - C^-T rt as an (n_pad x m_pad) matrix (W upper triangular: K range starts at the row tile)
 int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt) {
@@ -82,6 +106,7 @@ int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int 
 
 static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vout);
 static int small_path_buffers(egx_gp *gp);
+static void posterior_batch(egx_gp *const *gps, int len, PosteriorBatch &pb);
 
 int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *vout) {
     EGX_RC(check_query(gp, xq, m));
@@ -113,25 +138,53 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
             gp->winv_fail_epoch = gp->fit_epoch;
         }
     }
-    Workspace &w = gp->ws[0];
-    const int n_pad = gp->n_pad, d = gp->d, p = gp->p;
-    // chunk so that the (m_tile x n_pad) block of predict_var stays <= 1 GiB
-    int64_t cap = ((int64_t)1 << 27) / n_pad / kTile * kTile;
+    return predict_run(&gp, 1, &xq, m, yout ? &yout : nullptr, vout ? &vout : nullptr);
+}
+
+// The queries of one chunk of the batched posterior: so many that the (m_tile x n_pad) block of predict_var stays <= 1 GiB
+// (kBlockDoubles).  ONE rule for predict_run's chunks and for how many members of a run fit beside each other
+// (predict_run_members): the chunks of a run must be the lone call's, or the bits are not.
+constexpr int64_t kBlockDoubles = (int64_t)1 << 27;
+static int64_t predict_chunk_cap(int n_pad, bool want_var) {
+    if (!want_var) return 65536;
+    int64_t cap = kBlockDoubles / n_pad / kTile * kTile;
     if (cap < kTile) cap = kTile;
     if (cap > 16384) cap = 16384;
-    if (!vout) cap = 65536;
+    return cap;
+}
+// how many members' (m_pad x n_pad) blocks of the largest chunk of m queries stay within kBlockDoubles together (>= 1)
+static int predict_run_members(int n_pad, int64_t m, bool want_var, int len) {
+    if (!want_var) return len;
+    const int64_t m_pad = round_up(std::min(m, predict_chunk_cap(n_pad, true)), kTile);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(len, kBlockDoubles / (m_pad * n_pad)));
+}
+
+// The batched posterior of a run of `len` fitted models of one shape (one n, d, trend and correlation; fit_hcols equal) whose
+// factors sit at one stride -- members of a group in consecutive slots, or ONE model: predict_impl's batched route is this with
+// len = 1.  Member j answers its own m queries xq[j] (original units) into yout[j] / vout[j] (either array may be nullptr as a
+// whole).  One launch sequence, one upload, one read-back and one host synchronisation per chunk, whatever len is; the
+// kernels take the member as a grid coordinate and do a member's arithmetic the same way whatever its companions, and the
+// chunks are those of the lone call, so every member's results are the lone call's bits.
+int predict_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m, double *const *yout, double *const *vout) {
+    egx_gp *lead = gps[0];
+    Workspace &w = lead->ws[0];
+    const int n_pad = lead->n_pad, d = lead->d, p = lead->p;
+    const bool prescaled = predict_mean_prescaled(d, lead->fit_hcols);
+    const int64_t cap = predict_chunk_cap(n_pad, vout != nullptr);
     // Two chunks in flight on two streams: while the GPU works on chunk i the host post-processes chunk i - 1 and
     // normalises / uploads chunk i + 1, and the tail of one chunk's solve overlaps the head of the next (the (m x n)
     // block of a chunk is bounded at 1 GiB, so 100 000 query points at n = 8192 are 7 chunks).
     struct Slot {
         DevBuf d_xraw, d_xqT, d_racc, d_RT, d_s0, d_sl;  // sized by the first (largest) chunk, reused by the later ones
-        std::vector<double> xn, racc, s0, sl;
+        std::vector<double> stage, racc, s0, sl;          // stage: the members' raw rows side by side (len > 1)
         int64_t m0 = 0;
         int mc = 0, m_pad = 0, msplit = 1;
         hipStream_t stream = nullptr;
     } slots[2];
     slots[0].stream = w.stream;
     slots[1].stream = w.lk.s2 ? w.lk.s2 : w.stream;
+    PosteriorBatch pb;
+    posterior_batch(gps, len, pb);
     auto enqueue = [&](Slot &sl_, int64_t m0) -> int {
         const int mc = (int)((m - m0 < cap) ? (m - m0) : cap);
         const int m_pad = (int)round_up(mc, kTile);
@@ -139,53 +192,78 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
         sl_.mc = mc;
         sl_.m_pad = m_pad;
         hipStream_t st = sl_.stream;
-        EGX_RC(upload_queries(gp, xq, m0, mc, m_pad, sl_.xn, sl_.d_xraw, sl_.d_xqT, st));
+        // the raw rows as the caller holds them (xq outlives the call, the staging copy the slot), normalised on the device
+        // (algorithm.rs:254) with every member's own x_mean | x_std
+        const size_t blk = (size_t)mc * d;
+        EGX_RC(sl_.d_xraw.alloc(blk * len));
+        EGX_RC(sl_.d_xqT.alloc((size_t)d * m_pad * len));
+        const double *src = xq[0] + (size_t)m0 * d;
+        if (len > 1) {
+            sl_.stage.resize(blk * len);
+            for (int j = 0; j < len; j++) std::memcpy(&sl_.stage[blk * j], xq[j] + (size_t)m0 * d, sizeof(double) * blk);
+            src = sl_.stage.data();
+        }
+        EGX_HIP_CHECK(hipMemcpyAsync(sl_.d_xraw.p, src, sizeof(double) * blk * len, hipMemcpyHostToDevice, st));
+        pb.sq = (int64_t)d * m_pad;
+        EGX_RC(launch_normalize_queries(st, pb, sl_.d_xraw.p, (int64_t)blk, mc, d, sl_.d_xqT.p, m_pad, m_pad));
         const int msplit = sl_.msplit = mean_splits(n_pad, m_pad);  // (partial sums added below)
         if (yout) {
-            EGX_RC(sl_.d_racc.alloc((size_t)msplit * m_pad));
-            EGX_RC(launch_predict_mean(st, gp->corr, sl_.d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
-                                       gp->fit_hcols, gp->d_gamma, sl_.d_racc.p, msplit,
-                                       gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
+            EGX_RC(sl_.d_racc.alloc((size_t)msplit * m_pad * len));
+            PosteriorBatch pm = pb;
+            pm.sracc = (int64_t)msplit * m_pad;
+            if (prescaled)
+                for (int j = 0; j < len; j++) pm.ptrs.xT[j] = dev_xs_fit(gps[j]);
+            EGX_RC(launch_predict_mean(st, lead->corr, pm, sl_.d_xqT.p, m_pad, m_pad, n_pad, n_pad, d, lead->fit_hcols, sl_.d_racc.p,
+                                       msplit, prescaled ? 1 : 0));
         }
         if (vout) {
-            EGX_RC(sl_.d_RT.alloc((size_t)m_pad * n_pad));
-            EGX_RC(sl_.d_s0.alloc(m_pad));
-            EGX_RC(sl_.d_sl.alloc((size_t)m_pad * p));
-            EGX_RC(posterior_solve(gp, st, sl_.d_xqT.p, m_pad, sl_.d_RT.p, sl_.d_s0.p, sl_.d_sl.p));
+            EGX_RC(sl_.d_RT.alloc((size_t)m_pad * n_pad * len));
+            EGX_RC(sl_.d_s0.alloc((size_t)m_pad * len));
+            EGX_RC(sl_.d_sl.alloc((size_t)m_pad * p * len));
+            EGX_RC(posterior_solve_run(gps, len, st, sl_.d_xqT.p, m_pad, sl_.d_RT.p, sl_.d_s0.p, sl_.d_sl.p));
         }
         return EGX_SUCCESS;
     };
-    std::vector<double> f(p), rhs(p), u(p);
+    std::vector<double> f(p), rhs(p), u(p), xn(d);
     auto finish = [&](Slot &sl_) -> int {
         const int mc = sl_.mc, m_pad = sl_.m_pad, msplit = sl_.msplit;
         const int64_t m0 = sl_.m0;
         EGX_HIP_CHECK(hipStreamSynchronize(sl_.stream));
         // (the copies go to pageable memory: issued after the wait, they cost their transfer time only)
+        const size_t nracc = (size_t)msplit * m_pad, ns0 = (size_t)m_pad, nsl = (size_t)m_pad * p;
         if (yout) {
-            sl_.racc.resize((size_t)msplit * m_pad);
-            EGX_HIP_CHECK(hipMemcpy(sl_.racc.data(), sl_.d_racc.p, sizeof(double) * (size_t)msplit * m_pad, hipMemcpyDeviceToHost));
+            sl_.racc.resize(nracc * len);
+            EGX_HIP_CHECK(hipMemcpy(sl_.racc.data(), sl_.d_racc.p, sizeof(double) * nracc * len, hipMemcpyDeviceToHost));
         }
         if (vout) {
-            sl_.s0.resize(m_pad);
-            sl_.sl.resize((size_t)m_pad * p);
-            EGX_HIP_CHECK(hipMemcpy(sl_.s0.data(), sl_.d_s0.p, sizeof(double) * m_pad, hipMemcpyDeviceToHost));
-            EGX_HIP_CHECK(hipMemcpy(sl_.sl.data(), sl_.d_sl.p, sizeof(double) * (size_t)m_pad * p, hipMemcpyDeviceToHost));
+            sl_.s0.resize(ns0 * len);
+            sl_.sl.resize(nsl * len);
+            EGX_HIP_CHECK(hipMemcpy(sl_.s0.data(), sl_.d_s0.p, sizeof(double) * ns0 * len, hipMemcpyDeviceToHost));
+            EGX_HIP_CHECK(hipMemcpy(sl_.sl.data(), sl_.d_sl.p, sizeof(double) * nsl * len, hipMemcpyDeviceToHost));
         }
-        const std::vector<double> &xn = sl_.xn, &racc = sl_.racc, &s0 = sl_.s0, &sl = sl_.sl;
-        for (int a = 0; a < mc; a++) {
-            hm::regression_row(gp->mean, xn.empty() ? nullptr : &xn[(size_t)a * d], d, f.data());
-            if (yout) {
-                double fb = 0.0, rg = 0.0;
-                for (int l = 0; l < p; l++) fb += f[l] * gp->beta[l];
-                for (int sp = 0; sp < msplit; sp++) rg += racc[(size_t)sp * m_pad + a];
-                yout[m0 + a] = (fb + rg) * gp->y_std + gp->y_mean;  // algorithm.rs:260-262
-            }
-            if (vout) {
-                // u = (Rq^T)^-1 (ft^T rt - f^T)   algorithm.rs:352-367 ; Rq^T lower triangular
-                for (int l = 0; l < p; l++) rhs[l] = sl[(size_t)a * p + l] - f[l];
-                const double usq = hm::trend_forward(gp->ft_qr_r.data(), p, rhs.data(), u.data());
-                double mse = gp->sigma2 * (1.0 - s0[a] + usq);  // algorithm.rs:272-274
-                vout[m0 + a] = (mse < 0.0) ? 0.0 : mse;         // :278
+        for (int j = 0; j < len; j++) {
+            const egx_gp *gp = gps[j];
+            const double *racc = yout ? &sl_.racc[nracc * j] : nullptr;
+            const double *s0 = vout ? &sl_.s0[ns0 * j] : nullptr, *sl = vout ? &sl_.sl[nsl * j] : nullptr;
+            const double *raw = xq[j] + (size_t)m0 * d;
+            for (int a = 0; a < mc; a++) {
+                // the trend needs the normalised coordinates (Linear / Quadratic): the same subtraction and division as the device's
+                if (gp->mean >= 1)
+                    for (int c = 0; c < d; c++) xn[c] = (raw[(size_t)a * d + c] - gp->x_mean[c]) / gp->x_std[c];
+                hm::regression_row(gp->mean, gp->mean >= 1 ? xn.data() : nullptr, d, f.data());
+                if (yout) {
+                    double fb = 0.0, rg = 0.0;
+                    for (int l = 0; l < p; l++) fb += f[l] * gp->beta[l];
+                    for (int sp = 0; sp < msplit; sp++) rg += racc[(size_t)sp * m_pad + a];
+                    yout[j][m0 + a] = (fb + rg) * gp->y_std + gp->y_mean;  // algorithm.rs:260-262
+                }
+                if (vout) {
+                    // u = (Rq^T)^-1 (ft^T rt - f^T)   algorithm.rs:352-367 ; Rq^T lower triangular
+                    for (int l = 0; l < p; l++) rhs[l] = sl[(size_t)a * p + l] - f[l];
+                    const double usq = hm::trend_forward(gp->ft_qr_r.data(), p, rhs.data(), u.data());
+                    double mse = gp->sigma2 * (1.0 - s0[a] + usq);     // algorithm.rs:272-274
+                    vout[j][m0 + a] = (mse < 0.0) ? 0.0 : mse;         // :278
+                }
             }
         }
         return EGX_SUCCESS;
@@ -488,6 +566,52 @@ int32_t egx_gp_predict_valvar(egx_gp *gp, const double *xq, int64_t m, double *y
     }
     std::unique_lock<std::shared_mutex> lock(gp->mu);
     return predict_impl(gp, xq, m, y, var);
+}
+
+// Runs of fitted members of one group in consecutive slots (the runs of egx_gp_finalize_multi) answer in lock-step: one
+// launch sequence per run and chunk.  A run is cut shorter where its (m_pad x n_pad) blocks would pass the 1 GiB that
+// predict_impl allows one handle -- the chunks stay the lone call's, which is what keeps the bits the lone call's.
+int32_t egx_gp_predict_valvar_multi(egx_gp *const *gps, int32_t k, const double *xq, int64_t m, double *y, double *var) {
+    if (m < 0 || (m > 0 && (!xq || (!y && !var)))) {
+        set_error(m > 0 && xq ? "NULL output: y and var" : "bad query array");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::vector<std::unique_lock<std::shared_mutex>> locks;
+    EGX_RC(lock_multi(gps, k, locks));
+    for (int32_t j = 1; j < k; j++)
+        if (gps[j]->d != gps[0]->d) {
+            set_error("egx_gp_predict_valvar_multi: the models must have the same input dimension");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    const size_t d = (size_t)gps[0]->d;
+    int first_rc = EGX_SUCCESS;
+    for (int i = 0; i < k;) {
+        egx_gp *g = gps[i];
+        int rc = check_query(g, xq, m);
+        int len = 1;
+        if (rc == EGX_SUCCESS) rc = set_device(g);
+        if (rc == EGX_SUCCESS && m > 0) {
+            if (g->group && g->fit_hcols == 1) {
+                len = run_len_multi(gps, k, i);
+                for (int j = 1; j < len; j++)
+                    if (!gps[i + j]->fitted || gps[i + j]->fit_hcols != 1 || gps[i + j]->mean != g->mean || gps[i + j]->n != g->n) len = j;
+                len = predict_run_members(g->n_pad, m, var != nullptr, len);
+                const double *xqs[kLockstepMax];
+                double *ys[kLockstepMax], *vs[kLockstepMax];
+                for (int j = 0; j < len; j++) {
+                    xqs[j] = xq + (size_t)(i + j) * m * d;
+                    ys[j] = y ? y + (size_t)(i + j) * m : nullptr;
+                    vs[j] = var ? var + (size_t)(i + j) * m : nullptr;
+                }
+                rc = predict_run(gps + i, len, xqs, m, y ? ys : nullptr, var ? vs : nullptr);
+            } else {
+                rc = predict_impl(g, xq + (size_t)i * m * d, m, y ? y + (size_t)i * m : nullptr, var ? var + (size_t)i * m : nullptr);
+            }
+        }
+        if (rc != EGX_SUCCESS && first_rc == EGX_SUCCESS) first_rc = rc;  // (the others still finish)
+        i += len;
+    }
+    return first_rc;
 }
 
 int32_t egx_gp_predict_gradients(egx_gp *gp, const double *x, int64_t m, double *grad) {

@@ -295,10 +295,14 @@ __global__ void k_scale_rows(const double *__restrict__ xT, int64_t ldx, int d, 
 // GaussianProcess::predict does first ((x - x_mean) / x_std, algorithm.rs:254).  The same IEEE subtraction and division
 // as the host loop this replaces, so the bits are the same; a 64-query slab goes through LDS so that both the reads and
 // the writes are contiguous.  par = x_mean (d) then x_std (d).
-__global__ __launch_bounds__(256) void k_normalize_queries(const double *__restrict__ xq, int m, int d,
-                                                           const double *__restrict__ par, double *__restrict__ xqT,
-                                                           int64_t ldq) {
+// blockIdx.z = member of a posterior batch (PosteriorBatchPtrs): its own normalisation, its query block sxq / sq doubles
+// behind the previous member's.
+__global__ __launch_bounds__(256) void k_normalize_queries(PosteriorBatchPtrs b, const double *__restrict__ xq_all, int64_t sxq,
+                                                           int m, int d, double *__restrict__ xqT_all, int64_t ldq, int64_t sq) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *__restrict__ xq = xq_all + (int64_t)blockIdx.z * sxq;
+    const double *__restrict__ par = b.par[blockIdx.z];
+    double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
     const int q0 = blockIdx.x * 64, tid = threadIdx.x;
     const int rows = (m - q0 < 64) ? (m - q0) : 64;
     // grid.y: chunks of kCorrDC dimensions (one for d <= 64)
@@ -316,12 +320,17 @@ __global__ __launch_bounds__(256) void k_normalize_queries(const double *__restr
     }
 }
 
+// blockIdx.z = member of a posterior batch: its own training inputs and coefficients, its query and output blocks sq / sR
+// doubles behind the previous member's
 template <int CORR, bool PRE>
-__global__ __launch_bounds__(256) void k_cross_corr(const double *__restrict__ xqT, int64_t ldq,
-                                                    const double *__restrict__ xT, int64_t ldx, int d,
-                                                    const double *__restrict__ coef, int hcols,
-                                                    double *__restrict__ R, int64_t ld) {
+__global__ __launch_bounds__(256) void k_cross_corr(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq, int64_t sq,
+                                                    int64_t ldx, int d, int hcols, double *__restrict__ R_all, int64_t ld,
+                                                    int64_t sR) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
+    const double *__restrict__ xT = b.xT[blockIdx.z];
+    const double *__restrict__ coef = b.coef[blockIdx.z];
+    double *__restrict__ R = R_all + (int64_t)blockIdx.z * sR;
     const int dc = d < kCorrDC ? d : kCorrDC;
     double *xi = sm, *xj = sm + dc * 64;
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
@@ -348,13 +357,17 @@ __global__ __launch_bounds__(256) void k_cross_corr(const double *__restrict__ x
 }
 
 // K2+K6 fused: racc[q] = sum_i k(xq, x_i) gamma_i ; one workgroup per 64 queries, loop over slabs.
+// (blockIdx.z = member of a posterior batch, as in k_predict_mean_srow below)
 template <int CORR, bool PRE>
-__global__ __launch_bounds__(256) void k_predict_mean(const double *__restrict__ xqT, int64_t ldq,
-                                                      const double *__restrict__ xT, int64_t ldx, int n_pad,
-                                                      int d, const double *__restrict__ coef, int hcols,
-                                                      const double *__restrict__ gamma,
-                                                      double *__restrict__ racc, int slabs_per_split, int m_pad) {
+__global__ __launch_bounds__(256) void k_predict_mean(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq,
+                                                      int64_t sq, int64_t ldx, int n_pad, int d, int hcols,
+                                                      double *__restrict__ racc_all, int64_t sracc, int slabs_per_split,
+                                                      int m_pad) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
+    const double *__restrict__ xT = b.xT[blockIdx.z];
+    const double *__restrict__ coef = b.coef[blockIdx.z];
+    const double *__restrict__ gamma = b.gamma[blockIdx.z];
     const int dc = d < kCorrDC ? d : kCorrDC;
     double *xi = sm, *xj = sm + dc * 64, *gs = sm + 2 * dc * 64;
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
@@ -388,7 +401,7 @@ __global__ __launch_bounds__(256) void k_predict_mean(const double *__restrict__
         v += __shfl_xor(v, 2);
         v += __shfl_xor(v, 4);
         v += __shfl_xor(v, 8);
-        if (tx == 0) racc[(int64_t)blockIdx.y * m_pad + blockIdx.x * 64 + ty * 4 + a] = v;
+        if (tx == 0) racc_all[(int64_t)blockIdx.z * sracc + (int64_t)blockIdx.y * m_pad + blockIdx.x * 64 + ty * 4 + a] = v;
     }
 }
 
@@ -397,13 +410,20 @@ __global__ __launch_bounds__(256) void k_predict_mean(const double *__restrict__
 // time, fetched from the PRESCALED training inputs of the fit (xs = c_k x, k-major) by the scalar unit, gamma with them --
 // and r . gamma accumulates in the lane's own register: no cross-lane reduction, no barrier inside the loop.  The four waves
 // of a workgroup take every fourth 16-row block of the split's training range; their partial sums meet in LDS at the end.
+// blockIdx.z = member of a posterior batch: a workgroup serves ONE member, so the member's prescaled rows and gamma stay
+// wave-uniform (scalar loads); its query and partial-sum blocks sit sq / sracc doubles behind the previous member's.
 template <int CORR>
-__global__ __launch_bounds__(256) void k_predict_mean_srow(const double *__restrict__ xqT, int64_t ldq,
-                                                           const double *__restrict__ xs, int64_t ldx, int n_pad, int d,
-                                                           const double *__restrict__ coef,
-                                                           const double *__restrict__ gamma, double *__restrict__ racc,
-                                                           int slabs_per_split, int m_pad) {
+__global__ __launch_bounds__(256) void k_predict_mean_srow(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq,
+                                                           int64_t sq, int64_t ldx, int n_pad, int d,
+                                                           double *__restrict__ racc_all, int64_t sracc, int slabs_per_split,
+                                                           int m_pad) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
+    const double *__restrict__ xs = b.xT[blockIdx.z];
+    const double *__restrict__ coef = b.coef[blockIdx.z];
+    const double *__restrict__ gamma = b.gamma[blockIdx.z];
+    // (this workgroup's 64 sums: one pointer across the loop, not the five values it is made of)
+    double *__restrict__ out = racc_all + ((int64_t)blockIdx.z * sracc + (int64_t)blockIdx.y * m_pad + blockIdx.x * 64);
     double *xq = sm, *part = sm + d * 64;  // 64 queries k-major, prescaled; 4 x 64 partial sums
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -450,7 +470,7 @@ __global__ __launch_bounds__(256) void k_predict_mean_srow(const double *__restr
     part[wave * 64 + lane] = sum;
     __syncthreads();
     if (tid < 64)
-        racc[(int64_t)blockIdx.y * m_pad + blockIdx.x * 64 + tid] = (part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]);
+        out[tid] = (part[tid] + part[64 + tid]) + (part[128 + tid] + part[192 + tid]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -724,12 +744,17 @@ __global__ void k_zero_upper(double *__restrict__ M, int64_t ld, int n) {
 }
 
 // one wave per query row: s0 = sum_i rt_i^2 ; sl[l] = sum_i rt_i * ft_l[i]
-__global__ __launch_bounds__(256) void k_row_reduce(const double *__restrict__ RT, int64_t ld, int m, int n,
-                                                    const double *__restrict__ ftT, int64_t ldf, int p,
-                                                    double *__restrict__ s0, double *__restrict__ sl) {
+// blockIdx.y = member of a posterior batch: its own ft^T rows; its RT, s0 and sl blocks sR, ss0, ssl doubles apart
+__global__ __launch_bounds__(256) void k_row_reduce(PosteriorBatchPtrs b, const double *__restrict__ RT_all, int64_t ld, int64_t sR,
+                                                    int m, int n, int64_t ldf, int p, double *__restrict__ s0_all, int64_t ss0,
+                                                    double *__restrict__ sl_all, int64_t ssl) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (q >= m) return;
+    const double *__restrict__ RT = RT_all + (int64_t)blockIdx.y * sR;
+    const double *__restrict__ ftT = b.ftT[blockIdx.y];
+    double *__restrict__ s0 = s0_all + (int64_t)blockIdx.y * ss0;
+    double *__restrict__ sl = sl_all + (int64_t)blockIdx.y * ssl;
     const double *row = RT + (int64_t)q * ld;
     double acc = 0.0;
     for (int i = lane; i < n; i += 64) acc = __builtin_fma(row[i], row[i], acc);
@@ -1027,26 +1052,34 @@ int launch_corr_sym(hipStream_t s, int corr, const double *xT, int64_t ldx, int 
     return EGX_SUCCESS;
 }
 
-int launch_cross_corr(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT,
-                      int64_t ldx, int n_pad, int d, const double *coef, int hcols, double *R, int64_t ld) {
-    dim3 grid(m_pad / 64, n_pad / 64);
+static bool posterior_count_ok(const PosteriorBatch &pb) {
+    if (pb.count >= 1 && pb.count <= kLockstepMax) return true;
+    set_error("posterior batch: count out of range");
+    return false;
+}
+
+int launch_cross_corr(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx,
+                      int n_pad, int d, int hcols, double *R, int64_t ld) {
+    if (!posterior_count_ok(pb)) return EGX_ERR_INVALID_VALUE;
+    dim3 grid(m_pad / 64, n_pad / 64, (unsigned)pb.count);
     const size_t lds = (size_t)2 * (d < kCorrDC ? d : kCorrDC) * 64 * sizeof(double);
     if (hcols == 1) {
-        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_cross_corr<C_, true>), grid, dim3(256), lds, s, xqT, ldq, xT, ldx, d, coef,
-                                                   hcols, R, ld));
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_cross_corr<C_, true>), grid, dim3(256), lds, s, pb.ptrs, xqT, ldq, pb.sq, ldx, d,
+                                                   hcols, R, ld, pb.sR));
     } else {
-        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_cross_corr<C_, false>), grid, dim3(256), lds, s, xqT, ldq, xT, ldx, d, coef,
-                                                   hcols, R, ld));
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_cross_corr<C_, false>), grid, dim3(256), lds, s, pb.ptrs, xqT, ldq, pb.sq, ldx, d,
+                                                   hcols, R, ld, pb.sR));
     }
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
 
-int launch_normalize_queries(hipStream_t s, const double *xq, int m, int d, const double *par, double *xqT, int64_t ldq,
-                             int m_pad) {
+int launch_normalize_queries(hipStream_t s, const PosteriorBatch &pb, const double *xq, int64_t sxq, int m, int d, double *xqT,
+                             int64_t ldq, int m_pad) {
+    if (!posterior_count_ok(pb)) return EGX_ERR_INVALID_VALUE;
     const size_t lds = (size_t)64 * ((d < kCorrDC ? d : kCorrDC) | 1) * sizeof(double);
-    hipLaunchKernelGGL(k_normalize_queries, dim3(m_pad / 64, (unsigned)((d + kCorrDC - 1) / kCorrDC)), dim3(256), lds, s, xq, m, d,
-                       par, xqT, ldq);
+    hipLaunchKernelGGL(k_normalize_queries, dim3(m_pad / 64, (unsigned)((d + kCorrDC - 1) / kCorrDC), (unsigned)pb.count), dim3(256),
+                       lds, s, pb.ptrs, xq, sxq, m, d, xqT, ldq, pb.sq);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
@@ -1057,28 +1090,36 @@ int launch_scale_rows(hipStream_t s, const double *xT, int64_t ldx, int d, const
     return EGX_SUCCESS;
 }
 
-int launch_predict_mean(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT,
-                        int64_t ldx, int n_pad, int d, const double *coef, int hcols, const double *gamma,
-                        double *racc, int nsplit, const double *xs_prescaled) {
+bool predict_mean_prescaled(int d, int hcols) { return hcols == 1 && d <= kCorrDC; }
+
+// pb.ptrs.xT: the members' training inputs, or (prescaled != 0: predict_mean_prescaled) the same times the coefficients of the fit
+int launch_predict_mean(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx,
+                        int n_pad, int d, int hcols, double *racc, int nsplit, int prescaled) {
+    if (!posterior_count_ok(pb)) return EGX_ERR_INVALID_VALUE;
     const size_t lds = (size_t)(2 * (d < kCorrDC ? d : kCorrDC) * 64 + 64) * sizeof(double);
     const int slabs = n_pad / 64;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > slabs) nsplit = slabs;
     const int per = (slabs + nsplit - 1) / nsplit;
     nsplit = (slabs + per - 1) / per;
-    if (hcols == 1 && xs_prescaled != nullptr && d <= kCorrDC) {
+    const dim3 grid(m_pad / 64, nsplit, (unsigned)pb.count);
+    if (prescaled && !predict_mean_prescaled(d, hcols)) {
+        set_error("predict_mean: the prescaled form needs hcols == 1 and d <= 64");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (prescaled) {
         const size_t lds_s = (size_t)(d * 64 + 256) * sizeof(double);
-        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_predict_mean_srow<C_>), dim3(m_pad / 64, nsplit), dim3(256), lds_s, s, xqT,
-                                                   ldq, xs_prescaled, ldx, n_pad, d, coef, gamma, racc, per, m_pad));
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_predict_mean_srow<C_>), grid, dim3(256), lds_s, s, pb.ptrs, xqT, ldq, pb.sq, ldx,
+                                                   n_pad, d, racc, pb.sracc, per, m_pad));
         EGX_HIP_CHECK(hipGetLastError());
         return EGX_SUCCESS;
     }
     if (hcols == 1) {
-        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_predict_mean<C_, true>), dim3(m_pad / 64, nsplit), dim3(256), lds, s, xqT,
-                                                   ldq, xT, ldx, n_pad, d, coef, hcols, gamma, racc, per, m_pad));
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_predict_mean<C_, true>), grid, dim3(256), lds, s, pb.ptrs, xqT, ldq, pb.sq, ldx,
+                                                   n_pad, d, hcols, racc, pb.sracc, per, m_pad));
     } else {
-        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_predict_mean<C_, false>), dim3(m_pad / 64, nsplit), dim3(256), lds, s, xqT,
-                                                   ldq, xT, ldx, n_pad, d, coef, hcols, gamma, racc, per, m_pad));
+        EGX_DISPATCH_CORR(corr, hipLaunchKernelGGL((k_predict_mean<C_, false>), grid, dim3(256), lds, s, pb.ptrs, xqT, ldq, pb.sq, ldx,
+                                                   n_pad, d, hcols, racc, pb.sracc, per, m_pad));
     }
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
@@ -1225,9 +1266,11 @@ int launch_zero_upper(hipStream_t s, double *M, int64_t ld, int n) {
     return EGX_SUCCESS;
 }
 
-int launch_row_reduce(hipStream_t s, const double *RT, int64_t ld, int m, int n, const double *ftT, int64_t ldf,
-                      int p, double *s0, double *sl) {
-    hipLaunchKernelGGL(k_row_reduce, dim3((m + 3) / 4), dim3(256), 0, s, RT, ld, m, n, ftT, ldf, p, s0, sl);
+int launch_row_reduce(hipStream_t s, const PosteriorBatch &pb, const double *RT, int64_t ld, int m, int n, int64_t ldf, int p,
+                      double *s0, double *sl) {
+    if (!posterior_count_ok(pb)) return EGX_ERR_INVALID_VALUE;
+    hipLaunchKernelGGL(k_row_reduce, dim3((m + 3) / 4, (unsigned)pb.count), dim3(256), 0, s, pb.ptrs, RT, ld, pb.sR, m, n, ldf, p, s0,
+                       pb.ss0, sl, pb.ssl);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

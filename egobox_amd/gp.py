@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .cv import GpMetrics, cross_validate  # noqa: E402
 from .multistart import prepare_multistart
 
 #: crates/gp/src/lib.rs:  GP_OPTIM_N_START = 10, GP_COBYLA_MIN_EVAL = 25, GP_COBYLA_MAX_EVAL = 1000
@@ -531,6 +532,36 @@ def fit_multi(handles, theta0s, lo, hi, max_eval=GP_COBYLA_MAX_EVAL):
     return ne
 
 
+def predict_valvar_multi(handles, xqs, want_val=True, want_var=True):
+    """egx_gp_predict_valvar_multi: the posterior of k fitted models at once, handles[j] answering ITS OWN queries xqs[j]
+    (xqs: k x m x d, original units).  Members of one group (GpHandle.create_group / GpParams.fit_group) in consecutive slots
+    answer in lock-step -- one launch sequence and one host synchronisation per run of members instead of one per member --
+    each bit for bit as its own batched `predict_valvar` would.  Returns (y, var), k x m each, None for the one not wanted."""
+    k = len(handles)
+    if k < 1:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi needs at least one model")
+    if not (want_val or want_var):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi: nothing asked for (want_val and want_var are False)")
+    hs = [getattr(h, "handle", h) for h in handles]
+    d = hs[0].d
+    if any(h.d != d for h in hs):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi: the models must have the same input dimension")
+    if len({id(h) for h in hs}) != k:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "the models of a multi-model call must be distinct handles")
+    xqs = L.as_f64(xqs)
+    if xqs.ndim == 2 and d == 1:
+        xqs = xqs[:, :, None]
+    if xqs.ndim != 3 or xqs.shape[0] != k or xqs.shape[2] != d:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"query points must be ({k}, m, {d}), got {xqs.shape}")
+    xqs = np.ascontiguousarray(xqs)
+    m = xqs.shape[1]
+    y = np.empty((k, m)) if want_val else None
+    v = np.empty((k, m)) if want_var else None
+    L.check(L.load().egx_gp_predict_valvar_multi(_handle_array(hs), k, L.dptr(xqs), m, L.dptr(y) if want_val else None,
+                                                  L.dptr(v) if want_var else None))
+    return y, v
+
+
 def set_tuning(knob, value):
     """egx_set_tuning: one of the factorisation's scheduling knobs by name; returns the previous value."""
     old = C.c_int32()
@@ -732,6 +763,12 @@ class GpParams:
             h.shrink(2)
         return GaussianProcess(h, self, n_evals)
 
+    def fits_groups(self):
+        """Whether `fit_group` takes these parameters: ThetaTuning Fixed or Full with COBYLA, no dimension reduction (what
+        the callers that choose between `fit_group` and a loop of `fit` ask: egobox_amd/cv.py)."""
+        t = self._theta_tuning
+        return t.kind in ("Fixed", "Full") and self._kpls_dim is None and not (t.kind == "Full" and self._optimizer == "lbfgs")
+
     def fit_group(self, xs, ys):
         """`fit` for k training sets of ONE shape at once (xs: k x n x d, ys: k x n; ThetaTuning Fixed or Full, no KPLS): what
         the expert loop of egobox-moe does one model after the other (crates/moe/src/algorithm.rs:167-177).  The models are
@@ -739,7 +776,7 @@ class GpParams:
         bit for bit the model `fit` returns for its training set.  Returns k GaussianProcess objects."""
         self.check()
         t = self._theta_tuning
-        if t.kind not in ("Fixed", "Full") or self._kpls_dim is not None or (t.kind == "Full" and self._optimizer == "lbfgs"):
+        if not self.fits_groups():
             raise L.InvalidValueError(L.ERR_INVALID_VALUE, "fit_group: ThetaTuning Fixed or Full (COBYLA), no dimension reduction")
         xs = np.asarray(xs, dtype=np.float64)
         ys = np.asarray(ys, dtype=np.float64)
@@ -777,8 +814,17 @@ class GpParams:
         return [GaussianProcess(h, self, ne) for h, ne in zip(hs, n_evals)]
 
 
-class GaussianProcess:
-    """Fitted model (crates/gp/src/algorithm.rs:174-192); state lives on the GPU."""
+class GaussianProcess(GpMetrics):
+    """Fitted model (crates/gp/src/algorithm.rs:174-192); state lives on the GPU.  The cross-validation scores of GpMetrics
+    (crates/gp/src/metrics.rs: q2 / pva / iae_alpha, k-fold and leave-one-out) refit `params_` per fold, the folds in
+    lock-step (egobox_amd/cv.py)."""
+
+    def _cv_targets(self):
+        return self.training_data[1]
+
+    def _cv_folds(self, kfold, want_var):
+        x, y = self.training_data
+        return cross_validate(self.params_, x, y, kfold, want_var)
 
     def __init__(self, handle, params, n_evals=1):
         self._h = handle

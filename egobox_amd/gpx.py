@@ -4,10 +4,11 @@
                 n_start, max_eval, seed) -> GpMix ;  GpMix.fit(xt, yt) -> Gpx
     Gpx.predict / predict_var / thetas / variances / likelihoods / dims / training_data / save / load
 
-Only what sits on the accelerated path is implemented: one cluster (n_clusters = 1), one regression and
-one correlation spec.  Clustering, expert selection by cross-validation and the GMM recombination stay in
-egobox-moe ("next").  `n_start = -1` is the reference's fixed-theta entry point
-(gp_mix.rs:202-208) used for parity.
+Only what sits on the accelerated path is implemented here: one cluster (n_clusters = 1), one regression and
+one correlation spec; clustering and the cross-validated expert selection are `GpMixture.params()`'s
+(egobox_amd/moe.py: n_clusters, expert_specs).  `n_start = -1` is the reference's fixed-theta entry point
+(gp_mix.rs:202-208) used for parity.  The cross-validation scores of GpMetrics (q2 / pva / iae_alpha) are forwarded to
+the expert.
 """
 from __future__ import annotations
 
@@ -54,8 +55,8 @@ def _single(spec, table, what):
     hits = [v for k, v in table.items() if spec & k]
     if len(hits) != 1:
         raise NotImplementedError(
-            f"{what}: expert selection among several specs is done by egobox-moe cross-validation "
-            f"(crates/moe/src/algorithm.rs:209-347), outside the accelerated path; pass exactly one spec")
+            f"{what}: exactly one spec expected here; expert selection among several specs by cross-validation "
+            f"(crates/moe/src/algorithm.rs:209-347) is GpMixture.params().expert_specs(regression, correlation)")
     return hits[0]()
 
 
@@ -125,6 +126,25 @@ class Gpx:
 
     def predict_valvar(self, x):
         return self._experts[0].predict_valvar(x)
+
+    # GpMetrics (crates/moe/src/metrics.rs:19-144), forwarded to the expert: folds refitted in lock-step (egobox_amd/cv.py)
+    def q2_k_score(self, kfold):
+        return self._experts[0].q2_k_score(kfold)
+
+    def q2_score(self):
+        return self._experts[0].q2_score()
+
+    def pva_k_score(self, kfold):
+        return self._experts[0].pva_k_score(kfold)
+
+    def pva_score(self):
+        return self._experts[0].pva_score()
+
+    def iae_alpha_k_score(self, kfold, plot_data=None):
+        return self._experts[0].iae_alpha_k_score(kfold, plot_data)
+
+    def iae_alpha_score(self, plot_data=None):
+        return self._experts[0].iae_alpha_score(plot_data)
 
     def predict_gradients(self, x):
         """python/src/gp_mix.rs `predict_gradients`: (m, nx) derivatives of the mean."""

@@ -6,8 +6,11 @@ Training mirrors egobox-moe's `GpMixture::params().n_clusters(k).fit(..)`:
   extract_part, sort_by_cluster                     crates/moe/src/algorithm.rs:1111-1121, clustering.rs:33-56
   GaussianMixture.fit                               GaussianMixtureModel::params(k).n_runs(20).fit, algorithm.rs:120-123
 The Gaussian mixture is trained inside libegx_gp_hip.so (egx_gmm_fit: full-covariance EM, the restarts in lock-step on the
-GPU); the experts go through `GpMixture.fit_experts`, clusters of equal size in lock-step.  Not here: NbClusters::Auto, expert
-selection by cross-validation over several specs, sparse-GP experts, a k-means initialisation.
+GPU); the experts go through `GpMixture.fit_experts`, clusters of equal size in lock-step.  With several allowed
+(regression, correlation) pairs (`expert_specs`) every cluster's expert is chosen by find_best_expert's 5-fold
+cross-validation (algorithm.rs:209-347), its folds fitted and asked in lock-step (egobox_amd/cv.py); a trained mixture
+answers the cross-validation scores of GpMetrics (crates/moe/src/metrics.rs).  Not here: NbClusters::Auto, sparse-GP
+experts, a k-means initialisation.
 
 Prediction mirrors what egobox-moe does with the trained mixture:
   GaussianMixture.predict_probas / predict        crates/moe/src/gaussian_mixture.rs:114-121, 231-283, 305-316
@@ -32,6 +35,9 @@ import math
 import numpy as np
 
 from ._lib import ERR_INVALID_VALUE, ERR_LINALG, ClusteringError, InvalidValueError
+from .cv import GpMetrics, cross_validate, cross_validate_surrogates, expert_pairs
+from .cv import pair_name as _pair_name
+from .cv import select_expert as _select_expert
 
 
 class GaussianMixture:
@@ -267,6 +273,8 @@ class GpMixtureParams:
         self._seed = 42
         self._device = -1
         self._n_runs = 20  # algorithm.rs:121
+        self._expert_pairs = None  # several allowed (mean, correlation) pairs: expert_specs
+        self._selection_tuning = None  # ThetaTuning of the selection's fold fits (None: the pairs' defaults): selection_tuning
 
     def n_clusters(self, n_clusters):
         if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
@@ -291,7 +299,7 @@ class GpMixtureParams:
 
     def regression_spec(self, spec):
         """One RegressionSpec flag (or a mean object); several at once ask for the cross-validated expert selection of
-        find_best_expert (algorithm.rs:209-347), which is not implemented."""
+        find_best_expert (algorithm.rs:209-347): that is `expert_specs`."""
         from . import gpx
         self._mean = gpx._single(spec, gpx._REGR, "regression_spec") if isinstance(spec, (int, gpx.RegressionSpec)) else spec
         return self
@@ -299,6 +307,34 @@ class GpMixtureParams:
     def correlation_spec(self, spec):
         from . import gpx
         self._corr = gpx._single(spec, gpx._CORR, "correlation_spec") if isinstance(spec, (int, gpx.CorrelationSpec)) else spec
+        return self
+
+    def expert_specs(self, regression=1, correlation=1):
+        """The allowed experts as two flag sets (RegressionSpec, CorrelationSpec; the defaults are CONSTANT and
+        SQUARED_EXPONENTIAL): with more than one (regression, correlation) pair every cluster's expert is the pair of the
+        smallest 5-fold cross-validation error (`select_expert`: find_best_expert, algorithm.rs:209-347), then trained on
+        the whole cluster as ever.  One pair is the reference's shortcut: no fold is fitted."""
+        pairs = expert_pairs(regression, correlation)
+        if len(pairs) == 1:
+            self._mean, self._corr, self._expert_pairs = pairs[0][0](), pairs[0][1](), None
+        else:
+            self._expert_pairs = pairs
+        return self
+
+    def select_expert(self, cluster_x, cluster_y, theta_tuning=None):
+        """(winning name, [(name, error), ..]) among the allowed pairs on one cluster (egobox_amd/cv.py select_expert).  The fold
+        fits use the pair's default GpParams plus kpls_dim, not this builder's tunings (expertise_macros.rs:22);
+        `theta_tuning` overrides that (extension)."""
+        pairs = self._expert_pairs or [(type(self._mean), type(self._corr))]
+        if theta_tuning is None:
+            theta_tuning = self._selection_tuning
+        return _select_expert(pairs, cluster_x, cluster_y, kpls_dim=self._kpls_dim, theta_tuning=theta_tuning, device=self._device)
+
+    def selection_tuning(self, theta_tuning):
+        """Extension: the ThetaTuning `fit` hands to `select_expert` for the selection's fold fits (None: the pairs' defaults,
+        as the reference, expertise_macros.rs:22).  `fit` reaches `select_expert` only through `_train_on_clusters`, so without
+        this a trained mixture could not use the `theta_tuning` extension of `select_expert`."""
+        self._selection_tuning = theta_tuning
         return self
 
     def theta_tunings(self, theta_tunings):
@@ -338,13 +374,14 @@ class GpMixtureParams:
         self._n_runs = int(n_runs)
         return self
 
-    def _expert_params(self, nc):
+    def _expert_params(self, nc, pair=None):
         from . import gp as G
         tt = self._theta_tunings
         if len(tt) != 1 and len(tt) != self._n_clusters:
             raise InvalidValueError(ERR_INVALID_VALUE, f"theta_tunings: 1 or n_clusters ({self._n_clusters}) expected, "
                                                        f"got {len(tt)}")
-        return G.GpParams(self._mean, self._corr).theta_tuning(tt[0] if len(tt) == 1 else tt[nc]).n_start(self._n_start) \
+        mean, corr = (self._mean, self._corr) if pair is None else (pair[0](), pair[1]())
+        return G.GpParams(mean, corr).theta_tuning(tt[0] if len(tt) == 1 else tt[nc]).n_start(self._n_start) \
             .max_eval(self._max_eval).kpls_dim(self._kpls_dim).device(self._device)
 
     def fit(self, x, y):
@@ -374,10 +411,23 @@ class GpMixtureParams:
         """train_on_clusters, crates/moe/src/algorithm.rs:144-205."""
         nx = x.shape[1]
         clusters = sort_by_cluster(gmx.n_clusters, data, gmx.predict(x))
-        check_number_of_points(clusters, nx, self._mean)
+        # (several allowed regressions: the most demanding one counts, algorithm.rs:387-393)
+        check_number_of_points(clusters, nx, self._mean if not self._expert_pairs
+                               else max((m() for m, _ in self._expert_pairs), key=lambda m: m.code))
         check_three_points(clusters)
         cxs, cys = [c[:, :nx] for c in clusters], [c[:, nx] for c in clusters]
-        if len(self._theta_tunings) == 1 and self._kpls_dim is None:
+        expert_errors = None
+        if self._expert_pairs:
+            # find_best_expert per cluster (algorithm.rs:167-177 -> :209-347): the choice by cross-validation, then the winner
+            # trained on the whole cluster under this builder's tunings
+            by_name = {_pair_name(m, c): (m, c) for m, c in self._expert_pairs}
+            expert_errors, experts = [], []
+            for i in range(len(clusters)):
+                name, table = self.select_expert(cxs[i], cys[i])
+                expert_errors.append(table)
+                experts.append(self._expert_params(i, by_name[name]).fit(cxs[i], cys[i]))
+            moe = GpMixture(experts, gmx, self._recombination)
+        elif len(self._theta_tunings) == 1 and self._kpls_dim is None:
             moe = GpMixture.fit_experts(self._expert_params(0), cxs, cys, gmx, self._recombination)
         else:  # a tuning per cluster, or the PLS rotations of each cluster's own data: one fit per expert
             moe = GpMixture([self._expert_params(i).fit(cxs[i], cys[i]) for i in range(len(clusters))], gmx,
@@ -390,12 +440,28 @@ class GpMixtureParams:
             return final
         moe.training_data = (x, y)
         moe.params_ = self
+        moe.expert_errors_ = expert_errors  # per cluster the selection's [(name, error), ..]; None without a selection
         return moe
 
 
-class GpMixture:
+class GpMixture(GpMetrics):
     """Experts + mixture.  `GpMixture.params()` builds and trains one; the constructor takes trained experts (`experts[i]` is
-    None for experts that live on another rank)."""
+    None for experts that live on another rank).  A mixture trained by `GpMixtureParams.fit` (it keeps `params_` and
+    `training_data`) answers the cross-validation scores of GpMetrics (crates/moe/src/metrics.rs:19-144)."""
+
+    def _cv_targets(self):
+        if getattr(self, "params_", None) is None:
+            raise InvalidValueError(ERR_INVALID_VALUE, "cross-validation scores need a mixture trained by GpMixtureParams.fit")
+        return self.training_data[1]
+
+    def _cv_folds(self, kfold, want_var):
+        y = self._cv_targets()
+        x, p = self.training_data[0], self.params_
+        if p._n_clusters == 1 and not p._expert_pairs and p._gmx is None:
+            # one cluster: the folds are those of its one expert, fitted and asked in lock-step
+            return cross_validate(p._expert_params(0), x, y, kfold, want_var)
+        # several clusters: the clusters' sizes differ from fold to fold, every fold is a training of its own
+        return cross_validate_surrogates(p.fit, x, y, kfold, want_var)
 
     @staticmethod
     def params():

@@ -290,6 +290,20 @@ int32_t egx_gp_fit_lbfgs(egx_gp *gp, const double *theta0s, int64_t n_starts, co
 int32_t egx_gp_predict(egx_gp *gp, const double *xq, int64_t m, double *y /*m*/);
 int32_t egx_gp_predict_var(egx_gp *gp, const double *xq, int64_t m, double *var /*m*/);
 int32_t egx_gp_predict_valvar(egx_gp *gp, const double *xq, int64_t m, double *y, double *var);
+/* The posterior of k DISTINCT fitted models in one call: gps[j] answers ITS OWN block of m queries, rows [j m, (j + 1) m) of
+ * xq (original units, normalised with gps[j]'s x_mean | x_std), into rows of y and var likewise (either may be NULL, not
+ * both).  What a k-fold cross-validation asks of the k fits of its folds (GpMetrics, crates/moe/src/metrics.rs:19-144;
+ * find_best_expert, crates/moe/src/algorithm.rs:209-347).  Members of one group (egx_gp_create_group) in consecutive slots
+ * answer in lock-step: one launch sequence, one upload, one read-back and one host synchronisation per run of members (the
+ * runs of egx_gp_finalize_multi) and chunk of queries, the member a grid coordinate of the kernels.  Any other handle is
+ * served on its own as by egx_gp_predict_valvar.  The lock-step route is the batched one for every m (no C^-T cache per
+ * member).  CONTRACT: for every member, y and var are bit for bit what egx_gp_predict_valvar(gps[j], block j, m, ..) returns
+ * on its batched route, which that call takes for m > 8; for m <= 8 the lone call may answer from its cached C^-T, and the
+ * two agree to rounding only.  Arguments as for the other _multi calls: NULL / k <= 0 / duplicate handles / unequal d are
+ * EGX_ERR_INVALID_VALUE before any work, the locks are taken in a fixed order, an unfitted member is EGX_ERR_NOT_FITTED; the
+ * first error is returned after every member has been served. */
+int32_t egx_gp_predict_valvar_multi(egx_gp *const *gps, int32_t k, const double *xq /*k x m x d, block j for gps[j]*/,
+                                    int64_t m, double *y /*k x m or NULL*/, double *var /*k x m or NULL*/);
 
 /* ---- x-gradients of the predictions (what EGO's infill optimiser asks per point):
  * GaussianProcess::predict_gradients algorithm.rs:510-549, predict_var_gradients(_single) :555-617, 702-709,

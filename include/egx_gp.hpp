@@ -443,6 +443,18 @@ inline GaussianProcess GpParams::fit(const double *x, int64_t n, int64_t d, cons
     return gp;
 }
 
+// The posterior of k fitted models in one call (egx_gp_predict_valvar_multi): model j answers rows [j m, (j + 1) m) of xq
+// (k x m x d, original units).  Members of one group (GpParams::fit_group) answer in lock-step, each bit for bit as its own
+// batched predict_valvar: what the folds of a cross-validation ask (crates/moe/src/metrics.rs:19-144).  Returns (y, var), k x m.
+inline std::pair<std::vector<double>, std::vector<double>> predict_valvar_group(const std::vector<const GaussianProcess *> &models,
+                                                                                const double *xq, int64_t m) {
+    std::vector<egx_gp *> hs;
+    for (const GaussianProcess *g : models) hs.push_back(g->handle());
+    std::vector<double> y(hs.size() * (size_t)m), v(hs.size() * (size_t)m);
+    check(egx_gp_predict_valvar_multi(hs.data(), (int32_t)hs.size(), xq, m, y.data(), v.data()));
+    return {std::move(y), std::move(v)};
+}
+
 // GpMixture::predict / predict_var over fitted experts of THIS process (crates/moe/src/algorithm.rs:411-423, 670-685 smooth;
 // :879-935 hard): probas (m x n_experts row-major) are the responsibilities, xq (m x d) in original units.
 inline std::pair<std::vector<double>, std::vector<double>> moe_predict_valvar(const std::vector<const GaussianProcess *> &experts,
