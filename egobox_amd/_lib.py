@@ -72,6 +72,11 @@ class InfillStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("best_start", C.c_int64), ("evals", c_int64_p)]
 
 
+class InfillCstrStats(C.Structure):
+    _fields_ = [("rounds", C.c_int64), ("best_start", C.c_int64), ("feasible", C.c_int32), ("violation", C.c_double),
+                ("evals", c_int64_p)]
+
+
 class Timings(C.Structure):
     _fields_ = [("corr_build_ms", C.c_double), ("potrf_ms", C.c_double), ("potrf_syrk_ms", C.c_double),
                 ("solve_ms", C.c_double), ("host_ms", C.c_double), ("total_ms", C.c_double),
@@ -189,6 +194,11 @@ SIGNATURES = [
     ("egx_infill_scaling", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p]),
     ("egx_infill_optimize", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
                                         c_double_p, C.POINTER(InfillStats)]),
+    ("egx_infill_set_cstr_strategy", C.c_int32, [C.c_void_p, C.c_int32, c_double_p]),
+    ("egx_infill_get_cstr_strategy", C.c_int32, [C.c_void_p, c_int32_p, c_double_p]),
+    ("egx_infill_eval_cstr", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("egx_infill_optimize_cstr", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                             c_double_p, c_double_p, C.POINTER(InfillCstrStats)]),
     ("egx_infill_create_mix", C.c_int32, [C.POINTER(InfillConfig), C.POINTER(InfillSurrogate), c_double_p, C.c_int32,
                                           C.POINTER(C.c_void_p)]),
     ("egx_infill_eval_experts", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,

@@ -235,6 +235,17 @@ int launch_infill_mix(hipStream_t s, const InfillMix &g);
 int launch_infill_combine(hipStream_t s, const infill::Params &prm, int k, int d, int64_t m, int64_t mstride, const double *mean,
                           const double *var, const double *gmean, const double *gvar, const double *tol, const int *flag,
                           double *value, double *grad);
+// The mean halves of launch_infill_trend / _xgrad_finish / _mix (a constraint surrogate under EGX_CSTR_MEAN): s0, sl, R, Rt,
+// dneg, out_v, evar, egvar, var, gvar are not read or written; the means keep the bits of the full forms.
+int launch_infill_trend_mean(hipStream_t s, const InfillTrend &t);
+int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *x_std,
+                                    double *gmean);
+int launch_infill_mix_mean(hipStream_t s, const InfillMix &g);
+// EGX_CSTR_MEAN / _UTB: value[i] (the objective model's criterion, no feasibility factor), cstr[i * k + j], grad (m x d),
+// gcstr (m x k x d); any output may be nullptr; scale: the k scale_cstr on the device
+int launch_infill_cstr(hipStream_t s, const infill::Params &prm, int strategy, int k, int d, int64_t m, int64_t mstride,
+                       const double *mean, const double *var, const double *gmean, const double *gvar, const double *scale,
+                       const int *flag, double *value, double *cstr, double *grad, double *gcstr);
 // the scaling pass' terms per point, on the device with k_infill_combine's text: ei (EI value; nullptr = skipped), base (the
 // objective of prm without the feasibility factor) and fac (pofs, or logpofs for LogEI); base == nullptr skips both
 int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, int64_t m, int64_t mstride, const double *mean,

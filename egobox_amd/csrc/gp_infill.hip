@@ -17,6 +17,15 @@
 // k_infill_mix launch per (tile, surrogate) recombines them into the slot (smooth: the weighted sums; hard: the expert of the
 // first maximum of the responsibilities -- every expert still evaluates the whole tile, so that every launch keeps the padded
 // batch of 128).  Locks, caches, checks and scratch sizes run over the flat list of all experts.
+//
+// CONSTRAINT STRATEGIES (egx_infill_set_cstr_strategy).  EGX_CSTR_INFILL folds the constraint surrogates into the objective (the
+// above).  Under EGX_CSTR_MEAN / _UTB the objective carries no feasibility factor and the constraints are handed to the
+// optimiser as c(x) <= 0 (egx_infill_eval_cstr, egx_infill_optimize_cstr; solver_infill_optim.rs:148-204).  Under MEAN nobody
+// reads a constraint surrogate's variance, and its experts run the MEAN-ONLY sequence: prepare, predict_mean, the mean half of
+// the trend tail (and, for gradients, ONE launch_xgrad with gamma and the mean half of its finish) -- no posterior_solve, no
+// weights, no second contraction; the means keep the bits of the full sequence, which forms r . gamma before its solve as
+// well.  A call that does not ask for anything of the constraint surrogates (egx_infill_eval without parts under MEAN / UTB)
+// does not run them at all.
 #include <set>
 
 #include "gmx_point.h"
@@ -54,6 +63,11 @@ struct egx_infill {
     DevBuf xqT, racc, RT, s0, sl, Wt, dneg, out_y, out_v;
     // the experts of the mixtures: their tables (slot-major like mean / var), d p / d x of one tile, the diagnostics of a call
     DevBuf emean, evar, egmean, egvar, dprob, dg_probas, dg_dprobas;
+    // how the constraint surrogates enter (infill::CstrStrategy), their scales, the tables of egx_infill_eval_cstr
+    int strategy = infill::kCstrInfill;
+    std::vector<double> scale_cstr;  // one per constraint, ones until set
+    DevBuf d_scale, cstr, gcstr;
+    bool scale_on_device = false;
 };
 
 namespace {
@@ -146,9 +160,37 @@ int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool w
     return launch_infill_xgrad_finish(st, tr, d, nsplit, h->out_y.p, h->out_v.p, dev_xnorm(gp) + d, gmean, gvar);
 }
 
+// The mean-only sequence of one expert for one tile: what expert_tile launches for mean / gmean and nothing else.
+int expert_tile_mean(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *gmean, int *flag) {
+    const int d = h->d;
+    egx_gp *gp = h->models[j];
+    const int n = gp->n, n_pad = gp->n_pad;
+    const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
+    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag));
+    EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
+                               gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
+                               gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
+    InfillTrend tr;
+    tr.p = gp->p, tr.rp = gp->rhs_pad, tr.msplit = msplit;
+    tr.xqT = h->xqT.p, tr.fidx = gp->d_fidx, tr.beta = gp->d_tbeta;
+    tr.racc = h->racc.p;
+    tr.y_mean = gp->y_mean, tr.y_std = gp->y_std;
+    tr.mean = mean;
+    EGX_RC(launch_infill_trend_mean(st, tr));
+    if (!want_g) return EGX_SUCCESS;
+    EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
+                        gp->d_gamma, 0, 1, nsplit, h->out_y.p));
+    return launch_infill_xgrad_finish_mean(st, tr, d, nsplit, h->out_y.p, dev_xnorm(gp) + d, gmean);
+}
+
+// what egx_infill_eval_cstr asks for beside value / grad (host pointers, any nullptr)
+struct CstrOut {
+    double *cstr = nullptr, *gcstr = nullptr;
+};
+
 // The evaluation proper; the handle's and the models' locks are held.  value / grad / every member of parts may be nullptr.
 int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
-                const ExpertDiag *diag = nullptr) {
+                const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr) {
     if (m < 0 || (m > 0 && !xq)) {
         set_error("bad query array");
         return EGX_ERR_INVALID_VALUE;
@@ -157,11 +199,17 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     EGX_RC(check_fitted(h));
     if (m == 0) return EGX_SUCCESS;
     const bool want_g = grad || (parts && (parts->grad_mean || parts->grad_var)) ||
-                        (diag && (diag->gmean || diag->gvar || diag->dprobas));
+                        (diag && (diag->gmean || diag->gvar || diag->dprobas)) || (co && co->gcstr);
+    // the constraint surrogates: folded into the objective (all of them, the full sequence), or run only when something of
+    // theirs is asked for, and then mean-only when no variance of theirs is read
+    const bool folded = h->strategy == infill::kCstrInfill;
+    const bool run_c = folded || parts || diag || (co && (co->cstr || co->gcstr));
+    const bool mean_c = h->strategy == infill::kCstrMean && !diag && !(parts && (parts->var || parts->grad_var));
+    const int n_obj = h->surr[0].k;  // models[0 .. n_obj) are the objective's experts
     EGX_RC(set_device(h->models[0]));
     hipStream_t st = h->models[0]->ws[0].stream;
-    if (want_g)
-        for (int e = 0; e < ne; e++) EGX_RC(ensure_winv(h->models[e]));  // once per fitted state (synchronises the model's stream)
+    if (want_g)  // once per fitted state (synchronises the model's stream); the mean-only sequence does not read C^-T
+        for (int e = 0; e < (run_c && !mean_c ? ne : n_obj); e++) EGX_RC(ensure_winv(h->models[e]));
     for (int e = 0; e < ne; e++) EGX_RC(ensure_trend_state(h->models[e], st));
     for (Surrogate &sg : h->surr)
         if (sg.k >= 2 && !sg.on_device) {
@@ -169,6 +217,11 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
             EGX_HIP_CHECK(hipMemcpyAsync(sg.d_gmx.p, sg.gmx.data(), sizeof(double) * sg.gmx.size(), hipMemcpyHostToDevice, st));
             sg.on_device = true;
         }
+    if (k > 0 && !folded && !h->scale_on_device) {
+        EGX_RC(h->d_scale.alloc(k));
+        EGX_HIP_CHECK(hipMemcpyAsync(h->d_scale.p, h->scale_cstr.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+        h->scale_on_device = true;
+    }
     if (k > 0 && !h->tol_on_device) {
         EGX_RC(h->d_tol.alloc(k));
         EGX_HIP_CHECK(hipMemcpyAsync(h->d_tol.p, h->tol.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
@@ -214,6 +267,10 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
             EGX_RC(h->dprob.alloc((size_t)kTile * h->k_max * d));
         }
     }
+    if (co && k > 0) {
+        if (co->cstr) EGX_RC(h->cstr.alloc((size_t)M * k));
+        if (co->gcstr) EGX_RC(h->gcstr.alloc((size_t)M * k * d));
+    }
     if (diag_mix) {
         EGX_RC(h->dg_probas.alloc((size_t)M * dsg->k));
         if (diag->dprobas) EGX_RC(h->dg_dprobas.alloc((size_t)M * dsg->k * d));
@@ -222,11 +279,17 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     EGX_HIP_CHECK(hipMemcpyAsync(h->xraw.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st));
     for (int64_t t0 = 0; t0 < m; t0 += kTile) {
         const int mt = (int)std::min<int64_t>(kTile, m - t0);
-        for (int js = 0; js < nm; js++) {
+        for (int js = 0; js < (run_c ? nm : 1); js++) {
             const Surrogate &sg = h->surr[js];
             const bool lone = sg.k < 2;  // a lone expert writes the surrogate's slot, the experts of a mixture their own tables
+            const bool mean_only = js > 0 && mean_c;
             for (int e = 0; e < sg.k; e++) {
                 const size_t row = (lone ? (size_t)js : (size_t)(sg.eslot + e)) * M + t0;
+                if (mean_only) {
+                    EGX_RC(expert_tile_mean(h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
+                                            want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr, nullptr));
+                    continue;
+                }
                 EGX_RC(expert_tile(h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
                                    (lone ? h->var.p : h->evar.p) + row, want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr,
                                    want_g ? (lone ? h->gvar.p : h->egvar.p) + row * d : nullptr,
@@ -249,12 +312,22 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
                 mx.probas = h->dg_probas.p + (size_t)t0 * sg.k;
                 if (diag->dprobas) mx.dp = h->dg_dprobas.p + (size_t)t0 * sg.k * d;
             }
-            EGX_RC(launch_infill_mix(st, mx));
+            EGX_RC(mean_only ? launch_infill_mix_mean(st, mx) : launch_infill_mix(st, mx));
         }
     }
-    if (value)
+    if (value && folded)
         EGX_RC(launch_infill_combine(st, h->prm, k, d, m, M, h->mean.p, h->var.p, want_g ? h->gmean.p : nullptr,
                                      want_g ? h->gvar.p : nullptr, h->d_tol.p, flag, h->value.p, grad ? h->grad.p : nullptr));
+    if (value && !folded) {  // the objective model alone; the constraint values beside it for egx_infill_eval_cstr
+        const int kc = co ? k : 0;
+        EGX_RC(launch_infill_cstr(st, h->prm, h->strategy, kc, d, m, M, h->mean.p, h->var.p, want_g ? h->gmean.p : nullptr,
+                                  want_g ? h->gvar.p : nullptr, h->d_scale.p, flag, h->value.p, kc && co->cstr ? h->cstr.p : nullptr,
+                                  grad ? h->grad.p : nullptr, kc && co->gcstr ? h->gcstr.p : nullptr));
+        if (kc && co->cstr)
+            EGX_HIP_CHECK(hipMemcpyAsync(co->cstr, h->cstr.p, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost, st));
+        if (kc && co->gcstr)
+            EGX_HIP_CHECK(hipMemcpyAsync(co->gcstr, h->gcstr.p, sizeof(double) * (size_t)m * k * d, hipMemcpyDeviceToHost, st));
+    }
     if (value) EGX_HIP_CHECK(hipMemcpyAsync(value, h->value.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
     if (grad) EGX_HIP_CHECK(hipMemcpyAsync(grad, h->grad.p, sizeof(double) * (size_t)m * d, hipMemcpyDeviceToHost, st));
     if (parts)
@@ -302,8 +375,8 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
 }
 
 int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
-                 const ExpertDiag *diag = nullptr) {
-    const int rc = eval_locked(h, xq, m, value, grad, parts, diag);
+                 const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr) {
+    const int rc = eval_locked(h, xq, m, value, grad, parts, diag, co);
     if (rc) {  // nothing may still run on the handle's buffers
         (void)hipStreamSynchronize(h->models[0]->ws[0].stream);
         (void)hipGetLastError();
@@ -337,6 +410,7 @@ int finish_create(egx_infill *h, const egx_infill_config &cfg) {
     h->prm.scale_ic = cfg.scale_ic;
     h->prm.scale = cfg.scale;
     h->prm.feasibility = cfg.feasibility != 0;
+    h->scale_cstr.assign(h->surr.size() - 1, 1.0);
     return EGX_SUCCESS;
 }
 
@@ -542,7 +616,11 @@ int32_t egx_infill_scaling(egx_infill *h, const double *pts, int64_t npts, doubl
     }
     std::lock_guard<std::mutex> lock(h->mu);
     ModelLocks locks(h);
-    const int nm = (int)h->surr.size(), k = nm - 1;
+    const int nm = (int)h->surr.size(), n_cstr = nm - 1;
+    // under EGX_CSTR_MEAN / _UTB the scale is that of the objective alone (compute_infill_obj_scale with cstr_infill = false,
+    // solver_computations.rs:322-330): the terms below are formed as for a handle without constraint models
+    const bool folded = h->strategy == infill::kCstrInfill;
+    const int k = folded ? n_cstr : 0;
     // ONE values-only pass over all points (means and variances of every model stay on the device); the criterion's terms are
     // then formed ON THE DEVICE with the text of k_infill_combine, so that what is stored is bit for bit the largest |value|
     // egx_infill_eval returns at scale = 1 (all values finite).  The host does the NaN / inf -> 1 replacement, the last
@@ -597,19 +675,166 @@ int32_t egx_infill_scaling(egx_infill *h, const double *pts, int64_t npts, doubl
         scale = std::fmax(scale, std::fabs(v));
     }
     if (scale < 100.0 * infill::kEps || std::isnan(scale) || std::isinf(scale)) scale = 1.0;
-    if (scale_cstr)  // compute_cstr_scales, utils/misc.rs:10-28
-        for (int j = 1; j <= k; j++) {
+    if (scale_cstr || !folded)  // compute_cstr_scales, utils/misc.rs:10-28
+        for (int j = 1; j <= n_cstr; j++) {
             double best = -1.0;
             for (int64_t i = 0; i < npts; i++) {
                 const double v = mean[(size_t)j * npts + i];
                 if (!std::isinf(v) && std::fabs(v) > best) best = std::fabs(v);
             }
-            scale_cstr[j - 1] = best < 0.0 ? 1.0 : best;
+            const double sc = best < 0.0 ? 1.0 : best;
+            if (scale_cstr) scale_cstr[j - 1] = sc;
+            // kept for egx_infill_eval_cstr (a scale the handle could not divide by -- 0, NaN -- leaves the stored one)
+            if (!folded && sc > 0.0 && std::isfinite(sc)) {
+                h->scale_cstr[j - 1] = sc;
+                h->scale_on_device = false;
+            }
         }
     h->prm.scale_ic = scale_ic;
     h->prm.scale = scale;
     if (scale_ic_out) *scale_ic_out = scale_ic;
     if (scale_out) *scale_out = scale;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_set_cstr_strategy(egx_infill *h, int32_t strategy, const double *scale_cstr) {
+    if (!h) {
+        set_error("NULL handle");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (strategy < EGX_CSTR_INFILL || strategy > EGX_CSTR_UTB) {
+        set_error("infill: unknown constraint strategy");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    const size_t k = h->surr.size() - 1;
+    if (scale_cstr) {
+        for (size_t j = 0; j < k; j++)
+            if (!(scale_cstr[j] > 0.0) || std::isinf(scale_cstr[j])) {
+                set_error("infill: scale_cstr " + std::to_string(j) + " must be positive and finite");
+                return EGX_ERR_INVALID_VALUE;
+            }
+        h->scale_cstr.assign(scale_cstr, scale_cstr + k);
+        h->scale_on_device = false;
+    }
+    h->strategy = strategy;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_get_cstr_strategy(egx_infill *h, int32_t *strategy, double *scale_cstr) {
+    if (!h || !strategy) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    *strategy = h->strategy;
+    if (scale_cstr) std::copy(h->scale_cstr.begin(), h->scale_cstr.end(), scale_cstr);
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_eval_cstr(egx_infill *h, const double *xq, int64_t m, double *value, double *cstr, double *grad,
+                             double *grad_cstr) {
+    if (!h || (m > 0 && !value) || (m > 0 && h->surr.size() > 1 && !cstr)) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->strategy == infill::kCstrInfill) {
+        set_error("infill: the handle folds its constraints into the objective (EGX_CSTR_INFILL); set EGX_CSTR_MEAN or EGX_CSTR_UTB");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    ModelLocks locks(h);
+    CstrOut co;
+    co.cstr = cstr, co.gcstr = grad_cstr;
+    return eval_guarded(h, xq, m, value, grad, nullptr, nullptr, &co);
+}
+
+int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start,
+                                 int64_t max_eval, double *f_best, double *x_best, double *c_best, egx_infill_cstr_stats *stats) {
+    if (!h || !lo || !hi || !x_start || !f_best || !x_best || n_start < 1 || (h->surr.size() > 1 && !c_best)) {
+        set_error("infill optimize: NULL argument or no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int d = h->d, k = (int)h->surr.size() - 1;
+    for (int i = 0; i < d; i++)
+        if (!(lo[i] <= hi[i]) || std::isinf(lo[i]) || std::isinf(hi[i])) {
+            set_error("infill optimize: bounds must be finite with lo <= hi (coordinate " + std::to_string(i) + ")");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    for (int64_t s = 0; s < n_start; s++)
+        for (int i = 0; i < d; i++)
+            if (!std::isfinite(x_start[s * d + i])) {
+                set_error("infill optimize: start point " + std::to_string(s) + " has a non-finite coordinate");
+                return EGX_ERR_INVALID_VALUE;
+            }
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->strategy == infill::kCstrInfill) {
+        set_error("infill optimize: the handle folds its constraints into the objective (EGX_CSTR_INFILL); use egx_infill_optimize");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    ModelLocks locks(h);
+    // one general-constraint COBYLA per start, configured as egx_infill_optimize's (optimizer.rs:123-167: no constraint
+    // tolerances; solver_infill_optim.rs:217-227)
+    if (max_eval <= 0) max_eval = std::min<int64_t>(10 * n_start * d, 2000);
+    const std::vector<double> blo(lo, lo + d), bhi(hi, hi + d);
+    // a point is FEASIBLE when c_j <= cstr_tol_j / scale_cstr_j: Egor's acceptance tolerance in the units of c
+    std::vector<double> cfeas((size_t)k);
+    for (int j = 0; j < k; j++) cfeas[j] = h->tol[j] / h->scale_cstr[j];
+    std::vector<Cobyla> mach;
+    mach.reserve((size_t)n_start);
+    for (int64_t s = 0; s < n_start; s++)
+        mach.emplace_back(std::vector<double>(x_start + s * d, x_start + (s + 1) * d), blo, bhi, k, 0.5, 1e-4, 1e-4, max_eval, 0.0, true,
+                          true, cfeas);
+    std::vector<double> pts, vals, cvals, x;
+    std::vector<size_t> who;
+    int64_t rounds = 0;
+    // all starts in LOCK-STEP: a round's trial points are ONE values-only egx_infill_eval_cstr
+    for (;;) {
+        pts.clear();
+        who.clear();
+        for (size_t q = 0; q < mach.size(); q++)
+            if (mach[q].ask(x)) {
+                who.push_back(q);
+                pts.insert(pts.end(), x.begin(), x.end());
+            }
+        if (who.empty()) break;
+        vals.assign(who.size(), 0.0);
+        cvals.assign(who.size() * (size_t)k + 1, 0.0);
+        CstrOut co;
+        co.cstr = k > 0 ? cvals.data() : nullptr;
+        EGX_RC(eval_guarded(h, pts.data(), (int64_t)who.size(), vals.data(), nullptr, nullptr, nullptr, &co));
+        rounds++;
+        for (size_t q = 0; q < who.size(); q++) mach[who[q]].tell(vals[q], cvals.data() + q * (size_t)k);
+    }
+    // The best EVALUATED point: feasible beats infeasible, then the smaller objective (feasible) or the smaller violation
+    // max_j (c_j - cstr_tol_j / scale_cstr_j) (infeasible); the first point of a start and the first start win ties.  The
+    // reference returns every run's final vertex and takes the smallest objective, feasible or not (:229-232).
+    auto better = [&](const Cobyla &a, const Cobyla &b) {  // a strictly better than b
+        if (a.best_feasible() != b.best_feasible()) return a.best_feasible();
+        return a.best_feasible() ? a.best_key() < b.best_key() : a.best_violation() < b.best_violation();
+    };
+    int64_t best = 0;
+    for (int64_t s = 1; s < n_start; s++)
+        if (better(mach[(size_t)s], mach[(size_t)best])) best = s;
+    const Cobyla &win = mach[(size_t)best];
+    *f_best = win.best_f();
+    std::copy(win.best_x().begin(), win.best_x().end(), x_best);
+    if (k > 0) std::copy(win.best_c().begin(), win.best_c().end(), c_best);
+    if (stats) {
+        stats->rounds = rounds;
+        stats->best_start = best;
+        stats->feasible = win.best_feasible() ? 1 : 0;
+        stats->violation = k > 0 ? win.best_violation() : 0.0;
+        if (stats->evals)
+            for (int64_t s = 0; s < n_start; s++) stats->evals[s] = mach[(size_t)s].evals();
+    }
+    bool any_finite = false;
+    for (const Cobyla &c : mach) any_finite |= c.any_finite_f();
+    if (!any_finite) {
+        *f_best = std::numeric_limits<double>::infinity();
+        set_error("infill optimize: no start met a finite objective value");
+        return EGX_ERR_NO_FINITE_START;
+    }
     return EGX_SUCCESS;
 }
 

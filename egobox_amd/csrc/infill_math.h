@@ -17,7 +17,11 @@
 //                                                        (EI, WB2, WB2S) or obj - logpofs (LogEI); feasibility == 0 replaces obj by
 //                                                        -1 (0 for LogEI) and its gradient by 0 (:410-416, 441-466)
 //
-// Three places where the reference is NOT followed (each pinned by tests/test_infill_cpu.py):
+//   constraint values           solver/solver_computations.rs:196-257   what the optimiser is handed as c(x) <= 0 when
+//                                                        cstr_infill = false: mean_cstr = mu_c / scale_cstr, or the upper trust
+//                                                        bound (mu_c + 3 sigma_c) / scale_cstr (CSTR_DOUBT = 3)
+//
+// Four places where the reference is NOT followed (each pinned by tests/test_infill_cpu.py):
 //   1. log_ei_helper far in the tail.  The reference's erfcx(z) = exp(z^2) erfc(z) (logei_helper.rs:9-11) leaves double range near
 //      u = -37.6 and its own asymptotic branch starts at u <= -1e6 only.  Here, for u <= kTailSwitch = -20 the asymptotic form is
 //      used directly:  log_term = -2 ln|u| + log1p(-3/u^2 + 15/u^4 - 105/u^6 + ...)  (12 terms), never exp(z^2).
@@ -25,6 +29,9 @@
 //      for tol = 0 only.  Here: -mu'/s - (tol - mu) s' / s^2.
 //   3. sigma_weight in the gradient.  eval_grad_infill_obj (solver_computations.rs:387-391) passes None where the value got
 //      Some(sigma_weight).  Here value and gradient use the same k.
+//   4. sigma' of the upper trust bound.  upper_trust_bound_cstr (solver_computations.rs:224-257) takes var_grad[[0, 0]], the FIRST
+//      coordinate's derivative of the variance, for every coordinate of its gradient (:242).  Here coordinate c uses d var / d x_c
+//      (tests/c_host/infill_cstr_math_test.cpp; at d = 1 both agree).
 //   (A consequence of the feasibility rule: without constraint models the reference's gradient ignores `feasibility` (:438-439)
 //    while its value is the constant -1 / 0; here the gradient of that constant is 0 as well.)
 #pragma once
@@ -225,6 +232,23 @@ EGX_IM_HD void objective_grad(const Params &p, int k, int d, const double *mu, c
         }
         grad[c * gout] = ig * pf + pg * infill;
     }
+}
+
+// How the constraint surrogates enter the optimisation (egx_cstr_strategy): kCstrInfill folds them into the objective (pofs /
+// logpofs above); kCstrMean / kCstrUtb hand cstr_value to the optimiser as c(x) <= 0 and leave the objective without the factor.
+enum CstrStrategy { kCstrInfill = 0, kCstrMean = 1, kCstrUtb = 2 };
+constexpr double kCstrDoubt = 3.0;  // CSTR_DOUBT
+
+EGX_IM_HD double cstr_value(int strategy, double mu, double var, double scale) {
+    if (strategy == kCstrUtb) return (mu + kCstrDoubt * sqrt(var)) / scale;
+    return mu / scale;
+}
+// one component: dmu, dvar are d mu_c / d x_c, d var_c / d x_c (deviation 4)
+EGX_IM_HD double cstr_grad(int strategy, double var, double dmu, double dvar, double scale) {
+    if (strategy != kCstrUtb) return dmu / scale;
+    const double sigma = sqrt(var);
+    const double sp = sigma < kEps ? 0.0 : dvar / (2.0 * sigma);
+    return (dmu + kCstrDoubt * sp) / scale;
 }
 
 }  // namespace infill

@@ -79,5 +79,27 @@ EGX_MX_HD void mix_grad(bool smooth, int k, int d, const double *p, int64_t sp, 
     }
 }
 
+// The mean half of mix_value / mix_grad alone, for a surrogate whose variance nobody reads (a constraint handed to the optimiser
+// as its scaled mean): the same terms in the same order, so the bits are those of the full forms.
+EGX_MX_HD double mix_mean(bool smooth, int k, const double *p, int64_t sp, const double *mu, int64_t se) {
+    if (!smooth) return mu[mix_first_max(k, p, sp) * se];
+    double am = 0.0;
+    for (int e = 0; e < k; e++) am += mix_mean_term(p[e * sp], mu[e * se]);
+    return am;
+}
+EGX_MX_HD void mix_grad_mean(bool smooth, int k, int d, const double *p, int64_t sp, const double *dp, int64_t sdp, const double *mu,
+                             int64_t se, const double *gmu, int64_t sg, double *gmean) {
+    if (!smooth) {
+        const int e = mix_first_max(k, p, sp);
+        for (int l = 0; l < d; l++) gmean[l] = gmu[e * sg + l];
+        return;
+    }
+    for (int l = 0; l < d; l++) {
+        double am = 0.0;
+        for (int e = 0; e < k; e++) am += mix_grad_mean_term(p[e * sp], dp[e * sdp + l], mu[e * se], gmu[e * sg + l]);
+        gmean[l] = am;
+    }
+}
+
 }  // namespace infill
 }  // namespace egx

@@ -7,6 +7,10 @@
 //   k_infill_mix       a surrogate with several experts: the responsibilities of its Gaussian mixture at the point (gmx_point.h)
 //                      and infill_mix_math.h across the experts, into the surrogate's slot of the tables k_infill_combine reads
 //   k_infill_combine   infill_math.h across the 1 + k models of a point: value and gradient of the minimised objective
+//   k_infill_trend_mean, k_infill_xgrad_finish_mean, k_infill_mix_mean   the MEAN halves of the three kernels above, for a
+//                      constraint surrogate whose variance nobody reads (EGX_CSTR_MEAN): no substitution, no s0 / sl, no
+//                      second contraction -- the same sums in the same order, so the means keep the full sequence's bits
+//   k_infill_cstr      the objective without the feasibility factor and the constraint values handed to the optimiser
 // None of them is matrix-shaped: they are latency-bound tails whose point is to keep the call free of host round trips.
 // Every reduction runs in a fixed order that depends on the model alone, and a workgroup (or thread) owns one point: a point's
 // result does not depend on its position in the tile nor on its companions.
@@ -101,6 +105,22 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_trend(TrendArgs g) {
     for (int l = t; l < g.rp; l += kInfThreads) g.dneg[(int64_t)a * g.rp + l] = l < p ? -s[l] : 0.0;
 }
 
+// The mean of k_infill_trend alone: prod[p], part[msplit] in LDS, thread 0 adds them in the same order.
+__global__ __launch_bounds__(kInfThreads) void k_infill_trend_mean(TrendArgs g) {
+    extern __shared__ double lds[];
+    const int p = g.p, a = blockIdx.x, t = threadIdx.x;
+    double *prod = lds, *part = lds + p;
+    for (int l = t; l < p; l += kInfThreads) prod[l] = trend_column(g.fidx, l, g.xqT, kTile, a) * g.beta[l];
+    for (int sp = t; sp < g.msplit; sp += kInfThreads) part[sp] = g.racc[(int64_t)sp * kTile + a];
+    __syncthreads();
+    if (t == 0) {
+        double fb = 0.0, rg = 0.0;
+        for (int l = 0; l < p; l++) fb += prod[l];
+        for (int sp = 0; sp < g.msplit; sp++) rg += part[sp];
+        g.mean[a] = (fb + rg) * g.y_std + g.y_mean;
+    }
+}
+
 struct XgFinishArgs {
     int d, p, rp, nsplit;
     const double *xqT;
@@ -158,6 +178,30 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish(XgFinishArg
     }
 }
 
+// The gmean of k_infill_xgrad_finish alone (out_v, dneg, gvar are not read).
+__global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish_mean(XgFinishArgs g) {
+    __shared__ double st_y[kXgStage];
+    const int a = blockIdx.x, t = threadIdx.x, d = g.d, ns = g.nsplit;
+    int kc = kXgStage / ns;
+    if (kc > kInfThreads) kc = kInfThreads;
+    for (int k0 = 0; k0 < d; k0 += kc) {
+        const int kn = d - k0 < kc ? d - k0 : kc;
+        __syncthreads();
+        for (int e = t; e < ns * kn; e += kInfThreads) {
+            const int sp = e / kn, kk = e - sp * kn;
+            st_y[kk * ns + sp] = g.out_y[((int64_t)sp * kTile + a) * d + k0 + kk];
+        }
+        __syncthreads();
+        if (t < kn) {
+            const int k = k0 + t;
+            double sy = 0.0;
+            for (int sp = 0; sp < ns; sp++) sy += st_y[t * ns + sp];
+            const double dfy = jac_dot(g, a, k, g.beta, 1.0);
+            g.gmean[(int64_t)a * d + k] = (dfy + sy) * g.y_std / g.x_std[k];
+        }
+    }
+}
+
 // A surrogate that is a mixture of k >= 2 experts, after the experts' sequences have written their tables for the tile: one
 // lane per point, 64-lane workgroups (kTile / 64 of them).  The lane's raw coordinates (a flagged point: zeros, as the experts
 // got), its responsibilities p and the scratch of the derivative (z, v': d each; u: k) live in LDS rows of odd stride; the
@@ -196,6 +240,33 @@ __global__ __launch_bounds__(64) void k_infill_mix(const double *__restrict__ xq
                          gmean + a * d, gvar + a * d);
 }
 
+// The mean half of k_infill_mix: the same responsibilities, mix_mean / mix_grad_mean; evar / egvar / var / gvar do not exist.
+__global__ __launch_bounds__(64) void k_infill_mix_mean(const double *__restrict__ xq, const int *__restrict__ flag, int mt, int d,
+                                                       int k, int smooth, int want_g, const double *__restrict__ means,
+                                                       const double *__restrict__ precs, const double *__restrict__ par,
+                                                       const double *__restrict__ emean, const double *__restrict__ egmean,
+                                                       int64_t estride, double *__restrict__ mean, double *__restrict__ gmean,
+                                                       double *__restrict__ dp) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int q0 = blockIdx.x * 64, lane = threadIdx.x, ds = d | 1, ks = k | 1;
+    const int rows = mt - q0 < 64 ? mt - q0 : 64;
+    if (rows <= 0) return;
+    double *xs = sm, *ps = xs + 64 * ds, *zs = ps + 64 * ks, *vps = zs + 64 * ds, *us = vps + 64 * ds;
+    for (int e = lane; e < rows * d; e += 64) {
+        const int i = e / d, j = e - i * d;
+        xs[i * ds + j] = flag[q0 + i] ? 0.0 : xq[(int64_t)q0 * d + e];
+    }
+    __syncthreads();
+    if (lane >= rows) return;
+    const int64_t a = q0 + lane;
+    const double *x = xs + lane * ds;
+    double *p = ps + lane * ks, *dpa = dp ? dp + a * k * d : nullptr;
+    gmx_probas_point(x, d, k, means, precs, par, p);
+    if (dpa) gmx_probas_deriv_point(x, zs + lane * ds, vps + lane * ds, us + lane * ks, d, k, means, precs, par, dpa);
+    mean[a] = infill::mix_mean(smooth != 0, k, p, 1, emean + a, estride);
+    if (want_g) infill::mix_grad_mean(smooth != 0, k, d, p, 1, dpa, d, emean + a, estride, egmean + a * d, estride * d, gmean + a * d);
+}
+
 // one thread per point of the call; model j of point i at j * mstride + i (mean, var) and (j * mstride + i) * d (gradients)
 __global__ __launch_bounds__(kInfThreads) void k_infill_combine(infill::Params prm, int k, int d, int64_t m, int64_t mstride,
                                                                const double *__restrict__ mean, const double *__restrict__ var,
@@ -213,6 +284,39 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_combine(infill::Params p
     value[i] = infill::objective(prm, k, mean + i, var + i, mstride, tol);
     if (grad)
         infill::objective_grad(prm, k, d, mean + i, var + i, mstride, gmean + i * d, gvar + i * d, mstride * d, tol, grad + i * d, 1);
+}
+
+// What the optimiser is handed when the constraint surrogates are NOT folded into the objective (EGX_CSTR_MEAN / _UTB), one
+// thread per point: value = the objective of the objective model alone (k_infill_scale_terms' base: prm.feasibility = 1, no
+// factor), cstr[i * k + j] = infill::cstr_value of constraint model j + 1, and optionally their gradients grad (m x d) and
+// gcstr (m x k x d).  var / gvar of the constraint models are read under UTB only.  A flagged point: +inf, +inf, zeros.
+__global__ __launch_bounds__(kInfThreads) void k_infill_cstr(infill::Params prm, int strategy, int k, int d, int64_t m,
+                                                            int64_t mstride, const double *__restrict__ mean,
+                                                            const double *__restrict__ var, const double *__restrict__ gmean,
+                                                            const double *__restrict__ gvar, const double *__restrict__ scale,
+                                                            const int *__restrict__ flag, double *__restrict__ value,
+                                                            double *__restrict__ cstr, double *__restrict__ grad,
+                                                            double *__restrict__ gcstr) {
+    const int64_t i = (int64_t)blockIdx.x * kInfThreads + threadIdx.x;
+    if (i >= m) return;
+    const bool bad = flag[i] != 0, utb = strategy == infill::kCstrUtb;
+    if (value) value[i] = bad ? INFINITY : infill::objective(prm, 0, mean + i, var + i, mstride, nullptr);
+    if (grad) {
+        if (bad)
+            for (int c = 0; c < d; c++) grad[i * d + c] = 0.0;
+        else
+            infill::objective_grad(prm, 0, d, mean + i, var + i, mstride, gmean + i * d, gvar + i * d, mstride * d, nullptr,
+                                   grad + i * d, 1);
+    }
+    for (int j = 1; j <= k; j++) {
+        const int64_t o = j * mstride + i;
+        const double v = utb ? var[o] : 0.0;
+        if (cstr) cstr[i * k + j - 1] = bad ? INFINITY : infill::cstr_value(strategy, mean[o], v, scale[j - 1]);
+        if (gcstr)
+            for (int c = 0; c < d; c++)
+                gcstr[(i * k + j - 1) * d + c] =
+                    bad ? 0.0 : infill::cstr_grad(strategy, v, gmean[o * d + c], utb ? gvar[o * d + c] : 0.0, scale[j - 1]);
+    }
 }
 
 // The terms of the scaling pass (egx_infill_scaling), one thread per point, with the text k_infill_combine runs:
@@ -282,6 +386,68 @@ int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int n
     g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.dneg = t.dneg, g.out_y = out_y, g.out_v = out_v, g.x_std = x_std;
     g.sigma2 = t.sigma2, g.y_std = t.y_std, g.gmean = gmean, g.gvar = gvar;
     hipLaunchKernelGGL(k_infill_xgrad_finish, dim3(kTile), dim3(kInfThreads), 0, s, g);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_cstr(hipStream_t s, const infill::Params &prm, int strategy, int k, int d, int64_t m, int64_t mstride,
+                       const double *mean, const double *var, const double *gmean, const double *gvar, const double *scale,
+                       const int *flag, double *value, double *cstr, double *grad, double *gcstr) {
+    if (m <= 0) return EGX_SUCCESS;
+    if ((strategy != infill::kCstrMean && strategy != infill::kCstrUtb) || ((grad || gcstr) && !gmean) ||
+        ((grad || (gcstr && strategy == infill::kCstrUtb)) && !gvar) || (k > 0 && (cstr || gcstr) && !scale)) {
+        set_error("infill: bad arguments of the constraint evaluation");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    infill::Params p = prm;
+    p.feasibility = 1;
+    hipLaunchKernelGGL(k_infill_cstr, dim3((unsigned)((m + kInfThreads - 1) / kInfThreads)), dim3(kInfThreads), 0, s, p, strategy, k,
+                       d, m, mstride, mean, var, gmean, gvar, scale, flag, value, cstr, grad, gcstr);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_trend_mean(hipStream_t s, const InfillTrend &t) {
+    const size_t lds = sizeof(double) * ((size_t)t.p + (size_t)t.msplit);
+    if (lds > 65536) {
+        set_error("infill: more than 2560 regression columns");
+        return EGX_ERR_UNSUPPORTED;
+    }
+    TrendArgs g{};
+    g.p = t.p, g.rp = t.rp, g.msplit = t.msplit, g.want_d = 0;
+    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.racc = t.racc;
+    g.y_mean = t.y_mean, g.y_std = t.y_std, g.mean = t.mean;
+    hipLaunchKernelGGL(k_infill_trend_mean, dim3(kTile), dim3(kInfThreads), lds, s, g);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *x_std,
+                                    double *gmean) {
+    if (nsplit < 1 || nsplit > kXgStage) {
+        set_error("infill: split count of the x-gradient contraction out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    XgFinishArgs g{};
+    g.d = d, g.p = t.p, g.rp = t.rp, g.nsplit = nsplit;
+    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.out_y = out_y, g.x_std = x_std;
+    g.y_std = t.y_std, g.gmean = gmean;
+    hipLaunchKernelGGL(k_infill_xgrad_finish_mean, dim3(kTile), dim3(kInfThreads), 0, s, g);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_mix_mean(hipStream_t s, const InfillMix &g) {
+    const size_t lds = infill_mix_lds_bytes(g.d, g.k);
+    if (g.k < 2 || g.mt < 1 || g.mt > kTile || lds > kInfillMixMaxLds || (g.smooth && g.want_g && !g.dp)) {
+        set_error("infill: bad arguments of the mixture recombination");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (lds > 64 * 1024)
+        EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_infill_mix_mean),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_infill_mix_mean, dim3(kTile / 64), dim3(64), lds, s, g.xq, g.flag, g.mt, g.d, g.k, g.smooth ? 1 : 0,
+                       g.want_g ? 1 : 0, g.means, g.precs, g.par, g.emean, g.egmean, g.estride, g.mean, g.gmean, g.dp);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

@@ -11,6 +11,8 @@ from . import _lib as L
 
 #: criterion constants (egx_infill_criterion)
 EI, LOG_EI, WB2, WB2S = 0, 1, 2, 3
+#: how the constraint surrogates enter the optimisation (egx_cstr_strategy)
+CSTR_STRATEGIES = {"infill": 0, "mean": 1, "utb": 2}
 
 
 def _gp_handle(model):
@@ -193,6 +195,65 @@ class InfillObjective:
             L.check(rc)
         stats = dict(evals=evals, rounds=int(st.rounds), best_start=int(st.best_start), finite=rc == L.SUCCESS)
         return f.value, xb, stats
+
+    # ---- the constraint surrogates as constraints of the optimiser (cstr_infill = false) --------------------------------
+    def set_cstr_strategy(self, strategy, scale_cstr=None):
+        """"infill": the constraint surrogates are folded into the objective as (log) probabilities of feasibility (the
+        default).  "mean" / "utb": the objective carries no factor and the surrogates are handed to the optimiser as
+        c(x) <= 0, their scaled mean or upper trust bound (mean + 3 sigma) / scale_cstr (solver_infill_optim.rs:148-204).
+        scale_cstr (n_cstr,) positive and finite, or None to keep the stored scales (ones at first; `scaling` stores its own)."""
+        if strategy not in CSTR_STRATEGIES:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: cstr strategy must be one of {sorted(CSTR_STRATEGIES)}")
+        sc = None
+        if scale_cstr is not None:
+            sc = L.as_f64(np.atleast_1d(np.asarray(scale_cstr, dtype=np.float64)), 1)
+            if sc.shape[0] != self.n_cstr:
+                raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: {self.n_cstr} constraint models but {sc.shape[0]} scales")
+        L.check(self._lib.egx_infill_set_cstr_strategy(self._h, CSTR_STRATEGIES[strategy],
+                                                       L.dptr(sc) if sc is not None and self.n_cstr else None))
+
+    def cstr_strategy(self):
+        """(strategy name, scale_cstr (n_cstr,))."""
+        s = C.c_int32()
+        sc = np.ones(max(self.n_cstr, 1))
+        L.check(self._lib.egx_infill_get_cstr_strategy(self._h, C.byref(s), L.dptr(sc)))
+        return {v: k for k, v in CSTR_STRATEGIES.items()}[s.value], sc[:self.n_cstr].copy()
+
+    def constraints(self, x, grad=False):
+        """What the optimiser sees under "mean" / "utb" (egx_infill_eval_cstr): (value (m,), cstr (m, n_cstr)), with grad=True
+        also (grad (m, d), grad_cstr (m, n_cstr, d)).  c <= 0 is feasible."""
+        x = self._points(x)
+        m, d, k = x.shape[0], self.d, self.n_cstr
+        value, cstr = np.empty(m), np.empty((m, k))
+        g = np.empty((m, d)) if grad else None
+        gc = np.empty((m, k, d)) if grad else None
+        spare = np.empty(1)  # a valid address for the empty tables of n_cstr = 0
+        L.check(self._lib.egx_infill_eval_cstr(self._h, L.dptr(x), m, L.dptr(value), L.dptr(cstr if cstr.size else spare),
+                                               L.dptr(g) if grad else None, L.dptr(gc if k and m else spare) if grad else None))
+        return (value, cstr, g, gc) if grad else (value, cstr)
+
+    def optimize_constrained(self, xlimits, x_start, max_eval=None):
+        """The multistart with the constraint surrogates as nonlinear constraints (egx_infill_optimize_cstr): one
+        general-constraint COBYLA per row of x_start inside xlimits (d, 2), all starts in lock-step.  Returns (x, f, c, stats):
+        the best evaluated point -- feasible before infeasible, then the smaller objective, or the smaller violation --, the
+        objective and the constraint values there, and a dict of evals, rounds, best_start, feasible, violation, finite."""
+        lim = L.as_f64(xlimits, 2)
+        if lim.shape != (self.d, 2):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
+        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+        xs = self._points(x_start)
+        n_start = xs.shape[0]
+        f, xb, cb = C.c_double(), np.empty(self.d), np.empty(max(self.n_cstr, 1))
+        evals = np.zeros(n_start, dtype=np.int64)
+        st = L.InfillCstrStats(0, 0, 0, 0.0, evals.ctypes.data_as(L.c_int64_p))
+        rc = self._lib.egx_infill_optimize_cstr(self._h, L.dptr(lo), L.dptr(hi), L.dptr(xs), n_start,
+                                                0 if max_eval is None else int(max_eval), C.byref(f), L.dptr(xb), L.dptr(cb),
+                                                C.byref(st))
+        if rc != L.ERR_NO_FINITE_START:
+            L.check(rc)
+        stats = dict(evals=evals, rounds=int(st.rounds), best_start=int(st.best_start), feasible=bool(st.feasible),
+                     violation=float(st.violation), finite=rc == L.SUCCESS)
+        return xb, f.value, cb[:self.n_cstr].copy(), stats
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

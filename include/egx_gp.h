@@ -607,11 +607,13 @@ int32_t egx_sgp_get_state(egx_sgp *sgp, double *theta, double *sigma2, double *n
  * whether the point is evaluated alone, at another position, or among others; value is bit for bit the same with and
  * without grad.
  *
- * Three DEVIATIONS from the reference (egobox_amd/csrc/infill_math.h):
+ * Four DEVIATIONS from the reference (egobox_amd/csrc/infill_math.h):
  *   1. log_ei_helper (utils/logei_helper.rs) is exact on the whole line: below u = -20 the asymptotic series replaces
  *      exp(z^2) erfc(z), which leaves double range near u = -37.6 in the reference (wrong or NaN down to u = -1e6).
  *   2. pof_grad (cstr_pof.rs:42-43) is the derivative of Phi((tol - mu) / sigma) for every tol, not only for tol = 0.
  *   3. the gradient uses the same sigma_weight as the value (solver_computations.rs:387-391 passes None).
+ *   4. the gradient of the upper trust bound of a constraint (egx_infill_eval_cstr under EGX_CSTR_UTB) uses every coordinate's
+ *      own d var / d x_c; upper_trust_bound_cstr (:242) takes the first coordinate's for all of them.
  * NaN in a point: value = +inf, gradient 0, for that point only (solver_infill_optim.rs:87-90).  m = 0 succeeds. */
 typedef struct egx_infill egx_infill;
 typedef enum { EGX_INFILL_EI = 0, EGX_INFILL_LOG_EI = 1, EGX_INFILL_WB2 = 2, EGX_INFILL_WB2S = 3 } egx_infill_criterion;
@@ -666,6 +668,55 @@ typedef struct {
 } egx_infill_stats;
 int32_t egx_infill_optimize(egx_infill *h, const double *lo /*d*/, const double *hi /*d*/, const double *x_start /*n_start*d*/,
                             int64_t n_start, int64_t max_eval, double *f_best, double *x_best /*d*/, egx_infill_stats *stats);
+
+/* ---- the constraint surrogates as constraints of the optimiser ---------------------------------------------------------
+ * EgorConfig defaults to cstr_infill = false, cstr_strategy = MeanConstraint (solver/egor_config.rs:255-256): the criterion is
+ * optimised WITHOUT the probability-of-feasibility factor (eval_infill_obj, solver_computations.rs:356-374) and every
+ * constraint surrogate is handed to the optimiser as a nonlinear inequality constraint c_j(x) <= 0
+ * (solver_infill_optim.rs:148-204): its scaled mean mu_j / scale_cstr_j (mean_cstr, :196-220) or its scaled upper trust bound
+ * (mu_j + 3 sigma_j) / scale_cstr_j (upper_trust_bound_cstr, :224-257).  A handle starts in EGX_CSTR_INFILL (everything above);
+ * in EGX_CSTR_MEAN / _UTB
+ *   - egx_infill_eval's value / grad are the objective model's criterion alone, -crit / scale: no factor, and `feasibility` is
+ *     not consulted (as eval_infill_obj); parts stay as they are.  The constraint surrogates run only when parts are asked
+ *     for, and under MEAN only their MEAN-ONLY launch sequence (no solve against the factor) unless parts->var or
+ *     parts->grad_var is asked for.  Their means keep the bits of the full sequence.
+ *   - egx_infill_scaling skips the factor (compute_infill_obj_scale with cstr_infill = false, :322-330) and stores the
+ *     scale_cstr it computes in the handle (an entry that is not positive and finite leaves the stored one).
+ *   - egx_infill_optimize is unchanged: it optimises whatever egx_infill_eval returns.
+ * scale_cstr: n_cstr positive finite values (EGX_ERR_INVALID_VALUE otherwise), or NULL to keep the stored ones (ones at first). */
+typedef enum { EGX_CSTR_INFILL = 0 /* pofs / logpofs in the objective */, EGX_CSTR_MEAN = 1, EGX_CSTR_UTB = 2 } egx_cstr_strategy;
+int32_t egx_infill_set_cstr_strategy(egx_infill *h, int32_t strategy, const double *scale_cstr /*n_cstr, or NULL: keep*/);
+int32_t egx_infill_get_cstr_strategy(egx_infill *h, int32_t *strategy, double *scale_cstr /*n_cstr or NULL*/);
+/* What the optimiser sees at m points: value (m) as egx_infill_eval's in these modes, cstr[i * n_cstr + j] the constraint values,
+ * and optionally their x-gradients grad (m x d), grad_cstr[(i * n_cstr + j) * d + c].  Under MEAN the constraint surrogates'
+ * experts run the mean-only sequence; under UTB the full one.  A NaN / infinite point: value = +inf, cstr = +inf, zero
+ * gradients.  A point's bits do not depend on its companions or its position.  EGX_ERR_INVALID_VALUE on an EGX_CSTR_INFILL
+ * handle.  n_cstr = 0 is allowed (cstr / grad_cstr untouched, may be NULL); m = 0 succeeds. */
+int32_t egx_infill_eval_cstr(egx_infill *h, const double *xq, int64_t m, double *value /*m*/, double *cstr /*m*n_cstr*/,
+                             double *grad /*m*d or NULL*/, double *grad_cstr /*m*n_cstr*d or NULL*/);
+/* The multistart of solver_infill_optim.rs:217-236 with the constraints: one general-constraint COBYLA per start (Powell's
+ * method with his full trust-region subproblem, egobox_amd/csrc/cobyla.h; rhobeg 0.5, ftol_rel = ftol_abs = 1e-4, no
+ * constraint tolerances given to it -- optimizers/optimizer.rs:123-126 --, at most max_eval evaluations each; max_eval <= 0:
+ * min(10 n_start d, 2000)), all starts in LOCK-STEP: a round is ONE values-only egx_infill_eval_cstr of the trial points, and
+ * every start walks bit for bit the points it walks alone.
+ * DEVIATION in what is returned.  The reference takes every run's final vertex and the smallest objective over the starts,
+ * feasible or not (:229-232).  Here the best EVALUATED point is returned under this ordering: a point is feasible when
+ * c_j <= cstr_tol_j / scale_cstr_j for every j (the handle's cstr_tols, Egor's acceptance tolerance); feasible beats infeasible;
+ * among feasible points the smaller objective wins (a value at or beyond 1e30 counting as +inf), among infeasible ones the
+ * smaller max_j (c_j - cstr_tol_j / scale_cstr_j); the first point within a start and the first start win ties.
+ * *f_best and c_best are bit for bit egx_infill_eval_cstr at x_best; stats->feasible / violation (that maximum; 0 without
+ * constraints) describe the returned point.  An infeasible best point is EGX_SUCCESS with feasible = 0; no finite objective
+ * value at all: *f_best = +inf and EGX_ERR_NO_FINITE_START.  EGX_ERR_INVALID_VALUE on an EGX_CSTR_INFILL handle and for the
+ * arguments egx_infill_optimize refuses.  n_cstr = 0: a bound-constrained run of the same class (c_best may be NULL). */
+typedef struct {
+    int64_t rounds, best_start;
+    int32_t feasible;
+    double violation;
+    int64_t *evals; /* n_start evaluation counts, or NULL */
+} egx_infill_cstr_stats;
+int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo /*d*/, const double *hi /*d*/, const double *x_start /*n_start*d*/,
+                                 int64_t n_start, int64_t max_eval, double *f_best, double *x_best /*d*/, double *c_best /*n_cstr*/,
+                                 egx_infill_cstr_stats *stats);
 
 /* ---- ... on mixtures of experts -------------------------------------------------------------------------------------
  * What EGO holds for its objective and every constraint is a clustered surrogate (GpMixture, crates/moe/src/algorithm.rs):

@@ -649,6 +649,55 @@ class InfillObjective {
         o.best_start = st.best_start;
         return o;
     }
+    // ---- the constraint surrogates as constraints of the optimiser (cstr_infill = false; solver_infill_optim.rs:148-204)
+    void set_cstr_strategy(egx_cstr_strategy strategy, const std::vector<double> &scale_cstr = {}) {
+        if (!scale_cstr.empty() && (int64_t)scale_cstr.size() != k_)
+            throw InvalidValueError(EGX_ERR_INVALID_VALUE, "InfillObjective: one scale per constraint");
+        check(egx_infill_set_cstr_strategy(h_.get(), strategy, scale_cstr.empty() ? nullptr : scale_cstr.data()));
+    }
+    std::pair<egx_cstr_strategy, std::vector<double>> cstr_strategy() const {
+        int32_t s = 0;
+        std::vector<double> sc((size_t)(k_ > 0 ? k_ : 1), 1.0);
+        check(egx_infill_get_cstr_strategy(h_.get(), &s, sc.data()));
+        sc.resize((size_t)k_);
+        return {(egx_cstr_strategy)s, std::move(sc)};
+    }
+    struct Constraints {
+        std::vector<double> value, cstr, grad, grad_cstr;  // m, m k, m d, m k d (the gradients empty unless asked for)
+    };
+    Constraints constraints(const double *x, int64_t m, bool grad = false) const {
+        Constraints c;
+        const size_t mm = (size_t)m, k = (size_t)k_, d = (size_t)d_;
+        c.value.resize(mm), c.cstr.resize(mm * k + 1);
+        if (grad) c.grad.resize(mm * d), c.grad_cstr.resize(mm * k * d + 1);
+        check(egx_infill_eval_cstr(h_.get(), x, m, c.value.data(), c.cstr.data(), grad ? c.grad.data() : nullptr,
+                                   grad ? c.grad_cstr.data() : nullptr));
+        c.cstr.resize(mm * k);
+        if (grad) c.grad_cstr.resize(mm * k * d);
+        return c;
+    }
+    struct ConstrainedOptimum {
+        double f = 0.0, violation = 0.0;
+        std::vector<double> x, c;
+        std::vector<int64_t> evals;
+        int64_t rounds = 0, best_start = 0;
+        bool feasible = false, finite = true;
+    };
+    ConstrainedOptimum optimize_constrained(const double *lo, const double *hi, const double *x_start, int64_t n_start,
+                                            int64_t max_eval = 0) {
+        ConstrainedOptimum o;
+        o.x.assign((size_t)d_, 0.0);
+        o.c.assign((size_t)k_ + 1, 0.0);
+        o.evals.assign((size_t)n_start, 0);
+        egx_infill_cstr_stats st{0, 0, 0, 0.0, o.evals.data()};
+        const int32_t rc = egx_infill_optimize_cstr(h_.get(), lo, hi, x_start, n_start, max_eval, &o.f, o.x.data(), o.c.data(), &st);
+        if (rc != EGX_ERR_NO_FINITE_START) check(rc);
+        o.c.resize((size_t)k_);
+        o.finite = rc == EGX_SUCCESS;
+        o.rounds = st.rounds, o.best_start = st.best_start;
+        o.feasible = st.feasible != 0, o.violation = st.violation;
+        return o;
+    }
     egx_infill *handle() const { return h_.get(); }
 
   private:

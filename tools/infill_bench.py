@@ -13,6 +13,15 @@ mixture entry points) with the same host arithmetic; fused = the handle of egx_i
 profiles/infill_mix_eval_ab.txt.
 
     python tools/infill_bench.py --mix [--out profiles/infill_mix_eval_ab.txt] [--reps 15]
+
+--cstr times ONE LOCK-STEP ROUND of the constrained multistart -- a values-only evaluation of 20 trial points -- on one handle
+in its three constraint strategies: MEAN and UTB (egx_infill_eval_cstr: the objective model and the constraint values; under
+MEAN the constraint models run the mean-only sequence) and INFILL (egx_infill_eval: the constraints folded into the
+objective, the full sequence for every model).  The INFILL leg uses only entry points that exist without the strategies: on
+a commit without them the tool times that leg alone, which is the yardstick.  Legs alternated (infill, mean, utb, infill
+again), medians, written to profiles/infill_cstr_round.txt.
+
+    python tools/infill_bench.py --cstr [--out profiles/infill_cstr_round.txt] [--reps 15]
 """
 import argparse
 import os
@@ -101,11 +110,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--mix", action="store_true", help="the mixture leg (k = 3 experts, smooth) instead of the single-model legs")
+    ap.add_argument("--cstr", action="store_true", help="one lock-step round in MEAN, UTB and INFILL mode on one handle")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
+        args.out = os.path.join(ROOT, "profiles", "infill_cstr_round.txt" if args.cstr else
+                                "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
     def emit(s):
@@ -121,6 +132,32 @@ def main():
         for _ in range(10):
             obj.value(xq)
             obj.value_and_grad(xq)
+        return
+    if args.cstr:
+        m = 20
+        emit("# one lock-step round of the constrained multistart: a values-only evaluation of %d trial points on ONE handle in its" % m)
+        emit("# three constraint strategies; LogEI; constraint models of the objective's size; median ms over %d calls after 3" % args.reps)
+        emit("# warm-ups; legs alternated (infill, mean, utb, infill again: the two infill runs show the spread)")
+        emit("# n d n_cstr m infill_a_ms mean_ms utb_ms infill_b_ms infill_spread mean/infill utb/infill 1/(1+n_cstr)")
+        for n, d, k in ((2048, 8, 1), (4096, 8, 2), (4096, 8, 4)):
+            hs, ys = build(n, d, k)
+            obj = egx.InfillObjective(hs[0], hs[1:], [0.0] * k, criterion=egx.LOG_EI, fmin=float(np.quantile(ys[0], 0.05)))
+            xq = np.random.default_rng(1).random((m, d))
+            has = hasattr(obj, "set_cstr_strategy")
+
+            def leg(strategy):
+                if not has:
+                    return float("nan") if strategy != "infill" else median_ms(lambda: obj.value(xq), args.reps)
+                obj.set_cstr_strategy(strategy)
+                return median_ms((lambda: obj.value(xq)) if strategy == "infill" else (lambda: obj.constraints(xq)), args.reps)
+            ia, me, ut, ib = leg("infill"), leg("mean"), leg("utb"), leg("infill")
+            i0 = min(ia, ib)
+            emit(f"{n} {d} {k} {m} {ia:.3f} {me:.3f} {ut:.3f} {ib:.3f} {abs(ia - ib):.3f} {me / i0:.3f} {ut / i0:.3f} {1.0 / (1 + k):.3f}")
+            obj.close()
+            for h in hs:
+                h.close()
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
         return
     if args.mix:
         kx = 3
