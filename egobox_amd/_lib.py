@@ -77,6 +77,14 @@ class InfillCstrStats(C.Structure):
                 ("evals", c_int64_p)]
 
 
+class XTypeC(C.Structure):
+    """egx_xtype"""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("values", c_double_p)]
+
+
+_XT_P = C.POINTER(XTypeC)
+
+
 class Timings(C.Structure):
     _fields_ = [("corr_build_ms", C.c_double), ("potrf_ms", C.c_double), ("potrf_syrk_ms", C.c_double),
                 ("solve_ms", C.c_double), ("host_ms", C.c_double), ("total_ms", C.c_double),
@@ -97,6 +105,18 @@ SIGNATURES = [
     ("egx_normalize", C.c_int32, [c_double_p, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p]),
     ("egx_regression_ncols", C.c_int64, [C.c_int32, C.c_int64]),
     ("egx_regression_basis", C.c_int32, [C.c_int32, c_double_p, C.c_int64, C.c_int64, c_double_p]),
+    ("egx_mixint_unfolded_dim", C.c_int32, [_XT_P, C.c_int32, c_int64_p]),
+    ("egx_mixint_continuous_limits", C.c_int32, [_XT_P, C.c_int32, c_double_p]),
+    ("egx_mixint_unfold", C.c_int32, [_XT_P, C.c_int32, c_double_p, C.c_int64, c_double_p]),
+    ("egx_mixint_fold", C.c_int32, [_XT_P, C.c_int32, c_double_p, C.c_int64, c_double_p]),
+    ("egx_mixint_cast", C.c_int32, [_XT_P, C.c_int32, c_double_p, C.c_int64, c_double_p]),
+    ("egx_mixint_to_discrete", C.c_int32, [_XT_P, C.c_int32, c_double_p, C.c_int64, c_double_p]),
+    ("egx_gp_set_xtypes", C.c_int32, [C.c_void_p, _XT_P, C.c_int32]),
+    ("egx_gp_get_xtypes", C.c_int32, [C.c_void_p, _XT_P, C.c_int32, c_int32_p, c_double_p, c_int64_p]),
+    ("egx_gmx_predict_probas_mixint", C.c_int32, [C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_double,
+                                                  c_double_p, C.c_int64, c_double_p, _XT_P, C.c_int32]),
+    ("egx_gmx_predict_probas_derivatives_mixint", C.c_int32, [C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64,
+                                                              C.c_double, c_double_p, C.c_int64, c_double_p, _XT_P, C.c_int32]),
     ("egx_gp_create", C.c_int32, [C.POINTER(GpConfig), c_double_p, c_double_p, C.c_int64, C.c_int64,
                                   C.POINTER(C.c_void_p)]),
     ("egx_gp_destroy", None, [C.c_void_p]),

@@ -7,6 +7,7 @@
 
 #include "../../include/egx_gp.h"
 #include "schedule.h"
+#include "mixint.h"
 
 namespace egx {
 
@@ -62,6 +63,8 @@ struct PosteriorBatchPtrs {
     const double *coef[kLockstepMax];   // d x hcols
     const double *gamma[kLockstepMax];  // n_pad                                          launch_predict_mean
     const double *ftT[kLockstepMax];    // p rows, ldf apart                              launch_row_reduce
+    const mixint::Col *spec[kLockstepMax];  // the member's typed columns (mixint.h: d of them | the Ord values) or nullptr: its
+                                            // queries are cast where launch_normalize_queries reads them
 };
 struct PosteriorBatch {
     int count = 1;
@@ -79,13 +82,14 @@ inline int launch_cross_corr(hipStream_t s, int corr, const double *xqT, int64_t
     return launch_cross_corr(s, corr, pb, xqT, ldq, m_pad, ldx, n_pad, d, hcols, R, ld);
 }
 // raw row-major queries -> normalised k-major (d x ldq, zero padded to m_pad); par = x_mean (d) | x_std (d) on the device;
-// member z reads its m raw rows at xq + z * sxq
+// member z reads its m raw rows at xq + z * sxq.  A member with ptrs.spec gets every coordinate cast to its nearest admissible
+// discrete value (mixint.h) as it is read: the typed instantiation of the same kernel, the same single launch
 int launch_normalize_queries(hipStream_t s, const PosteriorBatch &pb, const double *xq, int64_t sxq, int m, int d, double *xqT,
                              int64_t ldq, int m_pad);
 inline int launch_normalize_queries(hipStream_t s, const double *xq, int m, int d, const double *par, double *xqT, int64_t ldq,
-                                    int m_pad) {
+                                    int m_pad, const mixint::Col *spec = nullptr) {
     PosteriorBatch pb;
-    pb.ptrs.par[0] = par;
+    pb.ptrs.par[0] = par, pb.ptrs.spec[0] = spec;
     return launch_normalize_queries(s, pb, xq, 0, m, d, xqT, ldq, m_pad);
 }
 // racc[split * m_pad + q] = partial sum_i k(xq, x_i) * gamma[i] over the split's training range (gamma zero padded to
@@ -196,8 +200,11 @@ namespace infill {
 struct Params;
 }
 // raw rows (mt x d, mt <= kTile) -> normalised k-major tile xqT (d x kTile); par = x_mean (d) | x_std (d); points with a
-// non-finite coordinate are zeroed and flagged (flag: kTile ints or nullptr), the slots beyond mt are zero
-int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag);
+// non-finite coordinate are zeroed and flagged (flag: kTile ints or nullptr), the slots beyond mt are zero.
+// spec != nullptr (mixint.h): the coordinates are cast as they are read, and xcast (mt x d, or nullptr) receives the tile's CAST
+// raw rows -- what k_infill_mix reads in place of xq, so that the responsibilities see the cast point as the experts do
+int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag,
+                          const mixint::Col *spec = nullptr, double *xcast = nullptr);
 struct InfillTrend {
     int p = 1, rp = 0, msplit = 1;
     const double *xqT = nullptr;   // d x kTile
@@ -282,8 +289,10 @@ int launch_gmm_estep(hipStream_t s, const GmmLaunch &g);
 int launch_gmm_mstep(hipStream_t s, const GmmLaunch &g, double reg_covar);
 // The fitted mixture at m raw points (m x d on the device), one lane per point on the calling thread's default stream: the
 // responsibilities (out: m x k) or, deriv, their x-derivatives (m x k x d).  blk = gmx_pack's block (gmx_point.h) on the device,
-// lds = the dynamic LDS the caller has sized and bounded.
-int launch_gmx_probas(bool deriv, const double *xq, int64_t m, int d, int k, const double *blk, size_t lds, double *out);
+// lds = the dynamic LDS the caller has sized and bounded.  spec != nullptr (mixint.h, on the device): the points are cast as they
+// are staged.
+int launch_gmx_probas(bool deriv, const double *xq, int64_t m, int d, int k, const double *blk, size_t lds, double *out,
+                      const mixint::Col *spec = nullptr);
 
 // ---- kernels_chol.hip -------------------------------------------------------
 // In-place blocked right-looking Cholesky of the leading n_pad x n_pad block (lower), applied to

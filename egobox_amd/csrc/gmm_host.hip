@@ -49,6 +49,18 @@ int gmx_upload(const std::string &who, int32_t device, const double *weights, co
     return EGX_SUCCESS;
 }
 
+// the typed calls' device table (mixint.h), on the device gmx_upload has selected; nothing for an untyped call
+int spec_upload(const egx::MixSpec &sp, egx::DevBuf &d_spec) {
+    if (sp.empty()) return EGX_SUCCESS;
+    const std::vector<double> tab = sp.table();
+    EGX_RC(d_spec.alloc(tab.size()));
+    EGX_HIP_CHECK(hipMemcpy(d_spec.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    return EGX_SUCCESS;
+}
+const egx::mixint::Col *spec_ptr(const egx::MixSpec &sp, const egx::DevBuf &d_spec) {
+    return sp.empty() ? nullptr : reinterpret_cast<const egx::mixint::Col *>(d_spec.p);
+}
+
 }  // namespace
 
 extern "C" {
@@ -256,25 +268,34 @@ int32_t egx_gmx_precisions_chol(const double *covariances, int64_t k, int64_t d,
 
 int32_t egx_gmx_predict_probas(int32_t device, const double *weights, const double *means, const double *precisions_chol,
                                int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m, double *probas) {
+    return egx_gmx_predict_probas_mixint(device, weights, means, precisions_chol, k, d, heaviside_factor, xq, m, probas, nullptr, 0);
+}
+
+int32_t egx_gmx_predict_probas_mixint(int32_t device, const double *weights, const double *means, const double *precisions_chol,
+                                      int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m, double *probas,
+                                      const egx_xtype *xt, int32_t nx) {
     if (!weights || !means || !precisions_chol || k < 1 || d < 1 || d > 4096 || m < 0 || (m > 0 && (!xq || !probas)) ||
         !(heaviside_factor > 0.0)) {
         set_error("egx_gmx_predict_probas: bad arguments");
         return EGX_ERR_INVALID_VALUE;
     }
+    egx::MixSpec sp;
+    if (nx != 0) EGX_RC(egx::mixspec_build("egx_gmx_predict_probas_mixint", xt, nx, d, sp));
     if (m == 0) return EGX_SUCCESS;
     if (k == 1) {  // gaussian_mixture.rs:115-116
         for (int64_t a = 0; a < m; a++) probas[a] = 1.0;
         return EGX_SUCCESS;
     }
-    egx::DevBuf d_x, d_blk, d_out;
+    egx::DevBuf d_x, d_blk, d_out, d_spec;
     EGX_RC(gmx_upload("egx_gmx_predict_probas", device, weights, means, precisions_chol, k, d, heaviside_factor, xq, m, d_x, d_blk));
+    EGX_RC(spec_upload(sp, d_spec));
     EGX_RC(d_out.alloc((size_t)m * k));
     const size_t lds = sizeof(double) * 64 * (size_t)(d | 1);
     if (lds > 160 * 1024) {
         set_error("egx_gmx_predict_probas: d too large for one workgroup's LDS");
         return EGX_ERR_INVALID_VALUE;
     }
-    EGX_RC(egx::launch_gmx_probas(false, d_x.p, m, (int)d, (int)k, d_blk.p, lds, d_out.p));
+    EGX_RC(egx::launch_gmx_probas(false, d_x.p, m, (int)d, (int)k, d_blk.p, lds, d_out.p, spec_ptr(sp, d_spec)));
     EGX_HIP_CHECK(hipMemcpy(probas, d_out.p, sizeof(double) * (size_t)m * k, hipMemcpyDeviceToHost));
     return EGX_SUCCESS;
 }
@@ -282,22 +303,32 @@ int32_t egx_gmx_predict_probas(int32_t device, const double *weights, const doub
 int32_t egx_gmx_predict_probas_derivatives(int32_t device, const double *weights, const double *means,
                                            const double *precisions_chol, int64_t k, int64_t d, double heaviside_factor,
                                            const double *xq, int64_t m, double *dprobas) {
+    return egx_gmx_predict_probas_derivatives_mixint(device, weights, means, precisions_chol, k, d, heaviside_factor, xq, m, dprobas,
+                                                     nullptr, 0);
+}
+
+int32_t egx_gmx_predict_probas_derivatives_mixint(int32_t device, const double *weights, const double *means,
+                                                  const double *precisions_chol, int64_t k, int64_t d, double heaviside_factor,
+                                                  const double *xq, int64_t m, double *dprobas, const egx_xtype *xt, int32_t nx) {
     if (!weights || !means || !precisions_chol || k < 1 || d < 1 || m < 0 || (m > 0 && (!xq || !dprobas)) ||
         !(heaviside_factor > 0.0)) {
         set_error("egx_gmx_predict_probas_derivatives: bad arguments");
         return EGX_ERR_INVALID_VALUE;
     }
+    egx::MixSpec sp;
+    if (nx != 0) EGX_RC(egx::mixspec_build("egx_gmx_predict_probas_derivatives_mixint", xt, nx, d, sp));
     if (m == 0) return EGX_SUCCESS;
     const size_t lds = sizeof(double) * 64 * (size_t)(3 * (d | 1) + (k | 1));
     if (lds > 160 * 1024) {
         set_error("egx_gmx_predict_probas_derivatives: d / k too large for one workgroup's LDS (3 d + k <= 320)");
         return EGX_ERR_INVALID_VALUE;
     }
-    egx::DevBuf d_x, d_blk, d_out;
+    egx::DevBuf d_x, d_blk, d_out, d_spec;
     EGX_RC(gmx_upload("egx_gmx_predict_probas_derivatives", device, weights, means, precisions_chol, k, d, heaviside_factor, xq, m,
                       d_x, d_blk));
+    EGX_RC(spec_upload(sp, d_spec));
     EGX_RC(d_out.alloc((size_t)m * k * d));
-    EGX_RC(egx::launch_gmx_probas(true, d_x.p, m, (int)d, (int)k, d_blk.p, lds, d_out.p));
+    EGX_RC(egx::launch_gmx_probas(true, d_x.p, m, (int)d, (int)k, d_blk.p, lds, d_out.p, spec_ptr(sp, d_spec)));
     EGX_HIP_CHECK(hipMemcpy(dprobas, d_out.p, sizeof(double) * (size_t)m * k * d, hipMemcpyDeviceToHost));
     return EGX_SUCCESS;
 }

@@ -147,6 +147,31 @@ struct EvalResult {
     std::vector<double> ft_qr_r;  // p x p row-major
 };
 
+// A validated mixed-integer spec (egx_gp_set_xtypes, the egx_mixint_* helpers; mixint_host.hip): the caller's columns with the
+// Ord values copied (xt[j].values is NOT kept), and the per-unfolded-column table mixint.h's arithmetic reads
+struct MixSpec {
+    std::vector<egx_xtype> xt;
+    std::vector<mixint::Col> cols;  // d
+    std::vector<double> vals;       // every Ord column's values, in column order
+    bool empty() const { return cols.empty(); }
+    bool same(const MixSpec &o) const {
+        return cols.size() == o.cols.size() && vals.size() == o.vals.size() &&
+               (cols.empty() || std::memcmp(cols.data(), o.cols.data(), sizeof(mixint::Col) * cols.size()) == 0) &&
+               (vals.empty() || std::memcmp(vals.data(), o.vals.data(), sizeof(double) * vals.size()) == 0);
+    }
+    // the device table: the columns, then the values
+    std::vector<double> table() const {
+        std::vector<double> t(2 * cols.size() + vals.size());
+        static_assert(sizeof(mixint::Col) == 2 * sizeof(double), "two doubles per column");
+        if (!cols.empty()) std::memcpy(t.data(), cols.data(), sizeof(mixint::Col) * cols.size());
+        if (!vals.empty()) std::memcpy(t.data() + 2 * cols.size(), vals.data(), sizeof(double) * vals.size());
+        return t;
+    }
+};
+// validates (EGX_ERR_INVALID_VALUE / _UNSUPPORTED with a message that starts with `who` and names the entry) and builds;
+// d_expect >= 0: the unfolded dimension must be it
+int mixspec_build(const char *who, const egx_xtype *xt, int32_t nx, int64_t d_expect, MixSpec &out);
+
 }  // namespace egx
 
 namespace egx {
@@ -212,6 +237,9 @@ struct egx_gp : egx::HandleRes {
     uint64_t fit_epoch = 0, winv_epoch = ~(uint64_t)0, trend_epoch = ~(uint64_t)0;
     uint64_t winv_fail_epoch = ~(uint64_t)0;  // fit for which the C^-T cache could not be built (batched path serves it)
     egx_timings timings{};
+    // mixed-integer spec (egx_gp_set_xtypes; empty: a continuous model) and its device table (mixint.h: d columns | Ord values)
+    egx::MixSpec xspec;
+    egx::DevMem<double> d_xspec;
 };
 
 namespace egx {
@@ -230,6 +258,14 @@ int fit_reduce_finalize(egx_gp *gp, const double *theta_base, const std::vector<
 // workspace i's hand-off words in slab_I
 inline int *dev_sync(const egx_gp *gp, int i) { return gp->slab_I + gp->sync_off + (int64_t)i * gp->stride_S; }
 inline double *dev_xs_fit(const egx_gp *gp) { return gp->d_xT + (size_t)gp->d * gp->n_pad; }
+// the device table of the handle's xtypes, or nullptr: what the kernels that read raw query rows cast by
+inline const egx::mixint::Col *dev_spec(const egx_gp *gp) {
+    return gp->xspec.empty() ? nullptr : reinterpret_cast<const egx::mixint::Col *>(gp->d_xspec.p);
+}
+// coordinate j of the query row as the model sees it: cast when the handle carries xtypes (the same text as the device's)
+inline double query_coord(const egx_gp *gp, const double *row, int j) {
+    return gp->xspec.empty() ? row[j] : egx::mixint::cast_coord(gp->xspec.cols.data(), gp->xspec.vals.data(), row, 1, j);
+}
 inline double *dev_xnorm(const egx_gp *gp) { return gp->d_fit_coef + (size_t)gp->d * (gp->has_w ? gp->h : 1); }
 
 namespace egx {

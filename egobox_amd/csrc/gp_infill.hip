@@ -60,6 +60,7 @@ struct egx_infill {
     bool tol_on_device = false;
     // buffers of a call (grow-only): the whole call's points and results, then the scratch of ONE (tile, model) step
     DevBuf xraw, flag, mean, var, gmean, gvar, value, grad;
+    DevBuf xcast;  // models with xtypes and a mixture among the surrogates: the call's CAST raw points (k_infill_prepare_mixint)
     DevBuf xqT, racc, RT, s0, sl, Wt, dneg, out_y, out_v;
     // the experts of the mixtures: their tables (slot-major like mean / var), d p / d x of one tile, the diagnostics of a call
     DevBuf emean, evar, egmean, egvar, dprob, dg_probas, dg_dprobas;
@@ -120,6 +121,17 @@ int check_shapes(egx_infill *h) {
     return EGX_SUCCESS;
 }
 
+// Mixed-integer models: every expert of every surrogate carries the same xtypes as expert 0 of the objective, or none does -- the
+// points of a call are one design space.  Read from the models at EVERY call (as their fitted state is), under their locks.
+int check_specs(const egx_infill *h) {
+    for (size_t e = 1; e < h->models.size(); e++)
+        if (!h->models[e]->xspec.same(h->models[0]->xspec)) {
+            set_error("infill: " + who(h, (int)e) + " and " + who(h, 0) + " carry different xtypes (egx_gp_set_xtypes): all or none, the same spec");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    return EGX_SUCCESS;
+}
+
 // what egx_infill_eval_experts asks for: the parts of surrogate j's experts and its responsibilities (host pointers, any nullptr)
 struct ExpertDiag {
     int j = 0;
@@ -134,7 +146,9 @@ int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool w
     egx_gp *gp = h->models[j];
     const int n = gp->n, n_pad = gp->n_pad;
     const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
-    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag));
+    // (xtypes: cast in the same launch; the expert that writes the flags leaves the cast raw tile for k_infill_mix as well)
+    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag, dev_spec(gp),
+                                 flag && h->n_eslots > 0 && dev_spec(gp) ? h->xcast.p + (size_t)t0 * d : nullptr));
     // r . gamma in split partial sums (algorithm.rs:260-262), before the solve overwrites r
     EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
                                gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
@@ -166,7 +180,7 @@ int expert_tile_mean(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, b
     egx_gp *gp = h->models[j];
     const int n = gp->n, n_pad = gp->n_pad;
     const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
-    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag));
+    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag, dev_spec(gp)));
     EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
                                gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
                                gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
@@ -197,6 +211,7 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     }
     const int ne = (int)h->models.size(), nm = (int)h->surr.size(), k = nm - 1, d = h->d;
     EGX_RC(check_fitted(h));
+    EGX_RC(check_specs(h));
     if (m == 0) return EGX_SUCCESS;
     const bool want_g = grad || (parts && (parts->grad_mean || parts->grad_var)) ||
                         (diag && (diag->gmean || diag->gvar || diag->dprobas)) || (co && co->gcstr);
@@ -237,6 +252,8 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
         ns_max = std::max(ns_max, xgrad_splits(gp->n, kTile));
     }
     EGX_RC(h->xraw.alloc((size_t)m * d));
+    const bool typed = !h->models[0]->xspec.empty();
+    if (typed && h->n_eslots > 0) EGX_RC(h->xcast.alloc((size_t)m * d));
     EGX_RC(h->flag.alloc((size_t)(M + 1) / 2));
     EGX_RC(h->mean.alloc((size_t)nm * M));
     EGX_RC(h->var.alloc((size_t)nm * M));
@@ -298,7 +315,7 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
             if (lone) continue;
             InfillMix mx;
             mx.mt = mt, mx.d = d, mx.k = sg.k, mx.smooth = sg.smooth, mx.want_g = want_g;
-            mx.xq = h->xraw.p + (size_t)t0 * d, mx.flag = flag + t0;
+            mx.xq = (typed ? h->xcast.p : h->xraw.p) + (size_t)t0 * d, mx.flag = flag + t0;
             mx.means = sg.d_gmx.p, mx.precs = sg.d_gmx.p + (size_t)sg.k * d, mx.par = mx.precs + (size_t)sg.k * d * d;
             mx.emean = h->emean.p + (size_t)sg.eslot * M + t0, mx.evar = h->evar.p + (size_t)sg.eslot * M + t0;
             mx.estride = M;
@@ -404,6 +421,7 @@ int config_ok(const egx_infill_config &cfg) {
 int finish_create(egx_infill *h, const egx_infill_config &cfg) {
     EGX_RC(check_shapes(h));
     EGX_RC(check_fitted(h));
+    EGX_RC(check_specs(h));
     h->prm.kind = cfg.criterion;
     h->prm.fmin = cfg.fmin;
     h->prm.sigma_weight = cfg.sigma_weight;

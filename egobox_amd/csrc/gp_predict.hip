@@ -19,12 +19,12 @@ static int upload_queries(egx_gp *gp, const double *xq, int64_t m0, int m, int m
     EGX_RC(d_xraw.alloc((size_t)m * d));
     EGX_RC(d_xqT.alloc((size_t)d * m_pad));
     EGX_HIP_CHECK(hipMemcpyAsync(d_xraw.p, xq + (size_t)m0 * d, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, s));
-    EGX_RC(launch_normalize_queries(s, d_xraw.p, m, d, dev_xnorm(gp), d_xqT.p, m_pad, m_pad));
-    if (gp->mean >= 1) {
+    EGX_RC(launch_normalize_queries(s, d_xraw.p, m, d, dev_xnorm(gp), d_xqT.p, m_pad, m_pad, dev_spec(gp)));
+    if (gp->mean >= 1) {  // (a model with xtypes: the cast coordinates, as the device forms them)
         xn.resize((size_t)m * d);
         const double *src = xq + (size_t)m0 * d;
         for (int a = 0; a < m; a++)
-            for (int j = 0; j < d; j++) xn[(size_t)a * d + j] = (src[(size_t)a * d + j] - gp->x_mean[j]) / gp->x_std[j];
+            for (int j = 0; j < d; j++) xn[(size_t)a * d + j] = (query_coord(gp, src + (size_t)a * d, j) - gp->x_mean[j]) / gp->x_std[j];
     } else {
         xn.clear();
     }
@@ -73,6 +73,7 @@ static void posterior_batch(egx_gp *const *gps, int len, PosteriorBatch &pb) {
         pb.ptrs.coef[j] = g->d_fit_coef;
         pb.ptrs.gamma[j] = g->d_gamma;
         pb.ptrs.ftT[j] = g->ws[0].M + (size_t)g->n_pad * g->ld;
+        pb.ptrs.spec[j] = dev_spec(g);
     }
 }
 // ... of a run of `len` models of one shape whose factors sit at one stride (members of a group in consecutive slots; a lone
@@ -249,7 +250,7 @@ int predict_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m,
             for (int a = 0; a < mc; a++) {
                 // the trend needs the normalised coordinates (Linear / Quadratic): the same subtraction and division as the device's
                 if (gp->mean >= 1)
-                    for (int c = 0; c < d; c++) xn[c] = (raw[(size_t)a * d + c] - gp->x_mean[c]) / gp->x_std[c];
+                    for (int c = 0; c < d; c++) xn[c] = (query_coord(gp, raw + (size_t)a * d, c) - gp->x_mean[c]) / gp->x_std[c];
                 hm::regression_row(gp->mean, gp->mean >= 1 ? xn.data() : nullptr, d, f.data());
                 if (yout) {
                     double fb = 0.0, rg = 0.0;
@@ -358,7 +359,7 @@ static int small_path_query(egx_gp *gp, const double *xq, int64_t a, std::vector
     xn.resize(d);
     slab.assign((size_t)d * kTile, 0.0);
     for (int j = 0; j < d; j++) {
-        xn[j] = (xq[(size_t)a * d + j] - gp->x_mean[j]) / gp->x_std[j];
+        xn[j] = (query_coord(gp, xq + (size_t)a * d, j) - gp->x_mean[j]) / gp->x_std[j];
         slab[(size_t)j * kTile] = xn[j];
     }
     EGX_HIP_CHECK(hipMemcpyAsync(gp->sp_xq, slab.data(), sizeof(double) * slab.size(), hipMemcpyHostToDevice, gp->ws[0].stream));

@@ -95,7 +95,7 @@ int cov_prepare(egx_gp *gp, const double *xq, int m, CovBufs &b) {
     EGX_RC(b.xraw.alloc((size_t)m * d));
     EGX_RC(b.xqT.alloc((size_t)d * m_pad));
     EGX_HIP_CHECK(hipMemcpyAsync(b.xraw.p, xq, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, st));
-    EGX_RC(launch_normalize_queries(st, b.xraw.p, m, d, dev_xnorm(gp), b.xqT.p, m_pad, m_pad));
+    EGX_RC(launch_normalize_queries(st, b.xraw.p, m, d, dev_xnorm(gp), b.xqT.p, m_pad, m_pad, dev_spec(gp)));
     // rt (algorithm.rs:337-350), held transposed: the predict_var solve.  Its columns n .. n_pad - 1 (padding of the training
     // set) are not part of rt and are zeroed before the Gram matrix contracts over them.
     EGX_RC(b.RT.alloc((size_t)m_pad * n_pad));

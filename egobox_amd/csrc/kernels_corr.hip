@@ -297,6 +297,11 @@ __global__ void k_scale_rows(const double *__restrict__ xT, int64_t ldx, int d, 
 // the writes are contiguous.  par = x_mean (d) then x_std (d).
 // blockIdx.z = member of a posterior batch (PosteriorBatchPtrs): its own normalisation, its query block sxq / sq doubles
 // behind the previous member's.
+// TYPED: a member with b.spec (mixint.h) gets its coordinates cast where they are read.  An Int / Ord coordinate is cast from
+// itself; a coordinate of an Enum group needs the group's first maximum, and takes it over the WHOLE group from the raw row in
+// global memory (a group may straddle the boundary between two chunks of kCorrDC dimensions: the chunk's part is not enough).
+// The untyped instantiation is the kernel as it was.
+template <bool TYPED>
 __global__ __launch_bounds__(256) void k_normalize_queries(PosteriorBatchPtrs b, const double *__restrict__ xq_all, int64_t sxq,
                                                            int m, int d, double *__restrict__ xqT_all, int64_t ldq, int64_t sq) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -309,9 +314,13 @@ __global__ __launch_bounds__(256) void k_normalize_queries(PosteriorBatchPtrs b,
     const int c0 = blockIdx.y * kCorrDC;
     const int dn = (d - c0 < kCorrDC) ? (d - c0) : kCorrDC;
     const int ds = dn | 1;  // odd row stride: the transposed reads below spread over the banks
+    const mixint::Col *__restrict__ spec = TYPED ? b.spec[blockIdx.z] : nullptr;
     for (int e = tid; e < rows * dn; e += 256) {
         const int i = e / dn, k = e - i * dn;
-        sm[i * ds + k] = xq[(int64_t)(q0 + i) * d + c0 + k];
+        if (TYPED && spec)
+            sm[i * ds + k] = mixint::cast_coord(spec, mixint::table_values(spec, d), xq + (int64_t)(q0 + i) * d, 1, c0 + k);
+        else
+            sm[i * ds + k] = xq[(int64_t)(q0 + i) * d + c0 + k];
     }
     __syncthreads();
     for (int e = tid; e < dn * 64; e += 256) {
@@ -1078,8 +1087,11 @@ int launch_normalize_queries(hipStream_t s, const PosteriorBatch &pb, const doub
                              int64_t ldq, int m_pad) {
     if (!posterior_count_ok(pb)) return EGX_ERR_INVALID_VALUE;
     const size_t lds = (size_t)64 * ((d < kCorrDC ? d : kCorrDC) | 1) * sizeof(double);
-    hipLaunchKernelGGL(k_normalize_queries, dim3(m_pad / 64, (unsigned)((d + kCorrDC - 1) / kCorrDC), (unsigned)pb.count), dim3(256),
-                       lds, s, pb.ptrs, xq, sxq, m, d, xqT, ldq, pb.sq);
+    bool typed = false;
+    for (int j = 0; j < pb.count; j++) typed = typed || pb.ptrs.spec[j] != nullptr;
+    const dim3 grid(m_pad / 64, (unsigned)((d + kCorrDC - 1) / kCorrDC), (unsigned)pb.count);
+    if (typed) hipLaunchKernelGGL(k_normalize_queries<true>, grid, dim3(256), lds, s, pb.ptrs, xq, sxq, m, d, xqT, ldq, pb.sq);
+    else hipLaunchKernelGGL(k_normalize_queries<false>, grid, dim3(256), lds, s, pb.ptrs, xq, sxq, m, d, xqT, ldq, pb.sq);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

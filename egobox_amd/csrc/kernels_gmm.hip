@@ -312,26 +312,43 @@ int launch_gmm_mstep(hipStream_t s, const GmmLaunch &g, double reg_covar) {
 
 // Responsibilities of a Gaussian mixture at m points (gmx_probas_point): one lane per point, the workgroup's 64 points staged
 // in LDS (row stride d | 1: a lane walks its own row), means, scaled factors and par read as wave-uniform operands.
-__global__ __launch_bounds__(64) void k_gmx_probas(const double *__restrict__ xq, int64_t m, int d, int k,
-                                                  const double *__restrict__ means, const double *__restrict__ precs,
-                                                  const double *__restrict__ par, double *__restrict__ probas) {
+// TYPED (the two _mixint kernels below): the points are cast (mixint.h) as they are staged.
+template <bool TYPED>
+__device__ __forceinline__ void gmx_probas_body(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                const double *__restrict__ means, const double *__restrict__ precs,
+                                                const double *__restrict__ par, double *__restrict__ probas,
+                                                const mixint::Col *__restrict__ spec) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int64_t q0 = (int64_t)blockIdx.x * 64;
     const int lane = threadIdx.x, ds = d | 1;
     const int rows = (int)((m - q0 < 64) ? (m - q0) : 64);
     for (int e = lane; e < rows * d; e += 64) {
         const int i = e / d, j = e - i * d;
-        sm[i * ds + j] = xq[q0 * d + e];
+        if (TYPED) sm[i * ds + j] = mixint::cast_coord(spec, mixint::table_values(spec, d), xq + (q0 + i) * d, 1, j);
+        else sm[i * ds + j] = xq[q0 * d + e];
     }
     __syncthreads();
     if (lane >= rows) return;
     gmx_probas_point(sm + lane * ds, d, k, means, precs, par, probas + (q0 + lane) * k);
 }
+__global__ __launch_bounds__(64) void k_gmx_probas(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                  const double *__restrict__ means, const double *__restrict__ precs,
+                                                  const double *__restrict__ par, double *__restrict__ probas) {
+    gmx_probas_body<false>(xq, m, d, k, means, precs, par, probas, nullptr);
+}
+__global__ __launch_bounds__(64) void k_gmx_probas_mixint(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                         const double *__restrict__ means, const double *__restrict__ precs,
+                                                         const double *__restrict__ par, double *__restrict__ probas,
+                                                         const mixint::Col *__restrict__ spec) {
+    gmx_probas_body<true>(xq, m, d, k, means, precs, par, probas, spec);
+}
 
 // ... and their x-derivatives (gmx_probas_deriv_point), one lane per point: the lane's scratch (x, z, v': d each; u: k) in LDS.
-__global__ __launch_bounds__(64) void k_gmx_probas_deriv(const double *__restrict__ xq, int64_t m, int d, int k,
-                                                        const double *__restrict__ means, const double *__restrict__ precs,
-                                                        const double *__restrict__ par, double *__restrict__ out) {
+template <bool TYPED>
+__device__ __forceinline__ void gmx_probas_deriv_body(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                      const double *__restrict__ means, const double *__restrict__ precs,
+                                                      const double *__restrict__ par, double *__restrict__ out,
+                                                      const mixint::Col *__restrict__ spec) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int64_t q0 = (int64_t)blockIdx.x * 64;
     const int lane = threadIdx.x, ds = d | 1, ks = k | 1;
@@ -339,21 +356,37 @@ __global__ __launch_bounds__(64) void k_gmx_probas_deriv(const double *__restric
     double *xs = sm, *zs = sm + 64 * ds, *vps = zs + 64 * ds, *us = vps + 64 * ds;
     for (int e = lane; e < rows * d; e += 64) {
         const int i = e / d, j = e - i * d;
-        xs[i * ds + j] = xq[q0 * d + e];
+        if (TYPED) xs[i * ds + j] = mixint::cast_coord(spec, mixint::table_values(spec, d), xq + (q0 + i) * d, 1, j);
+        else xs[i * ds + j] = xq[q0 * d + e];
     }
     __syncthreads();
     if (lane >= rows) return;
     gmx_probas_deriv_point(xs + lane * ds, zs + lane * ds, vps + lane * ds, us + lane * ks, d, k, means, precs, par,
                            out + (q0 + lane) * (int64_t)k * d);
 }
+__global__ __launch_bounds__(64) void k_gmx_probas_deriv(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                        const double *__restrict__ means, const double *__restrict__ precs,
+                                                        const double *__restrict__ par, double *__restrict__ out) {
+    gmx_probas_deriv_body<false>(xq, m, d, k, means, precs, par, out, nullptr);
+}
+__global__ __launch_bounds__(64) void k_gmx_probas_deriv_mixint(const double *__restrict__ xq, int64_t m, int d, int k,
+                                                               const double *__restrict__ means, const double *__restrict__ precs,
+                                                               const double *__restrict__ par, double *__restrict__ out,
+                                                               const mixint::Col *__restrict__ spec) {
+    gmx_probas_deriv_body<true>(xq, m, d, k, means, precs, par, out, spec);
+}
 
-int launch_gmx_probas(bool deriv, const double *xq, int64_t m, int d, int k, const double *blk, size_t lds, double *out) {
+int launch_gmx_probas(bool deriv, const double *xq, int64_t m, int d, int k, const double *blk, size_t lds, double *out,
+                      const mixint::Col *spec) {
     const double *precs = blk + (size_t)k * d, *par = precs + (size_t)k * d * d;
     const dim3 grid((unsigned)((m + 63) / 64));
     if (deriv && lds > 64 * 1024)
-        EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gmx_probas_deriv),
+        EGX_HIP_CHECK(hipFuncSetAttribute(spec ? reinterpret_cast<const void *>(&k_gmx_probas_deriv_mixint)
+                                               : reinterpret_cast<const void *>(&k_gmx_probas_deriv),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (deriv) hipLaunchKernelGGL(k_gmx_probas_deriv, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out);
+    if (deriv && spec) hipLaunchKernelGGL(k_gmx_probas_deriv_mixint, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out, spec);
+    else if (deriv) hipLaunchKernelGGL(k_gmx_probas_deriv, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out);
+    else if (spec) hipLaunchKernelGGL(k_gmx_probas_mixint, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out, spec);
     else hipLaunchKernelGGL(k_gmx_probas, grid, dim3(64), lds, 0, xq, m, d, k, blk, precs, par, out);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;

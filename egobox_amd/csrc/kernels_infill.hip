@@ -42,6 +42,26 @@ __global__ __launch_bounds__(kTile) void k_infill_prepare(const double *__restri
     for (int j = 0; j < d; j++) xqT[(int64_t)j * kTile + a] = live ? (xq[(int64_t)a * d + j] - par[j]) / par[d + j] : 0.0;
     if (flag) flag[a] = bad;
 }
+// ... of a model that carries xtypes (mixint.h): the same with every coordinate cast where it is read.  A finite coordinate
+// stays finite under the cast and a non-finite one non-finite, so the flags are those of the raw rows.  xcast (mt x d, or
+// nullptr) receives the cast raw rows (a flagged point: its raw row), for k_infill_mix.
+__global__ __launch_bounds__(kTile) void k_infill_prepare_mixint(const double *__restrict__ xq, int mt, int d,
+                                                                 const double *__restrict__ par, double *__restrict__ xqT,
+                                                                 int *__restrict__ flag, const mixint::Col *__restrict__ spec,
+                                                                 double *__restrict__ xcast) {
+    const int a = threadIdx.x;
+    const double *vals = mixint::table_values(spec, d);
+    int bad = 0;
+    if (a < mt)
+        for (int j = 0; j < d; j++) bad |= !isfinite(xq[(int64_t)a * d + j]);
+    const bool live = a < mt && !bad;
+    for (int j = 0; j < d; j++) {
+        const double c = live ? mixint::cast_coord(spec, vals, xq + (int64_t)a * d, 1, j) : 0.0;
+        xqT[(int64_t)j * kTile + a] = live ? (c - par[j]) / par[d + j] : 0.0;
+        if (xcast && a < mt) xcast[(int64_t)a * d + j] = live ? c : xq[(int64_t)a * d + j];
+    }
+    if (flag) flag[a] = bad;
+}
 
 struct TrendArgs {
     int p, rp, msplit, want_d;
@@ -353,8 +373,10 @@ int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, i
     return EGX_SUCCESS;
 }
 
-int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag) {
-    hipLaunchKernelGGL(k_infill_prepare, dim3(1), dim3(kTile), 0, s, xq, mt, d, par, xqT, flag);
+int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag,
+                          const mixint::Col *spec, double *xcast) {
+    if (spec) hipLaunchKernelGGL(k_infill_prepare_mixint, dim3(1), dim3(kTile), 0, s, xq, mt, d, par, xqT, flag, spec, xcast);
+    else hipLaunchKernelGGL(k_infill_prepare, dim3(1), dim3(kTile), 0, s, xq, mt, d, par, xqT, flag);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

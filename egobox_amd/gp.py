@@ -215,6 +215,21 @@ class GpHandle:
     def __exit__(self, *a):
         self.close()
 
+    # -- mixed-integer design space
+    def set_xtypes(self, xtypes):
+        """egx_gp_set_xtypes: from now on every query point is cast to its nearest admissible discrete point on the device
+        (`egobox_amd.mixint`); the unfolded dimension of `xtypes` must be `d`.  None or () clears.  The training inputs are
+        taken as already cast."""
+        from .mixint import set_handle_xtypes
+        set_handle_xtypes(self, xtypes)
+        return self
+
+    @property
+    def xtypes(self):
+        """The `XType`s the handle carries ([] when none)."""
+        from .mixint import get_handle_xtypes
+        return get_handle_xtypes(self)
+
     # -- likelihood
     def set_lockstep(self, width):
         """Candidates of `likelihood_batch` factored in lock-step by one launch sequence (egx_gp_set_lockstep);
@@ -835,6 +850,11 @@ class GaussianProcess(GpMetrics):
     @staticmethod
     def params(mean=None, corr=None):
         return GpParams(mean, corr)
+
+    def set_xtypes(self, xtypes):
+        """`GpHandle.set_xtypes` of the model's handle."""
+        self._h.set_xtypes(xtypes)
+        return self
 
     def predict(self, x):
         return self._h.predict(x)

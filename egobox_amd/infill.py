@@ -53,8 +53,9 @@ def _surrogate(model, j):
 
 class InfillObjective:
     """`egx_infill`: one objective model, k >= 0 constraint models (kept alive by this object), a criterion and its parameters.
-    A model is a GpHandle, a GaussianProcess, a single-expert Gpx or a single-rank `egobox_amd.moe.GpMixture` of library-backed
-    experts (any number of clusters, smooth or hard): with a mixture among them the handle is built by egx_infill_create_mix
+    A model is a GpHandle, a GaussianProcess, a single-expert Gpx, a single-rank `egobox_amd.moe.GpMixture` of library-backed
+    experts (any number of clusters, smooth or hard) or an `egobox_amd.mixint.MixintGpMixture`; models that carry xtypes
+    (`GpHandle.set_xtypes`) must all carry the same ones, and every point is then cast on the device before it is evaluated: with a mixture among them the handle is built by egx_infill_create_mix
     and the recombination runs on the GPU; with single models only, by egx_infill_create as before.
 
     value / gradient are those of the MINIMISED objective: -crit / scale, times the probability of feasibility of the
@@ -64,7 +65,12 @@ class InfillObjective:
                  scale_ic=1.0, scale=1.0):
         lib = L.load()
         self._lib = lib
+        from .mixint import MixintGpMixture
         from .moe import GpMixture
+        # a mixed-integer mixture: its inner mixture, whose experts carry the xtypes (the library casts the points it generates
+        # and is given; the optimisers work in the unfolded continuous box, `to_discrete_space` folds x_best)
+        obj_model = obj_model.moe if isinstance(obj_model, MixintGpMixture) else obj_model
+        cstr_models = tuple(m.moe if isinstance(m, MixintGpMixture) else m for m in cstr_models)
         mixed = any(isinstance(m, GpMixture) for m in (obj_model, *cstr_models))
         if mixed:
             self._surrogates = [_surrogate(m, j) for j, m in enumerate((obj_model, *cstr_models))]

@@ -147,29 +147,50 @@ class GaussianMixture:
             return np.ones((x.shape[0], 1))
         return np.exp(self._log_resp(x))
 
-    def predict_probas_device(self, x, device=-1):
+    def predict_probas_device(self, x, device=-1, xtypes=None):
         """The same responsibilities from the library (egx_gmx_predict_probas: one lane per point on the GPU); what the
-        library-side recombination of `GpMixture` consumes."""
+        library-side recombination of `GpMixture` consumes.  xtypes (`egobox_amd.mixint.XType`s): the points are cast on the
+        device first (egx_gmx_predict_probas_mixint)."""
         from . import _lib as L
         lib = L.load()
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
         k, nx = self.means.shape
         out = np.empty((x.shape[0], k))
+        if xtypes:
+            from .mixint import _c_xtypes
+            arr, nxt, _keep = _c_xtypes(xtypes)
+            L.check(lib.egx_gmx_predict_probas_mixint(int(device), L.dptr(np.ascontiguousarray(self.weights)),
+                                                      L.dptr(np.ascontiguousarray(self.means)),
+                                                      L.dptr(np.ascontiguousarray(self.precisions_chol)), k, nx,
+                                                      self.heaviside_factor, L.dptr(x), x.shape[0], L.dptr(out), arr, nxt))
+            return out
         L.check(lib.egx_gmx_predict_probas(int(device), L.dptr(np.ascontiguousarray(self.weights)),
                                            L.dptr(np.ascontiguousarray(self.means)),
                                            L.dptr(np.ascontiguousarray(self.precisions_chol)), k, nx,
                                            self.heaviside_factor, L.dptr(x), x.shape[0], L.dptr(out)))
         return out
 
-    def predict_probas_derivatives_device(self, x, device=-1):
-        """d p_c / d x, (m, k, nx), from the library (egx_gmx_predict_probas_derivatives, one lane per point on the GPU)."""
+    def predict_probas_derivatives_device(self, x, device=-1, xtypes=None):
+        """d p_c / d x, (m, k, nx), from the library (egx_gmx_predict_probas_derivatives, one lane per point on the GPU);
+        xtypes: at the cast points (egx_gmx_predict_probas_derivatives_mixint)."""
         from . import _lib as L
         lib = L.load()
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
         k, nx = self.means.shape
         if 3 * nx + k > 320:  # (the kernel keeps one point per lane with 3 nx + k doubles of LDS scratch: beyond that, the host form)
+            if xtypes:
+                from .mixint import cast_to_discrete_values
+                x = cast_to_discrete_values(xtypes, x)
             return self.predict_probas_derivatives(x)
         out = np.empty((x.shape[0], k, nx))
+        if xtypes:
+            from .mixint import _c_xtypes
+            arr, nxt, _keep = _c_xtypes(xtypes)
+            L.check(lib.egx_gmx_predict_probas_derivatives_mixint(int(device), L.dptr(np.ascontiguousarray(self.weights)),
+                                                                  L.dptr(np.ascontiguousarray(self.means)),
+                                                                  L.dptr(np.ascontiguousarray(self.precisions_chol)), k, nx,
+                                                                  self.heaviside_factor, L.dptr(x), x.shape[0], L.dptr(out), arr, nxt))
+            return out
         L.check(lib.egx_gmx_predict_probas_derivatives(int(device), L.dptr(np.ascontiguousarray(self.weights)),
                                                        L.dptr(np.ascontiguousarray(self.means)),
                                                        L.dptr(np.ascontiguousarray(self.precisions_chol)), k, nx,
@@ -505,6 +526,13 @@ class GpMixture(GpMetrics):
     def _mine(self, i):
         return i % self.world == self.rank and self.experts[i] is not None
 
+    #: the `XType`s of a mixed-integer mixture (set by `egobox_amd.mixint.MixintGpMixture`, whose experts carry them as well):
+    #: the responsibilities are then taken at the cast point, on the device
+    xtypes = None
+
+    def _probas(self, dev, x):
+        return dev(x, xtypes=self.xtypes) if self.xtypes else dev(x)
+
     def _allreduce(self, *arrays):
         if self.world == 1:
             return arrays
@@ -541,7 +569,7 @@ class GpMixture(GpMetrics):
         m, d = x.shape
         k = len(self.experts)
         dev = getattr(self.gmx, "predict_probas_device", None)  # the library's kernel; a duck-typed mixture keeps its own
-        probas = np.ascontiguousarray(dev(x) if dev is not None else self.gmx.predict_probas(x), dtype=np.float64)
+        probas = np.ascontiguousarray(self._probas(dev, x) if dev is not None else self.gmx.predict_probas(x), dtype=np.float64)
         harr = (C.c_void_p * max(1, len(hs)))(*[h.value if hasattr(h, "value") else h for h in hs])
         iarr = np.asarray(ids, dtype=np.int32)
         val = np.empty(m) if want_val else None
@@ -626,11 +654,11 @@ class GpMixture(GpMetrics):
         k = len(self.experts)
         smooth = self.recombination == "smooth"
         dev = getattr(self.gmx, "predict_probas_device", None)
-        probas = np.ascontiguousarray(dev(x) if dev is not None else self.gmx.predict_probas(x), dtype=np.float64)
+        probas = np.ascontiguousarray(self._probas(dev, x) if dev is not None else self.gmx.predict_probas(x), dtype=np.float64)
         dprobas = None
         if smooth and k > 1:
             ddev = getattr(self.gmx, "predict_probas_derivatives_device", None)
-            dprobas = np.ascontiguousarray(ddev(x) if ddev is not None else self.gmx.predict_probas_derivatives(x),
+            dprobas = np.ascontiguousarray(self._probas(ddev, x) if ddev is not None else self.gmx.predict_probas_derivatives(x),
                                            dtype=np.float64)
         harr = (C.c_void_p * max(1, len(hs)))(*[h.value if hasattr(h, "value") else h for h in hs])
         iarr = np.asarray(ids, dtype=np.int32)

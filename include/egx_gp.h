@@ -146,6 +146,38 @@ int64_t egx_regression_ncols(int32_t mean, int64_t d);
 /* mean_models.rs value(): F (n x p) from (normalised) x (n x d). */
 int32_t egx_regression_basis(int32_t mean, const double *x, int64_t n, int64_t d, double *f /*n*p*/);
 
+/* ---- mixed-integer design spaces (host side, no device needed) ------------
+ * XType (crates/ego/src/types.rs) and the free functions of crates/ego/src/gpmix/mixint.rs:38-226.  A spec is nx typed
+ * columns; its UNFOLDED, continuously relaxed form has d = sum (ENUM ? n : 1) columns, an Enum column of n levels being a
+ * one-hot group of n.  The arithmetic (csrc/mixint.h, one text for host and device):
+ *   cast      FLOAT unchanged; INT rounds half away from zero (f64::round; the sign of zero is kept, NO clamping to lo / hi, as in the
+ *             reference); ORD takes the value with the smallest |x - v|, the FIRST in list order on a tie; an ENUM group becomes the
+ *             one-hot of its FIRST maximum.  A NaN / +-inf INT or ORD coordinate stays as it is, an ENUM group with a non-finite
+ *             entry becomes all NaN (the reference panics): a non-finite point stays non-finite.
+ *   unfold    the enum index (truncated, `as usize`) becomes the one-hot group; an index outside [0, n) or a non-finite one is
+ *             EGX_ERR_INVALID_VALUE, the message names row and column
+ *   fold      the index of the group's first maximum (NaN for a group with a non-finite entry)
+ *   to_discrete = cast, then fold (mixint.rs:220-226); continuous_limits: ORD min / max of its values, ENUM [0, 1] per level
+ * Where the reference is not followed: its fold slices the unfolded row at the FOLDED index (:89) and its unfold reads the
+ * non-enum columns at the UNFOLDED index (:126), which is right only while no Enum column precedes; here fold reads at the
+ * unfolded index and unfold at the folded one (csrc/mixint.h says on which specs the two agree).
+ * Every function validates the spec first (EGX_ERR_INVALID_VALUE, the message names the entry): unknown kind, ORD with n < 1 or a
+ * non-finite value, ENUM with n < 1, lo > hi; more than EGX_MIXINT_MAX_ORD_VALUES Ord values in all is EGX_ERR_UNSUPPORTED. */
+typedef enum { EGX_XTYPE_FLOAT = 0, EGX_XTYPE_INT = 1, EGX_XTYPE_ORD = 2, EGX_XTYPE_ENUM = 3 } egx_xtype_kind;
+typedef struct {
+    int32_t kind;         /* egx_xtype_kind */
+    int32_t n;            /* ORD: number of values, ENUM: number of levels (ignored otherwise) */
+    double lo, hi;        /* FLOAT / INT */
+    const double *values; /* ORD (n), borrowed during the call only */
+} egx_xtype;
+#define EGX_MIXINT_MAX_ORD_VALUES 4096 /* Ord values per spec, all columns together: the nearest-value search is a loop per coordinate */
+int32_t egx_mixint_unfolded_dim(const egx_xtype *xt, int32_t nx, int64_t *d);
+int32_t egx_mixint_continuous_limits(const egx_xtype *xt, int32_t nx, double *xlimits /*d*2*/);
+int32_t egx_mixint_unfold(const egx_xtype *xt, int32_t nx, const double *x /*m*nx*/, int64_t m, double *out /*m*d*/);
+int32_t egx_mixint_fold(const egx_xtype *xt, int32_t nx, const double *x /*m*d*/, int64_t m, double *out /*m*nx*/);
+int32_t egx_mixint_cast(const egx_xtype *xt, int32_t nx, const double *x /*m*d*/, int64_t m, double *out /*m*d, may be x*/);
+int32_t egx_mixint_to_discrete(const egx_xtype *xt, int32_t nx, const double *x /*m*d*/, int64_t m, double *out /*m*nx*/);
+
 /* ---- handle lifetime ------------------------------------------------------
  * Replaces the theta-independent part of GpValidParams::fit
  * (crates/gp/src/algorithm.rs:795-866): copies x (n x d) and y (n), normalises
@@ -158,6 +190,20 @@ int32_t egx_gp_dims(const egx_gp *gp, int64_t *n, int64_t *d, int64_t *p, int64_
 /* the handle's own copy of the raw training set (GaussianProcess::training_data, algorithm.rs:969-978: the fitted model
  * owns copies of x and y); x_out (n*d), y_out (n), either may be NULL */
 int32_t egx_gp_get_training_data(const egx_gp *gp, double *x_out, double *y_out);
+/* MixintGpMixture (crates/ego/src/gpmix/mixint.rs:589-697): a model that carries xtypes casts every query point to its nearest
+ * admissible discrete point before it is used, in EVERY call that takes query points -- egx_gp_predict / _var / _valvar, the three
+ * _gradients (the model's gradients at the cast point with respect to the unfolded coordinates, m x d, :656-687),
+ * egx_gp_predict_covariance, egx_gp_sample, egx_gp_predict_valvar_multi (every member by its own spec or none),
+ * egx_moe_predict_valvar(_gradients) (the experts cast for themselves) and the infill handles built on it -- ON THE DEVICE, in the
+ * kernel that reads the raw rows anyway: no extra launch, no host pass over the queries.  The result is bit for bit what the
+ * model without xtypes returns on egx_mixint_cast(x).  The spec is copied (host copy and a small device table); its unfolded
+ * dimension must equal the handle's d (EGX_ERR_INVALID_VALUE, as every fault of egx_mixint_*; checked before the device is touched).
+ * nx == 0 clears: the handle is a continuous model again -- same kernels, same bits as before.  The TRAINING inputs are the
+ * caller's business: pass them already cast to egx_gp_create; the handle does not recast them. */
+int32_t egx_gp_set_xtypes(egx_gp *gp, const egx_xtype *xt, int32_t nx);
+/* the spec back: *nx columns (the first min(cap, *nx) written to xt), *n_ord_values Ord values in column order into ord_values (or
+ * NULL: xt[j].values is then NULL); any output may be NULL.  *nx == 0: no xtypes. */
+int32_t egx_gp_get_xtypes(egx_gp *gp, egx_xtype *xt /*cap*/, int32_t cap, int32_t *nx, double *ord_values, int64_t *n_ord_values);
 
 /* ---- likelihood (the unit COBYLA multiplies) ------------------------------
  * One evaluation of `reduced_likelihood(fx, corr.value(d, theta, w), ...)`
@@ -499,6 +545,15 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
 int32_t egx_gmx_predict_probas_derivatives(int32_t device, const double *weights, const double *means,
                                            const double *precisions_chol, int64_t k, int64_t d, double heaviside_factor,
                                            const double *xq, int64_t m, double *dprobas /*m*k*d*/);
+/* The typed forms of the two stateless mixture calls: the same arguments plus a spec whose unfolded dimension is d; the points are
+ * cast (egx_mixint_cast) on the device as the kernel stages them.  nx == 0 is the untyped call. */
+int32_t egx_gmx_predict_probas_mixint(int32_t device, const double *weights, const double *means, const double *precisions_chol,
+                                      int64_t k, int64_t d, double heaviside_factor, const double *xq, int64_t m,
+                                      double *probas /*m*k*/, const egx_xtype *xt, int32_t nx);
+int32_t egx_gmx_predict_probas_derivatives_mixint(int32_t device, const double *weights, const double *means,
+                                                  const double *precisions_chol, int64_t k, int64_t d, double heaviside_factor,
+                                                  const double *xq, int64_t m, double *dprobas /*m*k*d*/, const egx_xtype *xt,
+                                                  int32_t nx);
 /* x-gradients of the mixture's mean and variance: GpMixture::predict_gradients_smooth / predict_var_gradients_smooth
  * (crates/moe/src/algorithm.rs:691-783:  sum_e p_e grad y_e + p'_e y_e ,  sum_e p_e^2 grad v_e + 2 p_e p'_e v_e) and
  * predict_gradients_hard / predict_var_gradients_hard (:942-1010: the expert of argmax_e p_e) -- what EGO's infill
@@ -599,7 +654,12 @@ int32_t egx_sgp_get_state(egx_sgp *sgp, double *theta, double *sigma2, double *n
  * and its x-gradient, for m points per call, from ONE objective model and n_cstr >= 0 constraint models (dense GPs, all
  * fitted, same d, same device; n may differ) -- or, through egx_infill_create_mix below, from surrogates that are mixtures
  * of such GPs.  The models are BORROWED: they must outlive the handle, and a call always reads
- * their CURRENT fitted state.  feasibility == 0 replaces obj by -1 (0 for LogEI) and its gradient by 0 (:410-416, 441-466).
+ * their CURRENT fitted state -- and their CURRENT xtypes (egx_gp_set_xtypes), checked at creation and again at every call: all
+ * models (every expert of every surrogate) carry the same spec, or none does, else EGX_ERR_INVALID_VALUE naming the two.  With
+ * xtypes every point of every call below -- egx_infill_eval, _eval_cstr, _eval_experts, _scaling, and the trial points
+ * egx_infill_optimize / _optimize_cstr generate themselves -- is cast on the device before it is evaluated, the mixtures'
+ * responsibilities included; the optimisers work in the unfolded continuous box, x_best is the evaluated point as proposed (fold
+ * it with egx_mixint_to_discrete) and *f_best is bit for bit egx_infill_eval there.  feasibility == 0 replaces obj by -1 (0 for LogEI) and its gradient by 0 (:410-416, 441-466).
  * The reference evaluates this one point at a time with 2 (1 + n_cstr) predict calls per evaluation; here a call is one
  * upload, one launch sequence per 128-point tile and model, one synchronisation, and nothing is computed on the host.
  *

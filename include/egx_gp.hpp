@@ -83,6 +83,61 @@ struct ThetaTuning {
     }
 };
 
+// XType (crates/ego/src/types.rs) and the free functions of crates/ego/src/gpmix/mixint.rs:38-226 over the egx_mixint_* helpers
+struct XType {
+    int32_t kind = EGX_XTYPE_FLOAT;
+    double lo = 0.0, hi = 0.0;
+    std::vector<double> values;  // Ord
+    int32_t n = 0;               // Enum levels
+    static XType Float(double lo, double hi) { XType t; t.lo = lo, t.hi = hi; return t; }
+    static XType Int(double lo, double hi) { XType t; t.kind = EGX_XTYPE_INT, t.lo = lo, t.hi = hi; return t; }
+    static XType Ord(std::vector<double> v) { XType t; t.kind = EGX_XTYPE_ORD, t.n = (int32_t)v.size(), t.values = std::move(v); return t; }
+    static XType Enum(int32_t n) { XType t; t.kind = EGX_XTYPE_ENUM, t.n = n; return t; }
+};
+namespace mixint {
+// the C structs of a spec; they borrow the Ord values of `xt`, which must outlive them
+inline std::vector<egx_xtype> c_xtypes(const std::vector<XType> &xt) {
+    std::vector<egx_xtype> c(xt.size());
+    for (size_t j = 0; j < xt.size(); j++) c[j] = egx_xtype{xt[j].kind, xt[j].n, xt[j].lo, xt[j].hi, xt[j].values.empty() ? nullptr : xt[j].values.data()};
+    return c;
+}
+inline int64_t unfolded_dim(const std::vector<XType> &xt) {
+    const auto c = c_xtypes(xt);
+    int64_t d = 0;
+    check(egx_mixint_unfolded_dim(c.data(), (int32_t)c.size(), &d));
+    return d;
+}
+inline std::vector<double> as_continuous_limits(const std::vector<XType> &xt) {  // d x 2
+    const auto c = c_xtypes(xt);
+    std::vector<double> lim((size_t)unfolded_dim(xt) * 2);
+    check(egx_mixint_continuous_limits(c.data(), (int32_t)c.size(), lim.data()));
+    return lim;
+}
+namespace detail {
+using RowFn = int32_t (*)(const egx_xtype *, int32_t, const double *, int64_t, double *);
+inline std::vector<double> rows(RowFn fn, const std::vector<XType> &xt, const double *x, int64_t m, int64_t cols_out) {
+    const auto c = c_xtypes(xt);
+    std::vector<double> out((size_t)(m * cols_out));
+    check(fn(c.data(), (int32_t)c.size(), x, m, out.data()));
+    return out;
+}
+}  // namespace detail
+// x: m rows of the folded (nx columns) or unfolded (d columns) space, as the C functions take them
+inline std::vector<double> unfold_with_enum_mask(const std::vector<XType> &xt, const double *x, int64_t m) {
+    return detail::rows(egx_mixint_unfold, xt, x, m, unfolded_dim(xt));
+}
+inline std::vector<double> to_continuous_space(const std::vector<XType> &xt, const double *x, int64_t m) { return unfold_with_enum_mask(xt, x, m); }
+inline std::vector<double> fold_with_enum_index(const std::vector<XType> &xt, const double *x, int64_t m) {
+    return detail::rows(egx_mixint_fold, xt, x, m, (int64_t)xt.size());
+}
+inline std::vector<double> cast_to_discrete_values(const std::vector<XType> &xt, const double *x, int64_t m) {
+    return detail::rows(egx_mixint_cast, xt, x, m, unfolded_dim(xt));
+}
+inline std::vector<double> to_discrete_space(const std::vector<XType> &xt, const double *x, int64_t m) {
+    return detail::rows(egx_mixint_to_discrete, xt, x, m, (int64_t)xt.size());
+}
+}  // namespace mixint
+
 class GaussianProcess;
 
 // GpParams / GpValidParams, parameters.rs:80-313
@@ -119,6 +174,12 @@ class GpParams {
 class GaussianProcess {
   public:
     static GpParams params(Mean m, Corr c) { return GpParams(m, c); }
+
+    // egx_gp_set_xtypes: every query point is cast to its nearest admissible discrete point on the device from now on; {} clears
+    void set_xtypes(const std::vector<XType> &xt) {
+        const auto c = mixint::c_xtypes(xt);
+        check(egx_gp_set_xtypes(h_.get(), c.empty() ? nullptr : c.data(), (int32_t)c.size()));
+    }
 
     std::vector<double> predict(const double *x, int64_t m) const {
         std::vector<double> y((size_t)m);
