@@ -1,0 +1,355 @@
+// Closed-form gradient of the sparse GP's likelihood (FITC / VFE) with respect to theta, sigma2 and noise (new capability: the
+// reference tunes the sparse model derivative-free).  DESIGN.md 4.6 has the derivation; in the notation of sgp_host.hip
+// (RT = R_nz C_z^-T, V^T = sigma RT, A = I + V D V^T = L L^T, b = L^-1 V (beta o y), Wz = C_z^-T, Wa = L^-T):
+//   E~     = RT L^-T                                  launch_trsm_rows on a copy of RT
+//   alpha  = beta o (y - sigma E~ b) = Sigma^-1 y,   e_t = sigma2 |E~_t|^2            launch_row_reduce + k_sgp_grad_rows
+//   p_t    = beta_t - beta_t^2 e_t - alpha_t^2,      q = p (FITC), beta (VFE),        r = beta - q >= 0
+//   T^T    = [diag(beta) E~ L^-1 - diag(q) RT] C_z^-1 - alpha w^T   (n x nz)          two launch_gemm_nt_sub
+//   H      = V diag(q) V^T = (A - I) - V diag(r) V^T  -- r >= 0, so the signed weights of FITC cost ONE more Gram product
+//            (launch_gram_lower on W, refilled with sqrt(r)); VFE has r = 0 and none
+//   S^     = sigma2 S = Wz (I - Wa Wa^T - H) Wz^T - w~ w~^T,  w~ = sigma w = Wz Wa b   (nz x nz; three small GEMMs)
+//   dL/dtheta_k = -sigma2 sum T^T o d_k R_nz + 1/2 sum S^ o d_k R_zz
+//   dL/dsigma2  = -1/2 [2 sum T^T o R_nz - sum S^ o R_zz / sigma2 + c_sigma],   dL/dnoise = -1/2 c_nu
+// The two sums over a rectangle of pairs are k_sgp_grad_rect, the rectangular counterpart of k_grad_accum (kernels_corr.hip K7):
+// rows from one k-major point set, columns from another, a weight per pair; pass one recomputes R[t, i] from the coordinates
+// (RT no longer holds it), pass two accumulates the d outputs with dlog_dc, output d is the plain sum of weight * R.  It serves
+// R_nz (xT, zT, T^T) and R_zz (zT, zT, S^: the diagonal has R = 1 and d log R = 0, which is the unit diagonal without nugget that
+// dL/dsigma2 wants and no term in dL/dtheta).  One partial vector per workgroup and a fixed-order reduce: no atomics, the same
+// bits on every call.
+// Extra device memory, allocated by the first gradient call and kept in the handle: ONE n_pad x z_pad buffer (E~, then T^T;
+// 4.1 GB at n = 10^6, nz = 512), 7 n_pad vectors, one zext^2 and three z_pad^2 matrices.  diag(q) RT - diag(beta) E~ L^-1 lives
+// in W, which is free after the Gram products.  Nothing n-long goes to the host.
+#include "sgp_handle.h"
+#include "corr_pair.h"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace egx;
+
+namespace {
+
+constexpr int kRectDC = 64;       // input dimensions staged per pass (2 x 64 x 64 doubles = 64 KB of LDS)
+constexpr int kRectMaxWG = 2048;  // workgroups (partial vectors) per output chunk
+
+template <int CORR, int DK>
+__global__ __launch_bounds__(256) void k_sgp_grad_rect(const double *__restrict__ xT, int64_t ldx, int n,
+                                                       const double *__restrict__ zT, int64_t ldz, int nz, int d,
+                                                       const double *__restrict__ coef, const double *__restrict__ T, int64_t ldt,
+                                                       int ntc, int ntiles, int nout, int nout_pad, double *__restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int dc = d < kRectDC ? d : kRectDC;
+    double *xi = sm, *xj = sm + dc * 64;
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    const int o0 = blockIdx.y * DK;
+    double acc[DK];
+#pragma unroll
+    for (int oo = 0; oo < DK; oo++) acc[oo] = 0.0;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int bi = t / ntc, bj = t - bi * ntc;
+        // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
+        PairAcc<CORR> pa[4][4];
+        for (int c0 = 0; c0 < d; c0 += dc) {
+            const int dn = (d - c0 < dc) ? (d - c0) : dc;
+            __syncthreads();  // the previous readers of the slabs are done
+            stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid);
+            stage_slab(xj, zT + (int64_t)c0 * ldz, ldz, bj * 64, dn, tid);
+            __syncthreads();
+            for (int k = 0; k < dn; k++) {
+                double vi[4], vj[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) vi[a] = xi[k * 64 + ty * 4 + a];
+#pragma unroll
+                for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
+                const double *ck = coef + (c0 + k);
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) pa[a][b].add(vi[a] - vj[b], ck, 1);
+            }
+        }
+        double wp[4][4];  // T[t, i] R[t, i] inside the n x nz rectangle, else 0
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            const int i = bi * 64 + ty * 4 + a;
+            const double *trow = T + (int64_t)i * ldt + bj * 64 + tx * 4;
+            const double2 t01 = *reinterpret_cast<const double2 *>(trow);
+            const double2 t23 = *reinterpret_cast<const double2 *>(trow + 2);
+            const double tv[4] = {t01.x, t01.y, t23.x, t23.y};
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int j = bj * 64 + tx * 4 + b;
+                wp[a][b] = (i < n && j < nz) ? pa[a][b].value() * tv[b] : 0.0;
+            }
+        }
+        // ---- pass 2: this workgroup's outputs o0 .. o0 + DK - 1: o < d <-> input dimension o, o == d the plain sum.
+        // d > dc: the chunk's dimensions are staged again, from slab row 0
+        int base = 0;
+        if (d > dc) {
+            const int dn = (d - o0 < DK) ? (d - o0) : DK;
+            __syncthreads();
+            if (dn > 0) {
+                stage_slab(xi, xT + (int64_t)o0 * ldx, ldx, bi * 64, dn, tid);
+                stage_slab(xj, zT + (int64_t)o0 * ldz, ldz, bj * 64, dn, tid);
+            }
+            __syncthreads();
+            base = o0;
+        }
+#pragma unroll
+        for (int oo = 0; oo < DK; oo++) {
+            const int o = o0 + oo;
+            if (o < d) {
+                const double c = coef[o];
+                double vi[4], vj[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) vi[a] = xi[(o - base) * 64 + ty * 4 + a];
+#pragma unroll
+                for (int b = 0; b < 4; b++) vj[b] = xj[(o - base) * 64 + tx * 4 + b];
+                double sacc = acc[oo];
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) sacc = __builtin_fma(wp[a][b], dlog_dc<CORR>(c, fabs(vi[a] - vj[b])), sacc);
+                acc[oo] = sacc;
+            } else if (o == d) {
+                double sacc = acc[oo];
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) sacc += wp[a][b];
+                acc[oo] = sacc;
+            }
+        }
+    }
+    // ---- one reduction per workgroup: lanes of a wave (xor shuffles), then the four waves in a fixed order
+    __syncthreads();
+    double *red = sm;  // [4][DK]
+#pragma unroll
+    for (int oo = 0; oo < DK; oo++) {
+        double v = acc[oo];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if ((tid & 63) == 0) red[(tid >> 6) * DK + oo] = v;
+    }
+    __syncthreads();
+    if (tid < DK && o0 + tid < nout)
+        part[(int64_t)blockIdx.x * nout_pad + o0 + tid] = ((red[tid] + red[DK + tid]) + red[2 * DK + tid]) + red[3 * DK + tid];
+}
+
+// out[o] = sum over the nwg partial vectors, in a fixed order: 256 lanes take every 256th, then a tree in LDS
+__global__ __launch_bounds__(256) void k_sgp_grad_reduce(const double *__restrict__ part, int nwg, int nout_pad,
+                                                         double *__restrict__ out) {
+    __shared__ double red[256];
+    const int o = blockIdx.x, tid = threadIdx.x;
+    double v = 0.0;
+    for (int b = tid; b < nwg; b += 256) v += part[(int64_t)b * nout_pad + o];
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) out[o] = red[0];
+}
+
+// The per-point quantities, t < n_pad (zeros beyond n): alpha, beta, q, sqrt(r), p
+__global__ __launch_bounds__(256) void k_sgp_grad_rows(int n, int n_pad, const double *__restrict__ s0, const double *__restrict__ e2,
+                                                       const double *__restrict__ eb, const double *__restrict__ y, double sigma,
+                                                       double sigma2, double noise, double nugget, int vfe,
+                                                       double *__restrict__ alpha, double *__restrict__ beta, double *__restrict__ q,
+                                                       double *__restrict__ sr, double *__restrict__ p) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_pad) return;
+    double al = 0.0, be = 0.0, qv = 0.0, rv = 0.0, pv = 0.0;
+    if (t < n) {
+        const double nu = vfe ? fmax(noise, nugget) : sigma2 * (1.0 - s0[t]) + noise;
+        be = 1.0 / nu;
+        al = be * (y[t] - sigma * eb[t]);
+        rv = be * be * (sigma2 * e2[t]) + al * al;
+        pv = be - rv;
+        qv = vfe ? be : pv;
+        if (vfe) rv = 0.0;
+    }
+    alpha[t] = al;
+    beta[t] = be;
+    q[t] = qv;
+    sr[t] = sqrt(rv);
+    p[t] = pv;
+}
+
+// part[b * 32 + 0 / 1] = block b's share of sum a[t] / sum c[t], t < n: elements b * 256 + tid + k * gridDim.x * 256, a tree in
+// LDS -- a fixed order; k_sgp_grad_reduce adds the blocks
+__global__ __launch_bounds__(256) void k_sgp_sum2(const double *__restrict__ a, const double *__restrict__ c, int n,
+                                                  double *__restrict__ part) {
+    __shared__ double ra[256], rc[256];
+    const int tid = threadIdx.x;
+    double va = 0.0, vc = 0.0;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + tid; t < n; t += (int64_t)gridDim.x * 256) {
+        va += a[t];
+        vc += c[t];
+    }
+    ra[tid] = va;
+    rc[tid] = vc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            ra[tid] += ra[tid + s];
+            rc[tid] += rc[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        part[(int64_t)blockIdx.x * 32] = ra[0];
+        part[(int64_t)blockIdx.x * 32 + 1] = rc[0];
+    }
+}
+
+// F[t][i] = q[t] RT[t][i], E[t][i] *= beta[t] over the n_pad x z_pad rectangle (z_pad is even)
+__global__ __launch_bounds__(256) void k_sgp_scale_pair(const double *__restrict__ RT, const double *__restrict__ q,
+                                                        const double *__restrict__ beta, int z_pad, int64_t count,
+                                                        double *__restrict__ F, double *__restrict__ E) {
+    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (e >= count) return;
+    const int t = (int)(e / z_pad);
+    const double qt = q[t], bt = beta[t];
+    const double2 r = *reinterpret_cast<const double2 *>(RT + e);
+    const double2 v = *reinterpret_cast<const double2 *>(E + e);
+    *reinterpret_cast<double2 *>(F + e) = make_double2(qt * r.x, qt * r.y);
+    *reinterpret_cast<double2 *>(E + e) = make_double2(bt * v.x, bt * v.y);
+}
+
+// M[t][i] = -scale * a[t] * w[i] over rows x cols (cols even)
+__global__ __launch_bounds__(256) void k_sgp_outer_neg(const double *__restrict__ a, const double *__restrict__ w, double scale,
+                                                       int cols, int64_t count, double *__restrict__ M) {
+    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (e >= count) return;
+    const int t = (int)(e / cols), i = (int)(e - (int64_t)t * cols);
+    const double at = -scale * a[t];
+    *reinterpret_cast<double2 *>(M + e) = make_double2(at * w[i], at * w[i + 1]);
+}
+
+// M1 (z_pad x z_pad, both triangles) = I - H,  H = V D V^T - V diag(r) V^T = -G + G2 from the Gram kernels' lower tiles
+// (read at i >= j only: exactly symmetric); G2 == nullptr: r = 0 (VFE)
+__global__ __launch_bounds__(256) void k_sgp_form_m1(const double *__restrict__ G, const double *__restrict__ G2, int zext,
+                                                     int z_pad, double *__restrict__ M1) {
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (j >= z_pad) return;
+    const int64_t lo = (int64_t)(i > j ? i : j) * zext + (i > j ? j : i);
+    double h = -G[lo];
+    if (G2) h += G2[lo];
+    M1[(int64_t)i * z_pad + j] = ((i == j) ? 1.0 : 0.0) - h;
+}
+
+// out (nout doubles) = the sums over the n x nz rectangle with rows xT, columns zT and weights T
+int launch_grad_rect(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, const double *zT, int64_t ldz, int nz, int d,
+                     const double *coef, const double *T, int64_t ldt, double *part, double *out) {
+    const int nout = d + 1, nout_pad = (int)round_up(nout, 32);
+    const int ntc = (nz + 63) / 64;
+    const int64_t nt = (int64_t)((n + 63) / 64) * ntc;
+    if (nt > 0x7fffffff) {
+        set_error("sparse GP gradient: too many tiles");
+        return EGX_ERR_UNSUPPORTED;
+    }
+    const int ntiles = (int)nt, nwg = ntiles < kRectMaxWG ? ntiles : kRectMaxWG;
+    const int dc = d < kRectDC ? d : kRectDC;
+    const int dk = nout <= 8 ? 8 : (nout <= 16 ? 16 : 32);
+    const size_t lds = sizeof(double) * (size_t)std::max(2 * dc * 64, 4 * dk);
+    const dim3 grid((unsigned)nwg, (unsigned)((nout + dk - 1) / dk));
+#define EGX_RECT(C_, DK_)                                                                                                    \
+    hipLaunchKernelGGL((k_sgp_grad_rect<C_, DK_>), grid, dim3(256), lds, s, xT, ldx, n, zT, ldz, nz, d, coef, T, ldt, ntc, ntiles, \
+                       nout, nout_pad, part)
+#define EGX_RECT_DK(C_)                 \
+    if (dk == 8) EGX_RECT(C_, 8);       \
+    else if (dk == 16) EGX_RECT(C_, 16); \
+    else EGX_RECT(C_, 32)
+    switch (corr) {
+        case EGX_CORR_SQUARED_EXPONENTIAL: EGX_RECT_DK(EGX_CORR_SQUARED_EXPONENTIAL); break;
+        case EGX_CORR_ABSOLUTE_EXPONENTIAL: EGX_RECT_DK(EGX_CORR_ABSOLUTE_EXPONENTIAL); break;
+        case EGX_CORR_MATERN32: EGX_RECT_DK(EGX_CORR_MATERN32); break;
+        case EGX_CORR_MATERN52: EGX_RECT_DK(EGX_CORR_MATERN52); break;
+        default: set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;
+    }
+#undef EGX_RECT_DK
+#undef EGX_RECT
+    hipLaunchKernelGGL(k_sgp_grad_reduce, dim3((unsigned)nout), dim3(256), 0, s, part, nwg, nout_pad, out);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+}  // namespace
+
+namespace egx {
+
+// After a successful sgp_eval(theta, sigma2, noise) whose factors are resident (Kz, dinv_z, RT, s0, A with b in row z_pad,
+// dinv_a, G): grad (d + 2) = dL/dtheta_0..d-1, dL/dsigma2, dL/dnoise.  Caller holds g->mu.
+int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad) {
+    const int n = g->n, d = g->d, nz = g->nz, n_pad = g->n_pad, z_pad = g->z_pad, zext = g->zext;
+    const int vfe = g->method != 0;
+    const double sigma = std::sqrt(sigma2);
+    hipStream_t s = g->stream;
+    const size_t rect = (size_t)n_pad * z_pad, sq = (size_t)z_pad * z_pad;
+    const int nout = d + 1, nout_pad = (int)round_up(nout, 32);
+    EGX_RC(g->gr_E.alloc(rect));
+    EGX_RC(g->gr_rows.alloc((size_t)7 * n_pad));
+    EGX_RC(g->gr_sq.alloc(3 * sq));
+    EGX_RC(g->gr_vec.alloc((size_t)2 * z_pad));
+    EGX_RC(g->gr_part.alloc((size_t)kRectMaxWG * nout_pad));
+    EGX_RC(g->gr_out.alloc((size_t)2 * nout_pad + 32));
+    if (!vfe) EGX_RC(g->gr_G2.alloc((size_t)zext * zext));
+    double *E = g->gr_E.p, *F = g->W.p;  // W (zext x n_pad) holds the n_pad x z_pad F once the Gram products are done
+    double *e2 = g->gr_rows.p, *eb = e2 + n_pad, *alpha = eb + n_pad, *beta = alpha + n_pad, *q = beta + n_pad, *sr = q + n_pad,
+           *p = sr + n_pad;
+    double *M1 = g->gr_sq.p, *X = M1 + sq, *Sh = X + sq;
+    double *t1 = g->gr_vec.p, *wt = t1 + z_pad;
+    double *out_nz = g->gr_out.p, *out_zz = out_nz + nout_pad, *sums = out_zz + nout_pad;
+    const double *b = g->A.p + (size_t)z_pad * z_pad;  // row z_pad of A: L^-1 V (beta o y), zero beyond nz
+    EGX_RC(sgp_ensure_inverse_factors(g));  // Wz = C_z^-T, Wa = L^-T of the resident factors
+    // E~ = RT L^-T, its row norms and E~ b
+    EGX_HIP_CHECK(hipMemcpyAsync(E, g->RT.p, sizeof(double) * rect, hipMemcpyDeviceToDevice, s));
+    EGX_RC(launch_trsm_rows(s, g->A.p, z_pad, z_pad, g->dinv_a.p, E, z_pad, n_pad));
+    EGX_RC(launch_row_reduce(s, E, z_pad, n_pad, nz, b, z_pad, 1, e2, eb));
+    hipLaunchKernelGGL(k_sgp_grad_rows, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, n, n_pad, g->s0.p, e2, eb, g->y.p,
+                       sigma, sigma2, noise, g->nugget, vfe, alpha, beta, q, sr, p);
+    const int nsum = std::min(256, (n + 1023) / 1024);
+    hipLaunchKernelGGL(k_sgp_sum2, dim3((unsigned)nsum), dim3(256), 0, s, p, g->s0.p, n, g->gr_part.p);
+    hipLaunchKernelGGL(k_sgp_grad_reduce, dim3(2), dim3(256), 0, s, g->gr_part.p, nsum, 32, sums);
+    // FITC: G2 = -V diag(r) V^T, the Gram product of the likelihood with sqrt(r) in place of sqrt(beta)
+    if (!vfe) {
+        EGX_RC(sgp_launch_transpose_scale(g, sr, sigma));
+        EGX_RC(launch_gram_lower(s, g->W.p, n_pad, zext, n_pad, g->gr_G2.p, zext, g->P.p));
+    }
+    // w~ = Wz Wa b
+    EGX_RC(launch_uptri_gemv(s, g->Wa.p, z_pad, z_pad, b, t1));
+    EGX_RC(launch_uptri_gemv(s, g->Wz.p, z_pad, z_pad, t1, wt));
+    // S^ = Wz (I - H - Wa Wa^T) Wz^T - w~ w~^T
+    hipLaunchKernelGGL(k_sgp_form_m1, dim3((unsigned)((z_pad + 255) / 256), (unsigned)z_pad), dim3(256), 0, s, g->G.p,
+                       vfe ? nullptr : g->gr_G2.p, zext, z_pad, M1);
+    EGX_RC(launch_gemm_nt_sub(s, M1, z_pad, g->Wa.p, z_pad, g->Wa.p, z_pad, z_pad, z_pad, z_pad, 0));
+    EGX_HIP_CHECK(hipMemsetAsync(X, 0, sizeof(double) * sq, s));
+    EGX_RC(launch_gemm_nt_sub(s, X, z_pad, g->Wz.p, z_pad, M1, z_pad, z_pad, z_pad, z_pad, 0));  // X = -Wz M1 (M1 symmetric)
+    hipLaunchKernelGGL(k_sgp_outer_neg, dim3((unsigned)((sq / 2 + 255) / 256)), dim3(256), 0, s, wt, wt, 1.0, z_pad, (int64_t)sq, Sh);
+    EGX_RC(launch_gemm_nt_sub(s, Sh, z_pad, X, z_pad, g->Wz.p, z_pad, z_pad, z_pad, z_pad, 0));
+    // T^T = -alpha w^T - F C_z^-1,  F = diag(q) RT - diag(beta) E~ L^-1
+    hipLaunchKernelGGL(k_sgp_scale_pair, dim3((unsigned)((rect / 2 + 255) / 256)), dim3(256), 0, s, g->RT.p, q, beta, z_pad,
+                       (int64_t)rect, F, E);
+    EGX_RC(launch_gemm_nt_sub(s, F, z_pad, E, z_pad, g->Wa.p, z_pad, n_pad, z_pad, z_pad, 0));
+    hipLaunchKernelGGL(k_sgp_outer_neg, dim3((unsigned)((rect / 2 + 255) / 256)), dim3(256), 0, s, alpha, wt, 1.0 / sigma, z_pad,
+                       (int64_t)rect, E);
+    EGX_RC(launch_gemm_nt_sub(s, E, z_pad, F, z_pad, g->Wz.p, z_pad, n_pad, z_pad, z_pad, 0));
+    // the two rectangles of pairs
+    EGX_RC(launch_grad_rect(s, g->corr, g->xT.p, n_pad, n, g->zT.p, z_pad, nz, d, g->coef.p, E, z_pad, g->gr_part.p, out_nz));
+    EGX_RC(launch_grad_rect(s, g->corr, g->zT.p, z_pad, nz, g->zT.p, z_pad, nz, d, g->coef.p, Sh, z_pad, g->gr_part.p, out_zz));
+    std::vector<double> h((size_t)2 * nout_pad + 32);
+    EGX_HIP_CHECK(hipMemcpyAsync(h.data(), g->gr_out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    EGX_HIP_CHECK(hipStreamSynchronize(s));
+    const double *hn = h.data(), *hz = hn + nout_pad;
+    const double sum_p = h[(size_t)2 * nout_pad], sum_s0 = h[(size_t)2 * nout_pad + 1];
+    for (int k = 0; k < d; k++) grad[k] = -sigma2 * hn[k] + 0.5 * hz[k];
+    const double nu = std::fmax(noise, g->nugget), be = 1.0 / nu;
+    const double c_sigma = vfe ? (double)n * be : sum_p;
+    grad[d] = -0.5 * (2.0 * hn[d] - hz[d] / sigma2 + c_sigma);
+    if (!vfe) grad[d + 1] = -0.5 * sum_p;
+    else grad[d + 1] = (noise > g->nugget) ? -0.5 * (sum_p - be * be * ((double)n * sigma2 - sigma2 * sum_s0)) : 0.0;
+    return EGX_SUCCESS;
+}
+
+}  // namespace egx

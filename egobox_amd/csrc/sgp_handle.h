@@ -1,5 +1,5 @@
 // Internal header of the sparse-GP translation units (sgp_host.hip: handle, likelihood, fit, state; sgp_predict.hip:
-// predictions, their x-gradients, sampling).
+// predictions, their x-gradients, sampling; sgp_grad.hip: the likelihood's gradient).
 #pragma once
 #include <mutex>
 #include <vector>
@@ -26,6 +26,9 @@ struct egx_sgp {
     bool winv_ok = false;
     egx::DevBuf Wz, Wa, q_x, q_RT, q_E, q_Ct, q_part, q_out;
     std::vector<double> h_x, h_out;
+    // likelihood gradient (sgp_grad.hip): grow-only workspace of egx_sgp_likelihood_grad, allocated by its first call.  gr_E is
+    // the one n_pad x z_pad buffer (E~, then T^T); gr_rows 7 n_pad vectors; gr_G2 zext^2 (FITC); gr_sq three z_pad^2 matrices
+    egx::DevBuf gr_E, gr_rows, gr_G2, gr_sq, gr_vec, gr_part, gr_out;
 };
 
 
@@ -33,4 +36,13 @@ namespace egx {
 // ---- sgp_predict.hip ----
 // any subset of mean (m), variance (m), d mean / dx (m x d), d var / dx (m x d) of the m queries; caller holds g->mu
 int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout, double *gyout, double *gvout);
+// Wz <- C_z^-T, Wa <- L^-T for the resident factors (cached until the next evaluation of the likelihood); caller holds g->mu
+int sgp_ensure_inverse_factors(egx_sgp *g);
+// ---- sgp_host.hip ----
+// W <- [scale * diag(sb) RT]^T with the row sb o y below it: the operand of the likelihood's Gram product, for any weights sb (n)
+int sgp_launch_transpose_scale(egx_sgp *g, const double *sb, double scale);
+// ---- sgp_grad.hip ----
+// grad (d + 2) = dL/dtheta, dL/dsigma2, dL/dnoise at the parameters of the evaluation whose factors are resident
+// (a successful sgp_eval that has just returned); caller holds g->mu
+int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad);
 }  // namespace egx

@@ -12,7 +12,8 @@
 //   A = I + G = L L^T,  b = L^-1 V (beta o y)                         launch_potrf with the right-hand side riding below A
 // The Woodbury matrix of the reference (nz x nz inverses) is never formed for predictions:
 //   kx^T Kmm^-1 kx = |U^-1 kx|^2,   kx^T U^-T (L L^T)^-1 U^-1 kx = |L^-1 U^-1 kx|^2   (two launch_trsm_rows + k_row_reduce)
-// Predictions, their x-gradients and sampling: sgp_predict.hip.
+// Predictions, their x-gradients and sampling: sgp_predict.hip.  The likelihood's closed-form gradient: sgp_grad.hip (its entry
+// points, egx_sgp_likelihood_grad and egx_sgp_fit_lbfgs, are here beside the evaluation they extend).
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -21,6 +22,7 @@
 
 #include "sgp_handle.h"
 #include "cobyla.h"
+#include "lbfgs.h"
 
 using namespace egx;
 
@@ -199,7 +201,83 @@ int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, 
     return EGX_SUCCESS;
 }
 
+// The box of a fit in x = log10(params) and the checks of its arguments (egx_sgp_fit, egx_sgp_fit_lbfgs): np parameters per start
+int sgp_fit_box(const double *params0s, int64_t n_starts, const double *lo, const double *hi, int np, std::vector<double> &blo,
+                std::vector<double> &bhi) {
+    blo.resize(np);
+    bhi.resize(np);
+    for (int i = 0; i < np; i++) {
+        if (!(lo[i] > 0.0) || !(hi[i] >= lo[i])) {
+            set_error("sparse GP parameter bounds must satisfy 0 < lo <= hi");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        blo[i] = std::log10(lo[i]);
+        bhi[i] = std::log10(hi[i]);
+    }
+    for (int64_t i = 0; i < n_starts * np; i++)
+        if (!(params0s[i] > 0.0)) {
+            set_error("sparse GP start points must be > 0");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    return EGX_SUCCESS;
+}
+
+// The end of a fit: the keeping evaluation at the best start's point (f = -likelihood at x = log10(params))
+int sgp_fit_keep(egx_sgp *g, double best_f, const std::vector<double> &best_x, int estimate_noise, double noise_fixed) {
+    const int d = g->d;
+    if (!std::isfinite(best_f)) {
+        set_error("sparse GP: no start point gave a finite likelihood");
+        return EGX_ERR_LIKELIHOOD;
+    }
+    std::vector<double> th(d);
+    for (int i = 0; i < d; i++) th[i] = std::pow(10.0, best_x[i]);
+    Eval ev;
+    const int rc = sgp_eval(g, th.data(), d, std::pow(10.0, best_x[d]),
+                            estimate_noise ? std::pow(10.0, best_x[d + 1]) : noise_fixed, ev, true);
+    if (rc) return rc;
+    if (ev.status != EGX_STATUS_OK) {
+        set_error("sparse GP: final evaluation failed");
+        return EGX_ERR_LINALG;
+    }
+    return EGX_SUCCESS;
+}
+
+// f(x) = -L(10^x) and its gradient in x = log10(params) for the L-BFGS machine: g_x = -p ln10 dL/dp, the noise component
+// dropped when the noise is fixed.  A failed evaluation is f = +inf with a zero gradient.
+int sgp_eval_grad_x(egx_sgp *g, const std::vector<double> &xv, int estimate_noise, double noise_fixed, double &f,
+                    std::vector<double> &gx) {
+    const int d = g->d, np = d + 1 + (estimate_noise ? 1 : 0);
+    std::vector<double> prm(d + 2), grad(d + 2, 0.0);
+    for (int i = 0; i <= d; i++) prm[i] = std::pow(10.0, xv[i]);
+    prm[d + 1] = estimate_noise ? std::pow(10.0, xv[d + 1]) : noise_fixed;
+    Eval ev;
+    EGX_RC(sgp_eval(g, prm.data(), d, prm[d], prm[d + 1], ev, false));
+    f = std::numeric_limits<double>::infinity();
+    gx.assign(np, 0.0);
+    if (ev.status != EGX_STATUS_OK) return EGX_SUCCESS;
+    EGX_RC(sgp_grad_tail(g, prm[d], prm[d + 1], grad.data()));
+    f = -ev.lkh;
+    const double ln10 = std::log(10.0);
+    for (int i = 0; i < np; i++) gx[i] = -prm[i] * ln10 * grad[i];
+    for (int i = 0; i < np; i++)
+        if (!std::isfinite(gx[i])) {
+            f = std::numeric_limits<double>::infinity();
+            gx.assign(np, 0.0);
+            break;
+        }
+    return EGX_SUCCESS;
+}
+
 }  // namespace
+
+namespace egx {
+int sgp_launch_transpose_scale(egx_sgp *g, const double *sb, double scale) {
+    hipLaunchKernelGGL(k_sgp_transpose_scale, dim3(g->n_pad / 32, g->zext / 32), dim3(256), 0, g->stream, g->RT.p, g->z_pad, g->n,
+                       g->nz, sb, g->y.p, scale, g->W.p, g->n_pad);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+}  // namespace egx
 
 extern "C" {
 
@@ -359,6 +437,25 @@ int32_t egx_sgp_likelihood(egx_sgp *g, const double *theta, int64_t theta_len, d
     return EGX_SUCCESS;
 }
 
+// The likelihood of egx_sgp_likelihood (the same launches first: the same bits) and its gradient, grad (d + 2) = dL/dtheta_0..d-1
+// (of the broadcast theta when theta_len == 1), dL/dsigma2, dL/dnoise; zeros whenever *status != EGX_STATUS_OK
+int32_t egx_sgp_likelihood_grad(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, double noise, double *lkh,
+                                double *grad, int32_t *status) {
+    if (!g || !theta || !lkh || !grad || !status) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    Eval ev;
+    EGX_RC(sgp_eval(g, theta, theta_len, sigma2, noise, ev, false));
+    for (int i = 0; i < g->d + 2; i++) grad[i] = 0.0;
+    if (ev.status == EGX_STATUS_OK) EGX_RC(sgp_grad_tail(g, sigma2, noise, grad));
+    *lkh = ev.lkh;
+    *status = ev.status;
+    return EGX_SUCCESS;
+}
+
 int32_t egx_sgp_finalize(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, double noise) {
     if (!g || !theta) {
         set_error("NULL argument");
@@ -388,20 +485,8 @@ int32_t egx_sgp_fit(egx_sgp *g, const double *params0s, int64_t n_starts, const 
     std::lock_guard<std::mutex> lock(g->mu);
     EGX_HIP_CHECK(hipSetDevice(g->device));
     const int d = g->d, np = d + 1 + (estimate_noise ? 1 : 0);
-    std::vector<double> blo(np), bhi(np);
-    for (int i = 0; i < np; i++) {
-        if (!(lo[i] > 0.0) || !(hi[i] >= lo[i])) {
-            set_error("sparse GP parameter bounds must satisfy 0 < lo <= hi");
-            return EGX_ERR_INVALID_VALUE;
-        }
-        blo[i] = std::log10(lo[i]);
-        bhi[i] = std::log10(hi[i]);
-    }
-    for (int64_t i = 0; i < n_starts * np; i++)
-        if (!(params0s[i] > 0.0)) {
-            set_error("sparse GP start points must be > 0");
-            return EGX_ERR_INVALID_VALUE;
-        }
+    std::vector<double> blo, bhi;
+    EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
     // maxeval = clamp(10 * theta_dim, 25, max_eval)  sparse_algorithm.rs:601-603
     int64_t per_start = 10 * (int64_t)d;
     if (per_start < 25) per_start = 25;
@@ -446,21 +531,42 @@ int32_t egx_sgp_fit(egx_sgp *g, const double *params0s, int64_t n_starts, const 
     }
     if (first_rc) return first_rc;
     if (n_evals_out) *n_evals_out = evals;
-    if (!std::isfinite(best_f)) {
-        set_error("sparse GP: no start point gave a finite likelihood");
-        return EGX_ERR_LIKELIHOOD;
+    return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);
+}
+
+// The gradient-based counterpart of egx_sgp_fit (new: on the closed-form gradient, sgp_grad.hip): a projected L-BFGS (lbfgs.h) per
+// start on x = log10(params), same parameter layout, box and checks.  The starts run one after the other -- the handle has one
+// workspace --, the best wins (the first on ties), one keeping evaluation follows.  max_iter < 1: 50 iterations per start.
+int32_t egx_sgp_fit_lbfgs(egx_sgp *g, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
+                          int32_t estimate_noise, double noise_fixed, int64_t max_iter, int64_t *n_evals_out) {
+    if (!g || !params0s || !lo || !hi || n_starts < 1) {
+        set_error("NULL argument / no start point");
+        return EGX_ERR_INVALID_VALUE;
     }
-    std::vector<double> th(d);
-    for (int i = 0; i < d; i++) th[i] = std::pow(10.0, best_x[i]);
-    Eval ev;
-    const int rc = sgp_eval(g, th.data(), d, std::pow(10.0, best_x[d]),
-                            estimate_noise ? std::pow(10.0, best_x[d + 1]) : noise_fixed, ev, true);
-    if (rc) return rc;
-    if (ev.status != EGX_STATUS_OK) {
-        set_error("sparse GP: final evaluation failed");
-        return EGX_ERR_LINALG;
+    std::lock_guard<std::mutex> lock(g->mu);
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    const int np = g->d + 1 + (estimate_noise ? 1 : 0);
+    std::vector<double> blo, bhi;
+    EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
+    if (max_iter < 1) max_iter = 50;
+    double best_f = std::numeric_limits<double>::infinity();
+    std::vector<double> best_x, xv, gx;
+    int64_t evals = 0;
+    for (int64_t st = 0; st < n_starts; st++) {
+        LbfgsStart m(params0s + st * np, np, blo, bhi, max_iter);
+        while (m.ask(xv)) {
+            double f;
+            EGX_RC(sgp_eval_grad_x(g, xv, estimate_noise, noise_fixed, f, gx));
+            evals++;
+            m.tell(f, gx);
+        }
+        if (m.f < best_f) {
+            best_f = m.f;
+            best_x = m.x;
+        }
     }
-    return EGX_SUCCESS;
+    if (n_evals_out) *n_evals_out = evals;
+    return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);
 }
 
 // Fitted state: theta (d), sigma2, noise, likelihood, Woodbury vector (nz) and -- computed on the host from the two

@@ -82,8 +82,12 @@ int check_sgp_query(egx_sgp *g, const double *xq, int64_t m) {
     return EGX_SUCCESS;
 }
 
+}  // namespace
+
+namespace egx {
+
 // Wz <- C_z^-T, Wa <- L^-T for the resident factors; invalidated by every evaluation of the likelihood (sgp_eval)
-int ensure_inverse_factors(egx_sgp *g) {
+int sgp_ensure_inverse_factors(egx_sgp *g) {
     if (g->winv_ok) return EGX_SUCCESS;
     const int z_pad = g->z_pad;
     const size_t sq = (size_t)z_pad * z_pad;
@@ -101,10 +105,6 @@ int ensure_inverse_factors(egx_sgp *g) {
     return EGX_SUCCESS;
 }
 
-}  // namespace
-
-namespace egx {
-
 int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout, double *gyout, double *gvout) {
     EGX_RC(check_sgp_query(g, xq, m));
     const int d = g->d, nz = g->nz, z_pad = g->z_pad;
@@ -115,7 +115,7 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
     }
     if (m == 0) return EGX_SUCCESS;
     hipStream_t s = g->stream;
-    if (gvout) EGX_RC(ensure_inverse_factors(g));
+    if (gvout) EGX_RC(sgp_ensure_inverse_factors(g));
     const int64_t cap = 65536;
     const int vfe = g->method != 0;
     const bool point = grad && m <= kSgpPointMax;  // few queries: another end of the gradient sequence (below)

@@ -99,6 +99,17 @@ class SgpHandle:
                                              C.byref(st)))
         return lk.value, st.value
 
+    def likelihood_grad(self, theta, sigma2, noise):
+        """(likelihood, gradient, status): the likelihood of `likelihood` (same bits) and its closed-form gradient
+        (d + 2: dL/dtheta_0..d-1 -- of the broadcast theta when one value is given --, dL/dsigma2, dL/dnoise), zeros
+        whenever status != 0 (egx_sgp_likelihood_grad)."""
+        th = L.as_f64(np.atleast_1d(theta), 1)
+        lk, st = C.c_double(), C.c_int32()
+        grad = np.zeros(self.d + 2)
+        L.check(self._lib.egx_sgp_likelihood_grad(self._h, L.dptr(th), th.size, float(sigma2), float(noise), C.byref(lk),
+                                                  L.dptr(grad), C.byref(st)))
+        return lk.value, grad, st.value
+
     def finalize(self, theta, sigma2, noise):
         th = L.as_f64(np.atleast_1d(theta), 1)
         L.check(self._lib.egx_sgp_finalize(self._h, L.dptr(th), th.size, float(sigma2), float(noise)))
@@ -109,6 +120,16 @@ class SgpHandle:
         ne = C.c_int64()
         L.check(self._lib.egx_sgp_fit(self._h, L.dptr(p0), p0.shape[0], L.dptr(lo), L.dptr(hi), int(bool(estimate_noise)),
                                       float(noise_fixed), int(max_eval), C.byref(ne)))
+        return ne.value
+
+    def fit_lbfgs(self, params0s, lo, hi, estimate_noise, noise_fixed, max_iter=50):
+        """As `fit` (same starts, box and parameter layout) by a projected L-BFGS on log10(params) driven by
+        `likelihood_grad` (egx_sgp_fit_lbfgs); returns the number of likelihood + gradient evaluations."""
+        p0 = L.as_f64(params0s, 2)
+        lo, hi = L.as_f64(lo, 1), L.as_f64(hi, 1)
+        ne = C.c_int64()
+        L.check(self._lib.egx_sgp_fit_lbfgs(self._h, L.dptr(p0), p0.shape[0], L.dptr(lo), L.dptr(hi),
+                                            int(bool(estimate_noise)), float(noise_fixed), int(max_iter), C.byref(ne)))
         return ne.value
 
     def _q(self, x):
@@ -204,6 +225,7 @@ class SgpParams:
         self._theta_tuning = G.ThetaTuning.Full([G.ThetaTuning.DEFAULT_INIT], [DEFAULT_THETA_BOUNDS])
         self._n_start, self._max_eval = G.GP_OPTIM_N_START, G.GP_COBYLA_MAX_EVAL
         self._nugget, self._seed, self._device = G.DEFAULT_NUGGET, None, -1
+        self._optimizer = "cobyla"  # the reference's optimiser; "lbfgs" uses the closed-form likelihood gradient
 
     def sparse_method(self, m):
         self._method = {"fitc": FITC, "vfe": VFE}[m.lower()] if isinstance(m, str) else int(m)
@@ -237,6 +259,14 @@ class SgpParams:
 
     def nugget(self, v):
         self._nugget = float(v)
+        return self
+
+    def optimizer(self, name):
+        """"cobyla" (default, as the reference tunes the sparse model), or the extension "lbfgs" (projected L-BFGS on
+        log10(params) driven by the closed-form likelihood gradient), as `GpParams.optimizer`."""
+        if name not in ("cobyla", "lbfgs"):
+            raise ValueError("optimizer must be 'cobyla' or 'lbfgs'")
+        self._optimizer = name
         return self
 
     def seed(self, s):
@@ -278,8 +308,11 @@ class SgpParams:
         for i, (lo, hi) in enumerate(bounds):   # keep every start inside its box
             params0[i] = min(max(params0[i], lo), hi)
         starts_log10, _ = prepare_multistart(self._n_start, params0, bounds, seed=42 if self._seed is None else self._seed)
-        n_evals = h.fit(10.0 ** starts_log10, [b[0] for b in bounds], [b[1] for b in bounds], est,
-                        self._noise.init, self._max_eval)
+        lo, hi = [b[0] for b in bounds], [b[1] for b in bounds]
+        if self._optimizer == "lbfgs":  # iterations per start from max_eval as GpParams.fit does
+            n_evals = h.fit_lbfgs(10.0 ** starts_log10, lo, hi, est, self._noise.init, max(5, min(100, self._max_eval // 4)))
+        else:
+            n_evals = h.fit(10.0 ** starts_log10, lo, hi, est, self._noise.init, self._max_eval)
         sgp = SparseGaussianProcess(h, self, n_evals)
         sgp._xy = (x, y)
         return sgp
@@ -392,14 +425,14 @@ class SparseGpMix:
     """python/src/sparse_gp_mix.rs: SparseGpx.builder(...) -> SparseGpMix, .fit(xt, yt) -> SparseGpx (single expert)."""
 
     def __init__(self, corr_spec=1, theta_init=None, theta_bounds=None, kpls_dim=None, n_start=G.GP_OPTIM_N_START, nz=None,
-                 z=None, method=FITC, seed=None, max_eval=G.GP_COBYLA_MAX_EVAL, device=-1):
+                 z=None, method=FITC, seed=None, max_eval=G.GP_COBYLA_MAX_EVAL, device=-1, optimizer="cobyla"):
         if kpls_dim is not None:
             raise NotImplementedError("KPLS rotations come from linfa-pls (outside the accelerated path)")
         if nz is None and z is None:
             raise ValueError("either nz or z has to be specified")  # sparse_gp_mix.rs builder check
         self.corr_spec, self.theta_init, self.theta_bounds = int(corr_spec), theta_init, theta_bounds
         self.n_start, self.nz, self.z, self.method, self.seed = n_start, nz, z, method, seed
-        self.max_eval, self.device = max_eval, device
+        self.max_eval, self.device, self.optimizer = max_eval, device, optimizer
 
     def fit(self, xt, yt):
         yt = np.asarray(yt, dtype=np.float64)
@@ -410,7 +443,7 @@ class SparseGpMix:
             raise NotImplementedError("pass exactly one correlation spec (expert selection belongs to egobox-moe)")
         ind = Inducings.Located(self.z) if self.z is not None else Inducings.Randomized(self.nz)
         p = SgpParams(corrs[self.corr_spec](), ind).sparse_method(self.method).n_start(self.n_start) \
-            .max_eval(self.max_eval).seed(self.seed).device(self.device)
+            .max_eval(self.max_eval).seed(self.seed).device(self.device).optimizer(self.optimizer)
         if self.theta_init is not None:
             p.theta_init(self.theta_init)
         if self.theta_bounds is not None:

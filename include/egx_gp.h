@@ -617,6 +617,18 @@ int32_t egx_sgp_finalize(egx_sgp *sgp, const double *theta, int64_t theta_len, d
  * params0s (n_starts x np), lo / hi (np), np = d + 1 + (estimate_noise != 0); maxeval = clamp(10 d, 25, max_eval) */
 int32_t egx_sgp_fit(egx_sgp *sgp, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
                     int32_t estimate_noise, double noise_fixed, int64_t max_eval, int64_t *n_evals_out);
+/* No counterpart in the reference (it tunes the sparse model derivative-free): the likelihood of egx_sgp_likelihood -- the same
+ * bits -- and its CLOSED-FORM gradient, grad (d + 2) = dL/dtheta_0..d-1 (of the broadcast theta when theta_len == 1),
+ * dL/dsigma2, dL/dnoise (VFE: dL/dnoise is exactly 0 while noise <= nugget, where the likelihood does not depend on it).
+ * Status and failure as egx_sgp_likelihood; whenever *status != 0, *lkh = -inf and grad is zeros.  Like egx_sgp_likelihood it
+ * un-fits the handle.  The first call allocates one more n_pad x z_pad buffer, which the handle keeps. */
+int32_t egx_sgp_likelihood_grad(egx_sgp *sgp, const double *theta, int64_t theta_len, double sigma2, double noise, double *lkh,
+                                double *grad /* d + 2: dL/dtheta_0..d-1, dL/dsigma2, dL/dnoise */, int32_t *status);
+/* egx_sgp_fit by a projected L-BFGS on x = log10(params) driven by egx_sgp_likelihood_grad: the same parameter layout, box and
+ * checks; the starts run one after the other, the best wins (the first on ties), one keeping evaluation follows.
+ * max_iter < 1: 50 iterations per start.  *n_evals_out counts likelihood + gradient evaluations. */
+int32_t egx_sgp_fit_lbfgs(egx_sgp *sgp, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
+                          int32_t estimate_noise, double noise_fixed, int64_t max_iter, int64_t *n_evals_out);
 /* SparseGaussianProcess::predict :237-241, predict_var :245-257 (clamp at 1e-15, + noise) */
 int32_t egx_sgp_predict(egx_sgp *sgp, const double *xq, int64_t m, double *y /*m*/);
 int32_t egx_sgp_predict_var(egx_sgp *sgp, const double *xq, int64_t m, double *var /*m*/);

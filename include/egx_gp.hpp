@@ -306,6 +306,24 @@ class SparseGaussianProcess {
     void finalize(const double *theta, int64_t theta_len, double sigma2, double noise) {
         check(egx_sgp_finalize(h_.get(), theta, theta_len, sigma2, noise));
     }
+    // the likelihood and its closed-form gradient (d + 2: theta.., sigma2, noise; zeros when status != 0): egx_sgp_likelihood_grad
+    struct LikelihoodGrad {
+        double likelihood;
+        std::vector<double> grad;
+        int32_t status;
+    };
+    LikelihoodGrad likelihood_grad(const double *theta, int64_t theta_len, double sigma2, double noise) {
+        LikelihoodGrad r{0.0, std::vector<double>((size_t)(d_ + 2)), 0};
+        check(egx_sgp_likelihood_grad(h_.get(), theta, theta_len, sigma2, noise, &r.likelihood, r.grad.data(), &r.status));
+        return r;
+    }
+    // multistart L-BFGS fit on that gradient (egx_sgp_fit_lbfgs); returns the number of likelihood + gradient evaluations
+    int64_t fit_lbfgs(const double *params0s, int64_t n_starts, const double *lo, const double *hi, bool estimate_noise,
+                      double noise_fixed, int64_t max_iter = 50) {
+        int64_t n_evals = 0;
+        check(egx_sgp_fit_lbfgs(h_.get(), params0s, n_starts, lo, hi, estimate_noise ? 1 : 0, noise_fixed, max_iter, &n_evals));
+        return n_evals;
+    }
     std::vector<double> predict(const double *x, int64_t m) const {
         std::vector<double> y((size_t)m);
         check(egx_sgp_predict(h_.get(), x, m, y.data()));
