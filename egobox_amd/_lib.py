@@ -68,6 +68,21 @@ class InfillSurrogate(C.Structure):
                 ("precisions_chol", c_double_p), ("heaviside_factor", C.c_double), ("smooth", C.c_int32)]
 
 
+#: egx_model_kind
+MODEL_GP, MODEL_SGP = 0, 1
+
+
+class ModelRef(C.Structure):
+    """egx_model_ref"""
+    _fields_ = [("kind", C.c_int32), ("handle", C.c_void_p)]
+
+
+class InfillSurrogateAny(C.Structure):
+    """egx_infill_surrogate_any"""
+    _fields_ = [("experts", C.POINTER(ModelRef)), ("n_experts", C.c_int32), ("weights", c_double_p), ("means", c_double_p),
+                ("precisions_chol", c_double_p), ("heaviside_factor", C.c_double), ("smooth", C.c_int32)]
+
+
 class InfillStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("best_start", C.c_int64), ("evals", c_int64_p)]
 
@@ -227,6 +242,13 @@ SIGNATURES = [
                                           C.POINTER(C.c_void_p)]),
     ("egx_infill_eval_experts", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,
                                             c_double_p, c_double_p, c_double_p]),
+    ("egx_infill_create_any", C.c_int32, [C.POINTER(InfillConfig), C.POINTER(InfillSurrogateAny), c_double_p, C.c_int32,
+                                          C.POINTER(C.c_void_p)]),
+    ("egx_moe_predict_valvar_sgp", C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p, C.c_int64, C.c_int64, c_double_p,
+                                               c_double_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, c_double_p]),
+    ("egx_moe_predict_valvar_gradients_sgp", C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p, C.c_int64, C.c_int64,
+                                                         c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int32,
+                                                         c_double_p, c_double_p]),
 ]
 
 

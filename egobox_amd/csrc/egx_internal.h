@@ -248,6 +248,15 @@ int launch_infill_trend_mean(hipStream_t s, const InfillTrend &t);
 int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *x_std,
                                     double *gmean);
 int launch_infill_mix_mean(hipStream_t s, const InfillMix &g);
+// A SPARSE expert's tails for one tile (sgp_predict.hip's host arithmetic): mean (kTile) = the msplit partial sums of
+// launch_predict_mean (racc: msplit x kTile; the weight vector carries sigma2) in split order; var (kTile, or nullptr: the
+// mean-only form) = max(sigma2 - sigma2 (p2 + s q2), 1e-15) + noise, p2 / q2 (kTile) the row reductions of the two block solves
+int launch_infill_sgp_finish(hipStream_t s, const double *racc, int msplit, const double *p2, const double *q2, double sigma2,
+                             double noise, int vfe, double *mean, double *var);
+// gmean / gvar (kTile x d) from launch_xgrad's partial sums (nsplit x kTile x d each): gmean = sum, gvar = gv_scale * sum, exactly
+// 0 where the raw variance is below the clamp; out_v / gvar nullptr: the mean-only form
+int launch_infill_sgp_xgrad_finish(hipStream_t s, const double *out_y, const double *out_v, int nsplit, int d, const double *p2,
+                                   const double *q2, double sigma2, int vfe, double gv_scale, double *gmean, double *gvar);
 // EGX_CSTR_MEAN / _UTB: value[i] (the objective model's criterion, no feasibility factor), cstr[i * k + j], grad (m x d),
 // gcstr (m x k x d); any output may be nullptr; scale: the k scale_cstr on the device
 int launch_infill_cstr(hipStream_t s, const infill::Params &prm, int strategy, int k, int d, int64_t m, int64_t mstride,

@@ -1,4 +1,4 @@
-// EGO's infill criterion on fitted dense GPs (crates/ego/src/criteria/{ei,wb2}.rs, utils/{logei_helper,cstr_pof}.rs,
+// EGO's infill criterion on fitted GPs, dense or sparse (crates/ego/src/criteria/{ei,wb2}.rs, utils/{logei_helper,cstr_pof}.rs,
 // solver/solver_computations.rs:132-193, 297-475, solver/solver_infill_optim.rs:148-236): the minimised objective and its
 // x-gradient for m points in one call, from one objective model and k constraint models; the scaling pass; the lock-step
 // COBYLA multistart.
@@ -18,6 +18,13 @@
 // first maximum of the responsibilities -- every expert still evaluates the whole tile, so that every launch keeps the padded
 // batch of 128).  Locks, caches, checks and scratch sizes run over the flat list of all experts.
 //
+// An EXPERT is a dense GP or a SPARSE one (egx_infill_create_any: tagged references, mixed freely).  A sparse expert writes the
+// same table slots from its own tile sequence, sgp_expert_tile: the batched route of sgp_query (sgp_predict.hip) at the padded
+// batch of 128 -- raw x, K(x, z) . (sigma2 vec) in split partial sums, K(x, z), the two block solves with their row reductions,
+// k_infill_sgp_finish (var = egx_sgp_predict_var's: clamp, then + noise); with gradients the two transposed products with the
+// cached inverse factors, launch_xgrad twice, k_infill_sgp_xgrad_finish (exactly 0 under the clamp).  Everything downstream
+// reads slots only.  Its mean-only twin runs no solve and keeps the means' bits.
+//
 // CONSTRAINT STRATEGIES (egx_infill_set_cstr_strategy).  EGX_CSTR_INFILL folds the constraint surrogates into the objective (the
 // above).  Under EGX_CSTR_MEAN / _UTB the objective carries no feasibility factor and the constraints are handed to the
 // optimiser as c(x) <= 0 (egx_infill_eval_cstr, egx_infill_optimize_cstr; solver_infill_optim.rs:148-204).  Under MEAN nobody
@@ -26,15 +33,30 @@
 // weights, no second contraction; the means keep the bits of the full sequence, which forms r . gamma before its solve as
 // well.  A call that does not ask for anything of the constraint surrogates (egx_infill_eval without parts under MEAN / UTB)
 // does not run them at all.
-#include <set>
+#include <map>
 
 #include "gmx_point.h"
-#include "gp_handle.h"
+#include "sgp_handle.h"
 #include "infill_math.h"
 
 using namespace egx;
 
 namespace {
+
+// A tagged reference to an expert: a dense model or a sparse one (egx_model_ref); exactly one of the two pointers is set
+struct ModelRef {
+    egx_gp *gp = nullptr;
+    egx_sgp *sg = nullptr;
+    ModelRef() = default;
+    explicit ModelRef(egx_gp *g) : gp(g) {}
+    explicit ModelRef(egx_sgp *g) : sg(g) {}
+    bool sparse() const { return sg != nullptr; }
+    const void *addr() const { return sg ? static_cast<const void *>(sg) : static_cast<const void *>(gp); }
+    int d() const { return sg ? sg->d : gp->d; }
+    int device() const { return sg ? sg->device : gp->device; }
+    bool fitted() const { return sg ? sg->fitted : (bool)gp->fitted; }
+    hipStream_t stream() const { return sg ? sg->stream : gp->ws[0].stream; }
+};
 
 // models[first .. first + k) are the surrogate's experts; with k >= 2 they own the slots [eslot, eslot + k) of the expert tables
 struct Surrogate {
@@ -49,7 +71,7 @@ struct Surrogate {
 
 struct egx_infill {
     std::mutex mu;
-    std::vector<egx_gp *> models;  // every expert of every surrogate, surrogate by surrogate (borrowed)
+    std::vector<ModelRef> models;  // every expert of every surrogate, surrogate by surrogate (borrowed)
     std::vector<Surrogate> surr;   // [0] the objective, then the constraints
     bool mix_api = false;          // created by egx_infill_create_mix: messages name surrogate and expert
     int n_eslots = 0, k_max = 1;
@@ -62,6 +84,9 @@ struct egx_infill {
     DevBuf xraw, flag, mean, var, gmean, gvar, value, grad;
     DevBuf xcast;  // models with xtypes and a mixture among the surrogates: the call's CAST raw points (k_infill_prepare_mixint)
     DevBuf xqT, racc, RT, s0, sl, Wt, dneg, out_y, out_v;
+    // sparse experts: x_mean = 0 | x_std = 1 (the prepare kernel's parameters for RAW points), |b~|^2 of a tile, the copy of a~
+    DevBuf ident, s1, sE;
+    bool ident_on_device = false;
     // the experts of the mixtures: their tables (slot-major like mean / var), d p / d x of one tile, the diagnostics of a call
     DevBuf emean, evar, egmean, egvar, dprob, dg_probas, dg_dprobas;
     // how the constraint surrogates enter (infill::CstrStrategy), their scales, the tables of egx_infill_eval_cstr
@@ -76,11 +101,17 @@ namespace {
 // The distinct models' locks (a model may serve twice, e.g. as objective and as a constraint), taken in ADDRESS order, not in
 // index order: two handles that hold the same models in opposite roles and are evaluated from two threads would otherwise
 // take the exclusive locks in opposite orders.
+// Dense and sparse models share ONE order (a dense model's lock is a shared mutex, a sparse model's a plain one).
 struct ModelLocks {
     std::vector<std::unique_lock<std::shared_mutex>> held;
+    std::vector<std::unique_lock<std::mutex>> held_sparse;
     explicit ModelLocks(egx_infill *h) {
-        const std::set<egx_gp *, std::less<egx_gp *>> distinct(h->models.begin(), h->models.end());
-        for (egx_gp *gp : distinct) held.emplace_back(gp->mu);
+        std::map<const void *, ModelRef, std::less<const void *>> distinct;
+        for (const ModelRef &r : h->models) distinct.emplace(r.addr(), r);
+        for (const auto &kv : distinct) {
+            if (kv.second.sparse()) held_sparse.emplace_back(kv.second.sg->mu);
+            else held.emplace_back(kv.second.gp->mu);
+        }
     }
 };
 
@@ -95,8 +126,9 @@ std::string who(const egx_infill *h, int idx) {
 
 int check_fitted(const egx_infill *h) {
     for (size_t e = 0; e < h->models.size(); e++)
-        if (!h->models[e]->fitted) {
-            set_error("infill: " + who(h, (int)e) + " is not fitted (call egx_gp_finalize or egx_gp_fit first)");
+        if (!h->models[e].fitted()) {
+            set_error("infill: " + who(h, (int)e) + " is not fitted (call " +
+                      (h->models[e].sparse() ? "egx_sgp_finalize or egx_sgp_fit" : "egx_gp_finalize or egx_gp_fit") + " first)");
             return EGX_ERR_NOT_FITTED;
         }
     return EGX_SUCCESS;
@@ -104,28 +136,37 @@ int check_fitted(const egx_infill *h) {
 
 // same d, same device as expert 0 of the objective
 int check_shapes(egx_infill *h) {
-    h->d = h->models[0]->d;
-    h->device = h->models[0]->device;
+    h->d = h->models[0].d();
+    h->device = h->models[0].device();
     for (size_t e = 1; e < h->models.size(); e++) {
-        if (h->models[e]->d != h->d) {
-            set_error("infill: " + who(h, (int)e) + " has " + std::to_string(h->models[e]->d) + " inputs, " + who(h, 0) + " has " +
+        if (h->models[e].d() != h->d) {
+            set_error("infill: " + who(h, (int)e) + " has " + std::to_string(h->models[e].d()) + " inputs, " + who(h, 0) + " has " +
                       std::to_string(h->d));
             return EGX_ERR_INVALID_VALUE;
         }
-        if (h->models[e]->device != h->device) {
-            set_error("infill: " + who(h, (int)e) + " lives on device " + std::to_string(h->models[e]->device) + ", " + who(h, 0) +
+        if (h->models[e].device() != h->device) {
+            set_error("infill: " + who(h, (int)e) + " lives on device " + std::to_string(h->models[e].device()) + ", " + who(h, 0) +
                       " on device " + std::to_string(h->device));
             return EGX_ERR_INVALID_VALUE;
         }
     }
+    // the x-gradient contraction of a sparse expert stages d * (hcols + 5) doubles, hcols = 1 (sgp_predict.hip)
+    for (size_t e = 0; e < h->models.size(); e++)
+        if (h->models[e].sparse() && (int64_t)h->d * 6 > 20480) {
+            set_error("infill: " + who(h, (int)e) + ": the x-gradients of a sparse model need 6 d <= 20480 (d " + std::to_string(h->d) + ")");
+            return EGX_ERR_UNSUPPORTED;
+        }
     return EGX_SUCCESS;
 }
 
 // Mixed-integer models: every expert of every surrogate carries the same xtypes as expert 0 of the objective, or none does -- the
 // points of a call are one design space.  Read from the models at EVERY call (as their fitted state is), under their locks.
+// A sparse model carries none.
 int check_specs(const egx_infill *h) {
+    static const MixSpec none;
+    auto spec = [](const ModelRef &r) -> const MixSpec & { return r.sparse() ? none : r.gp->xspec; };
     for (size_t e = 1; e < h->models.size(); e++)
-        if (!h->models[e]->xspec.same(h->models[0]->xspec)) {
+        if (!spec(h->models[e]).same(spec(h->models[0]))) {
             set_error("infill: " + who(h, (int)e) + " and " + who(h, 0) + " carry different xtypes (egx_gp_set_xtypes): all or none, the same spec");
             return EGX_ERR_INVALID_VALUE;
         }
@@ -143,7 +184,7 @@ struct ExpertDiag {
 int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *var, double *gmean,
                 double *gvar, int *flag) {
     const int d = h->d;
-    egx_gp *gp = h->models[j];
+    egx_gp *gp = h->models[j].gp;
     const int n = gp->n, n_pad = gp->n_pad;
     const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
     // (xtypes: cast in the same launch; the expert that writes the flags leaves the cast raw tile for k_infill_mix as well)
@@ -177,7 +218,7 @@ int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool w
 // The mean-only sequence of one expert for one tile: what expert_tile launches for mean / gmean and nothing else.
 int expert_tile_mean(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *gmean, int *flag) {
     const int d = h->d;
-    egx_gp *gp = h->models[j];
+    egx_gp *gp = h->models[j].gp;
     const int n = gp->n, n_pad = gp->n_pad;
     const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
     EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag, dev_spec(gp)));
@@ -195,6 +236,53 @@ int expert_tile_mean(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, b
     EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
                         gp->d_gamma, 0, 1, nsplit, h->out_y.p));
     return launch_infill_xgrad_finish_mean(st, tr, d, nsplit, h->out_y.p, dev_xnorm(gp) + d, gmean);
+}
+
+// A SPARSE expert's launch sequence for one tile, the batched route of sgp_query (sgp_predict.hip) at the padded batch of 128
+// whatever the call's size: raw x, K(x, z) . (sigma2 vec) in split partial sums, K(x, z), the two block solves with their row
+// reductions, the finish; with gradients the two transposed products with the cached inverse factors (sgp_ensure_inverse_factors,
+// built by eval_locked), the two contractions and their finish.  Arguments as expert_tile.
+int sgp_expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *var, double *gmean,
+                    double *gvar, int *flag) {
+    const int d = h->d;
+    egx_sgp *g = h->models[j].sg;
+    const int nz = g->nz, z_pad = g->z_pad, vfe = g->method != 0;
+    const int msplit = mean_splits(z_pad, kTile), nsplit = xgrad_splits(nz, kTile);
+    const size_t blk = (size_t)kTile * z_pad;
+    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, h->ident.p, h->xqT.p, flag));
+    EGX_RC(launch_predict_mean(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->vec.p, h->racc.p, msplit));
+    EGX_RC(launch_cross_corr(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, h->RT.p, z_pad));
+    EGX_RC(launch_trsm_rows(st, g->Kz.p, z_pad, z_pad, g->dinv_z.p, h->RT.p, z_pad, kTile));  // a~ = C_z^-1 r
+    EGX_RC(launch_row_reduce(st, h->RT.p, z_pad, kTile, nz, nullptr, 0, 0, h->s0.p, nullptr));
+    if (want_g) EGX_RC(sgp_launch_scale_copy(st, h->RT.p, vfe ? -1.0 : 1.0, (int64_t)blk, h->sE.p));  // E = -s a~: the GEMMs subtract
+    EGX_RC(launch_trsm_rows(st, g->A.p, z_pad, z_pad, g->dinv_a.p, h->RT.p, z_pad, kTile));  // b~ = L^-1 a~
+    EGX_RC(launch_row_reduce(st, h->RT.p, z_pad, kTile, nz, nullptr, 0, 0, h->s1.p, nullptr));
+    EGX_RC(launch_infill_sgp_finish(st, h->racc.p, msplit, h->s0.p, h->s1.p, g->sigma2, g->noise, vfe, mean, var));
+    if (!want_g) return EGX_SUCCESS;
+    // E -= b~ (L^-T)^T, then Ct = 0 - C_z^-T E^T = s c transposed (z_pad x 128): the weight layout of launch_xgrad
+    EGX_RC(launch_gemm_nt_sub(st, h->sE.p, z_pad, h->RT.p, z_pad, g->Wa.p, z_pad, kTile, z_pad, z_pad, 0, 0));
+    EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * blk, st));
+    EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, g->Wz.p, z_pad, h->sE.p, z_pad, z_pad, kTile, z_pad, 0, 1));
+    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p));
+    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, h->Wt.p, kTile, 0, nsplit,
+                        h->out_v.p));
+    return launch_infill_sgp_xgrad_finish(st, h->out_y.p, h->out_v.p, nsplit, d, h->s0.p, h->s1.p, g->sigma2, vfe,
+                                          (vfe ? -2.0 : 2.0) * g->sigma2, gmean, gvar);
+}
+
+// The mean-only sequence of a sparse expert: what sgp_expert_tile launches for mean / gmean and nothing else -- no K(x, z) block,
+// no solve; the same partial sums in the same order, so the means keep the full sequence's bits.
+int sgp_expert_tile_mean(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, bool want_g, double *mean, double *gmean, int *flag) {
+    const int d = h->d;
+    egx_sgp *g = h->models[j].sg;
+    const int nz = g->nz, z_pad = g->z_pad;
+    const int msplit = mean_splits(z_pad, kTile), nsplit = xgrad_splits(nz, kTile);
+    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, h->ident.p, h->xqT.p, flag));
+    EGX_RC(launch_predict_mean(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->vec.p, h->racc.p, msplit));
+    EGX_RC(launch_infill_sgp_finish(st, h->racc.p, msplit, nullptr, nullptr, g->sigma2, g->noise, 0, mean, nullptr));
+    if (!want_g) return EGX_SUCCESS;
+    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p));
+    return launch_infill_sgp_xgrad_finish(st, h->out_y.p, nullptr, nsplit, d, nullptr, nullptr, g->sigma2, 0, 0.0, gmean, nullptr);
 }
 
 // what egx_infill_eval_cstr asks for beside value / grad (host pointers, any nullptr)
@@ -221,11 +309,30 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     const bool run_c = folded || parts || diag || (co && (co->cstr || co->gcstr));
     const bool mean_c = h->strategy == infill::kCstrMean && !diag && !(parts && (parts->var || parts->grad_var));
     const int n_obj = h->surr[0].k;  // models[0 .. n_obj) are the objective's experts
-    EGX_RC(set_device(h->models[0]));
-    hipStream_t st = h->models[0]->ws[0].stream;
+    EGX_HIP_CHECK(hipSetDevice(h->device));
+    hipStream_t st = h->models[0].stream();
+    bool any_sparse = false;
+    for (const ModelRef &r : h->models) any_sparse |= r.sparse();
     if (want_g)  // once per fitted state (synchronises the model's stream); the mean-only sequence does not read C^-T
-        for (int e = 0; e < (run_c && !mean_c ? ne : n_obj); e++) EGX_RC(ensure_winv(h->models[e]));
-    for (int e = 0; e < ne; e++) EGX_RC(ensure_trend_state(h->models[e], st));
+        for (int e = 0; e < (run_c && !mean_c ? ne : n_obj); e++) {
+            const ModelRef &r = h->models[e];
+            if (!r.sparse()) {
+                EGX_RC(ensure_winv(r.gp));
+            } else if (!r.sg->winv_ok) {  // built on the model's own stream: wait before the call's stream reads them
+                EGX_RC(sgp_ensure_inverse_factors(r.sg));
+                EGX_HIP_CHECK(hipStreamSynchronize(r.sg->stream));
+            }
+        }
+    for (int e = 0; e < ne; e++)
+        if (!h->models[e].sparse()) EGX_RC(ensure_trend_state(h->models[e].gp, st));
+    if (any_sparse && !h->ident_on_device) {
+        std::vector<double> id((size_t)2 * d, 0.0);
+        std::fill(id.begin() + d, id.end(), 1.0);
+        EGX_RC(h->ident.alloc(id.size()));
+        EGX_HIP_CHECK(hipMemcpyAsync(h->ident.p, id.data(), sizeof(double) * id.size(), hipMemcpyHostToDevice, st));
+        EGX_HIP_CHECK(hipStreamSynchronize(st));  // id is a local
+        h->ident_on_device = true;
+    }
     for (Surrogate &sg : h->surr)
         if (sg.k >= 2 && !sg.on_device) {
             EGX_RC(sg.d_gmx.alloc(sg.gmx.size()));
@@ -243,8 +350,16 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
         h->tol_on_device = true;
     }
     const int64_t M = round_up(m, kTile);
-    int n_pad_max = 0, p_max = 0, rp_max = 0, ms_max = 0, ns_max = 0;
-    for (egx_gp *gp : h->models) {
+    int n_pad_max = 0, p_max = 1, rp_max = 1, ms_max = 0, ns_max = 0, z_pad_max = 0;
+    for (const ModelRef &r : h->models) {
+        if (r.sparse()) {  // the inducing points stand where a dense model's training points do
+            n_pad_max = std::max(n_pad_max, r.sg->z_pad);
+            z_pad_max = std::max(z_pad_max, r.sg->z_pad);
+            ms_max = std::max(ms_max, mean_splits(r.sg->z_pad, kTile));
+            ns_max = std::max(ns_max, xgrad_splits(r.sg->nz, kTile));
+            continue;
+        }
+        const egx_gp *gp = r.gp;
         n_pad_max = std::max(n_pad_max, gp->n_pad);
         p_max = std::max(p_max, gp->p);
         rp_max = std::max(rp_max, gp->rhs_pad);
@@ -252,7 +367,7 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
         ns_max = std::max(ns_max, xgrad_splits(gp->n, kTile));
     }
     EGX_RC(h->xraw.alloc((size_t)m * d));
-    const bool typed = !h->models[0]->xspec.empty();
+    const bool typed = !h->models[0].sparse() && !h->models[0].gp->xspec.empty();
     if (typed && h->n_eslots > 0) EGX_RC(h->xcast.alloc((size_t)m * d));
     EGX_RC(h->flag.alloc((size_t)(M + 1) / 2));
     EGX_RC(h->mean.alloc((size_t)nm * M));
@@ -263,7 +378,9 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     EGX_RC(h->RT.alloc((size_t)kTile * n_pad_max));
     EGX_RC(h->s0.alloc(kTile));
     EGX_RC(h->sl.alloc((size_t)kTile * p_max));
+    if (any_sparse) EGX_RC(h->s1.alloc(kTile));
     if (want_g) {
+        if (any_sparse) EGX_RC(h->sE.alloc((size_t)kTile * z_pad_max));
         EGX_RC(h->gmean.alloc((size_t)nm * M * d));
         EGX_RC(h->gvar.alloc((size_t)nm * M * d));
         EGX_RC(h->grad.alloc((size_t)M * d));
@@ -302,15 +419,17 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
             const bool mean_only = js > 0 && mean_c;
             for (int e = 0; e < sg.k; e++) {
                 const size_t row = (lone ? (size_t)js : (size_t)(sg.eslot + e)) * M + t0;
+                const bool sparse = h->models[sg.first + e].sparse();
                 if (mean_only) {
-                    EGX_RC(expert_tile_mean(h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
-                                            want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr, nullptr));
+                    EGX_RC((sparse ? sgp_expert_tile_mean : expert_tile_mean)(
+                        h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
+                        want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr, nullptr));
                     continue;
                 }
-                EGX_RC(expert_tile(h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
-                                   (lone ? h->var.p : h->evar.p) + row, want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr,
-                                   want_g ? (lone ? h->gvar.p : h->egvar.p) + row * d : nullptr,
-                                   sg.first + e == 0 ? flag + t0 : nullptr));
+                EGX_RC((sparse ? sgp_expert_tile : expert_tile)(
+                    h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row, (lone ? h->var.p : h->evar.p) + row,
+                    want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr,
+                    want_g ? (lone ? h->gvar.p : h->egvar.p) + row * d : nullptr, sg.first + e == 0 ? flag + t0 : nullptr));
             }
             if (lone) continue;
             InfillMix mx;
@@ -395,7 +514,7 @@ int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, doub
                  const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr) {
     const int rc = eval_locked(h, xq, m, value, grad, parts, diag, co);
     if (rc) {  // nothing may still run on the handle's buffers
-        (void)hipStreamSynchronize(h->models[0]->ws[0].stream);
+        (void)hipStreamSynchronize(h->models[0].stream());
         (void)hipGetLastError();
     }
     return rc;
@@ -461,7 +580,7 @@ int32_t egx_infill_create(const egx_infill_config *cfg_in, egx_gp *obj_model, eg
     }
     EGX_RC(config_ok(cfg));
     std::unique_ptr<egx_infill> h(new egx_infill);
-    h->models.push_back(obj_model);
+    h->models.emplace_back(obj_model);
     for (int j = 0; j < n_cstr; j++) {
         if (!cstr_models[j]) {
             set_error("infill: model " + std::to_string(j + 1) + " is NULL");
@@ -471,7 +590,7 @@ int32_t egx_infill_create(const egx_infill_config *cfg_in, egx_gp *obj_model, eg
             set_error("infill: tolerance " + std::to_string(j) + " is NaN");
             return EGX_ERR_INVALID_VALUE;
         }
-        h->models.push_back(cstr_models[j]);
+        h->models.emplace_back(cstr_models[j]);
         h->tol.push_back(cstr_tols[j]);
     }
     for (size_t j = 0; j < h->models.size(); j++) {  // every surrogate a lone expert
@@ -483,8 +602,38 @@ int32_t egx_infill_create(const egx_infill_config *cfg_in, egx_gp *obj_model, eg
     return EGX_SUCCESS;
 }
 
-int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_surrogate *surrogates, const double *cstr_tols,
-                              int32_t n_cstr, egx_infill **out) {
+}  // extern "C"
+
+namespace {
+
+// expert e of a surrogate as a ModelRef: egx_infill_create_mix's dense handles, egx_infill_create_any's tagged references
+int expert_ref(const egx_infill_surrogate &sv, int e, const std::string &name, ModelRef &out) {
+    if (!sv.experts[e]) {
+        set_error(name + " expert " + std::to_string(e) + " is NULL");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    out = ModelRef(sv.experts[e]);
+    return EGX_SUCCESS;
+}
+int expert_ref(const egx_infill_surrogate_any &sv, int e, const std::string &name, ModelRef &out) {
+    const egx_model_ref &r = sv.experts[e];
+    if (r.kind != EGX_MODEL_GP && r.kind != EGX_MODEL_SGP) {
+        set_error(name + " expert " + std::to_string(e) + " has the unknown kind " + std::to_string(r.kind) +
+                  " (EGX_MODEL_GP or EGX_MODEL_SGP)");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (!r.handle) {
+        set_error(name + " expert " + std::to_string(e) + " is NULL");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    out = r.kind == EGX_MODEL_SGP ? ModelRef(static_cast<egx_sgp *>(r.handle)) : ModelRef(static_cast<egx_gp *>(r.handle));
+    return EGX_SUCCESS;
+}
+
+// egx_infill_create_mix and egx_infill_create_any: the same checks in the same order, the same handle
+template <class SurrogateView>
+int32_t create_from_surrogates(const egx_infill_config *cfg_in, const SurrogateView *surrogates, const double *cstr_tols,
+                               int32_t n_cstr, egx_infill **out) {
     if (!out) {
         set_error("out handle pointer is NULL");
         return EGX_ERR_INVALID_VALUE;
@@ -500,7 +649,7 @@ int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_
     std::unique_ptr<egx_infill> h(new egx_infill);
     h->mix_api = true;
     for (int j = 0; j <= n_cstr; j++) {
-        const egx_infill_surrogate &sv = surrogates[j];
+        const SurrogateView &sv = surrogates[j];
         const std::string name = "infill: surrogate " + std::to_string(j);
         if (sv.n_experts < 1 || !sv.experts) {
             set_error(name + " needs at least one expert");
@@ -514,15 +663,12 @@ int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_
         Surrogate &sg = h->surr.back();
         sg.first = (int)h->models.size(), sg.k = sv.n_experts, sg.smooth = sv.smooth != 0;
         for (int e = 0; e < sv.n_experts; e++) {
-            if (!sv.experts[e]) {
-                set_error(name + " expert " + std::to_string(e) + " is NULL");
-                return EGX_ERR_INVALID_VALUE;
-            }
-            h->models.push_back(sv.experts[e]);
+            ModelRef ref;
+            EGX_RC(expert_ref(sv, e, name, ref));
+            h->models.push_back(ref);
         }
         if (j > 0) h->tol.push_back(cstr_tols[j - 1]);
         if (sg.k < 2) continue;  // one cluster: the responsibilities are ones, the mixture is not read
-        const int64_t kk = sg.k, d = sv.experts[0]->d;
         if (!sv.weights || !sv.means || !sv.precisions_chol) {
             set_error(name + ": NULL weights, means or precisions_chol");
             return EGX_ERR_INVALID_VALUE;
@@ -531,6 +677,7 @@ int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_
             set_error(name + ": heaviside_factor must be positive and finite");
             return EGX_ERR_INVALID_VALUE;
         }
+        const int64_t kk = sg.k, d = h->models[sg.first].d();  // (the first read of a model: the pointer checks are done)
         bool finite = true, positive = true;
         for (int64_t i = 0; i < kk; i++) finite &= std::isfinite(sv.weights[i]), positive &= sv.weights[i] > 0.0;
         for (int64_t i = 0; i < kk * d; i++) finite &= std::isfinite(sv.means[i]);
@@ -561,6 +708,20 @@ int32_t egx_infill_create_mix(const egx_infill_config *cfg_in, const egx_infill_
     EGX_RC(finish_create(h.get(), cfg));
     *out = h.release();
     return EGX_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t egx_infill_create_mix(const egx_infill_config *cfg, const egx_infill_surrogate *surrogates, const double *cstr_tols,
+                              int32_t n_cstr, egx_infill **out) {
+    return create_from_surrogates(cfg, surrogates, cstr_tols, n_cstr, out);
+}
+
+int32_t egx_infill_create_any(const egx_infill_config *cfg, const egx_infill_surrogate_any *surrogates, const double *cstr_tols,
+                              int32_t n_cstr, egx_infill **out) {
+    return create_from_surrogates(cfg, surrogates, cstr_tols, n_cstr, out);
 }
 
 int32_t egx_infill_eval_experts(egx_infill *h, int32_t j, const double *xq, int64_t m, double *mean, double *var, double *grad_mean,
@@ -646,7 +807,7 @@ int32_t egx_infill_scaling(egx_infill *h, const double *pts, int64_t npts, doubl
     std::vector<double> mean((size_t)nm * npts);
     egx_infill_parts parts{mean.data(), nullptr, nullptr, nullptr};
     EGX_RC(eval_guarded(h, pts, npts, nullptr, nullptr, &parts));
-    hipStream_t st = h->models[0]->ws[0].stream;
+    hipStream_t st = h->models[0].stream();
     const int64_t M = round_up(npts, kTile);
     const int *flag = reinterpret_cast<const int *>(h->flag.p);
     EGX_RC(h->value.alloc((size_t)2 * M));  // [0, M): ei, then base; [M, 2M): fac

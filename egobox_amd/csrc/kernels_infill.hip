@@ -11,6 +11,9 @@
 //                      constraint surrogate whose variance nobody reads (EGX_CSTR_MEAN): no substitution, no s0 / sl, no
 //                      second contraction -- the same sums in the same order, so the means keep the full sequence's bits
 //   k_infill_cstr      the objective without the feasibility factor and the constraint values handed to the optimiser
+//   k_infill_sgp_finish, k_infill_sgp_xgrad_finish   a SPARSE expert's tails (sgp_predict.hip's host arithmetic): the split sums of
+//                      the mean, the clamped variance + noise with the host's roundings, the gradients (0 under the clamp);
+//                      var / gvar == nullptr is their mean-only form
 // None of them is matrix-shaped: they are latency-bound tails whose point is to keep the call free of host round trips.
 // Every reduction runs in a fixed order that depends on the model alone, and a workgroup (or thread) owns one point: a point's
 // result does not depend on its position in the tile nor on its companions.
@@ -220,6 +223,70 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish_mean(XgFini
             g.gmean[(int64_t)a * d + k] = (dfy + sy) * g.y_std / g.x_std[k];
         }
     }
+}
+
+// ---- a SPARSE expert's tails (sgp_predict.hip's host arithmetic per tile) ---------------------------------------------------
+// One lane per point of the tile (two waves).  mean = the msplit partial sums of K(x, z) . (sigma2 vec) added in split order
+// (the vector carries sigma2: egx_sgp's resident `vec`); var = max(sigma2 - sigma2 (p2 + s q2), 1e-15) + noise with the roundings
+// of sgp_query's host loop, so the clamp falls where egx_sgp_predict_var's does.  A flagged point was zeroed by the prepare
+// kernel and is evaluated like any other (the criterion kernels answer for it), as in k_infill_trend.
+__global__ __launch_bounds__(kTile) void k_infill_sgp_finish(const double *__restrict__ racc, int msplit, const double *__restrict__ p2,
+                                                            const double *__restrict__ q2, double sigma2, double noise, int vfe,
+                                                            double *__restrict__ mean, double *__restrict__ var) {
+    const int a = threadIdx.x;
+    double rg = 0.0;
+    for (int sp = 0; sp < msplit; sp++) rg = __dadd_rn(rg, racc[(int64_t)sp * kTile + a]);
+    mean[a] = rg;
+    if (!var) return;
+    const double quad = vfe ? __dmul_rn(sigma2, __dadd_rn(p2[a], q2[a])) : __dmul_rn(sigma2, __dsub_rn(p2[a], q2[a]));
+    double v = __dsub_rn(sigma2, quad);
+    if (v < 1e-15) v = 1e-15;
+    var[a] = __dadd_rn(v, noise);
+}
+
+// One thread per (point, coordinate) of the tile: the nsplit partial sums of the two contractions added in split order, then
+// gmean = 1 * sum (the weights carry sigma2), gvar = gv_scale * sum -- exactly 0 where the raw variance is below the clamp
+// (the decision of k_infill_sgp_finish, formed with the same roundings).  out_v / gvar nullptr: the mean half alone.
+__global__ __launch_bounds__(kInfThreads) void k_infill_sgp_xgrad_finish(const double *__restrict__ out_y,
+                                                                        const double *__restrict__ out_v, int nsplit, int d,
+                                                                        const double *__restrict__ p2, const double *__restrict__ q2,
+                                                                        double sigma2, int vfe, double gv_scale,
+                                                                        double *__restrict__ gmean, double *__restrict__ gvar) {
+    const int i = blockIdx.x * kInfThreads + threadIdx.x;
+    if (i >= kTile * d) return;
+    const int a = i / d;
+    const int64_t s_split = (int64_t)kTile * d;
+    double sy = 0.0;
+    for (int sp = 0; sp < nsplit; sp++) sy = __dadd_rn(sy, out_y[(int64_t)sp * s_split + i]);
+    gmean[i] = sy;
+    if (!gvar) return;
+    double sv = 0.0;
+    for (int sp = 0; sp < nsplit; sp++) sv = __dadd_rn(sv, out_v[(int64_t)sp * s_split + i]);
+    const double quad = vfe ? __dmul_rn(sigma2, __dadd_rn(p2[a], q2[a])) : __dmul_rn(sigma2, __dsub_rn(p2[a], q2[a]));
+    gvar[i] = __dsub_rn(sigma2, quad) < 1e-15 ? 0.0 : __dmul_rn(gv_scale, sv);
+}
+
+int launch_infill_sgp_finish(hipStream_t s, const double *racc, int msplit, const double *p2, const double *q2, double sigma2,
+                             double noise, int vfe, double *mean, double *var) {
+    if (msplit < 1 || !racc || !mean || (var && (!p2 || !q2))) {
+        set_error("infill: bad arguments of the sparse expert's finish");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    hipLaunchKernelGGL(k_infill_sgp_finish, dim3(1), dim3(kTile), 0, s, racc, msplit, p2, q2, sigma2, noise, vfe, mean, var);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
+int launch_infill_sgp_xgrad_finish(hipStream_t s, const double *out_y, const double *out_v, int nsplit, int d, const double *p2,
+                                   const double *q2, double sigma2, int vfe, double gv_scale, double *gmean, double *gvar) {
+    if (nsplit < 1 || d < 1 || !out_y || !gmean || (gvar && (!out_v || !p2 || !q2))) {
+        set_error("infill: bad arguments of the sparse expert's gradient finish");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    hipLaunchKernelGGL(k_infill_sgp_xgrad_finish, dim3((unsigned)((kTile * d + kInfThreads - 1) / kInfThreads)), dim3(kInfThreads), 0,
+                       s, out_y, out_v, nsplit, d, p2, q2, sigma2, vfe, gv_scale, gmean, gvar);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
 }
 
 // A surrogate that is a mixture of k >= 2 experts, after the experts' sequences have written their tables for the tile: one

@@ -23,12 +23,31 @@ struct ExpertRows {
     std::vector<double> y, v, gy, gv;  // values (me each) and x-gradients (me x d each) of one expert call
 };
 
+// the prediction entry points of the two kinds of expert, under one set of names
+inline int ex_predict(egx_gp *g, const double *x, int64_t m, double *y) { return egx_gp_predict(g, x, m, y); }
+inline int ex_predict_var(egx_gp *g, const double *x, int64_t m, double *v) { return egx_gp_predict_var(g, x, m, v); }
+inline int ex_predict_valvar(egx_gp *g, const double *x, int64_t m, double *y, double *v) { return egx_gp_predict_valvar(g, x, m, y, v); }
+inline int ex_gradients(egx_gp *g, const double *x, int64_t m, double *gy) { return egx_gp_predict_gradients(g, x, m, gy); }
+inline int ex_var_gradients(egx_gp *g, const double *x, int64_t m, double *gv) { return egx_gp_predict_var_gradients(g, x, m, gv); }
+inline int ex_valvar_gradients(egx_gp *g, const double *x, int64_t m, double *gy, double *gv) {
+    return egx_gp_predict_valvar_gradients(g, x, m, gy, gv);
+}
+inline int ex_predict(egx_sgp *g, const double *x, int64_t m, double *y) { return egx_sgp_predict(g, x, m, y); }
+inline int ex_predict_var(egx_sgp *g, const double *x, int64_t m, double *v) { return egx_sgp_predict_var(g, x, m, v); }
+inline int ex_predict_valvar(egx_sgp *g, const double *x, int64_t m, double *y, double *v) { return egx_sgp_predict_valvar(g, x, m, y, v); }
+inline int ex_gradients(egx_sgp *g, const double *x, int64_t m, double *gy) { return egx_sgp_predict_gradients(g, x, m, gy); }
+inline int ex_var_gradients(egx_sgp *g, const double *x, int64_t m, double *gv) { return egx_sgp_predict_var_gradients(g, x, m, gv); }
+inline int ex_valvar_gradients(egx_sgp *g, const double *x, int64_t m, double *gy, double *gv) {
+    return egx_sgp_predict_valvar_gradients(g, x, m, gy, gv);
+}
+
 // one expert's values through the entry point that serves the outputs wanted
-int expert_values(egx_gp *gp, const double *xin, int64_t me, bool want_y, bool want_v, ExpertRows &s) {
+template <class Expert>
+int expert_values(Expert *gp, const double *xin, int64_t me, bool want_y, bool want_v, ExpertRows &s) {
     if (want_y) s.y.resize(me);
     if (want_v) s.v.resize(me);
-    if (want_y && want_v) return egx_gp_predict_valvar(gp, xin, me, s.y.data(), s.v.data());
-    return want_y ? egx_gp_predict(gp, xin, me, s.y.data()) : egx_gp_predict_var(gp, xin, me, s.v.data());
+    if (want_y && want_v) return ex_predict_valvar(gp, xin, me, s.y.data(), s.v.data());
+    return want_y ? ex_predict(gp, xin, me, s.y.data()) : ex_predict_var(gp, xin, me, s.v.data());
 }
 
 // the local fold's payload through the collective (failures are carried into it: a rank that left early would hang the
@@ -47,25 +66,23 @@ int exchange_and_sum(egx_sweep *sw, const char *who, moe::LocalFold &lf, size_t 
     return EGX_SUCCESS;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t egx_moe_predict_valvar(egx_sweep *sw, egx_gp *const *experts, const int32_t *expert_ids, int64_t n_local,
-                               int64_t n_experts, const double *probas, const double *xq, int64_t m, int64_t d,
-                               int32_t smooth, double *val, double *var) {
+// egx_moe_predict_valvar / _valvar_sgp: `who` names the entry point in messages
+template <class Expert>
+int32_t moe_valvar(const char *who, egx_sweep *sw, Expert *const *experts, const int32_t *expert_ids, int64_t n_local,
+                   int64_t n_experts, const double *probas, const double *xq, int64_t m, int64_t d, int32_t smooth, double *val,
+                   double *var) {
     if (n_local < 0 || n_experts < 1 || m < 0 || d < 1 || (m > 0 && (!probas || !xq)) || (n_local > 0 && (!experts || !expert_ids)) ||
         (!val && !var)) {
-        set_error("egx_moe_predict_valvar: bad arguments");
+        set_error(std::string(who) + ": bad arguments");
         return EGX_ERR_INVALID_VALUE;
     }
     if (!sw && n_local != n_experts) {
-        set_error("egx_moe_predict_valvar: without a sweep handle (single process) every expert must be local");
+        set_error(std::string(who) + ": without a sweep handle (single process) every expert must be local");
         return EGX_ERR_INVALID_VALUE;
     }
     if (m == 0) return EGX_SUCCESS;
-    const moe::Fold<egx_gp> f{experts, expert_ids, n_local, n_experts, probas, xq, m, d, 1, smooth != 0};
-    auto eval = [&](egx_gp *gp, const double *xin, int64_t me, ExpertRows &s, std::string &msg) {
+    const moe::Fold<Expert> f{experts, expert_ids, n_local, n_experts, probas, xq, m, d, 1, smooth != 0};
+    auto eval = [&](Expert *gp, const double *xin, int64_t me, ExpertRows &s, std::string &msg) {
         const int rc = expert_values(gp, xin, me, val != nullptr, var != nullptr, s);
         if (rc) msg = last_error_string();
         return rc;
@@ -73,32 +90,33 @@ int32_t egx_moe_predict_valvar(egx_sweep *sw, egx_gp *const *experts, const int3
     auto acc = [&](int32_t g, const ExpertRows &s, const int64_t *rows, int64_t me, double *tv, double *tw) {
         moe::accumulate_values(probas, n_experts, m, g, val ? s.y.data() : nullptr, var ? s.v.data() : nullptr, rows, me, tv, tw);
     };
-    moe::LocalFold lf = moe::fold_local<ExpertRows>("egx_moe_predict_valvar", f, eval, acc);
-    return exchange_and_sum(sw, "egx_moe_predict_valvar", lf, (size_t)m, val, var);
+    moe::LocalFold lf = moe::fold_local<ExpertRows>(who, f, eval, acc);
+    return exchange_and_sum(sw, who, lf, (size_t)m, val, var);
 }
 
-int32_t egx_moe_predict_valvar_gradients(egx_sweep *sw, egx_gp *const *experts, const int32_t *expert_ids, int64_t n_local,
-                                         int64_t n_experts, const double *probas, const double *dprobas, const double *xq,
-                                         int64_t m, int64_t d, int32_t smooth, double *grad_val, double *grad_var) {
+template <class Expert>
+int32_t moe_valvar_gradients(const char *who, egx_sweep *sw, Expert *const *experts, const int32_t *expert_ids, int64_t n_local,
+                             int64_t n_experts, const double *probas, const double *dprobas, const double *xq, int64_t m, int64_t d,
+                             int32_t smooth, double *grad_val, double *grad_var) {
     if (n_local < 0 || n_experts < 1 || m < 0 || d < 1 || (m > 0 && (!probas || !xq)) || (n_local > 0 && (!experts || !expert_ids)) ||
         (!grad_val && !grad_var) || (smooth && n_experts > 1 && m > 0 && !dprobas)) {
-        set_error("egx_moe_predict_valvar_gradients: bad arguments (the smooth recombination of more than one expert needs dprobas)");
+        set_error(std::string(who) + ": bad arguments (the smooth recombination of more than one expert needs dprobas)");
         return EGX_ERR_INVALID_VALUE;
     }
     if (!sw && n_local != n_experts) {
-        set_error("egx_moe_predict_valvar_gradients: without a sweep handle (single process) every expert must be local");
+        set_error(std::string(who) + ": without a sweep handle (single process) every expert must be local");
         return EGX_ERR_INVALID_VALUE;
     }
     if (m == 0) return EGX_SUCCESS;
     const bool need_pp = smooth && n_experts > 1;  // the p' terms need the experts' values too
-    const moe::Fold<egx_gp> f{experts, expert_ids, n_local, n_experts, probas, xq, m, d, d, smooth != 0};
-    auto eval = [&](egx_gp *gp, const double *xin, int64_t me, ExpertRows &s, std::string &msg) {
+    const moe::Fold<Expert> f{experts, expert_ids, n_local, n_experts, probas, xq, m, d, d, smooth != 0};
+    auto eval = [&](Expert *gp, const double *xin, int64_t me, ExpertRows &s, std::string &msg) {
         int rc;
         if (grad_val) s.gy.resize((size_t)me * d);
         if (grad_var) s.gv.resize((size_t)me * d);
-        if (grad_val && grad_var) rc = egx_gp_predict_valvar_gradients(gp, xin, me, s.gy.data(), s.gv.data());
-        else if (grad_val) rc = egx_gp_predict_gradients(gp, xin, me, s.gy.data());
-        else rc = egx_gp_predict_var_gradients(gp, xin, me, s.gv.data());
+        if (grad_val && grad_var) rc = ex_valvar_gradients(gp, xin, me, s.gy.data(), s.gv.data());
+        else if (grad_val) rc = ex_gradients(gp, xin, me, s.gy.data());
+        else rc = ex_var_gradients(gp, xin, me, s.gv.data());
         if (!rc && need_pp) rc = expert_values(gp, xin, me, grad_val != nullptr, grad_var != nullptr, s);
         if (rc) msg = last_error_string();
         return rc;
@@ -107,8 +125,38 @@ int32_t egx_moe_predict_valvar_gradients(egx_sweep *sw, egx_gp *const *experts, 
         moe::accumulate_gradients(probas, need_pp ? dprobas : nullptr, n_experts, m, d, g, grad_val ? s.gy.data() : nullptr,
                                   grad_var ? s.gv.data() : nullptr, s.y.data(), s.v.data(), rows, me, tv, tw);
     };
-    moe::LocalFold lf = moe::fold_local<ExpertRows>("egx_moe_predict_valvar_gradients", f, eval, acc);
-    return exchange_and_sum(sw, "egx_moe_predict_valvar_gradients", lf, (size_t)m * d, grad_val, grad_var);
+    moe::LocalFold lf = moe::fold_local<ExpertRows>(who, f, eval, acc);
+    return exchange_and_sum(sw, who, lf, (size_t)m * d, grad_val, grad_var);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t egx_moe_predict_valvar(egx_sweep *sw, egx_gp *const *experts, const int32_t *expert_ids, int64_t n_local,
+                               int64_t n_experts, const double *probas, const double *xq, int64_t m, int64_t d,
+                               int32_t smooth, double *val, double *var) {
+    return moe_valvar("egx_moe_predict_valvar", sw, experts, expert_ids, n_local, n_experts, probas, xq, m, d, smooth, val, var);
+}
+
+int32_t egx_moe_predict_valvar_sgp(egx_sweep *sw, egx_sgp *const *experts, const int32_t *expert_ids, int64_t n_local,
+                                   int64_t n_experts, const double *probas, const double *xq, int64_t m, int64_t d,
+                                   int32_t smooth, double *val, double *var) {
+    return moe_valvar("egx_moe_predict_valvar_sgp", sw, experts, expert_ids, n_local, n_experts, probas, xq, m, d, smooth, val, var);
+}
+
+int32_t egx_moe_predict_valvar_gradients(egx_sweep *sw, egx_gp *const *experts, const int32_t *expert_ids, int64_t n_local,
+                                         int64_t n_experts, const double *probas, const double *dprobas, const double *xq,
+                                         int64_t m, int64_t d, int32_t smooth, double *grad_val, double *grad_var) {
+    return moe_valvar_gradients("egx_moe_predict_valvar_gradients", sw, experts, expert_ids, n_local, n_experts, probas, dprobas, xq,
+                                m, d, smooth, grad_val, grad_var);
+}
+
+int32_t egx_moe_predict_valvar_gradients_sgp(egx_sweep *sw, egx_sgp *const *experts, const int32_t *expert_ids, int64_t n_local,
+                                             int64_t n_experts, const double *probas, const double *dprobas, const double *xq,
+                                             int64_t m, int64_t d, int32_t smooth, double *grad_val, double *grad_var) {
+    return moe_valvar_gradients("egx_moe_predict_valvar_gradients_sgp", sw, experts, expert_ids, n_local, n_experts, probas, dprobas,
+                                xq, m, d, smooth, grad_val, grad_var);
 }
 
 }  // extern "C"

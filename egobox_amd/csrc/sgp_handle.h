@@ -38,6 +38,8 @@ namespace egx {
 int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout, double *gyout, double *gvout);
 // Wz <- C_z^-T, Wa <- L^-T for the resident factors (cached until the next evaluation of the likelihood); caller holds g->mu
 int sgp_ensure_inverse_factors(egx_sgp *g);
+// E <- sgn * RT over `count` doubles (an even count): the copy of a~ the transposed products subtract from
+int sgp_launch_scale_copy(hipStream_t s, const double *RT, double sgn, int64_t count, double *E);
 // ---- sgp_host.hip ----
 // W <- [scale * diag(sb) RT]^T with the row sb o y below it: the operand of the likelihood's Gram product, for any weights sb (n)
 int sgp_launch_transpose_scale(egx_sgp *g, const double *sb, double scale);

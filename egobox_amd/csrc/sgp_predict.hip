@@ -86,6 +86,12 @@ int check_sgp_query(egx_sgp *g, const double *xq, int64_t m) {
 
 namespace egx {
 
+int sgp_launch_scale_copy(hipStream_t s, const double *RT, double sgn, int64_t count, double *E) {
+    hipLaunchKernelGGL(k_sgp_scale_copy, dim3((unsigned)((count / 2 + 255) / 256)), dim3(256), 0, s, RT, sgn, count, E);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
 // Wz <- C_z^-T, Wa <- L^-T for the resident factors; invalidated by every evaluation of the likelihood (sgp_eval)
 int sgp_ensure_inverse_factors(egx_sgp *g) {
     if (g->winv_ok) return EGX_SUCCESS;

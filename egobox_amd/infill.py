@@ -16,9 +16,17 @@ CSTR_STRATEGIES = {"infill": 0, "mean": 1, "utb": 2}
 
 
 def _gp_handle(model):
-    """The `GpHandle` behind a GpHandle, a GaussianProcess or a single-expert Gpx."""
+    """The `GpHandle` behind a GpHandle, a GaussianProcess or a single-expert Gpx -- or the `SgpHandle` behind an SgpHandle, a
+    SparseGaussianProcess or a single-expert SparseGpx."""
     from .gp import GaussianProcess, GpHandle
     from .gpx import Gpx
+    from .sgp import SgpHandle, SparseGaussianProcess, SparseGpx
+    if isinstance(model, SparseGpx):
+        model = model._sgp
+    if isinstance(model, SparseGaussianProcess):
+        model = model._h
+    if isinstance(model, SgpHandle):
+        return model
     if isinstance(model, Gpx):
         if len(model._experts) != 1:
             raise L.InvalidValueError(L.ERR_INVALID_VALUE, "infill: mixtures with more than one cluster are not supported")
@@ -26,7 +34,8 @@ def _gp_handle(model):
     if isinstance(model, GaussianProcess):
         model = model.handle
     if not isinstance(model, GpHandle):
-        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: expected a GpHandle, GaussianProcess or Gpx, got {type(model).__name__}")
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: expected a GpHandle, GaussianProcess, Gpx, SgpHandle, "
+                                                       f"SparseGaussianProcess or SparseGpx, got {type(model).__name__}")
     return model
 
 
@@ -34,6 +43,9 @@ def _surrogate(model, j):
     """(expert handles, GaussianMixture or None, smooth) of surrogate j: a `GpMixture` of any number of clusters, or a single
     model (one expert, no mixture)."""
     from .moe import GaussianMixture, GpMixture
+    from .sgp import SparseGpx
+    if isinstance(model, SparseGpx) and model._moe is not None:  # a trained sparse mixture: its inner GpMixture
+        model = model._moe
     if not isinstance(model, GpMixture):
         return [_gp_handle(model)], None, True
     name = f"infill: surrogate {j}"
@@ -47,22 +59,26 @@ def _surrogate(model, j):
             experts.append(_gp_handle(expert))
         except L.InvalidValueError:
             raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{name} expert {e}: expected a library-backed GaussianProcess or "
-                                                           f"GpHandle, got {type(expert).__name__}") from None
+                                                           f"GpHandle (or their sparse counterparts), got "
+                                                           f"{type(expert).__name__}") from None
     return experts, model.gmx, model.recombination == "smooth"
 
 
 class InfillObjective:
     """`egx_infill`: one objective model, k >= 0 constraint models (kept alive by this object), a criterion and its parameters.
-    A model is a GpHandle, a GaussianProcess, a single-expert Gpx, a single-rank `egobox_amd.moe.GpMixture` of library-backed
+    A model is a GpHandle, a GaussianProcess, a single-expert Gpx, their sparse counterparts (SgpHandle, SparseGaussianProcess,
+    SparseGpx; a handle with a sparse model anywhere is built by egx_infill_create_any), a single-rank `egobox_amd.moe.GpMixture` of library-backed
     experts (any number of clusters, smooth or hard) or an `egobox_amd.mixint.MixintGpMixture`; models that carry xtypes
     (`GpHandle.set_xtypes`) must all carry the same ones, and every point is then cast on the device before it is evaluated: with a mixture among them the handle is built by egx_infill_create_mix
     and the recombination runs on the GPU; with single models only, by egx_infill_create as before.
 
     value / gradient are those of the MINIMISED objective: -crit / scale, times the probability of feasibility of the
-    constraint models (EI, WB2, WB2S) or minus its logarithm (LOG_EI)."""
+    constraint models (EI, WB2, WB2S) or minus its logarithm (LOG_EI).
+
+    tagged=True builds the handle by egx_infill_create_any even when no model is sparse (the same handle, the same bits)."""
 
     def __init__(self, obj_model, cstr_models=(), cstr_tols=(), criterion=LOG_EI, fmin=0.0, sigma_weight=1.0, feasibility=True,
-                 scale_ic=1.0, scale=1.0):
+                 scale_ic=1.0, scale=1.0, tagged=False):
         lib = L.load()
         self._lib = lib
         from .mixint import MixintGpMixture
@@ -71,7 +87,9 @@ class InfillObjective:
         # and is given; the optimisers work in the unfolded continuous box, `to_discrete_space` folds x_best)
         obj_model = obj_model.moe if isinstance(obj_model, MixintGpMixture) else obj_model
         cstr_models = tuple(m.moe if isinstance(m, MixintGpMixture) else m for m in cstr_models)
-        mixed = any(isinstance(m, GpMixture) for m in (obj_model, *cstr_models))
+        from .sgp import SgpHandle, SparseGpx
+        mixed = any(isinstance(m, GpMixture) or (isinstance(m, SparseGpx) and m._moe is not None)
+                    for m in (obj_model, *cstr_models))
         if mixed:
             self._surrogates = [_surrogate(m, j) for j, m in enumerate((obj_model, *cstr_models))]
             self._models = [e for experts, _, _ in self._surrogates for e in experts]
@@ -88,7 +106,21 @@ class InfillObjective:
         cfg.criterion, cfg.feasibility = int(criterion), int(bool(feasibility))
         cfg.fmin, cfg.sigma_weight, cfg.scale_ic, cfg.scale = float(fmin), float(sigma_weight), float(scale_ic), float(scale)
         self._h = C.c_void_p()
-        if mixed:
+        sparse = tagged or any(isinstance(m, SgpHandle) for m in self._models)
+        if sparse:  # tagged references (egx_infill_create_any): dense and sparse experts side by side
+            keep, structs = [], (L.InfillSurrogateAny * (k + 1))()
+            for st, (experts, gmx, smooth) in zip(structs, self._surrogates):
+                arr = (L.ModelRef * len(experts))(*[L.ModelRef(L.MODEL_SGP if isinstance(e, SgpHandle) else L.MODEL_GP,
+                                                               e._h.value) for e in experts])
+                st.experts, st.n_experts, st.smooth, st.heaviside_factor = arr, len(experts), int(smooth), 1.0
+                keep.append(arr)
+                if gmx is not None:
+                    w, mu, pc = L.as_f64(gmx.weights), L.as_f64(gmx.means), L.as_f64(gmx.precisions_chol)
+                    st.weights, st.means, st.precisions_chol = L.dptr(w), L.dptr(mu), L.dptr(pc)
+                    st.heaviside_factor = float(gmx.heaviside_factor)
+                    keep += [w, mu, pc]
+            L.check(lib.egx_infill_create_any(C.byref(cfg), structs, L.dptr(tols) if k else None, k, C.byref(self._h)))
+        elif mixed:
             keep, structs = [], (L.InfillSurrogate * (k + 1))()
             for st, (experts, gmx, smooth) in zip(structs, self._surrogates):
                 arr = (C.c_void_p * len(experts))(*[e._h.value for e in experts])

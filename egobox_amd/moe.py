@@ -546,26 +546,33 @@ class GpMixture(GpMetrics):
         return tuple(out[i] for i in range(len(arrays)))
 
     def _library_handles(self):
-        """The egx_gp* of this rank's experts when ALL of them are GPU handles (and the collective, if any, is the
-        library's): then the recombination runs inside libegx_gp_hip.so (egx_moe_predict_valvar)."""
+        """(ids, handles, sparse) of this rank's experts when ALL of them are GPU handles of ONE kind -- dense (egx_gp*) or
+        sparse (egx_sgp*: SparseGaussianProcess / SgpHandle) -- and the collective, if any, is the library's: then the
+        recombination runs inside libegx_gp_hip.so (egx_moe_predict_valvar, or its _sgp twin).  A mixture of both kinds
+        takes the numpy fold below."""
+        from .sgp import SgpHandle
         if self.world > 1 and self.sweep is None:
             return None
-        ids, hs = [], []
+        ids, hs, kinds = [], [], set()
         for i, e in enumerate(self.experts):
             if not self._mine(i):
                 continue
-            h = getattr(getattr(e, "_h", None), "_h", None)
+            owner = e if isinstance(e, SgpHandle) else getattr(e, "_h", None)
+            h = getattr(owner, "_h", None)
             if h is None or not h:
                 return None
+            kinds.add(isinstance(owner, SgpHandle))
             ids.append(i)
             hs.append(h)
-        return ids, hs
+        if len(kinds) > 1:
+            return None
+        return ids, hs, bool(kinds and kinds.pop())
 
     def _predict_valvar_library(self, x, lib_handles, want_val, want_var):
         import ctypes as C
         from . import _lib as L
         lib = L.load()
-        ids, hs = lib_handles
+        ids, hs, sparse = lib_handles
         m, d = x.shape
         k = len(self.experts)
         dev = getattr(self.gmx, "predict_probas_device", None)  # the library's kernel; a duck-typed mixture keeps its own
@@ -574,10 +581,11 @@ class GpMixture(GpMetrics):
         iarr = np.asarray(ids, dtype=np.int32)
         val = np.empty(m) if want_val else None
         var = np.empty(m) if want_var else None
-        L.check(lib.egx_moe_predict_valvar(self.sweep._h if self.sweep is not None else None, harr,
-                                           iarr.ctypes.data_as(L.c_int32_p), len(hs), k, L.dptr(probas), L.dptr(x), m, d,
-                                           1 if self.recombination == "smooth" else 0,
-                                           L.dptr(val) if want_val else None, L.dptr(var) if want_var else None))
+        entry = lib.egx_moe_predict_valvar_sgp if sparse else lib.egx_moe_predict_valvar
+        L.check(entry(self.sweep._h if self.sweep is not None else None, harr,
+                      iarr.ctypes.data_as(L.c_int32_p), len(hs), k, L.dptr(probas), L.dptr(x), m, d,
+                      1 if self.recombination == "smooth" else 0,
+                      L.dptr(val) if want_val else None, L.dptr(var) if want_var else None))
         return (val if want_val else np.zeros(m)), (var if want_var else np.zeros(m))
 
     def predict_valvar(self, x, want_val=True, want_var=True):
@@ -649,7 +657,7 @@ class GpMixture(GpMetrics):
         import ctypes as C
         from . import _lib as L
         lib = L.load()
-        ids, hs = lib_handles
+        ids, hs, sparse = lib_handles
         m, d = x.shape
         k = len(self.experts)
         smooth = self.recombination == "smooth"
@@ -664,11 +672,12 @@ class GpMixture(GpMetrics):
         iarr = np.asarray(ids, dtype=np.int32)
         gy = np.empty((m, d)) if want_val else None
         gv = np.empty((m, d)) if want_var else None
-        L.check(lib.egx_moe_predict_valvar_gradients(self.sweep._h if self.sweep is not None else None, harr,
-                                                     iarr.ctypes.data_as(L.c_int32_p), len(hs), k, L.dptr(probas),
-                                                     L.dptr(dprobas) if dprobas is not None else None, L.dptr(x), m, d,
-                                                     1 if smooth else 0, L.dptr(gy) if want_val else None,
-                                                     L.dptr(gv) if want_var else None))
+        entry = lib.egx_moe_predict_valvar_gradients_sgp if sparse else lib.egx_moe_predict_valvar_gradients
+        L.check(entry(self.sweep._h if self.sweep is not None else None, harr,
+                      iarr.ctypes.data_as(L.c_int32_p), len(hs), k, L.dptr(probas),
+                      L.dptr(dprobas) if dprobas is not None else None, L.dptr(x), m, d,
+                      1 if smooth else 0, L.dptr(gy) if want_val else None,
+                      L.dptr(gv) if want_var else None))
         return (gy if want_val else np.zeros((m, d))), (gv if want_var else np.zeros((m, d)))
 
     def predict_valvar_gradients(self, x, want_val=True, want_var=True):

@@ -811,7 +811,7 @@ int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo /*d*/, const do
  * weights that are not positive, differing d or device.  EGX_ERR_NOT_FITTED names surrogate and expert, here and in every
  * later call.  EGX_ERR_UNSUPPORTED when 3 (d | 1) + 2 (k | 1) > 320 (the recombination keeps that many doubles of LDS per
  * point; every mixture egx_gmm_fit can train, d <= 35 and k <= 16, fits).
- * Out of scope: mixtures whose experts live on several ranks (egx_sweep) and sparse-GP experts (egx_sgp). */
+ * Out of scope: mixtures whose experts live on several ranks (egx_sweep).  Sparse-GP experts (egx_sgp): egx_infill_create_any below. */
 typedef struct {
     egx_gp *const *experts; int32_t n_experts;       /* one per cluster, fitted, same d and device */
     const double *weights /*k*/, *means /*k*d*/, *precisions_chol /*k*d*d*/;  /* as egx_gmx_predict_probas; may be NULL when n_experts == 1 */
@@ -826,6 +826,47 @@ int32_t egx_infill_create_mix(const egx_infill_config *cfg, const egx_infill_sur
 int32_t egx_infill_eval_experts(egx_infill *h, int32_t j, const double *xq, int64_t m,
                                 double *mean /*k*m*/, double *var /*k*m*/, double *grad_mean /*k*m*d*/, double *grad_var /*k*m*d*/,
                                 double *probas /*m*k*/, double *dprobas /*m*k*d*/);
+
+/* ---- ... with SPARSE experts ------------------------------------------------------------------------------------------
+ * The same handle from TAGGED model references: an expert is a dense model (egx_gp*) or a fitted sparse one (egx_sgp*), mixed
+ * freely across the surrogates and inside one mixture; everything else as egx_infill_surrogate / egx_infill_create_mix, and a
+ * handle of dense experts only returns the bits of egx_infill_create / _create_mix.  Every egx_infill_* call works on such a
+ * handle unchanged (eval, eval_experts, eval_cstr, scaling, optimize, optimize_cstr, set / get_params, set / get_cstr_strategy).
+ * A sparse expert runs, per 128-point tile and at the padded batch of 128 whatever m is, the BATCHED sequence of
+ * egx_sgp_predict_valvar / _valvar_gradients (never their few-query route: a point's bits do not depend on its companions or
+ * its position): raw x (the sparse model does not normalise), K(x, z), the two block solves with their row reductions, the
+ * mean; with gradients the two transposed products with the cached inverse factors and the two contractions.  Semantics:
+ *   - the `var` of a sparse model (egx_infill_parts, egx_infill_eval_experts) is egx_sgp_predict_var's: the raw variance
+ *     clamped at 1e-15, THEN + noise; its gradient is egx_sgp_predict_var_gradients': exactly 0 where the clamp holds;
+ *   - the mean is the sum, in split order, of the partial sums of K(x, z) . (sigma2 vec) over a split of the inducing points
+ *     that depends on nz alone (within rounding of egx_sgp_predict, not bit for bit); a constraint surrogate under
+ *     EGX_CSTR_MEAN runs no solve and its means keep the bits of the full sequence;
+ *   - the model's fitted state is read at every call, as for dense models (a refit between two calls is followed);
+ *   - sparse handles carry no xtypes: a handle that mixes typed dense models with sparse ones is refused (all or none);
+ *   - the limit of the sparse x-gradients, 6 d <= 20480, is checked at creation: EGX_ERR_UNSUPPORTED.
+ * Checked before the device is touched, EGX_ERR_INVALID_VALUE naming surrogate and expert: NULL experts / handles, a kind that
+ * is neither EGX_MODEL_GP nor EGX_MODEL_SGP, n_experts < 1, the mixture data as for egx_infill_create_mix.
+ * Out of scope: mixtures whose experts live on several ranks (egx_sweep), xtypes on sparse models. */
+typedef enum { EGX_MODEL_GP = 0, EGX_MODEL_SGP = 1 } egx_model_kind;
+typedef struct { int32_t kind; void *handle; } egx_model_ref;        /* egx_gp* or egx_sgp*, borrowed */
+typedef struct {
+    const egx_model_ref *experts; int32_t n_experts;
+    const double *weights /*k*/, *means /*k*d*/, *precisions_chol /*k*d*d*/;
+    double heaviside_factor;
+    int32_t smooth;
+} egx_infill_surrogate_any;
+int32_t egx_infill_create_any(const egx_infill_config *cfg, const egx_infill_surrogate_any *surrogates /*1 + n_cstr*/,
+                              const double *cstr_tols, int32_t n_cstr, egx_infill **out);
+
+/* egx_moe_predict_valvar / _valvar_gradients for a mixture of SPARSE experts: the same arguments, routing, workers, order of
+ * additions, failure semantics and sw == NULL; every expert answers through egx_sgp_predict* on its points. */
+int32_t egx_moe_predict_valvar_sgp(egx_sweep *sw, egx_sgp *const *experts, const int32_t *expert_ids, int64_t n_local,
+                                   int64_t n_experts, const double *probas /*m*n_experts*/, const double *xq /*m*d*/,
+                                   int64_t m, int64_t d, int32_t smooth, double *val /*m*/, double *var /*m*/);
+int32_t egx_moe_predict_valvar_gradients_sgp(egx_sweep *sw, egx_sgp *const *experts, const int32_t *expert_ids, int64_t n_local,
+                                             int64_t n_experts, const double *probas /*m*n_experts*/,
+                                             const double *dprobas /*m*n_experts*d*/, const double *xq /*m*d*/, int64_t m,
+                                             int64_t d, int32_t smooth, double *grad_val /*m*d*/, double *grad_var /*m*d*/);
 
 #ifdef __cplusplus
 }

@@ -609,11 +609,28 @@ inline GmmFit gmm_fit(const double *data, int64_t n, int32_t dim, int32_t n_clus
 //
 // A surrogate of the mixture form (egx_infill_create_mix): the experts of a GpMixture (borrowed) and a copy of its Gaussian
 // mixture, as egx_gmx_predict_probas takes it.  One expert: the mixture is not read and may stay empty.
+// With SPARSE experts (egx_infill_create_any): build the surrogate from a SparseGaussianProcess, or add() experts of either
+// kind in cluster order; `models` then holds the tagged references and `experts` stays empty.
 struct InfillSurrogate {
     std::vector<const GaussianProcess *> experts;  // one per cluster
     std::vector<double> weights, means, precisions_chol;  // k, k x d, k x d x d
     double heaviside_factor = 1.0;
     bool smooth = true;  // false: hard recombination
+    std::vector<egx_model_ref> models;  // dense and sparse experts, one per cluster (non-empty: used instead of `experts`)
+    int64_t d = 0;                      // inputs of the models added
+
+    InfillSurrogate() = default;
+    explicit InfillSurrogate(const SparseGaussianProcess &sgp) { add(sgp); }  // one sparse expert, no mixture
+    InfillSurrogate &add(const GaussianProcess &gp) {
+        models.push_back(egx_model_ref{EGX_MODEL_GP, gp.handle()});
+        d = gp.dims().first;
+        return *this;
+    }
+    InfillSurrogate &add(const SparseGaussianProcess &sgp) {
+        models.push_back(egx_model_ref{EGX_MODEL_SGP, sgp.handle()});
+        d = sgp.dims().first;
+        return *this;
+    }
 };
 
 class InfillObjective {
@@ -633,6 +650,32 @@ class InfillObjective {
         cfg.fmin = fmin;
         cfg.sigma_weight = sigma_weight;
         cfg.feasibility = feasibility ? 1 : 0;
+        bool tagged = false;
+        for (const InfillSurrogate &sv : surrogates) tagged |= !sv.models.empty();
+        if (tagged) {  // sparse experts somewhere: every surrogate as tagged references (egx_infill_create_any)
+            std::vector<std::vector<egx_model_ref>> refs(surrogates.size());
+            std::vector<egx_infill_surrogate_any> raw_a(surrogates.size());
+            for (size_t j = 0; j < surrogates.size(); j++) {
+                const InfillSurrogate &sv = surrogates[j];
+                refs[j] = sv.models;
+                if (refs[j].empty())
+                    for (const GaussianProcess *e : sv.experts) refs[j].push_back(egx_model_ref{EGX_MODEL_GP, e ? e->handle() : nullptr});
+                n_experts_.push_back((int64_t)refs[j].size());
+                raw_a[j].experts = refs[j].data();
+                raw_a[j].n_experts = (int32_t)refs[j].size();
+                raw_a[j].weights = sv.weights.empty() ? nullptr : sv.weights.data();
+                raw_a[j].means = sv.means.empty() ? nullptr : sv.means.data();
+                raw_a[j].precisions_chol = sv.precisions_chol.empty() ? nullptr : sv.precisions_chol.data();
+                raw_a[j].heaviside_factor = sv.heaviside_factor;
+                raw_a[j].smooth = sv.smooth ? 1 : 0;
+            }
+            egx_infill *raw = nullptr;
+            check(egx_infill_create_any(&cfg, raw_a.data(), cstr_tols.data(), (int32_t)cstr_tols.size(), &raw));
+            h_.reset(raw);
+            d_ = !surrogates[0].models.empty() ? surrogates[0].d : surrogates[0].experts[0]->dims().first;
+            k_ = (int64_t)cstr_tols.size();
+            return;
+        }
         std::vector<std::vector<egx_gp *>> hs(surrogates.size());
         std::vector<egx_infill_surrogate> raw_s(surrogates.size());
         for (size_t j = 0; j < surrogates.size(); j++) {

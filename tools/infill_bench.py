@@ -22,6 +22,13 @@ a commit without them the tool times that leg alone, which is the yardstick.  Le
 again), medians, written to profiles/infill_cstr_round.txt.
 
     python tools/infill_bench.py --cstr [--out profiles/infill_cstr_round.txt] [--reps 15]
+
+--sparse runs the SPARSE leg: the objective is one sparse GP (n = 20000, nz = 512, d = 8, Matern-5/2, FITC), no constraints,
+value + gradient at m = 1, 128, 4096.  Composed = egx_sgp_predict_valvar + egx_sgp_predict_valvar_gradients (at m = 1 their
+few-query route) with the same host arithmetic; fused = the handle of egx_infill_create_any, which runs the batched route at
+the padded batch of 128 whatever m is.  Same protocol, written to profiles/infill_sparse_bench.txt; no threshold is set.
+
+    python tools/infill_bench.py --sparse [--out profiles/infill_sparse_bench.txt] [--reps 15]
 """
 import argparse
 import os
@@ -111,12 +118,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--mix", action="store_true", help="the mixture leg (k = 3 experts, smooth) instead of the single-model legs")
     ap.add_argument("--cstr", action="store_true", help="one lock-step round in MEAN, UTB and INFILL mode on one handle")
+    ap.add_argument("--sparse", action="store_true", help="the sparse leg: one sparse objective (nz = 512, d = 8), value + gradient")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "infill_cstr_round.txt" if args.cstr else
-                                "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
+        args.out = os.path.join(ROOT, "profiles", "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
+                                else "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
     def emit(s):
@@ -156,6 +164,42 @@ def main():
             obj.close()
             for h in hs:
                 h.close()
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        return
+    if args.sparse:
+        n, nz, d = 20000, 512, 8
+        emit("# infill evaluation on a sparse objective, composed (egx_sgp_predict_valvar + egx_sgp_predict_valvar_gradients + host")
+        emit("# arithmetic) vs fused (egx_infill_create_any / egx_infill_eval); LogEI, value + gradient, no constraints; Matern-5/2,")
+        emit("# FITC; median ms over %d calls (m = 4096: a fifth of them) after 3 warm-ups; legs alternated" % args.reps)
+        emit("# n nz d m composed_a_ms fused_ms composed_b_ms composed_spread fused/composed verdict  (composed_lib_ms: its two library calls alone)")
+        rng = np.random.default_rng(0)
+        x = rng.random((n, d)) * 2 - 1
+        y = np.sin(3 * x[:, 0]) + 0.5 * np.cos(2 * x[:, -1]) + 0.05 * rng.standard_normal(n)
+        z = x[rng.permutation(n)[:nz]].copy()
+        h = egx.SgpHandle(x, y, z, corr=3, method=0)
+        h.finalize(np.full(d, 2.0 / np.sqrt(d)), 1.3, 0.01)
+        fmin = float(np.quantile(y, 0.05))
+        obj = egx.InfillObjective(h, criterion=egx.LOG_EI, fmin=fmin)
+        for m in (1, 128, 4096):
+            xq = rng.random((m, d)) * 2 - 1
+            reps = args.reps if m < 4096 else max(3, args.reps // 5)
+            fused = lambda: obj.value_and_grad(xq)  # noqa: E731
+            lib = lambda: (h.predict_valvar(xq), h.predict_valvar_gradients(xq))  # noqa: E731
+            comp = lambda: composed([h], [], fmin, xq, True)  # noqa: E731
+            vc, gc = comp()
+            vf, gf = fused()
+            ok = np.allclose(vf, vc, rtol=1e-6, atol=1e-6) and np.allclose(gf, gc, rtol=1e-4, atol=1e-5 * (1 + np.abs(gc).max()))
+            ca = median_ms(comp, reps)
+            fu = median_ms(fused, reps)
+            cb = median_ms(comp, reps)
+            cl = median_ms(lib, reps)
+            c = min(ca, cb)
+            verdict = "fused faster" if fu < c else ("within the spread" if fu <= max(ca, cb) else "FUSED SLOWER")
+            emit(f"{n} {nz} {d} {m} {ca:.3f} {fu:.3f} {cb:.3f} {abs(ca - cb):.3f} {fu / c:.3f} {verdict}"
+                 + ("" if ok else "  RESULTS DIFFER") + f"  (composed_lib_ms {cl:.3f})")
+        obj.close()
+        h.close()
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         return
