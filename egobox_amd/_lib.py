@@ -92,6 +92,12 @@ class InfillCstrStats(C.Structure):
                 ("evals", c_int64_p)]
 
 
+class InfillSlsqpStats(C.Structure):
+    """egx_infill_slsqp_stats"""
+    _fields_ = [("rounds", C.c_int64), ("best_start", C.c_int64), ("feasible", C.c_int32), ("violation", C.c_double),
+                ("evals", c_int64_p), ("stop", c_int32_p)]
+
+
 class XTypeC(C.Structure):
     """egx_xtype"""
     _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("values", c_double_p)]
@@ -238,6 +244,8 @@ SIGNATURES = [
     ("egx_infill_eval_cstr", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("egx_infill_optimize_cstr", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
                                              c_double_p, c_double_p, C.POINTER(InfillCstrStats)]),
+    ("egx_infill_optimize_slsqp", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                              c_double_p, c_double_p, C.POINTER(InfillSlsqpStats)]),
     ("egx_infill_create_mix", C.c_int32, [C.POINTER(InfillConfig), C.POINTER(InfillSurrogate), c_double_p, C.c_int32,
                                           C.POINTER(C.c_void_p)]),
     ("egx_infill_eval_experts", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,

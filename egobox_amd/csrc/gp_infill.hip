@@ -38,6 +38,7 @@
 #include "gmx_point.h"
 #include "sgp_handle.h"
 #include "infill_math.h"
+#include "slsqp.h"
 
 using namespace egx;
 
@@ -1009,6 +1010,105 @@ int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo, const double *
     }
     bool any_finite = false;
     for (const Cobyla &c : mach) any_finite |= c.any_finite_f();
+    if (!any_finite) {
+        *f_best = std::numeric_limits<double>::infinity();
+        set_error("infill optimize: no start met a finite objective value");
+        return EGX_ERR_NO_FINITE_START;
+    }
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_optimize_slsqp(egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start,
+                                  int64_t max_eval, double *f_best, double *x_best, double *c_best, egx_infill_slsqp_stats *stats) {
+    if (!h || !lo || !hi || !x_start || !f_best || !x_best || n_start < 1) {
+        set_error("infill optimize: NULL argument or no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int d = h->d;
+    for (int i = 0; i < d; i++)
+        if (!(lo[i] <= hi[i]) || std::isinf(lo[i]) || std::isinf(hi[i])) {
+            set_error("infill optimize: bounds must be finite with lo <= hi (coordinate " + std::to_string(i) + ")");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    for (int64_t s = 0; s < n_start; s++)
+        for (int i = 0; i < d; i++)
+            if (!std::isfinite(x_start[s * d + i])) {
+                set_error("infill optimize: start point " + std::to_string(s) + " has a non-finite coordinate");
+                return EGX_ERR_INVALID_VALUE;
+            }
+    std::lock_guard<std::mutex> lock(h->mu);
+    // EGX_CSTR_INFILL: the constraint models are inside the objective, the machines see none
+    const int k = h->strategy == infill::kCstrInfill ? 0 : (int)h->surr.size() - 1;
+    if (k > 0 && !c_best) {
+        set_error("infill optimize: NULL argument or no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    ModelLocks locks(h);
+    // one SLSQP per start: ftol_rel = ftol_abs = 1e-4, at most min(10 n_start d, 2000) evaluations each
+    // (solver_infill_optim.rs:217-227).  The machine is told c_j as evaluated and solves c_j <= cstr_tol_j / scale_cstr_j: the
+    // constraint c_j - cstr_tol_j / scale_cstr_j <= 0 that optimizer.rs:188-199 hands to slsqp::minimize.
+    if (max_eval <= 0) max_eval = std::min<int64_t>(10 * n_start * d, 2000);
+    const std::vector<double> blo(lo, lo + d), bhi(hi, hi + d);
+    std::vector<double> cfeas((size_t)k);
+    for (int j = 0; j < k; j++) cfeas[j] = h->tol[j] / h->scale_cstr[j];
+    std::vector<Slsqp> mach;
+    mach.reserve((size_t)n_start);
+    for (int64_t s = 0; s < n_start; s++)
+        mach.emplace_back(std::vector<double>(x_start + s * d, x_start + (s + 1) * d), blo, bhi, k, 1e-4, 1e-4, max_eval, cfeas);
+    std::vector<double> pts, vals, grads, cvals, cgrads, x;
+    std::vector<size_t> who;
+    int64_t rounds = 0;
+    // all starts in LOCK-STEP: a round's points, line-search trial points included, are ONE evaluation with gradients
+    for (;;) {
+        pts.clear();
+        who.clear();
+        bool want_grad = true;
+        for (size_t q = 0; q < mach.size(); q++)
+            if (mach[q].ask(x, want_grad)) {
+                who.push_back(q);
+                pts.insert(pts.end(), x.begin(), x.end());
+            }
+        if (who.empty()) break;
+        const size_t m = who.size();
+        vals.assign(m, 0.0);
+        grads.assign(m * d, 0.0);
+        cvals.assign(m * (size_t)k + 1, 0.0);
+        cgrads.assign(m * (size_t)k * d + 1, 0.0);
+        if (h->strategy == infill::kCstrInfill) {
+            EGX_RC(eval_guarded(h, pts.data(), (int64_t)m, vals.data(), grads.data(), nullptr));
+        } else {
+            CstrOut co;
+            co.cstr = k > 0 ? cvals.data() : nullptr, co.gcstr = k > 0 ? cgrads.data() : nullptr;
+            EGX_RC(eval_guarded(h, pts.data(), (int64_t)m, vals.data(), grads.data(), nullptr, nullptr, &co));
+        }
+        rounds++;
+        for (size_t q = 0; q < m; q++)
+            mach[who[q]].tell(vals[q], cvals.data() + q * (size_t)k, grads.data() + q * d, cgrads.data() + q * (size_t)k * d);
+    }
+    // the best EVALUATED point, in egx_infill_optimize_cstr's ordering
+    auto better = [&](const Slsqp &a, const Slsqp &b) {  // a strictly better than b
+        if (a.best_feasible() != b.best_feasible()) return a.best_feasible();
+        return a.best_feasible() ? a.best_key() < b.best_key() : a.best_violation() < b.best_violation();
+    };
+    bool any_finite = false;
+    for (const Slsqp &c : mach) any_finite |= c.any_finite_f();
+    int64_t best = 0;  // nothing finite anywhere: start 0, whose only point is the start clamped into the box
+    for (int64_t s = 1; s < n_start && any_finite; s++)
+        if (better(mach[(size_t)s], mach[(size_t)best])) best = s;
+    const Slsqp &win = mach[(size_t)best];
+    *f_best = win.best_f();
+    std::copy(win.best_x().begin(), win.best_x().end(), x_best);
+    if (k > 0) std::copy(win.best_c().begin(), win.best_c().end(), c_best);
+    if (stats) {
+        stats->rounds = rounds;
+        stats->best_start = best;
+        stats->feasible = win.best_feasible() ? 1 : 0;
+        stats->violation = k > 0 ? win.best_violation() : 0.0;
+        for (int64_t s = 0; s < n_start; s++) {
+            if (stats->evals) stats->evals[s] = mach[(size_t)s].evals();
+            if (stats->stop) stats->stop[s] = (int32_t)mach[(size_t)s].status();
+        }
+    }
     if (!any_finite) {
         *f_best = std::numeric_limits<double>::infinity();
         set_error("infill optimize: no start met a finite objective value");

@@ -293,6 +293,32 @@ class InfillObjective:
                      violation=float(st.violation), finite=rc == L.SUCCESS)
         return xb, f.value, cb[:self.n_cstr].copy(), stats
 
+    def optimize_slsqp(self, xlimits, x_start, max_eval=None):
+        """The multistart with the reference's default inner optimiser, SLSQP (egx_infill_optimize_slsqp): one machine per row
+        of x_start inside xlimits (d, 2), all starts in lock-step, a round being one evaluation with gradients.  Works in every
+        strategy: under "infill" (or without constraint models) a bound-constrained run and c is empty; under "mean" / "utb"
+        subject to c_j <= cstr_tol_j / scale_cstr_j.  Returns (x, f, c, stats) as optimize_constrained, stats with `stop` beside:
+        per start 1 budget, 2 converged, 3 line search could not move, 4 no finite value at the start, 5 inconsistent."""
+        lim = L.as_f64(xlimits, 2)
+        if lim.shape != (self.d, 2):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
+        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+        xs = self._points(x_start)
+        n_start = xs.shape[0]
+        k = 0 if self.cstr_strategy()[0] == "infill" else self.n_cstr
+        f, xb, cb = C.c_double(), np.empty(self.d), np.empty(max(self.n_cstr, 1))
+        evals = np.zeros(n_start, dtype=np.int64)
+        stop = np.zeros(n_start, dtype=np.int32)
+        st = L.InfillSlsqpStats(0, 0, 0, 0.0, evals.ctypes.data_as(L.c_int64_p), stop.ctypes.data_as(L.c_int32_p))
+        rc = self._lib.egx_infill_optimize_slsqp(self._h, L.dptr(lo), L.dptr(hi), L.dptr(xs), n_start,
+                                                 0 if max_eval is None else int(max_eval), C.byref(f), L.dptr(xb), L.dptr(cb),
+                                                 C.byref(st))
+        if rc != L.ERR_NO_FINITE_START:
+            L.check(rc)
+        stats = dict(evals=evals, stop=stop, rounds=int(st.rounds), best_start=int(st.best_start), feasible=bool(st.feasible),
+                     violation=float(st.violation), finite=rc == L.SUCCESS)
+        return xb, f.value, cb[:k].copy(), stats
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.egx_infill_destroy(self._h)

@@ -789,6 +789,34 @@ typedef struct {
 int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo /*d*/, const double *hi /*d*/, const double *x_start /*n_start*d*/,
                                  int64_t n_start, int64_t max_eval, double *f_best, double *x_best /*d*/, double *c_best /*n_cstr*/,
                                  egx_infill_cstr_stats *stats);
+/* The same multistart with the reference's DEFAULT inner optimiser, InfillOptimizer::Slsqp (solver/egor_config.rs:246): one
+ * SLSQP per start (Kraft's algorithm, egobox_amd/csrc/slsqp.h; ftol_rel = ftol_abs = 1e-4, solver_infill_optim.rs:225-226, at
+ * most max_eval evaluations each; max_eval <= 0: min(10 n_start d, 2000)), all starts in LOCK-STEP: a round collects the point
+ * of every start that still runs -- a line-search trial point as much as an iterate -- and is ONE evaluation WITH gradients,
+ * egx_infill_eval (EGX_CSTR_INFILL, or n_cstr = 0) or egx_infill_eval_cstr (EGX_CSTR_MEAN / _UTB); no point is evaluated
+ * twice, and every start walks bit for bit the points it walks alone.  Works in all three strategies:
+ *   EGX_CSTR_INFILL, or n_cstr = 0   a bound-constrained run; c_best is untouched (may be NULL), feasible = 1, violation = 0;
+ *   EGX_CSTR_MEAN / _UTB             subject to c_j(x) - cstr_tol_j / scale_cstr_j <= 0 (optimizers/optimizer.rs:188-199).
+ * Returned: the best EVALUATED point in egx_infill_optimize_cstr's ordering (the same deviation from :229-232): feasible
+ * (c_j <= cstr_tol_j / scale_cstr_j for all j) beats infeasible, then the smaller objective, or the smaller violation; the
+ * first point and the first start win ties.  *f_best and c_best are bit for bit the evaluation at x_best.  On a handle with
+ * xtypes the trial points are cast on the device and the machine works in the unfolded box with the gradients at the cast
+ * point (gpmix/mixint.rs:656-687); x_best is the point as proposed.  A value that is NaN, or at or beyond 1e30, counts as
+ * +inf: at a trial point it shortens the step, at a start point it ends that start.  No finite objective at all:
+ * *f_best = +inf, x_best = start 0 clamped into the box, EGX_ERR_NO_FINITE_START.  The argument checks are
+ * egx_infill_optimize_cstr's.  stop[s]: why start s ended -- 1 the evaluation budget, 2 Kraft's convergence test, 3 the line
+ * search could not move (no descent direction after the resets of the Hessian, or only non-finite values), 4 no finite value
+ * at the start point, 5 the quadratic subproblem stayed inconsistent. */
+typedef struct {
+    int64_t rounds, best_start;
+    int32_t feasible;
+    double violation;
+    int64_t *evals; /* n_start counts of distinct points evaluated, or NULL */
+    int32_t *stop;  /* n_start stop codes, or NULL */
+} egx_infill_slsqp_stats;
+int32_t egx_infill_optimize_slsqp(egx_infill *h, const double *lo /*d*/, const double *hi /*d*/, const double *x_start /*n_start*d*/,
+                                  int64_t n_start, int64_t max_eval, double *f_best, double *x_best /*d*/,
+                                  double *c_best /*n_cstr, or NULL*/, egx_infill_slsqp_stats *stats);
 
 /* ---- ... on mixtures of experts -------------------------------------------------------------------------------------
  * What EGO holds for its objective and every constraint is a clustered surrogate (GpMixture, crates/moe/src/algorithm.rs):

@@ -820,6 +820,25 @@ class InfillObjective {
         o.feasible = st.feasible != 0, o.violation = st.violation;
         return o;
     }
+    // InfillOptimizer::Slsqp, the reference's default, as one call (egx_infill_optimize_slsqp); works in every strategy
+    struct SlsqpOptimum : ConstrainedOptimum {
+        std::vector<int32_t> stop;  // per start: 1 budget, 2 converged, 3 line search, 4 no finite start value, 5 inconsistent
+    };
+    SlsqpOptimum optimize_slsqp(const double *lo, const double *hi, const double *x_start, int64_t n_start, int64_t max_eval = 0) {
+        SlsqpOptimum o;
+        o.x.assign((size_t)d_, 0.0);
+        o.c.assign((size_t)k_ + 1, 0.0);
+        o.evals.assign((size_t)n_start, 0);
+        o.stop.assign((size_t)n_start, 0);
+        egx_infill_slsqp_stats st{0, 0, 0, 0.0, o.evals.data(), o.stop.data()};
+        const int32_t rc = egx_infill_optimize_slsqp(h_.get(), lo, hi, x_start, n_start, max_eval, &o.f, o.x.data(), o.c.data(), &st);
+        if (rc != EGX_ERR_NO_FINITE_START) check(rc);
+        o.c.resize(cstr_strategy().first == EGX_CSTR_INFILL ? 0 : (size_t)k_);  // folded constraints: none are returned
+        o.finite = rc == EGX_SUCCESS;
+        o.rounds = st.rounds, o.best_start = st.best_start;
+        o.feasible = st.feasible != 0, o.violation = st.violation;
+        return o;
+    }
     egx_infill *handle() const { return h_.get(); }
 
   private:

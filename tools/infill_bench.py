@@ -29,6 +29,16 @@ few-query route) with the same host arithmetic; fused = the handle of egx_infill
 the padded batch of 128 whatever m is.  Same protocol, written to profiles/infill_sparse_bench.txt; no threshold is set.
 
     python tools/infill_bench.py --sparse [--out profiles/infill_sparse_bench.txt] [--reps 15]
+
+--slsqp times the reference's DEFAULT inner optimiser, SLSQP under EGX_CSTR_MEAN, on one handle (a dense objective, n = 500,
+d = 8, two constraint models, WB2) from 20 starts, the reference's n_start: (a) egx_infill_optimize_slsqp, all starts in
+lock-step; (b) the only way to run that optimiser without the call -- scipy's SLSQP, one start after the other, on the
+m = 1 closure constraints(x, grad=True) (one library call per distinct point: value, gradient, constraints, Jacobian), which
+uses only entry points that exist without the feature and is the yardstick on any commit; (c) egx_infill_optimize_cstr (COBYLA) from the same starts.  Every leg gets ftol 1e-4 and
+at most 200 evaluations per start.  Legs alternated, medians with quartiles, the three optima, written to
+profiles/infill_slsqp_bench.txt; no threshold is set.
+
+    python tools/infill_bench.py --slsqp [--out profiles/infill_slsqp_bench.txt] [--reps 7]
 """
 import argparse
 import os
@@ -113,17 +123,103 @@ def median_ms(fn, reps, warm=3):
     return float(np.median(t))
 
 
+def quartiles_ms(fn, reps, warm=1):
+    """(q25, median, q75) of the wall time in ms, and the last result"""
+    out = None
+    for _ in range(warm):
+        out = fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return tuple(float(v) for v in np.percentile(t, [25, 50, 75])), out
+
+
+def run_slsqp(args, emit):
+    n, d, k, n_start, budget = 500, 8, 2, 20, 200
+    hs, ys = [], []
+    for j in range(1 + k):  # constraint 2 cuts the centre of the box out: active at the optimum
+        x, y = workload.make_training_set(n, d, seed=100 + j)
+        y = 1e-3 * y if j == 0 else (y - np.quantile(y, 0.6) if j == 1 else np.quantile(y, 0.25) - y)
+        h = egx.GpHandle(x, y)
+        h.finalize(np.full(d, 1.5))
+        hs.append(h), ys.append(y)
+    tols = [1e-3, 1e-3]
+    obj = egx.InfillObjective(hs[0], hs[1:], tols, criterion=egx.WB2, fmin=float(np.quantile(ys[0], 0.05)))
+    rng = np.random.default_rng(1)
+    lim = np.array([[0.0, 1.0]] * d)
+    starts = rng.random((n_start, d))
+    obj.set_cstr_strategy("mean")
+    obj.scaling(rng.random((200, d)))
+    cfeas = np.array(tols) / obj.cstr_strategy()[1]
+    has = hasattr(obj, "optimize_slsqp")
+
+    def leg_lib():
+        return obj.optimize_slsqp(lim, starts, max_eval=budget)
+
+    def leg_scipy():
+        from scipy.optimize import minimize
+        res, calls = [], []
+        for x0 in starts:
+            memo = {}
+
+            def at(x):  # ONE m = 1 library call per distinct point: value, gradient, constraints and their Jacobian
+                key = x.tobytes()
+                if key not in memo:
+                    v, c, g, gc = obj.constraints(x[None], grad=True)
+                    memo[key] = (v[0], g[0], c[0], gc[0])
+                return memo[key]
+            cons = [{"type": "ineq", "fun": lambda x: cfeas - at(x)[2], "jac": lambda x: -at(x)[3]}]
+            r = minimize(lambda x: at(x)[:2], x0, jac=True, method="SLSQP", bounds=[tuple(b) for b in lim], constraints=cons,
+                         options={"ftol": 1e-4, "maxiter": budget})
+            v, _, c, _ = at(r.x)
+            res.append((not np.max(c - cfeas) > 0.0, v, r.x, c))
+            calls.append(len(memo))
+        feas = [r for r in res if r[0]]
+        best = min(feas or res, key=lambda r: r[1] if feas else np.max(r[3] - cfeas))
+        return best[2], best[1], best[3], dict(evals=np.array(calls), feasible=best[0], violation=float(np.max(best[3] - cfeas)))
+
+    def leg_cobyla():
+        return obj.optimize_constrained(lim, starts, max_eval=budget)
+
+    emit("# SLSQP multistart under EGX_CSTR_MEAN: n %d d %d n_cstr %d n_start %d WB2, ftol 1e-4, at most %d evaluations per start;"
+         % (n, d, k, n_start, budget))
+    emit("# (a) egx_infill_optimize_slsqp, (b) scipy SLSQP start after start on the m = 1 closures, (c) egx_infill_optimize_cstr")
+    emit("# (COBYLA); wall ms as q25 median q75 over %d runs after 1 warm-up, legs alternated (b, a, c, b again)" % args.reps)
+    try:
+        import scipy
+        sp = tuple(int(v) for v in scipy.__version__.split(".")[:2]) < (1, 16)
+    except ImportError:
+        sp = False
+    legs = [("b", leg_scipy, sp), ("a", leg_lib, has), ("c", leg_cobyla, True), ("b2", leg_scipy, sp)]
+    emit("# leg q25_ms median_ms q75_ms rounds evals_per_start(min median max) f_best feasible violation")
+    for name, fn, on in legs:
+        if not on:
+            emit(f"{name} not available here")
+            continue
+        (q1, q2, q3), (xb, fb, cb, st) = quartiles_ms(fn, args.reps)
+        ev = st["evals"]
+        emit(f"{name} {q1:.1f} {q2:.1f} {q3:.1f} {st.get('rounds', int(ev.sum()))} {ev.min()} {int(np.median(ev))} {ev.max()} {fb:.9g} "
+             f"{int(st['feasible'])} {st['violation']:.3e}")
+    emit("# rounds of leg b: its evaluation calls, every one a launch sequence of its own for one point")
+    obj.close()
+    for h in hs:
+        h.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--mix", action="store_true", help="the mixture leg (k = 3 experts, smooth) instead of the single-model legs")
     ap.add_argument("--cstr", action="store_true", help="one lock-step round in MEAN, UTB and INFILL mode on one handle")
     ap.add_argument("--sparse", action="store_true", help="the sparse leg: one sparse objective (nz = 512, d = 8), value + gradient")
+    ap.add_argument("--slsqp", action="store_true", help="20 starts of SLSQP: the lock-step call, scipy on the m = 1 closures, COBYLA")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
+        args.out = os.path.join(ROOT, "profiles", "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
                                 else "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
@@ -140,6 +236,11 @@ def main():
         for _ in range(10):
             obj.value(xq)
             obj.value_and_grad(xq)
+        return
+    if args.slsqp:
+        run_slsqp(args, emit)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
         return
     if args.cstr:
         m = 20
