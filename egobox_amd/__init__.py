@@ -21,7 +21,7 @@ from .sgp import (Inducings, ParamTuning, SgpHandle, SgpParams, SparseGaussianPr
 from . import cv, infill, moe, workload  # noqa: E402
 from .cv import GpMetrics, IaeAlphaPlotData, cross_validate, fold_indices  # noqa: E402
 from .moe import GaussianMixture, GpMixture, GpMixtureParams  # noqa: E402
-from .infill import EI, LOG_EI, WB2, WB2S, InfillObjective  # noqa: E402
+from .infill import EI, LOG_EI, WB2, WB2S, InfillObjective, QEiStrategy  # noqa: E402
 from . import mixint  # noqa: E402
 from .mixint import (MixintContext, MixintGpMixture, MixintGpMixtureParams, XType, as_continuous_limits,  # noqa: E402
                      cast_to_discrete_values, fold_with_enum_index, to_continuous_space, to_discrete_space, unfold_with_enum_mask)

@@ -98,6 +98,12 @@ class InfillSlsqpStats(C.Structure):
                 ("evals", c_int64_p), ("stop", c_int32_p)]
 
 
+class InfillBatchConfig(C.Structure):
+    """egx_infill_batch_config"""
+    _fields_ = [("strategy", C.c_int32), ("optimizer", C.c_int32), ("max_eval", C.c_int64), ("scaling_points", c_double_p),
+                ("n_scaling", C.c_int64)]
+
+
 class XTypeC(C.Structure):
     """egx_xtype"""
     _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("values", c_double_p)]
@@ -257,6 +263,13 @@ SIGNATURES = [
     ("egx_moe_predict_valvar_gradients_sgp", C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p, C.c_int64, C.c_int64,
                                                          c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int32,
                                                          c_double_p, c_double_p]),
+    ("egx_infill_push_pending", C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
+    ("egx_infill_clear_pending", C.c_int32, [C.c_void_p]),
+    ("egx_infill_get_pending", C.c_int32, [C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
+    ("egx_infill_virtual_point", C.c_int32, [C.c_void_p, c_double_p, C.c_int32, c_double_p]),
+    ("egx_infill_batch_config_default", None, [C.POINTER(InfillBatchConfig)]),
+    ("egx_infill_optimize_batch", C.c_int32, [C.c_void_p, C.POINTER(InfillBatchConfig), c_double_p, c_double_p, c_double_p,
+                                              C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p, c_int32_p]),
 ]
 
 

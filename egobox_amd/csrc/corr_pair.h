@@ -127,4 +127,21 @@ __device__ __forceinline__ double dlog_dc(double c, double a) {
     return -k5over3 * (a * t) * u * rcp_ge1(__builtin_fma(k5over3 * t, t, u));
 }
 
+// d r / d x_k = r * xgrad_factor(x_ak - x_jk) (the closed forms above k_xgrad, kernels_corr.hip); shared with kernels_pending.hip
+template <int CORR>
+__device__ __forceinline__ double xgrad_factor(double diff, const double *__restrict__ c, int hcols) {
+    if (CORR == EGX_CORR_SQUARED_EXPONENTIAL) return -(c[0] * c[0]) * diff;
+    if (CORR == EGX_CORR_ABSOLUTE_EXPONENTIAL) return -copysign(c[0], diff);
+    const double ad = fabs(diff);
+    double sacc = 0.0;
+    for (int l = 0; l < hcols; l++) {
+        const double t = c[l] * ad;
+        if (CORR == EGX_CORR_MATERN32)
+            sacc += c[l] * (kSqrt3 / __builtin_fma(kSqrt3, t, 1.0) - kSqrt3);
+        else
+            sacc += c[l] * ((kSqrt5 + 2.0 * k5over3 * t) / (1.0 + kSqrt5 * t + k5over3 * (t * t)) - kSqrt5);
+    }
+    return copysign(1.0, diff) * sacc;
+}
+
 }  // namespace egx

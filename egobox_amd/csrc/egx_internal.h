@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
 
 #include "../../include/egx_gp.h"
@@ -266,6 +267,37 @@ int launch_infill_cstr(hipStream_t s, const infill::Params &prm, int strategy, i
 // objective of prm without the feasibility factor) and fac (pofs, or logpofs for LogEI); base == nullptr skips both
 int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, int64_t m, int64_t mstride, const double *mean,
                               const double *var, const double *tol, const int *flag, double *ei, double *base, double *fac);
+
+// ---- kernels_pending.hip ----------------------------------------------------
+// A model conditioned on the q <= 16 pending points of its infill handle (pending_math.h), per tile of kTile queries.
+constexpr int kPendingQV = 4;     // columns of W^ per pass of the contraction
+constexpr int kPendingMaxD = 64;  // the lane's query coordinates and the finish's d c / d x live in LDS
+int pending_splits(int nz);       // splits of the nz = n + q points of Z for one tile: a function of nz alone
+// c[a, v] = sum_j r(x_a, Z_j) W^[j, v] and (outg != nullptr) its gradient in the tile's normalised coordinates, as partial sums
+// per split: outc (nsplit x kTile x q), outg (nsplit x kTile x q x d).  ZT: d x ldz k-major, nz points; W: nz x 16 row-major
+int launch_pending_cross(hipStream_t s, int corr, const double *xqT, const double *ZT, int64_t ldz, int nz, int d, const double *coef,
+                         int hcols, const double *W, int q, int nsplit, double *outc, double *outg);
+struct PendingFinish {
+    int q = 0, d = 0, p = 0;
+    int nsplit_c = 0, nsplit_g = 0;  // splits of the partial sums of c and of d c / d x
+    bool composed = false;           // the layouts of the composed form: per column launch_predict_mean's and launch_xgrad's
+    const double *xqT = nullptr;    // d x kTile
+    const int *fidx = nullptr;      // 2 p
+    const double *tv = nullptr;     // 16 x p: t_v = D_v
+    const double *small = nullptr;  // chol(S) (16 x 16, lower) | alpha (16)
+    const double *outc = nullptr, *outg = nullptr;
+    const double *x_std = nullptr;  // d
+    double sigma2 = 0.0, sigma2c = 0.0, y_std = 1.0;  // the fitted and the conditioned process variance (raw units)
+    double *mean = nullptr, *var = nullptr, *gmean = nullptr, *gvar = nullptr;  // rewritten in place; var / gvar nullptr: mean only
+    double *emit = nullptr;         // kTile x 16: the cross-covariances themselves and nothing rewritten
+};
+int launch_pending_finish(hipStream_t s, const PendingFinish &f);
+// a push: column v of W^, t_v and the point's coordinates in Z from query 0 of the tile sequence that just ran
+int launch_pending_capture(hipStream_t s, const double *Wt, const double *dneg, const double *xqT, int n, int d, int p, int v,
+                           double *W, double *Wc, double *tv, double *ZT, int64_t ldz);
+// egx_set_tuning "pending_composed": 1 = the composed form (q launches of launch_predict_mean / launch_xgrad over Z with a
+// column of W^ as the weight vector) even where the fused contraction applies (d <= kPendingMaxD); 0 (default): fused there
+extern std::atomic<int> g_pending_composed;
 
 // ---- kernels_gmm.hip --------------------------------------------------------
 // EM of a Gaussian mixture for R restarts in lock-step over one (n x D) data set (egx_gmm_fit).  DP = D rounded up to a

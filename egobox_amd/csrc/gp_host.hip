@@ -1066,6 +1066,7 @@ int32_t egx_set_tuning(const char *knob, int32_t value, int32_t *previous) {
     int old = set_knob(knob, value);
     if (old == -2147483647 - 1) old = pipe_set_knob(knob, value);  // the chain kernel's knobs (kernels_pipe.hip)
     if (old == -2147483647 - 1 && std::string(knob) == "pipe_retry") old = g_pipe_retry.exchange(value);
+    if (old == -2147483647 - 1 && std::string(knob) == "pending_composed") old = g_pending_composed.exchange(value != 0 ? 1 : 0);
     if (old == -2147483647 - 1) {
         set_error(std::string("egx_set_tuning: unknown knob '") + knob + "'");
         return EGX_ERR_INVALID_VALUE;

@@ -33,11 +33,22 @@
 // weights, no second contraction; the means keep the bits of the full sequence, which forms r . gamma before its solve as
 // well.  A call that does not ask for anything of the constraint surrogates (egx_infill_eval without parts under MEAN / UTB)
 // does not run them at all.
+//
+// PENDING POINTS (egx_infill_push_pending; the q_points loop of solver_impl.rs:622-791).  The handle keeps up to 16 virtual
+// observations and conditions every (lone, dense) surrogate on them in closed form (pending_math.h) instead of refitting it:
+// right after expert_tile / expert_tile_mean, while h->xqT still holds the model's normalised tile, k_pending_cross contracts
+// the tile against the model's training points followed by the pending ones with the extended weight matrix W^ = [W_v ; I_q]
+// and k_pending_finish rewrites the tile's mean / var / gmean / gvar in place (kernels_pending.hip) -- nothing downstream
+// changes.  A push runs the new point's own sequence once (a tile holding one point) WITHOUT the conditioning, keeps the
+// weight column posterior_weights / posterior_weights_trend made for it and its -dneg as column q of W^ / t_q, takes its
+// covariances with the points already pending from the same two kernels, and borders chol(S), alpha and sigma2' on the host.
+// With q = 0 none of this runs: the launch sequence is the one above, bit for bit.
 #include <map>
 
 #include "gmx_point.h"
 #include "sgp_handle.h"
 #include "infill_math.h"
+#include "pending_math.h"
 #include "slsqp.h"
 
 using namespace egx;
@@ -68,7 +79,31 @@ struct Surrogate {
     bool on_device = false;
 };
 
+// A lone dense surrogate conditioned on the handle's q pending points (pending_math.h): the points after the model's training
+// points in ITS normalisation, the extended weight matrix W^ = [W_v ; I_q], the trend columns t_v, chol(S) and alpha (host
+// and device), the conditioned process variance.  Valid for ONE fitted state of the model (epoch).
+struct PendModel {
+    DevBuf ZT, W, tv, small;  // d x ldz | (n + 16) x 16 | 16 x p | L (16 x 16) and alpha (16)
+    DevBuf Wc;                // W^ column-major (16 x ldz): the weight vectors of the composed form
+    int64_t ldz = 0;
+    int n = -1;
+    uint64_t epoch = 0;
+    double sigma2c = 0.0;
+    std::vector<double> L = std::vector<double>((size_t)pending::kLd * pending::kLd, 0.0);
+    std::vector<double> alpha = std::vector<double>(pending::kMaxPending, 0.0), delta = alpha;
+};
+
+// a push: the new point runs the models' own sequences WITHOUT the conditioning; its cross-covariances with the points already
+// pending come back in emit (surrogate-major, kTile x 16 each; the point is row 0), its weights are captured as column q
+struct PushCapture {
+    DevBuf emit;
+};
+
 }  // namespace
+
+namespace egx {
+std::atomic<int> g_pending_composed{0};
+}
 
 struct egx_infill {
     std::mutex mu;
@@ -95,6 +130,12 @@ struct egx_infill {
     std::vector<double> scale_cstr;  // one per constraint, ones until set
     DevBuf d_scale, cstr, gcstr;
     bool scale_on_device = false;
+    // the pending points of a q-point batch (egx_infill_push_pending): q of them, as stored (cast raw x, q x d; raw y, q x n_surr),
+    // every surrogate's conditioning state, the partial sums of one (tile, model) step of k_pending_cross
+    int q = 0;
+    std::vector<double> pend_x, pend_y;
+    std::vector<PendModel> pend;
+    DevBuf pc_c, pc_g;
 };
 
 namespace {
@@ -286,6 +327,67 @@ int sgp_expert_tile_mean(egx_infill *h, hipStream_t st, int j, int64_t t0, int m
     return launch_infill_sgp_xgrad_finish(st, h->out_y.p, nullptr, nsplit, d, nullptr, nullptr, g->sigma2, 0, 0.0, gmean, nullptr);
 }
 
+// the fused contraction where it applies, unless the composed form is asked for (egx_set_tuning "pending_composed")
+bool pending_composed(int d) { return d > kPendingMaxD || g_pending_composed.load() != 0; }
+
+// Right after expert_tile / expert_tile_mean of the lone dense surrogate js, while h->xqT holds its normalised tile: the tile's
+// entries of the tables conditioned IN PLACE on the pending points (var / gvar nullptr: the mean shift alone).  A push (cap)
+// rewrites nothing: it takes the tile's cross-covariances with the points already pending, then captures query 0's weights.
+int pending_tile(egx_infill *h, hipStream_t st, int js, bool want_g, double *mean, double *var, double *gmean, double *gvar,
+                 PushCapture *cap) {
+    const int d = h->d;
+    PendModel &pm = h->pend[js];
+    const egx_gp *gp = h->models[h->surr[js].first].gp;
+    if (h->q > 0) {
+        const int nz = gp->n + h->q;
+        const bool g = want_g && !cap;
+        PendingFinish f;
+        f.composed = pending_composed(d);
+        if (!f.composed) {
+            f.nsplit_c = f.nsplit_g = pending_splits(nz);
+            EGX_RC(launch_pending_cross(st, gp->corr, h->xqT.p, pm.ZT.p, pm.ldz, nz, d, gp->d_fit_coef, gp->fit_hcols, pm.W.p, h->q,
+                                        f.nsplit_c, h->pc_c.p, g ? h->pc_g.p : nullptr));
+        } else {  // what one writes without the kernel: per column the existing contractions over Z with w_v as the weight vector
+            f.nsplit_c = mean_splits((int)pm.ldz, kTile), f.nsplit_g = xgrad_splits(nz, kTile);
+            for (int v = 0; v < h->q; v++) {
+                const double *wv = pm.Wc.p + (size_t)v * pm.ldz;
+                EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, pm.ZT.p, pm.ldz, (int)pm.ldz, d, gp->d_fit_coef,
+                                           gp->fit_hcols, wv, h->pc_c.p + (size_t)v * f.nsplit_c * kTile, f.nsplit_c));
+                if (g)
+                    EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, pm.ZT.p, pm.ldz, nz, d, gp->d_fit_coef, gp->fit_hcols, wv,
+                                        0, 1, f.nsplit_g, h->pc_g.p + (size_t)v * f.nsplit_g * kTile * d));
+            }
+        }
+        f.q = h->q, f.d = d, f.p = gp->p;
+        f.xqT = h->xqT.p, f.fidx = gp->d_fidx, f.tv = pm.tv.p, f.small = pm.small.p, f.outc = h->pc_c.p, f.outg = g ? h->pc_g.p : nullptr;
+        f.x_std = dev_xnorm(gp) + d;
+        f.sigma2 = gp->sigma2, f.sigma2c = pm.sigma2c, f.y_std = gp->y_std;
+        if (cap) {
+            f.emit = cap->emit.p + (size_t)js * kTile * pending::kLd;
+        } else {
+            f.mean = mean, f.var = var, f.gmean = g ? gmean : nullptr, f.gvar = g ? gvar : nullptr;
+        }
+        EGX_RC(launch_pending_finish(st, f));
+    }
+    if (cap)
+        EGX_RC(launch_pending_capture(st, h->Wt.p, h->dneg.p, h->xqT.p, gp->n, d, gp->p, h->q, pm.W.p, pm.Wc.p, pm.tv.p, pm.ZT.p,
+                                      pm.ldz));
+    return EGX_SUCCESS;
+}
+
+// pending points belong to one fitted state of every model
+int check_pending(const egx_infill *h) {
+    for (size_t js = 0; js < h->pend.size() && h->q > 0; js++) {
+        const egx_gp *gp = h->models[h->surr[js].first].gp;
+        if (gp->fit_epoch != h->pend[js].epoch || gp->n != h->pend[js].n) {
+            set_error("infill: " + who(h, h->surr[js].first) + " was refitted since its pending points were pushed (call "
+                      "egx_infill_clear_pending)");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    }
+    return EGX_SUCCESS;
+}
+
 // what egx_infill_eval_cstr asks for beside value / grad (host pointers, any nullptr)
 struct CstrOut {
     double *cstr = nullptr, *gcstr = nullptr;
@@ -293,7 +395,7 @@ struct CstrOut {
 
 // The evaluation proper; the handle's and the models' locks are held.  value / grad / every member of parts may be nullptr.
 int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
-                const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr) {
+                const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr, PushCapture *cap = nullptr) {
     if (m < 0 || (m > 0 && !xq)) {
         set_error("bad query array");
         return EGX_ERR_INVALID_VALUE;
@@ -301,7 +403,9 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
     const int ne = (int)h->models.size(), nm = (int)h->surr.size(), k = nm - 1, d = h->d;
     EGX_RC(check_fitted(h));
     EGX_RC(check_specs(h));
+    EGX_RC(check_pending(h));
     if (m == 0) return EGX_SUCCESS;
+    const bool pending = h->q > 0 || cap;  // (q = 0 and no push: nothing below differs from a handle without pending points)
     const bool want_g = grad || (parts && (parts->grad_mean || parts->grad_var)) ||
                         (diag && (diag->gmean || diag->gvar || diag->dprobas)) || (co && co->gcstr);
     // the constraint surrogates: folded into the objective (all of them, the full sequence), or run only when something of
@@ -406,6 +510,15 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
         if (co->cstr) EGX_RC(h->cstr.alloc((size_t)M * k));
         if (co->gcstr) EGX_RC(h->gcstr.alloc((size_t)M * k * d));
     }
+    if (pending && h->q > 0) {
+        int ns_p = 1;  // the larger of the fused form's splits and the composed form's (per column: mean_splits, xgrad_splits)
+        for (int js = 0; js < nm; js++) {
+            const int nz = h->models[h->surr[js].first].gp->n + h->q;
+            ns_p = std::max(ns_p, std::max(pending_splits(nz), std::max(mean_splits((int)h->pend[js].ldz, kTile), xgrad_splits(nz, kTile))));
+        }
+        EGX_RC(h->pc_c.alloc((size_t)ns_p * kTile * pending::kLd));
+        if (want_g && !cap) EGX_RC(h->pc_g.alloc((size_t)ns_p * kTile * pending::kLd * d));
+    }
     if (diag_mix) {
         EGX_RC(h->dg_probas.alloc((size_t)M * dsg->k));
         if (diag->dprobas) EGX_RC(h->dg_dprobas.alloc((size_t)M * dsg->k * d));
@@ -425,12 +538,18 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
                     EGX_RC((sparse ? sgp_expert_tile_mean : expert_tile_mean)(
                         h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row,
                         want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr, nullptr));
+                    if (pending)
+                        EGX_RC(pending_tile(h, st, js, want_g, h->mean.p + row, nullptr, want_g ? h->gmean.p + row * d : nullptr, nullptr,
+                                            cap));
                     continue;
                 }
                 EGX_RC((sparse ? sgp_expert_tile : expert_tile)(
                     h, st, sg.first + e, t0, mt, want_g, (lone ? h->mean.p : h->emean.p) + row, (lone ? h->var.p : h->evar.p) + row,
                     want_g ? (lone ? h->gmean.p : h->egmean.p) + row * d : nullptr,
                     want_g ? (lone ? h->gvar.p : h->egvar.p) + row * d : nullptr, sg.first + e == 0 ? flag + t0 : nullptr));
+                if (pending)
+                    EGX_RC(pending_tile(h, st, js, want_g, h->mean.p + row, h->var.p + row, want_g ? h->gmean.p + row * d : nullptr,
+                                        want_g ? h->gvar.p + row * d : nullptr, cap));
             }
             if (lone) continue;
             InfillMix mx;
@@ -512,8 +631,8 @@ int eval_locked(egx_infill *h, const double *xq, int64_t m, double *value, doubl
 }
 
 int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
-                 const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr) {
-    const int rc = eval_locked(h, xq, m, value, grad, parts, diag, co);
+                 const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr, PushCapture *cap = nullptr) {
+    const int rc = eval_locked(h, xq, m, value, grad, parts, diag, co, cap);
     if (rc) {  // nothing may still run on the handle's buffers
         (void)hipStreamSynchronize(h->models[0].stream());
         (void)hipGetLastError();
@@ -1193,6 +1312,270 @@ int32_t egx_infill_optimize(egx_infill *h, const double *lo, const double *hi, c
     if (!std::isfinite(fb[best])) {
         set_error("infill optimize: no start ended at a finite value");
         return EGX_ERR_NO_FINITE_START;
+    }
+    return EGX_SUCCESS;
+}
+
+}  // extern "C"
+
+namespace {
+
+// every surrogate a lone dense model, d within the contraction's reach
+int pending_supported(const egx_infill *h) {
+    for (size_t js = 0; js < h->surr.size(); js++) {
+        const Surrogate &sg = h->surr[js];
+        if (sg.k >= 2 || h->models[sg.first].sparse()) {
+            set_error("infill: pending points are not supported on surrogate " + std::to_string(js) +
+                      (sg.k >= 2 ? " (a mixture of " + std::to_string(sg.k) + " experts)" : " (a sparse model)"));
+            return EGX_ERR_UNSUPPORTED;
+        }
+    }
+    if (h->d > 1024) {  // (the finish keeps 16 d doubles of one point in LDS)
+        set_error("infill: pending points need d <= 1024 (d " + std::to_string(h->d) + ")");
+        return EGX_ERR_UNSUPPORTED;
+    }
+    return EGX_SUCCESS;
+}
+
+// the first push of a batch: Z <- the model's normalised training points, W^ and t_v zeroed, for the model's current fitted state
+int pending_begin(egx_infill *h, hipStream_t st) {
+    const int d = h->d;
+    h->pend.resize(h->surr.size());
+    for (size_t js = 0; js < h->surr.size(); js++) {
+        PendModel &pm = h->pend[js];
+        const egx_gp *gp = h->models[h->surr[js].first].gp;
+        pm.ldz = round_up((int64_t)gp->n + pending::kMaxPending, 64);
+        EGX_RC(pm.ZT.alloc((size_t)d * pm.ldz));
+        EGX_RC(pm.W.alloc((size_t)(gp->n + pending::kMaxPending) * pending::kLd));
+        EGX_RC(pm.Wc.alloc((size_t)pending::kMaxPending * pm.ldz));
+        EGX_HIP_CHECK(hipMemsetAsync(pm.Wc.p, 0, sizeof(double) * (size_t)pending::kMaxPending * pm.ldz, st));
+        EGX_RC(pm.tv.alloc((size_t)pending::kMaxPending * gp->p));
+        EGX_RC(pm.small.alloc((size_t)pending::kLd * pending::kLd + pending::kMaxPending));
+        EGX_HIP_CHECK(hipMemsetAsync(pm.ZT.p, 0, sizeof(double) * (size_t)d * pm.ldz, st));
+        EGX_HIP_CHECK(hipMemsetAsync(pm.W.p, 0, sizeof(double) * (size_t)(gp->n + pending::kMaxPending) * pending::kLd, st));
+        EGX_HIP_CHECK(hipMemsetAsync(pm.tv.p, 0, sizeof(double) * (size_t)pending::kMaxPending * gp->p, st));
+        EGX_HIP_CHECK(hipMemcpy2DAsync(pm.ZT.p, sizeof(double) * pm.ldz, gp->d_xT, sizeof(double) * gp->n_pad, sizeof(double) * gp->n,
+                                       d, hipMemcpyDeviceToDevice, st));
+        pm.n = gp->n, pm.epoch = gp->fit_epoch, pm.sigma2c = gp->sigma2;
+        std::fill(pm.L.begin(), pm.L.end(), 0.0);
+        std::fill(pm.alpha.begin(), pm.alpha.end(), 0.0);
+        std::fill(pm.delta.begin(), pm.delta.end(), 0.0);
+    }
+    return EGX_SUCCESS;
+}
+
+// the handle's and the models' locks are held
+int push_locked(egx_infill *h, const double *x, const double *y) {
+    const int nm = (int)h->surr.size(), d = h->d, q = h->q;
+    EGX_RC(check_fitted(h));
+    EGX_RC(pending_supported(h));
+    EGX_RC(check_specs(h));
+    EGX_RC(check_pending(h));
+    if (q >= pending::kMaxPending) {
+        set_error("infill: at most " + std::to_string(pending::kMaxPending) + " pending points");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    for (int i = 0; i < d; i++)
+        if (!std::isfinite(x[i])) {
+            set_error("infill: pending point has a non-finite coordinate " + std::to_string(i));
+            return EGX_ERR_INVALID_VALUE;
+        }
+    for (int j = 0; j < nm; j++)
+        if (!std::isfinite(y[j])) {
+            set_error("infill: pending point has a non-finite value for surrogate " + std::to_string(j));
+            return EGX_ERR_INVALID_VALUE;
+        }
+    EGX_HIP_CHECK(hipSetDevice(h->device));
+    hipStream_t st = h->models[0].stream();
+    std::vector<double> xc((size_t)d);
+    for (int i = 0; i < d; i++) xc[i] = query_coord(h->models[0].gp, x, i);
+    if (q == 0) {
+        const int rc = pending_begin(h, st);
+        if (rc) {
+            (void)hipStreamSynchronize(st);
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    // the point's own sequence on every model, unconditioned and with gradients (the weights), and its covariances with the
+    // points already pending
+    PushCapture cap;
+    EGX_RC(cap.emit.alloc((size_t)nm * kTile * pending::kLd));
+    std::vector<double> mean((size_t)nm), var((size_t)nm), gm((size_t)nm * d), gv((size_t)nm * d);
+    egx_infill_parts parts{mean.data(), var.data(), gm.data(), gv.data()};
+    EGX_RC(eval_guarded(h, xc.data(), 1, nullptr, nullptr, &parts, nullptr, nullptr, &cap));
+    std::vector<double> c((size_t)nm * pending::kLd, 0.0);
+    if (q > 0)
+        EGX_HIP_CHECK(hipMemcpy2D(c.data(), sizeof(double) * pending::kLd, cap.emit.p, sizeof(double) * kTile * pending::kLd,
+                                  sizeof(double) * pending::kLd, nm, hipMemcpyDeviceToHost));
+    // border chol(S), alpha and sigma2' of every model on copies: nothing is kept unless every pivot holds
+    std::vector<std::vector<double>> Ln((size_t)nm), an((size_t)nm), dn((size_t)nm);
+    std::vector<double> s2((size_t)nm);
+    for (int js = 0; js < nm; js++) {
+        PendModel &pm = h->pend[js];
+        const egx_gp *gp = h->models[h->surr[js].first].gp;
+        Ln[js] = pm.L, dn[js] = pm.delta, an[js].assign(pending::kMaxPending, 0.0);
+        const double unit = gp->sigma2 > 0.0 ? var[js] / gp->sigma2 : 0.0;  // k(x_v, x_v) = s^2(x_v)
+        if (!pending::chol_border(Ln[js].data(), q, c.data() + (size_t)js * pending::kLd, unit + gp->nugget)) {
+            set_error("infill: pending point " + std::to_string(q) + ": the covariance of the pending points is not positive "
+                      "definite for surrogate " + std::to_string(js) + " (a point pushed twice, or on a training point)");
+            return EGX_ERR_LINALG;
+        }
+        dn[js][q] = (y[js] - mean[js]) / gp->y_std;
+        const double quad = pending::solve_alpha(Ln[js].data(), q + 1, dn[js].data(), an[js].data());
+        s2[js] = pending::sigma2_conditioned(gp->sigma2, gp->y_std, gp->n, q + 1, quad);
+    }
+    std::vector<double> up((size_t)pending::kLd * pending::kLd + pending::kMaxPending);
+    for (int js = 0; js < nm; js++) {
+        std::copy(Ln[js].begin(), Ln[js].end(), up.begin());
+        std::copy(an[js].begin(), an[js].end(), up.begin() + (size_t)pending::kLd * pending::kLd);
+        EGX_HIP_CHECK(hipMemcpy(h->pend[js].small.p, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice));
+    }
+    for (int js = 0; js < nm; js++) {
+        PendModel &pm = h->pend[js];
+        pm.L = Ln[js], pm.alpha = an[js], pm.delta = dn[js], pm.sigma2c = s2[js];
+    }
+    h->pend_x.insert(h->pend_x.end(), xc.begin(), xc.end());
+    h->pend_y.insert(h->pend_y.end(), y, y + nm);
+    h->q = q + 1;
+    return EGX_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t egx_infill_push_pending(egx_infill *h, const double *x, const double *y) {
+    if (!h || !x || !y) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    return push_locked(h, x, y);
+}
+
+int32_t egx_infill_clear_pending(egx_infill *h) {
+    if (!h) {
+        set_error("NULL handle");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->q = 0;
+    h->pend_x.clear();
+    h->pend_y.clear();
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_get_pending(egx_infill *h, int32_t *q, double *x, double *y, double *sigma2) {
+    if (!h || !q) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    *q = h->q;
+    if (x) std::copy(h->pend_x.begin(), h->pend_x.end(), x);
+    if (y) std::copy(h->pend_y.begin(), h->pend_y.end(), y);
+    if (sigma2)
+        for (size_t js = 0; js < h->surr.size(); js++) {
+            const Surrogate &sg = h->surr[js];
+            if (h->q > 0) sigma2[js] = h->pend[js].sigma2c;
+            else if (sg.k < 2) sigma2[js] = h->models[sg.first].sparse() ? h->models[sg.first].sg->sigma2 : h->models[sg.first].gp->sigma2;
+            else sigma2[js] = std::numeric_limits<double>::quiet_NaN();  // a mixture has no single process variance
+        }
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_virtual_point(egx_infill *h, const double *x, int32_t strategy, double *y) {
+    if (!h || !y || (strategy != EGX_QEI_CL_MIN && !x)) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (strategy < EGX_QEI_KB || strategy > EGX_QEI_CL_MIN) {
+        set_error("infill: unknown q-EI strategy");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);
+    const int nm = (int)h->surr.size();
+    if (strategy == EGX_QEI_CL_MIN) {  // y_data[[index_min, ic]] (solver_computations.rs:269-275)
+        for (int js = 0; js < nm; js++) {
+            const Surrogate &sg = h->surr[js];
+            if (sg.k >= 2 || h->models[sg.first].sparse()) {
+                set_error("infill: the constant-liar minimum needs lone dense models (surrogate " + std::to_string(js) + ")");
+                return EGX_ERR_UNSUPPORTED;
+            }
+            if (h->models[sg.first].gp->n != h->models[0].gp->n) {
+                set_error("infill: the constant-liar minimum needs every model on the same rows (surrogate " + std::to_string(js) +
+                          " has " + std::to_string(h->models[sg.first].gp->n) + ", the objective " +
+                          std::to_string(h->models[0].gp->n) + ")");
+                return EGX_ERR_INVALID_VALUE;
+            }
+        }
+        const std::vector<double> &y0 = h->models[0].gp->y_raw;
+        size_t imin = 0;
+        for (size_t i = 1; i < y0.size(); i++)
+            if (y0[i] < y0[imin]) imin = i;
+        for (int js = 0; js < nm; js++) y[js] = h->models[h->surr[js].first].gp->y_raw[imin];
+        return EGX_SUCCESS;
+    }
+    for (int i = 0; i < h->d; i++)
+        if (!std::isfinite(x[i])) {
+            set_error("infill: virtual point at a non-finite coordinate " + std::to_string(i));
+            return EGX_ERR_INVALID_VALUE;
+        }
+    std::vector<double> mean((size_t)nm), var((size_t)nm);
+    egx_infill_parts parts{mean.data(), var.data(), nullptr, nullptr};
+    EGX_RC(eval_guarded(h, x, 1, nullptr, nullptr, &parts));
+    const double conf = strategy == EGX_QEI_KB ? 0.0 : (strategy == EGX_QEI_KB_LB ? -3.0 : 3.0);
+    y[0] = mean[0] + conf * std::sqrt(var[0]);
+    for (int js = 1; js < nm; js++) y[js] = mean[js];
+    return EGX_SUCCESS;
+}
+
+void egx_infill_batch_config_default(egx_infill_batch_config *cfg) {
+    if (!cfg) return;
+    cfg->strategy = EGX_QEI_KB;
+    cfg->optimizer = EGX_BATCH_SLSQP;
+    cfg->max_eval = 0;
+    cfg->scaling_points = nullptr;
+    cfg->n_scaling = 0;
+}
+
+int32_t egx_infill_optimize_batch(egx_infill *h, const egx_infill_batch_config *cfg_in, const double *lo, const double *hi,
+                                  const double *x_start, int64_t n_start, int32_t q, double *x_out, double *y_virtual, double *f_out,
+                                  int32_t *n_found) {
+    if (n_found) *n_found = 0;
+    if (!h || !lo || !hi || !x_start || !x_out || !y_virtual || !f_out || !n_found || n_start < 1) {
+        set_error("infill batch: NULL argument or no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    egx_infill_batch_config cfg;
+    if (cfg_in) cfg = *cfg_in; else egx_infill_batch_config_default(&cfg);
+    if (q < 1 || q > EGX_INFILL_MAX_PENDING || cfg.strategy < EGX_QEI_KB || cfg.strategy > EGX_QEI_CL_MIN ||
+        (cfg.optimizer != EGX_BATCH_COBYLA && cfg.optimizer != EGX_BATCH_SLSQP) || (cfg.scaling_points && cfg.n_scaling < 1)) {
+        set_error("infill batch: q must be 1 .. 16, the strategy an egx_qei_strategy, the optimizer COBYLA or SLSQP");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int d = h->d, nm = (int)h->surr.size();
+    std::vector<double> cb((size_t)nm);
+    // every step through the public entry points (each takes the handle's lock itself): the loop a caller would write
+    for (int i = 0; i < q; i++) {
+        const double *xs = x_start + (size_t)i * n_start * d;
+        double *xo = x_out + (size_t)i * d, *yv = y_virtual + (size_t)i * nm;
+        if (cfg.scaling_points) EGX_RC(egx_infill_scaling(h, cfg.scaling_points, cfg.n_scaling, nullptr, nullptr, nullptr));
+        int32_t strategy = EGX_CSTR_INFILL;
+        EGX_RC(egx_infill_get_cstr_strategy(h, &strategy, nullptr));
+        if (cfg.optimizer == EGX_BATCH_SLSQP)
+            EGX_RC(egx_infill_optimize_slsqp(h, lo, hi, xs, n_start, cfg.max_eval, f_out + i, xo, cb.data(), nullptr));
+        else if (strategy == EGX_CSTR_INFILL)
+            EGX_RC(egx_infill_optimize(h, lo, hi, xs, n_start, cfg.max_eval, f_out + i, xo, nullptr));
+        else
+            EGX_RC(egx_infill_optimize_cstr(h, lo, hi, xs, n_start, cfg.max_eval, f_out + i, xo, cb.data(), nullptr));
+        EGX_RC(egx_infill_virtual_point(h, xo, cfg.strategy, yv));
+        EGX_RC(egx_infill_push_pending(h, xo, yv));
+        *n_found = i + 1;
     }
     return EGX_SUCCESS;
 }

@@ -11,7 +11,7 @@
 // (no |a|^2+|b|^2-2ab trick: cancellation would break 1e-8 parity for near-duplicate points).
 // HBM traffic is the algorithmic minimum: X read once per tile row/column from L2, R written once.
 #include "egx_internal.h"
-#include "corr_pair.h"  // exp_nonpos, PairAcc, stage_slab, dlog_dc (shared with sgp_grad.hip)
+#include "corr_pair.h"  // exp_nonpos, PairAcc, stage_slab, dlog_dc, xgrad_factor (shared with sgp_grad.hip, kernels_pending.hip)
 
 #include <algorithm>
 #include <cstdlib>
@@ -397,22 +397,6 @@ __global__ __launch_bounds__(256) void k_predict_mean_srow(PosteriorBatchPtrs b,
 //   Matern   g = sign(diff) sum_l c_kl (f'(t_l) / f(t_l) - q),  t_l = c_kl |diff|,  f = 1 + q t [+ 5/3 t^2]
 // (the closed form of the reference's product-over-all-but-one loops; sign(+0) = +1 like f64::signum).
 // ---------------------------------------------------------------------------------------------
-template <int CORR>
-__device__ __forceinline__ double xgrad_factor(double diff, const double *__restrict__ c, int hcols) {
-    if (CORR == EGX_CORR_SQUARED_EXPONENTIAL) return -(c[0] * c[0]) * diff;
-    if (CORR == EGX_CORR_ABSOLUTE_EXPONENTIAL) return -copysign(c[0], diff);
-    const double ad = fabs(diff);
-    double sacc = 0.0;
-    for (int l = 0; l < hcols; l++) {
-        const double t = c[l] * ad;
-        if (CORR == EGX_CORR_MATERN32)
-            sacc += c[l] * (kSqrt3 / __builtin_fma(kSqrt3, t, 1.0) - kSqrt3);
-        else
-            sacc += c[l] * ((kSqrt5 + 2.0 * k5over3 * t) / (1.0 + kSqrt5 * t + k5over3 * (t * t)) - kSqrt5);
-    }
-    return copysign(1.0, diff) * sacc;
-}
-
 constexpr int kXgThreads = 128;
 constexpr size_t kLdsBytes = 160 * 1024;  // LDS of one CU (gfx950)
 

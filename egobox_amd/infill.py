@@ -4,6 +4,7 @@ minimises and its x-gradient for many points per call, the scaling pass and the 
 from __future__ import annotations
 
 import ctypes as C
+import enum
 
 import numpy as np
 
@@ -13,6 +14,26 @@ from . import _lib as L
 EI, LOG_EI, WB2, WB2S = 0, 1, 2, 3
 #: how the constraint surrogates enter the optimisation (egx_cstr_strategy)
 CSTR_STRATEGIES = {"infill": 0, "mean": 1, "utb": 2}
+
+
+class QEiStrategy(enum.IntEnum):
+    """How the virtual observation of a q-point batch is chosen (egx_qei_strategy; crates/ego/src/types.rs:59-68)."""
+    KB = 0      #: Kriging believer: the objective's mean
+    KB_LB = 1   #: ... its lower bound, mean - 3 sigma
+    KB_UB = 2   #: ... its upper bound, mean + 3 sigma
+    CL_MIN = 3  #: constant liar: the training row with the smallest objective value
+
+
+_QEI = {"kb": QEiStrategy.KB, "kb_lb": QEiStrategy.KB_LB, "kb_ub": QEiStrategy.KB_UB, "cl_min": QEiStrategy.CL_MIN}
+BATCH_OPTIMIZERS = {"cobyla": 0, "slsqp": 1}
+
+
+def _qei(strategy):
+    if isinstance(strategy, str):
+        if strategy.lower() not in _QEI:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: q-EI strategy must be one of {sorted(_QEI)}")
+        return int(_QEI[strategy.lower()])
+    return int(QEiStrategy(strategy))
 
 
 def _gp_handle(model):
@@ -318,6 +339,69 @@ class InfillObjective:
         stats = dict(evals=evals, stop=stop, rounds=int(st.rounds), best_start=int(st.best_start), feasible=bool(st.feasible),
                      violation=float(st.violation), finite=rc == L.SUCCESS)
         return xb, f.value, cb[:k].copy(), stats
+
+    # ---- q points per iteration: pending (virtual) observations the models are conditioned on, no refit --------------------
+    def push_pending(self, x, y):
+        """Add the virtual observation (x (d,), y (1 + n_cstr,): objective, then the constraints) to the handle: from now on
+        every evaluation runs on the models conditioned on it (egx_infill_push_pending).  At most 16; lone dense models only."""
+        x = self._points(x)
+        y = L.as_f64(np.atleast_1d(np.asarray(y, dtype=np.float64)), 1)
+        if x.shape[0] != 1 or y.shape[0] != 1 + self.n_cstr:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: a pending point is x ({self.d},) and y ({1 + self.n_cstr},)")
+        L.check(self._lib.egx_infill_push_pending(self._h, L.dptr(x), L.dptr(y)))
+
+    def clear_pending(self):
+        """Drop the pending points: the handle evaluates its fitted models again, bit for bit as before the first push."""
+        L.check(self._lib.egx_infill_clear_pending(self._h))
+
+    @property
+    def pending(self):
+        """(x (q, d) as stored -- cast --, y (q, 1 + n_cstr), sigma2 (1 + n_cstr,) the conditioned process variances)."""
+        q = C.c_int32()
+        nm = 1 + self.n_cstr
+        x, y, s2 = np.zeros((16, self.d)), np.zeros((16, nm)), np.zeros(nm)
+        L.check(self._lib.egx_infill_get_pending(self._h, C.byref(q), L.dptr(x), L.dptr(y), L.dptr(s2)))
+        return x[:q.value].copy(), y[:q.value].copy(), s2
+
+    def virtual_point(self, x, strategy="kb"):
+        """compute_virtual_point (solver_computations.rs:261-292) at x on the handle's current (conditioned) models:
+        (1 + n_cstr,) values, what `push_pending` takes."""
+        x = self._points(x)
+        y = np.empty(1 + self.n_cstr)
+        L.check(self._lib.egx_infill_virtual_point(self._h, L.dptr(x), _qei(strategy), L.dptr(y)))
+        return y
+
+    def optimize_batch(self, xlimits, x_start, q, strategy="kb", optimizer="slsqp", scaling_points=None, max_eval=None):
+        """The q loop of solver_impl.rs:622-791 in one call (egx_infill_optimize_batch): per step the multistart from
+        x_start[i] ((q, n_start, d)), the virtual point at its optimum, the push.  Returns (x (n_found, d), y_virtual
+        (n_found, 1 + n_cstr), f (n_found,), n_found); an error at step i is raised after nothing was found, else the steps
+        before it are returned (their points stay pending)."""
+        lim = L.as_f64(xlimits, 2)
+        if lim.shape != (self.d, 2):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
+        if optimizer not in BATCH_OPTIMIZERS:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: optimizer must be one of {sorted(BATCH_OPTIMIZERS)}")
+        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+        q = int(q)
+        xs = L.as_f64(x_start, 3)
+        if q < 1 or xs.shape[0] != q or xs.shape[2] != self.d:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: x_start must be ({q}, n_start, {self.d}), got {xs.shape}")
+        cfg = L.InfillBatchConfig()
+        self._lib.egx_infill_batch_config_default(C.byref(cfg))
+        cfg.strategy, cfg.optimizer = _qei(strategy), BATCH_OPTIMIZERS[optimizer]
+        cfg.max_eval = 0 if max_eval is None else int(max_eval)
+        pts = None
+        if scaling_points is not None:
+            pts = self._points(scaling_points)
+            cfg.scaling_points, cfg.n_scaling = L.dptr(pts), pts.shape[0]
+        nm = 1 + self.n_cstr
+        x, y, f, nf = np.zeros((q, self.d)), np.zeros((q, nm)), np.zeros(q), C.c_int32()
+        rc = self._lib.egx_infill_optimize_batch(self._h, C.byref(cfg), L.dptr(lo), L.dptr(hi), L.dptr(xs), xs.shape[1], q,
+                                                 L.dptr(x), L.dptr(y), L.dptr(f), C.byref(nf))
+        if rc != L.SUCCESS and nf.value == 0:
+            L.check(rc)
+        n = nf.value
+        return x[:n].copy(), y[:n].copy(), f[:n].copy(), n
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

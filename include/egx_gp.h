@@ -896,6 +896,52 @@ int32_t egx_moe_predict_valvar_gradients_sgp(egx_sweep *sw, egx_sgp *const *expe
                                              const double *dprobas /*m*n_experts*d*/, const double *xq /*m*d*/, int64_t m,
                                              int64_t d, int32_t smooth, double *grad_val /*m*d*/, double *grad_var /*m*d*/);
 
+/* ---- q points per iteration: PENDING points on the infill handle ----------------------------------------------------------
+ * The reference's q_points > 1 loop (crates/ego/src/solver/solver_impl.rs:622-791) appends a VIRTUAL observation at the point
+ * it just found (compute_virtual_point, solver_computations.rs:261-292) and refits every surrogate before it looks for the
+ * next one.  Here the handle keeps up to EGX_INFILL_MAX_PENDING virtual observations and CONDITIONS its models on them in closed
+ * form (csrc/pending_math.h): no model is refitted or touched.  While q > 0 every evaluation of the handle -- egx_infill_eval,
+ * _eval_cstr, _scaling, the three optimisers, the parts tables, a lone expert's row of _eval_experts -- runs on the
+ * conditioned models; with q = 0 (never pushed, or after egx_infill_clear_pending) the handle launches exactly what it
+ * launched before, bit for bit.  What the conditioning equals: a refit of each model on its n + q points at its theta with its
+ * normalisation (x_mean, x_std, y_mean, y_std) FROZEN; the reference's refit re-normalises.  fmin stays what the caller set.
+ * push_pending: x is cast with the models' xtypes first, as a query would be; y holds one raw value per surrogate (objective,
+ * then the constraints).  Errors: a 17th point, a non-finite coordinate or value: EGX_ERR_INVALID_VALUE; a mixture (two or more
+ * experts) or a sparse expert among the surrogates: EGX_ERR_UNSUPPORTED naming the surrogate; d > 1024: EGX_ERR_UNSUPPORTED; a
+ * pivot of S = k(X_v, X_v) + nugget I that is not positive: EGX_ERR_LINALG -- and the handle is as it was before the call.
+ * Pending points belong to ONE fitted state of every model: after a model was refitted every evaluation returns
+ * EGX_ERR_INVALID_VALUE saying so, until egx_infill_clear_pending.
+ * Up to d = 64 the cross-covariances of a tile come from one fused contraction (csrc/kernels_pending.hip); beyond, and everywhere
+ * with egx_set_tuning("pending_composed", 1), from q launches of the existing mean / x-gradient contractions (the same values to
+ * rounding, not the same bits). */
+#define EGX_INFILL_MAX_PENDING 16
+typedef enum { EGX_QEI_KB = 0, EGX_QEI_KB_LB = 1, EGX_QEI_KB_UB = 2, EGX_QEI_CL_MIN = 3 } egx_qei_strategy;
+int32_t egx_infill_push_pending(egx_infill *h, const double *x /*d*/, const double *y /*1 + n_cstr*/);
+int32_t egx_infill_clear_pending(egx_infill *h);
+/* *q; optionally (any may be NULL) the points as stored (q x d, cast), their values (q x (1 + n_cstr)) and the conditioned
+ * process variance of every surrogate (1 + n_cstr; the fitted one while q = 0) */
+int32_t egx_infill_get_pending(egx_infill *h, int32_t *q, double *x, double *y, double *sigma2);
+/* compute_virtual_point at x on the handle's CURRENT (conditioned) models: y (1 + n_cstr).  KB / KB_LB / KB_UB: the objective's
+ * mean + {0, -3, +3} sqrt(var), the mean of every constraint.  CL_MIN: the training row with the smallest objective value, every
+ * model's y at that row (x is not read); all models must hold the same number of rows, else EGX_ERR_INVALID_VALUE. */
+int32_t egx_infill_virtual_point(egx_infill *h, const double *x /*d*/, int32_t strategy, double *y);
+typedef enum { EGX_BATCH_COBYLA = 0, EGX_BATCH_SLSQP = 1 } egx_infill_batch_optimizer;
+typedef struct {
+    int32_t strategy;  /* egx_qei_strategy */
+    int32_t optimizer; /* COBYLA: egx_infill_optimize (EGX_CSTR_INFILL) or _optimize_cstr; SLSQP: egx_infill_optimize_slsqp */
+    int64_t max_eval;  /* as the optimisers' (<= 0: their default) */
+    const double *scaling_points; /* n_scaling x d, or NULL: egx_infill_scaling on the conditioned models before every step */
+    int64_t n_scaling;
+} egx_infill_batch_config;
+void egx_infill_batch_config_default(egx_infill_batch_config *cfg); /* KB, SLSQP, 0, NULL, 0 */
+/* The q loop in one call: optimise from the step's own starts, compute the virtual point there, push it, again.  The pending
+ * points already on the handle stay and count towards the 16.  Stops at the first step whose optimiser or push fails and
+ * returns that error with the steps completed so far in *n_found (their points stay pending); f_out[i] is the criterion of
+ * step i at x_out[i] on the models conditioned on the steps before it. */
+int32_t egx_infill_optimize_batch(egx_infill *h, const egx_infill_batch_config *cfg, const double *lo /*d*/, const double *hi /*d*/,
+                                  const double *x_start /*q*n_start*d*/, int64_t n_start, int32_t q, double *x_out /*q*d*/,
+                                  double *y_virtual /*q*(1+n_cstr)*/, double *f_out /*q*/, int32_t *n_found);
+
 #ifdef __cplusplus
 }
 #endif

@@ -633,6 +633,14 @@ struct InfillSurrogate {
     }
 };
 
+// QEiStrategy, crates/ego/src/types.rs:59-68
+enum class QEiStrategy {
+    KrigingBeliever = EGX_QEI_KB,
+    KrigingBelieverLowerBound = EGX_QEI_KB_LB,
+    KrigingBelieverUpperBound = EGX_QEI_KB_UB,
+    ConstantLiarMinimum = EGX_QEI_CL_MIN
+};
+
 class InfillObjective {
   public:
     // what surrogate j was recombined from (egx_infill_eval_experts): expert-major parts, responsibilities, their derivatives
@@ -838,6 +846,43 @@ class InfillObjective {
         o.rounds = st.rounds, o.best_start = st.best_start;
         o.feasible = st.feasible != 0, o.violation = st.violation;
         return o;
+    }
+    // ---- q points per iteration (solver_impl.rs:622-791): pending virtual observations the models are conditioned on, no refit
+    void push_pending(const double *x, const double *y) { check(egx_infill_push_pending(h_.get(), x, y)); }
+    void clear_pending() { check(egx_infill_clear_pending(h_.get())); }
+    int32_t n_pending() const {
+        int32_t q = 0;
+        check(egx_infill_get_pending(h_.get(), &q, nullptr, nullptr, nullptr));
+        return q;
+    }
+    // compute_virtual_point on the current (conditioned) models: 1 + n_cstr values
+    std::vector<double> virtual_point(const double *x, QEiStrategy strategy = QEiStrategy::KrigingBeliever) const {
+        std::vector<double> y((size_t)k_ + 1);
+        check(egx_infill_virtual_point(h_.get(), x, (int32_t)strategy, y.data()));
+        return y;
+    }
+    struct Batch {
+        std::vector<double> x, y_virtual, f;  // n_found d, n_found (1 + n_cstr), n_found
+        int32_t n_found = 0;
+    };
+    // x_start: q x n_start x d; an error at a later step returns the steps before it (their points stay pending)
+    Batch optimize_batch(const double *lo, const double *hi, const double *x_start, int64_t n_start, int32_t q,
+                         QEiStrategy strategy = QEiStrategy::KrigingBeliever, bool slsqp = true, int64_t max_eval = 0,
+                         const double *scaling_points = nullptr, int64_t n_scaling = 0) {
+        egx_infill_batch_config cfg;
+        egx_infill_batch_config_default(&cfg);
+        cfg.strategy = (int32_t)strategy;
+        cfg.optimizer = slsqp ? EGX_BATCH_SLSQP : EGX_BATCH_COBYLA;
+        cfg.max_eval = max_eval;
+        cfg.scaling_points = scaling_points, cfg.n_scaling = n_scaling;
+        Batch b;
+        const size_t qq = (size_t)(q > 0 ? q : 0), nm = (size_t)k_ + 1;
+        b.x.assign(qq * (size_t)d_ + 1, 0.0), b.y_virtual.assign(qq * nm + 1, 0.0), b.f.assign(qq + 1, 0.0);
+        const int32_t rc = egx_infill_optimize_batch(h_.get(), &cfg, lo, hi, x_start, n_start, q, b.x.data(), b.y_virtual.data(),
+                                                     b.f.data(), &b.n_found);
+        if (rc != EGX_SUCCESS && b.n_found == 0) check(rc);
+        b.x.resize((size_t)b.n_found * (size_t)d_), b.y_virtual.resize((size_t)b.n_found * nm), b.f.resize((size_t)b.n_found);
+        return b;
     }
     egx_infill *handle() const { return h_.get(); }
 

@@ -39,6 +39,18 @@ at most 200 evaluations per start.  Legs alternated, medians with quartiles, the
 profiles/infill_slsqp_bench.txt; no threshold is set.
 
     python tools/infill_bench.py --slsqp [--out profiles/infill_slsqp_bench.txt] [--reps 7]
+
+--pending times the q-point batch (pending points: the models conditioned on virtual observations, no refit) on a dense objective
+and two constraint models under EGX_CSTR_MEAN, d = 8, n = 500 and n = 4096: (a) one value + gradient evaluation at m = 1, 20,
+4096 with q = 0, 1, 4, 8, 16 pending points -- q = 0 is the handle of the parent commit, the others add k_pending_cross and
+k_pending_finish per (tile, model), FUSED, or with egx_set_tuning("pending_composed", 1) q launches of the existing mean and
+x-gradient contractions in place of k_pending_cross, COMPOSED; (b) egx_infill_optimize_batch (q = 4, 20 starts, SLSQP, Kriging believer) against the REFIT
+LOOP a caller writes without it: per step a new GpHandle on the n + i points finalised at the old theta, a new InfillObjective,
+one optimize_slsqp, the believer's value from predict.  The refit loop uses only entry points that exist without the feature
+and is the yardstick on any commit.  Legs alternated, >= 3 warm-ups, medians with quartiles, written to
+profiles/infill_pending_bench.txt; no threshold is set.
+
+    python tools/infill_bench.py --pending [--out profiles/infill_pending_bench.txt] [--reps 9]
 """
 import argparse
 import os
@@ -208,6 +220,93 @@ def run_slsqp(args, emit):
         h.close()
 
 
+def run_pending(args, emit):
+    d, k, n_start, q_batch, budget = 8, 2, 20, 4, 200
+    rng = np.random.default_rng(1)
+    lim = np.array([[0.0, 1.0]] * d)
+    emit("# pending points: objective + %d constraint models under EGX_CSTR_MEAN, d %d, LogEI; wall ms as q25 median q75 over %d"
+         % (k, d, args.reps))
+    emit("# runs after 3 warm-ups, legs alternated")
+    for n in (500, 4096):
+        xs, ys, hs = [], [], []
+        for j in range(1 + k):
+            x, y = workload.make_training_set(n, d, seed=100 + j)
+            y = 1e-3 * y if j == 0 else (y - np.quantile(y, 0.6) if j == 1 else np.quantile(y, 0.25) - y)
+            h = egx.GpHandle(x, y)
+            h.finalize(np.full(d, 1.5))
+            xs.append(x), ys.append(y), hs.append(h)
+        tols = [1e-3, 1e-3]
+        kw = dict(criterion=egx.LOG_EI, fmin=float(np.quantile(ys[0], 0.05)))
+        obj = egx.InfillObjective(hs[0], hs[1:], tols, **kw)
+        obj.set_cstr_strategy("mean")
+        has = hasattr(obj, "push_pending")
+        # (a) one evaluation with gradients; the q legs of one m are visited in turn, twice (the two q = 0 runs show the spread)
+        emit("# (a) n m q fused: q25_ms median_ms q75_ms  composed (q > 0): q25_ms median_ms q75_ms"
+             "  [constraints(x, grad=True): value, gradient, constraints, their Jacobian]")
+        pend = rng.random((16, d))
+        for m in (1, 20, 4096):
+            xq = rng.random((m, d))
+            for q in (0, 1, 4, 8, 16, 0):
+                if q and not has:
+                    emit(f"a {n} {m} {q} not available here")
+                    continue
+                if has:
+                    obj.clear_pending()
+                    for v in range(q):
+                        obj.push_pending(pend[v], obj.virtual_point(pend[v], "kb_ub"))
+                (q1, q2, q3), _ = quartiles_ms(lambda: obj.constraints(xq, grad=True), args.reps, warm=3)
+                line = f"a {n} {m} {q} {q1:.3f} {q2:.3f} {q3:.3f}"
+                if q:  # the composed form on the same handle: q launches of the existing contractions per (tile, model)
+                    egx.set_tuning("pending_composed", 1)
+                    try:
+                        (c1, c2, c3), _ = quartiles_ms(lambda: obj.constraints(xq, grad=True), args.reps, warm=3)
+                    finally:
+                        egx.set_tuning("pending_composed", 0)
+                    line += f" {c1:.3f} {c2:.3f} {c3:.3f}"
+                emit(line)
+        if has:
+            obj.clear_pending()
+        # (b) the batch
+        starts = rng.random((q_batch, n_start, d))
+
+        def leg_batch():
+            obj.clear_pending()
+            return obj.optimize_batch(lim, starts, q_batch, strategy="kb", optimizer="slsqp", max_eval=budget)[2]
+
+        def leg_refit():
+            xa, ya, f = [x.copy() for x in xs], [y.copy() for y in ys], []
+            for i in range(q_batch):
+                if i == 0:
+                    cur, own = hs, []
+                else:
+                    own = [egx.GpHandle(xj, yj) for xj, yj in zip(xa, ya)]
+                    for h in own:
+                        h.finalize(np.full(d, 1.5))
+                    cur = own
+                o = egx.InfillObjective(cur[0], cur[1:], tols, **kw)
+                o.set_cstr_strategy("mean")
+                xb, fb = o.optimize_slsqp(lim, starts[i], max_eval=budget)[:2]
+                yv = [float(h.predict(xb[None])[0]) for h in cur]
+                o.close()
+                for h in own:
+                    h.close()
+                for j in range(1 + k):
+                    xa[j], ya[j] = np.vstack([xa[j], xb]), np.append(ya[j], yv[j])
+                f.append(fb)
+            return np.array(f)
+
+        emit("# (b) leg n q n_start q25_ms median_ms q75_ms f_out  [batch: egx_infill_optimize_batch; refit: the caller's loop]")
+        for name, fn, on in (("refit", leg_refit, True), ("batch", leg_batch, has), ("refit2", leg_refit, True)):
+            if not on:
+                emit(f"b {name} {n} not available here")
+                continue
+            (q1, q2, q3), f = quartiles_ms(fn, max(3, args.reps // 3), warm=3)
+            emit(f"b {name} {n} {q_batch} {n_start} {q1:.1f} {q2:.1f} {q3:.1f} " + " ".join(f"{v:.6g}" for v in f))
+        obj.close()
+        for h in hs:
+            h.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -215,11 +314,12 @@ def main():
     ap.add_argument("--cstr", action="store_true", help="one lock-step round in MEAN, UTB and INFILL mode on one handle")
     ap.add_argument("--sparse", action="store_true", help="the sparse leg: one sparse objective (nz = 512, d = 8), value + gradient")
     ap.add_argument("--slsqp", action="store_true", help="20 starts of SLSQP: the lock-step call, scipy on the m = 1 closures, COBYLA")
+    ap.add_argument("--pending", action="store_true", help="pending points: one evaluation at q = 0 .. 16, the batch call against the refit loop")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
+        args.out = os.path.join(ROOT, "profiles", "infill_pending_bench.txt" if args.pending else "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
                                 else "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
@@ -237,8 +337,8 @@ def main():
             obj.value(xq)
             obj.value_and_grad(xq)
         return
-    if args.slsqp:
-        run_slsqp(args, emit)
+    if args.slsqp or args.pending:
+        (run_pending if args.pending else run_slsqp)(args, emit)
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         return
