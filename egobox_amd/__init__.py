@@ -25,6 +25,9 @@ from .infill import EI, LOG_EI, WB2, WB2S, InfillObjective, QEiStrategy  # noqa:
 from . import mixint  # noqa: E402
 from .mixint import (MixintContext, MixintGpMixture, MixintGpMixtureParams, XType, as_continuous_limits,  # noqa: E402
                      cast_to_discrete_values, fold_with_enum_index, to_continuous_space, to_discrete_space, unfold_with_enum_mask)
+from . import doe, egor  # noqa: E402
+from .doe import FullFactorial, Lhs, Random, Sampling, lhs, sampling  # noqa: E402
+from .egor import Egor, GpConfig, OptimResult  # noqa: E402
 from .sweep import Sweep, best_candidate, rendezvous_sweep, shard_indices, sweep_likelihood  # noqa: E402
 
 __all__ = [n for n in dir() if not n.startswith("_")]
