@@ -16,6 +16,15 @@
 //                      var == nullptr is its mean-only twin (a constraint surrogate under EGX_CSTR_MEAN: the mean shift alone).
 // A lane or a workgroup owns a point and every order of summation depends on the model and q alone: a point's bits do not depend
 // on its companions.
+//
+// Nor on the INSTANCE of k_pending_cross that formed them: the values-only instance (<.., 1, false>), the gradient instances
+// (DK = 8 / 16) and the three pass widths QV must give a column the same value sum bit for bit (InfillObjective.value against
+// value_and_grad, a narrow last pass against a full one).  With the compiler free to fuse a multiply into an add ACROSS
+// statements, which pairs it fuses depends on what else an instance computes from the same operands (xgrad_factor shares the
+// subexpressions of PairAcc::add), and value() differed from value_and_grad() in the last bits at d > 8.  So this file is
+// compiled with contraction inside one expression only -- a function of the source text, the same in every instance.  The
+// pragma comes before the headers: it has to cover PairAcc, exp_nonpos and xgrad_factor as they are parsed.
+#pragma clang fp contract(on)
 #include "egx_internal.h"
 #include "corr_pair.h"
 #include "pending_math.h"

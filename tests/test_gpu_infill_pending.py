@@ -4,19 +4,16 @@ criterion as the arithmetic of those parts, the exactness of the switch, the bel
 manual loop and against the refit, errors and state, a C host."""
 import os
 import subprocess
-import types
 
 import numpy as np
 import pytest
 
-import infill_oracle as IO
-import pending_oracle as PO
-from test_gpu_infill import CRITERIA, KINDS, MEANS, PRED_RTOL, _check_criterion, _grad_tol
-from test_gpu_sample import oracle_from_handle
+from pending_cases import (KEYS, PRED_RTOL, TOLS, _assert_conditioned, _case, _check_batch, _check_clear_pending,
+                           _check_companions, _check_composed_form, _check_parts_against_refit, _close, _push_all, _ys)
+from test_gpu_infill import CRITERIA, _check_criterion
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOLS = [0.3, 0.1]
 
 
 @pytest.fixture(scope="module")
@@ -29,71 +26,6 @@ def egx():
 def O():
     from oracle import gp_oracle
     return gp_oracle
-
-
-def _ys(y):
-    """the objective (scaled as in tests/test_gpu_infill.py) and two constraint outputs on the same rows"""
-    return [1e-3 * y, y - np.quantile(y, 0.6), np.quantile(y, 0.7) - y]
-
-
-def _case(egx, O, n, d, q, theta, mean, corr, m=40, w=None):
-    """three fitted models on workload.make_training_set(n, d, seed=1), their oracles, q pending points and m queries uniform in
-    the data's box, virtual values = base mean + 3 sigma N(0, 1)"""
-    from egobox_amd import workload
-    x, y = workload.make_training_set(n, d, seed=1)
-    c = types.SimpleNamespace(x=x, ys=_ys(y), n=n, d=d, q=q, hs=[], gs=[])
-    th = np.atleast_1d(np.asarray(theta, dtype=np.float64))
-    th = np.full(d if w is None else w.shape[1], th[0]) if th.size == 1 else th
-    for yj in c.ys:
-        h = egx.GpHandle(x, yj, mean=mean, corr=corr, w_star=w)
-        h.finalize(th)
-        c.hs.append(h)
-        c.gs.append(oracle_from_handle(O, h, MEANS[mean], KINDS[corr], x, yj, w_star=w))
-    rng = np.random.default_rng(1000 * n + 10 * d + q)
-    lo, hi = x.min(axis=0), x.max(axis=0)
-    c.lo, c.hi = lo, hi
-    c.xv = lo + (hi - lo) * rng.random((q, d))
-    c.xq = lo + (hi - lo) * rng.random((m, d))
-    c.yv = np.empty((q, 3))
-    for j, g in enumerate(c.gs):
-        mu, var = g.predict_valvar(c.xv)
-        c.yv[:, j] = mu + 3.0 * np.sqrt(var) * rng.standard_normal(q)
-    c.fmin = float(np.quantile(c.ys[0], 0.1))
-    return c
-
-
-def _close(c):
-    for h in c.hs:
-        h.close()
-
-
-def _assert_conditioned(c, xq):
-    """the condition on the cases, on the ORACLE: below it s^2 - c^T S^-1 c loses its digits in any double evaluation"""
-    min_diag, min_unit = PO.cond_report(c.gs[0], c.xv, xq)  # (the three models share x, theta, kernel and trend)
-    print(f"n {c.n} d {c.d} q {c.q}: min diag S {min_diag:.3g}, min conditioned unit variance {min_unit:.3g}")
-    assert min_diag >= 1e-2 and min_unit >= 1e-4
-
-
-def _push_all(obj, c):
-    for v in range(c.q):
-        obj.push_pending(c.xv[v], c.yv[v])
-
-
-def _check_parts_against_refit(c, p, xq, sigma2):
-    for j, g in enumerate(c.gs):
-        ref = PO.refit_frozen(g, c.xv, c.yv[:, j])
-        ry, rv = ref.predict_valvar(xq)
-        gy, gv = ref.predict_valvar_gradients(xq)
-        for name, got, want in (("mean", p["mean"][j], np.ravel(ry)), ("var", p["var"][j] / ref.inner.sigma2, np.ravel(rv) / ref.inner.sigma2),
-                                ("grad_mean", p["grad_mean"][j] / np.abs(gy).max(), gy / np.abs(gy).max()),
-                                ("grad_var", p["grad_var"][j] / np.abs(gv).max(), gv / np.abs(gv).max())):
-            print(f"  model {j} {name}: worst abs error {np.max(np.abs(got - want)):.3e} (scale {np.max(np.abs(want)):.3e})")
-        print(f"  model {j} sigma2: {sigma2[j]:.12e} refit {ref.inner.sigma2:.12e}")
-        np.testing.assert_allclose(p["mean"][j], np.ravel(ry), rtol=PRED_RTOL, atol=1e-9)
-        np.testing.assert_allclose(p["var"][j], np.ravel(rv), rtol=PRED_RTOL, atol=1e-9 * ref.inner.sigma2)
-        np.testing.assert_allclose(p["grad_mean"][j], gy, **_grad_tol(gy))
-        np.testing.assert_allclose(p["grad_var"][j], gv, **_grad_tol(gv))
-        np.testing.assert_allclose(sigma2[j], ref.inner.sigma2, rtol=1e-6)
 
 
 # ---- 1. parts against the refit ----------------------------------------------------------------------------------------------
@@ -152,20 +84,7 @@ def test_parts_composed_form(egx, O, n, d, q, theta, mean):
         _assert_conditioned(c, c.xq)
         with egx.InfillObjective(c.hs[0], c.hs[1:], TOLS, criterion=egx.EI, fmin=c.fmin) as obj:
             _push_all(obj, c)
-            fused = obj.parts(c.xq)
-            assert egx.set_tuning("pending_composed", 1) == 0
-            try:
-                comp = obj.parts(c.xq)
-                _check_parts_against_refit(c, comp, c.xq, obj.pending[2])
-                obj.set_cstr_strategy("mean", [1.0, 1.0])  # the mean-only twin on the composed layouts
-                cs, gc = obj.constraints(c.xq, grad=True)[1::2]
-                np.testing.assert_array_equal(cs, comp["mean"][1:].T)
-                np.testing.assert_array_equal(gc, comp["grad_mean"][1:].transpose(1, 0, 2))
-            finally:
-                assert egx.set_tuning("pending_composed", 0) == 1
-            for k in KEYS[2:]:
-                scale = np.abs(fused[k]).reshape(3, -1).max(axis=1).reshape((3,) + (1,) * (fused[k].ndim - 1))
-                assert np.max(np.abs(comp[k] - fused[k]) / scale) <= 1e-9, k
+            _check_composed_form(egx, c, obj)
     finally:
         _close(c)
 
@@ -219,43 +138,12 @@ def test_criterion_is_the_arithmetic_of_the_conditioned_parts(egx, mid):
 
 
 # ---- 3. exactness of the switch -----------------------------------------------------------------------------------------------
-KEYS = ("value", "grad", "mean", "var", "grad_mean", "grad_var")
-
-
 def test_clear_pending_gives_back_the_fitted_handle_bit_for_bit(egx, mid):
-    c = mid
-    kw = dict(criterion=egx.LOG_EI, fmin=c.fmin)
-    with egx.InfillObjective(c.hs[0], c.hs[1:], TOLS, **kw) as never, egx.InfillObjective(c.hs[0], c.hs[1:], TOLS, **kw) as obj:
-        want = never.parts(c.xq)
-        before = obj.parts(c.xq)
-        _push_all(obj, c)
-        with_pending = obj.parts(c.xq)
-        assert not np.array_equal(with_pending["mean"], want["mean"])
-        obj.clear_pending()
-        assert obj.pending[0].shape == (0, c.d)
-        after = obj.parts(c.xq)
-        for k in KEYS:
-            np.testing.assert_array_equal(before[k], want[k])
-            np.testing.assert_array_equal(after[k], want[k])
-        np.testing.assert_array_equal(obj.value(c.xq), never.value(c.xq))
-        np.testing.assert_array_equal(obj.pending[2], [g.inner.sigma2 for g in c.gs])
+    _check_clear_pending(egx, mid)
 
 
 def test_a_conditioned_point_does_not_depend_on_its_companions(egx, mid):
-    c = mid
-    with egx.InfillObjective(c.hs[0], c.hs[1:], TOLS, criterion=egx.LOG_EI, fmin=c.fmin) as obj:
-        _push_all(obj, c)
-        big = obj.parts(c.xq)  # 131 points: two tiles, the second ragged
-        for i in (0, 57, 127, 128, 130):
-            one = obj.parts(c.xq[i])
-            for k in KEYS:
-                np.testing.assert_array_equal(np.take(big[k], i, axis=0 if k in ("value", "grad") else 1),
-                                              np.take(one[k], 0, axis=0 if k in ("value", "grad") else 1))
-        # ... nor on the constraint strategy's mean-only sequence
-        obj.set_cstr_strategy("mean", [1.0, 1.0])
-        v, cs, g, gc = obj.constraints(c.xq, grad=True)
-        np.testing.assert_array_equal(cs, big["mean"][1:].T)
-        np.testing.assert_array_equal(gc, big["grad_mean"][1:].transpose(1, 0, 2))
+    _check_companions(egx, mid)  # 131 points: two tiles, the second ragged
 
 
 # ---- 4. the believer property -------------------------------------------------------------------------------------------------
@@ -294,34 +182,7 @@ def small(egx, O):
 @pytest.mark.parametrize("optimizer", ["slsqp", "cobyla"])
 @pytest.mark.parametrize("strategy", ["kb", "cl_min"])
 def test_batch_is_the_manual_loop_and_the_refit(egx, small, optimizer, strategy):
-    c, q, ns = small, 4, 8
-    lim = np.stack([c.lo, c.hi], axis=1)
-    starts = c.lo + (c.hi - c.lo) * np.random.default_rng(17).random((q, ns, c.d))
-    kw = dict(criterion=egx.LOG_EI, fmin=c.fmin)
-    with egx.InfillObjective(c.hs[0], c.hs[1:], TOLS, **kw) as a, egx.InfillObjective(c.hs[0], c.hs[1:], TOLS, **kw) as b:
-        x, yv, f, nf = a.optimize_batch(lim, starts, q, strategy=strategy, optimizer=optimizer)
-        assert nf == 4
-        for i in range(q):  # the loop a caller writes
-            xi, fi = (b.optimize_slsqp(lim, starts[i])[:2] if optimizer == "slsqp" else b.optimize(lim, starts[i])[1::-1])
-            yi = b.virtual_point(xi, strategy)
-            b.push_pending(xi, yi)
-            np.testing.assert_array_equal(x[i], xi)
-            np.testing.assert_array_equal(yv[i], yi)
-            assert f[i] == fi
-        np.testing.assert_array_equal(a.pending[0], x)
-        np.testing.assert_array_equal(a.pending[1], yv)
-        if strategy == "cl_min":
-            imin = int(np.argmin(c.ys[0]))
-            np.testing.assert_array_equal(yv, np.tile([yj[imin] for yj in c.ys], (q, 1)))
-        prm = a.params
-        for i in range(q):  # f_out[i] from refits on the first i points
-            refs = [g if i == 0 else PO.refit_frozen(g, x[:i], yv[:i, j]) for j, g in enumerate(c.gs)]
-            mv = [r.predict_valvar(x[i:i + 1]) for r in refs]
-            mean, var = np.array([float(m[0][0]) for m in mv]), np.array([float(m[1][0]) for m in mv])
-            want = IO.objective(a.criterion, mean, var, TOLS, prm["fmin"], prm["sigma_weight"], prm["scale_ic"], prm["scale"],
-                                prm["feasibility"], dev=True)
-            print(f"{optimizer} {strategy} step {i}: f {f[i]:.12e} refit {want:.12e}")
-            np.testing.assert_allclose(f[i], want, rtol=1e-6)
+    _check_batch(egx, small, 4, 8, optimizer, strategy)
 
 
 # ---- 6. errors and state ------------------------------------------------------------------------------------------------------

@@ -50,6 +50,17 @@ def test_closed_form_is_the_frozen_refit(n, d, q, theta, corr, mean):
     assert em <= 1e-10 and ev <= 1e-10 and es <= 1e-10
 
 
+def test_the_case_tables_data_is_the_workloads():
+    """tests/pending_cases.py imports without the library, so it takes its data from the oracle: the same numbers"""
+    from egobox_amd import workload
+    import pending_cases as PC
+    for n, d in ((130, 9), (260, 17)):
+        x, y = workload.make_training_set(n, d, seed=1)
+        got = PC._draw(n, d, 2, 3)
+        np.testing.assert_array_equal(got[0], x)
+        np.testing.assert_array_equal(got[1], y)
+
+
 # ---- pending_math.h on the host -----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
