@@ -17,7 +17,7 @@
 // Every start of the multistart is one machine; the driver advances all of them in lock-step and evaluates their
 // requests as ONE egx_gp_likelihood_batch (gp_fit.hip).
 // Two classes: CobylaBox (bounds only, the closed form above) and, further down, Cobyla (m nonlinear constraints beside the
-// bounds, Powell's TRSTLP in full) for the infill optimiser whose constraint surrogates are constraints (gp_infill.hip).
+// bounds, Powell's TRSTLP in full) for the infill optimiser whose constraint surrogates are constraints (infill_optimize.hip).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -570,7 +570,7 @@ private:
     }
 };
 
-// COBYLA with GENERAL nonlinear inequality constraints, the optimiser behind egx_infill_optimize_cstr (gp_infill.hip): the
+// COBYLA with GENERAL nonlinear inequality constraints, the optimiser behind egx_infill_optimize_cstr (infill_optimize.hip): the
 // reference hands every constraint surrogate to `cobyla` as a nonlinear constraint (crates/ego/src/solver/
 // solver_infill_optim.rs:148-204).  Powell's algorithm as CobylaBox restates it -- the same COBYLB simplex / merit / radius
 // logic, now over m + 2n constraints -- with his TRSTLP in full: stage one minimises the greatest violation of the

@@ -196,7 +196,7 @@ int launch_trmm_mean(hipStream_t s, const double *L, int64_t ldl, int m_pad, con
 
 // ---- kernels_infill.hip -----------------------------------------------------
 // The host arithmetic of predict_impl / xgrad_impl as kernels over ONE tile of kTile query points of one model, and the
-// criterion of infill_math.h across the models of a point (gp_infill.hip).
+// criterion of infill_math.h across the models of a point (infill_eval.hip).
 namespace infill {
 struct Params;
 }

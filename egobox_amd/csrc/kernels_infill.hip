@@ -1,4 +1,4 @@
-// Kernels of the fused infill evaluation (gp_infill.hip): everything predict_impl / xgrad_impl do on the HOST between their
+// Kernels of the fused infill evaluation (infill_eval.hip): everything predict_impl / xgrad_impl do on the HOST between their
 // launches, per tile of kTile = 128 query points and per model, plus the criterion itself:
 //   k_infill_prepare   raw queries -> normalised k-major tile (algorithm.rs:254), non-finite points flagged and zeroed
 //   k_infill_trend     mean = f beta + sum of the split partial sums (algorithm.rs:260-262); A = f - ft^T rt, Rq^T u = A, Rq D = u,

@@ -1,6 +1,6 @@
-// Kernels of the PENDING points of an infill handle (gp_infill.hip, pending_math.h): a fitted model conditioned on q <= 16
+// Kernels of the PENDING points of an infill handle (infill_pending.hip, pending_math.h): a fitted model conditioned on q <= 16
 // virtual observations without a refit.  Per tile of kTile = 128 queries and per conditioned model, right after the model's own
-// tile sequence (expert_tile / expert_tile_mean), while the normalised tile is still in place:
+// tile sequence (expert_tile, infill_eval.hip), while the normalised tile is still in place:
 //   k_pending_cross    the rectangular multi-column contraction over Z = the training points followed by the pending ones,
 //                          c[a, v]             = sum_j r(x_a, Z_j) W^[j, v]
 //                          d c[a, v] / d x_ak  = sum_j d_k r(x_a, Z_j) W^[j, v]

@@ -1,4 +1,4 @@
-// Conditioning a fitted universal-kriging model on q VIRTUAL observations in closed form (gp_infill.hip: the pending points of a
+// Conditioning a fitted universal-kriging model on q VIRTUAL observations in closed form (infill_pending.hip: the pending points of a
 // q-point infill batch; crates/ego/src/solver/solver_impl.rs:622-791 refits instead).  With k(x, x') = r(x, x') - rt(x)^T rt(x')
 // + u(x)^T u(x') the model's unit posterior covariance (algorithm.rs:330-369), X_v / y_v the virtual observations in the model's
 // own normalisation,

@@ -1,5 +1,5 @@
 // SLSQP for  minimise f(x)  subject to  c_j(x) <= cfeas_j (j < k)  and  lo <= x <= hi,  as a resumable (ask / tell)
-// state machine: the optimiser behind egx_infill_optimize_slsqp (gp_infill.hip).
+// state machine: the optimiser behind egx_infill_optimize_slsqp (infill_optimize.hip).
 //
 // The reference's default inner optimiser is the `slsqp` crate (crates/ego/src/optimizers/optimizer.rs:169-204), a port of
 // the SLSQP in NLopt, which is D. Kraft's "A software package for sequential quadratic programming" (DFVLR-FB 88-28, 1988).

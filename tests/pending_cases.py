@@ -1,5 +1,5 @@
 """Helper of the pending-point tests (not a test): the recipe of a case, the checks the GPU files share, and the table of shapes
-at which the fused conditioning (egobox_amd/csrc/kernels_pending.hip, gp_infill.hip pending_tile) branches.  Imports without the
+at which the fused conditioning (egobox_amd/csrc/kernels_pending.hip, infill_pending.hip pending_tile) branches.  Imports without the
 library: the data comes from oracle.gp_oracle.lhs_classic / griewank, which draw the numbers of workload.make_training_set.
 
 tests/test_pending_cases_cpu.py checks on the oracle alone that every row is well posed and that the rows named after an LDS

@@ -1,4 +1,4 @@
-"""The fused infill evaluation on the GPU (egx_infill_*; egobox_amd/csrc/gp_infill.hip, kernels_infill.hip): its parts against
+"""The fused infill evaluation on the GPU (egx_infill_*; egobox_amd/csrc/infill_eval.hip, kernels_infill.hip): its parts against
 oracle.gp_oracle on the handle's own fitted state, the criterion against tests/infill_oracle.py applied to those parts, the
 bit-independence of a point from its companions, the scaling pass, the lock-step multistart, errors and state."""
 import os

@@ -1,5 +1,5 @@
 """The constraint surrogates as constraints of the infill optimiser (cstr_infill = false; egx_infill_set_cstr_strategy,
-egx_infill_eval_cstr, egx_infill_optimize_cstr; gp_infill.hip, kernels_infill.hip, cobyla.h): the constraint values and
+egx_infill_eval_cstr, egx_infill_optimize_cstr; infill_eval.hip, infill_optimize.hip, kernels_infill.hip, cobyla.h): the constraint values and
 their gradients against the handle's own parts (the mean-only launch sequence against the full one, bit for bit), against
 oracle.gp_oracle and against central differences; the modes; the lock-step multistart with general constraints; a compiled
 host of the C ABI and of the C++ mirror."""

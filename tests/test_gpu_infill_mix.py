@@ -1,4 +1,4 @@
-"""The infill criterion on mixtures of experts (egx_infill_create_mix, k_infill_mix; egobox_amd/csrc/gp_infill.hip,
+"""The infill criterion on mixtures of experts (egx_infill_create_mix, k_infill_mix; egobox_amd/csrc/infill_eval.hip,
 kernels_infill.hip, infill_mix_math.h, gmx_point.h): a handle of single experts against the old entry point bit for bit, the
 surrogate parts against the library's mixture predictions, the criterion against tests/infill_oracle.py on those parts, the
 expert diagnostics, the bit-independence of a point from its companions, NaN points, the lock-step multistart, a re-finalised

@@ -1,4 +1,4 @@
-"""Pending points on the infill handle (egx_infill_push_pending and friends; gp_infill.hip, kernels_pending.hip, pending_math.h):
+"""Pending points on the infill handle (egx_infill_push_pending and friends; infill_pending.hip, kernels_pending.hip, pending_math.h):
 the conditioned parts against an actual refit with frozen normalisation (tests/pending_oracle.py on oracle.gp_oracle), the
 criterion as the arithmetic of those parts, the exactness of the switch, the believer property, the batch call against the
 manual loop and against the refit, errors and state, a C host."""

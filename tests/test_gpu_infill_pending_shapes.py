@@ -1,4 +1,4 @@
-"""The conditioning of an infill handle on its pending points (egobox_amd/csrc/kernels_pending.hip, gp_infill.hip pending_tile) at
+"""The conditioning of an infill handle on its pending points (egobox_amd/csrc/kernels_pending.hip, infill_pending.hip pending_tile) at
 the shapes where its launch code branches -- the table of tests/pending_cases.py, which tests/test_pending_cases_cpu.py holds to
 its gate and to the thresholds on the CPU:
 

@@ -1,4 +1,4 @@
-"""The fused infill evaluation (egx_infill_eval and its variants; egobox_amd/csrc/gp_infill.hip, kernels_infill.hip) at the shapes
+"""The fused infill evaluation (egx_infill_eval and its variants; egobox_amd/csrc/infill_eval.hip, kernels_infill.hip) at the shapes
 where its kernels branch, against the CPU oracle on the handle's own fitted state (test_gpu_sample.oracle_from_handle; nothing
 is refitted), tests/infill_oracle.py for the criterion and oracle/moe_oracle.py for the recombination of a mixture:
 
@@ -46,8 +46,8 @@ def geometry(n, d, mean):
     """What the fused sequence does with a model of n points, d inputs and trend `mean` (0 constant, 1 linear, 2 quadratic) at
     the fixed 128-point tile.  Mirrors
       gp_host.hip slab_geometry:              n_pad = round_up(n, n >= 4096 ? kNB = 256 : kTile = 128), rhs_pad = round_up(p + 1, 128)
-      gp_infill.hip mean_splits:              msplit = min(ceil(1024 / (kTile / 64)), n_pad / 64), evened out over the slabs
-      gp_infill.hip xgrad_splits:             nsplit = min(512, ceil(n / 64)), evened out over the slabs
+      gp_predict.hip mean_splits:             msplit = min(ceil(1024 / (kTile / 64)), n_pad / 64), evened out over the slabs
+      gp_predict.hip xgrad_splits:            nsplit = min(512, ceil(n / 64)), evened out over the slabs
       kernels_infill.hip k_infill_xgrad_finish: kc = min(kInfThreads = 256, kXgStage = 2048 / nsplit), passes k0 = 0, kc, ... < d
       kernels_infill.hip k_infill_trend:      loops over l < p, j < p and sp < msplit strided by kInfThreads = 256"""
     p = [1, 1 + d, 1 + d + d * (d + 1) // 2][mean]

@@ -1,4 +1,4 @@
-"""The lock-step SLSQP multistart of the infill criterion (egx_infill_optimize_slsqp; gp_infill.hip, csrc/slsqp.h): the
+"""The lock-step SLSQP multistart of the infill criterion (egx_infill_optimize_slsqp; infill_optimize.hip, csrc/slsqp.h, csrc/multistart.h): the
 evaluation contract of what it returns, the lock-step contract against one-start runs, the three constraint strategies, the
 handle kinds (dense, mixture, sparse, typed), Kraft's own code driven by the library's m = 1 callbacks, the refusals, and a
 compiled C host."""

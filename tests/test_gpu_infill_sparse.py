@@ -1,4 +1,4 @@
-"""Sparse experts in the infill handle (egx_infill_create_any; sgp_expert_tile in egobox_amd/csrc/gp_infill.hip, the sparse tails
+"""Sparse experts in the infill handle (egx_infill_create_any; sgp_expert_tile in egobox_amd/csrc/infill_eval.hip, the sparse tails
 of kernels_infill.hip) and sparse mixtures (egx_moe_predict_valvar(_gradients)_sgp, SparseGpMix(n_clusters=k)) on the GPU.
 
 Inputs of tests/test_gpu_sgp_surrogate.py::test_gradients_vs_analytic_oracle: problem(700, 40, 3, seed=corr), theta =
