@@ -270,6 +270,9 @@ SIGNATURES = [
     ("egx_infill_batch_config_default", None, [C.POINTER(InfillBatchConfig)]),
     ("egx_infill_optimize_batch", C.c_int32, [C.c_void_p, C.POINTER(InfillBatchConfig), c_double_p, c_double_p, c_double_p,
                                               C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    ("egx_infill_set_active", C.c_int32, [C.c_void_p, c_int32_p, C.c_int32, c_double_p]),
+    ("egx_infill_clear_active", C.c_int32, [C.c_void_p]),
+    ("egx_infill_get_active", C.c_int32, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
 ]
 
 

@@ -112,10 +112,12 @@ inline int launch_predict_mean(hipStream_t s, int corr, const double *xqT, int64
 // xs[k][i] = coef[k] * xT[k][i] over a (d x ldx) k-major array
 int launch_scale_rows(hipStream_t s, const double *xT, int64_t ldx, int d, const double *coef, double *xs);
 // x-gradient contraction out[split][a][k] = sum_j w(j, a) d r(x_a, x_j) / d x_ak over the split's training range;
-// Wt = gamma (vec != 0, ldw ignored) or the transposed (n x m_pad) weight matrix; m_pad multiple of 128
+// Wt = gamma (vec != 0, ldw ignored) or the transposed (n x m_pad) weight matrix; m_pad multiple of 128.
+// cols (a DEVICE array of ncols distinct column indices in [0, d), or nullptr): the column-list form -- the listed columns k
+// alone, with the bits of the full form, and +0.0 in every other column of out
 int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT, int64_t ldx,
                  int n, int d, const double *coef, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit,
-                 double *out);
+                 double *out, const int *cols = nullptr, int ncols = 0);
 // few-query form of launch_xgrad with a weight VECTOR: out (ceil(n / 256) x m x d) partial sums, lanes over training points
 int launch_xgrad_point(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m, const double *xT, int64_t ldx, int n,
                        int d, const double *coef, int hcols, const double *wvec, double *out);

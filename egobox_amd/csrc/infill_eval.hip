@@ -30,6 +30,12 @@
 // posterior_solve, no weights, no second contraction; the means keep the bits of the full sequence, which forms r . gamma
 // before its solve as well.  A call that does not ask for anything of the constraint surrogates (egx_infill_eval without parts
 // under MEAN / UTB) does not run them at all.
+//
+// ACTIVE COORDINATES (egx_infill_set_active; CoEGO).  While an activity is set, egx_infill_eval, egx_infill_eval_cstr and the
+// optimisers' rounds go through eval_active: the compact rows are expanded on the host (infill_active.h), the call above runs
+// full width with the experts' x-gradient contractions restricted to the listed columns (launch_xgrad's column list: the pair
+// correlation once per pass of LISTED columns, +0.0 in the others), and the listed gradient columns are gathered on the host.
+// Nothing else of the sequence changes, and every other caller of eval_guarded launches what it launched before.
 #include "gmx_point.h"
 #include "infill_handle.h"
 
@@ -105,6 +111,8 @@ int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, const 
     const int n = gp->n, n_pad = gp->n_pad;
     const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
     const bool mean_only = !o.var, want_g = o.gmean != nullptr;
+    const int *cols = h->use_cols ? h->d_active.p : nullptr;  // active coordinates: the contractions' column list
+    const int ncols = h->use_cols ? (int)h->active.size() : 0;
     if (mean_only) flag = nullptr;
     // (xtypes: cast in the same launch; the expert that writes the flags leaves the cast raw tile for k_infill_mix as well)
     EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag, dev_spec(gp),
@@ -123,7 +131,7 @@ int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, const 
         EGX_RC(launch_infill_trend_mean(st, tr));
         if (!want_g) return EGX_SUCCESS;
         EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                            gp->d_gamma, 0, 1, nsplit, h->out_y.p));
+                            gp->d_gamma, 0, 1, nsplit, h->out_y.p, cols, ncols));
         return launch_infill_xgrad_finish_mean(st, tr, d, nsplit, h->out_y.p, dev_xnorm(gp) + d, o.gmean);
     }
     // rt = C^-1 r (held transposed), sum rt^2 and ft^T rt (:337-352)
@@ -139,9 +147,9 @@ int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, const 
     EGX_RC(posterior_weights(gp, st, h->RT.p, kTile, h->Wt.p));
     EGX_RC(posterior_weights_trend(gp, st, h->dneg.p, kTile, h->Wt.p));
     EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                        gp->d_gamma, 0, 1, nsplit, h->out_y.p));
+                        gp->d_gamma, 0, 1, nsplit, h->out_y.p, cols, ncols));
     EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                        h->Wt.p, kTile, 0, nsplit, h->out_v.p));
+                        h->Wt.p, kTile, 0, nsplit, h->out_v.p, cols, ncols));
     return launch_infill_xgrad_finish(st, tr, d, nsplit, h->out_y.p, h->out_v.p, dev_xnorm(gp) + d, o.gmean, o.gvar);
 }
 
@@ -157,13 +165,16 @@ int sgp_expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, co
     const int msplit = mean_splits(z_pad, kTile), nsplit = xgrad_splits(nz, kTile);
     const size_t blk = (size_t)kTile * z_pad;
     const bool mean_only = !o.var, want_g = o.gmean != nullptr;
+    const int *cols = h->use_cols ? h->d_active.p : nullptr;
+    const int ncols = h->use_cols ? (int)h->active.size() : 0;
     if (mean_only) flag = nullptr;
     EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, h->ident.p, h->xqT.p, flag));
     EGX_RC(launch_predict_mean(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->vec.p, h->racc.p, msplit));
     if (mean_only) {
         EGX_RC(launch_infill_sgp_finish(st, h->racc.p, msplit, nullptr, nullptr, g->sigma2, g->noise, 0, o.mean, nullptr));
         if (!want_g) return EGX_SUCCESS;
-        EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p));
+        EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p, cols,
+                            ncols));
         return launch_infill_sgp_xgrad_finish(st, h->out_y.p, nullptr, nsplit, d, nullptr, nullptr, g->sigma2, 0, 0.0, o.gmean, nullptr);
     }
     EGX_RC(launch_cross_corr(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, h->RT.p, z_pad));
@@ -178,9 +189,10 @@ int sgp_expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, co
     EGX_RC(launch_gemm_nt_sub(st, h->sE.p, z_pad, h->RT.p, z_pad, g->Wa.p, z_pad, kTile, z_pad, z_pad, 0, 0));
     EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * blk, st));
     EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, g->Wz.p, z_pad, h->sE.p, z_pad, z_pad, kTile, z_pad, 0, 1));
-    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p));
+    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p, cols,
+                        ncols));
     EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, h->Wt.p, kTile, 0, nsplit,
-                        h->out_v.p));
+                        h->out_v.p, cols, ncols));
     return launch_infill_sgp_xgrad_finish(st, h->out_y.p, h->out_v.p, nsplit, d, h->s0.p, h->s1.p, g->sigma2, vfe,
                                           (vfe ? -2.0 : 2.0) * g->sigma2, o.gmean, o.gvar);
 }
@@ -251,6 +263,11 @@ int ensure_device_state(egx_infill *h, hipStream_t st, const EvalPlan &p) {
         if (sg.k >= 2) EGX_RC(upload_once(sg.d_gmx, sg.on_device, sg.gmx.data(), sg.gmx.size(), st));
     if (k > 0 && !p.folded) EGX_RC(upload_once(h->d_scale, h->scale_on_device, h->scale_cstr.data(), (size_t)k, st));
     if (k > 0) EGX_RC(upload_once(h->d_tol, h->tol_on_device, h->tol.data(), (size_t)k, st));
+    if (h->use_cols && p.want_g && !h->active_on_device) {  // (h->active stays as it is until the next egx_infill_set_active)
+        EGX_RC(h->d_active.alloc(h->active.size()));
+        EGX_HIP_CHECK(hipMemcpyAsync(h->d_active.p, h->active.data(), sizeof(int) * h->active.size(), hipMemcpyHostToDevice, st));
+        h->active_on_device = true;
+    }
     return EGX_SUCCESS;
 }
 
@@ -606,6 +623,38 @@ int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, doub
     return rc ? settle_failed(h, rc) : rc;  // nothing may still run on the handle's buffers
 }
 
+int eval_active(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
+                const CstrOut *co) {
+    if (h->active.empty() || m <= 0 || !xq) return eval_guarded(h, xq, m, value, grad, parts, nullptr, co);
+    const int d = h->d;
+    const size_t mm = (size_t)m, nm = h->surr.size(), k = nm - 1;
+    h->act_x.resize(mm * d);
+    active::expand(xq, m, h->active, h->x_base, h->act_x.data());
+    // full-width stand-ins for what is width() wide in the caller's arrays
+    egx_infill_parts full{};
+    CstrOut cfull;
+    if (grad) h->act_g.resize(mm * d);
+    if (parts) {
+        full = *parts;
+        if (parts->grad_mean) h->act_gm.resize(nm * mm * d), full.grad_mean = h->act_gm.data();
+        if (parts->grad_var) h->act_gv.resize(nm * mm * d), full.grad_var = h->act_gv.data();
+    }
+    if (co) {
+        cfull = *co;
+        if (co->gcstr) h->act_gc.resize(mm * k * d + 1), cfull.gcstr = h->act_gc.data();
+    }
+    h->use_cols = true;
+    const int rc = eval_guarded(h, h->act_x.data(), m, value, grad ? h->act_g.data() : nullptr, parts ? &full : nullptr, nullptr,
+                                co ? &cfull : nullptr);
+    h->use_cols = false;
+    EGX_RC(rc);
+    if (grad) active::gather(h->act_g.data(), m, d, h->active, grad);
+    if (parts && parts->grad_mean) active::gather(h->act_gm.data(), (int64_t)(nm * mm), d, h->active, parts->grad_mean);
+    if (parts && parts->grad_var) active::gather(h->act_gv.data(), (int64_t)(nm * mm), d, h->active, parts->grad_var);
+    if (co && co->gcstr) active::gather(h->act_gc.data(), (int64_t)(mm * k), d, h->active, co->gcstr);
+    return EGX_SUCCESS;
+}
+
 }  // namespace egx
 
 extern "C" {
@@ -714,7 +763,7 @@ int32_t egx_infill_eval(egx_infill *h, const double *xq, int64_t m, double *valu
     if (!h || (m > 0 && !value)) return fail(EGX_ERR_INVALID_VALUE, "NULL argument");
     std::lock_guard<std::mutex> lock(h->mu);
     ModelLocks locks(h);
-    return eval_guarded(h, xq, m, value, grad, parts);
+    return eval_active(h, xq, m, value, grad, parts);
 }
 
 int32_t egx_infill_eval_cstr(egx_infill *h, const double *xq, int64_t m, double *value, double *cstr, double *grad,
@@ -727,7 +776,36 @@ int32_t egx_infill_eval_cstr(egx_infill *h, const double *xq, int64_t m, double 
     ModelLocks locks(h);
     CstrOut co;
     co.cstr = cstr, co.gcstr = grad_cstr;
-    return eval_guarded(h, xq, m, value, grad, nullptr, nullptr, &co);
+    return eval_active(h, xq, m, value, grad, nullptr, &co);
+}
+
+int32_t egx_infill_set_active(egx_infill *h, const int32_t *active, int32_t n_active, const double *x_base) {
+    if (!h) return fail(EGX_ERR_INVALID_VALUE, "NULL handle");
+    std::lock_guard<std::mutex> lock(h->mu);
+    std::string msg;
+    if (!active::check(active, n_active, x_base, h->d, msg)) return fail(EGX_ERR_INVALID_VALUE, msg);
+    h->active.assign(active, active + n_active);
+    h->x_base.assign(x_base, x_base + h->d);
+    h->active_on_device = false;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_clear_active(egx_infill *h) {
+    if (!h) return fail(EGX_ERR_INVALID_VALUE, "NULL handle");
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->active.clear();
+    h->x_base.clear();
+    h->active_on_device = false;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_get_active(egx_infill *h, int32_t *n_active, int32_t *active, double *x_base) {
+    if (!h || !n_active) return fail(EGX_ERR_INVALID_VALUE, "NULL argument");
+    std::lock_guard<std::mutex> lock(h->mu);
+    *n_active = (int32_t)h->active.size();
+    if (active) std::copy(h->active.begin(), h->active.end(), active);
+    if (x_base) std::copy(h->x_base.begin(), h->x_base.end(), x_base);
+    return EGX_SUCCESS;
 }
 
 int32_t egx_infill_eval_experts(egx_infill *h, int32_t j, const double *xq, int64_t m, double *mean, double *var, double *grad_mean,

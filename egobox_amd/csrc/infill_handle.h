@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sgp_handle.h"
+#include "infill_active.h"
 #include "infill_math.h"
 #include "pending_math.h"
 
@@ -115,6 +116,16 @@ struct egx_infill {
     std::vector<double> pend_x, pend_y;
     std::vector<egx::PendModel> pend;
     egx::DevBuf pc_c, pc_g;
+    // the active coordinates (egx_infill_set_active, infill_active.h): empty = none.  The entry points whose width becomes
+    // n_active expand their compact rows into act_x, evaluate full width with use_cols set -- the experts' x-gradient
+    // contractions then take the column list d_active -- and gather the listed gradient columns out of act_g / act_gm /
+    // act_gv / act_gc.  Every other caller of eval_guarded leaves use_cols clear and launches what it launched before.
+    std::vector<int> active;
+    std::vector<double> x_base;
+    egx::DevMem<int> d_active;
+    bool active_on_device = false, use_cols = false;
+    std::vector<double> act_x, act_g, act_gm, act_gv, act_gc;
+    int width() const { return active.empty() ? d : (int)active.size(); }  // of a trial point
 };
 
 namespace egx {
@@ -146,6 +157,10 @@ int check_specs(const egx_infill *h);
 // When it fails nothing runs on the handle's buffers any more.
 int eval_guarded(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
                  const ExpertDiag *diag = nullptr, const CstrOut *co = nullptr, PushCapture *cap = nullptr);
+// egx_infill_eval / _eval_cstr and the optimisers' rounds: eval_guarded, and while an activity is set the same call on the
+// expanded rows with the column-list contractions; xq, grad, the gradient fields of parts and co->gcstr are width() wide
+int eval_active(egx_infill *h, const double *xq, int64_t m, double *value, double *grad, const egx_infill_parts *parts,
+                const CstrOut *co = nullptr);
 // after a failed step on the handle's stream: wait for what was launched, clear the runtime's last error; returns rc
 int settle_failed(const egx_infill *h, int rc);
 

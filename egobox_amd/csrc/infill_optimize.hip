@@ -1,7 +1,9 @@
 // The lock-step multistarts of the infill criterion (crates/ego/src/solver/solver_infill_optim.rs:148-236) and the q-point batch
 // call on top of them.  Every start is one ask / tell machine (cobyla.h, slsqp.h); multistart.h advances all of them in
 // lock-step, and a round's points -- line-search trial points included -- are ONE evaluation of infill_eval.hip.  Each entry
-// point: validate, take the locks, build the machines, run the rounds around eval_guarded, pick the winner, fill the stats.
+// point: take the handle's lock, validate (the width of lo / hi / x_start is the activity's while one is set,
+// egx_infill_set_active), take the models' locks, build the machines, run the rounds around eval_active, pick the winner, fill
+// the stats.
 //
 // The three differ in these points ON PURPOSE (callers and tests observe them):
 //  1. egx_infill_optimize keeps its OWN best evaluated point per start (multistart::BestEvaluated) and does not take
@@ -29,13 +31,14 @@ using namespace egx;
 
 namespace {
 
-// the arguments the three entry points share; needs_c_best: a handle with constraints must be given c_best (checked here, before the lock)
+// the arguments the three entry points share; needs_c_best: a handle with constraints must be given c_best (checked here, before
+// anything else).  Called under the handle's lock: the width of lo / hi / x_start is the activity's while one is set
 int check_args(const egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start, const double *f_best,
                const double *x_best, const double *c_best, bool needs_c_best) {
     if (!h || !lo || !hi || !x_start || !f_best || !x_best || n_start < 1 || (needs_c_best && h->surr.size() > 1 && !c_best))
         return fail(EGX_ERR_INVALID_VALUE, "infill optimize: NULL argument or no start point");
     std::string msg;
-    if (!multistart::check_box_and_starts(lo, hi, x_start, n_start, h->d, msg)) return fail(EGX_ERR_INVALID_VALUE, msg);
+    if (!multistart::check_box_and_starts(lo, hi, x_start, n_start, h->width(), msg)) return fail(EGX_ERR_INVALID_VALUE, msg);
     return EGX_SUCCESS;
 }
 
@@ -79,9 +82,10 @@ extern "C" {
 
 int32_t egx_infill_optimize(egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start,
                             int64_t max_eval, double *f_best, double *x_best, egx_infill_stats *stats) {
-    EGX_RC(check_args(h, lo, hi, x_start, n_start, f_best, x_best, nullptr, false));
-    const int d = h->d;
+    if (!h) return fail(EGX_ERR_INVALID_VALUE, "infill optimize: NULL argument or no start point");
     std::lock_guard<std::mutex> lock(h->mu);
+    EGX_RC(check_args(h, lo, hi, x_start, n_start, f_best, x_best, nullptr, false));
+    const int d = h->width();  // the machines' dimension: n_active while an activity is set
     ModelLocks locks(h);
     max_eval = multistart::budget(max_eval, n_start, d);
     const std::vector<double> blo(lo, lo + d), bhi(hi, hi + d);
@@ -95,7 +99,7 @@ int32_t egx_infill_optimize(egx_infill *h, const double *lo, const double *hi, c
         mach,
         [&](const multistart::Round &r) {  // a round's trial points are ONE values-only evaluation
             vals.assign(r.size(), 0.0);
-            return eval_guarded(h, r.pts.data(), (int64_t)r.size(), vals.data(), nullptr, nullptr);
+            return eval_active(h, r.pts.data(), (int64_t)r.size(), vals.data(), nullptr, nullptr);
         },
         [&](const multistart::Round &r, size_t q, CobylaBox &m) {
             seen.told(r.who[q], vals[q], r.pts.data() + q * d);
@@ -118,9 +122,10 @@ int32_t egx_infill_optimize(egx_infill *h, const double *lo, const double *hi, c
 
 int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start,
                                  int64_t max_eval, double *f_best, double *x_best, double *c_best, egx_infill_cstr_stats *stats) {
-    EGX_RC(check_args(h, lo, hi, x_start, n_start, f_best, x_best, c_best, true));
-    const int d = h->d, k = (int)h->surr.size() - 1;
+    if (!h) return fail(EGX_ERR_INVALID_VALUE, "infill optimize: NULL argument or no start point");
     std::lock_guard<std::mutex> lock(h->mu);
+    EGX_RC(check_args(h, lo, hi, x_start, n_start, f_best, x_best, c_best, true));
+    const int d = h->width(), k = (int)h->surr.size() - 1;
     if (h->strategy == infill::kCstrInfill)  // difference 3
         return fail(EGX_ERR_INVALID_VALUE,
                     "infill optimize: the handle folds its constraints into the objective (EGX_CSTR_INFILL); use egx_infill_optimize");
@@ -140,7 +145,7 @@ int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo, const double *
             cvals.assign(r.size() * (size_t)k + 1, 0.0);  // difference 4
             CstrOut co;
             co.cstr = k > 0 ? cvals.data() : nullptr;
-            return eval_guarded(h, r.pts.data(), (int64_t)r.size(), vals.data(), nullptr, nullptr, nullptr, &co);
+            return eval_active(h, r.pts.data(), (int64_t)r.size(), vals.data(), nullptr, nullptr, &co);
         },
         [&](const multistart::Round &, size_t q, Cobyla &m) { m.tell(vals[q], cvals.data() + q * (size_t)k); }, rc);
     EGX_RC(rc);
@@ -150,9 +155,10 @@ int32_t egx_infill_optimize_cstr(egx_infill *h, const double *lo, const double *
 
 int32_t egx_infill_optimize_slsqp(egx_infill *h, const double *lo, const double *hi, const double *x_start, int64_t n_start,
                                   int64_t max_eval, double *f_best, double *x_best, double *c_best, egx_infill_slsqp_stats *stats) {
-    EGX_RC(check_args(h, lo, hi, x_start, n_start, f_best, x_best, nullptr, false));
-    const int d = h->d;
+    if (!h) return fail(EGX_ERR_INVALID_VALUE, "infill optimize: NULL argument or no start point");
     std::lock_guard<std::mutex> lock(h->mu);
+    EGX_RC(check_args(h, lo, hi, x_start, n_start, f_best, x_best, nullptr, false));
+    const int d = h->width();
     const bool folded = h->strategy == infill::kCstrInfill;  // difference 3: the machines see no constraint
     const int k = folded ? 0 : (int)h->surr.size() - 1;
     if (k > 0 && !c_best) return fail(EGX_ERR_INVALID_VALUE, "infill optimize: NULL argument or no start point");
@@ -172,10 +178,10 @@ int32_t egx_infill_optimize_slsqp(egx_infill *h, const double *lo, const double 
             grads.assign(m * d, 0.0);
             cvals.assign(m * (size_t)k + 1, 0.0);  // difference 4
             cgrads.assign(m * (size_t)k * d + 1, 0.0);
-            if (folded) return eval_guarded(h, r.pts.data(), (int64_t)m, vals.data(), grads.data(), nullptr);
+            if (folded) return eval_active(h, r.pts.data(), (int64_t)m, vals.data(), grads.data(), nullptr);
             CstrOut co;
             co.cstr = k > 0 ? cvals.data() : nullptr, co.gcstr = k > 0 ? cgrads.data() : nullptr;
-            return eval_guarded(h, r.pts.data(), (int64_t)m, vals.data(), grads.data(), nullptr, nullptr, &co);
+            return eval_active(h, r.pts.data(), (int64_t)m, vals.data(), grads.data(), nullptr, &co);
         },
         [&](const multistart::Round &, size_t q, Slsqp &m) {
             m.tell(vals[q], cvals.data() + q * (size_t)k, grads.data() + q * d, cgrads.data() + q * (size_t)k * d);
@@ -209,6 +215,11 @@ int32_t egx_infill_optimize_batch(egx_infill *h, const egx_infill_batch_config *
     if (q < 1 || q > EGX_INFILL_MAX_PENDING || cfg.strategy < EGX_QEI_KB || cfg.strategy > EGX_QEI_CL_MIN ||
         (cfg.optimizer != EGX_BATCH_COBYLA && cfg.optimizer != EGX_BATCH_SLSQP) || (cfg.scaling_points && cfg.n_scaling < 1))
         return fail(EGX_ERR_INVALID_VALUE, "infill batch: q must be 1 .. 16, the strategy an egx_qei_strategy, the optimizer COBYLA or SLSQP");
+    {  // a batch step pushes its full-width point: not under active coordinates
+        std::lock_guard<std::mutex> lock(h->mu);
+        if (!h->active.empty())
+            return fail(EGX_ERR_UNSUPPORTED, "infill batch: active coordinates are set (egx_infill_set_active); call egx_infill_clear_active first");
+    }
     const int d = h->d, nm = (int)h->surr.size();
     std::vector<double> cb((size_t)nm);
     // every step through the public entry points (each takes the handle's lock itself): the loop a caller would write

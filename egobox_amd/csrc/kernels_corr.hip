@@ -456,6 +456,70 @@ __global__ __launch_bounds__(kXgThreads) void k_xgrad(const double *__restrict__
 #undef EGX_XA
 }
 
+// COLUMN-LIST form of k_xgrad (an infill handle with active coordinates, egx_infill_set_active): out[a][c] for the ncols listed
+// columns c = cols[0 .. ncols) alone, DK of them per pass -- the pair correlation runs over all d coordinates once per DK LISTED
+// columns instead of once per DK columns of d.  Every unlisted column of the lane's d-wide row is written +0.0 (the lane owns
+// its row: the fill and the later stores of the listed columns are the same thread's, in program order), so whatever reads the
+// partial sums downstream sees defined values everywhere.  LDS layout, slab width, the split of the training range and the j
+// order are k_xgrad's: a listed column accumulates the same __builtin_fma sequence and has k_xgrad's bits
+// (tests/test_gpu_infill_active.py).  cols: distinct, in [0, d), in any order (checked on the host, infill_active.h).
+template <int CORR, int DK, bool VEC, bool XAG = false>
+__global__ __launch_bounds__(kXgThreads) void k_xgrad_cols(const double *__restrict__ xqT, int64_t ldq,
+                                                           const double *__restrict__ xT, int64_t ldx, int n, int d,
+                                                           const double *__restrict__ coef, int hcols,
+                                                           const double *__restrict__ Wt, int64_t ldw, int slabs_per_split,
+                                                           double *__restrict__ out, int m_pad, int js_shift,
+                                                           const int *__restrict__ cols, int ncols) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int jsh = XAG ? js_shift : 6, JS = 1 << jsh;
+    double *xa = sm;                                  // [d][kXgThreads]  (not with XAG)
+    double *xj = sm + (XAG ? 0 : d * kXgThreads);     // [d][JS]
+    double *cs = xj + d * JS;                         // [d * hcols]
+    const int tid = threadIdx.x;
+    const int a = blockIdx.x * kXgThreads + tid;
+    const double *xag = xqT + a;
+#define EGX_XA(k_) (XAG ? xag[(int64_t)(k_) * ldq] : xa[(k_) * kXgThreads + tid])
+    if (!XAG)
+        for (int k = 0; k < d; k++) xa[k * kXgThreads + tid] = xqT[(int64_t)k * ldq + a];
+    for (int e = tid; e < d * hcols; e += kXgThreads) cs[e] = coef[e];
+    const int j_lo = blockIdx.y * slabs_per_split * 64;
+    int j_hi = j_lo + slabs_per_split * 64;
+    if (j_hi > n) j_hi = n;
+    double *o = out + ((int64_t)blockIdx.y * m_pad + a) * d;
+    for (int k = 0; k < d; k++) o[k] = 0.0;
+    for (int c0 = 0; c0 < ncols; c0 += DK) {
+        double acc[DK], xr[DK];
+        int col[DK];
+#pragma unroll
+        for (int kk = 0; kk < DK; kk++) {
+            col[kk] = (c0 + kk < ncols) ? cols[c0 + kk] : 0;
+            acc[kk] = 0.0;
+            xr[kk] = (c0 + kk < ncols) ? EGX_XA(col[kk]) : 0.0;
+        }
+        for (int j0 = j_lo; j0 < j_hi; j0 += JS) {
+            __syncthreads();
+            for (int e = tid; e < d * JS; e += kXgThreads) xj[e] = xT[(int64_t)(e >> jsh) * ldx + j0 + (e & (JS - 1))];
+            __syncthreads();
+            const int jn = (j_hi - j0 < JS) ? (j_hi - j0) : JS;
+            for (int jj = 0; jj < jn; jj++) {
+                PairAcc<CORR> pa;
+                for (int k = 0; k < d; k++) pa.add(EGX_XA(k) - xj[k * JS + jj], cs + k * hcols, hcols);
+                const double wv = VEC ? Wt[j0 + jj] : Wt[(int64_t)(j0 + jj) * ldw + a];
+                const double rw = pa.value() * wv;
+#pragma unroll
+                for (int kk = 0; kk < DK; kk++)
+                    if (c0 + kk < ncols)
+                        acc[kk] = __builtin_fma(rw, xgrad_factor<CORR>(xr[kk] - xj[col[kk] * JS + jj],
+                                                                       cs + col[kk] * hcols, hcols), acc[kk]);
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < DK; kk++)
+            if (c0 + kk < ncols) o[col[kk]] = acc[kk];
+    }
+#undef EGX_XA
+}
+
 // Few-query form of the x-gradient contraction (single-point calls): the lanes run over TRAINING points instead of queries
 // (one pair per lane, no sequential pair loop), the d partial sums are reduced across the workgroup.
 //   out[(blockIdx.y * m + a) * d + k] = sum over the block's 256 training points of w_j d r(x_a, x_j) / d x_ak
@@ -1010,7 +1074,7 @@ int launch_predict_mean(hipStream_t s, int corr, const PosteriorBatch &pb, const
 // out: nsplit x m_pad x d partial sums (nsplit returned); Wt = gamma (vec != 0) or the (n x m_pad) weight matrix
 int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT, int64_t ldx,
                  int n, int d, const double *coef, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit,
-                 double *out) {
+                 double *out, const int *cols, int ncols) {
     const int slabs = (n + 63) / 64;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > slabs) nsplit = slabs;
@@ -1042,7 +1106,34 @@ int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_
         else EGX_XG1(C_, 32, false, true)                  \
     } else if (vec) EGX_XG1(C_, DK_, true, false)          \
     else EGX_XG1(C_, DK_, false, false)
-    if (d <= 8) {
+    // the column-list form (cols: ncols distinct device indices in [0, d)): its own kernel, its pass width by the LIST's length
+#define EGX_XGC1(C_, DK_, VEC_, XAG_)                                                                                        \
+    {                                                                                                                        \
+        if (lds > 65536)                                                                                                     \
+            EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xgrad_cols<C_, DK_, VEC_, XAG_>),            \
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
+        hipLaunchKernelGGL((k_xgrad_cols<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, xqT, ldq, xT, ldx, n, d,     \
+                           coef, hcols, Wt, ldw, per, out, m_pad, js_shift, cols, ncols);                                    \
+    }
+#define EGX_XGC(C_, DK_)                                   \
+    if (xag) {                                             \
+        if (vec) EGX_XGC1(C_, DK_, true, true)             \
+        else EGX_XGC1(C_, DK_, false, true)                \
+    } else if (vec) EGX_XGC1(C_, DK_, true, false)         \
+    else EGX_XGC1(C_, DK_, false, false)
+    if (cols) {
+        if (ncols < 1 || ncols > d) {
+            set_error("x-gradients: a column list of " + std::to_string(ncols) + " entries for " + std::to_string(d) + " inputs");
+            return EGX_ERR_INVALID_VALUE;
+        }
+        if (ncols <= 8) {
+            EGX_DISPATCH_CORR(corr, EGX_XGC(C_, 8));
+        } else if (ncols <= 16) {
+            EGX_DISPATCH_CORR(corr, EGX_XGC(C_, 16));
+        } else {
+            EGX_DISPATCH_CORR(corr, EGX_XGC(C_, 32));
+        }
+    } else if (d <= 8) {
         EGX_DISPATCH_CORR(corr, EGX_XG(C_, 8));
     } else if (d <= 16) {
         EGX_DISPATCH_CORR(corr, EGX_XG(C_, 16));
@@ -1051,6 +1142,8 @@ int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_
     }
 #undef EGX_XG1
 #undef EGX_XG
+#undef EGX_XGC1
+#undef EGX_XGC
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

@@ -8,7 +8,10 @@ Everything here is host orchestration: every O(n^3) and O(n^2 m) step runs in th
 named above.  The random stream is numpy's (`numpy.random.default_rng(seed)`), not the reference's Xoshiro256Plus: the same data
 and seed give the same answer here, not the reference's points.
 
-Not here (a clean `InvalidValueError`, or no argument at all): TREGO, CoEGO, function constraints (`subject_to` / `fcstrs`), the
+`Egor(coego_n_coop=k)` is CoEGO (solver/coego.rs): the coordinates are split into k random groups, theta is tuned and the
+criterion optimised over one group at a time, through the active coordinates of the infill handle (`InfillObjective.set_active`).
+
+Not here (a clean `InvalidValueError`, or no argument at all): TREGO, function constraints (`subject_to` / `fcstrs`), the
 sigma-weight portfolio, hot start / `outdir` / warm start files, `NbClusters::Auto` and its reclustering rule, sparse surrogates, a
 C++ mirror, and training objective and constraints as one lock-step group.
 """
@@ -36,6 +39,7 @@ EGO_DEFAULT_MAX_ITERS = 20       # egor_config.rs:171
 EGO_GP_OPTIM_N_START = 10        # egor_config.rs:13
 EGO_GP_OPTIM_MAX_EVAL = 50       # egor_config.rs:15
 DUPLICATE_L1 = 100.0 * np.finfo(np.float64).eps  # utils/misc.rs:49
+GMM_MAX_DIM = 36                 # the widest training row [x, y] the mixture's training takes (egx_gmm_fit)
 
 _CRITERIA = {"ei": EI, "log_ei": LOG_EI, "logei": LOG_EI, "wb2": WB2, "wb2s": WB2S}
 _OPTIMIZERS = ("slsqp", "cobyla")
@@ -202,6 +206,32 @@ def theta_bounds(bounds, dim, corr_spec):
     return [(float(1.0 / lmax), float(1.0 / lmin))]
 
 
+# ---- CoEGO: cooperative groups of coordinates (solver/coego.rs) ---------------------------------------------------------------
+def random_activity(nx, n_coop, rng):
+    """get_random_activity (coego.rs:55-84): a (g_nb, g_size) integer array holding a shuffled 0 .. nx - 1, one row per group,
+    g_nb = min(n_coop, nx).  When g_nb does not divide nx the rows are one longer than nx // g_nb and the last column of the
+    rows from nx % g_nb on holds the marker nx, which `strip` removes."""
+    nx = int(nx)
+    g_nb = min(int(n_coop), nx)
+    if g_nb < 1:
+        raise _invalid(f"random_activity: n_coop >= 1 and nx >= 1 expected, got {n_coop} and {nx}")
+    idx = rng.permutation(nx).astype(np.int64)
+    remainder = nx % g_nb
+    if remainder == 0:
+        return idx.reshape(g_nb, nx // g_nb)
+    g_size = nx // g_nb + 1
+    cut = g_nb * (g_size - 1)
+    out = np.full((g_nb, g_size), nx, dtype=np.int64)
+    out[:, :g_size - 1] = idx[:cut].reshape(g_nb, g_size - 1)
+    out[:remainder, g_size - 1] = idx[cut:]
+    return out
+
+
+def strip(active, dim):
+    """The indices of an activity row below dim, in order: without the marker of an incomplete row (coego.rs:134-136)."""
+    return [int(i) for i in active if int(i) < int(dim)]
+
+
 # ---- configuration -----------------------------------------------------------------------------------------------------------
 class GpConfig:
     """The surrogates' configuration (egor_config.rs:19-53, python/src/gp_config.rs): constant trend, squared exponential kernel,
@@ -233,6 +263,14 @@ class GpConfig:
         return self
 
 
+def _one_cluster(xt):
+    """The one-cluster mixture of the rows xt in closed form: their mean and covariance (what EM converges to for one cluster, with
+    its 1e-6 on the diagonal).  The responsibilities of one cluster are ones and nothing reads more of it."""
+    from .moe import GaussianMixture
+    cov = np.atleast_2d(np.cov(xt.T, bias=True)) + 1e-6 * np.eye(xt.shape[1])
+    return GaussianMixture([1.0], xt.mean(axis=0, keepdims=True), cov[None, :, :])
+
+
 def _close_model(model):
     """Give a surrogate's device handles back (a `GpMixture` or a `MixintGpMixture`; closing twice is harmless)."""
     for e in getattr(model, "moe", model).experts:
@@ -254,7 +292,7 @@ class Egor:
                  infill_strategy=LOG_EI, cstr_infill=False, cstr_strategy="mean", q_points=1, q_infill_strategy=QEiStrategy.KB,
                  q_optmod=1, infill_optimizer="slsqp", target=-sys.float_info.max, seed=None,
                  trego=False, coego_n_coop=0, outdir=None, warm_start=False, hot_start=None):
-        for name, on in (("trego", trego), ("coego_n_coop", coego_n_coop), ("outdir", outdir is not None),
+        for name, on in (("trego", trego), ("outdir", outdir is not None),
                          ("warm_start", warm_start), ("hot_start", hot_start is not None)):
             if on:
                 raise _invalid(f"{name} is not implemented")
@@ -264,6 +302,18 @@ class Egor:
         if not isinstance(self.gp_config, GpConfig):
             raise _invalid(f"gp_config must be a GpConfig, got {type(gp_config).__name__}")
         self.gp_config.check()
+        # CoEGO: 0 is off; the groups split the columns of the (unfolded) continuous space, as the reference's xlimits.nrows().
+        # The reference clamps n_coop with min(n_coop, nx) (coego.rs:57); a larger value is refused here.
+        if isinstance(coego_n_coop, bool) or not isinstance(coego_n_coop, (int, np.integer)) or coego_n_coop < 0:
+            raise _invalid(f"coego_n_coop must be a number >= 0, got {coego_n_coop!r}")
+        self.coego_n_coop = int(coego_n_coop)
+        if self.coego_n_coop > self.xlimits.shape[0]:
+            raise _invalid(f"coego_n_coop ({self.coego_n_coop}) exceeds the {self.xlimits.shape[0]} columns of the design space")
+        if self.coego_n_coop and self.gp_config.kpls_dim is not None:
+            raise _invalid("coego_n_coop and gp_config.kpls_dim exclude each other (egor_config.rs:458-462)")
+        if self.coego_n_coop and int(self.gp_config.n_clusters) != 1:
+            raise _invalid("coego_n_coop needs gp_config.n_clusters = 1: theta is updated group by group in the mono-cluster case "
+                           "only (solver_impl.rs:251-291)")
         self.n_cstr = int(n_cstr)
         if self.n_cstr < 0:
             raise _invalid(f"n_cstr must not be negative, got {n_cstr}")
@@ -308,6 +358,8 @@ class Egor:
         #: how many proposed rows the last `minimize` rejected as duplicates, and how many iterations it ran
         self.n_rejected_ = 0
         self.n_iter_ = 0
+        #: CoEGO: the last infill step's cooperation, one (active columns, xcoop after the group's optimisation) per group
+        self.last_coego_ = []
 
     # ---- spaces --------------------------------------------------------------------------------------------------------------
     def _unfold(self, x):
@@ -338,8 +390,11 @@ class Egor:
         return self._y(fun(x), x.shape[0])
 
     # ---- surrogates ----------------------------------------------------------------------------------------------------------
-    def _make_surrogate(self, xt, yt, make_clustering, optimize_theta, clustering, theta_inits):
-        """make_clustered_surrogate (solver_impl.rs:121-295) without CoEGO: (model, its experts' thetas (k, dim))."""
+    def _make_surrogate(self, xt, yt, make_clustering, optimize_theta, clustering, theta_inits, actives=None):
+        """make_clustered_surrogate (solver_impl.rs:121-295): (model, its experts' thetas (k, dim)).  With CoEGO's `actives`
+        (solver_impl.rs:162-295, COEGO_IMPROVEMENT_CHECK = false) a tuned theta is tuned group by group: one fit per group with
+        ThetaTuning.Partial on the group's components, each from the thetas of the fit before, the last model kept.  A step
+        that reuses theta (Fixed) fits ONCE: the reference refits identically per group."""
         from .moe import GpMixtureParams
         cfg = self.gp_config
         dim = int(cfg.kpls_dim) if cfg.kpls_dim is not None else xt.shape[1]
@@ -349,6 +404,10 @@ class Egor:
                 raise _invalid(f"gp_config.theta_init must hold 1 or {dim} values, got {init.size}")
             theta_inits = np.tile(np.broadcast_to(init, (dim,)), (int(cfg.n_clusters), 1))
         bounds = theta_bounds(cfg.theta_bounds, dim, cfg.corr_spec)
+        # one cluster on rows wider than the mixture's training takes (high dimension is CoEGO's ground): the closed form
+        fit_gmx = make_clustering
+        if make_clustering and int(cfg.n_clusters) == 1 and xt.shape[1] + 1 > GMM_MAX_DIM:
+            clustering, fit_gmx = _one_cluster(xt), False
         params = GpMixtureParams().n_clusters(int(cfg.n_clusters)) \
             .recombination(cfg.recombination, 1.0 if cfg.recombination == "smooth" else None) \
             .expert_specs(cfg.regr_spec, cfg.corr_spec).kpls_dim(cfg.kpls_dim).n_start(cfg.n_start).max_eval(cfg.max_eval)
@@ -356,36 +415,79 @@ class Egor:
             tunings = [ThetaTuning.Full(t, bounds) for t in theta_inits]
         else:
             tunings = [ThetaTuning.Fixed(t) for t in theta_inits]
+        if actives is not None and (make_clustering or optimize_theta):
+            model = None
+            for active in actives:
+                params.theta_tunings([ThetaTuning.Partial(t, bounds, strip(active, dim)) for t in theta_inits])
+                if not (fit_gmx and model is None):
+                    params.gmx(clustering)  # (one cluster: the first group's mixture serves the groups after it)
+                builder = params if self.xtypes is None else mixint.MixintGpMixtureParams(self.xtypes, params)
+                new = builder.fit(xt, yt)
+                if model is not None:
+                    _close_model(model)
+                model = new
+                clustering = getattr(model, "moe", model).gmx
+                theta_inits = np.stack([np.asarray(e.theta(), dtype=np.float64) for e in _experts(model)])
+            return model, theta_inits
         params.theta_tunings(tunings)
-        if not make_clustering:
+        if not fit_gmx:
             params.gmx(clustering)
         builder = params if self.xtypes is None else mixint.MixintGpMixtureParams(self.xtypes, params)
         model = builder.fit(xt, yt)
         return model, np.stack([np.asarray(e.theta(), dtype=np.float64) for e in _experts(model)])
 
     # ---- one EGO step --------------------------------------------------------------------------------------------------------
-    def _multistart(self, x_data, rng):
+    def _multistart(self, x_data, rng, active=None):
         """MiddlePickerMultiStarter (solver_computations.rs:53-114): midpoints of a random tenth of the training rows (at least
-        two), completed from a Maximin LHS of at least three rows."""
+        two), completed from a Maximin LHS of at least three rows.  `active` (CoEGO): training rows and limits restricted to
+        those columns (:65-66, 86)."""
         nt = x_data.shape[0]
         pick = rng.permutation(nt)[:max(nt // 10, 2)]
-        mid = start_points(x_data[pick], self.xlimits[:, 0], self.xlimits[:, 1], self.n_start)
+        xt, lim = (x_data[pick], self.xlimits) if active is None else (x_data[pick][:, active], self.xlimits[active])
+        mid = start_points(xt, lim[:, 0], lim[:, 1], self.n_start)
         missing = self.n_start - mid.shape[0]
         if missing <= 0:
             return mid
-        extra = Lhs(self.xlimits, "maximin", rng).sample(max(missing, 3))[:missing]
+        extra = Lhs(lim, "maximin", rng).sample(max(missing, 3))[:missing]
         return np.vstack([mid, extra])
 
-    def _optimize(self, obj, x_start):
+    def _optimize(self, obj, x_start, xlimits=None):
         """One multistart with the configured optimiser: (f, x, finite)."""
+        xlimits = self.xlimits if xlimits is None else xlimits
         max_eval = min(10 * x_start.size, INFILL_MAX_EVAL_DEFAULT)  # solver_infill_optim.rs:224
         if self.infill_optimizer == "slsqp":
-            x, f, _c, st = obj.optimize_slsqp(self.xlimits, x_start, max_eval)
+            x, f, _c, st = obj.optimize_slsqp(xlimits, x_start, max_eval)
         elif self.cstr_infill or self.n_cstr == 0:
-            f, x, st = obj.optimize(self.xlimits, x_start, max_eval)
+            f, x, st = obj.optimize(xlimits, x_start, max_eval)
         else:
-            x, f, _c, st = obj.optimize_constrained(self.xlimits, x_start, max_eval)
+            x, f, _c, st = obj.optimize_constrained(xlimits, x_start, max_eval)
         return f, x, bool(st["finite"]) and bool(np.isfinite(f))
+
+    def _coego_optimize(self, obj, x_data, best_index, actives, ms_rng):
+        """The cooperative infill step (solver_infill_optim.rs:67-271, COEGO_IMPROVEMENT_CHECK = false): from xcoop = the current
+        best row, group by group: the criterion over the group's columns with the others at xcoop, up to N_MAX_OPTIM multistarts,
+        the optimum written into xcoop.  Returns ((f of the last group that succeeded, xcoop) or None, seconds optimising)."""
+        d = self.xlimits.shape[0]
+        xcoop = x_data[best_index].copy()
+        found, t_opt = None, 0.0
+        self.last_coego_ = []
+        try:
+            for row in actives:
+                active = strip(row, d)
+                obj.set_active(active, xcoop)
+                for _attempt in range(N_MAX_OPTIM):
+                    x_start = self._multistart(x_data, ms_rng, active)
+                    to = time.perf_counter()
+                    f, x, ok = self._optimize(obj, x_start, self.xlimits[active])
+                    t_opt += time.perf_counter() - to
+                    if ok:
+                        xcoop[active] = x
+                        found = (f, xcoop)
+                        break
+                self.last_coego_.append((np.asarray(active, dtype=np.int64), xcoop.copy()))
+        finally:
+            obj.clear_active()
+        return (None if found is None else (found[0], xcoop.copy())), t_opt
 
     def _virtual_point(self, xk, y_data, models):
         """compute_virtual_point (solver_computations.rs:261-292), from the models' own predictions."""
@@ -398,11 +500,12 @@ class Egor:
             pred += conf * float(np.sqrt(models[0].predict_var(x)[0]))
         return np.array([pred] + [float(m.predict(x)[0]) for m in models[1:]])
 
-    def select_next_points(self, init, iteration, clusterings, theta_inits, x_data, y_data, best_index, rng):
+    def select_next_points(self, init, iteration, clusterings, theta_inits, x_data, y_data, best_index, rng, actives=None):
         """select_next_points (solver_impl.rs:562-800) without the portfolio: q_points rows of the continuous space with their
         virtual outputs, and the criterion's value at the last of them.  `clusterings` / `theta_inits` (lists of 1 + n_cstr,
         None at first) are updated in place: the mixtures of the first fit are reused, every expert's theta starts the next
-        fit.  Returns (x_dat (q, d), y_dat (q, 1 + n_cstr), infill_value)."""
+        fit.  `actives`: CoEGO's activity (`random_activity`), or None.  Returns (x_dat (q, d), y_dat (q, 1 + n_cstr),
+        infill_value)."""
         d = self.xlimits.shape[0]
         x_dat, y_dat = np.zeros((0, d)), np.zeros((0, 1 + self.n_cstr))
         infill_value = float("inf")
@@ -418,7 +521,7 @@ class Egor:
                 try:
                     for k in range(1 + self.n_cstr):  # one after the other
                         model, thetas = self._make_surrogate(xt, yt[:, k], make_clustering, optimize_theta, clusterings[k],
-                                                             theta_inits[k])
+                                                             theta_inits[k], actives)
                         new.append(model)
                         clusterings[k], theta_inits[k] = getattr(model, "moe", model).gmx, thetas
                 finally:
@@ -438,7 +541,9 @@ class Egor:
                     t2 = time.perf_counter()
                     ms_rng = np.random.default_rng(int(rng.integers(2 ** 63)))
                     found, t_opt = None, 0.0
-                    for _attempt in range(N_MAX_OPTIM):
+                    if actives is not None:  # CoEGO: group by group, each with its own attempts
+                        found, t_opt = self._coego_optimize(obj, x_data, best_index, actives, ms_rng)
+                    for _attempt in range(0 if actives is not None else N_MAX_OPTIM):
                         x_start = self._multistart(x_data, ms_rng)
                         to = time.perf_counter()
                         f, x, ok = self._optimize(obj, x_start)
@@ -474,7 +579,8 @@ class Egor:
         rng = np.random.default_rng(self.seed)
         best_index = find_best_result_index(y_data, None, self.cstr_tol)
         nm = 1 + self.n_cstr
-        x_dat, _, _ = self.select_next_points(True, 0, [None] * nm, [None] * nm, x_data, y_data, best_index, rng)
+        actives = random_activity(self.xlimits.shape[0], self.coego_n_coop, rng) if self.coego_n_coop else None
+        x_dat, _, _ = self.select_next_points(True, 0, [None] * nm, [None] * nm, x_data, y_data, best_index, rng, actives)
         return self._fold(x_dat)
 
     def get_result_index(self, x_doe=None, y_doe=None):
@@ -512,12 +618,15 @@ class Egor:
         best_index = find_best_result_index(y_data, None, self.cstr_tol)
         retries = MAX_POINT_ADDITION_RETRY
         self.n_rejected_, self.n_iter_ = 0, 0
+        # CoEGO: an activity drawn before the first iteration and again after every iteration (egor_solver.rs:251-256, 372-378)
+        actives = random_activity(self.xlimits.shape[0], self.coego_n_coop, rng) if self.coego_n_coop else None
         for it in range(int(max_iters)):
             if y_data[best_index, 0] <= self.target:
                 break
             converged = False
             while True:
-                x_dat, y_dat, _ = self.select_next_points(it == 0, it, clusterings, theta_inits, x_data, y_data, best_index, rng)
+                x_dat, y_dat, _ = self.select_next_points(it == 0, it, clusterings, theta_inits, x_data, y_data, best_index, rng,
+                                                          actives)
                 n_before = x_data.shape[0]
                 x_data, y_data, _, added = update_data(x_data, y_data, None, x_dat, y_dat, None)
                 self.n_rejected_ += x_dat.shape[0] - len(added)
@@ -533,4 +642,6 @@ class Egor:
             y_data[n_before:] = self._eval(fun, x_data[n_before:])
             best_index = find_best_result_index_from(best_index, n_before, y_data, None, self.cstr_tol)
             self.n_iter_ = it + 1
+            if self.coego_n_coop:
+                actives = random_activity(self.xlimits.shape[0], self.coego_n_coop, rng)
         return OptimResult(self._fold(x_data[best_index:best_index + 1])[0], y_data[best_index].copy(), self._fold(x_data), y_data)

@@ -158,6 +158,7 @@ class InfillObjective:
             L.check(lib.egx_infill_create(C.byref(cfg), self._models[0]._h, arr if k else None, L.dptr(tols) if k else None, k,
                                           C.byref(self._h)))
         self.d, self.n_cstr, self.criterion = self._models[0].d, k, int(criterion)
+        self._active = None  # (indices, x_base) while active coordinates are set
 
     # ---- parameters ----------------------------------------------------------------------------------------------------
     @property
@@ -175,18 +176,64 @@ class InfillObjective:
         L.check(self._lib.egx_infill_set_params(self._h, float(p["fmin"]), float(p["sigma_weight"]), float(p["scale_ic"]),
                                                 float(p["scale"]), int(bool(p["feasibility"]))))
 
+    # ---- active coordinates (CoEGO) -------------------------------------------------------------------------------------
+    def set_active(self, active, x_base):
+        """Optimise over the columns `active` (distinct indices in [0, d), any order) with the others held at x_base (d,)
+        (egx_infill_set_active): from now on `value`, `value_and_grad`, `parts`, `constraints` take (m, n_active) rows -- value j
+        of a row stands for column active[j] -- and return n_active-wide gradients, the three `optimize*` take (n_active, 2)
+        limits and (n_start, n_active) starts.  Values and the listed gradient columns are bit for bit the full-width ones.
+        `scaling`, `expert_parts` and the pending-point calls stay d wide; `optimize_batch` is refused."""
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(active)))
+        if idx.size == 0:  # (an empty list has no integer type of its own; the library refuses n_active = 0)
+            idx = idx.astype(np.int32)
+        if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: active must be a list of column indices, got {active!r}")
+        if idx.size and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, "infill: active holds an index outside the int32 range")
+        idx = idx.astype(np.int32)
+        xb = L.as_f64(np.atleast_1d(np.asarray(x_base, dtype=np.float64)), 1)
+        if xb.shape[0] != self.d:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: x_base must be ({self.d},), got {xb.shape}")
+        L.check(self._lib.egx_infill_set_active(self._h, idx.ctypes.data_as(L.c_int32_p), idx.shape[0], L.dptr(xb)))
+        self._active = (idx.astype(np.int64), xb.copy())
+
+    def clear_active(self):
+        """Back to full-width points: every call returns the bits it returned before `set_active`."""
+        L.check(self._lib.egx_infill_clear_active(self._h))
+        self._active = None
+
+    @property
+    def active(self):
+        """None, or (indices (n_active,), x_base (d,)) as the handle holds them (egx_infill_get_active)."""
+        n = C.c_int32()
+        idx, xb = np.zeros(self.d, dtype=np.int32), np.zeros(self.d)
+        L.check(self._lib.egx_infill_get_active(self._h, C.byref(n), idx.ctypes.data_as(L.c_int32_p), L.dptr(xb)))
+        return None if n.value == 0 else (idx[:n.value].astype(np.int64), xb)
+
+    @property
+    def width(self):
+        """Columns of a trial point, a limit, a gradient row: n_active while an activity is set, else d."""
+        return self.d if self._active is None else int(self._active[0].shape[0])
+
     # ---- evaluation ----------------------------------------------------------------------------------------------------
-    def _points(self, x):
+    def _points(self, x, d=None):
+        d = self.d if d is None else d
         x = L.as_f64(x)
         if x.ndim == 1:
-            x = x.reshape(1, -1) if self.d > 1 or x.shape[0] == 1 else x.reshape(-1, 1)
-        if x.ndim != 2 or x.shape[1] != self.d:
-            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: points must be (m, {self.d}), got {x.shape}")
+            x = x.reshape(1, -1) if d > 1 or x.shape[0] == 1 else x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[1] != d:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: points must be (m, {d}), got {x.shape}")
         return np.ascontiguousarray(x)
 
+    def _limits(self, xlimits):
+        lim = L.as_f64(xlimits, 2)
+        if lim.shape != (self.width, 2):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.width}, 2), got {lim.shape}")
+        return np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+
     def _eval(self, x, want_grad, want_parts):
-        x = self._points(x)
-        m, d, nm = x.shape[0], self.d, 1 + self.n_cstr
+        x = self._points(x, self.width)
+        m, d, nm = x.shape[0], self.width, 1 + self.n_cstr
         value = np.empty(m)
         grad = np.empty((m, d)) if want_grad else None
         parts, pstruct = None, None
@@ -239,13 +286,10 @@ class InfillObjective:
     def optimize(self, xlimits, x_start, max_eval=None):
         """The bound-constrained multistart (solver_infill_optim.rs:148-236): one COBYLA per row of x_start (n_start, d) inside
         xlimits (d, 2), all starts in lock-step.  Returns (f, x, stats); f = +inf when no start ended at a finite value."""
-        lim = L.as_f64(xlimits, 2)
-        if lim.shape != (self.d, 2):
-            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
-        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
-        xs = self._points(x_start)
+        lo, hi = self._limits(xlimits)
+        xs = self._points(x_start, self.width)
         n_start = xs.shape[0]
-        f, xb = C.c_double(), np.empty(self.d)
+        f, xb = C.c_double(), np.empty(self.width)
         evals = np.zeros(n_start, dtype=np.int64)
         st = L.InfillStats(0, 0, evals.ctypes.data_as(L.c_int64_p))
         rc = self._lib.egx_infill_optimize(self._h, L.dptr(lo), L.dptr(hi), L.dptr(xs), n_start,
@@ -281,8 +325,8 @@ class InfillObjective:
     def constraints(self, x, grad=False):
         """What the optimiser sees under "mean" / "utb" (egx_infill_eval_cstr): (value (m,), cstr (m, n_cstr)), with grad=True
         also (grad (m, d), grad_cstr (m, n_cstr, d)).  c <= 0 is feasible."""
-        x = self._points(x)
-        m, d, k = x.shape[0], self.d, self.n_cstr
+        x = self._points(x, self.width)
+        m, d, k = x.shape[0], self.width, self.n_cstr
         value, cstr = np.empty(m), np.empty((m, k))
         g = np.empty((m, d)) if grad else None
         gc = np.empty((m, k, d)) if grad else None
@@ -296,13 +340,10 @@ class InfillObjective:
         general-constraint COBYLA per row of x_start inside xlimits (d, 2), all starts in lock-step.  Returns (x, f, c, stats):
         the best evaluated point -- feasible before infeasible, then the smaller objective, or the smaller violation --, the
         objective and the constraint values there, and a dict of evals, rounds, best_start, feasible, violation, finite."""
-        lim = L.as_f64(xlimits, 2)
-        if lim.shape != (self.d, 2):
-            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
-        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
-        xs = self._points(x_start)
+        lo, hi = self._limits(xlimits)
+        xs = self._points(x_start, self.width)
         n_start = xs.shape[0]
-        f, xb, cb = C.c_double(), np.empty(self.d), np.empty(max(self.n_cstr, 1))
+        f, xb, cb = C.c_double(), np.empty(self.width), np.empty(max(self.n_cstr, 1))
         evals = np.zeros(n_start, dtype=np.int64)
         st = L.InfillCstrStats(0, 0, 0, 0.0, evals.ctypes.data_as(L.c_int64_p))
         rc = self._lib.egx_infill_optimize_cstr(self._h, L.dptr(lo), L.dptr(hi), L.dptr(xs), n_start,
@@ -320,14 +361,11 @@ class InfillObjective:
         strategy: under "infill" (or without constraint models) a bound-constrained run and c is empty; under "mean" / "utb"
         subject to c_j <= cstr_tol_j / scale_cstr_j.  Returns (x, f, c, stats) as optimize_constrained, stats with `stop` beside:
         per start 1 budget, 2 converged, 3 line search could not move, 4 no finite value at the start, 5 inconsistent."""
-        lim = L.as_f64(xlimits, 2)
-        if lim.shape != (self.d, 2):
-            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"infill: xlimits must be ({self.d}, 2), got {lim.shape}")
-        lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
-        xs = self._points(x_start)
+        lo, hi = self._limits(xlimits)
+        xs = self._points(x_start, self.width)
         n_start = xs.shape[0]
         k = 0 if self.cstr_strategy()[0] == "infill" else self.n_cstr
-        f, xb, cb = C.c_double(), np.empty(self.d), np.empty(max(self.n_cstr, 1))
+        f, xb, cb = C.c_double(), np.empty(self.width), np.empty(max(self.n_cstr, 1))
         evals = np.zeros(n_start, dtype=np.int64)
         stop = np.zeros(n_start, dtype=np.int32)
         st = L.InfillSlsqpStats(0, 0, 0, 0.0, evals.ctypes.data_as(L.c_int64_p), stop.ctypes.data_as(L.c_int32_p))

@@ -942,6 +942,30 @@ int32_t egx_infill_optimize_batch(egx_infill *h, const egx_infill_batch_config *
                                   const double *x_start /*q*n_start*d*/, int64_t n_start, int32_t q, double *x_out /*q*d*/,
                                   double *y_virtual /*q*(1+n_cstr)*/, double *f_out /*q*/, int32_t *n_found);
 
+/* ---- ACTIVE COORDINATES on the infill handle (CoEGO, crates/ego/src/solver/coego.rs, solver_infill_optim.rs:67-271) ---------
+ * CoEGO optimises the criterion over one group of coordinates at a time, the others held at the current best point.  While an
+ * activity is set a trial point is a COMPACT row of n_active values: value j of the row replaces x_base[active[j]], every other
+ * column is x_base's.  `active`: n_active DISTINCT column indices in [0, d), 1 <= n_active <= d, in any order (CoEGO's groups
+ * are shuffled); x_base: d finite values.  Anything else: EGX_ERR_INVALID_VALUE naming the offending entry, before the device is
+ * touched, and the handle keeps what it had.  On a handle with xtypes the indices count the unfolded columns and x_base is a raw
+ * unfolded row: the cast happens where it happens without an activity.
+ * Width n_active instead of d while an activity is set:
+ *   egx_infill_eval           xq, grad, parts->grad_mean / grad_var
+ *   egx_infill_eval_cstr      xq, grad, grad_cstr
+ *   egx_infill_optimize, _optimize_cstr, _optimize_slsqp    lo, hi, x_start, x_best; the machines run in n_active dimensions
+ *                             and the default budget is min(10 n_start n_active, 2000)
+ * Width d as ever, the activity is not read: egx_infill_scaling, _eval_experts, _push_pending, _get_pending, _virtual_point.
+ * egx_infill_optimize_batch returns EGX_ERR_UNSUPPORTED while an activity is set.
+ * The value of a compact point is bit for bit the full-width call's at the expanded row, its gradient bit for bit that call's
+ * columns active[0 .. n_active) -- on every kind of handle (lone dense models, mixtures, sparse experts, typed models, pending
+ * points); a non-finite value in a compact row gives +inf and a zero gradient for that point only.  Rows are expanded and
+ * columns gathered on the host (csrc/infill_active.h); the experts' x-gradient contractions compute the listed columns alone
+ * (k_xgrad_cols, csrc/kernels_corr.hip).  Without an activity every entry point returns the bits it returned before. */
+int32_t egx_infill_set_active(egx_infill *h, const int32_t *active /*n_active*/, int32_t n_active, const double *x_base /*d*/);
+int32_t egx_infill_clear_active(egx_infill *h);
+/* *n_active (0: no activity); optionally the indices and the base point (each d long at most, or NULL) */
+int32_t egx_infill_get_active(egx_infill *h, int32_t *n_active, int32_t *active /*d, or NULL*/, double *x_base /*d, or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

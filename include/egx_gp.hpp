@@ -742,7 +742,7 @@ class InfillObjective {
     }
     // ... and eval_grad_infill_obj_with_cstrs: (m) values, (m x d) gradients
     std::pair<std::vector<double>, std::vector<double>> value_and_grad(const double *x, int64_t m) const {
-        std::vector<double> v((size_t)m), g((size_t)(m * d_));
+        std::vector<double> v((size_t)m), g((size_t)(m * width()));
         check(egx_infill_eval(h_.get(), x, m, v.data(), g.data(), nullptr));
         return {std::move(v), std::move(g)};
     }
@@ -769,7 +769,7 @@ class InfillObjective {
     };
     Optimum optimize(const double *lo, const double *hi, const double *x_start, int64_t n_start, int64_t max_eval = 0) {
         Optimum o;
-        o.x.assign((size_t)d_, 0.0);
+        o.x.assign((size_t)width(), 0.0);
         o.evals.assign((size_t)n_start, 0);
         egx_infill_stats st{0, 0, o.evals.data()};
         const int32_t rc = egx_infill_optimize(h_.get(), lo, hi, x_start, n_start, max_eval, &o.f, o.x.data(), &st);
@@ -797,7 +797,7 @@ class InfillObjective {
     };
     Constraints constraints(const double *x, int64_t m, bool grad = false) const {
         Constraints c;
-        const size_t mm = (size_t)m, k = (size_t)k_, d = (size_t)d_;
+        const size_t mm = (size_t)m, k = (size_t)k_, d = (size_t)width();
         c.value.resize(mm), c.cstr.resize(mm * k + 1);
         if (grad) c.grad.resize(mm * d), c.grad_cstr.resize(mm * k * d + 1);
         check(egx_infill_eval_cstr(h_.get(), x, m, c.value.data(), c.cstr.data(), grad ? c.grad.data() : nullptr,
@@ -816,7 +816,7 @@ class InfillObjective {
     ConstrainedOptimum optimize_constrained(const double *lo, const double *hi, const double *x_start, int64_t n_start,
                                             int64_t max_eval = 0) {
         ConstrainedOptimum o;
-        o.x.assign((size_t)d_, 0.0);
+        o.x.assign((size_t)width(), 0.0);
         o.c.assign((size_t)k_ + 1, 0.0);
         o.evals.assign((size_t)n_start, 0);
         egx_infill_cstr_stats st{0, 0, 0, 0.0, o.evals.data()};
@@ -834,7 +834,7 @@ class InfillObjective {
     };
     SlsqpOptimum optimize_slsqp(const double *lo, const double *hi, const double *x_start, int64_t n_start, int64_t max_eval = 0) {
         SlsqpOptimum o;
-        o.x.assign((size_t)d_, 0.0);
+        o.x.assign((size_t)width(), 0.0);
         o.c.assign((size_t)k_ + 1, 0.0);
         o.evals.assign((size_t)n_start, 0);
         o.stop.assign((size_t)n_start, 0);
@@ -884,6 +884,32 @@ class InfillObjective {
         b.x.resize((size_t)b.n_found * (size_t)d_), b.y_virtual.resize((size_t)b.n_found * nm), b.f.resize((size_t)b.n_found);
         return b;
     }
+    // ---- active coordinates (CoEGO): while set, points, limits and gradients above are n_active wide (egx_infill_set_active);
+    // value j of a compact row stands for column active[j], the other columns are x_base's
+    void set_active(const std::vector<int> &active, const std::vector<double> &x_base) {
+        if ((int64_t)x_base.size() != d_) throw InvalidValueError(EGX_ERR_INVALID_VALUE, "InfillObjective: x_base must hold d values");
+        const std::vector<int32_t> idx(active.begin(), active.end());
+        check(egx_infill_set_active(h_.get(), idx.data(), (int32_t)idx.size(), x_base.data()));
+        w_ = (int64_t)idx.size();
+    }
+    void clear_active() {
+        check(egx_infill_clear_active(h_.get()));
+        w_ = 0;
+    }
+    struct Active {
+        std::vector<int> indices;    // empty: no activity
+        std::vector<double> x_base;
+    };
+    Active active() const {
+        int32_t n = 0;
+        std::vector<int32_t> idx((size_t)d_);
+        std::vector<double> xb((size_t)d_);
+        check(egx_infill_get_active(h_.get(), &n, idx.data(), xb.data()));
+        Active a;
+        if (n > 0) a.indices.assign(idx.begin(), idx.begin() + n), a.x_base = std::move(xb);
+        return a;
+    }
+    int64_t width() const { return w_ > 0 ? w_ : d_; }  // of a point, a limit, a gradient row
     egx_infill *handle() const { return h_.get(); }
 
   private:
@@ -891,7 +917,7 @@ class InfillObjective {
         void operator()(egx_infill *p) const { egx_infill_destroy(p); }
     };
     std::unique_ptr<egx_infill, Deleter> h_;
-    int64_t d_ = 0, k_ = 0;
+    int64_t d_ = 0, k_ = 0, w_ = 0;   // w_: n_active while an activity is set
     std::vector<int64_t> n_experts_;  // per surrogate
 };
 

@@ -51,6 +51,16 @@ and is the yardstick on any commit.  Legs alternated, >= 3 warm-ups, medians wit
 profiles/infill_pending_bench.txt; no threshold is set.
 
     python tools/infill_bench.py --pending [--out profiles/infill_pending_bench.txt] [--reps 9]
+
+--active times ACTIVE COORDINATES (egx_infill_set_active; CoEGO) on one handle in one process: an objective and two constraint
+models, squared exponential, d = 32, 64, 128, 256 at n = 500 and n = 2000; one evaluation of 20 points with gradients, FULL
+width (d columns: what the handle launches without an activity, k_xgrad) against an ACTIVITY of a = ceil(d / 5) shuffled columns
+(compact rows, k_xgrad_cols: the pair correlation once per pass of listed columns), in both ways the optimisers evaluate: the
+constraints folded into the objective (value_and_grad, six contractions per tile) and as mean constraints (constraints(x,
+grad=True), four).  Legs alternated (full, active, full again: the two full runs show the spread), 3 warm-ups, medians with
+quartiles, written to profiles/infill_active_bench.txt; no threshold is set.
+
+    python tools/infill_bench.py --active [--out profiles/infill_active_bench.txt] [--reps 15]
 """
 import argparse
 import os
@@ -307,6 +317,46 @@ def run_pending(args, emit):
             h.close()
 
 
+def run_active(args, emit):
+    k, m = 2, 20
+    rng = np.random.default_rng(1)
+    emit("# active coordinates: objective + %d constraint models, squared exponential, LogEI; one evaluation of %d points with" % (k, m))
+    emit("# gradients, full width (d columns) against an activity of a = ceil(d / 5) shuffled columns on the SAME handle; wall ms as")
+    emit("# q25 median q75 over %d calls after 3 warm-ups, legs alternated (full, active, full again); speedup = median full /" % args.reps)
+    emit("# median active, full = the mean of the two full runs' medians")
+    emit("# strategy n d a full: q25_ms median_ms q75_ms  active: q25_ms median_ms q75_ms  full again: q25_ms median_ms q75_ms  speedup")
+    for n in (500, 2000):
+        for d in (32, 64, 128, 256):
+            hs, ys = [], []
+            for j in range(1 + k):
+                x, y = workload.make_training_set(n, d, seed=100 + j)
+                y = 1e-3 * y if j == 0 else y - np.quantile(y, 0.6)
+                h = egx.GpHandle(x, y)
+                h.finalize(np.full(d, 1.5 / d))
+                hs.append(h), ys.append(y)
+            a = -(-d // 5)
+            act = rng.permutation(d)[:a]
+            xq = rng.random((m, d))
+            xb, xc = xq[0].copy(), np.ascontiguousarray(xq[:, act])
+            with egx.InfillObjective(hs[0], hs[1:], [1e-3] * k, criterion=egx.LOG_EI, fmin=float(np.quantile(ys[0], 0.05))) as obj:
+                for strategy in ("infill", "mean"):
+                    obj.set_cstr_strategy(strategy)
+                    call = obj.value_and_grad if strategy == "infill" else (lambda pts: obj.constraints(pts, grad=True))
+                    legs = []
+                    for leg in ("full", "active", "full"):
+                        if leg == "active":
+                            obj.set_active(act, xb)
+                        pts = xc if leg == "active" else xq
+                        legs.append(quartiles_ms(lambda: call(pts), args.reps, warm=3)[0])
+                        obj.clear_active()
+                    full = 0.5 * (legs[0][1] + legs[2][1])
+                    emit(f"{strategy} {n} {d} {a} " + "  ".join(f"{q1:.3f} {q2:.3f} {q3:.3f}" for q1, q2, q3 in legs) +
+                         f"  {full / legs[1][1]:.2f}")
+            for h in hs:
+                h.close()
+            egx.trim()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -315,11 +365,12 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="the sparse leg: one sparse objective (nz = 512, d = 8), value + gradient")
     ap.add_argument("--slsqp", action="store_true", help="20 starts of SLSQP: the lock-step call, scipy on the m = 1 closures, COBYLA")
     ap.add_argument("--pending", action="store_true", help="pending points: one evaluation at q = 0 .. 16, the batch call against the refit loop")
+    ap.add_argument("--active", action="store_true", help="active coordinates: one evaluation of 20 points, full width against a = d / 5 columns")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "infill_pending_bench.txt" if args.pending else "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
+        args.out = os.path.join(ROOT, "profiles", "infill_active_bench.txt" if args.active else "infill_pending_bench.txt" if args.pending else "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
                                 else "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
@@ -337,8 +388,8 @@ def main():
             obj.value(xq)
             obj.value_and_grad(xq)
         return
-    if args.slsqp or args.pending:
-        (run_pending if args.pending else run_slsqp)(args, emit)
+    if args.slsqp or args.pending or args.active:
+        (run_active if args.active else run_pending if args.pending else run_slsqp)(args, emit)
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         return
