@@ -226,6 +226,12 @@ SIGNATURES = [
                                             c_int32_p]),
     ("egx_sgp_fit_lbfgs", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int32, C.c_double,
                                       C.c_int64, c_int64_p]),
+    ("egx_sgp_likelihood_grad_z", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, C.c_double, C.c_double, c_double_p, c_double_p,
+                                              c_double_p, c_int32_p]),
+    ("egx_sgp_set_inducings", C.c_int32, [C.c_void_p, c_double_p]),
+    ("egx_sgp_get_inducings", C.c_int32, [C.c_void_p, c_double_p]),
+    ("egx_sgp_fit_lbfgs_z", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int32, C.c_double,
+                                        C.c_int64, c_double_p, c_double_p, C.c_int64, c_int64_p]),
     ("egx_sgp_predict", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_sgp_predict_var", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_sgp_predict_valvar", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),

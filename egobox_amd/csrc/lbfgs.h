@@ -2,7 +2,7 @@
 // at the point ask() hands out and reports them with tell().  The variable is x = log10(parameter); a step moves at most one
 // decade, the line search is Armijo on the projected step, the memory is 8 pairs.  Host only (no device code: compiles under
 // g++, tests/c_host/lbfgs_test.cpp).  Used by egx_gp_fit_lbfgs (gp_fit.hip, every start in lock-step) and egx_sgp_fit_lbfgs
-// (sgp_host.hip, the starts one after the other).
+// (sgp_host.hip, the starts one after the other); egx_sgp_fit_lbfgs_z adds one start in mixed variables (LbfgsStart::Linear).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -29,6 +29,14 @@ struct LbfgsStart {
     LbfgsStart(const double *theta0, int h_, const std::vector<double> &lo, const std::vector<double> &hi, int64_t max_it)
         : h(h_), max_iter(max_it), blo(&lo), bhi(&hi), x(h_), g(h_), pg(h_), dir(h_), xn(h_) {
         for (int i = 0; i < h; i++) x[i] = std::log10(theta0[i]);
+        clip(x);
+    }
+    // The same machine started from variables that are not log10 of anything (egx_sgp_fit_lbfgs_z: log10 parameters followed by
+    // inducing coordinates scaled to [0, 1]): x0 is the point itself, clipped to the box.  "One decade per step" then reads "one
+    // unit of the caller's variables per step".
+    struct Linear {};
+    LbfgsStart(Linear, const double *x0, int h_, const std::vector<double> &lo, const std::vector<double> &hi, int64_t max_it)
+        : h(h_), max_iter(max_it), blo(&lo), bhi(&hi), x(x0, x0 + h_), g(h_), pg(h_), dir(h_), xn(h_) {
         clip(x);
     }
     // the point to evaluate next (log10 theta), or false when this start is finished

@@ -19,6 +19,7 @@
 // Extra device memory, allocated by the first gradient call and kept in the handle: ONE n_pad x z_pad buffer (E~, then T^T;
 // 4.1 GB at n = 10^6, nz = 512), 7 n_pad vectors, one zext^2 and three z_pad^2 matrices.  diag(q) RT - diag(beta) E~ L^-1 lives
 // in W, which is free after the Gram products.  Nothing n-long goes to the host.
+// The gradient in the inducing points (sgp_grad_tail_z, k_sgp_grad_cols) contracts the same T^T and S^ once more.
 #include "sgp_handle.h"
 #include "corr_pair.h"
 
@@ -275,6 +276,197 @@ int launch_grad_rect(hipStream_t s, int corr, const double *xT, int64_t ldx, int
     return EGX_SUCCESS;
 }
 
+// ---- the gradient in the inducing points: the column-reducing counterpart of k_sgp_grad_rect
+//   out[j, k] = scale * sum_i T[i, j] R(x_i, z_j) phi_k(x_ik - z_jk),   phi_k(dlt) = d ln r(a, b) / d a_k at dlt = a_k - b_k
+// over the same rectangles and weights.  (xT, zT, T^T) with scale sigma2 is the first sum of dL/dz; (zT, zT, S^) with scale -1 is
+// the second: S^ and R_zz are symmetric and phi is odd, so sum_b S^[j, b] R phi_k(z_j - z_b) = -sum_i S^[i, j] R phi_k(z_i - z_j),
+// rows reduced as in the first -- one kernel serves both.
+constexpr int kColsTargetWG = 1024;  // workgroups per output chunk that the runs of row tiles are sized for
+
+// phi_k: odd in dlt and exactly 0 at dlt == 0, the kink of the absolute exponential included (sgn(0) = 0, what the central
+// difference gives where an inducing point sits on a training point; xgrad_factor's copysign yields -c at +0, and other
+// kernels depend on its bits).  Matern: c sgn(dlt) (ln(1 + ..) - ..)'(t) at t = c |dlt|, with t sgn(dlt) = c dlt.
+template <int CORR>
+__device__ __forceinline__ double dlog_da(double c, double dlt) {
+    if (CORR == EGX_CORR_SQUARED_EXPONENTIAL) return -(c * c) * dlt;
+    if (CORR == EGX_CORR_ABSOLUTE_EXPONENTIAL) return dlt > 0.0 ? -c : (dlt < 0.0 ? c : 0.0);
+    const double t = c * fabs(dlt), cd = (c * c) * dlt;
+    if (CORR == EGX_CORR_MATERN32) return -3.0 * cd * rcp_ge1(__builtin_fma(kSqrt3, t, 1.0));
+    const double u = __builtin_fma(kSqrt5, t, 1.0);
+    return -k5over3 * cd * u * rcp_ge1(__builtin_fma(k5over3 * t, t, u));
+}
+
+// A workgroup owns column tile blockIdx.y, the run of row tiles [blockIdx.x * tpc, .. + tpc) and the output dimensions
+// blockIdx.z * DK ..; pass 1 is k_sgp_grad_rect's, pass 2 keeps one accumulator per (column, output dimension).  The sum over
+// rows meets in a fixed order: a lane's four rows of a tile and its tiles one after the other in registers, the four lanes of
+// a wave that share tx (xor shuffles over the ty bits 16, 32), the four waves through LDS; the partial [64 columns][d] goes to
+// part[blockIdx.x], and k_sgp_grad_cols_reduce adds the runs in order.  No atomics: the same bits on every call.
+template <int CORR, int DK>
+__global__ __launch_bounds__(256) void k_sgp_grad_cols(const double *__restrict__ xT, int64_t ldx, int n,
+                                                       const double *__restrict__ zT, int64_t ldz, int nz, int d,
+                                                       const double *__restrict__ coef, const double *__restrict__ T, int64_t ldt,
+                                                       int nrt, int tpc, int ncol_pad, double *__restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int dc = d < kRectDC ? d : kRectDC;
+    double *xi = sm, *xj = sm + dc * 64;
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    const int bj = blockIdx.y, o0 = blockIdx.z * DK;
+    const int r0 = blockIdx.x * tpc, r1 = (r0 + tpc < nrt) ? r0 + tpc : nrt;
+    double acc[4][DK];
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+#pragma unroll
+        for (int oo = 0; oo < DK; oo++) acc[b][oo] = 0.0;
+    for (int bi = r0; bi < r1; bi++) {
+        // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
+        PairAcc<CORR> pa[4][4];
+        for (int c0 = 0; c0 < d; c0 += dc) {
+            const int dn = (d - c0 < dc) ? (d - c0) : dc;
+            __syncthreads();  // the previous readers of the slabs are done
+            stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid);
+            stage_slab(xj, zT + (int64_t)c0 * ldz, ldz, bj * 64, dn, tid);
+            __syncthreads();
+            for (int k = 0; k < dn; k++) {
+                double vi[4], vj[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) vi[a] = xi[k * 64 + ty * 4 + a];
+#pragma unroll
+                for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
+                const double *ck = coef + (c0 + k);
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) pa[a][b].add(vi[a] - vj[b], ck, 1);
+            }
+        }
+        double wp[4][4];  // T[i, j] R[i, j] inside the n x nz rectangle, else 0
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            const int i = bi * 64 + ty * 4 + a;
+            const double *trow = T + (int64_t)i * ldt + bj * 64 + tx * 4;
+            const double2 t01 = *reinterpret_cast<const double2 *>(trow);
+            const double2 t23 = *reinterpret_cast<const double2 *>(trow + 2);
+            const double tv[4] = {t01.x, t01.y, t23.x, t23.y};
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int j = bj * 64 + tx * 4 + b;
+                wp[a][b] = (i < n && j < nz) ? pa[a][b].value() * tv[b] : 0.0;
+            }
+        }
+        // ---- pass 2: output dimensions o0 .. o0 + DK - 1 of this lane's four columns.  d > dc: they are staged again, from
+        // slab row 0
+        int base = 0;
+        if (d > dc) {
+            const int dn = (d - o0 < DK) ? (d - o0) : DK;
+            __syncthreads();
+            stage_slab(xi, xT + (int64_t)o0 * ldx, ldx, bi * 64, dn, tid);
+            stage_slab(xj, zT + (int64_t)o0 * ldz, ldz, bj * 64, dn, tid);
+            __syncthreads();
+            base = o0;
+        }
+#pragma unroll
+        for (int oo = 0; oo < DK; oo++) {
+            const int o = o0 + oo;
+            if (o < d) {
+                const double c = coef[o];
+                double vi[4], vj[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) vi[a] = xi[(o - base) * 64 + ty * 4 + a];
+#pragma unroll
+                for (int b = 0; b < 4; b++) vj[b] = xj[(o - base) * 64 + tx * 4 + b];
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    double sacc = acc[b][oo];
+#pragma unroll
+                    for (int a = 0; a < 4; a++) sacc = __builtin_fma(wp[a][b], dlog_da<CORR>(c, vi[a] - vj[b]), sacc);
+                    acc[b][oo] = sacc;
+                }
+            }
+        }
+    }
+    // ---- one reduction per workgroup: the lanes of a wave that share tx, then the four waves in a fixed order
+    __syncthreads();
+    double *red = sm;  // [4 waves][64 columns][DK]
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+#pragma unroll
+        for (int oo = 0; oo < DK; oo++) {
+            double v = acc[b][oo];
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            if ((tid & 48) == 0) red[((tid >> 6) * 64 + tx * 4 + b) * DK + oo] = v;
+        }
+    __syncthreads();
+    for (int e = tid; e < 64 * DK; e += 256) {
+        const int col = e / DK, o = o0 + (e - col * DK);
+        if (o < d)
+            part[((int64_t)blockIdx.x * ncol_pad + bj * 64 + col) * d + o] =
+                ((red[e] + red[64 * DK + e]) + red[2 * 64 * DK + e]) + red[3 * 64 * DK + e];
+    }
+}
+
+// out[j * d + k] = scale * (the runs' partials of column j, dimension k, added in run order), j < nz
+__global__ __launch_bounds__(256) void k_sgp_grad_cols_reduce(const double *__restrict__ part, int nruns, int64_t run_stride,
+                                                              int64_t count, double scale, double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    double v = 0.0;
+    for (int r = 0; r < nruns; r++) v += part[(int64_t)r * run_stride + e];
+    out[e] = scale * v;
+}
+
+// The runs of row tiles of a rectangle with `rows` rows and `cols` columns: (tiles per run, number of runs) -- a function of
+// the two sizes alone
+void cols_runs(int rows, int cols, int &tpc, int &nruns) {
+    const int nrt = (rows + 63) / 64, ntc = (cols + 63) / 64;
+    const int want = std::max(1, std::min(nrt, (kColsTargetWG + ntc - 1) / ntc));
+    tpc = std::max((nrt + want - 1) / want, std::min(nrt, 2));  // two tiles at least share a workgroup's reduction
+    nruns = (nrt + tpc - 1) / tpc;
+}
+size_t cols_part_doubles(int rows, int cols, int d) {
+    int tpc, nruns;
+    cols_runs(rows, cols, tpc, nruns);
+    return (size_t)nruns * (size_t)((cols + 63) / 64 * 64) * (size_t)d;
+}
+
+// out (nz x d) = scale * the column sums over the n x nz rectangle with rows xT, columns zT and weights T
+int launch_grad_cols(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, const double *zT, int64_t ldz, int nz, int d,
+                     const double *coef, const double *T, int64_t ldt, double scale, double *part, double *out) {
+    const int nrt = (n + 63) / 64, ntc = (nz + 63) / 64, ncol_pad = ntc * 64;
+    int tpc, nruns;
+    cols_runs(n, nz, tpc, nruns);
+    const int dc = d < kRectDC ? d : kRectDC;
+    const int dk = d <= 4 ? 4 : (d <= 8 ? 8 : 16);
+    const int nzc = (d + dk - 1) / dk;
+    if (ntc > 65535 || nzc > 65535) {
+        set_error("sparse GP gradient in the inducing points: too many column tiles or dimensions");
+        return EGX_ERR_UNSUPPORTED;
+    }
+    const size_t lds = sizeof(double) * (size_t)std::max(2 * dc * 64, 4 * 64 * dk);
+    const dim3 grid((unsigned)nruns, (unsigned)ntc, (unsigned)nzc);
+#define EGX_COLS(C_, DK_)                                                                                                       \
+    hipLaunchKernelGGL((k_sgp_grad_cols<C_, DK_>), grid, dim3(256), lds, s, xT, ldx, n, zT, ldz, nz, d, coef, T, ldt, nrt, tpc, \
+                       ncol_pad, part)
+#define EGX_COLS_DK(C_)                \
+    if (dk == 4) EGX_COLS(C_, 4);      \
+    else if (dk == 8) EGX_COLS(C_, 8); \
+    else EGX_COLS(C_, 16)
+    switch (corr) {
+        case EGX_CORR_SQUARED_EXPONENTIAL: EGX_COLS_DK(EGX_CORR_SQUARED_EXPONENTIAL); break;
+        case EGX_CORR_ABSOLUTE_EXPONENTIAL: EGX_COLS_DK(EGX_CORR_ABSOLUTE_EXPONENTIAL); break;
+        case EGX_CORR_MATERN32: EGX_COLS_DK(EGX_CORR_MATERN32); break;
+        case EGX_CORR_MATERN52: EGX_COLS_DK(EGX_CORR_MATERN52); break;
+        default: set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;
+    }
+#undef EGX_COLS_DK
+#undef EGX_COLS
+    const int64_t count = (int64_t)nz * d;
+    hipLaunchKernelGGL(k_sgp_grad_cols_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, part, nruns,
+                       (int64_t)ncol_pad * d, count, scale, out);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
 }  // namespace
 
 namespace egx {
@@ -349,6 +541,26 @@ int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad) {
     grad[d] = -0.5 * (2.0 * hn[d] - hz[d] / sigma2 + c_sigma);
     if (!vfe) grad[d + 1] = -0.5 * sum_p;
     else grad[d + 1] = (noise > g->nugget) ? -0.5 * (sum_p - be * be * ((double)n * sigma2 - sigma2 * sum_s0)) : 0.0;
+    return EGX_SUCCESS;
+}
+
+// Right after a successful sgp_grad_tail (T^T still in gr_E, S^ in the third matrix of gr_sq, theta in coef):
+//   dL/dz[j, k] = sigma2 sum_t T^T[t, j] R(x_t, z_j) phi_k(x_tk - z_jk) + sum_b S^[j, b] R(z_j, z_b) phi_k(z_jk - z_bk)
+// two launches of k_sgp_grad_cols, the two nz x d results added on the host.  Caller holds g->mu.
+int sgp_grad_tail_z(egx_sgp *g, double sigma2, double *grad_z) {
+    const int n = g->n, d = g->d, nz = g->nz, n_pad = g->n_pad, z_pad = g->z_pad;
+    hipStream_t s = g->stream;
+    const size_t sq = (size_t)z_pad * z_pad, cnt = (size_t)nz * d;
+    EGX_RC(g->gz_part.alloc(std::max(cols_part_doubles(n, nz, d), cols_part_doubles(nz, nz, d))));
+    EGX_RC(g->gz_out.alloc(2 * cnt));
+    const double *E = g->gr_E.p, *Sh = g->gr_sq.p + 2 * sq;
+    double *out_nz = g->gz_out.p, *out_zz = out_nz + cnt;
+    EGX_RC(launch_grad_cols(s, g->corr, g->xT.p, n_pad, n, g->zT.p, z_pad, nz, d, g->coef.p, E, z_pad, sigma2, g->gz_part.p, out_nz));
+    EGX_RC(launch_grad_cols(s, g->corr, g->zT.p, z_pad, nz, g->zT.p, z_pad, nz, d, g->coef.p, Sh, z_pad, -1.0, g->gz_part.p, out_zz));
+    std::vector<double> h(2 * cnt);
+    EGX_HIP_CHECK(hipMemcpyAsync(h.data(), g->gz_out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    EGX_HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t e = 0; e < cnt; e++) grad_z[e] = h[e] + h[cnt + e];
     return EGX_SUCCESS;
 }
 

@@ -29,6 +29,11 @@ struct egx_sgp {
     // likelihood gradient (sgp_grad.hip): grow-only workspace of egx_sgp_likelihood_grad, allocated by its first call.  gr_E is
     // the one n_pad x z_pad buffer (E~, then T^T); gr_rows 7 n_pad vectors; gr_G2 zext^2 (FITC); gr_sq three z_pad^2 matrices
     egx::DevBuf gr_E, gr_rows, gr_G2, gr_sq, gr_vec, gr_part, gr_out;
+    // gradient in the inducing points (sgp_grad.hip, sgp_grad_tail_z): the partial column sums [row chunk][column][d] and the
+    // two reduced nz x d matrices, grow-only like gr_part; the current inducing points (nz x d, row-major: what zT holds) and
+    // the per-column range of the training inputs, the default box of egx_sgp_fit_lbfgs_z
+    egx::DevBuf gz_part, gz_out;
+    std::vector<double> z_host, x_lo, x_hi;
 };
 
 
@@ -47,4 +52,7 @@ int sgp_launch_transpose_scale(egx_sgp *g, const double *sb, double scale);
 // grad (d + 2) = dL/dtheta, dL/dsigma2, dL/dnoise at the parameters of the evaluation whose factors are resident
 // (a successful sgp_eval that has just returned); caller holds g->mu
 int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad);
+// grad_z (nz x d, row-major) = dL/dz right after a successful sgp_grad_tail, whose pair weights T^T (gr_E) and S^ (gr_sq) it
+// contracts once more; caller holds g->mu
+int sgp_grad_tail_z(egx_sgp *g, double sigma2, double *grad_z);
 }  // namespace egx

@@ -13,7 +13,8 @@
 // The Woodbury matrix of the reference (nz x nz inverses) is never formed for predictions:
 //   kx^T Kmm^-1 kx = |U^-1 kx|^2,   kx^T U^-T (L L^T)^-1 U^-1 kx = |L^-1 U^-1 kx|^2   (two launch_trsm_rows + k_row_reduce)
 // Predictions, their x-gradients and sampling: sgp_predict.hip.  The likelihood's closed-form gradient: sgp_grad.hip (its entry
-// points, egx_sgp_likelihood_grad and egx_sgp_fit_lbfgs, are here beside the evaluation they extend).
+// points, egx_sgp_likelihood_grad and egx_sgp_fit_lbfgs, are here beside the evaluation they extend, and so are those of the
+// gradient in the inducing points: egx_sgp_likelihood_grad_z, egx_sgp_set_inducings / _get_inducings, egx_sgp_fit_lbfgs_z).
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -268,6 +269,95 @@ int sgp_eval_grad_x(egx_sgp *g, const std::vector<double> &xv, int estimate_nois
     return EGX_SUCCESS;
 }
 
+// The starts of egx_sgp_fit_lbfgs, one after the other: the best (f, x = log10 params), the first on ties, and the evaluations
+int sgp_lbfgs_starts(egx_sgp *g, const double *params0s, int64_t n_starts, int np, const std::vector<double> &blo,
+                     const std::vector<double> &bhi, int estimate_noise, double noise_fixed, int64_t max_iter, double &best_f,
+                     std::vector<double> &best_x, int64_t &evals) {
+    std::vector<double> xv, gx;
+    best_f = std::numeric_limits<double>::infinity();
+    evals = 0;
+    for (int64_t st = 0; st < n_starts; st++) {
+        LbfgsStart m(params0s + st * np, np, blo, bhi, max_iter);
+        while (m.ask(xv)) {
+            double f;
+            EGX_RC(sgp_eval_grad_x(g, xv, estimate_noise, noise_fixed, f, gx));
+            evals++;
+            m.tell(f, gx);
+        }
+        if (m.f < best_f) {
+            best_f = m.f;
+            best_x = m.x;
+        }
+    }
+    return EGX_SUCCESS;
+}
+
+// zT <- z (nz x d row-major; k-major and padded as at creation).  The resident factors belong to the old points: the handle is
+// un-fitted and the cached inverse factors are dropped.
+int sgp_upload_z(egx_sgp *g, const double *z) {
+    const int d = g->d, nz = g->nz;
+    const size_t zp = g->z_pad;
+    std::vector<double> zT((size_t)d * zp, 0.0);
+    for (int i = 0; i < nz; i++)
+        for (int k = 0; k < d; k++) zT[(size_t)k * zp + i] = z[(size_t)i * d + k];
+    EGX_HIP_CHECK(hipMemcpyAsync(g->zT.p, zT.data(), sizeof(double) * zT.size(), hipMemcpyHostToDevice, g->stream));
+    EGX_HIP_CHECK(hipStreamSynchronize(g->stream));  // zT is a local
+    if (z != g->z_host.data()) g->z_host.assign(z, z + (size_t)nz * d);
+    g->fitted = false;
+    g->winv_ok = false;
+    return EGX_SUCCESS;
+}
+
+// The box of the inducing points in phase 2 of egx_sgp_fit_lbfgs_z and the map from its unit variables:
+// z[j, k] = clamp(lo_k + u[j, k] (hi_k - lo_k)); a column with hi_k == lo_k keeps the points' own coordinates z0[., k]
+struct ZBox {
+    int nz = 0, d = 0;
+    std::vector<double> lo, hi, z0;
+    void to_z(const double *u, std::vector<double> &z) const {
+        z.resize((size_t)nz * d);
+        for (int j = 0; j < nz; j++)
+            for (int k = 0; k < d; k++) {
+                const size_t e = (size_t)j * d + k;
+                z[e] = hi[k] > lo[k] ? std::fmin(hi[k], std::fmax(lo[k], lo[k] + u[e] * (hi[k] - lo[k]))) : z0[e];
+            }
+    }
+};
+
+// f = -L and its gradient at xv = [log10 params (np), u (nz d)] for phase 2: the points are set, then the likelihood and both
+// gradients are evaluated.  g_u = -(hi_k - lo_k) dL/dz[j, k], 0 in a fixed column.  A failed evaluation is f = +inf.
+int sgp_eval_grad_xz(egx_sgp *g, const std::vector<double> &xv, int np, int estimate_noise, double noise_fixed, const ZBox &box,
+                     double &f, std::vector<double> &gx) {
+    const int d = g->d, nz = g->nz;
+    const size_t h = (size_t)np + (size_t)nz * d;
+    std::vector<double> prm(d + 2), grad(d + 2, 0.0), z, gz((size_t)nz * d, 0.0);
+    box.to_z(xv.data() + np, z);
+    EGX_RC(sgp_upload_z(g, z.data()));
+    for (int i = 0; i <= d; i++) prm[i] = std::pow(10.0, xv[i]);
+    prm[d + 1] = estimate_noise ? std::pow(10.0, xv[d + 1]) : noise_fixed;
+    Eval ev;
+    EGX_RC(sgp_eval(g, prm.data(), d, prm[d], prm[d + 1], ev, false));
+    f = std::numeric_limits<double>::infinity();
+    gx.assign(h, 0.0);
+    if (ev.status != EGX_STATUS_OK) return EGX_SUCCESS;
+    EGX_RC(sgp_grad_tail(g, prm[d], prm[d + 1], grad.data()));
+    EGX_RC(sgp_grad_tail_z(g, prm[d], gz.data()));
+    f = -ev.lkh;
+    const double ln10 = std::log(10.0);
+    for (int i = 0; i < np; i++) gx[i] = -prm[i] * ln10 * grad[i];
+    for (int j = 0; j < nz; j++)
+        for (int k = 0; k < d; k++) {
+            const size_t e = (size_t)j * d + k;
+            gx[np + e] = box.hi[k] > box.lo[k] ? -(box.hi[k] - box.lo[k]) * gz[e] : 0.0;
+        }
+    for (size_t i = 0; i < h; i++)
+        if (!std::isfinite(gx[i])) {
+            f = std::numeric_limits<double>::infinity();
+            gx.assign(h, 0.0);
+            break;
+        }
+    return EGX_SUCCESS;
+}
+
 }  // namespace
 
 namespace egx {
@@ -353,6 +443,14 @@ int32_t egx_sgp_create(const egx_sgp_config *cfg_in, const double *x, const doub
     g->zext = g->z_pad + kTile;
     g->y_host.assign(y, y + n);
     for (int64_t i = 0; i < n; i++) g->yty += y[i] * y[i];
+    g->z_host.assign(z, z + nz * d);
+    g->x_lo.assign(x, x + d);
+    g->x_hi.assign(x, x + d);
+    for (int64_t i = 1; i < n; i++)
+        for (int64_t k = 0; k < d; k++) {
+            g->x_lo[k] = std::fmin(g->x_lo[k], x[i * d + k]);
+            g->x_hi[k] = std::fmax(g->x_hi[k], x[i * d + k]);
+        }
     auto fail = [&](int rc) {
         egx_sgp_destroy(g);
         return rc;
@@ -549,21 +647,123 @@ int32_t egx_sgp_fit_lbfgs(egx_sgp *g, const double *params0s, int64_t n_starts, 
     std::vector<double> blo, bhi;
     EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
     if (max_iter < 1) max_iter = 50;
-    double best_f = std::numeric_limits<double>::infinity();
-    std::vector<double> best_x, xv, gx;
+    double best_f;
+    std::vector<double> best_x;
     int64_t evals = 0;
-    for (int64_t st = 0; st < n_starts; st++) {
-        LbfgsStart m(params0s + st * np, np, blo, bhi, max_iter);
+    EGX_RC(sgp_lbfgs_starts(g, params0s, n_starts, np, blo, bhi, estimate_noise, noise_fixed, max_iter, best_f, best_x, evals));
+    if (n_evals_out) *n_evals_out = evals;
+    return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);
+}
+
+// egx_sgp_likelihood_grad (the same launches first: the same bits of *lkh and grad) and the gradient in the inducing points,
+// grad_z (nz x d, row-major like z), from two more launches over the pair weights that call leaves on the device (sgp_grad.hip)
+int32_t egx_sgp_likelihood_grad_z(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, double noise, double *lkh,
+                                  double *grad, double *grad_z, int32_t *status) {
+    if (!g || !theta || !lkh || !grad || !grad_z || !status) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    Eval ev;
+    EGX_RC(sgp_eval(g, theta, theta_len, sigma2, noise, ev, false));
+    for (int i = 0; i < g->d + 2; i++) grad[i] = 0.0;
+    for (size_t e = 0; e < (size_t)g->nz * g->d; e++) grad_z[e] = 0.0;
+    if (ev.status == EGX_STATUS_OK) {
+        EGX_RC(sgp_grad_tail(g, sigma2, noise, grad));
+        EGX_RC(sgp_grad_tail_z(g, sigma2, grad_z));
+    }
+    *lkh = ev.lkh;
+    *status = ev.status;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_sgp_set_inducings(egx_sgp *g, const double *z) {
+    if (!g || !z) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    for (size_t e = 0; e < (size_t)g->nz * g->d; e++)
+        if (!std::isfinite(z[e])) {
+            set_error("z contains non-finite values");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    return sgp_upload_z(g, z);
+}
+
+int32_t egx_sgp_get_inducings(egx_sgp *g, double *z) {
+    if (!g || !z) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    std::memcpy(z, g->z_host.data(), sizeof(double) * g->z_host.size());
+    return EGX_SUCCESS;
+}
+
+// egx_sgp_fit_lbfgs, then one more L-BFGS from its winner in which the inducing points move too (header: phase 2).  The phase-2
+// point is kept only where its likelihood is strictly higher; otherwise the points go back, bit for bit, to where they were.
+int32_t egx_sgp_fit_lbfgs_z(egx_sgp *g, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
+                            int32_t estimate_noise, double noise_fixed, int64_t max_iter, const double *z_lo, const double *z_hi,
+                            int64_t max_iter_z, int64_t *n_evals_out) {
+    if (!g || !params0s || !lo || !hi || n_starts < 1) {
+        set_error("NULL argument / no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if ((z_lo == nullptr) != (z_hi == nullptr)) {
+        set_error("z_lo and z_hi must be given together");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    const int d = g->d, nz = g->nz, np = d + 1 + (estimate_noise ? 1 : 0);
+    std::vector<double> blo, bhi;
+    EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
+    ZBox box;
+    box.nz = nz;
+    box.d = d;
+    box.lo = z_lo ? std::vector<double>(z_lo, z_lo + d) : g->x_lo;
+    box.hi = z_hi ? std::vector<double>(z_hi, z_hi + d) : g->x_hi;
+    for (int k = 0; k < d; k++)
+        if (!std::isfinite(box.lo[k]) || !std::isfinite(box.hi[k]) || !(box.hi[k] >= box.lo[k])) {
+            set_error("sparse GP inducing-point bounds must be finite with z_lo <= z_hi");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    if (max_iter < 1) max_iter = 50;
+    if (max_iter_z < 0) max_iter_z = 50;
+    double best_f;
+    std::vector<double> best_x;
+    int64_t evals = 0;
+    EGX_RC(sgp_lbfgs_starts(g, params0s, n_starts, np, blo, bhi, estimate_noise, noise_fixed, max_iter, best_f, best_x, evals));
+    if (max_iter_z > 0 && std::isfinite(best_f)) {
+        box.z0 = g->z_host;
+        const size_t nu = (size_t)nz * d;
+        std::vector<double> x0(np + nu), xlo(np + nu, 0.0), xhi(np + nu, 1.0), xv, gx;
+        for (int i = 0; i < np; i++) {
+            x0[i] = best_x[i];
+            xlo[i] = blo[i];
+            xhi[i] = bhi[i];
+        }
+        for (size_t e = 0; e < nu; e++) {
+            const int k = (int)(e % (size_t)d);
+            x0[np + e] = box.hi[k] > box.lo[k] ? (box.z0[e] - box.lo[k]) / (box.hi[k] - box.lo[k]) : 0.0;
+        }
+        LbfgsStart m(LbfgsStart::Linear(), x0.data(), (int)(np + nu), xlo, xhi, max_iter_z);
         while (m.ask(xv)) {
             double f;
-            EGX_RC(sgp_eval_grad_x(g, xv, estimate_noise, noise_fixed, f, gx));
+            EGX_RC(sgp_eval_grad_xz(g, xv, np, estimate_noise, noise_fixed, box, f, gx));
             evals++;
             m.tell(f, gx);
         }
+        std::vector<double> z = box.z0;
         if (m.f < best_f) {
             best_f = m.f;
-            best_x = m.x;
+            best_x.assign(m.x.begin(), m.x.begin() + np);
+            box.to_z(m.x.data() + np, z);
         }
+        EGX_RC(sgp_upload_z(g, z.data()));
     }
     if (n_evals_out) *n_evals_out = evals;
     return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);

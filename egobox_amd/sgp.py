@@ -132,6 +132,53 @@ class SgpHandle:
                                             int(bool(estimate_noise)), float(noise_fixed), int(max_iter), C.byref(ne)))
         return ne.value
 
+    def likelihood_grad_z(self, theta, sigma2, noise):
+        """(likelihood, gradient, grad_z, status): `likelihood_grad` (same bits) and dL/dz, (nz, d) like `z`, the gradient in
+        the inducing points; zeros whenever status != 0 (egx_sgp_likelihood_grad_z)."""
+        th = L.as_f64(np.atleast_1d(theta), 1)
+        lk, st = C.c_double(), C.c_int32()
+        grad, grad_z = np.zeros(self.d + 2), np.zeros((self.nz, self.d))
+        L.check(self._lib.egx_sgp_likelihood_grad_z(self._h, L.dptr(th), th.size, float(sigma2), float(noise), C.byref(lk),
+                                                    L.dptr(grad), L.dptr(grad_z), C.byref(st)))
+        return lk.value, grad, grad_z, st.value
+
+    def inducings(self):
+        """The current inducing points (nz, d), read from the library (egx_sgp_get_inducings)."""
+        z = np.empty((self.nz, self.d))
+        L.check(self._lib.egx_sgp_get_inducings(self._h, L.dptr(z)))
+        return z
+
+    def set_inducings(self, z):
+        """Replace the inducing points (same nz; finite values).  Un-fits the handle (egx_sgp_set_inducings)."""
+        z = np.ascontiguousarray(L.as_f64(z))
+        if z.shape != (self.nz, self.d):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"z must be ({self.nz}, {self.d}), got {z.shape}")
+        L.check(self._lib.egx_sgp_set_inducings(self._h, L.dptr(z)))
+        self.z = self.inducings()
+
+    def fit_lbfgs_z(self, params0s, lo, hi, estimate_noise, noise_fixed, max_iter=50, max_iter_z=50, z_lo=None, z_hi=None):
+        """`fit_lbfgs`, then one more L-BFGS from its winner over the parameters AND the inducing points, each boxed in
+        [z_lo, z_hi] (d values each; None: the range of the training inputs), driven by `likelihood_grad_z`
+        (egx_sgp_fit_lbfgs_z).  Never ends below `fit_lbfgs`; max_iter_z=0 is `fit_lbfgs`.  `z` / `inducings()` hold the
+        moved points afterwards.  Returns the number of evaluations of both phases."""
+        p0 = L.as_f64(params0s, 2)
+        lo, hi = L.as_f64(lo, 1), L.as_f64(hi, 1)
+        if (z_lo is None) != (z_hi is None):
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, "z_lo and z_hi must be given together")
+        zl = zh = None
+        if z_lo is not None:
+            zl = np.ascontiguousarray(np.broadcast_to(L.as_f64(np.atleast_1d(z_lo), 1), (self.d,)))
+            zh = np.ascontiguousarray(np.broadcast_to(L.as_f64(np.atleast_1d(z_hi), 1), (self.d,)))
+        ne = C.c_int64()
+        try:
+            L.check(self._lib.egx_sgp_fit_lbfgs_z(self._h, L.dptr(p0), p0.shape[0], L.dptr(lo), L.dptr(hi),
+                                                  int(bool(estimate_noise)), float(noise_fixed), int(max_iter),
+                                                  L.dptr(zl) if zl is not None else None, L.dptr(zh) if zh is not None else None,
+                                                  int(max_iter_z), C.byref(ne)))
+        finally:
+            self.z = self.inducings()
+        return ne.value
+
     def _q(self, x):
         x = L.as_f64(x)
         if x.ndim == 1:
@@ -226,6 +273,7 @@ class SgpParams:
         self._n_start, self._max_eval = G.GP_OPTIM_N_START, G.GP_COBYLA_MAX_EVAL
         self._nugget, self._seed, self._device = G.DEFAULT_NUGGET, None, -1
         self._optimizer = "cobyla"  # the reference's optimiser; "lbfgs" uses the closed-form likelihood gradient
+        self._opt_z = None          # optimize_inducings: (max_iter, (z_lo, z_hi) or None)
 
     def sparse_method(self, m):
         self._method = {"fitc": FITC, "vfe": VFE}[m.lower()] if isinstance(m, str) else int(m)
@@ -269,6 +317,14 @@ class SgpParams:
         self._optimizer = name
         return self
 
+    def optimize_inducings(self, max_iter=50, bounds=None):
+        """Extension (the reference's inducing points never move): after the "lbfgs" fit, one more L-BFGS from its winner in
+        which the inducing points move with the parameters (`SgpHandle.fit_lbfgs_z`), `max_iter` iterations at the most.
+        bounds: (z_lo, z_hi), d values each (or one for all), the box of every point; None: the range of the training
+        inputs.  Needs optimizer("lbfgs"); max_iter=0 switches it off again."""
+        self._opt_z = (int(max_iter), None if bounds is None else (bounds[0], bounds[1]))
+        return self
+
     def seed(self, s):
         self._seed = s
         return self
@@ -283,6 +339,11 @@ class SgpParams:
         if x.ndim == 1:
             x = x.reshape(-1, 1)
         y = np.asarray(y, dtype=np.float64).reshape(-1)
+        opt_z = self._opt_z is not None and self._opt_z[0] != 0
+        if opt_z and self._optimizer != "lbfgs":
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE,
+                                      'optimize_inducings moves the inducing points by the likelihood gradient: it needs '
+                                      'optimizer("lbfgs")')
         if self._inducings.kind == "Located":
             z = self._inducings.value
         else:  # make_inducings :833-848 (numpy shuffle instead of Xoshiro256Plus)
@@ -310,7 +371,17 @@ class SgpParams:
         starts_log10, _ = prepare_multistart(self._n_start, params0, bounds, seed=42 if self._seed is None else self._seed)
         lo, hi = [b[0] for b in bounds], [b[1] for b in bounds]
         if self._optimizer == "lbfgs":  # iterations per start from max_eval as GpParams.fit does
-            n_evals = h.fit_lbfgs(10.0 ** starts_log10, lo, hi, est, self._noise.init, max(5, min(100, self._max_eval // 4)))
+            max_iter = max(5, min(100, self._max_eval // 4))
+            if opt_z:
+                zb = self._opt_z[1] or (None, None)
+                try:
+                    n_evals = h.fit_lbfgs_z(10.0 ** starts_log10, lo, hi, est, self._noise.init, max_iter,
+                                            max_iter_z=self._opt_z[0], z_lo=zb[0], z_hi=zb[1])
+                except Exception:
+                    h.close()
+                    raise
+            else:
+                n_evals = h.fit_lbfgs(10.0 ** starts_log10, lo, hi, est, self._noise.init, max_iter)
         else:
             n_evals = h.fit(10.0 ** starts_log10, lo, hi, est, self._noise.init, self._max_eval)
         sgp = SparseGaussianProcess(h, self, n_evals)
@@ -429,11 +500,12 @@ class SparseGpMix:
     sparse expert per cluster -- Located(z): every expert the same z; Randomized(nz): nz rows of the expert's own cluster, drawn
     with the seed --, and `recombination` "hard" or "smooth"; smooth with heaviside_factor=None (the reference's Smooth(None))
     chooses the factor on one row out of five (`optimize_heaviside_factor`) and retrains on all rows.  n_clusters = 0 (automatic)
-    and kpls_dim are not implemented."""
+    and kpls_dim are not implemented.  optimize_inducings (an extension, with optimizer="lbfgs"): every expert moves its
+    inducing points by the likelihood gradient after its fit (`SgpParams.optimize_inducings`)."""
 
     def __init__(self, corr_spec=1, theta_init=None, theta_bounds=None, kpls_dim=None, n_start=G.GP_OPTIM_N_START, nz=None,
                  z=None, method=FITC, seed=None, max_eval=G.GP_COBYLA_MAX_EVAL, device=-1, optimizer="cobyla", n_clusters=1,
-                 recombination="smooth", heaviside_factor=None, n_runs=20):
+                 recombination="smooth", heaviside_factor=None, n_runs=20, optimize_inducings=False):
         if kpls_dim is not None:
             raise NotImplementedError("KPLS rotations come from linfa-pls (outside the accelerated path)")
         if int(n_clusters) == 0:
@@ -450,6 +522,8 @@ class SparseGpMix:
         self.max_eval, self.device, self.optimizer = max_eval, device, optimizer
         self.n_clusters, self.recombination, self.heaviside_factor = int(n_clusters), str(recombination).lower(), heaviside_factor
         self.n_runs = int(n_runs)
+        # False, True (50 iterations) or the number of iterations of `SgpParams.optimize_inducings`, per expert
+        self.optimize_inducings = optimize_inducings
 
     def _expert_params(self):
         corrs = {1: G.SquaredExponentialCorr, 2: G.AbsoluteExponentialCorr, 4: G.Matern32Corr, 8: G.Matern52Corr}
@@ -462,6 +536,8 @@ class SparseGpMix:
             p.theta_init(self.theta_init)
         if self.theta_bounds is not None:
             p.theta_bounds(self.theta_bounds)
+        if self.optimize_inducings:
+            p.optimize_inducings(50 if self.optimize_inducings is True else int(self.optimize_inducings))
         return p
 
     def fit(self, xt, yt):

@@ -629,6 +629,27 @@ int32_t egx_sgp_likelihood_grad(egx_sgp *sgp, const double *theta, int64_t theta
  * max_iter < 1: 50 iterations per start.  *n_evals_out counts likelihood + gradient evaluations. */
 int32_t egx_sgp_fit_lbfgs(egx_sgp *sgp, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
                           int32_t estimate_noise, double noise_fixed, int64_t max_iter, int64_t *n_evals_out);
+/* No counterpart in the reference (its inducing points never move): egx_sgp_likelihood_grad -- *lkh and grad bit for bit -- and,
+ * from the same pair weights, the gradient in the inducing points, grad_z (nz x d, row-major like z) = dL/dz_{j,k}.  Under the
+ * absolute exponential a coordinate where z_j meets a training point or another inducing point (the kernel's kink) contributes 0,
+ * what the central difference gives there.  Whenever *status != 0, grad_z is zeros too.  Un-fits the handle like its sibling. */
+int32_t egx_sgp_likelihood_grad_z(egx_sgp *sgp, const double *theta, int64_t theta_len, double sigma2, double noise, double *lkh,
+                                  double *grad /* d + 2 */, double *grad_z /* nz*d */, int32_t *status);
+/* Replace the inducing points by z (the same nz; finite values, else EGX_ERR_INVALID_VALUE and the handle stays as it was).
+ * Un-fits the handle: finalize or fit again before predicting.  egx_sgp_get_inducings returns the current points. */
+int32_t egx_sgp_set_inducings(egx_sgp *sgp, const double *z /*nz*d*/);
+int32_t egx_sgp_get_inducings(egx_sgp *sgp, double *z /*nz*d*/);
+/* egx_sgp_fit_lbfgs (phase 1, exactly), then ONE more projected L-BFGS from its winner over [log10 params (np), u (nz*d)],
+ * u = (z - z_lo) / (z_hi - z_lo) in [0, 1]: the inducing points move with the parameters, driven by egx_sgp_likelihood_grad_z.
+ * z_lo / z_hi (d each) box every inducing point; NULL: the per-column min / max of the training x.  A column with z_hi == z_lo
+ * is held where it is; points outside the box start from its nearest face.  An evaluation that fails (two points merged) counts
+ * as +inf and the line search backs off.  Phase 2 is kept only where it ends at a strictly higher likelihood than phase 1, so
+ * the result is never worse than egx_sgp_fit_lbfgs; the accepted points stay on the handle (egx_sgp_get_inducings) and one keeping
+ * evaluation follows.  max_iter_z == 0: no phase 2, the handle is left bit for bit as egx_sgp_fit_lbfgs leaves it; < 0: 50.
+ * *n_evals_out counts the evaluations of both phases. */
+int32_t egx_sgp_fit_lbfgs_z(egx_sgp *sgp, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
+                            int32_t estimate_noise, double noise_fixed, int64_t max_iter, const double *z_lo /*d or NULL*/,
+                            const double *z_hi /*d or NULL*/, int64_t max_iter_z, int64_t *n_evals_out);
 /* SparseGaussianProcess::predict :237-241, predict_var :245-257 (clamp at 1e-15, + noise) */
 int32_t egx_sgp_predict(egx_sgp *sgp, const double *xq, int64_t m, double *y /*m*/);
 int32_t egx_sgp_predict_var(egx_sgp *sgp, const double *xq, int64_t m, double *var /*m*/);

@@ -324,6 +324,40 @@ class SparseGaussianProcess {
         check(egx_sgp_fit_lbfgs(h_.get(), params0s, n_starts, lo, hi, estimate_noise ? 1 : 0, noise_fixed, max_iter, &n_evals));
         return n_evals;
     }
+    // likelihood_grad and, from the same pair weights, dL/dz (nz x d row-major): egx_sgp_likelihood_grad_z
+    struct LikelihoodGradZ {
+        double likelihood;
+        std::vector<double> grad, grad_z;
+        int32_t status;
+    };
+    LikelihoodGradZ likelihood_grad_z(const double *theta, int64_t theta_len, double sigma2, double noise) {
+        LikelihoodGradZ r{0.0, std::vector<double>((size_t)(d_ + 2)), std::vector<double>((size_t)(nz() * d_)), 0};
+        check(egx_sgp_likelihood_grad_z(h_.get(), theta, theta_len, sigma2, noise, &r.likelihood, r.grad.data(), r.grad_z.data(),
+                                        &r.status));
+        return r;
+    }
+    // the inducing points (nz x d row-major): replace them (un-fits the model) / read the current ones
+    void set_inducings(const double *z) { check(egx_sgp_set_inducings(h_.get(), z)); }
+    std::vector<double> inducings() const {
+        std::vector<double> z((size_t)(nz() * d_));
+        check(egx_sgp_get_inducings(h_.get(), z.data()));
+        return z;
+    }
+    // fit_lbfgs, then one more L-BFGS in which the inducing points move inside [z_lo, z_hi] (d each; nullptr: the range of the
+    // training inputs): egx_sgp_fit_lbfgs_z.  max_iter_z == 0 is fit_lbfgs.
+    int64_t fit_lbfgs_z(const double *params0s, int64_t n_starts, const double *lo, const double *hi, bool estimate_noise,
+                        double noise_fixed, int64_t max_iter = 50, const double *z_lo = nullptr, const double *z_hi = nullptr,
+                        int64_t max_iter_z = 50) {
+        int64_t n_evals = 0;
+        check(egx_sgp_fit_lbfgs_z(h_.get(), params0s, n_starts, lo, hi, estimate_noise ? 1 : 0, noise_fixed, max_iter, z_lo, z_hi,
+                                  max_iter_z, &n_evals));
+        return n_evals;
+    }
+    int64_t nz() const {
+        int64_t v = 0;
+        check(egx_sgp_dims(h_.get(), nullptr, nullptr, &v));
+        return v;
+    }
     std::vector<double> predict(const double *x, int64_t m) const {
         std::vector<double> y((size_t)m);
         check(egx_sgp_predict(h_.get(), x, m, y.data()));
