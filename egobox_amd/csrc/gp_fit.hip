@@ -1,9 +1,9 @@
-// Optimiser drivers above the likelihood (GpValidParams::fit with ThetaTuning::Full / Partial,
-// crates/gp/src/algorithm.rs:873-960, optimization.rs:26-169): multistart COBYLA (cobyla.h: Powell's method restated, all
-// starts in lock-step through one likelihood batch per round),
-// the new theta-gradient of the likelihood and a projected L-BFGS on it.
+// Optimiser drivers above the dense likelihood (GpValidParams::fit with ThetaTuning::Full / Partial, algorithm.rs:873-960,
+// optimization.rs:26-169): multistart COBYLA on one model (egx_gp_fit, egx_gp_fit_partial, egx_sweep_fit) and on the models of a
+// group (egx_gp_fit_multi), the theta-gradient of the likelihood and a projected L-BFGS on it.  Every
+// driver is LOCK-STEP: multistart::run over one machine per start, a round's points in one evaluation call.  The box, the
+// budget, the machines, the reduction and the winner are fit_starts.h's; this file holds only what touches a handle.
 #include "gp_handle.h"
-#include "lbfgs.h"
 
 using namespace egx;
 
@@ -24,97 +24,38 @@ int fit_run_starts(egx_gp *gp, const double *theta_base /*h*/, const std::vector
     }
     const int hfull = gp->h;
     const int h = (int)active.size();  // optimised dimensions
-    if (bounds_len != 1 && bounds_len != h) {  // algorithm.rs:901-912
-        set_error("Bounds for theta should be either 1-dim or dim of xtrain (" + std::to_string(h) + "), got " +
-                  std::to_string(bounds_len));
-        return EGX_ERR_INVALID_VALUE;
-    }
-    std::vector<double> blo(h), bhi(h);
-    for (int i = 0; i < h; i++) {
-        const double l = lo[bounds_len == 1 ? 0 : i], u = hi[bounds_len == 1 ? 0 : i];
-        if (!(l > 0.0) || !(u >= l)) {
-            set_error("theta bounds must satisfy 0 < lo <= hi");
-            return EGX_ERR_INVALID_VALUE;
-        }
-        blo[i] = std::log10(l);  // optimization.rs:32-35
-        bhi[i] = std::log10(u);
-    }
+    fit::Log10Box box;
+    EGX_RC(fit_box(lo, hi, bounds_len, h, theta0s, n_starts * h, fit::Dense, box));
     EGX_RC(set_device(gp));
-    // maxeval = clamp(10 h, GP_COBYLA_MIN_EVAL = 25, max_eval)  algorithm.rs:933-936
-    int64_t per_start = 10 * (int64_t)h;
-    if (per_start < 25) per_start = 25;
-    if (max_eval >= 25 && per_start > max_eval) per_start = max_eval;
-    for (int64_t s = 0; s < n_starts * h; s++)
-        if (!(theta0s[s] > 0.0)) {
-            set_error("theta start points must be > 0");
-            return EGX_ERR_INVALID_VALUE;
-        }
     results.assign((size_t)n_starts, StartResult{std::numeric_limits<double>::quiet_NaN(), std::vector<double>(h, 0.0), 0});
     gp->fitted = false;
-    // COBYLA (cobyla.h), one machine per start, rhobeg 0.5 / ftol_rel 1e-4 (optimization.rs:16-24), all machines
-    // advanced in LOCK-STEP: their trial points form one likelihood batch per round, pipelined over the
-    // handle's workspaces (the reference runs the starts as rayon tasks, algorithm.rs:928-945)
-    std::vector<int64_t> mine;
-    for (int64_t s = rank; s < n_starts; s += world) mine.push_back(s);
-    std::vector<CobylaBox> mach;
-    mach.reserve(mine.size());
-    for (int64_t s : mine) {
-        std::vector<double> x0(h);
-        for (int i = 0; i < h; i++) x0[i] = std::log10(theta0s[s * h + i]);
-        mach.emplace_back(x0, blo, bhi, 0.5, 1e-4, per_start);
-    }
-    std::vector<double> thetas, lk, x;
+    // one COBYLA machine per start of this rank, all advanced in LOCK-STEP: their trial points form one likelihood batch per
+    // round, pipelined over the handle's workspaces (the reference runs the starts as rayon tasks, algorithm.rs:928-945)
+    const std::vector<int64_t> mine = fit::shard(n_starts, rank, world);
+    std::vector<CobylaBox> mach = fit::cobyla_machines(theta0s, h, mine, box, fit::cobyla_budget(h, max_eval));
+    std::vector<double> thetas, lk;
     std::vector<int32_t> st;
-    std::vector<size_t> who;
-    for (;;) {
-        thetas.clear();
-        who.clear();
-        for (size_t q = 0; q < mach.size(); q++)
-            if (mach[q].ask(x)) {
-                who.push_back(q);
-                const size_t off = thetas.size();
-                thetas.insert(thetas.end(), theta_base, theta_base + hfull);
-                for (int i = 0; i < h; i++) thetas[off + active[i]] = std::pow(10.0, x[i]);
-            }
-        if (who.empty()) break;
-        lk.assign(who.size(), 0.0);
-        st.assign(who.size(), 0);
-        EGX_RC(likelihood_batch_core(gp, thetas.data(), (int64_t)who.size(), hfull, lk.data(), st.data()));
-        for (size_t q = 0; q < who.size(); q++) {
-            const bool ok = st[q] == EGX_STATUS_OK && !std::isnan(lk[q]);
-            mach[who[q]].tell(ok ? -lk[q] : std::numeric_limits<double>::infinity());  // algorithm.rs:893-896
-        }
-    }
-    for (size_t q = 0; q < mach.size(); q++) {
-        const CobylaBox &m = mach[q];
-        double fb = m.best_f();
-        if (std::isnan(fb) || fb >= 1e30) fb = std::numeric_limits<double>::infinity();  // optimization.rs:153-157
-        results[(size_t)mine[q]] = StartResult{fb, m.best_x(), m.evals()};
-    }
+    int rc;
+    multistart::run(
+        mach,
+        [&](const multistart::Round &r) {
+            fit::round_thetas(r, theta_base, hfull, active, thetas);
+            lk.assign(r.size(), 0.0);
+            st.assign(r.size(), 0);
+            return likelihood_batch_core(gp, thetas.data(), (int64_t)r.size(), hfull, lk.data(), st.data());
+        },
+        [&](const multistart::Round &, size_t q, CobylaBox &m) { m.tell(fit::cobyla_objective(st[q] == EGX_STATUS_OK, lk[q])); }, rc);
+    EGX_RC(rc);
+    for (size_t q = 0; q < mach.size(); q++) results[(size_t)mine[q]] = fit::cobyla_result(mach[q]);
     return EGX_SUCCESS;
 }
 
 int fit_reduce_finalize(egx_gp *gp, const double *theta_base, const std::vector<int> &active, const double *theta0s,
                         const std::vector<StartResult> &results, int64_t *n_evals_out) {
-    const int hfull = gp->h, h = (int)active.size();
-    double best_f = std::numeric_limits<double>::infinity();
-    std::vector<double> best_x(h, 0.0);
-    int64_t evals = 0;
-    for (size_t s = 0; s < results.size(); s++) {
-        evals += results[s].evals;
-        if (results[s].f < best_f) {  // algorithm.rs:942-945 reduce to min (first wins ties)
-            best_f = results[s].f;
-            best_x = results[s].x;
-        }
-    }
-    if (n_evals_out) *n_evals_out = evals;
-    std::vector<double> th(theta_base, theta_base + hfull);
-    if (std::isfinite(best_f))
-        for (int i = 0; i < h; i++) th[active[i]] = std::pow(10.0, best_x[i]);
-    else  // every start failed: the reference falls through with ones (algorithm.rs:943) -> 10^1... keep start 0
-        for (int i = 0; i < h; i++) th[active[i]] = theta0s[i];
+    // every start failed: the reference falls through with ones (algorithm.rs:943); start 0 is kept here
+    const std::vector<double> th = fit::winner_theta(theta_base, gp->h, active, fit::best_start(results, n_evals_out), theta0s);
     EGX_RC(set_device(gp));
-    return do_finalize(gp, th.data(), hfull);
+    return do_finalize(gp, th.data(), gp->h);
 }
 
 }  // namespace egx
@@ -136,9 +77,7 @@ int32_t egx_gp_fit(egx_gp *gp, const double *theta0s, int64_t n_starts, const do
         set_error("NULL argument / no start point");
         return EGX_ERR_INVALID_VALUE;
     }
-    std::vector<int> active(gp->h);
-    for (int i = 0; i < gp->h; i++) active[i] = i;
-    return fit_nm_core(gp, theta0s, active, theta0s, n_starts, lo, hi, bounds_len, max_eval, n_evals_out);
+    return fit_nm_core(gp, theta0s, fit::all_active(gp->h), theta0s, n_starts, lo, hi, bounds_len, max_eval, n_evals_out);
 }
 
 int32_t egx_gp_fit_partial(egx_gp *gp, const double *theta_init, const int64_t *active_idx, int64_t n_active,
@@ -401,11 +340,11 @@ int32_t egx_gp_likelihood_grad_batch(egx_gp *gp, const double *thetas, int64_t k
 }
 
 /* Gradient-based alternative to egx_gp_fit (new: uses the theta-gradient the reference does not have).
- * Projected L-BFGS on x = log10(theta) inside the box, one run per start; round 4: every start is an ask / tell machine
- * and ALL starts advance in lock-step -- a round's trial points (one per start that is still running) are ONE
- * likelihood + gradient batch (egx_gp_likelihood_grad_batch), as the COBYLA starts of egx_gp_fit are one likelihood
- * batch.  Each start walks exactly the points it walks alone.  Best start wins (the first on ties), then finalize.
- * max_iter bounds the iterations per start.  The machine: LbfgsStart, lbfgs.h. */
+ * Projected L-BFGS on x = log10(theta) inside the box, one ask / tell machine per start (LbfgsStart, lbfgs.h), ALL starts in
+ * lock-step: a round's trial points (one per start that is still running) are ONE likelihood + gradient batch
+ * (egx_gp_likelihood_grad_batch), as the COBYLA starts of egx_gp_fit are one likelihood batch.  Each start walks exactly the
+ * points it walks alone.  Best start wins (the first on ties), then finalize.  max_iter bounds the iterations per start;
+ * *n_evals_out is the number of points asked. */
 int32_t egx_gp_fit_lbfgs(egx_gp *gp, const double *theta0s, int64_t n_starts, const double *lo, const double *hi,
                          int64_t bounds_len, int64_t max_iter, int64_t *n_evals_out) {
     if (!gp || !theta0s || !lo || !hi || n_starts < 1) {
@@ -413,73 +352,100 @@ int32_t egx_gp_fit_lbfgs(egx_gp *gp, const double *theta0s, int64_t n_starts, co
         return EGX_ERR_INVALID_VALUE;
     }
     const int h = gp->h;
-    if (bounds_len != 1 && bounds_len != h) {
-        set_error("Bounds for theta should be either 1-dim or dim of xtrain (" + std::to_string(h) + "), got " +
-                  std::to_string(bounds_len));
-        return EGX_ERR_INVALID_VALUE;
-    }
-    std::vector<double> blo(h), bhi(h);
-    for (int i = 0; i < h; i++) {
-        const double l = lo[bounds_len == 1 ? 0 : i], u = hi[bounds_len == 1 ? 0 : i];
-        if (!(l > 0.0) || !(u >= l)) {
-            set_error("theta bounds must satisfy 0 < lo <= hi");
-            return EGX_ERR_INVALID_VALUE;
-        }
-        blo[i] = std::log10(l);
-        bhi[i] = std::log10(u);
-    }
-    for (int64_t s = 0; s < n_starts * h; s++)
-        if (!(theta0s[s] > 0.0)) {
-            set_error("theta start points must be > 0");
-            return EGX_ERR_INVALID_VALUE;
-        }
+    fit::Log10Box box;
+    EGX_RC(fit_box(lo, hi, bounds_len, h, theta0s, n_starts * h, fit::Dense, box));
     if (max_iter < 1) max_iter = 50;
     std::unique_lock<std::shared_mutex> lock(gp->mu);
     EGX_RC(set_device(gp));
     gp->fitted = false;
     const double ln10 = std::log(10.0), inf = std::numeric_limits<double>::infinity();
-    std::vector<LbfgsStart> mach;
-    mach.reserve((size_t)n_starts);
-    for (int64_t s = 0; s < n_starts; s++) mach.emplace_back(theta0s + s * h, h, blo, bhi, max_iter);
+    const std::vector<int> active = fit::all_active(h);
+    std::vector<LbfgsStart> mach = fit::lbfgs_machines(theta0s, h, fit::shard(n_starts), box, max_iter);
     int64_t evals = 0;
-    std::vector<double> thetas, lk, gr, x, gx(h);
+    std::vector<double> thetas, lk, gr, gx(h);
     std::vector<int32_t> stv;
-    std::vector<size_t> who;
-    for (;;) {
-        thetas.clear();
-        who.clear();
-        for (size_t q = 0; q < mach.size(); q++)
-            if (mach[q].ask(x)) {
-                who.push_back(q);
-                for (int i = 0; i < h; i++) thetas.push_back(std::pow(10.0, x[i]));
-            }
-        if (who.empty()) break;
-        lk.assign(who.size(), 0.0);
-        gr.assign(who.size() * (size_t)h, 0.0);
-        stv.assign(who.size(), 0);
-        evals += (int64_t)who.size();
-        EGX_RC(likelihood_grad_batch_core(gp, thetas.data(), (int64_t)who.size(), h, lk.data(), gr.data(), stv.data()));
-        // f(x) = -L(10^x), g = -dL/dx = -theta ln10 dL/dtheta
-        for (size_t q = 0; q < who.size(); q++) {
+    int rc;
+    multistart::run(
+        mach,
+        [&](const multistart::Round &r) {
+            fit::round_thetas(r, theta0s, h, active, thetas);
+            lk.assign(r.size(), 0.0);
+            gr.assign(r.size() * (size_t)h, 0.0);
+            stv.assign(r.size(), 0);
+            evals += (int64_t)r.size();
+            return likelihood_grad_batch_core(gp, thetas.data(), (int64_t)r.size(), h, lk.data(), gr.data(), stv.data());
+        },
+        [&](const multistart::Round &, size_t q, LbfgsStart &m) {  // f(x) = -L(10^x), g = -dL/dx = -theta ln10 dL/dtheta
             const bool ok = stv[q] == EGX_STATUS_OK && std::isfinite(lk[q]);
             for (int i = 0; i < h; i++) gx[i] = ok ? -thetas[q * h + i] * ln10 * gr[q * h + i] : 0.0;
-            mach[who[q]].tell(ok ? -lk[q] : inf, gx);
-        }
-    }
-    double best_f = inf;
-    std::vector<double> best_x(h, 0.0);
-    for (const auto &m : mach)
-        if (m.f < best_f) {
-            best_f = m.f;
-            best_x = m.x;
-        }
+            m.tell(ok ? -lk[q] : inf, gx);
+        },
+        rc);
+    EGX_RC(rc);
+    std::vector<StartResult> results;
+    for (const LbfgsStart &m : mach) results.push_back(StartResult{m.f, m.x, 0});
     if (n_evals_out) *n_evals_out = evals;
-    std::vector<double> th(h);
-    if (std::isfinite(best_f))
-        for (int i = 0; i < h; i++) th[i] = std::pow(10.0, best_x[i]);
-    else
-        for (int i = 0; i < h; i++) th[i] = theta0s[i];
+    const std::vector<double> th = fit::winner_theta(theta0s, h, active, fit::best_start(results), theta0s);
     return do_finalize(gp, th.data(), h);
+}
+
+// ThetaTuning::Full across MODELS: the tuned fit of every expert of a mixture (crates/moe/src/algorithm.rs:167-177 -> :209-262 ->
+// GpValidParams::fit -> the multistart COBYLA of crates/gp/src/algorithm.rs:921-945), the k x n_starts COBYLA machines advanced
+// in lock-step: per round and start index, the trial points of all models whose machine still asks are ONE lock-step
+// evaluation across the group's slab (what egx_gp_likelihood_multi does).  A machine only ever sees the values of its own
+// model, and a model's evaluation does not depend on its companions, so every member walks the trajectory it walks under
+// egx_gp_fit on a one-workspace handle: theta*, likelihood and predictions are the same bits.
+int32_t egx_gp_fit_multi(egx_gp *const *gps, int32_t k, const double *theta0s, int64_t n_starts, const double *lo, const double *hi,
+                         int64_t bounds_len, int64_t max_eval, int64_t *n_evals_out) {
+    if (!gps || k < 1 || !theta0s || !lo || !hi || n_starts < 1) {
+        set_error("NULL argument / no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::vector<std::unique_lock<std::shared_mutex>> locks;
+    EGX_RC(lock_multi(gps, k, locks));
+    const int h = gps[0]->h;
+    for (int32_t m = 0; m < k; m++)
+        if (gps[m]->h != h) {
+            set_error("egx_gp_fit_multi: the models must have the same number of hyperparameters");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    fit::Log10Box box;
+    EGX_RC(fit_box(lo, hi, bounds_len, h, theta0s, (int64_t)k * n_starts * h, fit::Dense, box));
+    // the machines START-MAJOR, model-minor (theta0s is model-major): a round's points are contiguous per start index
+    std::vector<int64_t> rows;
+    for (int64_t st = 0; st < n_starts; st++)
+        for (int32_t m = 0; m < k; m++) rows.push_back((int64_t)m * n_starts + st);
+    std::vector<CobylaBox> mach = fit::cobyla_machines(theta0s, h, rows, box, fit::cobyla_budget(h, max_eval));
+    const std::vector<int> active = fit::all_active(h);
+    std::vector<egx_gp *> sub;
+    std::vector<int32_t> stt;
+    std::vector<double> thetas, lk;
+    int rc;
+    multistart::run(
+        mach,
+        [&](const multistart::Round &r) {
+            fit::round_thetas(r, theta0s, h, active, thetas);
+            lk.assign(r.size(), 0.0), stt.assign(r.size(), 0);
+            // start index st of every model whose machine still asks: one lock-step evaluation
+            return fit::for_each_start(r, k, [&](int64_t, size_t q0, size_t count) {
+                sub.clear();
+                for (size_t q = q0; q < q0 + count; q++) sub.push_back(gps[r.who[q] % (size_t)k]);
+                return eval_multi_locked(sub.data(), (int32_t)count, thetas.data() + q0 * (size_t)h, h, false, lk.data() + q0,
+                                         stt.data() + q0);
+            });
+        },
+        [&](const multistart::Round &, size_t q, CobylaBox &m) { m.tell(fit::cobyla_objective(stt[q] == EGX_STATUS_OK, lk[q])); }, rc);
+    EGX_RC(rc);
+    // the reduction over every model's starts, then ONE lock-step finalize
+    std::vector<double> best;
+    for (int32_t m = 0; m < k; m++) {
+        std::vector<StartResult> results;
+        for (int64_t st = 0; st < n_starts; st++) results.push_back(fit::cobyla_result(mach[(size_t)(st * k + m)]));
+        const double *theta0 = theta0s + (size_t)m * n_starts * h;
+        const std::vector<double> th = fit::winner_theta(theta0, h, active, fit::best_start(results, n_evals_out ? n_evals_out + m : nullptr), theta0);
+        best.insert(best.end(), th.begin(), th.end());
+    }
+    return eval_multi_locked(gps, k, best.data(), h, true, nullptr, nullptr);
 }
 
 // ---- kernel-level entry points ------------------------------------------------------------------

@@ -20,7 +20,7 @@
 #include "dev_mem.h"
 #include "slot_pipeline.h"
 #include "host_math.h"
-#include "cobyla.h"
+#include "fit_starts.h"  // StartResult; cobyla.h, lbfgs.h, multistart.h
 
 #define EGX_RC(call)              \
     do {                          \
@@ -127,13 +127,6 @@ struct HandleRes {
         for (const auto &w : ws) b += w.device_bytes();
         return b;
     }
-};
-
-// outcome of one start of a multistart optimisation: objective (-likelihood), its minimiser in log10 theta, evaluations
-struct StartResult {
-    double f;
-    std::vector<double> x;
-    int64_t evals;
 };
 
 struct EvalResult {
@@ -250,6 +243,14 @@ int fit_run_starts(egx_gp *gp, const double *theta_base, const std::vector<int> 
                    int world, std::vector<StartResult> &results);
 int fit_reduce_finalize(egx_gp *gp, const double *theta_base, const std::vector<int> &active, const double *theta0s,
                         const std::vector<StartResult> &results, int64_t *n_evals_out);
+// the box of a fit and its `count` start values checked (fit_starts.h); a failed check's message is this thread's error
+inline int fit_box(const double *lo, const double *hi, int64_t bounds_len, int h, const double *x0s, int64_t count, fit::Model what,
+                   fit::Log10Box &box) {
+    std::string msg;
+    if (fit::log10_box(lo, hi, bounds_len, h, what, box, msg) && fit::positive_starts(x0s, count, what, msg)) return EGX_SUCCESS;
+    set_error(msg);
+    return EGX_ERR_INVALID_VALUE;
+}
 }  // namespace egx
 
 // x_mean (d) | x_std (d) on the device, behind the coefficients of the fit in the same allocation
@@ -330,10 +331,12 @@ int posterior_solve(egx_gp *gp, hipStream_t st, const double *xqT, int m_pad, do
 int posterior_solve_run(egx_gp *const *gps, int len, hipStream_t st, const double *xqT, int m_pad, double *RT, double *s0, double *sl);
 // predict_impl's batched route for such a run: member j answers xq[j] (m rows) into yout[j] / vout[j]
 int predict_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m, double *const *yout, double *const *vout);
-// gp_host.hip: the run of a multi-model call that starts at gps[i] (members of one group in consecutive slots), and the
-// exclusive locks of its k distinct handles in a fixed order
+// gp_host.hip: the run of a multi-model call that starts at gps[i] (members of one group in consecutive slots), the exclusive
+// locks of its k distinct handles in a fixed order, and -- under them -- model j's likelihood at row j of thetas (or its fit)
 int run_len_multi(egx_gp *const *gps, int k, int i);
 int lock_multi(egx_gp *const *gps, int32_t k, std::vector<std::unique_lock<std::shared_mutex>> &locks);
+int eval_multi_locked(egx_gp *const *gps, int32_t k, const double *thetas, int64_t theta_len, bool finalize, double *lkh,
+                      int32_t *status);
 int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt);
 int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int m_pad, double *Wt);
 // how many parts the training range is split into so that few queries still fill the chip (the caller adds the partial sums

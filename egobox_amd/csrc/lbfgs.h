@@ -1,8 +1,9 @@
 // Projected L-BFGS on a box as an ask / tell machine, one per start point: the caller evaluates the objective and its gradient
 // at the point ask() hands out and reports them with tell().  The variable is x = log10(parameter); a step moves at most one
 // decade, the line search is Armijo on the projected step, the memory is 8 pairs.  Host only (no device code: compiles under
-// g++, tests/c_host/lbfgs_test.cpp).  Used by egx_gp_fit_lbfgs (gp_fit.hip, every start in lock-step) and egx_sgp_fit_lbfgs
-// (sgp_host.hip, the starts one after the other); egx_sgp_fit_lbfgs_z adds one start in mixed variables (LbfgsStart::Linear).
+// g++, tests/c_host/lbfgs_test.cpp).  The machines of a fit's starts are built by fit_starts.h (lbfgs_machines: they point into
+// its Log10Box) and driven by multistart::run: egx_gp_fit_lbfgs (gp_fit.hip) every start in lock-step, egx_sgp_fit_lbfgs
+// (sgp_host.hip) the starts one after the other; egx_sgp_fit_lbfgs_z adds one start in mixed variables (LbfgsStart::Linear).
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -1,10 +1,11 @@
-// The lock-step multistart of the infill optimisers (infill_optimize.hip), without HIP: every start is one resumable
-// (ask / tell) machine -- CobylaBox, Cobyla (cobyla.h) or Slsqp (slsqp.h) -- and a ROUND hands the points all unfinished
-// machines ask for to ONE evaluation, then tells every machine its answer (the reference runs its starts one after the
-// other, crates/ego/src/solver/solver_infill_optim.rs:206-236).  A machine sees only its own points and values, so a start
-// walks bit for bit the points it walks alone, whatever its companions do.
-// Beside the round loop: the argument check of the three entry points with its messages, the evaluation budget's
-// default, and the two rules that pick the winning start.
+// The lock-step multistart of the infill optimisers (infill_optimize.hip) and of the hyperparameter fits (gp_fit.hip,
+// sgp_host.hip through fit_starts.h), without HIP: every start is one resumable (ask / tell) machine -- CobylaBox, Cobyla
+// (cobyla.h), Slsqp (slsqp.h) or LbfgsStart (lbfgs.h) -- and a ROUND hands the points all unfinished machines ask for to ONE
+// evaluation, then tells every machine its answer (the reference runs its starts one after the other,
+// crates/ego/src/solver/solver_infill_optim.rs:206-236, or as rayon tasks, crates/gp/src/algorithm.rs:928-945).  A machine sees
+// only its own points and values, so a start walks bit for bit the points it walks alone, whatever its companions do.
+// Beside the round loop, for the infill optimisers (the fits': fit_starts.h): the argument check of the three entry points
+// with its messages, the evaluation budget's default, and the two rules that pick the winning start.
 #pragma once
 #include <algorithm>
 #include <cmath>

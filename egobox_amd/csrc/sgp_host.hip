@@ -21,9 +21,7 @@
 #include <mutex>
 #include <vector>
 
-#include "sgp_handle.h"
-#include "cobyla.h"
-#include "lbfgs.h"
+#include "sgp_handle.h"  // (gp_handle.h: fit_starts.h with the optimisers' machines and the rules of a multistart fit)
 
 using namespace egx;
 
@@ -202,34 +200,14 @@ int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, 
     return EGX_SUCCESS;
 }
 
-// The box of a fit in x = log10(params) and the checks of its arguments (egx_sgp_fit, egx_sgp_fit_lbfgs): np parameters per start
-int sgp_fit_box(const double *params0s, int64_t n_starts, const double *lo, const double *hi, int np, std::vector<double> &blo,
-                std::vector<double> &bhi) {
-    blo.resize(np);
-    bhi.resize(np);
-    for (int i = 0; i < np; i++) {
-        if (!(lo[i] > 0.0) || !(hi[i] >= lo[i])) {
-            set_error("sparse GP parameter bounds must satisfy 0 < lo <= hi");
-            return EGX_ERR_INVALID_VALUE;
-        }
-        blo[i] = std::log10(lo[i]);
-        bhi[i] = std::log10(hi[i]);
-    }
-    for (int64_t i = 0; i < n_starts * np; i++)
-        if (!(params0s[i] > 0.0)) {
-            set_error("sparse GP start points must be > 0");
-            return EGX_ERR_INVALID_VALUE;
-        }
-    return EGX_SUCCESS;
-}
-
-// The end of a fit: the keeping evaluation at the best start's point (f = -likelihood at x = log10(params))
-int sgp_fit_keep(egx_sgp *g, double best_f, const std::vector<double> &best_x, int estimate_noise, double noise_fixed) {
+// The end of a fit: the keeping evaluation at the best start's point x = log10(params); nullptr: no start ended finite
+int sgp_fit_keep(egx_sgp *g, const StartResult *best, int estimate_noise, double noise_fixed) {
     const int d = g->d;
-    if (!std::isfinite(best_f)) {
+    if (!best) {
         set_error("sparse GP: no start point gave a finite likelihood");
         return EGX_ERR_LIKELIHOOD;
     }
+    const std::vector<double> &best_x = best->x;
     std::vector<double> th(d);
     for (int i = 0; i < d; i++) th[i] = std::pow(10.0, best_x[i]);
     Eval ev;
@@ -269,26 +247,23 @@ int sgp_eval_grad_x(egx_sgp *g, const std::vector<double> &xv, int estimate_nois
     return EGX_SUCCESS;
 }
 
-// The starts of egx_sgp_fit_lbfgs, one after the other: the best (f, x = log10 params), the first on ties, and the evaluations
-int sgp_lbfgs_starts(egx_sgp *g, const double *params0s, int64_t n_starts, int np, const std::vector<double> &blo,
-                     const std::vector<double> &bhi, int estimate_noise, double noise_fixed, int64_t max_iter, double &best_f,
-                     std::vector<double> &best_x, int64_t &evals) {
-    std::vector<double> xv, gx;
-    best_f = std::numeric_limits<double>::infinity();
-    evals = 0;
-    for (int64_t st = 0; st < n_starts; st++) {
-        LbfgsStart m(params0s + st * np, np, blo, bhi, max_iter);
-        while (m.ask(xv)) {
-            double f;
-            EGX_RC(sgp_eval_grad_x(g, xv, estimate_noise, noise_fixed, f, gx));
+// One L-BFGS machine after the other (fit_starts.h run_sequential: the handle has ONE workspace, and sgp_grad_tail reads what
+// sgp_eval of the same point left in it), each point through eval(x, f, gx) -> rc.  results: (f, x) per machine; evals grows by
+// the points asked.
+template <class EvalGrad>
+int sgp_lbfgs_run(std::vector<LbfgsStart> &mach, EvalGrad &&eval, std::vector<StartResult> &results, int64_t &evals) {
+    double f = 0.0;
+    std::vector<double> gx;
+    int rc;
+    fit::run_sequential(
+        mach,
+        [&](const multistart::Round &r) {
             evals++;
-            m.tell(f, gx);
-        }
-        if (m.f < best_f) {
-            best_f = m.f;
-            best_x = m.x;
-        }
-    }
+            return eval(r.pts, f, gx);
+        },
+        [&](const multistart::Round &, size_t, LbfgsStart &m) { m.tell(f, gx); }, rc);
+    EGX_RC(rc);
+    for (const LbfgsStart &m : mach) results.push_back(StartResult{m.f, m.x, 0});
     return EGX_SUCCESS;
 }
 
@@ -573,7 +548,9 @@ int32_t egx_sgp_finalize(egx_sgp *g, const double *theta, int64_t theta_len, dou
 }
 
 // Multistart derivative-free fit over x = log10([theta_1..theta_d, sigma2, (noise)]) (sparse_algorithm.rs:488-650):
-// params0s is (n_starts x np) in parameter space, lo/hi (np) its box, np = d + 1 + estimate_noise.
+// params0s is (n_starts x np) in parameter space, lo/hi (np) its box, np = d + 1 + estimate_noise.  COBYLA as for the dense model
+// (sparse_algorithm.rs:597-611), one start after the other.  An evaluation that fails with a HIP or argument error ends the fit
+// AT ONCE with its code (it used to go on evaluating and return that same first code at the end).
 int32_t egx_sgp_fit(egx_sgp *g, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
                     int32_t estimate_noise, double noise_fixed, int64_t max_eval, int64_t *n_evals_out) {
     if (!g || !params0s || !lo || !hi || n_starts < 1) {
@@ -583,76 +560,37 @@ int32_t egx_sgp_fit(egx_sgp *g, const double *params0s, int64_t n_starts, const 
     std::lock_guard<std::mutex> lock(g->mu);
     EGX_HIP_CHECK(hipSetDevice(g->device));
     const int d = g->d, np = d + 1 + (estimate_noise ? 1 : 0);
-    std::vector<double> blo, bhi;
-    EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
-    // maxeval = clamp(10 * theta_dim, 25, max_eval)  sparse_algorithm.rs:601-603
-    int64_t per_start = 10 * (int64_t)d;
-    if (per_start < 25) per_start = 25;
-    if (max_eval >= 25 && per_start > max_eval) per_start = max_eval;
-    int first_rc = EGX_SUCCESS;
-    auto objective = [&](const std::vector<double> &xv) -> double {
-        std::vector<double> th(d);
-        for (int i = 0; i < d; i++) th[i] = std::pow(10.0, xv[i]);
-        const double s2 = std::pow(10.0, xv[d]);
-        const double nv = estimate_noise ? std::pow(10.0, xv[d + 1]) : noise_fixed;
-        Eval ev;
-        const int rc = sgp_eval(g, th.data(), d, s2, nv, ev, false);
-        if (rc) {
-            if (!first_rc) first_rc = rc;
-            return std::numeric_limits<double>::infinity();
-        }
-        if (ev.status != EGX_STATUS_OK) return std::numeric_limits<double>::infinity();
-        return -ev.lkh;
-    };
-    double best_f = std::numeric_limits<double>::infinity();
-    std::vector<double> best_x;
-    int64_t evals = 0;
-    for (int64_t st = 0; st < n_starts; st++) {
-        std::vector<double> x0(np);
-        for (int i = 0; i < np; i++) x0[i] = std::log10(params0s[st * np + i]);
-        // COBYLA as the reference configures it for the sparse model too (sparse_algorithm.rs:597-611 ->
-        // optimization.rs:122-169)
-        StartResult r;
-        {
-            CobylaBox m(x0, blo, bhi, 0.5, 1e-4, per_start);
-            std::vector<double> xv;
-            while (m.ask(xv)) m.tell(objective(xv));
-            double fb = m.best_f();
-            if (std::isnan(fb) || fb >= 1e30) fb = std::numeric_limits<double>::infinity();
-            r = StartResult{fb, m.best_x(), m.evals()};
-        }
-        evals += r.evals;
-        if (r.f < best_f) {
-            best_f = r.f;
-            best_x = r.x;
-        }
-    }
-    if (first_rc) return first_rc;
-    if (n_evals_out) *n_evals_out = evals;
-    return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);
+    fit::Log10Box box;
+    EGX_RC(fit_box(lo, hi, np, np, params0s, n_starts * np, fit::Sparse, box));
+    // the budget counts the theta dimensions, not np (sparse_algorithm.rs:601-603)
+    std::vector<CobylaBox> mach = fit::cobyla_machines(params0s, np, fit::shard(n_starts), box, fit::cobyla_budget(d, max_eval));
+    Eval ev;
+    int rc;
+    fit::run_sequential(
+        mach,
+        [&](const multistart::Round &r) {
+            const double *xv = r.pts.data();
+            std::vector<double> th(d);
+            for (int i = 0; i < d; i++) th[i] = std::pow(10.0, xv[i]);
+            const double s2 = std::pow(10.0, xv[d]);
+            const double nv = estimate_noise ? std::pow(10.0, xv[d + 1]) : noise_fixed;
+            ev = Eval();
+            return sgp_eval(g, th.data(), d, s2, nv, ev, false);
+        },
+        [&](const multistart::Round &, size_t, CobylaBox &m) { m.tell(fit::cobyla_objective(ev.status == EGX_STATUS_OK, ev.lkh)); }, rc);
+    EGX_RC(rc);
+    std::vector<StartResult> results;
+    for (const CobylaBox &m : mach) results.push_back(fit::cobyla_result(m));
+    return sgp_fit_keep(g, fit::best_start(results, n_evals_out), estimate_noise, noise_fixed);
 }
 
 // The gradient-based counterpart of egx_sgp_fit (new: on the closed-form gradient, sgp_grad.hip): a projected L-BFGS (lbfgs.h) per
 // start on x = log10(params), same parameter layout, box and checks.  The starts run one after the other -- the handle has one
 // workspace --, the best wins (the first on ties), one keeping evaluation follows.  max_iter < 1: 50 iterations per start.
+// It is egx_sgp_fit_lbfgs_z without a phase 2 (the points' default box, the range of the training inputs, always passes).
 int32_t egx_sgp_fit_lbfgs(egx_sgp *g, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
                           int32_t estimate_noise, double noise_fixed, int64_t max_iter, int64_t *n_evals_out) {
-    if (!g || !params0s || !lo || !hi || n_starts < 1) {
-        set_error("NULL argument / no start point");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(g->mu);
-    EGX_HIP_CHECK(hipSetDevice(g->device));
-    const int np = g->d + 1 + (estimate_noise ? 1 : 0);
-    std::vector<double> blo, bhi;
-    EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
-    if (max_iter < 1) max_iter = 50;
-    double best_f;
-    std::vector<double> best_x;
-    int64_t evals = 0;
-    EGX_RC(sgp_lbfgs_starts(g, params0s, n_starts, np, blo, bhi, estimate_noise, noise_fixed, max_iter, best_f, best_x, evals));
-    if (n_evals_out) *n_evals_out = evals;
-    return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);
+    return egx_sgp_fit_lbfgs_z(g, params0s, n_starts, lo, hi, estimate_noise, noise_fixed, max_iter, nullptr, nullptr, 0, n_evals_out);
 }
 
 // egx_sgp_likelihood_grad (the same launches first: the same bits of *lkh and grad) and the gradient in the inducing points,
@@ -719,8 +657,8 @@ int32_t egx_sgp_fit_lbfgs_z(egx_sgp *g, const double *params0s, int64_t n_starts
     std::lock_guard<std::mutex> lock(g->mu);
     EGX_HIP_CHECK(hipSetDevice(g->device));
     const int d = g->d, nz = g->nz, np = d + 1 + (estimate_noise ? 1 : 0);
-    std::vector<double> blo, bhi;
-    EGX_RC(sgp_fit_box(params0s, n_starts, lo, hi, np, blo, bhi));
+    fit::Log10Box pbox;
+    EGX_RC(fit_box(lo, hi, np, np, params0s, n_starts * np, fit::Sparse, pbox));
     ZBox box;
     box.nz = nz;
     box.d = d;
@@ -731,42 +669,42 @@ int32_t egx_sgp_fit_lbfgs_z(egx_sgp *g, const double *params0s, int64_t n_starts
             set_error("sparse GP inducing-point bounds must be finite with z_lo <= z_hi");
             return EGX_ERR_INVALID_VALUE;
         }
-    if (max_iter < 1) max_iter = 50;
     if (max_iter_z < 0) max_iter_z = 50;
-    double best_f;
-    std::vector<double> best_x;
+    std::vector<StartResult> results;
     int64_t evals = 0;
-    EGX_RC(sgp_lbfgs_starts(g, params0s, n_starts, np, blo, bhi, estimate_noise, noise_fixed, max_iter, best_f, best_x, evals));
-    if (max_iter_z > 0 && std::isfinite(best_f)) {
+    std::vector<LbfgsStart> starts = fit::lbfgs_machines(params0s, np, fit::shard(n_starts), pbox, max_iter < 1 ? 50 : max_iter);
+    EGX_RC(sgp_lbfgs_run(
+        starts, [&](const std::vector<double> &xv, double &f, std::vector<double> &gx) { return sgp_eval_grad_x(g, xv, estimate_noise, noise_fixed, f, gx); },
+        results, evals));
+    const StartResult *best = fit::best_start(results);
+    std::vector<StartResult> end;  // phase 2's
+    if (max_iter_z > 0 && best) {
         box.z0 = g->z_host;
         const size_t nu = (size_t)nz * d;
-        std::vector<double> x0(np + nu), xlo(np + nu, 0.0), xhi(np + nu, 1.0), xv, gx;
+        std::vector<double> x0(np + nu), xlo(np + nu, 0.0), xhi(np + nu, 1.0);
         for (int i = 0; i < np; i++) {
-            x0[i] = best_x[i];
-            xlo[i] = blo[i];
-            xhi[i] = bhi[i];
+            x0[i] = best->x[i];
+            xlo[i] = pbox.lo[i];
+            xhi[i] = pbox.hi[i];
         }
         for (size_t e = 0; e < nu; e++) {
             const int k = (int)(e % (size_t)d);
             x0[np + e] = box.hi[k] > box.lo[k] ? (box.z0[e] - box.lo[k]) / (box.hi[k] - box.lo[k]) : 0.0;
         }
-        LbfgsStart m(LbfgsStart::Linear(), x0.data(), (int)(np + nu), xlo, xhi, max_iter_z);
-        while (m.ask(xv)) {
-            double f;
-            EGX_RC(sgp_eval_grad_xz(g, xv, np, estimate_noise, noise_fixed, box, f, gx));
-            evals++;
-            m.tell(f, gx);
-        }
+        std::vector<LbfgsStart> mach;
+        mach.emplace_back(LbfgsStart::Linear(), x0.data(), (int)(np + nu), xlo, xhi, max_iter_z);
+        EGX_RC(sgp_lbfgs_run(
+            mach, [&](const std::vector<double> &xv, double &f, std::vector<double> &gx) { return sgp_eval_grad_xz(g, xv, np, estimate_noise, noise_fixed, box, f, gx); },
+            end, evals));
         std::vector<double> z = box.z0;
-        if (m.f < best_f) {
-            best_f = m.f;
-            best_x.assign(m.x.begin(), m.x.begin() + np);
-            box.to_z(m.x.data() + np, z);
+        if (end[0].f < best->f) {
+            box.to_z(end[0].x.data() + np, z);
+            best = &end[0];  // (the keeping evaluation reads its first np variables)
         }
         EGX_RC(sgp_upload_z(g, z.data()));
     }
     if (n_evals_out) *n_evals_out = evals;
-    return sgp_fit_keep(g, best_f, best_x, estimate_noise, noise_fixed);
+    return sgp_fit_keep(g, best, estimate_noise, noise_fixed);
 }
 
 // Fitted state: theta (d), sigma2, noise, likelihood, Woodbury vector (nz) and -- computed on the host from the two

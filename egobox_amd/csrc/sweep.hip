@@ -546,8 +546,7 @@ int32_t egx_sweep_fit(egx_sweep *sw, const double *theta0s, int64_t n_starts, co
     }
     egx_gp *gp = sw->gp;
     const int h = gp->h, world = sw->world;
-    std::vector<int> active(h);
-    for (int i = 0; i < h; i++) active[i] = i;
+    const std::vector<int> active = fit::all_active(h);
     std::vector<StartResult> results;
     // one critical section on the replica from the first evaluation to the finalized model (the all-gather included: it has
     // its own deadline), as egx_gp_fit is on a plain handle.  Lock order as in egx_sweep_likelihood: the sweep, then its model.
@@ -569,12 +568,10 @@ int32_t egx_sweep_fit(egx_sweep *sw, const double *theta0s, int64_t n_starts, co
     std::vector<double> all;
     (void)set_device(gp);
     EGX_RC(sweep_exchange_status(sw, "egx_sweep_fit", local_rc, local_msg, part, all));
-    results.assign((size_t)n_starts, StartResult{std::numeric_limits<double>::infinity(), std::vector<double>(h, 0.0), 0});
+    results.clear();
     for (int64_t s = 0; s < n_starts; s++) {
         const double *q = all.data() + (size_t)(s % world) * part.size() + 1 + (size_t)s * per;
-        results[(size_t)s].f = q[0];
-        results[(size_t)s].evals = (int64_t)q[1];
-        results[(size_t)s].x.assign(q + 2, q + 2 + h);
+        results.push_back(StartResult{q[0], std::vector<double>(q + 2, q + 2 + h), (int64_t)q[1]});
     }
     return fit_reduce_finalize(gp, theta0s, active, theta0s, results, n_evals_out);
 }

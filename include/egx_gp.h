@@ -614,7 +614,8 @@ int32_t egx_sgp_likelihood(egx_sgp *sgp, const double *theta, int64_t theta_len,
 /* keep the state of one evaluation resident = a fit at fixed parameters */
 int32_t egx_sgp_finalize(egx_sgp *sgp, const double *theta, int64_t theta_len, double sigma2, double noise);
 /* SgpValidParams::fit :488-650: multistart derivative-free maximisation over log10 [theta.., sigma2, (noise)];
- * params0s (n_starts x np), lo / hi (np), np = d + 1 + (estimate_noise != 0); maxeval = clamp(10 d, 25, max_eval) */
+ * params0s (n_starts x np), lo / hi (np), np = d + 1 + (estimate_noise != 0); maxeval = clamp(10 d, 25, max_eval).
+ * An evaluation that fails with a HIP or argument error ends the fit at once with that code. */
 int32_t egx_sgp_fit(egx_sgp *sgp, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
                     int32_t estimate_noise, double noise_fixed, int64_t max_eval, int64_t *n_evals_out);
 /* No counterpart in the reference (it tunes the sparse model derivative-free): the likelihood of egx_sgp_likelihood -- the same
