@@ -177,6 +177,8 @@ SIGNATURES = [
     ("egx_gp_predict_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_var_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_predict_valvar_gradients", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    ("egx_gp_predict_valvar_gradients_multi", C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, c_double_p, C.c_int64, c_double_p,
+                                                          c_double_p]),
     ("egx_gp_predict_covariance", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
     ("egx_gp_sample", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, c_double_p, c_double_p,
                                   c_double_p]),
@@ -279,6 +281,7 @@ SIGNATURES = [
     ("egx_infill_set_active", C.c_int32, [C.c_void_p, c_int32_p, C.c_int32, c_double_p]),
     ("egx_infill_clear_active", C.c_int32, [C.c_void_p]),
     ("egx_infill_get_active", C.c_int32, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
+    ("egx_infill_get_runs", C.c_int32, [C.c_void_p, c_int32_p, c_int32_p]),
 ]
 
 

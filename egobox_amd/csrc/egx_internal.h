@@ -71,6 +71,7 @@ struct PosteriorBatch {
     int count = 1;
     PosteriorBatchPtrs ptrs{};
     int64_t sq = 0, sracc = 0, sR = 0, ss0 = 0, ssl = 0;  // doubles between two members' xqT / racc / R (RT) / s0 / sl blocks
+    int64_t sW = 0, sout = 0;  // ... their (n_pad x m_pad) weight matrices and their partial-sum blocks       launch_xgrad
 };
 // full (m_pad x n_pad) cross correlation block, row-major into R (ld), no diagonal handling
 int launch_cross_corr(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx,
@@ -112,12 +113,23 @@ inline int launch_predict_mean(hipStream_t s, int corr, const double *xqT, int64
 // xs[k][i] = coef[k] * xT[k][i] over a (d x ldx) k-major array
 int launch_scale_rows(hipStream_t s, const double *xT, int64_t ldx, int d, const double *coef, double *xs);
 // x-gradient contraction out[split][a][k] = sum_j w(j, a) d r(x_a, x_j) / d x_ak over the split's training range;
-// Wt = gamma (vec != 0, ldw ignored) or the transposed (n x m_pad) weight matrix; m_pad multiple of 128.
+// the weights are the member's gamma (vec != 0: pb.ptrs.gamma, Wt and ldw ignored) or its transposed (n x m_pad) weight matrix
+// at Wt + z * pb.sW; m_pad multiple of 128.  blockIdx.z = member of the posterior batch: its own training inputs and
+// coefficients (pb.ptrs.xT / coef), its query block pb.sq and its partial sums (nsplit x m_pad x d) pb.sout doubles behind the
+// previous member's.  nsplit is the caller's, from ONE member's shape (xgrad_splits): it fixes the order of the partial sums.
 // cols (a DEVICE array of ncols distinct column indices in [0, d), or nullptr): the column-list form -- the listed columns k
 // alone, with the bits of the full form, and +0.0 in every other column of out
-int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT, int64_t ldx,
-                 int n, int d, const double *coef, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit,
-                 double *out, const int *cols = nullptr, int ncols = 0);
+int launch_xgrad(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx, int n,
+                 int d, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit, double *out, const int *cols = nullptr,
+                 int ncols = 0);
+// ... of one model: a batch of one (Wt = gamma with vec != 0)
+inline int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT, int64_t ldx,
+                        int n, int d, const double *coef, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit,
+                        double *out, const int *cols = nullptr, int ncols = 0) {
+    PosteriorBatch pb;
+    pb.ptrs.xT[0] = xT, pb.ptrs.coef[0] = coef, pb.ptrs.gamma[0] = vec ? Wt : nullptr;
+    return launch_xgrad(s, corr, pb, xqT, ldq, m_pad, ldx, n, d, hcols, Wt, ldw, vec, nsplit, out, cols, ncols);
+}
 // few-query form of launch_xgrad with a weight VECTOR: out (ceil(n / 256) x m x d) partial sums, lanes over training points
 int launch_xgrad_point(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m, const double *xT, int64_t ldx, int n,
                        int d, const double *coef, int hcols, const double *wvec, double *out);
@@ -206,8 +218,17 @@ struct Params;
 // non-finite coordinate are zeroed and flagged (flag: kTile ints or nullptr), the slots beyond mt are zero.
 // spec != nullptr (mixint.h): the coordinates are cast as they are read, and xcast (mt x d, or nullptr) receives the tile's CAST
 // raw rows -- what k_infill_mix reads in place of xq, so that the responsibilities see the cast point as the experts do
-int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag,
-                          const mixint::Col *spec = nullptr, double *xcast = nullptr);
+// The member of a RUN of models (infill_runs.h) is a grid coordinate of the five kernels below: pb.count models read the same raw
+// tile, member z through pb.ptrs.par[z] (and .spec[z]: all typed alike, or none) into xqT + z * pb.sq; flag and xcast are member
+// 0's to write.  One model is a run of one.
+int launch_infill_prepare(hipStream_t s, const PosteriorBatch &pb, const double *xq, int mt, int d, double *xqT, int *flag,
+                          double *xcast = nullptr);
+inline int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag,
+                                 const mixint::Col *spec = nullptr, double *xcast = nullptr) {
+    PosteriorBatch pb;
+    pb.ptrs.par[0] = par, pb.ptrs.spec[0] = spec;
+    return launch_infill_prepare(s, pb, xq, mt, d, xqT, flag, xcast);
+}
 struct InfillTrend {
     int p = 1, rp = 0, msplit = 1;
     const double *xqT = nullptr;   // d x kTile
@@ -220,10 +241,22 @@ struct InfillTrend {
     double *mean = nullptr, *var = nullptr;  // kTile each
     double *dneg = nullptr;        // kTile x rp: -D = -B^-1 A^T zero padded, or nullptr (values only)
 };
-int launch_infill_trend(hipStream_t s, const InfillTrend &t);
+// t[0 .. count): the members of a run, every pointer the member's own (its blocks of the caller's layout among them); the members
+// have one trend and one split count
+int launch_infill_trend(hipStream_t s, const InfillTrend *t, int count);
+inline int launch_infill_trend(hipStream_t s, const InfillTrend &t) { return launch_infill_trend(s, &t, 1); }
 // gmean / gvar (kTile x d) from launch_xgrad's partial sums (nsplit x kTile x d each), original units
-int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *out_v,
-                               const double *x_std, double *gmean, double *gvar);
+struct InfillFinish {
+    const double *out_y = nullptr, *out_v = nullptr;  // the member's partial sums
+    const double *x_std = nullptr;                    // d
+    double *gmean = nullptr, *gvar = nullptr;         // kTile x d each (this tile of this model)
+};
+int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend *t, const InfillFinish *f, int count, int d, int nsplit);
+inline int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *out_v,
+                                      const double *x_std, double *gmean, double *gvar) {
+    const InfillFinish f{out_y, out_v, x_std, gmean, gvar};
+    return launch_infill_xgrad_finish(s, &t, &f, 1, d, nsplit);
+}
 // A surrogate with k >= 2 experts, one tile: the mixture's responsibilities at the tile's raw points and the recombination of
 // the experts' tables (expert c of point a at c * estride + a, gradients at (c * estride + a) * d) into the surrogate's slot.
 struct InfillMix {
@@ -247,9 +280,14 @@ int launch_infill_combine(hipStream_t s, const infill::Params &prm, int k, int d
                           double *value, double *grad);
 // The mean halves of launch_infill_trend / _xgrad_finish / _mix (a constraint surrogate under EGX_CSTR_MEAN): s0, sl, R, Rt,
 // dneg, out_v, evar, egvar, var, gvar are not read or written; the means keep the bits of the full forms.
-int launch_infill_trend_mean(hipStream_t s, const InfillTrend &t);
-int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *x_std,
-                                    double *gmean);
+int launch_infill_trend_mean(hipStream_t s, const InfillTrend *t, int count);
+inline int launch_infill_trend_mean(hipStream_t s, const InfillTrend &t) { return launch_infill_trend_mean(s, &t, 1); }
+int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend *t, const InfillFinish *f, int count, int d, int nsplit);
+inline int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y,
+                                           const double *x_std, double *gmean) {
+    const InfillFinish f{out_y, nullptr, x_std, gmean, nullptr};
+    return launch_infill_xgrad_finish_mean(s, &t, &f, 1, d, nsplit);
+}
 int launch_infill_mix_mean(hipStream_t s, const InfillMix &g);
 // A SPARSE expert's tails for one tile (sgp_predict.hip's host arithmetic): mean (kTile) = the msplit partial sums of
 // launch_predict_mean (racc: msplit x kTile; the weight vector carries sigma2) in split order; var (kTile, or nullptr: the

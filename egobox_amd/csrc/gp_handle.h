@@ -175,6 +175,11 @@ struct GroupSlabs {
     Slabs slabs;
     int device = 0, k = 0;
     int64_t sync_off = 0;  // of the group's I slab
+    // x-gradient state of the members (lazy, ensure_winv): C^-T (n_pad^2 doubles per slot) and -R^-1 F (n_pad x rhs_pad per slot)
+    // at one stride, so that a run of members takes its weight GEMMs in lock-step; winv_mu guards the allocation (members of a
+    // group may be called from different threads)
+    DevMem<double> W, NK;
+    std::mutex winv_mu;
     ~GroupSlabs();  // gp_host.hip: the slabs go to the resource pool (the next group of this shape adopts them), or are freed
 };
 }  // namespace egx
@@ -216,7 +221,8 @@ struct egx_gp : egx::HandleRes {
     egx::DevMem<double> slab_W, d_wabs;
     int slab_W_count = 0;
     // x-gradient state (lazy, per fitted factor): d_W = C^-T of the FITTED factor and
-    // -R^-1 F = -C^-T ft as an (n_pad x rhs_pad) matrix
+    // -R^-1 F = -C^-T ft as an (n_pad x rhs_pad) matrix.  A lone handle's own; a member of a group has its slot of the group's
+    // W / NK instead: read both through dev_winv() / dev_neg_invkf()
     egx::DevMem<double> d_W, d_neg_invkf;
     std::vector<double> h_neg_invkf;  // host copy (n x p) for the single-point path
     // device scratch of the single-point path, allocated once (a hipMalloc per call would cost more than the kernels)
@@ -266,6 +272,16 @@ inline const egx::mixint::Col *dev_spec(const egx_gp *gp) {
 // coordinate j of the query row as the model sees it: cast when the handle carries xtypes (the same text as the device's)
 inline double query_coord(const egx_gp *gp, const double *row, int j) {
     return gp->xspec.empty() ? row[j] : egx::mixint::cast_coord(gp->xspec.cols.data(), gp->xspec.vals.data(), row, 1, j);
+}
+// C^-T and -R^-1 F of the fitted factor (ensure_winv), or nullptr before the first use: the handle's own, or its slot of the
+// group's slab
+inline double *dev_winv(const egx_gp *gp) {
+    if (!gp->group) return gp->d_W.p;
+    return gp->group->W.p ? gp->group->W.p + (size_t)gp->group_slot * gp->n_pad * gp->n_pad : nullptr;
+}
+inline double *dev_neg_invkf(const egx_gp *gp) {
+    if (!gp->group) return gp->d_neg_invkf.p;
+    return gp->group->NK.p ? gp->group->NK.p + (size_t)gp->group_slot * gp->n_pad * gp->rhs_pad : nullptr;
 }
 inline double *dev_xnorm(const egx_gp *gp) { return gp->d_fit_coef + (size_t)gp->d * (gp->has_w ? gp->h : 1); }
 
@@ -339,6 +355,12 @@ int eval_multi_locked(egx_gp *const *gps, int32_t k, const double *thetas, int64
                       int32_t *status);
 int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt);
 int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int m_pad, double *Wt);
+// ... for a run of `len` members of a group in consecutive slots (ensure_winv done for each): one GEMM launch each, the blocks
+// of member j at RT + j m_pad n_pad, dneg + j m_pad rhs_pad, Wt + j n_pad m_pad; the two above are these with len = 1
+int posterior_weights_run(egx_gp *const *gps, int len, hipStream_t st, const double *RT, int m_pad, double *Wt);
+int posterior_weights_trend_run(egx_gp *const *gps, int len, hipStream_t st, const double *dneg, int m_pad, double *Wt);
+// xgrad_impl's batched route for such a run: member j answers xq[j] (m rows) into gy[j] / gv[j] (m x d each)
+int xgrad_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m, double *const *gy, double *const *gv);
 // how many parts the training range is split into so that few queries still fill the chip (the caller adds the partial sums
 // in order): launch_predict_mean's over rows = n_pad, launch_xgrad's over rows = n
 int mean_splits(int rows, int m_pad);

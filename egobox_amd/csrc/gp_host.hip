@@ -1280,7 +1280,7 @@ static int create_handle(const egx_gp_config *cfg_in, const double *x, const dou
     for (int i = 0; i < nws; i++) set_views(gp, gp->ws[(size_t)i], i);
     EGX_HIP_CHECK(hipMemcpy(gp->d_xT, xT.data(), sizeof(double) * xT.size(), hipMemcpyHostToDevice));
     EGX_HIP_CHECK(hipMemcpy(gp->d_rhsT, rhsT.data(), sizeof(double) * rhsT.size(), hipMemcpyHostToDevice));
-    {  // normalisation parameters for the query-side kernel (gp_predict.hip upload_queries)
+    {  // normalisation parameters for the query-side kernel (launch_normalize_queries)
         std::vector<double> par(gp->x_mean);
         par.insert(par.end(), gp->x_std.begin(), gp->x_std.end());
         EGX_HIP_CHECK(hipMemcpy(dev_xnorm(gp), par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));

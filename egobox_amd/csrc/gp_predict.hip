@@ -9,28 +9,6 @@ namespace egx {
 
 
 // ---- prediction -------------------------------------------------------------------------------
-// Upload a chunk of query points as the caller holds it and normalise it (algorithm.rs:254) into the k-major layout
-// (d x m_pad, zero padded) ON THE DEVICE: the host loop this replaces (a division and a strided store per coordinate) cost
-// four times the prediction kernel for 100 000 points.  xn (the normalised rows on the host) is filled only when the trend
-// needs the coordinates (Linear / Quadratic).  xq outlives the call, so nothing waits for the copy here.
-static int upload_queries(egx_gp *gp, const double *xq, int64_t m0, int m, int m_pad, std::vector<double> &xn,
-                          DevBuf &d_xraw, DevBuf &d_xqT, hipStream_t s) {
-    const int d = gp->d;
-    EGX_RC(d_xraw.alloc((size_t)m * d));
-    EGX_RC(d_xqT.alloc((size_t)d * m_pad));
-    EGX_HIP_CHECK(hipMemcpyAsync(d_xraw.p, xq + (size_t)m0 * d, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, s));
-    EGX_RC(launch_normalize_queries(s, d_xraw.p, m, d, dev_xnorm(gp), d_xqT.p, m_pad, m_pad, dev_spec(gp)));
-    if (gp->mean >= 1) {  // (a model with xtypes: the cast coordinates, as the device forms them)
-        xn.resize((size_t)m * d);
-        const double *src = xq + (size_t)m0 * d;
-        for (int a = 0; a < m; a++)
-            for (int j = 0; j < d; j++) xn[(size_t)a * d + j] = (query_coord(gp, src + (size_t)a * d, j) - gp->x_mean[j]) / gp->x_std[j];
-    } else {
-        xn.clear();
-    }
-    return EGX_SUCCESS;
-}
-
 int check_query(const egx_gp *gp, const double *xq, int64_t m) {
     if (!gp->fitted) {
         set_error("model is not fitted (call egx_gp_finalize or egx_gp_fit first)");
@@ -95,14 +73,33 @@ int posterior_solve_run(egx_gp *const *gps, int len, hipStream_t st, const doubl
 }
 // -Z^T = 0 - C^-T rt as an (n_pad x m_pad) matrix (W upper triangular: K range starts at the row tile)
 int posterior_weights(egx_gp *gp, hipStream_t st, const double *RT, int m_pad, double *Wt) {
-    const int n_pad = gp->n_pad;
-    EGX_HIP_CHECK(hipMemsetAsync(Wt, 0, sizeof(double) * (size_t)n_pad * m_pad, st));
-    return launch_gemm_nt_sub(st, Wt, m_pad, gp->d_W, n_pad, RT, n_pad, n_pad, m_pad, n_pad, 0, 1);
+    return posterior_weights_run(&gp, 1, st, RT, m_pad, Wt);
 }
 // -(Z + E)^T : Wt -= (-R^-1 F) (-D)^T
 int posterior_weights_trend(egx_gp *gp, hipStream_t st, const double *dneg, int m_pad, double *Wt) {
-    const int rp = gp->rhs_pad;
-    return launch_gemm_nt_sub(st, Wt, m_pad, gp->d_neg_invkf, rp, dneg, rp, gp->n_pad, m_pad, rp, 0, 0);
+    return posterior_weights_trend_run(&gp, 1, st, dneg, m_pad, Wt);
+}
+// ... of a run of `len` models of one shape whose C^-T and -R^-1 F sit at one stride (members of a group in consecutive slots:
+// the group's slab, ensure_winv; a lone model is a run of one): ONE GEMM launch, the member a grid coordinate.  Member j's blocks
+// are RT + j m_pad n_pad, dneg + j m_pad rhs_pad and Wt + j n_pad m_pad.  The GEMM's kernel is chosen by one matrix' shape.
+int posterior_weights_run(egx_gp *const *gps, int len, hipStream_t st, const double *RT, int m_pad, double *Wt) {
+    const egx_gp *lead = gps[0];
+    const int n_pad = lead->n_pad;
+    GemmBatch gb;
+    gb.count = len;
+    gb.sC = (int64_t)n_pad * m_pad, gb.sB = (int64_t)m_pad * n_pad;
+    if (len > 1) gb.sA = dev_winv(gps[1]) - dev_winv(lead);
+    EGX_HIP_CHECK(hipMemsetAsync(Wt, 0, sizeof(double) * (size_t)n_pad * m_pad * len, st));
+    return launch_gemm_nt_sub(st, Wt, m_pad, dev_winv(lead), n_pad, RT, n_pad, n_pad, m_pad, n_pad, 0, 1, nullptr, nullptr, &gb);
+}
+int posterior_weights_trend_run(egx_gp *const *gps, int len, hipStream_t st, const double *dneg, int m_pad, double *Wt) {
+    const egx_gp *lead = gps[0];
+    const int rp = lead->rhs_pad;
+    GemmBatch gb;
+    gb.count = len;
+    gb.sC = (int64_t)lead->n_pad * m_pad, gb.sB = (int64_t)m_pad * rp;
+    if (len > 1) gb.sA = dev_neg_invkf(gps[1]) - dev_neg_invkf(lead);
+    return launch_gemm_nt_sub(st, Wt, m_pad, dev_neg_invkf(lead), rp, dneg, rp, lead->n_pad, m_pad, rp, 0, 0, nullptr, nullptr, &gb);
 }
 
 static int predict_var_small(egx_gp *gp, const double *xq, int64_t m, double *vout);
@@ -117,12 +114,12 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
         // this path is an OPTIMISATION (a second n_pad^2 matrix): when it cannot be had -- allocation failure, or less
         // than its size + 25 % free on the device -- the batched path below serves the call, for this fit and all later
         // small calls on it.
-        const bool have_w = gp->winv_epoch == gp->fit_epoch && gp->d_W && gp->d_neg_invkf;
+        const bool have_w = gp->winv_epoch == gp->fit_epoch && dev_winv(gp) && dev_neg_invkf(gp);
         if (have_w || ++gp->small_var_calls >= 3) {
             int rc = EGX_SUCCESS;
-            if (!have_w && !gp->d_W) {
+            if (!have_w && !dev_winv(gp)) {  // (a member of a group: the slab of all its members)
                 size_t fr = 0, tot = 0;
-                const size_t need = sizeof(double) * (size_t)gp->n_pad * gp->n_pad;
+                const size_t need = sizeof(double) * (size_t)gp->n_pad * gp->n_pad * (gp->group ? gp->group->k : 1);
                 if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < need + need / 4) rc = EGX_ERR_HIP;
             }
             if (rc == EGX_SUCCESS) rc = ensure_winv(gp);
@@ -132,7 +129,7 @@ int predict_impl(egx_gp *gp, const double *xq, int64_t m, double *yout, double *
                 return predict_var_small(gp, xq, m, vout);
             }
             (void)hipGetLastError();
-            if (gp->winv_epoch != gp->fit_epoch) {  // give a half-built cache back
+            if (gp->winv_epoch != gp->fit_epoch && !gp->group) {  // give a half-built cache back (a group keeps its slab)
                 gp->d_W.reset();
                 gp->d_neg_invkf.reset();
             }
@@ -289,23 +286,33 @@ int predict_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m,
 // d_W <- C^-T (upper triangular, rows of the identity through the forward block substitution) and
 // d_neg_invkf <- -C^-T [ft | yt] for the factor resident in workspace 0; cached per fitted state.
 int ensure_winv(egx_gp *gp) {
-    if (gp->winv_epoch == gp->fit_epoch && gp->d_W && gp->d_neg_invkf) return EGX_SUCCESS;
+    if (gp->winv_epoch == gp->fit_epoch && dev_winv(gp) && dev_neg_invkf(gp)) return EGX_SUCCESS;
     Workspace &w = gp->ws[0];
     const int n_pad = gp->n_pad;
     const size_t sq = (size_t)n_pad * n_pad;
-    EGX_RC(gp->d_W.alloc(sq));
-    EGX_RC(gp->d_neg_invkf.alloc((size_t)n_pad * gp->rhs_pad));
+    if (gp->group) {
+        // a member of a group: the two matrices of ALL members in the group's slab, at one stride, allocated by whichever member
+        // asks first -- what lets a run of members take its weight GEMMs as one launch (posterior_weights_run); a member's own
+        // calls read the same matrix.  Memory per member is what a lone handle holds.
+        std::lock_guard<std::mutex> lk(gp->group->winv_mu);
+        EGX_RC(gp->group->W.alloc(sq * gp->group->k));
+        EGX_RC(gp->group->NK.alloc((size_t)n_pad * gp->rhs_pad * gp->group->k));
+    } else {
+        EGX_RC(gp->d_W.alloc(sq));
+        EGX_RC(gp->d_neg_invkf.alloc((size_t)n_pad * gp->rhs_pad));
+    }
+    double *const d_W = dev_winv(gp), *const d_neg_invkf = dev_neg_invkf(gp);
     // the rows of the identity, written on the device as far as the solve and the readers of W touch them (everything
     // on and above the diagonal 128-tiles): no host round trip, no 2 GiB memset
-    EGX_RC(launch_identity_rows(w.stream, gp->d_W, n_pad, n_pad));
-    EGX_RC(launch_trsm_rows(w.stream, w.M, gp->ld, n_pad, w.dinv, gp->d_W, n_pad, n_pad, 1));
-    EGX_HIP_CHECK(hipMemsetAsync(gp->d_neg_invkf, 0, sizeof(double) * (size_t)n_pad * gp->rhs_pad, w.stream));
+    EGX_RC(launch_identity_rows(w.stream, d_W, n_pad, n_pad));
+    EGX_RC(launch_trsm_rows(w.stream, w.M, gp->ld, n_pad, w.dinv, d_W, n_pad, n_pad, 1));
+    EGX_HIP_CHECK(hipMemsetAsync(d_neg_invkf, 0, sizeof(double) * (size_t)n_pad * gp->rhs_pad, w.stream));
     // 0 - W [ft | yt]: the rows [ft | yt]^T sit below the factor; W upper triangular -> K range starts at the row tile
-    EGX_RC(launch_gemm_nt_sub(w.stream, gp->d_neg_invkf, gp->rhs_pad, gp->d_W, n_pad, w.M + (size_t)n_pad * gp->ld,
+    EGX_RC(launch_gemm_nt_sub(w.stream, d_neg_invkf, gp->rhs_pad, d_W, n_pad, w.M + (size_t)n_pad * gp->ld,
                               gp->ld, n_pad, gp->rhs_pad, n_pad, 0, 1));
     {
         std::vector<double> tmp((size_t)n_pad * gp->rhs_pad);
-        EGX_HIP_CHECK(hipMemcpyAsync(tmp.data(), gp->d_neg_invkf, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, w.stream));
+        EGX_HIP_CHECK(hipMemcpyAsync(tmp.data(), d_neg_invkf, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, w.stream));
         EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
         gp->h_neg_invkf.resize((size_t)gp->n * gp->p);
         for (int i = 0; i < gp->n; i++)
@@ -372,7 +379,7 @@ static int small_path_solve(egx_gp *gp, std::vector<double> &y, std::vector<doub
     const int n = gp->n, n_pad = gp->n_pad, d = gp->d;
     EGX_RC(launch_cross_corr(w.stream, gp->corr, gp->sp_xq, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
                              gp->fit_hcols, gp->sp_R, n_pad));
-    EGX_RC(launch_uptri_solve_pair(w.stream, gp->d_W, n_pad, n, n_pad, gp->sp_R, gp->sp_P, gp->sp_y, gp->sp_z));
+    EGX_RC(launch_uptri_solve_pair(w.stream, dev_winv(gp), n_pad, n, n_pad, gp->sp_R, gp->sp_P, gp->sp_y, gp->sp_z));
     y.resize(n_pad);
     EGX_HIP_CHECK(hipMemcpyAsync(y.data(), gp->sp_y, sizeof(double) * n_pad, hipMemcpyDeviceToHost, w.stream));
     if (want_z) {
@@ -470,71 +477,119 @@ int xgrad_impl(egx_gp *gp, const double *xq, int64_t m, double *gy, double *gv) 
     // (the few-query kernel keeps 5 + hcols doubles per input dimension in LDS, the batched one 1 + hcols: very wide
     //  inputs take the batched form whatever m is)
     if (m > 0 && m <= 8 && (int64_t)gp->d * (gp->fit_hcols + 5) <= 20480) return xgrad_small(gp, xq, m, gy, gv);
-    Workspace &w = gp->ws[0];
-    const int n = gp->n, n_pad = gp->n_pad, d = gp->d, p = gp->p, rp = gp->rhs_pad;
-    if (gv) EGX_RC(ensure_winv(gp));
-    int64_t cap = ((int64_t)1 << 27) / n_pad / kTile * kTile;
-    if (cap < kTile) cap = kTile;
-    if (cap > 16384) cap = 16384;
-    if (!gv) cap = 65536;
-    std::vector<double> xn, part, sl, f(p), a_vec(p), u(p), dd(p), dneg, df(d);
+    return xgrad_run(&gp, 1, &xq, m, gy ? &gy : nullptr, gv ? &gv : nullptr);
+}
+
+// The batched x-gradients of a run of `len` fitted models of one shape whose factors -- and, for the variance, whose C^-T and
+// -R^-1 F (ensure_winv: the group's slab) -- sit at one stride: members of a group in consecutive slots, or ONE model
+// (xgrad_impl's batched route is this with len = 1).  Member j answers its own m queries xq[j] into gy[j] / gv[j] (m x d; either
+// array may be nullptr as a whole).  One launch sequence, one upload and one read-back per chunk and half, whatever len is.  The
+// kernels take the member as a grid coordinate, the splits of the training range come from one member's shape and the chunks are
+// the lone call's, so every member's results are the lone call's bits.
+int xgrad_run(egx_gp *const *gps, int len, const double *const *xq, int64_t m, double *const *gy, double *const *gv) {
+    egx_gp *lead = gps[0];
+    Workspace &w = lead->ws[0];
+    const int n = lead->n, n_pad = lead->n_pad, d = lead->d, p = lead->p, rp = lead->rhs_pad;
+    if (gv)
+        for (int j = 0; j < len; j++) EGX_RC(ensure_winv(gps[j]));
+    const int64_t cap = predict_chunk_cap(n_pad, gv != nullptr);
+    PosteriorBatch pb;
+    posterior_batch(gps, len, pb);
+    std::vector<double> stage, xn, part, sl, f(p), a_vec(p), u(p), dd(p), dneg, df(d);
     DevBuf d_xraw, d_xqT, d_out, d_RT, d_s0, d_sl, d_Wt, d_D;  // sized by the first (largest) chunk, reused by the others
     for (int64_t m0 = 0; m0 < m; m0 += cap) {
         const int mc = (int)((m - m0 < cap) ? (m - m0) : cap);
         const int m_pad = (int)round_up(mc, kTile);
         const int nsplit = xgrad_splits(n, m_pad);  // (partial sums added on the host)
-        EGX_RC(upload_queries(gp, xq, m0, mc, m_pad, xn, d_xraw, d_xqT, w.stream));
+        // the members' raw rows side by side, normalised on the device with every member's own x_mean | x_std; the trend needs
+        // the normalised coordinates on the host too (Linear / Quadratic; a model with xtypes: the cast ones, as the device's)
+        const size_t blk = (size_t)mc * d;
+        EGX_RC(d_xraw.alloc(blk * len));
+        EGX_RC(d_xqT.alloc((size_t)d * m_pad * len));
+        const double *src = xq[0] + (size_t)m0 * d;
+        if (len > 1) {
+            stage.resize(blk * len);
+            for (int j = 0; j < len; j++) std::memcpy(&stage[blk * j], xq[j] + (size_t)m0 * d, sizeof(double) * blk);
+            src = stage.data();
+        }
+        EGX_HIP_CHECK(hipMemcpyAsync(d_xraw.p, src, sizeof(double) * blk * len, hipMemcpyHostToDevice, w.stream));
+        pb.sq = (int64_t)d * m_pad;
+        EGX_RC(launch_normalize_queries(w.stream, pb, d_xraw.p, (int64_t)blk, mc, d, d_xqT.p, m_pad, m_pad));
+        if (lead->mean >= 1) {
+            xn.resize(blk * len);
+            for (int j = 0; j < len; j++) {
+                const egx_gp *gp = gps[j];
+                const double *raw = xq[j] + (size_t)m0 * d;
+                for (int a = 0; a < mc; a++)
+                    for (int c = 0; c < d; c++)
+                        xn[blk * j + (size_t)a * d + c] = (query_coord(gp, raw + (size_t)a * d, c) - gp->x_mean[c]) / gp->x_std[c];
+            }
+        } else {
+            xn.clear();
+        }
         const size_t out_sz = (size_t)nsplit * m_pad * d;
-        EGX_RC(d_out.alloc(out_sz));
-        part.resize(out_sz);
-        auto reduce_out = [&](int a, int k) {
+        pb.sout = (int64_t)out_sz;
+        EGX_RC(d_out.alloc(out_sz * len));
+        part.resize(out_sz * len);
+        auto reduce_out = [&](int j, int a, int k) {
             double sacc = 0.0;
-            for (int sidx = 0; sidx < nsplit; sidx++) sacc += part[((size_t)sidx * m_pad + a) * d + k];
+            for (int sidx = 0; sidx < nsplit; sidx++) sacc += part[out_sz * j + ((size_t)sidx * m_pad + a) * d + k];
             return sacc;
         };
+        auto xn_row = [&](int j, int a) { return xn.empty() ? nullptr : &xn[blk * j + (size_t)a * d]; };
         if (gy) {
-            EGX_RC(launch_xgrad(w.stream, gp->corr, d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n, d, gp->d_fit_coef,
-                                gp->fit_hcols, gp->d_gamma, 0, 1, nsplit, d_out.p));
-            EGX_HIP_CHECK(hipMemcpyAsync(part.data(), d_out.p, sizeof(double) * out_sz, hipMemcpyDeviceToHost, w.stream));
+            EGX_RC(launch_xgrad(w.stream, lead->corr, pb, d_xqT.p, m_pad, m_pad, n_pad, n, d, lead->fit_hcols, nullptr, 0, 1, nsplit,
+                                d_out.p));
+            EGX_HIP_CHECK(hipMemcpyAsync(part.data(), d_out.p, sizeof(double) * out_sz * len, hipMemcpyDeviceToHost, w.stream));
             EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
-            for (int a = 0; a < mc; a++) {
-                hm::regression_jac_dot(gp->mean, xn.empty() ? nullptr : &xn[(size_t)a * d], d, gp->beta.data(), df.data());
-                for (int k = 0; k < d; k++)
-                    gy[(size_t)(m0 + a) * d + k] = (df[k] + reduce_out(a, k)) * gp->y_std / gp->x_std[k];
+            for (int j = 0; j < len; j++) {
+                const egx_gp *gp = gps[j];
+                for (int a = 0; a < mc; a++) {
+                    hm::regression_jac_dot(gp->mean, xn_row(j, a), d, gp->beta.data(), df.data());
+                    for (int k = 0; k < d; k++)
+                        gy[j][(size_t)(m0 + a) * d + k] = (df[k] + reduce_out(j, a, k)) * gp->y_std / gp->x_std[k];
+                }
             }
         }
         if (gv) {
-            sl.resize((size_t)m_pad * p);
-            EGX_RC(d_RT.alloc((size_t)m_pad * n_pad));
-            EGX_RC(d_s0.alloc(m_pad));
-            EGX_RC(d_sl.alloc((size_t)m_pad * p));
-            EGX_RC(d_Wt.alloc((size_t)n_pad * m_pad));
-            EGX_RC(d_D.alloc((size_t)m_pad * rp));
-            EGX_RC(posterior_solve(gp, w.stream, d_xqT.p, m_pad, d_RT.p, d_s0.p, d_sl.p));
-            EGX_HIP_CHECK(hipMemcpyAsync(sl.data(), d_sl.p, sizeof(double) * (size_t)m_pad * p, hipMemcpyDeviceToHost,
-                                         w.stream));
-            EGX_RC(posterior_weights(gp, w.stream, d_RT.p, m_pad, d_Wt.p));
+            const size_t nsl = (size_t)m_pad * p, nD = (size_t)m_pad * rp;
+            sl.resize(nsl * len);
+            EGX_RC(d_RT.alloc((size_t)m_pad * n_pad * len));
+            EGX_RC(d_s0.alloc((size_t)m_pad * len));
+            EGX_RC(d_sl.alloc(nsl * len));
+            EGX_RC(d_Wt.alloc((size_t)n_pad * m_pad * len));
+            EGX_RC(d_D.alloc(nD * len));
+            EGX_RC(posterior_solve_run(gps, len, w.stream, d_xqT.p, m_pad, d_RT.p, d_s0.p, d_sl.p));
+            EGX_HIP_CHECK(hipMemcpyAsync(sl.data(), d_sl.p, sizeof(double) * nsl * len, hipMemcpyDeviceToHost, w.stream));
+            EGX_RC(posterior_weights_run(gps, len, w.stream, d_RT.p, m_pad, d_Wt.p));
             EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
             // D = B^-1 A^T per query (p x p work on the host), uploaded negated and zero padded to rhs_pad columns
-            dneg.assign((size_t)m_pad * rp, 0.0);
-            for (int a = 0; a < mc; a++) {
-                hm::regression_row(gp->mean, xn.empty() ? nullptr : &xn[(size_t)a * d], d, f.data());
-                for (int l = 0; l < p; l++) a_vec[l] = f[l] - sl[(size_t)a * p + l];
-                (void)hm::trend_forward(gp->ft_qr_r.data(), p, a_vec.data(), u.data());  // Rq^T u = A^T
-                hm::trend_backward(gp->ft_qr_r.data(), p, u.data(), dd.data());          // Rq D = u
-                for (int l = 0; l < p; l++) dneg[(size_t)a * rp + l] = -dd[l];
+            dneg.assign(nD * len, 0.0);
+            for (int j = 0; j < len; j++) {
+                const egx_gp *gp = gps[j];
+                for (int a = 0; a < mc; a++) {
+                    hm::regression_row(gp->mean, xn_row(j, a), d, f.data());
+                    for (int l = 0; l < p; l++) a_vec[l] = f[l] - sl[nsl * j + (size_t)a * p + l];
+                    (void)hm::trend_forward(gp->ft_qr_r.data(), p, a_vec.data(), u.data());  // Rq^T u = A^T
+                    hm::trend_backward(gp->ft_qr_r.data(), p, u.data(), dd.data());          // Rq D = u
+                    for (int l = 0; l < p; l++) dneg[nD * j + (size_t)a * rp + l] = -dd[l];
+                }
             }
             EGX_HIP_CHECK(hipMemcpyAsync(d_D.p, dneg.data(), sizeof(double) * dneg.size(), hipMemcpyHostToDevice, w.stream));
-            EGX_RC(posterior_weights_trend(gp, w.stream, d_D.p, m_pad, d_Wt.p));
-            EGX_RC(launch_xgrad(w.stream, gp->corr, d_xqT.p, m_pad, m_pad, gp->d_xT, n_pad, n, d, gp->d_fit_coef,
-                                gp->fit_hcols, d_Wt.p, m_pad, 0, nsplit, d_out.p));
-            EGX_HIP_CHECK(hipMemcpyAsync(part.data(), d_out.p, sizeof(double) * out_sz, hipMemcpyDeviceToHost, w.stream));
+            EGX_RC(posterior_weights_trend_run(gps, len, w.stream, d_D.p, m_pad, d_Wt.p));
+            pb.sW = (int64_t)n_pad * m_pad;
+            EGX_RC(launch_xgrad(w.stream, lead->corr, pb, d_xqT.p, m_pad, m_pad, n_pad, n, d, lead->fit_hcols, d_Wt.p, m_pad, 0, nsplit,
+                                d_out.p));
+            EGX_HIP_CHECK(hipMemcpyAsync(part.data(), d_out.p, sizeof(double) * out_sz * len, hipMemcpyDeviceToHost, w.stream));
             EGX_HIP_CHECK(hipStreamSynchronize(w.stream));
-            for (int a = 0; a < mc; a++) {
-                for (int l = 0; l < p; l++) dd[l] = -dneg[(size_t)a * rp + l];
-                hm::regression_jac_dot(gp->mean, xn.empty() ? nullptr : &xn[(size_t)a * d], d, dd.data(), df.data());
-                for (int k = 0; k < d; k++)
-                    gv[(size_t)(m0 + a) * d + k] = 2.0 * gp->sigma2 * (df[k] + reduce_out(a, k)) / gp->x_std[k];
+            for (int j = 0; j < len; j++) {
+                const egx_gp *gp = gps[j];
+                for (int a = 0; a < mc; a++) {
+                    for (int l = 0; l < p; l++) dd[l] = -dneg[nD * j + (size_t)a * rp + l];
+                    hm::regression_jac_dot(gp->mean, xn_row(j, a), d, dd.data(), df.data());
+                    for (int k = 0; k < d; k++)
+                        gv[j][(size_t)(m0 + a) * d + k] = 2.0 * gp->sigma2 * (df[k] + reduce_out(j, a, k)) / gp->x_std[k];
+                }
             }
         }
     }
@@ -607,6 +662,54 @@ int32_t egx_gp_predict_valvar_multi(egx_gp *const *gps, int32_t k, const double 
                 rc = predict_run(gps + i, len, xqs, m, y ? ys : nullptr, var ? vs : nullptr);
             } else {
                 rc = predict_impl(g, xq + (size_t)i * m * d, m, y ? y + (size_t)i * m : nullptr, var ? var + (size_t)i * m : nullptr);
+            }
+        }
+        if (rc != EGX_SUCCESS && first_rc == EGX_SUCCESS) first_rc = rc;  // (the others still finish)
+        i += len;
+    }
+    return first_rc;
+}
+
+// The x-gradients of the same runs in lock-step (xgrad_run); the run rule, the byte bound and the chunks are those of
+// egx_gp_predict_valvar_multi.  m <= 8: a lone call may take its few-query route, a run never does.
+int32_t egx_gp_predict_valvar_gradients_multi(egx_gp *const *gps, int32_t k, const double *xq, int64_t m, double *grad_y,
+                                              double *grad_var) {
+    if (m < 0 || (m > 0 && (!xq || (!grad_y && !grad_var)))) {
+        set_error(m > 0 && xq ? "NULL output: grad_y and grad_var" : "bad query array");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::vector<std::unique_lock<std::shared_mutex>> locks;
+    EGX_RC(lock_multi(gps, k, locks));
+    for (int32_t j = 1; j < k; j++)
+        if (gps[j]->d != gps[0]->d) {
+            set_error("egx_gp_predict_valvar_gradients_multi: the models must have the same input dimension");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    const size_t d = (size_t)gps[0]->d;
+    int first_rc = EGX_SUCCESS;
+    for (int i = 0; i < k;) {
+        egx_gp *g = gps[i];
+        int rc = check_query(g, xq, m);
+        int len = 1;
+        if (rc == EGX_SUCCESS) rc = set_device(g);
+        if (rc == EGX_SUCCESS && m > 0) {
+            const size_t blk = (size_t)m * d;
+            if (g->group && g->fit_hcols == 1) {
+                len = run_len_multi(gps, k, i);
+                for (int j = 1; j < len; j++)
+                    if (!gps[i + j]->fitted || gps[i + j]->fit_hcols != 1 || gps[i + j]->mean != g->mean || gps[i + j]->n != g->n) len = j;
+                len = predict_run_members(g->n_pad, m, grad_var != nullptr, len);
+                const double *xqs[kLockstepMax];
+                double *gys[kLockstepMax], *gvs[kLockstepMax];
+                for (int j = 0; j < len; j++) {
+                    xqs[j] = xq + (size_t)(i + j) * blk;
+                    gys[j] = grad_y ? grad_y + (size_t)(i + j) * blk : nullptr;
+                    gvs[j] = grad_var ? grad_var + (size_t)(i + j) * blk : nullptr;
+                }
+                rc = xgrad_run(gps + i, len, xqs, m, grad_y ? gys : nullptr, grad_var ? gvs : nullptr);
+            } else {
+                rc = xgrad_impl(g, xq + (size_t)i * blk, m, grad_y ? grad_y + (size_t)i * blk : nullptr,
+                                grad_var ? grad_var + (size_t)i * blk : nullptr);
             }
         }
         if (rc != EGX_SUCCESS && first_rc == EGX_SUCCESS) first_rc = rc;  // (the others still finish)

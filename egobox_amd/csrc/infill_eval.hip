@@ -3,15 +3,23 @@
 // one objective model and k constraint models; the scaling pass.  (The lock-step multistarts on top of it: infill_optimize.hip;
 // the pending points of a q-point batch: infill_pending.hip; the handle: infill_handle.h.)
 //
-// A call walks the points in tiles of EXACTLY kTile = 128 and, per tile, the models one after the other through the launch
+// A call walks the points in tiles of EXACTLY kTile = 128 and, per tile, the models through the launch
 // sequence of predict_impl / xgrad_impl (posterior_solve, posterior_weights, the split rules: gp_predict.hip); what those
 // do on the host between their launches runs in the kernels of kernels_infill.hip, and k_infill_combine applies
-// infill_math.h across the models.  One upload, one launch sequence per (tile, model), one combine, the copies back, ONE
-// synchronisation: the count depends on k and on the number of tiles only.
+// infill_math.h across the models.  One upload, one launch sequence per (tile, RUN of models), one combine, the copies back, ONE
+// synchronisation: the count depends on the runs and on the number of tiles only.
+//
+// RUNS (infill_runs.h, egx_infill_get_runs).  Consecutive lone dense surrogates of one shape go through ONE launch sequence per
+// tile, run_tile: the member is a grid coordinate of every kernel of it (the posterior batch of gp_predict.hip, the by-value
+// member blocks of kernels_infill.hip), its blocks of the tile buffers sit at the strides of the run's shape.  A mean-only run
+// takes the members' own pointers only; a full-sequence run reads factors, C^-T and -R^-1 F at one stride -- members of one
+// group in consecutive slots.  With pending points, or while a push is captured, every run has length 1.  A member's arithmetic
+// does not depend on its companions and the splits come from one member's shape: every output has the bits of runs of one.
 // Every launch of a tile has the padded batch size 128, and the splits of the training range are functions of the model
 // alone: the bits of a point do not depend on where it sits nor on its companions (tests/test_gpu_infill.py).
 //
-// The walk is tile -> surrogate -> expert through the same sequence; a lone expert writes the surrogate's slot of the tables,
+// The walk is tile -> run; a mixture or a sparse surrogate is a run of one walked expert by expert (a dense expert: run_tile with
+// one member).  A lone expert writes the surrogate's slot of the tables,
 // the experts of a mixture write the expert tables and ONE k_infill_mix launch per (tile, surrogate) recombines them into the
 // slot (smooth: the weighted sums; hard: the expert of the first maximum of the responsibilities -- every expert still
 // evaluates the whole tile, so that every launch keeps the padded batch of 128).
@@ -38,8 +46,11 @@
 // Nothing else of the sequence changes, and every other caller of eval_guarded launches what it launched before.
 #include "gmx_point.h"
 #include "infill_handle.h"
+#include "infill_runs.h"
 
 using namespace egx;
+
+static_assert(runs::kRunMax == kLockstepMax && runs::kRunTile == kTile, "infill_runs.h restates the launch widths");
 
 namespace egx {
 
@@ -102,61 +113,84 @@ int check_shapes(egx_infill *h) {
     return EGX_SUCCESS;
 }
 
-// One DENSE expert's launch sequence for one tile into o; flag: the tile's flags, written by the first expert of the call only
-// (else nullptr).  The MEAN-ONLY branch (o.var nullptr) is what the full sequence launches for mean / gmean and nothing else; it
-// runs for constraint surrogates only, which never own the call's flags nor its cast points.
-int expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, const TileOut &o, int *flag) {
+// The launch sequence of a RUN of `len` dense models of one shape (infill_runs.h; ONE model is a run of one: an expert of a
+// mixture, a surrogate that forms no run) for one tile: model jm[z] into o[z].  Every kernel takes the member as a grid
+// coordinate and does a member's arithmetic the same way whatever its companions, and the splits come from one member's shape:
+// a member's tables have the bits of its own run of one.  The tile buffers are laid out per member at the strides of the run's
+// shape.  flag: the tile's flags, written by member 0 -- the first expert of the call, which can only lead a run -- or nullptr.
+// The MEAN-ONLY branch (o[0].var nullptr: all members alike) is what the full sequence launches for mean / gmean and nothing
+// else; it runs for constraint surrogates only, which never own the call's flags nor its cast points.
+int run_tile(egx_infill *h, hipStream_t st, const int *jm, int len, int64_t t0, int mt, const TileOut *o, int *flag) {
     const int d = h->d;
-    egx_gp *gp = h->models[j].gp;
-    const int n = gp->n, n_pad = gp->n_pad;
+    egx_gp *gps[kLockstepMax];
+    for (int z = 0; z < len; z++) gps[z] = h->models[jm[z]].gp;
+    const egx_gp *lead = gps[0];
+    const int n = lead->n, n_pad = lead->n_pad, p = lead->p, rp = lead->rhs_pad, hcols = lead->fit_hcols;
     const int msplit = mean_splits(n_pad, kTile), nsplit = xgrad_splits(n, kTile);
-    const bool mean_only = !o.var, want_g = o.gmean != nullptr;
+    const bool mean_only = !o[0].var, want_g = o[0].gmean != nullptr;
     const int *cols = h->use_cols ? h->d_active.p : nullptr;  // active coordinates: the contractions' column list
     const int ncols = h->use_cols ? (int)h->active.size() : 0;
     if (mean_only) flag = nullptr;
+    const bool prescaled = hcols == 1 && predict_mean_prescaled(d, hcols);
+    PosteriorBatch pb, pm;  // pm: launch_predict_mean's, whose training inputs are the prescaled ones where that form exists
+    pb.count = len;
+    pb.sq = (int64_t)d * kTile, pb.sracc = (int64_t)msplit * kTile, pb.sW = (int64_t)n_pad * kTile, pb.sout = (int64_t)nsplit * kTile * d;
+    for (int z = 0; z < len; z++) {
+        const egx_gp *g = gps[z];
+        pb.ptrs.par[z] = dev_xnorm(g), pb.ptrs.spec[z] = dev_spec(g);
+        pb.ptrs.xT[z] = g->d_xT, pb.ptrs.coef[z] = g->d_fit_coef, pb.ptrs.gamma[z] = g->d_gamma;
+    }
+    pm = pb;
+    if (prescaled)
+        for (int z = 0; z < len; z++) pm.ptrs.xT[z] = dev_xs_fit(gps[z]);
     // (xtypes: cast in the same launch; the expert that writes the flags leaves the cast raw tile for k_infill_mix as well)
-    EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, dev_xnorm(gp), h->xqT.p, flag, dev_spec(gp),
-                                 flag && h->n_eslots > 0 && dev_spec(gp) ? h->xcast.p + (size_t)t0 * d : nullptr));
+    EGX_RC(launch_infill_prepare(st, pb, h->xraw.p + (size_t)t0 * d, mt, d, h->xqT.p, flag,
+                                 flag && h->n_eslots > 0 && dev_spec(lead) ? h->xcast.p + (size_t)t0 * d : nullptr));
     // r . gamma in split partial sums (algorithm.rs:260-262), before the solve overwrites r
-    EGX_RC(launch_predict_mean(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n_pad, d, gp->d_fit_coef,
-                               gp->fit_hcols, gp->d_gamma, h->racc.p, msplit,
-                               gp->fit_hcols == 1 ? dev_xs_fit(gp) : nullptr));
-    InfillTrend tr;
-    tr.p = gp->p, tr.rp = gp->rhs_pad, tr.msplit = msplit;
-    tr.xqT = h->xqT.p, tr.fidx = gp->d_fidx, tr.beta = gp->d_tbeta;
-    tr.racc = h->racc.p;
-    tr.y_mean = gp->y_mean, tr.y_std = gp->y_std;
-    tr.mean = o.mean;
+    EGX_RC(launch_predict_mean(st, lead->corr, pm, h->xqT.p, kTile, kTile, n_pad, n_pad, d, hcols, h->racc.p, msplit, prescaled ? 1 : 0));
+    InfillTrend tr[kLockstepMax];
+    InfillFinish fin[kLockstepMax];
+    for (int z = 0; z < len; z++) {
+        const egx_gp *g = gps[z];
+        InfillTrend &t = tr[z];
+        t.p = p, t.rp = rp, t.msplit = msplit;
+        t.xqT = h->xqT.p + (size_t)z * pb.sq, t.fidx = g->d_fidx, t.beta = g->d_tbeta;
+        t.racc = h->racc.p + (size_t)z * pb.sracc;
+        t.y_mean = g->y_mean, t.y_std = g->y_std;
+        t.mean = o[z].mean;
+        fin[z].x_std = dev_xnorm(g) + d, fin[z].gmean = o[z].gmean;
+        if (want_g) fin[z].out_y = h->out_y.p + (size_t)z * pb.sout;
+        if (mean_only) continue;
+        t.R = g->d_rq, t.Rt = g->d_rqT;
+        t.s0 = h->s0.p + (size_t)z * kTile, t.sl = h->sl.p + (size_t)z * kTile * p;
+        t.sigma2 = g->sigma2;
+        t.var = o[z].var;
+        if (!want_g) continue;
+        t.dneg = h->dneg.p + (size_t)z * kTile * rp;
+        fin[z].out_v = h->out_v.p + (size_t)z * pb.sout, fin[z].gvar = o[z].gvar;
+    }
     if (mean_only) {
-        EGX_RC(launch_infill_trend_mean(st, tr));
+        EGX_RC(launch_infill_trend_mean(st, tr, len));
         if (!want_g) return EGX_SUCCESS;
-        EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                            gp->d_gamma, 0, 1, nsplit, h->out_y.p, cols, ncols));
-        return launch_infill_xgrad_finish_mean(st, tr, d, nsplit, h->out_y.p, dev_xnorm(gp) + d, o.gmean);
+        EGX_RC(launch_xgrad(st, lead->corr, pb, h->xqT.p, kTile, kTile, n_pad, n, d, hcols, nullptr, 0, 1, nsplit, h->out_y.p, cols, ncols));
+        return launch_infill_xgrad_finish_mean(st, tr, fin, len, d, nsplit);
     }
     // rt = C^-1 r (held transposed), sum rt^2 and ft^T rt (:337-352)
-    EGX_RC(posterior_solve(gp, st, h->xqT.p, kTile, h->RT.p, h->s0.p, h->sl.p));
-    tr.R = gp->d_rq, tr.Rt = gp->d_rqT;
-    tr.s0 = h->s0.p, tr.sl = h->sl.p;
-    tr.sigma2 = gp->sigma2;
-    tr.var = o.var;
-    tr.dneg = want_g ? h->dneg.p : nullptr;
-    EGX_RC(launch_infill_trend(st, tr));
+    EGX_RC(posterior_solve_run(gps, len, st, h->xqT.p, kTile, h->RT.p, h->s0.p, h->sl.p));
+    EGX_RC(launch_infill_trend(st, tr, len));
     if (!want_g) return EGX_SUCCESS;
     // -(R^-1 r + R^-1 F D)^T as an (n_pad x 128) weight matrix, then the two contractions
-    EGX_RC(posterior_weights(gp, st, h->RT.p, kTile, h->Wt.p));
-    EGX_RC(posterior_weights_trend(gp, st, h->dneg.p, kTile, h->Wt.p));
-    EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                        gp->d_gamma, 0, 1, nsplit, h->out_y.p, cols, ncols));
-    EGX_RC(launch_xgrad(st, gp->corr, h->xqT.p, kTile, kTile, gp->d_xT, n_pad, n, d, gp->d_fit_coef, gp->fit_hcols,
-                        h->Wt.p, kTile, 0, nsplit, h->out_v.p, cols, ncols));
-    return launch_infill_xgrad_finish(st, tr, d, nsplit, h->out_y.p, h->out_v.p, dev_xnorm(gp) + d, o.gmean, o.gvar);
+    EGX_RC(posterior_weights_run(gps, len, st, h->RT.p, kTile, h->Wt.p));
+    EGX_RC(posterior_weights_trend_run(gps, len, st, h->dneg.p, kTile, h->Wt.p));
+    EGX_RC(launch_xgrad(st, lead->corr, pb, h->xqT.p, kTile, kTile, n_pad, n, d, hcols, nullptr, 0, 1, nsplit, h->out_y.p, cols, ncols));
+    EGX_RC(launch_xgrad(st, lead->corr, pb, h->xqT.p, kTile, kTile, n_pad, n, d, hcols, h->Wt.p, kTile, 0, nsplit, h->out_v.p, cols, ncols));
+    return launch_infill_xgrad_finish(st, tr, fin, len, d, nsplit);
 }
 
 // A SPARSE expert's launch sequence for one tile, the batched route of sgp_query (sgp_predict.hip) at the padded batch of 128
 // whatever the call's size: raw x, K(x, z) . (sigma2 vec) in split partial sums, K(x, z), the two block solves with their row
 // reductions, the finish; with gradients the two transposed products with the cached inverse factors (sgp_ensure_inverse_factors,
-// built by ensure_device_state), the two contractions and their finish.  Arguments as expert_tile.  The MEAN-ONLY branch: no
+// built by ensure_device_state), the two contractions and their finish.  Arguments as run_tile's, for ONE model j.  The MEAN-ONLY branch: no
 // K(x, z) block, no solve; the same partial sums in the same order, so the means keep the full sequence's bits.
 int sgp_expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, const TileOut &o, int *flag) {
     const int d = h->d;
@@ -227,6 +261,27 @@ EvalPlan make_plan(const egx_infill *h, int64_t m, const double *grad, const egx
     return p;
 }
 
+// the surrogates as infill_runs.h reads them, and the runs of a walk over them (mean_c: the constraints' sequence is mean-only)
+std::vector<runs::Shape> run_shapes(const egx_infill *h) {
+    std::vector<runs::Shape> out(h->surr.size());
+    for (size_t js = 0; js < h->surr.size(); js++) {
+        const Surrogate &sg = h->surr[js];
+        const ModelRef &r = h->models[sg.first];
+        runs::Shape &s = out[js];
+        s.lone_dense = sg.k < 2 && !r.sparse();
+        if (!s.lone_dense) continue;
+        const egx_gp *g = r.gp;
+        s.n = g->n, s.n_pad = g->n_pad, s.corr = g->corr, s.mean = g->mean, s.fit_hcols = g->fit_hcols, s.has_w = g->has_w;
+        s.group = g->group.get(), s.slot = g->group_slot;
+    }
+    return out;
+}
+// pending: the walk conditions on pending points or captures a push (EvalPlan::pending) -- every run has length 1
+std::vector<int> walk_runs(const egx_infill *h, bool mean_c, bool pending) {
+    const std::vector<runs::Shape> sh = run_shapes(h);
+    return runs::run_lengths(sh.data(), (int)sh.size(), mean_c, pending ? std::max(h->q, 1) : 0);
+}
+
 // a host array the handle uploads on first use (and again after it changed: the owner clears on_device)
 int upload_once(DevBuf &buf, bool &on_device, const double *src, size_t count, hipStream_t st) {
     if (on_device) return EGX_SUCCESS;
@@ -271,9 +326,11 @@ int ensure_device_state(egx_infill *h, hipStream_t st, const EvalPlan &p) {
     return EGX_SUCCESS;
 }
 
-// the call's tables and the scratch of one (tile, model) step, sized by the largest model
+// the call's tables and the scratch of one (tile, run) step, sized by the largest model and the longest run
 int reserve_scratch(egx_infill *h, const EvalPlan &p, const ExpertDiag *diag, const CstrOut *co, const PushCapture *cap) {
     const int nm = (int)h->surr.size(), k = nm - 1, d = h->d, ns = h->n_eslots;
+    size_t rl = 1;  // members of the longest run: the tile buffers hold one block per member
+    for (int len : walk_runs(h, p.mean_c, p.pending)) rl = std::max(rl, (size_t)len);
     const int64_t m = p.m, M = p.M;
     int n_pad_max = 0, p_max = 1, rp_max = 1, ms_max = 0, ns_max = 0, z_pad_max = 0;
     for (const ModelRef &r : h->models) {  // (the inducing points of a sparse model stand where a dense model's training points do)
@@ -290,21 +347,21 @@ int reserve_scratch(egx_infill *h, const EvalPlan &p, const ExpertDiag *diag, co
     EGX_RC(h->mean.alloc((size_t)nm * M));
     EGX_RC(h->var.alloc((size_t)nm * M));
     EGX_RC(h->value.alloc((size_t)M));
-    EGX_RC(h->xqT.alloc((size_t)d * kTile));
-    EGX_RC(h->racc.alloc((size_t)ms_max * kTile));
-    EGX_RC(h->RT.alloc((size_t)kTile * n_pad_max));
-    EGX_RC(h->s0.alloc(kTile));
-    EGX_RC(h->sl.alloc((size_t)kTile * p_max));
+    EGX_RC(h->xqT.alloc(rl * d * kTile));
+    EGX_RC(h->racc.alloc(rl * ms_max * kTile));
+    EGX_RC(h->RT.alloc(rl * kTile * n_pad_max));
+    EGX_RC(h->s0.alloc(rl * kTile));
+    EGX_RC(h->sl.alloc(rl * kTile * p_max));
     if (p.any_sparse) EGX_RC(h->s1.alloc(kTile));
     if (p.want_g) {
         if (p.any_sparse) EGX_RC(h->sE.alloc((size_t)kTile * z_pad_max));
         EGX_RC(h->gmean.alloc((size_t)nm * M * d));
         EGX_RC(h->gvar.alloc((size_t)nm * M * d));
         EGX_RC(h->grad.alloc((size_t)M * d));
-        EGX_RC(h->Wt.alloc((size_t)n_pad_max * kTile));
-        EGX_RC(h->dneg.alloc((size_t)kTile * rp_max));
-        EGX_RC(h->out_y.alloc((size_t)ns_max * kTile * d));
-        EGX_RC(h->out_v.alloc((size_t)ns_max * kTile * d));
+        EGX_RC(h->Wt.alloc(rl * n_pad_max * kTile));
+        EGX_RC(h->dneg.alloc(rl * kTile * rp_max));
+        EGX_RC(h->out_y.alloc(rl * ns_max * kTile * d));
+        EGX_RC(h->out_v.alloc(rl * ns_max * kTile * d));
     }
     if (ns > 0) {
         EGX_RC(h->emean.alloc((size_t)ns * M));
@@ -374,19 +431,32 @@ int mix_tile(egx_infill *h, hipStream_t st, const EvalPlan &p, int js, int64_t t
     return mean_only ? launch_infill_mix_mean(st, mx) : launch_infill_mix(st, mx);
 }
 
-// tile -> surrogate -> expert: the expert's sequence, the conditioning on the pending points, the mixture's recombination
+// tile -> run -> (a mixture, a sparse model: expert): the run's sequence, the conditioning on the pending points, the mixture's
+// recombination.  A lone dense surrogate that forms no run, and a dense expert of a mixture, is a run of one through the same code.
 int walk_tiles(egx_infill *h, hipStream_t st, const EvalPlan &p, const ExpertDiag *diag, PushCapture *cap) {
-    const int nm = (int)h->surr.size();
+    const int nm = p.run_c ? (int)h->surr.size() : 1;
+    const std::vector<int> lens = walk_runs(h, p.mean_c, p.pending);
     int *flag = reinterpret_cast<int *>(h->flag.p);
     for (int64_t t0 = 0; t0 < p.m; t0 += kTile) {
         const int mt = (int)std::min<int64_t>(kTile, p.m - t0);
-        for (int js = 0; js < (p.run_c ? nm : 1); js++) {
+        size_t r = 0;
+        for (int js = 0; js < nm; js += lens[r++]) {
             const Surrogate &sg = h->surr[js];
             const bool mean_only = js > 0 && p.mean_c;  // (the objective always runs the full sequence)
+            if (sg.k < 2 && !h->models[sg.first].sparse()) {
+                const int len = std::min(lens[r], nm - js);  // (a call that runs the objective alone)
+                int jm[kLockstepMax];
+                TileOut o[kLockstepMax];
+                for (int z = 0; z < len; z++) jm[z] = h->surr[js + z].first, o[z] = tile_out(h, p, js + z, 0, t0, mean_only);
+                EGX_RC(run_tile(h, st, jm, len, t0, mt, o, jm[0] == 0 ? flag + t0 : nullptr));
+                if (p.pending) EGX_RC(pending_tile(h, st, js, o[0], cap));  // (pending points: every run has length 1)
+                continue;
+            }
             for (int e = 0; e < sg.k; e++) {
                 const int j = sg.first + e;
                 const TileOut o = tile_out(h, p, js, e, t0, mean_only);
-                EGX_RC((h->models[j].sparse() ? sgp_expert_tile : expert_tile)(h, st, j, t0, mt, o, j == 0 ? flag + t0 : nullptr));
+                if (h->models[j].sparse()) EGX_RC(sgp_expert_tile(h, st, j, t0, mt, o, j == 0 ? flag + t0 : nullptr));
+                else EGX_RC(run_tile(h, st, &j, 1, t0, mt, &o, j == 0 ? flag + t0 : nullptr));
                 if (p.pending) EGX_RC(pending_tile(h, st, js, o, cap));  // (lone dense surrogates only: o is the surrogate's slot)
             }
             if (sg.k >= 2) EGX_RC(mix_tile(h, st, p, js, t0, mt, mean_only, diag));
@@ -805,6 +875,16 @@ int32_t egx_infill_get_active(egx_infill *h, int32_t *n_active, int32_t *active,
     *n_active = (int32_t)h->active.size();
     if (active) std::copy(h->active.begin(), h->active.end(), active);
     if (x_base) std::copy(h->x_base.begin(), h->x_base.end(), x_base);
+    return EGX_SUCCESS;
+}
+
+int32_t egx_infill_get_runs(egx_infill *h, int32_t *n_runs, int32_t *run_len) {
+    if (!h || !n_runs) return fail(EGX_ERR_INVALID_VALUE, "NULL argument");
+    std::lock_guard<std::mutex> lock(h->mu);
+    ModelLocks locks(h);  // (the shapes are read from the models)
+    const std::vector<int> lens = walk_runs(h, h->strategy == infill::kCstrMean, h->q > 0);
+    *n_runs = (int32_t)lens.size();
+    if (run_len) std::copy(lens.begin(), lens.end(), run_len);
     return EGX_SUCCESS;
 }
 

@@ -398,18 +398,30 @@ __global__ __launch_bounds__(256) void k_predict_mean_srow(PosteriorBatchPtrs b,
 // (the closed form of the reference's product-over-all-but-one loops; sign(+0) = +1 like f64::signum).
 // ---------------------------------------------------------------------------------------------
 constexpr int kXgThreads = 128;
+// A wave-uniform read of memory that nothing writes while the kernel runs, through the constant address space: a scalar load
+// whatever the compiler can prove about aliasing (a pointer taken from a by-value pointer block carries no __restrict__)
+__device__ __forceinline__ double uniform_ld(const double *p) {
+    return *(const __attribute__((address_space(4))) double *)p;
+}
 constexpr size_t kLdsBytes = 160 * 1024;  // LDS of one CU (gfx950)
 
+// blockIdx.z = member of a posterior batch (a workgroup serves ONE member): its own training inputs, coefficients and -- VEC --
+// weight vector, its query block, weight matrix and partial sums sq / sW / sout doubles behind the previous member's.
 // XAG (d > 64): the lane's own query coordinates come from global memory (L1 / L2) instead of a [d][kXgThreads] LDS
 // image, which together with the training slab would not fit any more; the slab is [d][2^js_shift] training points,
 // 64 wide up to d = 256 and narrower beyond (launch_xgrad picks the widest that fits the 160 KB of LDS)
 template <int CORR, int DK, bool VEC, bool XAG = false>
-__global__ __launch_bounds__(kXgThreads) void k_xgrad(const double *__restrict__ xqT, int64_t ldq,
-                                                      const double *__restrict__ xT, int64_t ldx, int n, int d,
-                                                      const double *__restrict__ coef, int hcols,
-                                                      const double *__restrict__ Wt, int64_t ldw, int slabs_per_split,
-                                                      double *__restrict__ out, int m_pad, int js_shift) {
+__global__ __launch_bounds__(kXgThreads) void k_xgrad(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq,
+                                                      int64_t sq, int64_t ldx, int n, int d, int hcols,
+                                                      const double *__restrict__ Wt_all, int64_t ldw, int64_t sW,
+                                                      int slabs_per_split, double *__restrict__ out_all, int64_t sout,
+                                                      int m_pad, int js_shift) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
+    const double *__restrict__ xT = b.xT[blockIdx.z];
+    const double *__restrict__ coef = b.coef[blockIdx.z];
+    const double *__restrict__ Wt = VEC ? b.gamma[blockIdx.z] : Wt_all + (int64_t)blockIdx.z * sW;
+    double *__restrict__ out = out_all + (int64_t)blockIdx.z * sout;
     const int jsh = XAG ? js_shift : 6, JS = 1 << jsh;
     double *xa = sm;                                  // [d][kXgThreads]  (not with XAG)
     double *xj = sm + (XAG ? 0 : d * kXgThreads);     // [d][JS]
@@ -440,7 +452,7 @@ __global__ __launch_bounds__(kXgThreads) void k_xgrad(const double *__restrict__
             for (int jj = 0; jj < jn; jj++) {
                 PairAcc<CORR> pa;
                 for (int k = 0; k < d; k++) pa.add(EGX_XA(k) - xj[k * JS + jj], cs + k * hcols, hcols);
-                const double wv = VEC ? Wt[j0 + jj] : Wt[(int64_t)(j0 + jj) * ldw + a];
+                const double wv = VEC ? uniform_ld(Wt + j0 + jj) : Wt[(int64_t)(j0 + jj) * ldw + a];
                 const double rw = pa.value() * wv;
 #pragma unroll
                 for (int kk = 0; kk < DK; kk++)
@@ -464,13 +476,17 @@ __global__ __launch_bounds__(kXgThreads) void k_xgrad(const double *__restrict__
 // order are k_xgrad's: a listed column accumulates the same __builtin_fma sequence and has k_xgrad's bits
 // (tests/test_gpu_infill_active.py).  cols: distinct, in [0, d), in any order (checked on the host, infill_active.h).
 template <int CORR, int DK, bool VEC, bool XAG = false>
-__global__ __launch_bounds__(kXgThreads) void k_xgrad_cols(const double *__restrict__ xqT, int64_t ldq,
-                                                           const double *__restrict__ xT, int64_t ldx, int n, int d,
-                                                           const double *__restrict__ coef, int hcols,
-                                                           const double *__restrict__ Wt, int64_t ldw, int slabs_per_split,
-                                                           double *__restrict__ out, int m_pad, int js_shift,
-                                                           const int *__restrict__ cols, int ncols) {
+__global__ __launch_bounds__(kXgThreads) void k_xgrad_cols(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq,
+                                                           int64_t sq, int64_t ldx, int n, int d, int hcols,
+                                                           const double *__restrict__ Wt_all, int64_t ldw, int64_t sW,
+                                                           int slabs_per_split, double *__restrict__ out_all, int64_t sout,
+                                                           int m_pad, int js_shift, const int *__restrict__ cols, int ncols) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
+    const double *__restrict__ xT = b.xT[blockIdx.z];
+    const double *__restrict__ coef = b.coef[blockIdx.z];
+    const double *__restrict__ Wt = VEC ? b.gamma[blockIdx.z] : Wt_all + (int64_t)blockIdx.z * sW;
+    double *__restrict__ out = out_all + (int64_t)blockIdx.z * sout;
     const int jsh = XAG ? js_shift : 6, JS = 1 << jsh;
     double *xa = sm;                                  // [d][kXgThreads]  (not with XAG)
     double *xj = sm + (XAG ? 0 : d * kXgThreads);     // [d][JS]
@@ -504,7 +520,7 @@ __global__ __launch_bounds__(kXgThreads) void k_xgrad_cols(const double *__restr
             for (int jj = 0; jj < jn; jj++) {
                 PairAcc<CORR> pa;
                 for (int k = 0; k < d; k++) pa.add(EGX_XA(k) - xj[k * JS + jj], cs + k * hcols, hcols);
-                const double wv = VEC ? Wt[j0 + jj] : Wt[(int64_t)(j0 + jj) * ldw + a];
+                const double wv = VEC ? uniform_ld(Wt + j0 + jj) : Wt[(int64_t)(j0 + jj) * ldw + a];
                 const double rw = pa.value() * wv;
 #pragma unroll
                 for (int kk = 0; kk < DK; kk++)
@@ -1071,15 +1087,15 @@ int launch_predict_mean(hipStream_t s, int corr, const PosteriorBatch &pb, const
     return EGX_SUCCESS;
 }
 
-// out: nsplit x m_pad x d partial sums (nsplit returned); Wt = gamma (vec != 0) or the (n x m_pad) weight matrix
-int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_pad, const double *xT, int64_t ldx,
-                 int n, int d, const double *coef, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit,
-                 double *out, const int *cols, int ncols) {
+// out: nsplit x m_pad x d partial sums per member; the weights are the members' gamma (vec != 0) or (n x m_pad) matrices
+int launch_xgrad(hipStream_t s, int corr, const PosteriorBatch &pb, const double *xqT, int64_t ldq, int m_pad, int64_t ldx, int n,
+                 int d, int hcols, const double *Wt, int64_t ldw, int vec, int nsplit, double *out, const int *cols, int ncols) {
+    if (!posterior_count_ok(pb)) return EGX_ERR_INVALID_VALUE;
     const int slabs = (n + 63) / 64;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > slabs) nsplit = slabs;
     const int per = (slabs + nsplit - 1) / nsplit;
-    dim3 grid(m_pad / kXgThreads, nsplit);
+    dim3 grid(m_pad / kXgThreads, nsplit, (unsigned)pb.count);
     // d <= 64: the lane's query coordinates in LDS; beyond: from global memory (XAG), the training slab alone in LDS,
     // as many training points wide (64, 32, ... 1) as fit beside the d x hcols coefficients
     const bool xag = d > kCorrDC;
@@ -1097,8 +1113,8 @@ int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_
         if (lds > 65536)                                                                                                     \
             EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xgrad<C_, DK_, VEC_, XAG_>),                 \
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hipLaunchKernelGGL((k_xgrad<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, xqT, ldq, xT, ldx, n, d, coef,    \
-                           hcols, Wt, ldw, per, out, m_pad, js_shift);                                                       \
+        hipLaunchKernelGGL((k_xgrad<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, pb.ptrs, xqT, ldq, pb.sq, ldx,    \
+                           n, d, hcols, Wt, ldw, pb.sW, per, out, pb.sout, m_pad, js_shift);                                 \
     }
 #define EGX_XG(C_, DK_)                                    \
     if (xag) {                                             \
@@ -1112,8 +1128,8 @@ int launch_xgrad(hipStream_t s, int corr, const double *xqT, int64_t ldq, int m_
         if (lds > 65536)                                                                                                     \
             EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xgrad_cols<C_, DK_, VEC_, XAG_>),            \
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hipLaunchKernelGGL((k_xgrad_cols<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, xqT, ldq, xT, ldx, n, d,     \
-                           coef, hcols, Wt, ldw, per, out, m_pad, js_shift, cols, ncols);                                    \
+        hipLaunchKernelGGL((k_xgrad_cols<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, pb.ptrs, xqT, ldq, pb.sq,    \
+                           ldx, n, d, hcols, Wt, ldw, pb.sW, per, out, pb.sout, m_pad, js_shift, cols, ncols);              \
     }
 #define EGX_XGC(C_, DK_)                                   \
     if (xag) {                                             \

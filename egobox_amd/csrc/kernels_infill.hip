@@ -33,10 +33,15 @@ namespace egx {
 
 constexpr int kInfThreads = 256;
 
-// one thread per point of the tile; xq: the tile's mt <= 128 raw rows (mt x d); par = x_mean (d) | x_std (d)
-__global__ __launch_bounds__(kTile) void k_infill_prepare(const double *__restrict__ xq, int mt, int d,
-                                                          const double *__restrict__ par, double *__restrict__ xqT,
-                                                          int *__restrict__ flag) {
+// one thread per point of the tile; xq: the tile's mt <= 128 raw rows (mt x d); par = x_mean (d) | x_std (d).
+// blockIdx.x = member of a run of models (infill_runs.h) that read the SAME raw tile, each through its own normalisation into its
+// own block of xqT, sq doubles behind the previous member's; the flags (and the cast rows) are member 0's to write: the
+// objective's, which owns the call's flags, can only lead a run
+__global__ __launch_bounds__(kTile) void k_infill_prepare(PosteriorBatchPtrs b, const double *__restrict__ xq, int mt, int d,
+                                                          double *__restrict__ xqT_all, int64_t sq, int *__restrict__ flag_lead) {
+    const double *__restrict__ par = b.par[blockIdx.x];
+    double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.x * sq;
+    int *flag = blockIdx.x == 0 ? flag_lead : nullptr;
     const int a = threadIdx.x;
     int bad = 0;
     if (a < mt)
@@ -48,10 +53,14 @@ __global__ __launch_bounds__(kTile) void k_infill_prepare(const double *__restri
 // ... of a model that carries xtypes (mixint.h): the same with every coordinate cast where it is read.  A finite coordinate
 // stays finite under the cast and a non-finite one non-finite, so the flags are those of the raw rows.  xcast (mt x d, or
 // nullptr) receives the cast raw rows (a flagged point: its raw row), for k_infill_mix.
-__global__ __launch_bounds__(kTile) void k_infill_prepare_mixint(const double *__restrict__ xq, int mt, int d,
-                                                                 const double *__restrict__ par, double *__restrict__ xqT,
-                                                                 int *__restrict__ flag, const mixint::Col *__restrict__ spec,
-                                                                 double *__restrict__ xcast) {
+__global__ __launch_bounds__(kTile) void k_infill_prepare_mixint(PosteriorBatchPtrs b, const double *__restrict__ xq, int mt, int d,
+                                                                 double *__restrict__ xqT_all, int64_t sq,
+                                                                 int *__restrict__ flag_lead, double *__restrict__ xcast_lead) {
+    const double *__restrict__ par = b.par[blockIdx.x];
+    const mixint::Col *__restrict__ spec = b.spec[blockIdx.x];
+    double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.x * sq;
+    int *flag = blockIdx.x == 0 ? flag_lead : nullptr;
+    double *xcast = blockIdx.x == 0 ? xcast_lead : nullptr;
     const int a = threadIdx.x;
     const double *vals = mixint::table_values(spec, d);
     int bad = 0;
@@ -80,10 +89,15 @@ struct TrendArgs {
     double *mean, *var;   // 128 each (this tile of this model)
     double *dneg;         // 128 x rp: -D, zero padded (want_d)
 };
+// the members of a run (infill_runs.h), by value: blockIdx.y = member, a workgroup serves one point of ONE member
+struct TrendBatch {
+    TrendArgs m[kLockstepMax];
+};
 
 // One workgroup per point (p reaches 561 for the quadratic trend at d = 32: Rq is streamed from L2 row by row).
 // LDS: s[p] (A, then u, then D), diag[p], prod[p] (f_l beta_l), part[msplit]; thread 0 adds them in predict_impl's order.
-__global__ __launch_bounds__(kInfThreads) void k_infill_trend(TrendArgs g) {
+__global__ __launch_bounds__(kInfThreads) void k_infill_trend(TrendBatch gb) {
+    const TrendArgs &g = gb.m[blockIdx.y];
     extern __shared__ double lds[];
     const int p = g.p, a = blockIdx.x, t = threadIdx.x;
     double *s = lds, *diag = lds + p, *prod = lds + 2 * p, *part = lds + 3 * p;
@@ -129,7 +143,8 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_trend(TrendArgs g) {
 }
 
 // The mean of k_infill_trend alone: prod[p], part[msplit] in LDS, thread 0 adds them in the same order.
-__global__ __launch_bounds__(kInfThreads) void k_infill_trend_mean(TrendArgs g) {
+__global__ __launch_bounds__(kInfThreads) void k_infill_trend_mean(TrendBatch gb) {
+    const TrendArgs &g = gb.m[blockIdx.y];
     extern __shared__ double lds[];
     const int p = g.p, a = blockIdx.x, t = threadIdx.x;
     double *prod = lds, *part = lds + p;
@@ -156,6 +171,9 @@ struct XgFinishArgs {
     double sigma2, y_std;
     double *gmean, *gvar;   // 128 x d each (this tile of this model)
 };
+struct XgFinishBatch {  // blockIdx.y = member of a run, as TrendBatch
+    XgFinishArgs m[kLockstepMax];
+};
 
 // sum_l v_l d f_l / d x_k at the point's normalised coordinates (host_math.h regression_jac_dot); sign * v[l * 1]
 __device__ inline double jac_dot(const XgFinishArgs &g, int a, int k, const double *v, double sign) {
@@ -171,7 +189,8 @@ __device__ inline double jac_dot(const XgFinishArgs &g, int a, int k, const doub
 // One workgroup per point.  The partial sums of kc = kXgStage / nsplit coordinates at a time are staged in LDS by all threads;
 // thread kk then adds the splits of its coordinate in order (xgrad_impl's reduce_out).
 constexpr int kXgStage = 2048;
-__global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish(XgFinishArgs g) {
+__global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish(XgFinishBatch gb) {
+    const XgFinishArgs &g = gb.m[blockIdx.y];
     __shared__ double st_y[kXgStage], st_v[kXgStage];
     const int a = blockIdx.x, t = threadIdx.x, d = g.d, ns = g.nsplit;
     int kc = kXgStage / ns;
@@ -202,7 +221,8 @@ __global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish(XgFinishArg
 }
 
 // The gmean of k_infill_xgrad_finish alone (out_v, dneg, gvar are not read).
-__global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish_mean(XgFinishArgs g) {
+__global__ __launch_bounds__(kInfThreads) void k_infill_xgrad_finish_mean(XgFinishBatch gb) {
+    const XgFinishArgs &g = gb.m[blockIdx.y];
     __shared__ double st_y[kXgStage];
     const int a = blockIdx.x, t = threadIdx.x, d = g.d, ns = g.nsplit;
     int kc = kXgStage / ns;
@@ -440,43 +460,79 @@ int launch_infill_scale_terms(hipStream_t s, const infill::Params &prm, int k, i
     return EGX_SUCCESS;
 }
 
-int launch_infill_prepare(hipStream_t s, const double *xq, int mt, int d, const double *par, double *xqT, int *flag,
-                          const mixint::Col *spec, double *xcast) {
-    if (spec) hipLaunchKernelGGL(k_infill_prepare_mixint, dim3(1), dim3(kTile), 0, s, xq, mt, d, par, xqT, flag, spec, xcast);
-    else hipLaunchKernelGGL(k_infill_prepare, dim3(1), dim3(kTile), 0, s, xq, mt, d, par, xqT, flag);
+static bool run_count_ok(int count) {
+    if (count >= 1 && count <= kLockstepMax) return true;
+    set_error("infill: run length out of range");
+    return false;
+}
+
+int launch_infill_prepare(hipStream_t s, const PosteriorBatch &pb, const double *xq, int mt, int d, double *xqT, int *flag,
+                          double *xcast) {
+    if (!run_count_ok(pb.count)) return EGX_ERR_INVALID_VALUE;
+    const dim3 grid((unsigned)pb.count);
+    if (pb.ptrs.spec[0]) hipLaunchKernelGGL(k_infill_prepare_mixint, grid, dim3(kTile), 0, s, pb.ptrs, xq, mt, d, xqT, pb.sq, flag, xcast);
+    else hipLaunchKernelGGL(k_infill_prepare, grid, dim3(kTile), 0, s, pb.ptrs, xq, mt, d, xqT, pb.sq, flag);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
 
-int launch_infill_trend(hipStream_t s, const InfillTrend &t) {
-    const size_t lds = sizeof(double) * ((size_t)3 * t.p + (size_t)t.msplit);
+static TrendArgs trend_args(const InfillTrend &t, bool mean_only) {
+    TrendArgs g{};
+    g.p = t.p, g.rp = t.rp, g.msplit = t.msplit, g.want_d = !mean_only && t.dneg != nullptr;
+    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.racc = t.racc;
+    g.y_mean = t.y_mean, g.y_std = t.y_std, g.mean = t.mean;
+    if (mean_only) return g;
+    g.R = t.R, g.Rt = t.Rt, g.s0 = t.s0, g.sl = t.sl;
+    g.sigma2 = t.sigma2;
+    g.var = t.var, g.dneg = t.dneg;
+    return g;
+}
+// the members of a run have one trend and one split count: the launch's LDS is member 0's
+static int launch_trend(hipStream_t s, const InfillTrend *t, int count, bool mean_only) {
+    if (!run_count_ok(count)) return EGX_ERR_INVALID_VALUE;
+    const size_t lds = sizeof(double) * ((size_t)(mean_only ? 1 : 3) * t[0].p + (size_t)t[0].msplit);
     if (lds > 65536) {
         set_error("infill: more than 2560 regression columns");
         return EGX_ERR_UNSUPPORTED;
     }
-    TrendArgs g;
-    g.p = t.p, g.rp = t.rp, g.msplit = t.msplit, g.want_d = t.dneg != nullptr;
-    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.R = t.R, g.Rt = t.Rt, g.racc = t.racc, g.s0 = t.s0, g.sl = t.sl;
-    g.sigma2 = t.sigma2, g.y_mean = t.y_mean, g.y_std = t.y_std;
-    g.mean = t.mean, g.var = t.var, g.dneg = t.dneg;
-    hipLaunchKernelGGL(k_infill_trend, dim3(kTile), dim3(kInfThreads), lds, s, g);
+    TrendBatch gb{};
+    for (int j = 0; j < count; j++) gb.m[j] = trend_args(t[j], mean_only);
+    const dim3 grid(kTile, (unsigned)count);
+    if (mean_only) hipLaunchKernelGGL(k_infill_trend_mean, grid, dim3(kInfThreads), lds, s, gb);
+    else hipLaunchKernelGGL(k_infill_trend, grid, dim3(kInfThreads), lds, s, gb);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
+int launch_infill_trend(hipStream_t s, const InfillTrend *t, int count) { return launch_trend(s, t, count, false); }
+int launch_infill_trend_mean(hipStream_t s, const InfillTrend *t, int count) { return launch_trend(s, t, count, true); }
 
-int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *out_v,
-                               const double *x_std, double *gmean, double *gvar) {
-    XgFinishArgs g;
+static int launch_xgrad_finish(hipStream_t s, const InfillTrend *t, const InfillFinish *f, int count, int d, int nsplit, bool mean_only) {
+    if (!run_count_ok(count)) return EGX_ERR_INVALID_VALUE;
     if (nsplit < 1 || nsplit > kXgStage) {
         set_error("infill: split count of the x-gradient contraction out of range");
         return EGX_ERR_INVALID_VALUE;
     }
-    g.d = d, g.p = t.p, g.rp = t.rp, g.nsplit = nsplit;
-    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.dneg = t.dneg, g.out_y = out_y, g.out_v = out_v, g.x_std = x_std;
-    g.sigma2 = t.sigma2, g.y_std = t.y_std, g.gmean = gmean, g.gvar = gvar;
-    hipLaunchKernelGGL(k_infill_xgrad_finish, dim3(kTile), dim3(kInfThreads), 0, s, g);
+    XgFinishBatch gb{};
+    for (int j = 0; j < count; j++) {
+        XgFinishArgs &g = gb.m[j];
+        g.d = d, g.p = t[j].p, g.rp = t[j].rp, g.nsplit = nsplit;
+        g.xqT = t[j].xqT, g.fidx = t[j].fidx, g.beta = t[j].beta, g.out_y = f[j].out_y, g.x_std = f[j].x_std;
+        g.y_std = t[j].y_std, g.gmean = f[j].gmean;
+        if (mean_only) continue;
+        g.dneg = t[j].dneg, g.out_v = f[j].out_v;
+        g.sigma2 = t[j].sigma2, g.gvar = f[j].gvar;
+    }
+    const dim3 grid(kTile, (unsigned)count);
+    if (mean_only) hipLaunchKernelGGL(k_infill_xgrad_finish_mean, grid, dim3(kInfThreads), 0, s, gb);
+    else hipLaunchKernelGGL(k_infill_xgrad_finish, grid, dim3(kInfThreads), 0, s, gb);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
+}
+int launch_infill_xgrad_finish(hipStream_t s, const InfillTrend *t, const InfillFinish *f, int count, int d, int nsplit) {
+    return launch_xgrad_finish(s, t, f, count, d, nsplit, false);
+}
+int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend *t, const InfillFinish *f, int count, int d, int nsplit) {
+    return launch_xgrad_finish(s, t, f, count, d, nsplit, true);
 }
 
 int launch_infill_cstr(hipStream_t s, const infill::Params &prm, int strategy, int k, int d, int64_t m, int64_t mstride,
@@ -492,36 +548,6 @@ int launch_infill_cstr(hipStream_t s, const infill::Params &prm, int strategy, i
     p.feasibility = 1;
     hipLaunchKernelGGL(k_infill_cstr, dim3((unsigned)((m + kInfThreads - 1) / kInfThreads)), dim3(kInfThreads), 0, s, p, strategy, k,
                        d, m, mstride, mean, var, gmean, gvar, scale, flag, value, cstr, grad, gcstr);
-    EGX_HIP_CHECK(hipGetLastError());
-    return EGX_SUCCESS;
-}
-
-int launch_infill_trend_mean(hipStream_t s, const InfillTrend &t) {
-    const size_t lds = sizeof(double) * ((size_t)t.p + (size_t)t.msplit);
-    if (lds > 65536) {
-        set_error("infill: more than 2560 regression columns");
-        return EGX_ERR_UNSUPPORTED;
-    }
-    TrendArgs g{};
-    g.p = t.p, g.rp = t.rp, g.msplit = t.msplit, g.want_d = 0;
-    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.racc = t.racc;
-    g.y_mean = t.y_mean, g.y_std = t.y_std, g.mean = t.mean;
-    hipLaunchKernelGGL(k_infill_trend_mean, dim3(kTile), dim3(kInfThreads), lds, s, g);
-    EGX_HIP_CHECK(hipGetLastError());
-    return EGX_SUCCESS;
-}
-
-int launch_infill_xgrad_finish_mean(hipStream_t s, const InfillTrend &t, int d, int nsplit, const double *out_y, const double *x_std,
-                                    double *gmean) {
-    if (nsplit < 1 || nsplit > kXgStage) {
-        set_error("infill: split count of the x-gradient contraction out of range");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    XgFinishArgs g{};
-    g.d = d, g.p = t.p, g.rp = t.rp, g.nsplit = nsplit;
-    g.xqT = t.xqT, g.fidx = t.fidx, g.beta = t.beta, g.out_y = out_y, g.x_std = x_std;
-    g.y_std = t.y_std, g.gmean = gmean;
-    hipLaunchKernelGGL(k_infill_xgrad_finish_mean, dim3(kTile), dim3(kInfThreads), 0, s, g);
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }

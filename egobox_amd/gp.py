@@ -547,20 +547,15 @@ def fit_multi(handles, theta0s, lo, hi, max_eval=GP_COBYLA_MAX_EVAL):
     return ne
 
 
-def predict_valvar_multi(handles, xqs, want_val=True, want_var=True):
-    """egx_gp_predict_valvar_multi: the posterior of k fitted models at once, handles[j] answering ITS OWN queries xqs[j]
-    (xqs: k x m x d, original units).  Members of one group (GpHandle.create_group / GpParams.fit_group) in consecutive slots
-    answer in lock-step -- one launch sequence and one host synchronisation per run of members instead of one per member --
-    each bit for bit as its own batched `predict_valvar` would.  Returns (y, var), k x m each, None for the one not wanted."""
+def _multi_queries(who, handles, xqs):
+    """(raw handles, k, xqs as a contiguous (k, m, d) array) of a multi-model posterior call, checked before any device work."""
     k = len(handles)
     if k < 1:
-        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi needs at least one model")
-    if not (want_val or want_var):
-        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi: nothing asked for (want_val and want_var are False)")
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{who} needs at least one model")
     hs = [getattr(h, "handle", h) for h in handles]
     d = hs[0].d
     if any(h.d != d for h in hs):
-        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi: the models must have the same input dimension")
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{who}: the models must have the same input dimension")
     if len({id(h) for h in hs}) != k:
         raise L.InvalidValueError(L.ERR_INVALID_VALUE, "the models of a multi-model call must be distinct handles")
     xqs = L.as_f64(xqs)
@@ -568,13 +563,41 @@ def predict_valvar_multi(handles, xqs, want_val=True, want_var=True):
         xqs = xqs[:, :, None]
     if xqs.ndim != 3 or xqs.shape[0] != k or xqs.shape[2] != d:
         raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"query points must be ({k}, m, {d}), got {xqs.shape}")
-    xqs = np.ascontiguousarray(xqs)
+    return hs, k, np.ascontiguousarray(xqs)
+
+
+def predict_valvar_multi(handles, xqs, want_val=True, want_var=True):
+    """egx_gp_predict_valvar_multi: the posterior of k fitted models at once, handles[j] answering ITS OWN queries xqs[j]
+    (xqs: k x m x d, original units).  Members of one group (GpHandle.create_group / GpParams.fit_group) in consecutive slots
+    answer in lock-step -- one launch sequence and one host synchronisation per run of members instead of one per member --
+    each bit for bit as its own batched `predict_valvar` would.  Returns (y, var), k x m each, None for the one not wanted."""
+    if len(handles) >= 1 and not (want_val or want_var):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "predict_valvar_multi: nothing asked for (want_val and want_var are False)")
+    hs, k, xqs = _multi_queries("predict_valvar_multi", handles, xqs)
     m = xqs.shape[1]
     y = np.empty((k, m)) if want_val else None
     v = np.empty((k, m)) if want_var else None
     L.check(L.load().egx_gp_predict_valvar_multi(_handle_array(hs), k, L.dptr(xqs), m, L.dptr(y) if want_val else None,
                                                   L.dptr(v) if want_var else None))
     return y, v
+
+
+def predict_valvar_gradients_multi(handles, xqs, want_val=True, want_var=True):
+    """egx_gp_predict_valvar_gradients_multi: the x-gradients of the mean and of the variance of k fitted models at once,
+    handles[j] answering ITS OWN queries xqs[j] (xqs: k x m x d, original units).  Members of one group in consecutive slots
+    answer in lock-step, each bit for bit as its own `predict_valvar_gradients` (m > 8; a lone call of at most 8 points may
+    take its few-query route, and the two then agree to rounding).  Returns (grad_y, grad_var), k x m x d each, None for the
+    one not wanted."""
+    if len(handles) >= 1 and not (want_val or want_var):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE,
+                                  "predict_valvar_gradients_multi: nothing asked for (want_val and want_var are False)")
+    hs, k, xqs = _multi_queries("predict_valvar_gradients_multi", handles, xqs)
+    m, d = xqs.shape[1], xqs.shape[2]
+    gy = np.empty((k, m, d)) if want_val else None
+    gv = np.empty((k, m, d)) if want_var else None
+    L.check(L.load().egx_gp_predict_valvar_gradients_multi(_handle_array(hs), k, L.dptr(xqs), m, L.dptr(gy) if want_val else None,
+                                                            L.dptr(gv) if want_var else None))
+    return gy, gv
 
 
 def set_tuning(knob, value):

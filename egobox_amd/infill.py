@@ -211,6 +211,15 @@ class InfillObjective:
         return None if n.value == 0 else (idx[:n.value].astype(np.int64), xb)
 
     @property
+    def runs(self):
+        """The lengths of the runs an evaluation walks (egx_infill_get_runs): consecutive surrogates of one shape that go through
+        one launch sequence per tile.  They sum to 1 + n_cstr; the results never depend on them."""
+        n = C.c_int32()
+        lens = np.zeros(1 + self.n_cstr, dtype=np.int32)
+        L.check(self._lib.egx_infill_get_runs(self._h, C.byref(n), lens.ctypes.data_as(L.c_int32_p)))
+        return [int(v) for v in lens[:n.value]]
+
+    @property
     def width(self):
         """Columns of a trial point, a limit, a gradient row: n_active while an activity is set, else d."""
         return self.d if self._active is None else int(self._active[0].shape[0])

@@ -278,7 +278,8 @@ int32_t egx_gp_likelihood_grad_batch(egx_gp *gp, const double *thetas, int64_t k
 int32_t egx_gp_finalize(egx_gp *gp, const double *theta, int64_t theta_len);
 /* Lock-step across MODELS.  The reference's callers multiply independent models, not only candidates of one model: the
  * expert loop of egobox-moe (crates/moe/src/algorithm.rs:167-177: one GP per cluster, fitted one after the other) and
- * EGO's objective + constraint surrogates (crates/ego/src/solver/solver_impl.rs:370-391).
+ * EGO's objective + constraint surrogates (crates/ego/src/solver/solver_impl.rs:370-391) -- whose QUERY side is lock-step too:
+ * egx_gp_predict_valvar_multi, egx_gp_predict_valvar_gradients_multi, and the runs of an infill handle (egx_infill_get_runs).
  *   egx_gp_create_group   k models of ONE shape (same n, d, trend, kernel, nugget: `cfg`; training sets x (k x n x d) and
  *                         y (k x n), one after the other) whose matrices live in one slab at the strides a lock-step launch
  *                         needs.  out[0..k) are ordinary handles with one workspace each -- every entry point works on them
@@ -361,6 +362,20 @@ int32_t egx_gp_predict_gradients(egx_gp *gp, const double *xq, int64_t m, double
 int32_t egx_gp_predict_var_gradients(egx_gp *gp, const double *xq, int64_t m, double *grad /*m*d*/);
 int32_t egx_gp_predict_valvar_gradients(egx_gp *gp, const double *xq, int64_t m, double *grad_y /*m*d*/,
                                         double *grad_var /*m*d*/);
+/* The x-gradients of k DISTINCT fitted models in one call -- the query side of egx_gp_create_group's client, an optimiser's
+ * objective and constraint surrogates (solver_impl.rs:370-391): gps[j] answers ITS OWN block of m queries, rows [j m, (j + 1) m)
+ * of xq, into block j (m x d) of grad_y and grad_var (either may be NULL, not both).  Runs of fitted members of one group in
+ * consecutive slots with one n and trend (and a correlation with one coefficient column per input: not KPLS + Matern) answer
+ * in lock-step: one launch sequence per run, chunk of queries and half, the member a grid coordinate of the x-gradient kernels
+ * and of the weight GEMMs, whose C^-T and -R^-1 F the group holds for all its members at one stride (allocated on the first
+ * such call or the first variance-gradient call of any member; per member what a lone handle holds).  A run is at most 16
+ * members and is cut where its blocks pass the bound of egx_gp_predict_valvar_multi; any other handle is served on its own
+ * as by egx_gp_predict_valvar_gradients.  CONTRACT: for every member and m > 8, both arrays are bit for bit what
+ * egx_gp_predict_valvar_gradients(gps[j], block j, m, ..) returns; for m <= 8 the lone call may take its few-query route, a
+ * run never does, and the two agree to rounding only.  Arguments, locking and errors as for egx_gp_predict_valvar_multi. */
+int32_t egx_gp_predict_valvar_gradients_multi(egx_gp *const *gps, int32_t k, const double *xq /*k x m x d, block j for gps[j]*/,
+                                              int64_t m, double *grad_y /*k x m x d or NULL*/,
+                                              double *grad_var /*k x m x d or NULL*/);
 
 /* ---- posterior covariance and trajectories (GpSurrogateExt::sample, crates/moe/src/surrogates.rs:66-81;
  * GaussianProcess::_compute_covariance algorithm.rs:310-326, sample_chol / sample_eig / sample :383-395, helper
@@ -987,6 +1002,18 @@ int32_t egx_infill_set_active(egx_infill *h, const int32_t *active /*n_active*/,
 int32_t egx_infill_clear_active(egx_infill *h);
 /* *n_active (0: no activity); optionally the indices and the base point (each d long at most, or NULL) */
 int32_t egx_infill_get_active(egx_infill *h, int32_t *n_active, int32_t *active /*d, or NULL*/, double *x_base /*d, or NULL*/);
+
+/* ---- runs.  An evaluation walks the points in tiles and, per tile, the surrogates in RUNS: consecutive surrogates that go through
+ * ONE launch sequence, the member a grid coordinate of every kernel of it, instead of one sequence each.  Surrogates js .. js +
+ * len - 1 form a run when each is a lone dense model; all have the same n, kernel, trend and coefficient columns; all take the same
+ * sequence kind (the objective always the full one; the constraints the mean-only one exactly under EGX_CSTR_MEAN, when no
+ * variance of theirs is asked for); the handle has no pending points; len <= 16.  A mean-only run needs nothing more (separately
+ * created models of one shape qualify); a full-sequence run also needs its members to be members of ONE group in consecutive
+ * slots (egx_gp_create_group), whose factors and C^-T sit at one stride.  Surrogates are never reordered.  CONTRACT: every
+ * output of every entry point of a handle is bit for bit what the same surrogates give with all runs of length 1.
+ * egx_infill_get_runs reports the runs of a walk over all surrogates under the current strategy and pending state: *n_runs, and
+ * their lengths in order (they sum to 1 + n_cstr). */
+int32_t egx_infill_get_runs(egx_infill *h, int32_t *n_runs, int32_t *run_len /* 1 + n_cstr, or NULL */);
 
 #ifdef __cplusplus
 }

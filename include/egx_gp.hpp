@@ -568,6 +568,18 @@ inline std::pair<std::vector<double>, std::vector<double>> predict_valvar_group(
     return {std::move(y), std::move(v)};
 }
 
+// The x-gradients of k fitted models in one call (egx_gp_predict_valvar_gradients_multi): model j answers rows [j m, (j + 1) m)
+// of xq.  Members of one group answer in lock-step, each bit for bit as its own predict_valvar_gradients (m > 8): what an
+// optimiser asks of its objective and constraint surrogates.  Returns (grad_y, grad_var), k x m x d each.
+inline std::pair<std::vector<double>, std::vector<double>> predict_valvar_gradients_group(
+    const std::vector<const GaussianProcess *> &models, const double *xq, int64_t m, int64_t d) {
+    std::vector<egx_gp *> hs;
+    for (const GaussianProcess *g : models) hs.push_back(g->handle());
+    std::vector<double> gy(hs.size() * (size_t)m * (size_t)d), gv(hs.size() * (size_t)m * (size_t)d);
+    check(egx_gp_predict_valvar_gradients_multi(hs.data(), (int32_t)hs.size(), xq, m, gy.data(), gv.data()));
+    return {std::move(gy), std::move(gv)};
+}
+
 // GpMixture::predict / predict_var over fitted experts of THIS process (crates/moe/src/algorithm.rs:411-423, 670-685 smooth;
 // :879-935 hard): probas (m x n_experts row-major) are the responsibilities, xq (m x d) in original units.
 inline std::pair<std::vector<double>, std::vector<double>> moe_predict_valvar(const std::vector<const GaussianProcess *> &experts,
@@ -944,6 +956,14 @@ class InfillObjective {
         return a;
     }
     int64_t width() const { return w_ > 0 ? w_ : d_; }  // of a point, a limit, a gradient row
+    // the lengths of the runs an evaluation walks (egx_infill_get_runs); they sum to 1 + n_cstr
+    std::vector<int32_t> runs() const {
+        int32_t n = 0;
+        std::vector<int32_t> len((size_t)k_ + 1, 0);
+        check(egx_infill_get_runs(h_.get(), &n, len.data()));
+        len.resize((size_t)n);
+        return len;
+    }
     egx_infill *handle() const { return h_.get(); }
 
   private:

@@ -61,6 +61,18 @@ grad=True), four).  Legs alternated (full, active, full again: the two full runs
 quartiles, written to profiles/infill_active_bench.txt; no threshold is set.
 
     python tools/infill_bench.py --active [--out profiles/infill_active_bench.txt] [--reps 15]
+
+--runs times RUNS (egx_infill_get_runs: consecutive surrogates of one shape through one launch sequence per tile) on an objective
+and k = 2, 8, 68 constraint models (68: the reference's mopta08 example), squared exponential, n = 300 and n = 2000 at d = 8, and
+d = 124 with 25 active columns at n = 300: one evaluation of 20 points with gradients, and the SLSQP multistart from 20 starts (at
+most 30 evaluations per start).  Two variants: MEAN -- separately created models, the constraints as mean constraints (what Egor
+builds by default: the run 1 | k) -- and FULL -- the models of one group, the constraints folded into the objective (one run of
+1 + k, cut at 16).  The tool uses only entry points that exist without runs: run on another build of the library with
+--package-root DIR (the directory that holds that build's egobox_amd), it times that build's walk, one sequence per model -- the
+yardstick.  A job alternates the two builds in one GPU call and takes the medians per shape; the spread comes from two runs of
+the same build.  Medians after 3 warm-ups, written to profiles/infill_runs_bench.txt; no threshold is set.
+
+    python tools/infill_bench.py --runs [--out profiles/infill_runs_bench.txt] [--reps 9] [--package-root DIR]
 """
 import argparse
 import os
@@ -70,7 +82,10 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+PKG_ROOT = ROOT
+if "--package-root" in sys.argv[1:-1]:  # another build of the library (--runs): before the import below
+    PKG_ROOT = os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1])
+sys.path.insert(0, PKG_ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import egobox_amd as egx  # noqa: E402
@@ -357,6 +372,46 @@ def run_active(args, emit):
             egx.trim()
 
 
+def run_runs(args, emit):
+    m, n_start, budget = 20, 20, 30
+    rng = np.random.default_rng(2)
+    emit("# runs: objective + k constraint models, squared exponential, LogEI; eval = one evaluation of %d points with gradients," % m)
+    emit("# slsqp = the SLSQP multistart from %d starts, at most %d evaluations per start; MEAN: separate models, mean constraints;" % (n_start, budget))
+    emit("# FULL: the models of one group, the constraints folded into the objective; a = active columns (0: full width);")
+    emit("# median wall ms over %d calls after 3 warm-ups; package: %s" % (args.reps, os.path.relpath(PKG_ROOT, ROOT)))
+    emit("# variant n d a k runs eval_ms slsqp_ms")
+    for n, d, a in ((300, 8, 0), (2000, 8, 0), (300, 124, 25)):
+        for k in (2, 8, 68):
+            xs, ys = [], []
+            for j in range(1 + k):
+                x, y = workload.make_training_set(n, d, seed=100 + j)
+                xs.append(x), ys.append(1e-3 * y if j == 0 else y - np.quantile(y, 0.6))
+            thetas = np.full((1 + k, d), 1.5 if d == 8 else 1.5 / d)
+            for variant in ("MEAN", "FULL"):
+                if variant == "FULL":
+                    hs = egx.GpHandle.create_group(np.stack(xs), np.stack(ys))
+                    egx.finalize_multi(hs, thetas)
+                else:
+                    hs = [egx.GpHandle(x, y) for x, y in zip(xs, ys)]
+                    for h, th in zip(hs, thetas):
+                        h.finalize(th)
+                with egx.InfillObjective(hs[0], hs[1:], [1e-3] * k, criterion=egx.LOG_EI, fmin=float(np.quantile(ys[0], 0.05))) as obj:
+                    obj.set_cstr_strategy("mean" if variant == "MEAN" else "infill")
+                    runs = "|".join(str(v) for v in obj.runs) if hasattr(type(obj), "runs") else "-"
+                    w = a if a else d
+                    if a:
+                        obj.set_active(rng.permutation(d)[:a], np.full(d, 0.5))
+                    xq, starts = rng.random((m, w)), rng.random((n_start, w))
+                    lim = np.tile([0.0, 1.0], (w, 1))
+                    call = obj.value_and_grad if variant == "FULL" else (lambda pts: obj.constraints(pts, grad=True))
+                    t_eval = median_ms(lambda: call(xq), args.reps)
+                    t_opt = median_ms(lambda: obj.optimize_slsqp(lim, starts, max_eval=budget), max(3, args.reps // 3), warm=1)
+                    emit(f"{variant} {n} {d} {a} {k} {runs} {t_eval:.3f} {t_opt:.3f}")
+                for h in hs:
+                    h.close()
+                egx.trim()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -366,11 +421,13 @@ def main():
     ap.add_argument("--slsqp", action="store_true", help="20 starts of SLSQP: the lock-step call, scipy on the m = 1 closures, COBYLA")
     ap.add_argument("--pending", action="store_true", help="pending points: one evaluation at q = 0 .. 16, the batch call against the refit loop")
     ap.add_argument("--active", action="store_true", help="active coordinates: one evaluation of 20 points, full width against a = d / 5 columns")
+    ap.add_argument("--runs", action="store_true", help="runs: objective + 2, 8, 68 constraints, one evaluation and the SLSQP multistart")
+    ap.add_argument("--package-root", default=None, help="(--runs) the directory that holds another build's egobox_amd package")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--only-m21", action="store_true", help="the m = 21 fused leg alone, small shape (for a kernel trace)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "infill_active_bench.txt" if args.active else "infill_pending_bench.txt" if args.pending else "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
+        args.out = os.path.join(ROOT, "profiles", "infill_runs_bench.txt" if args.runs else "infill_active_bench.txt" if args.active else "infill_pending_bench.txt" if args.pending else "infill_slsqp_bench.txt" if args.slsqp else "infill_cstr_round.txt" if args.cstr else "infill_sparse_bench.txt" if args.sparse
                                 else "infill_mix_eval_ab.txt" if args.mix else "infill_eval_ab.txt")
     lines = []
 
@@ -388,8 +445,8 @@ def main():
             obj.value(xq)
             obj.value_and_grad(xq)
         return
-    if args.slsqp or args.pending or args.active:
-        (run_active if args.active else run_pending if args.pending else run_slsqp)(args, emit)
+    if args.slsqp or args.pending or args.active or args.runs:
+        (run_runs if args.runs else run_active if args.active else run_pending if args.pending else run_slsqp)(args, emit)
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         return
