@@ -395,6 +395,7 @@ struct GemmTrace {
 // Look-ahead resources: s2 = chain stream (diagonal blocks, panel solves), s3 = side stream (the off-critical-path rest
 // of the chain's updates), both high priority; events: ev_lu (next diagonal block updated), ev_lur (rest of the next
 // group's columns updated), ev_panel (chain of the next group done), ev_a / ev_b (hand-offs between s2 and s3).
+// Both streams or none: launch_potrf takes a look-ahead without s2 or without s3 as no look-ahead.
 struct PotrfLookahead {
     hipStream_t s2 = nullptr, s3 = nullptr;
     hipEvent_t ev_lu = nullptr, ev_lur = nullptr, ev_panel = nullptr, ev_a = nullptr, ev_b = nullptr;

@@ -36,6 +36,7 @@
 #include "dev_mem.h"
 #include "potf2_blocks.h"
 #include "mfma_gemm_core.h"
+#include "potrf_plan.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -1061,7 +1062,7 @@ static std::atomic<int> g_trsv_stall{0};  // egx_set_tuning "trsv_stall" (test b
 static std::atomic<int> g_trsv_fused{1};          // EGX_TRSV_FUSED=0: the back-substitution gamma = C^-T rho as one launch PER BLOCK (rounds 1-5) instead of one launch
 static std::atomic<int> g_potrf_left{1};          // EGX_POTRF_LEFT: left-looking group updates (factor and C^-T rider) 0 never, 1 by schedule.h, 2 always
 constexpr int kTrsmGroupPanels = 4;   // panels per update in the solves after the factorisation
-constexpr int kLurSideMinCols = 6144; // LUr on the side stream only while at least this many columns trail the look-ahead group
+static_assert(kPlanPanel == kNB, "potrf_plan.h plans in panels of kNB columns");
 
 int chol_init() {
     static std::once_flag once;
@@ -1249,7 +1250,9 @@ int launch_gram_lower(hipStream_t s, const double *W, int64_t ldw, int rows, int
 //   * as soon as the next group's first diagonal block has been updated (LUd) that group's chain -- diagonal blocks,
 //     panel solves, in-group updates -- runs on the auxiliary high-priority streams (lk->s2 / lk->s3), concurrently with
 //     the rest of the look-ahead columns (LUr) and the trailing update (RU) on `s`.
-// lk == nullptr (or lk->s2 == nullptr) runs everything in order on `s`.
+// lk == nullptr (or a lk without both streams) runs everything in order on `s`.
+// The ORDER -- which launch and which event record / wait, on which stream -- is potrf_plan.h (host-testable: tests/c_host/
+// potrf_plan_test.cpp); the function resolves the plan's input and walks the plan.
 // batch != nullptr: batch->count matrices in lock-step (matrix z at M + z sM, dinv + z sD, info + z sI); every launch
 // below covers all of them (grid.z), the schedule is the one a single matrix of this size gets.
 int launch_potrf(hipStream_t s, double *M, int64_t ld, int n_pad, int m_tot, double *dinv, int *info,
@@ -1263,37 +1266,19 @@ int launch_potrf(hipStream_t s, double *M, int64_t ld, int n_pad, int m_tot, dou
     }
     const PotrfBatch pb = batch ? *batch : PotrfBatch();
     const unsigned nz = (unsigned)(pb.count > 0 ? pb.count : 1);
-    GemmBatch gb;
+    GemmBatch gb, gbw;  // the updates of the factor; of the rider (C and A in W, B in the factor)
     gb.count = (int)nz;
     gb.sC = gb.sA = gb.sB = pb.sM;
     gb.sInfo = pb.sI;
-    hipStream_t s2 = lk ? lk->s2 : nullptr, s3 = lk ? lk->s3 : nullptr;
-    auto potf2 = [&](hipStream_t st, int k0, int nbk) {
-        double *diag = M + (int64_t)k0 * ld + k0;
-        double *dtiles = dinv + (int64_t)(k0 / 64) * 4096;
-        // (the 64x64 tile inverses `dinv` -- for the solves AFTER the factorisation -- are built at the end, all at once;
-        //  during the factorisation their slots carry the 16x16 inverses + refinement flags to the panel solve)
-        hipLaunchKernelGGL(k_potf2_reg<16>, dim3(1, 1, nz), dim3(1024), RB_LDS_BYTES, st, diag, ld, nbk, dtiles, info, k0, n_pad,
-                           pb.sM, pb.sD, pb.sI);
-    };
-    auto trsm = [&](hipStream_t st, int k0, int nbk) {
-        const int below = m_tot - (k0 + nbk);  // a multiple of 64
-        if (below <= 0) return;
-        double *P = M + (int64_t)(k0 + nbk) * ld + k0;
-        const double *L = M + (int64_t)k0 * ld + k0;
-        const double *lin = dinv + (int64_t)(k0 / 64) * 4096;
-        if (below >= 4096)  // tall panels: two 16-row tiles per workgroup (+1 %, profiles/r02_run34_*)
-            hipLaunchKernelGGL((k_panel_trsm16<2, false>), dim3(below / 32, 1, nz), dim3(256), 0, st, P, ld, L, ld, lin, nbk,
-                               (const int *)info, pb.sM, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
-        else
-            hipLaunchKernelGGL((k_panel_trsm16<1, false>), dim3(below / 16, 1, nz), dim3(256), 0, st, P, ld, L, ld, lin, nbk,
-                               (const int *)info, pb.sM, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
-    };
-    // C[r0.., c0..c0+N) -= P[r0.., k0..k0+K) P[c0..c0+N, k0..k0+K)^T for the M rows from r0
-    auto update = [&](hipStream_t st, int r0, int c0, int Mr, int N, int k0, int K, int lower, bool *big, int tag = 0) -> int {
-        return launch_gemm_nt_sub(st, M + (int64_t)r0 * ld + c0, ld, M + (int64_t)r0 * ld + k0, ld,
-                                  M + (int64_t)c0 * ld + k0, ld, Mr, N, K, lower, 0, big, info, &gb, tag);
-    };
+    if (inv) {
+        gbw.count = (int)nz;
+        gbw.sC = gbw.sA = inv->sW;
+        gbw.sB = pb.sM;
+        gbw.sInfo = pb.sI;
+    }
+    // ---- prologue: everything the order depends on, resolved (potrf_plan.h takes it from here)
+    PotrfPlanInput in;
+    in.n_pad = n_pad, in.m_tot = m_tot;
     // groups of four panels (K = 1024 per trailing update: half the C tile traffic and tile boundaries of K = 512) pay
     // from n ~ 14000 on (measured, profiles/r02_run13_group_by_size.txt: n = 16384 -2 %, n = 12288 even, n = 8192 +5 %:
     // the chain of a group gets longer while its trailing update shrinks)
@@ -1303,7 +1288,14 @@ int launch_potrf(hipStream_t s, double *M, int64_t ld, int n_pad, int m_tot, dou
     //  process-wide knobs, so egx_set_tuning never changes the arithmetic of a handle that exists -- egx_gp_get_schedule stays
     //  true.  A device on which the launch does not fit -- one workgroup per diagonal block and matrix: a partitioned GPU -- takes
     //  the separate launches for the whole factorisation.)
-    const int GW = (pb.group_panels > 0 ? pb.group_panels : potrf_group_panels(n_pad)) * kNB;
+    const int GW = in.GW = (pb.group_panels > 0 ? pb.group_panels : potrf_group_panels(n_pad)) * kNB;
+    in.left = pb.left != 0;
+    in.w_left = pb.w_left != 0 && n_pad % 256 == 0;  // one decision for the whole factorisation (GW % 256 == 0)
+    in.lookahead = lk && lk->s2 && lk->s3;
+    in.rider = inv != nullptr;
+    in.seqs = pb.seqs;
+    in.look_min = g_look_min_cols, in.lur_side = g_lur_side;  // (streams only: the arithmetic is the same either way)
+    in.trace = trace && trace->ready;
     // (not with the theta-gradient's rider: a flow launch holds every compute unit, so the rider's substitution -- as many flops as
     //  the factorisation, which otherwise fill the chain's bubbles group by group -- would run behind it instead of beside it.
     //  Measured, one candidate, flow / separate launches: n = 8192 13.5 / 12.2 ms, 12288 38.6 / 35.3, 16384 77.8 / 76.5:
@@ -1311,309 +1303,103 @@ int launch_potrf(hipStream_t s, double *M, int64_t ld, int n_pad, int m_tot, dou
     //  to rounding, 1e-12, not bit for bit.)
     const bool flow = pb.sync != nullptr && pb.flow != 0 && nz == 1 && inv == nullptr && flow_fits(n_pad);
     // (a flow launch for the LAST columns of a right-looking factorisation: the switch happens on a group boundary)
-    const int tail_cols = (pb.sync != nullptr && pb.flow_tail > 0 && nz == 1 && inv == nullptr && !pb.left && pb.flow_tail < n_pad && (n_pad - pb.flow_tail) % GW == 0 &&
-                           flow_fits(pb.flow_tail))
-                              ? pb.flow_tail
-                              : 0;
-    const bool have_sync = flow || tail_cols > 0 || (pb.sync != nullptr && pb.pipe != 0 &&
+    in.tail_cols = (pb.sync != nullptr && pb.flow_tail > 0 && nz == 1 && inv == nullptr && !pb.left && pb.flow_tail < n_pad && (n_pad - pb.flow_tail) % GW == 0 &&
+                    flow_fits(pb.flow_tail))
+                       ? pb.flow_tail
+                       : 0;
+    const bool have_sync = flow || in.tail_cols > 0 || (pb.sync != nullptr && pb.pipe != 0 &&
                                     pipe_fits((int)nz, ((pb.whole || GW > n_pad ? n_pad : GW) + kNB - 1) / kNB));
-    const bool pipe = have_sync && !flow && tail_cols == 0;
+    in.chain = flow ? PotrfChain::FLOW
+               : in.tail_cols > 0 ? PotrfChain::FLOW_TAIL
+               : !have_sync ? PotrfChain::SEPARATE
+               : pb.whole ? PotrfChain::PIPE_WHOLE
+                          : PotrfChain::PIPE_GROUP;
     if (have_sync) EGX_HIP_CHECK(hipMemsetAsync(pb.sync, 0, sizeof(int) * (nz > 1 ? (size_t)pb.sS * nz : pipe_sync_ints(n_pad, m_tot)), s));
-    auto gwidth = [&](int g0) { return (n_pad - g0 < GW) ? (n_pad - g0) : GW; };
-    // panels of one group on stream `st`; `side` != nullptr splits every in-group update into the next diagonal block
-    // (on st) and the rest (on side); `first_wait` is waited for before the FIRST panel solve (the rest of the update
-    // that brought this group's columns up to date)
-    auto inner_factor = [&](hipStream_t st, int g0, int gw, hipStream_t side, hipEvent_t first_wait) -> int {
-        if (pipe) {  // one launch: diagonal blocks, panel solves and in-group updates hand over to each other on the device
-            // (first_wait -- the rest of the update that brought this group's columns up to date, on another stream -- is
-            //  waited for ON THE DEVICE by the first panel's solve tasks: pipe_signal behind that update)
-            //  With more than two launch sequences of the handle in flight the workgroups that spin on that word -- 96 per launch,
-            //  one compute unit each -- could leave the update they wait for no unit to run on (3 x 96 > 256): the STREAM waits then.
-            const bool on_device = first_wait != nullptr && pb.seqs <= 2;
-            if (first_wait && !on_device) EGX_HIP_CHECK(hipStreamWaitEvent(st, first_wait, 0));
-            const int rc2 = launch_potrf_pipe(st, M, ld, n_pad, m_tot, dinv, info, pb, g0, gw, on_device ? g0 / kNB + 1 : 0, st != s);
-            // (... and by the stream behind the launch: a matrix that lost a pivot skips its tasks without waiting for anything)
-            if (rc2 == EGX_SUCCESS && on_device) EGX_HIP_CHECK(hipStreamWaitEvent(st, first_wait, 0));
-            return rc2;
-        }
-        hipEvent_t pending = first_wait;
-        for (int k0 = g0; k0 < g0 + gw; k0 += kNB) {
-            const int nbk = (g0 + gw - k0 < kNB) ? (g0 + gw - k0) : kNB;
-            potf2(st, k0, nbk);
-            if (pending) {
-                EGX_HIP_CHECK(hipStreamWaitEvent(st, pending, 0));
-                pending = nullptr;
-            }
-            trsm(st, k0, nbk);
-            const int r1 = k0 + nbk;
-            if (r1 >= g0 + gw) break;
-            const int ncols = g0 + gw - r1;
-            const int nb1 = ncols < kNB ? ncols : kNB;  // width of the next panel
-            const int rest_rows = m_tot - r1 - nb1;
-            if (side && rest_rows >= 128) {
-                int rc2 = update(st, r1, r1, nb1, nb1, k0, nbk, 1, nullptr);  // the next diagonal block only
-                if (rc2) return rc2;
-                EGX_HIP_CHECK(hipEventRecord(lk->ev_a, st));
-                EGX_HIP_CHECK(hipStreamWaitEvent(side, lk->ev_a, 0));
-                // everything below it (blocks above the diagonal inside this rectangle are written but never read)
-                rc2 = update(side, r1 + nb1, r1, rest_rows, ncols, k0, nbk, 0, nullptr);
-                if (rc2) return rc2;
-                EGX_HIP_CHECK(hipEventRecord(lk->ev_b, side));
-                pending = lk->ev_b;
-            } else {
-                int rc2 = update(st, r1, r1, m_tot - r1, ncols, k0, nbk, 1, nullptr);
-                if (rc2) return rc2;
-            }
-        }
-        if (pending) EGX_HIP_CHECK(hipStreamWaitEvent(st, pending, 0));
-        return EGX_SUCCESS;
-    };
-    // The rows of W = C^-T through the group of panels [g0, g0 + gw), which is final on `s` when this is called (PotrfInverse,
-    // egx_internal.h): on inv->sw, beside whatever the factorisation does next.  Row i of the identity is zero left of
-    // column i, so panel k0 only has the rows [0, k0 + nbk) to solve and the updates as many rows to carry.
-    GemmBatch gbw;
-    if (inv) {
-        gbw.count = (int)nz;
-        gbw.sC = gbw.sA = inv->sW;
-        gbw.sB = pb.sM;
-        gbw.sInfo = pb.sI;
-    }
-    const bool w_left = pb.w_left != 0 && n_pad % 256 == 0;  // one decision for the whole factorisation (GW % 256 == 0)
-    auto inverse_group = [&](hipStream_t sfin, int g0, int gw) -> int {
-        if (!inv) return EGX_SUCCESS;
-        hipStream_t sw = inv->sw;
-        EGX_HIP_CHECK(hipEventRecord(inv->ev_grp, sfin));
-        EGX_HIP_CHECK(hipStreamWaitEvent(sw, inv->ev_grp, 0));
-        const int gend = g0 + gw;
-        for (int k0 = g0; k0 < gend; k0 += kNB) {
-            const int nbk = (gend - k0 < kNB) ? (gend - k0) : kNB;
-            const int m_eff = k0 + nbk;
-            double *P = inv->W + k0;
-            const double *L = M + (int64_t)k0 * ld + k0;
-            const double *lin = dinv + (int64_t)(k0 / 64) * 4096;
-            if (m_eff >= 4096)
-                hipLaunchKernelGGL((k_panel_trsm16<2, false>), dim3(m_eff / 32, 1, nz), dim3(256), 0, sw, P, inv->ldw, L, ld, lin, nbk,
-                                   (const int *)info, inv->sW, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
+
+    // ---- executor: the plan, step by step; every kind is launched here and nowhere else
+    std::vector<PotrfStep> plan;  // (local: launch_potrf runs concurrently on host threads)
+    plan.reserve(potrf_plan_max_steps(in));
+    potrf_plan(in, plan);
+    const hipStream_t streams[4] = {s, in.lookahead ? lk->s2 : nullptr, in.lookahead ? lk->s3 : nullptr, inv ? inv->sw : nullptr};
+    hipEvent_t events[8] = {};
+    if (in.lookahead)
+        events[(int)PotrfEvent::LU] = lk->ev_lu, events[(int)PotrfEvent::LUR] = lk->ev_lur, events[(int)PotrfEvent::PANEL] = lk->ev_panel,
+        events[(int)PotrfEvent::A] = lk->ev_a, events[(int)PotrfEvent::B] = lk->ev_b;
+    if (inv) events[(int)PotrfEvent::GRP] = inv->ev_grp, events[(int)PotrfEvent::DONE] = inv->ev_done;
+    for (const PotrfStep &p : plan) {
+        const hipStream_t st = streams[(int)p.stream];
+        switch (p.kind) {
+        case PotrfKind::POTF2:
+            // (the 64x64 tile inverses `dinv` -- for the solves AFTER the factorisation -- are built at the end, all at once;
+            //  during the factorisation their slots carry the 16x16 inverses + refinement flags to the panel solve)
+            hipLaunchKernelGGL(k_potf2_reg<16>, dim3(1, 1, nz), dim3(1024), RB_LDS_BYTES, st, M + (int64_t)p.k0 * ld + p.k0, ld, p.K,
+                               dinv + (int64_t)(p.k0 / 64) * 4096, info, p.k0, n_pad, pb.sM, pb.sD, pb.sI);
+            break;
+        case PotrfKind::TRSM:
+        case PotrfKind::W_TRSM: {  // the rows below the block; the rows [0, k0 + nbk) of W's columns
+            const bool fac = p.kind == PotrfKind::TRSM;
+            const int rows = fac ? m_tot - (p.k0 + p.K) : p.k0 + p.K;  // a multiple of 64
+            double *P = fac ? M + (int64_t)(p.k0 + p.K) * ld + p.k0 : inv->W + p.k0;
+            const int64_t ldp = fac ? ld : inv->ldw, sP = fac ? pb.sM : inv->sW;
+            const double *L = M + (int64_t)p.k0 * ld + p.k0;
+            const double *lin = dinv + (int64_t)(p.k0 / 64) * 4096;
+            if (rows >= 4096)  // tall panels: two 16-row tiles per workgroup (+1 %, profiles/r02_run34_*)
+                hipLaunchKernelGGL((k_panel_trsm16<2, false>), dim3(rows / 32, 1, nz), dim3(256), 0, st, P, ldp, L, ld, lin, p.K,
+                                   (const int *)info, sP, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
             else
-                hipLaunchKernelGGL((k_panel_trsm16<1, false>), dim3(m_eff / 16, 1, nz), dim3(256), 0, sw, P, inv->ldw, L, ld, lin, nbk,
-                                   (const int *)info, inv->sW, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
-            const int ncols = gend - (k0 + nbk);
-            if (ncols > 0) {
-                int rc2 = launch_gemm_nt_sub(sw, inv->W + (k0 + nbk), inv->ldw, inv->W + k0, inv->ldw,
-                                             M + (int64_t)(k0 + nbk) * ld + k0, ld, m_eff, ncols, nbk, 0, 0, nullptr, info, &gbw);
-                if (rc2) return rc2;
-            }
+                hipLaunchKernelGGL((k_panel_trsm16<1, false>), dim3(rows / 16, 1, nz), dim3(256), 0, st, P, ldp, L, ld, lin, p.K,
+                                   (const int *)info, sP, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
+            break;
         }
-        const int ncols = n_pad - gend;
-        if (ncols > 0 && w_left) {
-            // left-looking rider (round 4; w_left_for): the NEXT group's columns of W receive all earlier columns at once,
-            //     W[0:gend, next) = -W[0:gend, 0:gend) L[next, 0:gend)^T      (rows below gend: the identity, untouched)
-            // by one launch of the stream kernel with per-tile K ranges (row i of W is zero left of column i) and
-            // zero-initialised accumulators: a tile of W is written once by a long K loop, then read and written once by
-            // its group's own solves -- instead of one read-modify-write pass (K = 1024) per earlier group.  It only reads
-            // rows of the factor that are final with THIS group, so it is issued here, ahead of the next group's chain.
-            const int gwn = gwidth(gend);
-            const int nbx = gend / 128, nby = gwn / 256, nt = nbx * nby;
-            hipLaunchKernelGGL((k_gemm_stream<false, true>), dim3((unsigned)nt * nz, 1, 1), dim3(512), ST_LDS_BYTES, sw, inv->W + gend,
-                               inv->ldw, (const double *)inv->W, inv->ldw, (const double *)(M + (int64_t)gend * ld), ld, gend, nbx,
-                               nby, nt, (const int *)info, gbw);
-            EGX_HIP_CHECK(hipGetLastError());
-        } else if (ncols > 0) {
-            // (round 6 measured this update SPLIT into the next group's columns on this stream and the rest on a second rider stream
-            //  beside the next group's solves -- the timeline shows the rider six groups behind the factorisation with ~0.7 ms of
-            //  small launches exposed per group: one candidate 76.5 -> 79.4 ms at n = 16384, 35.3 -> 39.5 at 12288, 12.2 -> 14.2 at 8192
-            //  (a third stream competing with the factorisation, two launches' tails for one): profiles/r06_rider_split_ab.txt; gone)
-            int rc2 = launch_gemm_nt_sub(sw, inv->W + gend, inv->ldw, inv->W + g0, inv->ldw, M + (int64_t)gend * ld + g0, ld, gend,
-                                         ncols, gw, 0, 0, nullptr, info, &gbw);
-            if (rc2) return rc2;
-        }
-        return EGX_SUCCESS;
-    };
-    // (decided per HANDLE, never by the number of matrices in a launch: a matrix gets the same bits in any batch -- and with or
-    //  without the theta-gradient's rider: its substitution then follows the launch group by group instead of riding along)
-    if (flow || (pipe && pb.whole)) {
-        rc = flow ? launch_potrf_flow(s, M, ld, n_pad, m_tot, dinv, info, pb) : launch_potrf_pipe(s, M, ld, n_pad, m_tot, dinv, info, pb, 0, n_pad);
-        if (rc) return rc;
-        if (inv) {
-            for (int g0 = 0; g0 < n_pad; g0 += GW) {
-                rc = inverse_group(s, g0, gwidth(g0));
-                if (rc) return rc;
-            }
-            EGX_HIP_CHECK(hipEventRecord(inv->ev_done, inv->sw));
-            EGX_HIP_CHECK(hipStreamWaitEvent(s, inv->ev_done, 0));
-        }
-        hipLaunchKernelGGL(k_diag_tile_inverses, dim3(n_pad / 64, 1, nz), dim3(256), 0, s, (const double *)M, ld, dinv,
-                           dinv + (int64_t)(n_pad / 64) * 4096, pb.sM, pb.sD);
-        EGX_HIP_CHECK(hipGetLastError());
-        return EGX_SUCCESS;
-    }
-    if (pb.left) {
-        // LEFT-looking over the groups of panels (round 4): the columns of group J receive the contributions of ALL earlier
-        // columns in two updates -- a LONG one, K = every column before the previous group, and a SHORT one, K = the previous
-        // group (1024) -- instead of one read-modify-write pass per earlier group: a tile of the factor is read and written
-        // twice in the whole factorisation, by long K loops (what makes the theta-gradient's R^-1 launch run at 0.85 of
-        // peak; the long updates of a lock-step group of eight measured 0.82, the right-looking trailing updates 0.72).
-        // Look-ahead: the chain of group J (diagonal blocks, panel solves, in-group updates; stream s2) runs beside the
-        // long update of group J + 1 (stream s), which only needs the groups before J:
-        //     s :  ... U_long(J) | wait C(J-1) | U_short(J) | rec U(J) | U_long(J+1) | wait C(J) | U_short(J+1) ...
-        //     s2:                                            wait U(J) | chain(J) | rec C(J)
-        // A lone matrix' late long updates have few tiles with very long K loops and leave the chip underfilled: the mode is
-        // chosen per HANDLE (n_pad >= 14336 and a lock-step width of at least eight, PotrfBatch::left), never by the number of
-        // matrices in a launch, so a candidate's bits do not depend on its companions.
-        const bool la = s2 != nullptr;
-        hipStream_t sc = la ? s2 : s;  // the chain's stream
-        rc = inner_factor(s, 0, gwidth(0), s3, nullptr);
-        if (rc) return rc;
-        rc = inverse_group(s, 0, gwidth(0));
-        if (rc) return rc;
-        int gprev = 0;  // start of the previous group
-        for (int g0 = gwidth(0); g0 < n_pad; g0 += GW) {
-            const int gw = gwidth(g0);
-            if (gprev > 0) {  // U_long: columns [0, gprev), all final (C(J-2) was waited for before U_short(J-1))
-                const bool timed = trace && trace->ready && trace->used < GemmTrace::kMax;
-                if (timed) EGX_HIP_CHECK(hipEventRecord(trace->e0[trace->used], s));
-                rc = update(s, g0, g0, m_tot - g0, gw, 0, gprev, 1, nullptr, 1);
-                if (rc) return rc;
-                if (timed) {
-                    EGX_HIP_CHECK(hipEventRecord(trace->e1[trace->used], s));
-                    const double nr = (double)(n_pad - g0);
-                    trace->flops[trace->used] = (double)nz * 2.0 * gprev * (nr * gw - 0.5 * gw * (gw - 1.0));
-                    trace->used++;
-                }
-            }
-            if (la && gprev > 0) EGX_HIP_CHECK(hipStreamWaitEvent(s, lk->ev_panel, 0));  // C(J-1): the previous group is final
-            rc = update(s, g0, g0, m_tot - g0, gw, gprev, g0 - gprev, 1, nullptr, 2);     // U_short
+        case PotrfKind::UPDATE: {  // C[r0.., c0..c0+cols) -= P[r0.., k0..k0+K) P[c0..c0+cols, k0..k0+K)^T for the rows from r0
+            const bool timed = p.timed && trace->used < GemmTrace::kMax;
+            if (timed) EGX_HIP_CHECK(hipEventRecord(trace->e0[trace->used], st));
+            bool big = false;
+            rc = launch_gemm_nt_sub(st, M + (int64_t)p.r0 * ld + p.c0, ld, M + (int64_t)p.r0 * ld + p.k0, ld, M + (int64_t)p.c0 * ld + p.k0,
+                                    ld, p.rows, p.cols, p.K, p.lower, 0, &big, info, &gb, p.tag);
             if (rc) return rc;
-            if (la) {
-                EGX_HIP_CHECK(hipEventRecord(lk->ev_lu, s));
-                EGX_HIP_CHECK(hipStreamWaitEvent(sc, lk->ev_lu, 0));
-            }
-            rc = inner_factor(sc, g0, gw, la ? s3 : nullptr, nullptr);
-            if (rc) return rc;
-            if (la) EGX_HIP_CHECK(hipEventRecord(lk->ev_panel, sc));
-            rc = inverse_group(sc, g0, gw);
-            if (rc) return rc;
-            gprev = g0;
-        }
-        if (la && gprev > 0) EGX_HIP_CHECK(hipStreamWaitEvent(s, lk->ev_panel, 0));
-        if (inv) {
-            EGX_HIP_CHECK(hipEventRecord(inv->ev_done, inv->sw));
-            EGX_HIP_CHECK(hipStreamWaitEvent(s, inv->ev_done, 0));
-        }
-        hipLaunchKernelGGL(k_diag_tile_inverses, dim3(n_pad / 64, 1, nz), dim3(256), 0, s, (const double *)M, ld, dinv,
-                           dinv + (int64_t)(n_pad / 64) * 4096, pb.sM, pb.sD);
-        EGX_HIP_CHECK(hipGetLastError());
-        return EGX_SUCCESS;
-    }
-    rc = inner_factor(s, 0, gwidth(0), s3, nullptr);
-    if (rc) return rc;
-    rc = inverse_group(s, 0, gwidth(0));
-    if (rc) return rc;
-    for (int g0 = 0; g0 < n_pad; g0 += GW) {
-        const int gw = gwidth(g0);
-        const int r1 = g0 + gw;  // first row/col of the trailing matrix
-        if (r1 >= n_pad) break;  // (right-hand-side rows below the last block were solved by its panel)
-        const int gw1 = gwidth(r1);
-        if (tail_cols > 0 && n_pad - r1 == tail_cols) {
-            // the flow tail: ONE update of the whole trailing matrix by this group, then the trailing matrix -- every update of the
-            // columns before it applied -- is a factorisation of its own, as one flow launch (pipe_flow.h)
-            rc = update(s, r1, r1, m_tot - r1, n_pad - r1, g0, gw, 1, nullptr);
-            if (rc) return rc;
-            rc = launch_potrf_flow(s, M + (int64_t)r1 * ld + r1, ld, n_pad - r1, m_tot - r1, dinv + (int64_t)(r1 / 64) * 4096, info, pb, r1);
-            if (rc) return rc;
-            for (int t0 = r1; t0 < n_pad; t0 += GW) {
-                rc = inverse_group(s, t0, gwidth(t0));
-                if (rc) return rc;
+            if (timed && (p.timed == POTRF_TIMED || big)) {
+                EGX_HIP_CHECK(hipEventRecord(trace->e1[trace->used], st));
+                trace->flops[trace->used] = (double)nz * p.flops;
+                trace->used++;
             }
             break;
         }
-        // the cross-stream hand-off costs ~2 x 10 us; below ~3k trailing columns RU is shorter than that (and with
-        // several fits in flight the extra hand-offs cost more than they hide: profiles/r02_run23_tail_lookahead_ab.txt)
-        const bool look = (s2 != nullptr) && (n_pad - r1 - gw1 >= g_look_min_cols);
-        const int nb1 = gw1 < kNB ? gw1 : kNB;
-        if (look && s3) {
-            // LUd: the next group's first diagonal block; its chain may start.  LUr: the rest of the next group's columns.
-            rc = update(s, r1, r1, nb1, nb1, g0, gw, 1, nullptr);
+        case PotrfKind::W_UPDATE:
+            rc = launch_gemm_nt_sub(st, inv->W + p.c0, inv->ldw, inv->W + p.k0, inv->ldw, M + (int64_t)p.c0 * ld + p.k0, ld, p.rows, p.cols,
+                                    p.K, 0, 0, nullptr, info, &gbw);
             if (rc) return rc;
-            EGX_HIP_CHECK(hipEventRecord(lk->ev_lu, s));
-            EGX_HIP_CHECK(hipStreamWaitEvent(s2, lk->ev_lu, 0));
-            // LUr writes the next group's columns, RU the columns right of them, both only READ this group's panel: LUr goes
-            // to the (high-priority) side stream, so that RU fills the CUs LUr's last, partly filled round of tiles leaves idle
-            // (+0.8 % on the sweep, +1 % on a lone fit: profiles/r03_run4_lur_side_ab.txt, r03_run8_*).  Round 3 kept a lone
-            // matrix' LUr in front of RU because the driver line's roofline timed those RU launches one by one; since round 4
-            // that leg switches the side stream off for itself (egx_set_tuning "lur_side" = 0).  From n_pad 14336 on only
-            // (n = 16384 lone: 31.5 -> 30.9 ms; n = 8192: one fit 6.24 -> 6.44 ms, twelve in lock-step 260 -> 258 fits/s:
-            // profiles/r04_run11_lur_side_lone_ab.txt).  In the last ~6000 columns the chain is what a factorisation waits for and
-            // its first panel solve waits for LUr: there LUr runs ALONE in front of RU (250 us instead of 520-770 beside it;
-            // n = 16384 lone: 29.85 -> 29.6 ms, profiles/r04_run14_*).  Streams only: the arithmetic is the same either way.
-            hipStream_t slu = (g_lur_side && n_pad >= 14336 && n_pad - r1 - gw1 >= kLurSideMinCols) ? s3 : s;
-            if (slu != s) EGX_HIP_CHECK(hipStreamWaitEvent(slu, lk->ev_lu, 0));
-            rc = update(slu, r1 + nb1, r1, m_tot - r1 - nb1, gw1, g0, gw, 0, nullptr);
-            if (rc) return rc;
-            EGX_HIP_CHECK(hipEventRecord(lk->ev_lur, slu));
-            if (pipe) {
-                rc = pipe_signal(slu, pb, r1 / kNB + 1);
-                if (rc) return rc;
-            }
-            rc = inner_factor(s2, r1, gw1, s3, lk->ev_lur);
-            if (rc) return rc;
-            EGX_HIP_CHECK(hipEventRecord(lk->ev_panel, s2));
-        } else if (!look) {
-            // no look-ahead (small matrices, the last ~3000 columns): nothing runs beside the trailing update, so the next
-            // group's columns and the rest are ONE launch (round 4: one ramp-up and one tail instead of two)
-            const bool timed = trace && trace->ready && trace->used < GemmTrace::kMax;
-            if (timed) EGX_HIP_CHECK(hipEventRecord(trace->e0[trace->used], s));
-            bool big = false;
-            rc = update(s, r1, r1, m_tot - r1, n_pad - r1, g0, gw, 1, &big);
-            if (rc) return rc;
-            if (timed && big) {
-                EGX_HIP_CHECK(hipEventRecord(trace->e1[trace->used], s));
-                const double nc = (double)(n_pad - r1);
-                trace->flops[trace->used] = (double)nz * 2.0 * gw * nc * (nc + 1.0) / 2.0;
-                trace->used++;
-            }
-        } else {
-            // LU: the next group's columns only (look-ahead without a side stream)
-            rc = update(s, r1, r1, m_tot - r1, gw1, g0, gw, 1, nullptr);
-            if (rc) return rc;
-            EGX_HIP_CHECK(hipEventRecord(lk->ev_lu, s));
-            EGX_HIP_CHECK(hipStreamWaitEvent(s2, lk->ev_lu, 0));
-            rc = inner_factor(s2, r1, gw1, nullptr, nullptr);
-            if (rc) return rc;
-            EGX_HIP_CHECK(hipEventRecord(lk->ev_panel, s2));
+            break;
+        case PotrfKind::W_LEFT: {  // the stream kernel with per-tile K ranges and zero-initialised accumulators
+            const int nbx = p.c0 / 128, nby = p.cols / 256, nt = nbx * nby;
+            hipLaunchKernelGGL((k_gemm_stream<false, true>), dim3((unsigned)nt * nz, 1, 1), dim3(512), ST_LDS_BYTES, st, inv->W + p.c0,
+                               inv->ldw, (const double *)inv->W, inv->ldw, (const double *)(M + (int64_t)p.c0 * ld), ld, p.c0, nbx,
+                               nby, nt, (const int *)info, gbw);
+            EGX_HIP_CHECK(hipGetLastError());
+            break;
         }
-        // RU: the rest of the trailing matrix
-        const int r2 = r1 + gw1;
-        if (r2 < n_pad && look) {
-            const bool timed = trace && trace->ready && trace->used < GemmTrace::kMax;
-            if (timed) EGX_HIP_CHECK(hipEventRecord(trace->e0[trace->used], s));
-            bool big = false;
-            rc = update(s, r2, r2, m_tot - r2, n_pad - r2, g0, gw, 1, &big);
+        case PotrfKind::PIPE:
+            rc = launch_potrf_pipe(st, M, ld, n_pad, m_tot, dinv, info, pb, p.c0, p.cols, p.panel, p.high);
             if (rc) return rc;
-            if (timed && big) {
-                EGX_HIP_CHECK(hipEventRecord(trace->e1[trace->used], s));
-                const double nc = (double)(n_pad - r2);
-                trace->flops[trace->used] = (double)nz * 2.0 * gw * nc * (nc + 1.0) / 2.0;
-                trace->used++;
-            }
-        }
-        if (look) {
-            EGX_HIP_CHECK(hipStreamWaitEvent(s, lk->ev_panel, 0));
-        } else {
-            rc = inner_factor(s, r1, gw1, nullptr, nullptr);
+            break;
+        case PotrfKind::FLOW:
+            rc = launch_potrf_flow(st, M + (int64_t)p.r0 * ld + p.r0, ld, n_pad - p.r0, m_tot - p.r0, dinv + (int64_t)(p.r0 / 64) * 4096,
+                                   info, pb, p.r0);
             if (rc) return rc;
+            break;
+        case PotrfKind::SIGNAL:
+            rc = pipe_signal(st, pb, p.panel);
+            if (rc) return rc;
+            break;
+        case PotrfKind::TILE_INVERSES:
+            hipLaunchKernelGGL(k_diag_tile_inverses, dim3(n_pad / 64, 1, nz), dim3(256), 0, st, (const double *)M, ld, dinv,
+                               dinv + (int64_t)(n_pad / 64) * 4096, pb.sM, pb.sD);
+            EGX_HIP_CHECK(hipGetLastError());
+            break;
+        case PotrfKind::RECORD: EGX_HIP_CHECK(hipEventRecord(events[(int)p.ev], st)); break;
+        case PotrfKind::WAIT: EGX_HIP_CHECK(hipStreamWaitEvent(st, events[(int)p.ev], 0)); break;
         }
-        rc = inverse_group(s, r1, gw1);  // the group that has just become final
-        if (rc) return rc;
     }
-    if (inv) {  // W is complete; its panel solves read the 16 x 16 inverses the launch below overwrites
-        EGX_HIP_CHECK(hipEventRecord(inv->ev_done, inv->sw));
-        EGX_HIP_CHECK(hipStreamWaitEvent(s, inv->ev_done, 0));
-    }
-    // every stream has been joined into `s`: the 64x64 tile inverses of the complete factor(s), one launch
-    hipLaunchKernelGGL(k_diag_tile_inverses, dim3(n_pad / 64, 1, nz), dim3(256), 0, s, (const double *)M, ld, dinv,
-                       dinv + (int64_t)(n_pad / 64) * 4096, pb.sM, pb.sD);
-    EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
 }
 

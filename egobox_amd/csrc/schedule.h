@@ -2,6 +2,7 @@
 // tests/c_host/schedule_test.cpp walks the table).  Decided once per handle shape -- egx_gp_create, egx_gp_set_lockstep --
 // and stored in the handle (egx_gp::sched), never per launch, never by the number of matrices in a launch, and not by
 // egx_gp_shrink: all evaluations of a handle agree bit for bit (egx_gp_get_schedule shows the decision).
+// (WHICH form is decided here; the ORDER of the launches and event calls of each form is potrf_plan.h, host-testable as well.)
 //
 //   n_pad (padded size)   lock-step width   workspaces x panels     left   w_left   pipe   whole   panels per group
 //   <= 7168               any               <= 32                   0      0        1      1       (one launch)
