@@ -164,6 +164,10 @@ SIGNATURES = [
     ("egx_gp_likelihood_multi", C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, c_double_p, C.c_int64, c_double_p, C.POINTER(C.c_int32)]),
     ("egx_gp_fit_multi", C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64,
                                      c_int64_p]),
+    ("egx_gp_likelihood_grad_multi", C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p,
+                                                 C.POINTER(C.c_int32)]),
+    ("egx_gp_fit_lbfgs_multi", C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int64,
+                                           C.c_int64, c_int64_p]),
     ("egx_gp_fit", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64,
                                c_int64_p]),
     ("egx_gp_fit_partial", C.c_int32, [C.c_void_p, c_double_p, c_int64_p, C.c_int64, c_double_p, C.c_int64, c_double_p,

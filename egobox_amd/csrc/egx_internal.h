@@ -174,6 +174,8 @@ int launch_zero_upper(hipStream_t s, double *M, int64_t ld, int n);
 // Deterministic (fixed reduction order): a candidate's result does not depend on the batch it runs in.
 struct GradBatch {
     int count = 1;
+    const double *xT[kLockstepMax];     // d x ldx: the training inputs of the entry's OWNER (raw forms; the candidates of one
+                                        // handle all name the same array, the members of a group each their own)
     const double *xs[kLockstepMax];     // d x ldx: the inputs times the candidate's coefficients (prescaled form only)
     const double *coef[kLockstepMax];   // d x hcols
     const double *gamma[kLockstepMax];  // n_pad
@@ -183,10 +185,20 @@ struct GradBatch {
     double *out[kLockstepMax];          // nout
 };
 int grad_partial_doubles(int nout);
-int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, int d, int hcols, const double *wabs,
-                      int nout, int64_t ld, const GradBatch &batch, int prescaled = 0);
+int launch_grad_accum(hipStream_t s, int corr, int64_t ldx, int n, int d, int hcols, const double *wabs, int nout, int64_t ld,
+                      const GradBatch &batch, int prescaled = 0);
+// xs[j][k][i] = coef[j][k] * xT[j][k][i] for the entries j < count of b (their xT, coef and xs alone are read): launch_scale_rows
+// for every entry in ONE launch, the same product per element
+int launch_scale_rows_batch(hipStream_t s, const EvalBatchPtrs &b, int count, int64_t ldx, int d);
 // z (n) <- W y, W upper triangular row-major
 int launch_uptri_gemv(hipStream_t s, const double *W, int64_t ld, int n, const double *y, double *z);
+// ... for `count` matrices W + j sW, each with its own y[j] and z[j], in ONE launch (grid.y = matrix): row i of matrix j is summed
+// by one wave in the order launch_uptri_gemv sums it, so z[j] is bit for bit the lone launch's
+struct GemvBatchPtrs {
+    const double *y[kLockstepMax];
+    double *z[kLockstepMax];
+};
+int launch_uptri_gemv_batch(hipStream_t s, const double *W, int64_t sW, int64_t ld, int n, const GemvBatchPtrs &b, int count);
 // the same for `rows` right-hand sides, rows of Y (ldr apart): Z[a] = W Y[a], or base[a] + sc * W Y[a] with base != nullptr
 // (base may be Z)
 int launch_uptri_gemv_rows(hipStream_t s, const double *W, int64_t ld, int n, const double *Y, const double *base, double sc,

@@ -1,9 +1,11 @@
 // Optimiser drivers above the dense likelihood (GpValidParams::fit with ThetaTuning::Full / Partial, algorithm.rs:873-960,
 // optimization.rs:26-169): multistart COBYLA on one model (egx_gp_fit, egx_gp_fit_partial, egx_sweep_fit) and on the models of a
-// group (egx_gp_fit_multi), the theta-gradient of the likelihood and a projected L-BFGS on it.  Every
+// group (egx_gp_fit_multi), the theta-gradient of the likelihood and a projected L-BFGS on it -- both of
+// one handle's candidates and of a group's members (egx_gp_likelihood_grad_multi, egx_gp_fit_lbfgs_multi).  Every
 // driver is LOCK-STEP: multistart::run over one machine per start, a round's points in one evaluation call.  The box, the
 // budget, the machines, the reduction and the winner are fit_starts.h's; this file holds only what touches a handle.
 #include "gp_handle.h"
+#include "grad_runs.h"
 
 using namespace egx;
 
@@ -122,19 +124,11 @@ namespace egx {
 // buffers of `slab_W`).  Every stage is deterministic and its kernel choice depends on one matrix' size only, so a
 // candidate's (likelihood, gradient) are the same bits alone and in any batch.
 // ---------------------------------------------------------------------------------------------
-static int ensure_grad_scratch(egx_gp *gp, int ws_lo, int nuse) {
-    const size_t sq = (size_t)gp->n_pad * gp->n_pad;
-    if (gp->slab_W_count < nuse) {
-        gp->slab_W_count = 0;
-        EGX_RC(gp->slab_W.alloc(sq * (size_t)nuse));
-        gp->slab_W_count = nuse;
-    }
-    for (int i = ws_lo; i < ws_lo + nuse; i++) {
-        Workspace &w = gp->ws[i];
-        EGX_RC(w.d_gpart.alloc((size_t)grad_partial_doubles(gp->d)));
-        EGX_RC(w.d_gout.alloc((size_t)(gp->d + 64)));
-        EGX_RC(w.h_gout.alloc((size_t)(gp->d + 64)));
-    }
+// the gradient scratch of one evaluation's workspace, and |w_star| of its owner on the device (KPLS + Matern)
+static int ensure_grad_ws(egx_gp *gp, Workspace &w) {
+    EGX_RC(w.d_gpart.alloc((size_t)grad_partial_doubles(gp->d)));
+    EGX_RC(w.d_gout.alloc((size_t)(gp->d + 64)));
+    EGX_RC(w.h_gout.alloc((size_t)(gp->d + 64)));
     if (gp->has_w && !gp->d_wabs) {
         std::vector<double> wabs(gp->w_star.size());
         for (size_t e = 0; e < wabs.size(); e++) wabs[e] = std::fabs(gp->w_star[e]);
@@ -143,30 +137,38 @@ static int ensure_grad_scratch(egx_gp *gp, int ws_lo, int nuse) {
     }
     return EGX_SUCCESS;
 }
+// ... of the workspaces ws_lo .. ws_lo + nuse - 1 of ONE handle, with as many C^-T buffers in its slab_W
+static int ensure_grad_scratch(egx_gp *gp, int ws_lo, int nuse) {
+    const size_t sq = (size_t)gp->n_pad * gp->n_pad;
+    if (gp->slab_W_count < nuse) {
+        gp->slab_W_count = 0;
+        EGX_RC(gp->slab_W.alloc(sq * (size_t)nuse));
+        gp->slab_W_count = nuse;
+    }
+    for (int i = ws_lo; i < ws_lo + nuse; i++) EGX_RC(ensure_grad_ws(gp, gp->ws[i]));
+    return EGX_SUCCESS;
+}
 
-// the gradient stages of `count` consecutive workspaces from w0 (their factors in place, rho in d_rhs) on stream st;
-// C^-T buffers slot0 .. of slab_W
-// pre != 0: every candidate of the run has hcols == 1 and positive coefficients -- the trace kernel takes the prescaled form
-static int enqueue_grad_run(egx_gp *gp, hipStream_t st, int w0, int count, int slot0, const double *inv_s2, int hcols, int pre) {
+// The gradient stages of `count` evaluations in LOCK-STEP on stream st: evaluation j is of the training set of owners[j] on the
+// workspace wss[j] (its factor in place, rho in d_rhs), its C^-T -- it rode along the factorisation -- in W0 + j n_pad^2.  The
+// workspaces are consecutive slots of ONE slab, like enqueue_eval_core's (gp_host.hip): the candidates of one handle
+// (owners[j] = gp, wss[j] = &gp->ws[w0 + j], W0 in gp->slab_W), or the members of a run of a group (owners[j] = gps[j], wss[j] =
+// &gps[j]->ws[0], W0 in GroupSlabs::W).  Every stage has the entry as a grid coordinate and reads nothing of its companions.
+// pre != 0: every entry of the run has hcols == 1 and positive coefficients -- the trace kernel takes the prescaled form
+static int enqueue_grad_run(egx_gp *const *owners, Workspace *const *wss, int count, hipStream_t st, double *W0, const double *inv_s2,
+                            int hcols, int pre) {
+    const egx_gp *gp = owners[0];  // (the shape is every owner's)
     const int n = gp->n, n_pad = gp->n_pad;
     const int64_t sq = (int64_t)n_pad * n_pad;
-    Workspace &lead = gp->ws[w0];
-    double *W0 = gp->slab_W + (int64_t)slot0 * sq;  // C^-T of these candidates: rode along their factorisation
-    for (int j = 0; j < count; j++) {
-        Workspace &w = gp->ws[w0 + j];
-        EGX_RC(launch_uptri_gemv(st, W0 + (int64_t)j * sq, n_pad, n, w.d_rhs, w.d_vec));
-    }
-    GemmBatch gbm;
-    gbm.count = count;
-    gbm.sC = gp->stride_M;
-    gbm.sA = gbm.sB = sq;
-    EGX_RC(launch_syrk_uptri_neg(st, lead.M, gp->ld, W0, n_pad, n_pad, &gbm));
-    const int nout = (hcols == 1) ? gp->d : gp->h;
+    GemvBatchPtrs gv;
+    EvalBatchPtrs sc;  // (xT, coef, xs alone are read: launch_scale_rows_batch)
     GradBatch gb;
     gb.count = count;
     for (int j = 0; j < count; j++) {
-        Workspace &w = gp->ws[w0 + j];
-        if (pre) EGX_RC(launch_scale_rows(st, gp->d_xT, n_pad, gp->d, w.d_coef, w.d_xs));  // (K1 may have taken its LDS-only form)
+        Workspace &w = *wss[j];
+        gv.y[j] = w.d_rhs, gv.z[j] = w.d_vec;
+        sc.xT[j] = owners[j]->d_xT, sc.coef[j] = w.d_coef, sc.xs[j] = w.d_xs;
+        gb.xT[j] = owners[j]->d_xT;
         gb.xs[j] = w.d_xs;
         gb.coef[j] = w.d_coef;
         gb.gamma[j] = w.d_vec;
@@ -176,17 +178,41 @@ static int enqueue_grad_run(egx_gp *gp, hipStream_t st, int w0, int count, int s
         gb.out[j] = w.d_gout;
     }
     for (int j = count; j < kLockstepMax; j++) {
-        gb.xs[j] = gb.coef[j] = gb.gamma[j] = gb.rneg[j] = nullptr;
+        gv.y[j] = nullptr, gv.z[j] = nullptr;
+        sc.xT[j] = sc.coef[j] = nullptr, sc.xs[j] = nullptr;
+        gb.xT[j] = gb.xs[j] = gb.coef[j] = gb.gamma[j] = gb.rneg[j] = nullptr;
         gb.inv_s2[j] = 0.0;
         gb.part[j] = gb.out[j] = nullptr;
     }
-    EGX_RC(launch_grad_accum(st, gp->corr, gp->d_xT, n_pad, n, gp->d, hcols, hcols > 1 ? gp->d_wabs : nullptr, nout, gp->ld, gb,
-                             pre));
+    EGX_RC(launch_uptri_gemv_batch(st, W0, sq, n_pad, n, gv, count));  // gamma = W rho
+    GemmBatch gbm;
+    gbm.count = count;
+    gbm.sC = gp->stride_M;
+    gbm.sA = gbm.sB = sq;
+    EGX_RC(launch_syrk_uptri_neg(st, wss[0]->M, gp->ld, W0, n_pad, n_pad, &gbm));
+    const int nout = (hcols == 1) ? gp->d : gp->h;
+    if (pre) EGX_RC(launch_scale_rows_batch(st, sc, count, n_pad, gp->d));  // (K1 may have taken its LDS-only form)
+    EGX_RC(launch_grad_accum(st, gp->corr, n_pad, n, gp->d, hcols, hcols > 1 ? gp->d_wabs.p : nullptr, nout, gp->ld, gb, pre));
     for (int j = 0; j < count; j++) {
-        Workspace &w = gp->ws[w0 + j];
+        Workspace &w = *wss[j];
         EGX_HIP_CHECK(hipMemcpyAsync(w.h_gout, w.d_gout, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
     }
     return EGX_SUCCESS;
+}
+
+// What the host half of entry j's likelihood (finish_eval with keep = 2) means for its gradient: the result row, whether it has
+// a gradient, 1 / sigma2, and which form of the trace kernel ITS OWN coefficients allow
+static bool grad_entry(const EvalResult &res, int hcols, const std::vector<double> &coef, double &lkh, int32_t &status, double &inv_s2,
+                       char &pre) {
+    lkh = res.lkh;
+    status = res.status;
+    inv_s2 = 0.0, pre = 0;
+    if (res.status != EGX_STATUS_OK || !(res.sigma2n > 0.0) || !std::isfinite(res.lkh)) return false;
+    inv_s2 = 1.0 / res.sigma2n;
+    // the prescaled form divides by the coefficient once per output: an entry's OWN coefficients decide (never its
+    // companions': the kernel choice must not depend on the batch)
+    pre = gradruns::prescaled(hcols, coef.data(), (int)coef.size()) ? 1 : 0;
+    return true;
 }
 
 // dL/dtheta (h) from the kernel's sums over the coefficients (nout): the chain rule of make_coef
@@ -272,38 +298,122 @@ int likelihood_grad_batch_core(egx_gp *gp, const double *thetas, int64_t k, int6
         std::vector<double> inv_s2(cnt, 0.0);
         sl.ok.assign(cnt, 0);
         sl.pre.assign(cnt, 0);
+        std::vector<egx_gp *> owners((size_t)cnt, gp);
+        std::vector<Workspace *> wss((size_t)cnt);
         for (int j = 0; j < cnt; j++) {
             Workspace &w = gp->ws[w0 + j];
+            wss[(size_t)j] = &w;
             EvalResult res;
             EGX_RC(finish_eval(gp, w, res, 2));
             const int64_t c = sl.cand[j];
-            lkh[c] = res.lkh;
-            status[c] = res.status;
-            if (res.status != EGX_STATUS_OK || !(res.sigma2n > 0.0) || !std::isfinite(res.lkh)) continue;
+            if (!grad_entry(res, sl.hcols, sl.coefs[j], lkh[c], status[c], inv_s2[j], sl.pre[j])) continue;
             sl.ok[j] = 1;
-            inv_s2[j] = 1.0 / res.sigma2n;
-            // the prescaled form divides by the coefficient once per output: a candidate's OWN coefficients decide
-            // (never its companions': the kernel choice must not depend on the batch)
-            sl.pre[j] = sl.hcols == 1 ? 1 : 0;
-            for (double cj : sl.coefs[j])
-                if (!(cj > 0.0) || !std::isfinite(cj)) sl.pre[j] = 0;
             EGX_RC(upload_rho(gp, w, res, st));
         }
-        // maximal runs of consecutive candidates with a gradient (and the same form of the trace kernel): each run is one
-        // lock-step launch sequence
-        for (int j = 0; j < cnt;) {
-            if (!sl.ok[j]) {
-                j++;
-                continue;
-            }
-            int e = j;
-            while (e < cnt && sl.ok[e] && sl.pre[e] == sl.pre[j]) e++;
-            EGX_RC(enqueue_grad_run(gp, st, w0 + j, e - j, i * g.width + j, inv_s2.data() + j, sl.hcols, sl.pre[j]));
-            j = e;
-        }
+        // each run (grad_runs.h) is one lock-step launch sequence
+        const int64_t sq = (int64_t)gp->n_pad * gp->n_pad;
+        for (const gradruns::Run &r : gradruns::split(sl.ok.data(), sl.pre.data(), cnt))
+            EGX_RC(enqueue_grad_run(owners.data() + r.first, wss.data() + r.first, r.count, st,
+                                    gp->slab_W + (int64_t)(i * g.width + r.first) * sq, inv_s2.data() + r.first, sl.hcols, r.pre));
         return EGX_SUCCESS;
     };
     return run_slots(gp, g, src, k, admit, enqueue, advance);
+}
+
+// Likelihood + gradient of `len` members of ONE group in consecutive slots (1 <= len <= run_len_multi's cap), none with a NaN
+// theta, in LOCK-STEP: member j at row j of thetas, on its own workspace 0, its C^-T in its slot of the group's slab
+// (GroupSlabs::W).  Caller holds every member's lock and has set the device.  The sequence is likelihood_grad_batch_core's for
+// one slot -- the evaluation with the rider, the host halves, the gradient stages, the chain rule -- on the same kernels, so a
+// member's row is bit for bit its own egx_gp_likelihood_grad.  A member whose host half FAILS (a HIP error, not a status) keeps
+// its zero gradient and gives first_rc; the others finish.
+static int grad_run_members(egx_gp *const *gps, int len, const double *thetas, int64_t theta_len, double *lkh, double *grad,
+                            int32_t *status, int &first_rc) {
+    egx_gp *lead = gps[0];
+    const int h = lead->h;
+    const int64_t sq = (int64_t)lead->n_pad * lead->n_pad;
+    std::vector<std::vector<double>> coefs((size_t)len), thfull((size_t)len);
+    int hcols = 1;
+    for (int j = 0; j < len; j++) EGX_RC(make_coef(gps[j], thetas + (size_t)j * theta_len, theta_len, coefs[(size_t)j], hcols, &thfull[(size_t)j]));
+    {   // the group's C^-T slab, as ensure_winv allocates it (members of a group may be called from different threads)
+        std::lock_guard<std::mutex> lk(lead->group->winv_mu);
+        EGX_RC(lead->group->W.alloc((size_t)sq * lead->group->k));
+    }
+    std::vector<Workspace *> wss((size_t)len);
+    for (int j = 0; j < len; j++) {
+        egx_gp *gp = gps[j];
+        wss[(size_t)j] = &gp->ws[0];
+        EGX_RC(ensure_grad_ws(gp, gp->ws[0]));
+        // the rider overwrites this member's slot of the slab, which also caches C^-T of its FITTED factor for the x-gradients
+        // (ensure_winv): the member is un-fitted, and the slot no longer is that of any fit of it
+        gp->fitted = false;
+        gp->winv_epoch = ~(uint64_t)0;
+    }
+    double *W0 = lead->group->W.p + (int64_t)lead->group_slot * sq;
+    RunGuard guard{gps, len};
+    EGX_RC(enqueue_eval_members(gps, len, coefs.data(), hcols, W0));
+    const hipStream_t st = lead->ws[0].eval_stream;
+    std::vector<HostHalf> hh((size_t)len);
+    host_halves(gps, len, 2, hh.data());
+    std::vector<double> inv_s2((size_t)len, 0.0);
+    std::vector<char> ok((size_t)len, 0), pre((size_t)len, 0);
+    for (int j = 0; j < len; j++) {
+        if (hh[j].rc != EGX_SUCCESS) {
+            lkh[j] = -std::numeric_limits<double>::infinity(), status[j] = EGX_STATUS_OK;  // (the call returns the error)
+            set_error(hh[j].err);
+            if (first_rc == EGX_SUCCESS) first_rc = hh[j].rc;
+            continue;
+        }
+        if (!grad_entry(hh[j].res, hcols, coefs[(size_t)j], lkh[j], status[j], inv_s2[(size_t)j], pre[(size_t)j])) continue;
+        ok[(size_t)j] = 1;
+        EGX_RC(upload_rho(gps[j], *wss[(size_t)j], hh[j].res, st));
+    }
+    for (const gradruns::Run &r : gradruns::split(ok.data(), pre.data(), len))
+        EGX_RC(enqueue_grad_run(gps + r.first, wss.data() + r.first, r.count, st, W0 + (int64_t)r.first * sq, inv_s2.data() + r.first,
+                                hcols, r.pre));
+    EGX_HIP_CHECK(hipStreamSynchronize(st));
+    guard.synced = true;
+    for (int j = 0; j < len; j++)
+        if (ok[(size_t)j]) grad_chain_rule(gps[j], wss[(size_t)j]->h_gout, hcols, coefs[(size_t)j], thfull[(size_t)j], grad + (size_t)j * h);
+    return EGX_SUCCESS;
+}
+
+// egx_gp_likelihood_grad_multi under the members' locks: row j of thetas for gps[j]
+int likelihood_grad_multi_locked(egx_gp *const *gps, int32_t k, const double *thetas, int64_t theta_len, double *lkh, double *grad,
+                                 int32_t *status) {
+    const int h = gps[0]->h;
+    int first_rc = EGX_SUCCESS;
+    for (int i = 0; i < k;) {
+        const int len = run_len_multi(gps, k, i);
+        EGX_RC(set_device(gps[i]));
+        if (!gps[i]->group) {  // a lone handle: the lone core on its workspace 0
+            gps[i]->fitted = false;
+            EGX_RC(likelihood_grad_batch_core(gps[i], thetas + (size_t)i * theta_len, 1, theta_len, lkh + i, grad + (size_t)i * h, status + i));
+            i++;
+            continue;
+        }
+        // a run of members: a NaN theta is answered at once (algorithm.rs:885-891) and cuts the run -- the lock-step launches
+        // take CONSECUTIVE slots
+        for (int j = 0; j < len;) {
+            egx_gp *gp = gps[i + j];
+            const double *th = thetas + (size_t)(i + j) * theta_len;
+            for (int l = 0; l < h; l++) grad[(size_t)(i + j) * h + l] = 0.0;
+            if (has_nan(th, theta_len)) {
+                gp->fitted = false;
+                lkh[i + j] = -std::numeric_limits<double>::infinity(), status[i + j] = EGX_STATUS_NAN_THETA;
+                j++;
+                continue;
+            }
+            int e = j + 1;
+            while (e < len && !has_nan(thetas + (size_t)(i + e) * theta_len, theta_len)) {
+                for (int l = 0; l < h; l++) grad[(size_t)(i + e) * h + l] = 0.0;
+                e++;
+            }
+            EGX_RC(grad_run_members(gps + i + j, e - j, th, theta_len, lkh + i + j, grad + (size_t)(i + j) * h, status + i + j, first_rc));
+            j = e;
+        }
+        i += len;
+    }
+    return first_rc;
 }
 }  // namespace egx
 
@@ -443,6 +553,99 @@ int32_t egx_gp_fit_multi(egx_gp *const *gps, int32_t k, const double *theta0s, i
         for (int64_t st = 0; st < n_starts; st++) results.push_back(fit::cobyla_result(mach[(size_t)(st * k + m)]));
         const double *theta0 = theta0s + (size_t)m * n_starts * h;
         const std::vector<double> th = fit::winner_theta(theta0, h, active, fit::best_start(results, n_evals_out ? n_evals_out + m : nullptr), theta0);
+        best.insert(best.end(), th.begin(), th.end());
+    }
+    return eval_multi_locked(gps, k, best.data(), h, true, nullptr, nullptr);
+}
+
+// the locks of a multi-model call whose models must agree on h
+static int32_t lock_same_h(const char *who, egx_gp *const *gps, int32_t k, std::vector<std::unique_lock<std::shared_mutex>> &locks) {
+    EGX_RC(lock_multi(gps, k, locks));
+    for (int32_t m = 1; m < k; m++)
+        if (gps[m]->h != gps[0]->h) {
+            set_error(std::string(who) + ": the models must have the same number of hyperparameters");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    return EGX_SUCCESS;
+}
+
+int32_t egx_gp_likelihood_grad_multi(egx_gp *const *gps, int32_t k, const double *thetas, int64_t theta_len, double *lkh,
+                                     double *grads, int32_t *status) {
+    if (!gps || k < 1 || !thetas || !lkh || !grads || !status) {
+        set_error("NULL argument / no model");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::vector<std::unique_lock<std::shared_mutex>> locks;
+    EGX_RC(lock_same_h("egx_gp_likelihood_grad_multi", gps, k, locks));
+    if (theta_len != 1 && theta_len != gps[0]->h) {
+        set_error("theta should be either 1-dim or dim of xtrain (w_star.ncols()), got " + std::to_string(theta_len));
+        return EGX_ERR_INVALID_VALUE;
+    }
+    return likelihood_grad_multi_locked(gps, k, thetas, theta_len, lkh, grads, status);
+}
+
+// egx_gp_fit_lbfgs across MODELS: the k x n_starts LbfgsStart machines START-MAJOR, model-minor as egx_gp_fit_multi lays out its
+// COBYLA machines; per round and start index, the trial points of all models whose machine still asks are ONE
+// egx_gp_likelihood_grad_multi evaluation.  A machine only ever sees the values of its own model, and those are the bits of the
+// model's lone call, so every member walks the trajectory it walks under egx_gp_fit_lbfgs on a one-workspace handle.
+int32_t egx_gp_fit_lbfgs_multi(egx_gp *const *gps, int32_t k, const double *theta0s, int64_t n_starts, const double *lo, const double *hi,
+                               int64_t bounds_len, int64_t max_iter, int64_t *n_evals_out) {
+    if (!gps || k < 1 || !theta0s || !lo || !hi || n_starts < 1) {
+        set_error("NULL argument / no start point");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::vector<std::unique_lock<std::shared_mutex>> locks;
+    EGX_RC(lock_same_h("egx_gp_fit_lbfgs_multi", gps, k, locks));
+    const int h = gps[0]->h;
+    fit::Log10Box box;
+    EGX_RC(fit_box(lo, hi, bounds_len, h, theta0s, (int64_t)k * n_starts * h, fit::Dense, box));
+    if (max_iter < 1) max_iter = 50;
+    std::vector<int64_t> rows;
+    for (int64_t st = 0; st < n_starts; st++)
+        for (int32_t m = 0; m < k; m++) rows.push_back((int64_t)m * n_starts + st);
+    std::vector<LbfgsStart> mach = fit::lbfgs_machines(theta0s, h, rows, box, max_iter);
+    const double ln10 = std::log(10.0), inf = std::numeric_limits<double>::infinity();
+    const std::vector<int> active = fit::all_active(h);
+    std::vector<int64_t> evals((size_t)k, 0);
+    std::vector<egx_gp *> sub;
+    std::vector<double> thetas, lk, gr, gx(h);
+    std::vector<int32_t> stv;
+    int rc;
+    multistart::run(
+        mach,
+        [&](const multistart::Round &r) {
+            fit::round_thetas(r, theta0s, h, active, thetas);
+            lk.assign(r.size(), 0.0);
+            gr.assign(r.size() * (size_t)h, 0.0);
+            stv.assign(r.size(), 0);
+            return fit::for_each_start(r, k, [&](int64_t, size_t q0, size_t count) {
+                sub.clear();
+                for (size_t q = q0; q < q0 + count; q++) {
+                    sub.push_back(gps[r.who[q] % (size_t)k]);
+                    evals[r.who[q] % (size_t)k]++;
+                }
+                return likelihood_grad_multi_locked(sub.data(), (int32_t)count, thetas.data() + q0 * (size_t)h, h, lk.data() + q0,
+                                                    gr.data() + q0 * (size_t)h, stv.data() + q0);
+            });
+        },
+        [&](const multistart::Round &, size_t q, LbfgsStart &m) {  // f(x) = -L(10^x), g = -dL/dx = -theta ln10 dL/dtheta
+            const bool ok = stv[q] == EGX_STATUS_OK && std::isfinite(lk[q]);
+            for (int i = 0; i < h; i++) gx[i] = ok ? -thetas[q * h + i] * ln10 * gr[q * h + i] : 0.0;
+            m.tell(ok ? -lk[q] : inf, gx);
+        },
+        rc);
+    EGX_RC(rc);
+    // the reduction over every model's starts, then ONE lock-step finalize
+    std::vector<double> best;
+    for (int32_t m = 0; m < k; m++) {
+        std::vector<StartResult> results;
+        for (int64_t st = 0; st < n_starts; st++) {
+            const LbfgsStart &ms = mach[(size_t)(st * k + m)];
+            results.push_back(StartResult{ms.f, ms.x, 0});
+        }
+        if (n_evals_out) n_evals_out[m] = evals[(size_t)m];
+        const double *theta0 = theta0s + (size_t)m * n_starts * h;
+        const std::vector<double> th = fit::winner_theta(theta0, h, active, fit::best_start(results), theta0);
         best.insert(best.end(), th.begin(), th.end());
     }
     return eval_multi_locked(gps, k, best.data(), h, true, nullptr, nullptr);

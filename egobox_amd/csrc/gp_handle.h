@@ -296,7 +296,24 @@ int enqueue_eval(egx_gp *gp, Workspace &w, const std::vector<double> &coef, int 
 // W0 != nullptr: the `count` buffers W0 + j n_pad^2 receive C^-T of the candidates, riding along the factorisation
 int enqueue_eval_group(egx_gp *gp, int w0, int count, const std::vector<double> *coefs, int hcols, double *W0 = nullptr);
 // the same for `count` MODELS of one group (consecutive slots): member j evaluates on its own workspace 0, its own training set
-int enqueue_eval_members(egx_gp *const *gps, int count, const std::vector<double> *coefs, int hcols);
+// W0 != nullptr: member 0's slot of the group's C^-T slab (GroupSlabs::W); member j's rider writes the slot j behind it
+int enqueue_eval_members(egx_gp *const *gps, int count, const std::vector<double> *coefs, int hcols, double *W0 = nullptr);
+// The host halves (finish_eval with `keep`) of a run evaluated by enqueue_eval_members, side by side on host threads where they
+// issue no launches; RunGuard: whatever way such a run is left, nothing stays in flight on the lead's stream and every
+// member's eval_stream is its own again (gp_host.hip)
+struct HostHalf {
+    EvalResult res;
+    int rc = EGX_SUCCESS;
+    std::string err;  // (the error text is per thread)
+    std::chrono::steady_clock::time_point t0, t1;
+};
+void host_halves(egx_gp *const *gps, int len, int keep, HostHalf *hh);
+struct RunGuard {
+    egx_gp *const *gps;
+    int len;
+    bool synced = false;
+    ~RunGuard();
+};
 int finish_eval(egx_gp *gp, Workspace &w, EvalResult &out, int keep);  // 0 scalars, 1 fitted state, 2 rho only
 void record_timings(egx_gp *gp, Workspace &w, double host_ms, double solve_ms);
 bool has_nan(const double *theta, int64_t len);

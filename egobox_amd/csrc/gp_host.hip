@@ -455,10 +455,10 @@ int enqueue_eval_group(egx_gp *gp, int w0, int count, const std::vector<double> 
     for (int j = 0; j < count; j++) wss[(size_t)j] = &gp->ws[(size_t)(w0 + j)];
     return enqueue_eval_core(owners.data(), wss.data(), count, coefs, hcols, W0);
 }
-int enqueue_eval_members(egx_gp *const *gps, int count, const std::vector<double> *coefs, int hcols) {
+int enqueue_eval_members(egx_gp *const *gps, int count, const std::vector<double> *coefs, int hcols, double *W0) {
     std::vector<Workspace *> wss((size_t)count);
     for (int j = 0; j < count; j++) wss[(size_t)j] = &gps[j]->ws[0];
-    return enqueue_eval_core(gps, wss.data(), count, coefs, hcols, nullptr);
+    return enqueue_eval_core(gps, wss.data(), count, coefs, hcols, W0);
 }
 
 // one evaluation on one workspace (its own streams)
@@ -789,13 +789,7 @@ static_assert(kMaxRun <= kLockstepMax, "a run must fit one lock-step launch");
 // The host halves (finish_eval) of a run of `len` models evaluated by enqueue_eval_members.  On the host-GLS route (the
 // log-determinant over the diagonal, GLS: ~0.1 ms per model at n = 8192, no HIP launches) they run side by side on host threads;
 // the device-GLS route (p > 1 trend columns) issues launches: one after the other.
-struct HostHalf {
-    EvalResult res;
-    int rc = EGX_SUCCESS;
-    std::string err;  // (the error text is per thread)
-    std::chrono::steady_clock::time_point t0, t1;
-};
-static void host_halves(egx_gp *const *gps, int len, int keep, HostHalf *hh) {
+void host_halves(egx_gp *const *gps, int len, int keep, HostHalf *hh) {
     auto run = [&](int j) {
         hh[j].t0 = std::chrono::steady_clock::now();
         hh[j].rc = finish_eval(gps[j], gps[j]->ws[0], hh[j].res, keep);
@@ -819,18 +813,13 @@ static void host_halves(egx_gp *const *gps, int len, int keep, HostHalf *hh) {
 // Whatever way a run's evaluation is left, no work stays in flight on the lead's stream that writes into the members' pinned
 // buffers, and no member's eval_stream points at a stream of a handle that may be destroyed first.  (synced: the run ended
 // in a synchronisation of that stream: no second one, 30 us of a fit's host time)
-struct RunGuard {
-    egx_gp *const *gps;
-    int len;
-    bool synced = false;
-    ~RunGuard() {
-        if (!synced) {
-            (void)hipStreamSynchronize(gps[0]->ws[0].stream);
-            (void)hipGetLastError();
-        }
-        for (int j = 0; j < len; j++) gps[j]->ws[0].eval_stream = gps[j]->ws[0].stream;
+RunGuard::~RunGuard() {
+    if (!synced) {
+        (void)hipStreamSynchronize(gps[0]->ws[0].stream);
+        (void)hipGetLastError();
     }
-};
+    for (int j = 0; j < len; j++) gps[j]->ws[0].eval_stream = gps[j]->ws[0].stream;
+}
 
 // the error of a fit whose host half ended in `status`
 static int status_error(int status, const Workspace &w) {

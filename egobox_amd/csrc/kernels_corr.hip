@@ -614,19 +614,33 @@ __global__ void k_sum_partials(const double *__restrict__ P, int nsplit, int n_p
 
 // z[a][i] = (base ? base[a][i] + sc * acc : acc), acc = sum_{k >= i} W[i][k] y[a][k], for the rows a = blockIdx.y of y / base / z
 // (ldr apart): a wave per (row of W, right-hand side).  base may be z itself (an element is read by the lane that writes it).
+// (one row's sum, complete in every lane of its wave: the ONE text both kernels below run)
+__device__ __forceinline__ double uptri_row_dot(const double *__restrict__ W, int64_t ld, int n, const double *y, int i, int lane) {
+    const double *row = W + (int64_t)i * ld;
+    double acc = 0.0;
+    for (int k = (i & ~63) + lane; k < n; k += 64) acc = __builtin_fma((k >= i) ? row[k] : 0.0, y[k], acc);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    return acc;
+}
 __global__ __launch_bounds__(256) void k_uptri_gemv(const double *__restrict__ W, int64_t ld, int n, const double *y,
                                                     const double *base, double sc, double *z, int64_t ldr) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= n) return;
-    const double *row = W + (int64_t)i * ld;
     y += (int64_t)blockIdx.y * ldr;
-    double acc = 0.0;
-    for (int k = (i & ~63) + lane; k < n; k += 64) acc = __builtin_fma((k >= i) ? row[k] : 0.0, y[k], acc);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    const double acc = uptri_row_dot(W, ld, n, y, i, lane);
     if (lane == 0) {
         const int64_t e = (int64_t)blockIdx.y * ldr + i;
         z[e] = base ? base[e] + sc * acc : acc;
     }
+}
+// z[j] = W_j y[j] for the matrices W_j = W + j sW of a lock-step run (blockIdx.y = j: a candidate of one handle, or a member of
+// a group with its C^-T in the group's slab): the rows, the waves and the order of every sum are k_uptri_gemv's
+__global__ __launch_bounds__(256) void k_uptri_gemv_batch(const double *__restrict__ W, int64_t sW, int64_t ld, int n, GemvBatchPtrs b) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= n) return;
+    const int j = blockIdx.y;
+    const double acc = uptri_row_dot(W + (int64_t)j * sW, ld, n, b.y[j], i, lane);
+    if (lane == 0) b.z[j][i] = acc;
 }
 
 __global__ void k_fill_rows(double *__restrict__ M, int64_t ld, int r0, int rows_pad, const double *__restrict__ src,
@@ -795,13 +809,14 @@ __device__ __forceinline__ double dlog_f_scaled(double c) {
 
 // MODE 0: hcols > 1 (KPLS + Matern);  1: hcols == 1, raw inputs;  2: hcols == 1, inputs prescaled per candidate (gb.xs)
 template <int CORR, int MODE, int DK>
-__global__ __launch_bounds__(256) void k_grad_accum(const double *__restrict__ xT, int64_t ldx, int n, int d, int hcols,
-                                                    const double *__restrict__ wabs, int nout, int64_t ld, int ntiles,
-                                                    int nout_pad, GradBatch gb) {
+__global__ __launch_bounds__(256) void k_grad_accum(int64_t ldx, int n, int d, int hcols, const double *__restrict__ wabs, int nout,
+                                                    int64_t ld, int ntiles, int nout_pad, GradBatch gb) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int z = blockIdx.z;
     constexpr bool HC1 = MODE != 0, PRE = MODE == 2;
-    if (PRE) xT = gb.xs[z];  // this candidate's c_k x_k (k-major like xT)
+    // this entry's c_k x_k (k-major like xT), or its OWNER's inputs: one scalar load of a kernel argument either way -- the
+    // members of a group have a training set each
+    const double *__restrict__ xT = PRE ? gb.xs[z] : gb.xT[z];
     const double *__restrict__ coef = gb.coef[z];
     const double *__restrict__ gamma = gb.gamma[z];
     const double *__restrict__ Rneg = gb.rneg[z];
@@ -1224,6 +1239,16 @@ int launch_eval_front_batch(hipStream_t s, int corr, const EvalBatchPtrs &b, int
     return EGX_SUCCESS;
 }
 
+int launch_scale_rows_batch(hipStream_t s, const EvalBatchPtrs &b, int count, int64_t ldx, int d) {
+    if (count < 1 || count > kLockstepMax) {
+        set_error("scale_rows_batch: batch count out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    hipLaunchKernelGGL(k_scale_rows_batch, dim3((unsigned)((ldx + 255) / 256), (unsigned)count), dim3(256), 0, s, b, ldx, d);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
+}
+
 int launch_eval_tail(hipStream_t s, const EvalBatchPtrs &b, int count, int64_t ld, int n, int n_pad, int q, int rows, const int *sync) {
     hipLaunchKernelGGL(k_eval_tail, dim3((unsigned)((n_pad + 255) / 256), (unsigned)(rows ? 1 + q : 1), (unsigned)count), dim3(256), 0, s, b,
                        ld, n, n_pad, rows, sync);
@@ -1270,9 +1295,10 @@ int grad_partial_doubles(int nout) { return kGradMaxWG * (int)round_up(nout, 32)
 
 // batch.count candidates (grid.z); per candidate: coef (d x hcols), gamma (n_pad), rneg (-R^-1, lower, ld), inv_s2,
 // part (grad_partial_doubles(nout) doubles of scratch), out (nout doubles)
-// prescaled != 0 (hcols == 1, every coefficient > 0): batch.xs[z] holds candidate z's inputs times its coefficients
-int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, int d, int hcols, const double *wabs,
-                      int nout, int64_t ld, const GradBatch &batch, int prescaled) {
+// prescaled != 0 (hcols == 1, every coefficient > 0): batch.xs[z] holds candidate z's inputs times its coefficients;
+// otherwise batch.xT[z] the (d x ldx) inputs of its owner
+int launch_grad_accum(hipStream_t s, int corr, int64_t ldx, int n, int d, int hcols, const double *wabs, int nout, int64_t ld,
+                      const GradBatch &batch, int prescaled) {
     if (batch.count < 1 || batch.count > kLockstepMax) {
         set_error("grad_accum: batch count out of range");
         return EGX_ERR_INVALID_VALUE;
@@ -1285,7 +1311,7 @@ int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, in
     const size_t lds = sizeof(double) * (size_t)std::max(2 * dc * 64, 4 * dk);
     const dim3 grid((unsigned)nwg, (unsigned)((nout + dk - 1) / dk), (unsigned)batch.count);
 #define EGX_GA(C_, MODE_, DK_)                                                                                             \
-    hipLaunchKernelGGL((k_grad_accum<C_, MODE_, DK_>), grid, dim3(256), lds, s, xT, ldx, n, d, hcols, wabs, nout, ld, ntiles, \
+    hipLaunchKernelGGL((k_grad_accum<C_, MODE_, DK_>), grid, dim3(256), lds, s, ldx, n, d, hcols, wabs, nout, ld, ntiles, \
                        nout_pad, batch)
 #define EGX_GA_DK(C_, MODE_)                  \
     if (dk == 8) EGX_GA(C_, MODE_, 8);        \
@@ -1308,6 +1334,16 @@ int launch_grad_accum(hipStream_t s, int corr, const double *xT, int64_t ldx, in
 // z (n) <- W y for the upper triangular W (row-major): gamma = C^-T rho through the explicit C^-T of the theta-gradient
 int launch_uptri_gemv(hipStream_t s, const double *W, int64_t ld, int n, const double *y, double *z) {
     return launch_uptri_gemv_rows(s, W, ld, n, y, nullptr, 1.0, z, 0, 1);
+}
+
+int launch_uptri_gemv_batch(hipStream_t s, const double *W, int64_t sW, int64_t ld, int n, const GemvBatchPtrs &b, int count) {
+    if (count < 1 || count > kLockstepMax) {
+        set_error("uptri_gemv_batch: batch count out of range");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    hipLaunchKernelGGL(k_uptri_gemv_batch, dim3((n + 3) / 4, (unsigned)count), dim3(256), 0, s, W, sW, ld, n, b);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_SUCCESS;
 }
 
 int launch_uptri_gemv_rows(hipStream_t s, const double *W, int64_t ld, int n, const double *Y, const double *base, double sc,

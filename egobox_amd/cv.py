@@ -4,7 +4,7 @@ Every caller in egobox that multiplies fits is a cross-validation that refits pe
   GpMetrics (q2 / pva / iae_alpha, k-fold and leave-one-out)   crates/moe/src/metrics.rs:19-220 (twin: crates/gp/src/metrics.rs)
   find_best_expert through compute_error!                      crates/moe/src/algorithm.rs:209-347, expertise_macros.rs:14-51
 The k training sets of a cross-validation have ONE shape, which is what a group of models factors in lock-step
-(`GpParams.fit_group`: egx_gp_create_group + egx_gp_finalize_multi / egx_gp_fit_multi), and their validation predictions are
+(`GpParams.fit_group`: egx_gp_create_group + egx_gp_finalize_multi / egx_gp_fit_multi / egx_gp_fit_lbfgs_multi), and their validation predictions are
 one launch sequence per run of members (`predict_valvar_multi`: egx_gp_predict_valvar_multi).  Each fold's fit and predictions
 are bit for bit what `params.n_workspaces(1).fit(train)` + `predict_valvar(valid)` give (the latter on its batched route).
 
@@ -15,7 +15,8 @@ behaviour and could not be re-read.  A training set here keeps the original row 
 `iter_fold` swaps chunks in place, so its training rows may be a permutation of these -- which moves well-posed results at
 rounding level only.
 
-Not here: the folds of NbClusters::Auto (unequal cluster sizes, and a selection rule of its own), sparse-GP experts.
+Not here: the folds of NbClusters::Auto (unequal cluster sizes, and a selection rule of its own), sparse-GP experts, KPLS and
+ThetaTuning.Partial across models (those folds are a loop of lone fits).
 """
 from __future__ import annotations
 
@@ -60,7 +61,8 @@ def cross_validate(params, x, y, k, want_var=False):
     """The k folds of (x, y) under `params` (a GpParams): a list of `Fold`.  The training sets go through `params.fit_group`
     in batches whose matrices stay below 16 GiB, the validation blocks through `predict_valvar_multi`, and a batch's members
     are closed as soon as their predictions are down (leave-one-out at n = 2000 never holds 2000 factors).  Where `fit_group`
-    refuses (KPLS, ThetaTuning.Partial, L-BFGS) the folds are a loop of `params.fit`."""
+    refuses (KPLS, ThetaTuning.Partial) the folds are a loop of `params.fit`.  `optimizer("lbfgs")` folds go in lock-step too
+    (egx_gp_fit_lbfgs_multi: every round of the folds' L-BFGS machines is one likelihood + gradient evaluation of the group)."""
     from . import gp as G
     x = np.asarray(x, dtype=np.float64)
     if x.ndim == 1:

@@ -547,6 +547,54 @@ def fit_multi(handles, theta0s, lo, hi, max_eval=GP_COBYLA_MAX_EVAL):
     return ne
 
 
+def _multi_models(who, handles):
+    """The raw handles of a multi-model likelihood call, checked before any library call: at least one, all distinct."""
+    hs = [getattr(h, "handle", h) for h in handles]
+    if len(hs) < 1:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{who} needs at least one model")
+    if len({id(h) for h in hs}) != len(hs):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "the models of a multi-model call must be distinct handles")
+    if any(h.h != hs[0].h for h in hs):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"{who}: the models must have the same number of hyperparameters")
+    return hs
+
+
+def likelihood_grad_multi(handles, thetas):
+    """egx_gp_likelihood_grad_multi: (likelihoods (k), gradients (k x h), statuses (k)) of several models, row j of thetas for
+    handles[j].  Members of one group (GpHandle.create_group) in consecutive slots run every stage -- factorisation, C^-T, R^-1,
+    the trace kernel -- in lock-step; each row is bit for bit that handle's own `likelihood_grad`.  Un-fits every model."""
+    hs = _multi_models("likelihood_grad_multi", handles)
+    k, h = len(hs), hs[0].h
+    thetas = L.as_f64(thetas)
+    if thetas.ndim != 2 or thetas.shape[0] != k or thetas.shape[1] not in (1, h):
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"likelihood_grad_multi needs thetas ({k}, {h}) or ({k}, 1), got {thetas.shape}")
+    thetas = np.ascontiguousarray(thetas)
+    lk = np.empty(k)
+    g = np.zeros((k, h))
+    st = np.empty(k, dtype=np.int32)
+    L.check(L.load().egx_gp_likelihood_grad_multi(_handle_array(hs), k, L.dptr(thetas), thetas.shape[1], L.dptr(lk), L.dptr(g),
+                                                   st.ctypes.data_as(C.POINTER(C.c_int32))))
+    return lk, g, st
+
+
+def fit_lbfgs_multi(handles, theta0s, lo, hi, max_iter=50):
+    """egx_gp_fit_lbfgs_multi: the projected L-BFGS multistart of `fit_lbfgs` for several models at once (theta0s: k x n_starts x h
+    in linear theta units); the machines of all models advance in lock-step, a round's trial points per start index are one
+    `likelihood_grad_multi`.  Returns the evaluations per model; every model ends fitted as `fit_lbfgs` on a one-workspace handle
+    would leave it."""
+    hs = _multi_models("fit_lbfgs_multi", handles)
+    k, h = len(hs), hs[0].h
+    theta0s = L.as_f64(theta0s)
+    if theta0s.ndim != 3 or theta0s.shape[0] != k or theta0s.shape[1] < 1 or theta0s.shape[2] != h:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"fit_lbfgs_multi needs theta0s ({k}, n_starts, {h}), got {theta0s.shape}")
+    theta0s = np.ascontiguousarray(theta0s)
+    lo, hi = L.as_f64(np.atleast_1d(lo), 1), L.as_f64(np.atleast_1d(hi), 1)
+    ne = np.zeros(k, dtype=np.int64)
+    L.check(L.load().egx_gp_fit_lbfgs_multi(_handle_array(hs), k, L.dptr(theta0s), theta0s.shape[1], L.dptr(lo), L.dptr(hi), lo.size,
+                                             int(max_iter), ne.ctypes.data_as(L.c_int64_p)))
+    return ne
+
+
 def _multi_queries(who, handles, xqs):
     """(raw handles, k, xqs as a contiguous (k, m, d) array) of a multi-model posterior call, checked before any device work."""
     k = len(handles)
@@ -802,20 +850,22 @@ class GpParams:
         return GaussianProcess(h, self, n_evals)
 
     def fits_groups(self):
-        """Whether `fit_group` takes these parameters: ThetaTuning Fixed or Full with COBYLA, no dimension reduction (what
-        the callers that choose between `fit_group` and a loop of `fit` ask: egobox_amd/cv.py)."""
+        """Whether `fit_group` takes these parameters: ThetaTuning Fixed or Full (COBYLA or L-BFGS), no dimension reduction
+        (what the callers that choose between `fit_group` and a loop of `fit` ask: egobox_amd/cv.py).  Not here: ThetaTuning
+        Partial and KPLS across models."""
         t = self._theta_tuning
-        return t.kind in ("Fixed", "Full") and self._kpls_dim is None and not (t.kind == "Full" and self._optimizer == "lbfgs")
+        return t.kind in ("Fixed", "Full") and self._kpls_dim is None
 
     def fit_group(self, xs, ys):
         """`fit` for k training sets of ONE shape at once (xs: k x n x d, ys: k x n; ThetaTuning Fixed or Full, no KPLS): what
         the expert loop of egobox-moe does one model after the other (crates/moe/src/algorithm.rs:167-177).  The models are
-        created into one group of slabs (egx_gp_create_group) and factored in lock-step (egx_gp_finalize_multi); each is
-        bit for bit the model `fit` returns for its training set.  Returns k GaussianProcess objects."""
+        created into one group of slabs (egx_gp_create_group) and factored in lock-step (egx_gp_finalize_multi; tuned by
+        egx_gp_fit_multi, or by egx_gp_fit_lbfgs_multi with optimizer("lbfgs")); each is bit for bit the model
+        `n_workspaces(1).fit` returns for its training set.  Returns k GaussianProcess objects."""
         self.check()
         t = self._theta_tuning
         if not self.fits_groups():
-            raise L.InvalidValueError(L.ERR_INVALID_VALUE, "fit_group: ThetaTuning Fixed or Full (COBYLA), no dimension reduction")
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, "fit_group: ThetaTuning Fixed or Full, no dimension reduction")
         xs = np.asarray(xs, dtype=np.float64)
         ys = np.asarray(ys, dtype=np.float64)
         if ys.ndim == 3 and ys.shape[2] == 1:
@@ -843,8 +893,12 @@ class GpParams:
                         L.ERR_INVALID_VALUE, f"Bounds for theta should be either 1-dim or dim of xtrain ({dim}), got {len(b)}")
                 b = b * dim if len(b) == 1 else b
                 starts_log10, _ = prepare_multistart(self._n_start, theta0, b, seed=self._seed)
-                n_evals = [int(v) for v in fit_multi(hs, np.tile(10.0 ** starts_log10, (len(hs), 1, 1)), [lo for lo, _ in b],
-                                                     [hi for _, hi in b], self._max_eval)]
+                starts = np.tile(10.0 ** starts_log10, (len(hs), 1, 1))
+                if self._optimizer == "lbfgs":  # (max_eval -> max_iter as `fit` does)
+                    n_evals = [int(v) for v in fit_lbfgs_multi(hs, starts, [lo for lo, _ in b], [hi for _, hi in b],
+                                                               max(5, min(100, self._max_eval // 4)))]
+                else:
+                    n_evals = [int(v) for v in fit_multi(hs, starts, [lo for lo, _ in b], [hi for _, hi in b], self._max_eval)]
         except Exception:
             for h in hs:
                 h.close()

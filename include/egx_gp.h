@@ -309,6 +309,34 @@ int32_t egx_gp_likelihood_multi(egx_gp *const *gps, int32_t k, const double *the
  * theta*, likelihood and predictions are the same bits. */
 int32_t egx_gp_fit_multi(egx_gp *const *gps, int32_t k, const double *theta0s /*k x n_starts x h*/, int64_t n_starts,
                          const double *lo, const double *hi, int64_t bounds_len, int64_t max_eval, int64_t *n_evals_out /*k*/);
+/* The theta-gradient across MODELS (new, like egx_gp_likelihood_grad itself): likelihood and dL/dtheta of k DISTINCT handles with
+ * the same number of hyperparameters h, row j of thetas (k x theta_len) for gps[j]; lkh (k), dlkh_dtheta (k x h), status (k).
+ *   Handles  Members of one group (egx_gp_create_group) in consecutive slots form runs (at most 12) and run EVERY stage -- the
+ *            factorisation, the C^-T rider, R^-1 = C^-T C^-1, the trace kernel -- in lock-step, the member a grid coordinate;
+ *            their C^-T buffers are the group's (one n_pad^2 slot per member, shared with the x-gradients' cache: no buffer per
+ *            handle).  Every other handle -- a lone handle, a member out of order, a handle with w_star -- goes one by one.
+ *            The result never depends on which route was taken.
+ *   Bits     Row j is bit for bit what egx_gp_likelihood_grad(gps[j], thetas + j theta_len, ...) returns on that handle alone:
+ *            a matrix never sees its companions, and the form of the trace kernel depends on one member's shape and its OWN
+ *            coefficients only.
+ *   Status   as egx_gp_likelihood_grad_batch: a NaN theta row gives -inf, EGX_STATUS_NAN_THETA and a zero gradient -- not an
+ *            error return --, a member that is not positive definite its status and a zero gradient; neighbours are unaffected.
+ *   NOTE     like egx_gp_likelihood_multi the call evaluates on every member's workspace 0: a fitted member is UN-FITTED (also
+ *            one with spare workspaces, which egx_gp_likelihood_grad would keep fitted), and its cached C^-T is dropped; call
+ *            egx_gp_finalize[_multi] again before predicting.  A fitted model that is not part of the call keeps its state. */
+int32_t egx_gp_likelihood_grad_multi(egx_gp *const *gps, int32_t k, const double *thetas /*k x theta_len*/,
+                                     int64_t theta_len, double *lkh /*k*/, double *dlkh_dtheta /*k x h*/,
+                                     int32_t *status /*k*/);
+/* egx_gp_fit_lbfgs across MODELS: k x n_starts projected L-BFGS machines, start-major and model-minor as egx_gp_fit_multi lays
+ * out its COBYLA machines; per round and start index, the trial points of the models whose machine still asks are ONE
+ * egx_gp_likelihood_grad_multi evaluation.  The best start per model wins (the first on ties), then ONE egx_gp_finalize_multi
+ * of the winners.  theta0s is (k x n_starts x h) in linear theta units (model-major), lo / hi / bounds_len / max_iter as
+ * egx_gp_fit_lbfgs, n_evals_out (k, optional) the likelihood + gradient evaluations per model.  Every member ends exactly as
+ * egx_gp_fit_lbfgs leaves a one-workspace handle of its training set -- theta*, likelihood, evaluations and predictions are the
+ * same bits -- wherever the two handles factor by the same schedule (egx_gp_get_schedule): every padded size below 5376. */
+int32_t egx_gp_fit_lbfgs_multi(egx_gp *const *gps, int32_t k, const double *theta0s /*k x n_starts x h*/, int64_t n_starts,
+                               const double *lo, const double *hi, int64_t bounds_len, int64_t max_iter,
+                               int64_t *n_evals_out /*k*/);
 /* ThetaTuning::Full fit (algorithm.rs:874-948): multistart derivative-free
  * maximisation of the likelihood over log10(theta) in [lo,hi], then finalize.
  * theta0s is (n_starts x h) in LINEAR theta units: the caller supplies the

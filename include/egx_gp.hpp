@@ -280,6 +280,18 @@ class GaussianProcess {
     std::pair<int64_t, int64_t> dims() const { return {d_, 1}; }  // :436-439
     int64_t n_evals() const { return n_evals_; }
     egx_gp *handle() const { return h_.get(); }
+    // theta() / variance() / likelihood() read again from the handle after a fit that ran on it from outside (fit_lbfgs_group)
+    void adopt_fit(int64_t n_evals) {
+        int64_t hh = 0;
+        check(egx_gp_dims(h_.get(), nullptr, nullptr, nullptr, &hh));
+        theta_.resize((size_t)hh);
+        egx_gp_inner_view view{};
+        view.theta = theta_.data();
+        view.sigma2 = &sigma2_;
+        view.likelihood = &likelihood_;
+        check(egx_gp_get_inner(h_.get(), &view));
+        n_evals_ = n_evals;
+    }
 
   private:
     friend class GpParams;
@@ -578,6 +590,38 @@ inline std::pair<std::vector<double>, std::vector<double>> predict_valvar_gradie
     std::vector<double> gy(hs.size() * (size_t)m * (size_t)d), gv(hs.size() * (size_t)m * (size_t)d);
     check(egx_gp_predict_valvar_gradients_multi(hs.data(), (int32_t)hs.size(), xq, m, gy.data(), gv.data()));
     return {std::move(gy), std::move(gv)};
+}
+
+// The likelihood and dL/dtheta of k models in one call (egx_gp_likelihood_grad_multi): row j of thetas (k x theta_len) for
+// models[j].  Members of one group (GpParams::fit_group) run every stage in lock-step, each row bit for bit the model's own
+// egx_gp_likelihood_grad.  The call UN-FITS the models: fit them again (fit_lbfgs_group, egx_gp_finalize_multi) before predicting.
+inline GaussianProcess::LikelihoodGrad likelihood_grad_group(const std::vector<GaussianProcess *> &models, const double *thetas,
+                                                             int64_t theta_len) {
+    std::vector<egx_gp *> hs;
+    for (const GaussianProcess *g : models) hs.push_back(g->handle());
+    int64_t h = 0;
+    if (!hs.empty()) check(egx_gp_dims(hs[0], nullptr, nullptr, nullptr, &h));
+    GaussianProcess::LikelihoodGrad out;
+    out.likelihood.resize(hs.size());
+    out.gradient.assign(hs.size() * (size_t)h, 0.0);
+    out.status.resize(hs.size());
+    check(egx_gp_likelihood_grad_multi(hs.data(), (int32_t)hs.size(), thetas, theta_len, out.likelihood.data(), out.gradient.data(),
+                                       out.status.data()));
+    return out;
+}
+
+// The projected L-BFGS multistart on the theta-gradient for k models in one call (egx_gp_fit_lbfgs_multi): theta0s
+// (k x n_starts x h, linear theta units), lo / hi (bounds_len = 1 or h).  Members of one group advance in lock-step; every model
+// ends as egx_gp_fit_lbfgs leaves a one-workspace handle of its training set, and its theta() / variance() / likelihood() /
+// n_evals() are those of the new fit.  Returns the evaluations per model.
+inline std::vector<int64_t> fit_lbfgs_group(const std::vector<GaussianProcess *> &models, const double *theta0s, int64_t n_starts,
+                                            const double *lo, const double *hi, int64_t bounds_len, int64_t max_iter = 50) {
+    std::vector<egx_gp *> hs;
+    for (const GaussianProcess *g : models) hs.push_back(g->handle());
+    std::vector<int64_t> ne(hs.size(), 0);
+    check(egx_gp_fit_lbfgs_multi(hs.data(), (int32_t)hs.size(), theta0s, n_starts, lo, hi, bounds_len, max_iter, ne.data()));
+    for (size_t j = 0; j < models.size(); j++) models[j]->adopt_fit(ne[j]);
+    return ne;
 }
 
 // GpMixture::predict / predict_var over fitted experts of THIS process (crates/moe/src/algorithm.rs:411-423, 670-685 smooth;
