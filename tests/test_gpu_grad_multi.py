@@ -87,7 +87,8 @@ def test_mixed_forms_and_failures_in_one_run(egx):
     """Member 1: a NaN theta (answered at once; it cuts the run).  Member 2: one theta component EXACTLY 0.0 -- the library
     accepts it (checked on the lone call below: status OK), so the zero itself is used, not a smallest accepted value -- which
     puts it on the raw form of the trace kernel between prescaled neighbours.  Member 4: training rows 0 and 1 identical in a
-    group without nugget, so the second pivot is exactly zero: not positive definite.  Status paths only."""
+    group without nugget, so the second pivot is exactly zero: not positive definite.  Status paths only: the VALUES of a raw-form
+    member between prescaled neighbours are held to the closed form in tests/test_gpu_theta_grad.py::test_mixed_form_group_rows."""
     k, n, d = 6, 150, 3
     xs, ys = _sets(k, n, d, seed=77)
     xs[4, 1] = xs[4, 0]
