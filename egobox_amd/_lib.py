@@ -214,6 +214,9 @@ SIGNATURES = [
     ("egx_gmm_config_default", None, [C.POINTER(GmmConfig)]),
     ("egx_gmm_fit", C.c_int32, [C.POINTER(GmmConfig), c_double_p, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
                                 c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
+    ("egx_gmm_fit_wide", C.c_int32, [C.POINTER(GmmConfig), c_double_p, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                     c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p,
+                                     c_double_p]),
     ("egx_moe_predict_valvar_gradients", C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p, C.c_int64, C.c_int64,
                                                      c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int32,
                                                      c_double_p, c_double_p]),

@@ -363,8 +363,9 @@ struct GmmLaunch {
     const double *data = nullptr;  // n x D row-major
     int64_t n = 0;
     int D = 0, DP = 0, k = 0, R = 0;
-    int T = 0;        // tiles of kGmmTileRows rows
-    int rsplit = 1;   // workgroups per tile; workgroup y serves the restarts y, y + rsplit, ..
+    int T = 0;        // tiles of kGmmTileRows rows; the wide path: chunks (gmm_wide_plan.h)
+    int tpc = 1;      // the wide path: consecutive tiles of a chunk
+    int rsplit = 1;  // workgroups per tile; workgroup y serves the restarts y, y + rsplit, ..
     int init = 0;     // iteration 0: one-hot responsibilities on the nearest mean
     const int *active = nullptr;           // R: 0 = frozen, both kernels skip it
     double *means = nullptr;               // R x k x DP
@@ -380,6 +381,11 @@ inline size_t gmm_part_len(int DP) { return (size_t)(DP / 4) * (DP / 4 + 1) / 2 
 size_t gmm_estep_lds_bytes(int DP, int k);
 int launch_gmm_estep(hipStream_t s, const GmmLaunch &g);
 int launch_gmm_mstep(hipStream_t s, const GmmLaunch &g, double reg_covar);
+// kernels_gmm_wide.hip: the same two steps for rows up to 128 wide on the FP64 matrix unit (egx_gmm_fit_wide).  DP = D rounded
+// up to 16, T = chunks, part = chunks x R x k x gmm_wide::part_len(DP), prec starts as the identity (iteration 0 measures
+// ||x - mu||^2 through the same product)
+int launch_gmm_estep_wide(hipStream_t s, const GmmLaunch &g);
+int launch_gmm_mstep_wide(hipStream_t s, const GmmLaunch &g, double reg_covar);
 // The fitted mixture at m raw points (m x d on the device), one lane per point on the calling thread's default stream: the
 // responsibilities (out: m x k) or, deriv, their x-derivatives (m x k x d).  blk = gmx_pack's block (gmx_point.h) on the device,
 // lds = the dynamic LDS the caller has sized and bounded.  spec != nullptr (mixint.h, on the device): the points are cast as they

@@ -3,6 +3,8 @@
 // The n_runs restarts are independent EM problems of one shape over the SAME data: they advance in lock-step, one E-step
 // launch and one M-step launch per iteration for all of them (kernels_gmm.hip), the host reads the R lower bounds back and
 // freezes the restarts that stopped.  A restart computes the same bits alone and in any batch.
+// egx_gmm_fit_wide: the same training for rows up to 128 wide (kernels_gmm_wide.hip, gmm_wide_plan.h).  Both entry points are
+// gmm_fit_driver with their shapes and their launch pair (GmmPath).
 // ... and the fitted mixture's predict side: egx_gmx_precisions_chol (host) and egx_gmx_predict_probas(_derivatives).
 #include <algorithm>
 #include <cmath>
@@ -12,6 +14,7 @@
 
 #include "dev_mem.h"
 #include "egx_internal.h"
+#include "gmm_wide_plan.h"
 #include "gmx_point.h"
 #include "gp_handle.h"
 
@@ -61,60 +64,89 @@ const egx::mixint::Col *spec_ptr(const egx::MixSpec &sp, const egx::DevBuf &d_sp
     return sp.empty() ? nullptr : reinterpret_cast<const egx::mixint::Col *>(d_spec.p);
 }
 
-}  // namespace
+// The two trainings differ in their shapes and their launch pair only: the narrow path (kernels_gmm.hip: dim <= 36, 256-row
+// tiles, 4 x 4 moment blocks on the vector unit) and the wide one (kernels_gmm_wide.hip, gmm_wide_plan.h: dim <= 128, the
+// matrix unit).  fill() checks the width and sizes DP, T, tpc and the workspace before the device is touched.
+struct GmmPath {
+    std::string who;
+    int (*fill)(const GmmPath &, int D, int k, int R, int64_t n, egx::GmmLaunch &g, size_t &part_doubles);
+    int (*estep)(hipStream_t, const egx::GmmLaunch &);
+    int (*mstep)(hipStream_t, const egx::GmmLaunch &, double);
+    bool identity_prec;  // P before iteration 0: the identity (wide), or never read (narrow: zero)
+};
 
-extern "C" {
-
-void egx_gmm_config_default(egx_gmm_config *cfg) {
-    if (!cfg) return;
-    cfg->n_clusters = 1;
-    cfg->n_runs = 20;  // crates/moe/src/algorithm.rs:121
-    cfg->max_iter = 100;
-    cfg->device = -1;
-    cfg->tol = 1e-3;
-    cfg->reg_covar = 1e-6;
+int fill_narrow(const GmmPath &p, int D, int k, int R, int64_t n, egx::GmmLaunch &g, size_t &part_doubles) {
+    const int DP = (D + 3) / 4 * 4;
+    if (DP > egx::kGmmMaxDim || k > egx::kGmmMaxClusters) {
+        set_error(p.who + ": dim <= 36 and n_clusters <= 16 expected (got dim " + std::to_string(D) + ", n_clusters " +
+                  std::to_string(k) + "); egx_gmm_fit_wide takes dim <= 128");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int64_t T64 = (n + egx::kGmmTileRows - 1) / egx::kGmmTileRows;
+    part_doubles = (size_t)T64 * R * k * egx::gmm_part_len(DP);
+    if (T64 > (1 << 22) || part_doubles > ((size_t)1 << 29)) {  // (4 GiB of partial moments)
+        set_error(p.who + ": n * n_runs * n_clusters * dim^2 beyond the workspace limit of 4 GiB");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    g.DP = DP;
+    g.T = (int)T64;
+    return EGX_SUCCESS;
 }
 
-int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim, const double *init_means,
-                    double *weights, double *means, double *covariances, double *lower_bounds, int32_t *n_iters,
-                    int32_t *statuses, int32_t *best_run, double *all_weights, double *all_means, double *all_covariances) {
+int fill_wide(const GmmPath &p, int D, int k, int R, int64_t n, egx::GmmLaunch &g, size_t &part_doubles) {
+    namespace W = egx::gmm_wide;
+    if (D > W::kMaxDim || k > egx::kGmmMaxClusters) {
+        set_error(p.who + ": dim <= 128 and n_clusters <= 16 expected (got dim " + std::to_string(D) + ", n_clusters " +
+                  std::to_string(k) + ")");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const W::Plan pl = W::plan(n, D);
+    if (pl.tiles > ((int64_t)1 << 30) || !W::workspace_doubles(pl, R, k, part_doubles)) {
+        set_error(p.who + ": n_runs * n_clusters * dim^2 beyond the workspace limit of 4 GiB");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    g.DP = pl.DP;
+    g.T = (int)pl.chunks;
+    g.tpc = (int)pl.tiles_per_chunk;
+    return EGX_SUCCESS;
+}
+
+// Validation, the uploads, the round loop (the live mask up, an E-step and an M-step launch, the R lower bounds and flags
+// back, the stopped restarts frozen), the best run and the all-failed error: one text for both entry points.
+int gmm_fit_driver(const GmmPath &path, const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim,
+                   const double *init_means, double *weights, double *means, double *covariances, double *lower_bounds,
+                   int32_t *n_iters, int32_t *statuses, int32_t *best_run, double *all_weights, double *all_means,
+                   double *all_covariances) {
+    const std::string &who = path.who;
     if (!cfg || !data || !init_means || !weights || !means || !covariances || !lower_bounds || !n_iters || !statuses || !best_run) {
-        set_error("egx_gmm_fit: NULL argument");
+        set_error(who + ": NULL argument");
         return EGX_ERR_INVALID_VALUE;
     }
     const int k = cfg->n_clusters, R = cfg->n_runs, D = dim;
     if (k < 1 || D < 1 || n < k || R < 1 || cfg->max_iter < 1 || !(cfg->tol >= 0.0) || !(cfg->reg_covar >= 0.0) ||
         !std::isfinite(cfg->reg_covar)) {
-        set_error("egx_gmm_fit: n >= n_clusters >= 1, dim >= 1, n_runs >= 1, max_iter >= 1, tol >= 0 and reg_covar >= 0 expected");
+        set_error(who + ": n >= n_clusters >= 1, dim >= 1, n_runs >= 1, max_iter >= 1, tol >= 0 and reg_covar >= 0 expected");
         return EGX_ERR_INVALID_VALUE;
     }
-    const int DP = (D + 3) / 4 * 4;
-    if (DP > egx::kGmmMaxDim || k > egx::kGmmMaxClusters) {
-        set_error("egx_gmm_fit: dim <= 36 and n_clusters <= 16 expected (got dim " + std::to_string(D) + ", n_clusters " +
-                  std::to_string(k) + ")");
-        return EGX_ERR_INVALID_VALUE;
-    }
-    const int64_t T64 = (n + egx::kGmmTileRows - 1) / egx::kGmmTileRows;
-    const size_t len = egx::gmm_part_len(DP);
-    const size_t part_doubles = (size_t)T64 * R * k * len;
-    if (T64 > (1 << 22) || part_doubles > ((size_t)1 << 29)) {  // (4 GiB of partial moments)
-        set_error("egx_gmm_fit: n * n_runs * n_clusters * dim^2 beyond the workspace limit of 4 GiB");
-        return EGX_ERR_INVALID_VALUE;
-    }
+    egx::GmmLaunch g;
+    size_t part_doubles = 0;
+    EGX_RC(path.fill(path, D, k, R, n, g, part_doubles));
+    const int DP = g.DP;
+    const int64_t T64 = g.T;
     if (!all_finite(data, (size_t)n * D) || !all_finite(init_means, (size_t)R * k * D)) {
-        set_error("egx_gmm_fit: data and init_means must be finite");
+        set_error(who + ": data and init_means must be finite");
         return EGX_ERR_INVALID_VALUE;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
         (void)hipGetLastError();
-        set_error("egx_gmm_fit: no HIP device");
+        set_error(who + ": no HIP device");
         return EGX_ERR_NO_DEVICE;
     }
     int device = cfg->device;
     if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;  // the calling thread's current device
     if (device >= ndev) {
-        set_error("egx_gmm_fit: device out of range");
+        set_error(who + ": device out of range");
         return EGX_ERR_INVALID_VALUE;
     }
     EGX_HIP_CHECK(hipSetDevice(device));
@@ -137,18 +169,22 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
         for (int j = 0; j < D; j++) h_means[i * DP + j] = init_means[i * D + j];
     EGX_HIP_CHECK(hipMemcpy(d_data.p, data, sizeof(double) * (size_t)n * D, hipMemcpyHostToDevice));
     EGX_HIP_CHECK(hipMemcpy(d_means.p, h_means.data(), sizeof(double) * h_means.size(), hipMemcpyHostToDevice));
-    EGX_HIP_CHECK(hipMemset(d_prec.p, 0, sizeof(double) * rk * DP * DP));
+    if (path.identity_prec) {
+        std::vector<double> h_prec(rk * DP * DP, 0.0);
+        for (size_t i = 0; i < rk; i++)
+            for (int j = 0; j < DP; j++) h_prec[(i * DP + j) * DP + j] = 1.0;
+        EGX_HIP_CHECK(hipMemcpy(d_prec.p, h_prec.data(), sizeof(double) * h_prec.size(), hipMemcpyHostToDevice));
+    } else {
+        EGX_HIP_CHECK(hipMemset(d_prec.p, 0, sizeof(double) * rk * DP * DP));
+    }
     EGX_HIP_CHECK(hipMemset(d_cst.p, 0, sizeof(double) * rk));
     EGX_HIP_CHECK(hipMemset(d_lbst.p, 0, sizeof(double) * 2 * R));
 
-    egx::GmmLaunch g;
     g.data = d_data.p;
     g.n = n;
     g.D = D;
-    g.DP = DP;
     g.k = k;
     g.R = R;
-    g.T = (int)T64;
     // enough workgroups to fill the chip when the data has few tiles: the restarts are dealt over grid.y (a restart's
     // arithmetic does not depend on the deal)
     g.rsplit = (int)std::min<int64_t>(R, std::max<int64_t>(1, (1024 + T64 - 1) / T64));
@@ -174,8 +210,8 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
     for (int it = 0; it <= cfg->max_iter && n_active > 0; it++) {
         g.init = it == 0;
         EGX_HIP_CHECK(hipMemcpy(d_active.p, active.data(), sizeof(int) * R, hipMemcpyHostToDevice));
-        EGX_RC(egx::launch_gmm_estep(nullptr, g));
-        EGX_RC(egx::launch_gmm_mstep(nullptr, g, cfg->reg_covar));
+        EGX_RC(path.estep(nullptr, g));
+        EGX_RC(path.mstep(nullptr, g, cfg->reg_covar));
         EGX_HIP_CHECK(hipMemcpy(h_lbst.data(), d_lbst.p, sizeof(double) * 2 * R, hipMemcpyDeviceToHost));
         for (int r = 0; r < R; r++) {
             if (!active[r]) continue;
@@ -215,7 +251,7 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
     }
     if (all_covariances) std::copy(h_cov.begin(), h_cov.end(), all_covariances);
     if (best < 0) {
-        set_error("egx_gmm_fit: every restart failed (a covariance that is not positive definite, or a value that is not finite)");
+        set_error(who + ": every restart failed (a covariance that is not positive definite, or a value that is not finite)");
         return EGX_ERR_LINALG;
     }
     for (int c = 0; c < k; c++) {
@@ -225,6 +261,37 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
         std::copy(h_cov.begin() + i * D * D, h_cov.begin() + (i + 1) * D * D, covariances + (size_t)c * D * D);
     }
     return EGX_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+void egx_gmm_config_default(egx_gmm_config *cfg) {
+    if (!cfg) return;
+    cfg->n_clusters = 1;
+    cfg->n_runs = 20;  // crates/moe/src/algorithm.rs:121
+    cfg->max_iter = 100;
+    cfg->device = -1;
+    cfg->tol = 1e-3;
+    cfg->reg_covar = 1e-6;
+}
+
+int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim, const double *init_means,
+                    double *weights, double *means, double *covariances, double *lower_bounds, int32_t *n_iters,
+                    int32_t *statuses, int32_t *best_run, double *all_weights, double *all_means, double *all_covariances) {
+    static const GmmPath narrow{"egx_gmm_fit", fill_narrow, egx::launch_gmm_estep, egx::launch_gmm_mstep, false};
+    return gmm_fit_driver(narrow, cfg, data, n, dim, init_means, weights, means, covariances, lower_bounds, n_iters, statuses,
+                          best_run, all_weights, all_means, all_covariances);
+}
+
+int32_t egx_gmm_fit_wide(const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim, const double *init_means,
+                         double *weights, double *means, double *covariances, double *lower_bounds, int32_t *n_iters,
+                         int32_t *statuses, int32_t *best_run, double *all_weights, double *all_means,
+                         double *all_covariances) {
+    static const GmmPath wide{"egx_gmm_fit_wide", fill_wide, egx::launch_gmm_estep_wide, egx::launch_gmm_mstep_wide, true};
+    return gmm_fit_driver(wide, cfg, data, n, dim, init_means, weights, means, covariances, lower_bounds, n_iters, statuses,
+                          best_run, all_weights, all_means, all_covariances);
 }
 
 // ---- Gaussian mixture responsibilities ----------------------------------------------------------

@@ -11,6 +11,12 @@ and seed give the same answer here, not the reference's points.
 `Egor(coego_n_coop=k)` is CoEGO (solver/coego.rs): the coordinates are split into k random groups, theta is tuned and the
 criterion optimised over one group at a time, through the active coordinates of the infill handle (`InfillObjective.set_active`).
 
+Clustered surrogates (`GpConfig(n_clusters=k)`, k >= 2) train their mixture on the joined rows [x, y] through
+`moe.train_mixture`: up to 36 columns on the narrow path, up to 128 on the wide one (`GaussianMixture.fit_wide`), so a clustered
+`Egor` takes up to 127 input columns with hard recombination.  Smooth recombination's x-gradients and the infill handle on a
+mixture still need 3 d + k <= 320 (d of about 100).  With ONE cluster and more than 35 columns no mixture is trained at all: the
+closed form below (`_one_cluster`), as before.
+
 Not here (a clean `InvalidValueError`, or no argument at all): TREGO, function constraints (`subject_to` / `fcstrs`), the
 sigma-weight portfolio, hot start / `outdir` / warm start files, `NbClusters::Auto` and its reclustering rule, sparse surrogates, a
 C++ mirror, and training objective and constraints as one lock-step group.
@@ -39,7 +45,7 @@ EGO_DEFAULT_MAX_ITERS = 20       # egor_config.rs:171
 EGO_GP_OPTIM_N_START = 10        # egor_config.rs:13
 EGO_GP_OPTIM_MAX_EVAL = 50       # egor_config.rs:15
 DUPLICATE_L1 = 100.0 * np.finfo(np.float64).eps  # utils/misc.rs:49
-GMM_MAX_DIM = 36                 # the widest training row [x, y] the mixture's training takes (egx_gmm_fit)
+GMM_MAX_DIM = 36                 # the widest row [x, y] of the narrow mixture training; ONE cluster beyond it: the closed form
 
 _CRITERIA = {"ei": EI, "log_ei": LOG_EI, "logei": LOG_EI, "wb2": WB2, "wb2s": WB2S}
 _OPTIMIZERS = ("slsqp", "cobyla")

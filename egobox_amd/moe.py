@@ -64,7 +64,19 @@ class GaussianMixture:
         keep the restart with the greatest lower bound.  `init_means` (n_runs, n_clusters, dim) are the restarts' initial
         means; by default restart r starts from n_clusters distinct rows of `data` drawn by numpy.random.default_rng(seed)
         (not the reference's Xoshiro256Plus stream).  The result carries lower_bound_, n_iter_, and per restart
-        lower_bounds_, n_iters_, statuses_ (0 converged, 1 stopped at max_iter, 2 failed) and best_run_."""
+        lower_bounds_, n_iters_, statuses_ (0 converged, 1 stopped at max_iter, 2 failed) and best_run_.  dim <= 36; wider
+        rows: fit_wide."""
+        return cls._fit("egx_gmm_fit", data, n_clusters, n_runs, seed, max_iter, tol, reg_covar, init_means, device)
+
+    @classmethod
+    def fit_wide(cls, data, n_clusters, n_runs=20, seed=42, max_iter=100, tol=1e-3, reg_covar=1e-6, init_means=None, device=-1):
+        """`fit` for rows up to 128 wide (egx_gmm_fit_wide: the same EM with its two O(dim^2) products per row on the FP64
+        matrix unit).  Same arguments, attributes and defaults; narrow rows are taken too and agree with `fit` to rounding,
+        not to the bit."""
+        return cls._fit("egx_gmm_fit_wide", data, n_clusters, n_runs, seed, max_iter, tol, reg_covar, init_means, device)
+
+    @classmethod
+    def _fit(cls, entry, data, n_clusters, n_runs, seed, max_iter, tol, reg_covar, init_means, device):
         from . import _lib as L
         data = np.asarray(data, dtype=np.float64)
         if data.ndim != 2:
@@ -92,9 +104,9 @@ class GaussianMixture:
         n_iters, statuses = np.zeros(n_runs, dtype=np.int32), np.zeros(n_runs, dtype=np.int32)
         best = L.C.c_int32(-1)
         all_w, all_m, all_c = np.empty((n_runs, k)), np.empty((n_runs, k, dim)), np.empty((n_runs, k, dim, dim))
-        rc = lib.egx_gmm_fit(cfg, L.dptr(data), n, dim, L.dptr(init_means), L.dptr(weights), L.dptr(means), L.dptr(covs),
-                             L.dptr(lbs), n_iters.ctypes.data_as(L.c_int32_p), statuses.ctypes.data_as(L.c_int32_p),
-                             L.C.byref(best), L.dptr(all_w), L.dptr(all_m), L.dptr(all_c))
+        rc = getattr(lib, entry)(cfg, L.dptr(data), n, dim, L.dptr(init_means), L.dptr(weights), L.dptr(means), L.dptr(covs),
+                                 L.dptr(lbs), n_iters.ctypes.data_as(L.c_int32_p), statuses.ctypes.data_as(L.c_int32_p),
+                                 L.C.byref(best), L.dptr(all_w), L.dptr(all_m), L.dptr(all_c))
         if rc == ERR_LINALG:
             raise ClusteringError(rc, lib.egx_last_error().decode("utf-8", "replace"))
         L.check(rc)
@@ -215,6 +227,17 @@ class GaussianMixture:
         uprime = -deriv * u[:, :, None]                                            # (m, k, nx)
         vprime = uprime.sum(axis=1)                                                # (m, nx)
         return (uprime * v[:, None, None] - u[:, :, None] * vprime[:, None, :]) / (v * v)[:, None, None]
+
+
+GMM_NARROW_MAX_DIM = 36  # the widest row GaussianMixture.fit takes (egx_gmm_fit); beyond: fit_wide, up to 128
+
+
+def train_mixture(data, n_clusters, **kw):
+    """The mixture of a mixture of experts on the joined rows `data` (n, dim): GaussianMixture.fit up to 36 columns -- what
+    it has always been, to the bit -- and GaussianMixture.fit_wide beyond.  Keywords as GaussianMixture.fit."""
+    dim = np.shape(data)[1] if np.ndim(data) == 2 else 0
+    fit = GaussianMixture.fit if dim <= GMM_NARROW_MAX_DIM else GaussianMixture.fit_wide
+    return fit(data, n_clusters, **kw)
 
 
 def extract_part(data, quantile):
@@ -424,7 +447,7 @@ class GpMixtureParams:
             gmx = self._gmx
         else:
             training = extract_part(data, 5)[1] if smooth_none else data
-            gmm = GaussianMixture.fit(training, k, n_runs=self._n_runs, seed=self._seed, device=self._device)
+            gmm = train_mixture(training, k, n_runs=self._n_runs, seed=self._seed, device=self._device)
             gmx = gmm.marginal(nx, self._heaviside_factor if self._heaviside_factor is not None else 1.0)
         return self._train_on_clusters(x, y, data, gmx, smooth_none)
 

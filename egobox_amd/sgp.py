@@ -561,8 +561,8 @@ class SparseGpMix:
         data = np.column_stack([x, y])
         smooth_none = self.recombination == "smooth" and factor is None
         training = M.extract_part(data, 5)[1] if smooth_none else data
-        gmm = M.GaussianMixture.fit(training, k, n_runs=self.n_runs, seed=42 if self.seed is None else self.seed,
-                                    device=self.device)
+        gmm = M.train_mixture(training, k, n_runs=self.n_runs, seed=42 if self.seed is None else self.seed,
+                              device=self.device)
         gmx = gmm.marginal(nx, 1.0 if factor is None else float(factor))
         clusters = M.sort_by_cluster(k, data, gmx.predict(x))
         M.check_three_points(clusters)

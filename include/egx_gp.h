@@ -582,6 +582,16 @@ int32_t egx_gmm_fit(const egx_gmm_config *cfg, const double *data, int64_t n, in
                     double *covariances /*k*dim*dim*/, double *lower_bounds /*n_runs*/, int32_t *n_iters /*n_runs*/,
                     int32_t *statuses /*n_runs*/, int32_t *best_run, double *all_weights /*n_runs*k*/,
                     double *all_means /*n_runs*k*dim*/, double *all_covariances /*n_runs*k*dim*dim*/);
+/* The same training for rows up to 128 wide: arguments, outputs, statuses and errors are exactly those of egx_gmm_fit, with
+ * dim <= 128 and n_clusters <= 16 (beyond: EGX_ERR_INVALID_VALUE, checked before the device is touched).  The two products
+ * per row that cost O(dim^2) run on the FP64 matrix unit; narrow rows are taken too, and agree with egx_gmm_fit to rounding
+ * (the sums have another order, so not to the bit).  A restart computes the same bits alone and in any batch here as well.
+ * The mixture's x-derivatives and the infill handles on mixtures still need 3 d + k <= 320 (below). */
+int32_t egx_gmm_fit_wide(const egx_gmm_config *cfg, const double *data, int64_t n, int32_t dim,
+                         const double *init_means /*n_runs*k*dim*/, double *weights /*k*/, double *means /*k*dim*/,
+                         double *covariances /*k*dim*dim*/, double *lower_bounds /*n_runs*/, int32_t *n_iters /*n_runs*/,
+                         int32_t *statuses /*n_runs*/, int32_t *best_run, double *all_weights /*n_runs*k*/,
+                         double *all_means /*n_runs*k*dim*/, double *all_covariances /*n_runs*k*dim*dim*/);
 
 /* d p_c(x) / d x of those responsibilities: GaussianMixture::predict_probas_derivatives (gaussian_mixture.rs:127-170),
  * dprobas is (m x k x d) row-major; on the device, one lane per point (needs 3 d + k <= 320). */
@@ -903,7 +913,8 @@ int32_t egx_infill_optimize_slsqp(egx_infill *h, const double *lo /*d*/, const d
  * n_experts < 1, and for k >= 2 a heaviside factor that is not positive and finite, non-finite weights / means / factors,
  * weights that are not positive, differing d or device.  EGX_ERR_NOT_FITTED names surrogate and expert, here and in every
  * later call.  EGX_ERR_UNSUPPORTED when 3 (d | 1) + 2 (k | 1) > 320 (the recombination keeps that many doubles of LDS per
- * point; every mixture egx_gmm_fit can train, d <= 35 and k <= 16, fits).
+ * point; every mixture egx_gmm_fit can train, d <= 35 and k <= 16, fits; one of egx_gmm_fit_wide beyond d of about 100
+ * does not).
  * Out of scope: mixtures whose experts live on several ranks (egx_sweep).  Sparse-GP experts (egx_sgp): egx_infill_create_any below. */
 typedef struct {
     egx_gp *const *experts; int32_t n_experts;       /* one per cluster, fitted, same d and device */

@@ -668,8 +668,9 @@ struct GmmFit {
     std::vector<int32_t> n_iters, statuses;           // per restart; 0 converged, 1 stopped at max_iter, 2 failed
     int32_t best_run = -1;
 };
-inline GmmFit gmm_fit(const double *data, int64_t n, int32_t dim, int32_t n_clusters, const std::vector<double> &init_means,
-                      const egx_gmm_config *config = nullptr) {
+using GmmFitFn = decltype(&egx_gmm_fit);
+inline GmmFit gmm_fit_with(GmmFitFn fit, const double *data, int64_t n, int32_t dim, int32_t n_clusters,
+                           const std::vector<double> &init_means, const egx_gmm_config *config) {
     egx_gmm_config cfg;
     if (config)
         cfg = *config;
@@ -687,9 +688,18 @@ inline GmmFit gmm_fit(const double *data, int64_t n, int32_t dim, int32_t n_clus
     f.lower_bounds.resize((size_t)cfg.n_runs);
     f.n_iters.resize((size_t)cfg.n_runs);
     f.statuses.resize((size_t)cfg.n_runs);
-    check(egx_gmm_fit(&cfg, data, n, dim, init_means.data(), f.weights.data(), f.means.data(), f.covariances.data(),
-                      f.lower_bounds.data(), f.n_iters.data(), f.statuses.data(), &f.best_run, nullptr, nullptr, nullptr));
+    check(fit(&cfg, data, n, dim, init_means.data(), f.weights.data(), f.means.data(), f.covariances.data(),
+              f.lower_bounds.data(), f.n_iters.data(), f.statuses.data(), &f.best_run, nullptr, nullptr, nullptr));
     return f;
+}
+inline GmmFit gmm_fit(const double *data, int64_t n, int32_t dim, int32_t n_clusters, const std::vector<double> &init_means,
+                      const egx_gmm_config *config = nullptr) {
+    return gmm_fit_with(&egx_gmm_fit, data, n, dim, n_clusters, init_means, config);
+}
+// ... through egx_gmm_fit_wide: rows up to 128 wide (dim <= 128), the same outputs and errors
+inline GmmFit gmm_fit_wide(const double *data, int64_t n, int32_t dim, int32_t n_clusters, const std::vector<double> &init_means,
+                           const egx_gmm_config *config = nullptr) {
+    return gmm_fit_with(&egx_gmm_fit_wide, data, n, dim, n_clusters, init_means, config);
 }
 
 // EGO's infill criterion on fitted models (egx_infill_*, egx_gp.h): the objective the infill optimiser minimises and its
