@@ -24,6 +24,17 @@ void set_error(const std::string &msg);
         }                                                                                \
     } while (0)
 
+// From the run-time correlation kind to a template argument: CALL runs with C_ the kind as a constant expression; an unknown
+// kind makes the enclosing function return EGX_ERR_INVALID_VALUE
+#define EGX_DISPATCH_CORR(corr, CALL)                                                                           \
+    switch (corr) {                                                                                             \
+        case EGX_CORR_SQUARED_EXPONENTIAL: { constexpr int C_ = EGX_CORR_SQUARED_EXPONENTIAL; CALL; } break;    \
+        case EGX_CORR_ABSOLUTE_EXPONENTIAL: { constexpr int C_ = EGX_CORR_ABSOLUTE_EXPONENTIAL; CALL; } break;  \
+        case EGX_CORR_MATERN32: { constexpr int C_ = EGX_CORR_MATERN32; CALL; } break;                          \
+        case EGX_CORR_MATERN52: { constexpr int C_ = EGX_CORR_MATERN52; CALL; } break;                          \
+        default: ::egx::set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;                    \
+    }
+
 // hipMalloc that gives the pool of destroyed handles' resources on the current device back before it reports
 // out-of-memory (gp_host.hip): every device allocation of the library goes through it
 hipError_t dev_malloc_bytes(void **p, size_t bytes);

@@ -11,7 +11,7 @@
 // (no |a|^2+|b|^2-2ab trick: cancellation would break 1e-8 parity for near-duplicate points).
 // HBM traffic is the algorithmic minimum: X read once per tile row/column from L2, R written once.
 #include "egx_internal.h"
-#include "corr_pair.h"  // exp_nonpos, PairAcc, stage_slab, dlog_dc, xgrad_factor (shared with sgp_grad.hip, kernels_pending.hip)
+#include "corr_pair.h"  // the pieces of a pair tile, from staging to the fixed-order sums (shared with sgp_grad.hip, kernels_pending.hip)
 
 #include <algorithm>
 #include <cstdlib>
@@ -24,38 +24,6 @@ namespace egx {
 // changes): the pair accumulators (exponent sum, Matern product) simply run on across the chunks.
 constexpr int kCorrDC = 64;
 
-// 4x4 micro-tile of pair accumulators from two staged slabs: `dn` more dimensions (coef already points at the first one)
-template <int CORR, bool PRE = false, int RI = 4>  // PRE: the slabs were staged with the coefficients applied (hcols == 1);
-                                                    // RI x 4 pairs per lane (rows RI ty + a, columns 4 tx + b)
-__device__ __forceinline__ void tile_pairs_acc(const double *xi, const double *xj, const double *__restrict__ coef,
-                                               int hcols, int dn, int ty, int tx, PairAcc<CORR> (&acc)[RI][4]) {
-    for (int k = 0; k < dn; k++) {
-        double vi[RI], vj[4];
-#pragma unroll
-        for (int a = 0; a < RI; a++) vi[a] = xi[k * 64 + ty * RI + a];
-#pragma unroll
-        for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
-        const double *ck = coef + k * hcols;
-#pragma unroll
-        for (int a = 0; a < RI; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                if (PRE) acc[a][b].add_scaled(vi[a] - vj[b]);
-                else acc[a][b].add(vi[a] - vj[b], ck, hcols);
-            }
-    }
-}
-template <int CORR, bool PRE = false, int RI = 4>
-__device__ __forceinline__ void tile_pairs(const double *xi, const double *xj, const double *__restrict__ coef,
-                                           int hcols, int d, int ty, int tx, double (&r)[RI][4]) {
-    PairAcc<CORR> acc[RI][4];
-    tile_pairs_acc<CORR, PRE, RI>(xi, xj, coef, hcols, d, ty, tx, acc);
-#pragma unroll
-    for (int a = 0; a < RI; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) r[a][b] = acc[a][b].value();
-}
-
 // K1: symmetric training correlation matrix, 64x64 tiles, 128x128-granular lower triangle.
 template <int CORR, bool PRE, int RI>  // 64 x 64 tile per workgroup of 1024 / RI threads, RI x 4 pairs per lane
 __global__ __launch_bounds__(1024 / RI) void k_corr_sym(const double *__restrict__ xT, int64_t ldx, int n, int d,
@@ -64,25 +32,17 @@ __global__ __launch_bounds__(1024 / RI) void k_corr_sym(const double *__restrict
     // 1-D grid over the 128x128 tiles of the LOWER triangle only (4 workgroups per tile): a 2-D grid with an early exit
     // for the strictly-upper tiles launches twice the workgroups and leaves the real ones unevenly spread over the CUs
     constexpr int NT = 1024 / RI;
-    const int t = blockIdx.x >> 2, sub = blockIdx.x & 3;
-    int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (I * (I + 1) / 2 > t) I--;
-    while ((I + 1) * (I + 2) / 2 <= t) I++;
-    const int J = t - I * (I + 1) / 2;
+    const int sub = blockIdx.x & 3;
+    int I, J;
+    tri_tile(blockIdx.x >> 2, I, J);
     const int bi = 2 * I + (sub >> 1), bj = 2 * J + (sub & 1);
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int dc = d < kCorrDC ? d : kCorrDC;
     double *xi = sm, *xj = sm + dc * 64;
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     PairAcc<CORR> acc[RI][4];
-    for (int c0 = 0; c0 < d; c0 += dc) {
-        const int dn = (d - c0 < dc) ? (d - c0) : dc;
-        if (c0) __syncthreads();
-        stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid, PRE ? coef + c0 : nullptr, NT);
-        stage_slab(xj, xT + (int64_t)c0 * ldx, ldx, bj * 64, dn, tid, PRE ? coef + c0 : nullptr, NT);
-        __syncthreads();
-        tile_pairs_acc<CORR, PRE, RI>(xi, xj, coef + (int64_t)c0 * hcols, hcols, dn, ty, tx, acc);
-    }
+    tile_pairs_staged<CORR, PRE, RI>(xi, xj, {xT, ldx, bi * 64}, {xT, ldx, bj * 64}, d, dc, coef, hcols, tid, ty, tx, false, acc,
+                                     PRE ? coef : nullptr, NT);
     double r[RI][4];
 #pragma unroll
     for (int a = 0; a < RI; a++)
@@ -116,11 +76,9 @@ __global__ __launch_bounds__(1024 / RI) void k_corr_sym(const double *__restrict
 template <int CORR>
 __device__ __forceinline__ void corr_sym_srow_body(const double *__restrict__ xs, int64_t ldx, int n, int d, double diag,
                                                    double *__restrict__ M, int64_t ld) {
-    const int t = blockIdx.x >> 2, sub = blockIdx.x & 3;
-    int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (I * (I + 1) / 2 > t) I--;
-    while ((I + 1) * (I + 2) / 2 <= t) I++;
-    const int J = t - I * (I + 1) / 2;
+    const int sub = blockIdx.x & 3;
+    int I, J;
+    tri_tile(blockIdx.x >> 2, I, J);
     const int bi = 2 * I + (sub >> 1), bj = 2 * J + (sub & 1);
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double *xj = sm;  // the 64 column points, k-major
@@ -131,29 +89,7 @@ __device__ __forceinline__ void corr_sym_srow_body(const double *__restrict__ xs
     const int i0 = bi * 64 + wave * 16;
     const double *xr = xs + i0;  // wave-uniform: rows i0 .. i0 + 15 of dimension k at xr[k * ldx + a]
     PairAcc<CORR> acc[16];
-    for (int k = 0; k < d; k++) {
-        const double v = xj[k * 64 + lane];
-        const double4 r0 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx);
-        const double4 r1 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx + 4);
-        const double4 r2 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx + 8);
-        const double4 r3 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx + 12);
-        acc[0].add_scaled(r0.x - v);
-        acc[1].add_scaled(r0.y - v);
-        acc[2].add_scaled(r0.z - v);
-        acc[3].add_scaled(r0.w - v);
-        acc[4].add_scaled(r1.x - v);
-        acc[5].add_scaled(r1.y - v);
-        acc[6].add_scaled(r1.z - v);
-        acc[7].add_scaled(r1.w - v);
-        acc[8].add_scaled(r2.x - v);
-        acc[9].add_scaled(r2.y - v);
-        acc[10].add_scaled(r2.z - v);
-        acc[11].add_scaled(r2.w - v);
-        acc[12].add_scaled(r3.x - v);
-        acc[13].add_scaled(r3.y - v);
-        acc[14].add_scaled(r3.z - v);
-        acc[15].add_scaled(r3.w - v);
-    }
+    for (int k = 0; k < d; k++) srow_step<CORR>(xr + (int64_t)k * ldx, xj[k * 64 + lane], acc);
     const int j = bj * 64 + lane;
 #pragma unroll
     for (int a = 0; a < 16; a++) {
@@ -246,14 +182,8 @@ __global__ __launch_bounds__(256) void k_cross_corr(PosteriorBatchPtrs b, const 
     double *xi = sm, *xj = sm + dc * 64;
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     PairAcc<CORR> acc[4][4];
-    for (int c0 = 0; c0 < d; c0 += dc) {
-        const int dn = (d - c0 < dc) ? (d - c0) : dc;
-        if (c0) __syncthreads();
-        stage_slab(xi, xqT + (int64_t)c0 * ldq, ldq, blockIdx.x * 64, dn, tid, PRE ? coef + c0 : nullptr);
-        stage_slab(xj, xT + (int64_t)c0 * ldx, ldx, blockIdx.y * 64, dn, tid, PRE ? coef + c0 : nullptr);
-        __syncthreads();
-        tile_pairs_acc<CORR, PRE>(xi, xj, coef + (int64_t)c0 * hcols, hcols, dn, ty, tx, acc);
-    }
+    tile_pairs_staged<CORR, PRE>(xi, xj, {xqT, ldq, (int)(blockIdx.x * 64)}, {xT, ldx, (int)(blockIdx.y * 64)}, d, dc, coef, hcols,
+                                 tid, ty, tx, false, acc, PRE ? coef : nullptr);
     double r[4][4];
 #pragma unroll
     for (int a = 0; a < 4; a++)
@@ -347,29 +277,7 @@ __global__ __launch_bounds__(256) void k_predict_mean_srow(PosteriorBatchPtrs b,
     for (int j0 = j_lo + wave * 16; j0 < j_hi; j0 += 64) {
         const double *xr = xs + j0;  // wave-uniform
         PairAcc<CORR> acc[16];
-        for (int k = 0; k < d; k++) {
-            const double v = xq[k * 64 + lane];
-            const double4 r0 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx);
-            const double4 r1 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx + 4);
-            const double4 r2 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx + 8);
-            const double4 r3 = *reinterpret_cast<const double4 *>(xr + (int64_t)k * ldx + 12);
-            acc[0].add_scaled(r0.x - v);
-            acc[1].add_scaled(r0.y - v);
-            acc[2].add_scaled(r0.z - v);
-            acc[3].add_scaled(r0.w - v);
-            acc[4].add_scaled(r1.x - v);
-            acc[5].add_scaled(r1.y - v);
-            acc[6].add_scaled(r1.z - v);
-            acc[7].add_scaled(r1.w - v);
-            acc[8].add_scaled(r2.x - v);
-            acc[9].add_scaled(r2.y - v);
-            acc[10].add_scaled(r2.z - v);
-            acc[11].add_scaled(r2.w - v);
-            acc[12].add_scaled(r3.x - v);
-            acc[13].add_scaled(r3.y - v);
-            acc[14].add_scaled(r3.z - v);
-            acc[15].add_scaled(r3.w - v);
-        }
+        for (int k = 0; k < d; k++) srow_step<CORR>(xr + (int64_t)k * ldx, xq[k * 64 + lane], acc);
         const double4 g0 = *reinterpret_cast<const double4 *>(gamma + j0);
         const double4 g1 = *reinterpret_cast<const double4 *>(gamma + j0 + 4);
         const double4 g2 = *reinterpret_cast<const double4 *>(gamma + j0 + 8);
@@ -410,12 +318,20 @@ constexpr size_t kLdsBytes = 160 * 1024;  // LDS of one CU (gfx950)
 // XAG (d > 64): the lane's own query coordinates come from global memory (L1 / L2) instead of a [d][kXgThreads] LDS
 // image, which together with the training slab would not fit any more; the slab is [d][2^js_shift] training points,
 // 64 wide up to d = 256 and narrower beyond (launch_xgrad picks the widest that fits the 160 KB of LDS)
-template <int CORR, int DK, bool VEC, bool XAG = false>
+// LIST: the COLUMN-LIST form (an infill handle with active coordinates, egx_infill_set_active): out[a][c] for the ncols listed
+// columns c = cols[0 .. ncols) alone, DK of them per pass -- the pair correlation runs over all d coordinates once per DK LISTED
+// columns instead of once per DK columns of d.  Every unlisted column of the lane's d-wide row is written +0.0 (the lane owns
+// its row: the fill and the later stores of the listed columns are the same thread's, in program order), so whatever reads the
+// partial sums downstream sees defined values everywhere.  The two forms differ in which columns a pass holds (cols[c0 + kk]
+// against c0 + kk) and in that fill, nothing else: a listed column accumulates the same __builtin_fma sequence and has the
+// full form's bits (tests/test_gpu_infill_active.py).  cols: distinct, in [0, d), in any order (checked on the host,
+// infill_active.h); without LIST, cols and ncols are not read.
+template <int CORR, int DK, bool VEC, bool XAG = false, bool LIST = false>
 __global__ __launch_bounds__(kXgThreads) void k_xgrad(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq,
                                                       int64_t sq, int64_t ldx, int n, int d, int hcols,
                                                       const double *__restrict__ Wt_all, int64_t ldw, int64_t sW,
                                                       int slabs_per_split, double *__restrict__ out_all, int64_t sout,
-                                                      int m_pad, int js_shift) {
+                                                      int m_pad, int js_shift, const int *__restrict__ cols, int ncols) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
     const double *__restrict__ xT = b.xT[blockIdx.z];
@@ -437,80 +353,17 @@ __global__ __launch_bounds__(kXgThreads) void k_xgrad(PosteriorBatchPtrs b, cons
     int j_hi = j_lo + slabs_per_split * 64;
     if (j_hi > n) j_hi = n;
     double *o = out + ((int64_t)blockIdx.y * m_pad + a) * d;
-    for (int k0 = 0; k0 < d; k0 += DK) {
-        double acc[DK], xr[DK];
-#pragma unroll
-        for (int kk = 0; kk < DK; kk++) {
-            acc[kk] = 0.0;
-            xr[kk] = (k0 + kk < d) ? EGX_XA(k0 + kk) : 0.0;
-        }
-        for (int j0 = j_lo; j0 < j_hi; j0 += JS) {
-            __syncthreads();
-            for (int e = tid; e < d * JS; e += kXgThreads) xj[e] = xT[(int64_t)(e >> jsh) * ldx + j0 + (e & (JS - 1))];
-            __syncthreads();
-            const int jn = (j_hi - j0 < JS) ? (j_hi - j0) : JS;
-            for (int jj = 0; jj < jn; jj++) {
-                PairAcc<CORR> pa;
-                for (int k = 0; k < d; k++) pa.add(EGX_XA(k) - xj[k * JS + jj], cs + k * hcols, hcols);
-                const double wv = VEC ? uniform_ld(Wt + j0 + jj) : Wt[(int64_t)(j0 + jj) * ldw + a];
-                const double rw = pa.value() * wv;
-#pragma unroll
-                for (int kk = 0; kk < DK; kk++)
-                    if (k0 + kk < d)
-                        acc[kk] = __builtin_fma(rw, xgrad_factor<CORR>(xr[kk] - xj[(k0 + kk) * JS + jj],
-                                                                       cs + (k0 + kk) * hcols, hcols), acc[kk]);
-            }
-        }
-#pragma unroll
-        for (int kk = 0; kk < DK; kk++)
-            if (k0 + kk < d) o[k0 + kk] = acc[kk];
-    }
-#undef EGX_XA
-}
-
-// COLUMN-LIST form of k_xgrad (an infill handle with active coordinates, egx_infill_set_active): out[a][c] for the ncols listed
-// columns c = cols[0 .. ncols) alone, DK of them per pass -- the pair correlation runs over all d coordinates once per DK LISTED
-// columns instead of once per DK columns of d.  Every unlisted column of the lane's d-wide row is written +0.0 (the lane owns
-// its row: the fill and the later stores of the listed columns are the same thread's, in program order), so whatever reads the
-// partial sums downstream sees defined values everywhere.  LDS layout, slab width, the split of the training range and the j
-// order are k_xgrad's: a listed column accumulates the same __builtin_fma sequence and has k_xgrad's bits
-// (tests/test_gpu_infill_active.py).  cols: distinct, in [0, d), in any order (checked on the host, infill_active.h).
-template <int CORR, int DK, bool VEC, bool XAG = false>
-__global__ __launch_bounds__(kXgThreads) void k_xgrad_cols(PosteriorBatchPtrs b, const double *__restrict__ xqT_all, int64_t ldq,
-                                                           int64_t sq, int64_t ldx, int n, int d, int hcols,
-                                                           const double *__restrict__ Wt_all, int64_t ldw, int64_t sW,
-                                                           int slabs_per_split, double *__restrict__ out_all, int64_t sout,
-                                                           int m_pad, int js_shift, const int *__restrict__ cols, int ncols) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const double *__restrict__ xqT = xqT_all + (int64_t)blockIdx.z * sq;
-    const double *__restrict__ xT = b.xT[blockIdx.z];
-    const double *__restrict__ coef = b.coef[blockIdx.z];
-    const double *__restrict__ Wt = VEC ? b.gamma[blockIdx.z] : Wt_all + (int64_t)blockIdx.z * sW;
-    double *__restrict__ out = out_all + (int64_t)blockIdx.z * sout;
-    const int jsh = XAG ? js_shift : 6, JS = 1 << jsh;
-    double *xa = sm;                                  // [d][kXgThreads]  (not with XAG)
-    double *xj = sm + (XAG ? 0 : d * kXgThreads);     // [d][JS]
-    double *cs = xj + d * JS;                         // [d * hcols]
-    const int tid = threadIdx.x;
-    const int a = blockIdx.x * kXgThreads + tid;
-    const double *xag = xqT + a;
-#define EGX_XA(k_) (XAG ? xag[(int64_t)(k_) * ldq] : xa[(k_) * kXgThreads + tid])
-    if (!XAG)
-        for (int k = 0; k < d; k++) xa[k * kXgThreads + tid] = xqT[(int64_t)k * ldq + a];
-    for (int e = tid; e < d * hcols; e += kXgThreads) cs[e] = coef[e];
-    const int j_lo = blockIdx.y * slabs_per_split * 64;
-    int j_hi = j_lo + slabs_per_split * 64;
-    if (j_hi > n) j_hi = n;
-    double *o = out + ((int64_t)blockIdx.y * m_pad + a) * d;
-    for (int k = 0; k < d; k++) o[k] = 0.0;
-    for (int c0 = 0; c0 < ncols; c0 += DK) {
+    if (LIST)
+        for (int k = 0; k < d; k++) o[k] = 0.0;
+    const int nc = LIST ? ncols : d;  // the columns to produce, DK per pass
+    for (int c0 = 0; c0 < nc; c0 += DK) {
         double acc[DK], xr[DK];
         int col[DK];
 #pragma unroll
         for (int kk = 0; kk < DK; kk++) {
-            col[kk] = (c0 + kk < ncols) ? cols[c0 + kk] : 0;
+            col[kk] = !LIST ? c0 + kk : ((c0 + kk < nc) ? cols[c0 + kk] : 0);
             acc[kk] = 0.0;
-            xr[kk] = (c0 + kk < ncols) ? EGX_XA(col[kk]) : 0.0;
+            xr[kk] = (c0 + kk < nc) ? EGX_XA(col[kk]) : 0.0;
         }
         for (int j0 = j_lo; j0 < j_hi; j0 += JS) {
             __syncthreads();
@@ -524,14 +377,14 @@ __global__ __launch_bounds__(kXgThreads) void k_xgrad_cols(PosteriorBatchPtrs b,
                 const double rw = pa.value() * wv;
 #pragma unroll
                 for (int kk = 0; kk < DK; kk++)
-                    if (c0 + kk < ncols)
+                    if (c0 + kk < nc)
                         acc[kk] = __builtin_fma(rw, xgrad_factor<CORR>(xr[kk] - xj[col[kk] * JS + jj],
                                                                        cs + col[kk] * hcols, hcols), acc[kk]);
             }
         }
 #pragma unroll
         for (int kk = 0; kk < DK; kk++)
-            if (c0 + kk < ncols) o[col[kk]] = acc[kk];
+            if (c0 + kk < nc) o[col[kk]] = acc[kk];
     }
 #undef EGX_XA
 }
@@ -829,34 +682,13 @@ __global__ __launch_bounds__(256) void k_grad_accum(int64_t ldx, int n, int d, i
 #pragma unroll
     for (int oo = 0; oo < DK; oo++) acc[oo] = 0.0;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-        while (bi * (bi + 1) / 2 > t) bi--;
-        while ((bi + 1) * (bi + 2) / 2 <= t) bi++;
-        const int bj = t - bi * (bi + 1) / 2;
-        // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
+        int bi, bj;
+        tri_tile(t, bi, bj);
+        const SlabSrc si{xT, ldx, bi * 64}, sj{xT, ldx, bj * 64};
+        // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time; PRE: the
+        // inputs come prescaled, nothing is applied while staging)
         PairAcc<CORR> pa[4][4];
-        for (int c0 = 0; c0 < d; c0 += dc) {
-            const int dn = (d - c0 < dc) ? (d - c0) : dc;
-            __syncthreads();  // the previous readers of the slabs are done
-            stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid);
-            stage_slab(xj, xT + (int64_t)c0 * ldx, ldx, bj * 64, dn, tid);
-            __syncthreads();
-            for (int k = 0; k < dn; k++) {
-                double vi[4], vj[4];
-#pragma unroll
-                for (int a = 0; a < 4; a++) vi[a] = xi[k * 64 + ty * 4 + a];
-#pragma unroll
-                for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
-                const double *ck = coef + (int64_t)(c0 + k) * hcols;
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        if (PRE) pa[a][b].add_scaled(vi[a] - vj[b]);
-                        else pa[a][b].add(vi[a] - vj[b], ck, hcols);
-                    }
-            }
-        }
+        tile_pairs_staged<CORR, PRE>(xi, xj, si, sj, d, dc, coef, hcols, tid, ty, tx, true, pa);
         double wp[4][4];  // 2 R_ij (gamma_i gamma_j / sigma2 - Rinv_ij) for i > j inside the matrix, else 0
         {
             double gi[4], gj[4];
@@ -884,11 +716,7 @@ __global__ __launch_bounds__(256) void k_grad_accum(int64_t ldx, int n, int d, i
             // output o <-> input dimension o.  d > dc: the chunk's dimensions are staged again, from slab row 0
             int base = 0;
             if (d > dc) {
-                const int dn = (nout - o0 < DK) ? (nout - o0) : DK;
-                __syncthreads();
-                stage_slab(xi, xT + (int64_t)o0 * ldx, ldx, bi * 64, dn, tid);
-                stage_slab(xj, xT + (int64_t)o0 * ldx, ldx, bj * 64, dn, tid);
-                __syncthreads();
+                stage_pair(xi, xj, si.from(o0), sj.from(o0), (nout - o0 < DK) ? (nout - o0) : DK, tid, true);
                 base = o0;
             }
 #pragma unroll
@@ -916,12 +744,7 @@ __global__ __launch_bounds__(256) void k_grad_accum(int64_t ldx, int n, int d, i
             // KPLS + Matern: output o = theta_o gets a term from every input dimension j
             for (int c0 = 0; c0 < d; c0 += dc) {
                 const int dn = (d - c0 < dc) ? (d - c0) : dc;
-                if (d > dc) {
-                    __syncthreads();
-                    stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid);
-                    stage_slab(xj, xT + (int64_t)c0 * ldx, ldx, bj * 64, dn, tid);
-                    __syncthreads();
-                }
+                if (d > dc) stage_pair(xi, xj, si.from(c0), sj.from(c0), dn, tid, true);
                 for (int k = 0; k < dn; k++) {
                     double ad[4][4];
                     {
@@ -955,17 +778,8 @@ __global__ __launch_bounds__(256) void k_grad_accum(int64_t ldx, int n, int d, i
         }
     }
     // ---- one reduction per workgroup: lanes of a wave (xor shuffles), then the four waves in a fixed order
-    __syncthreads();
-    double *red = sm;  // [4][DK]
-#pragma unroll
-    for (int oo = 0; oo < DK; oo++) {
-        double v = acc[oo];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((tid & 63) == 0) red[(tid >> 6) * DK + oo] = v;
-    }
-    __syncthreads();
+    double v = wg_sum_dk<DK>(acc, sm, tid);
     if (tid < DK && o0 + tid < nout) {
-        double v = ((red[tid] + red[DK + tid]) + red[2 * DK + tid]) + red[3 * DK + tid];
         if (PRE) v *= dlog_f_scaled<CORR>(coef[o0 + tid]);
         gb.part[z][(int64_t)blockIdx.x * nout_pad + o0 + tid] = v;
     }
@@ -973,30 +787,13 @@ __global__ __launch_bounds__(256) void k_grad_accum(int64_t ldx, int n, int d, i
 
 // out[z][o] = sum over the nwg partial vectors, in a fixed order: 256 lanes take every 256th, then a tree in LDS
 __global__ __launch_bounds__(256) void k_grad_reduce(int nwg, int nout, int nout_pad, GradBatch gb) {
-    __shared__ double red[256];
     const int o = blockIdx.x, z = blockIdx.y, tid = threadIdx.x;
-    const double *part = gb.part[z];
-    double v = 0.0;
-    for (int b = tid; b < nwg; b += 256) v += part[(int64_t)b * nout_pad + o];
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) gb.out[z][o] = red[0];
+    const double v = sum_partial_vectors(gb.part[z], nwg, nout_pad, o, tid);
+    if (tid == 0) gb.out[z][o] = v;
 }
 
 // =============================================================================================
-#define EGX_DISPATCH_CORR(corr, CALL)                                                        \
-    switch (corr) {                                                                          \
-        case EGX_CORR_SQUARED_EXPONENTIAL: { constexpr int C_ = EGX_CORR_SQUARED_EXPONENTIAL; CALL; } break;   \
-        case EGX_CORR_ABSOLUTE_EXPONENTIAL: { constexpr int C_ = EGX_CORR_ABSOLUTE_EXPONENTIAL; CALL; } break; \
-        case EGX_CORR_MATERN32: { constexpr int C_ = EGX_CORR_MATERN32; CALL; } break;       \
-        case EGX_CORR_MATERN52: { constexpr int C_ = EGX_CORR_MATERN52; CALL; } break;       \
-        default: set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;        \
-    }
-
+// (EGX_DISPATCH_CORR, the switch from the run-time correlation kind to the template argument C_: egx_internal.h)
 int launch_corr_sym(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, int d, const double *coef,
                     int hcols, double nugget, double *M, int64_t ld, int n_pad, double *xs_scratch) {
     const int nt2 = n_pad / 128;  // n_pad is a multiple of 128
@@ -1123,35 +920,27 @@ int launch_xgrad(hipStream_t s, int corr, const PosteriorBatch &pb, const double
                   " coefficient columns do not fit the 160 KB of LDS (d * (hcols + 1) <= 20480)");
         return EGX_ERR_UNSUPPORTED;
     }
-#define EGX_XG1(C_, DK_, VEC_, XAG_)                                                                                         \
+#define EGX_XG1(C_, DK_, VEC_, XAG_, LIST_)                                                                                  \
     {                                                                                                                        \
         if (lds > 65536)                                                                                                     \
-            EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xgrad<C_, DK_, VEC_, XAG_>),                 \
+            EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xgrad<C_, DK_, VEC_, XAG_, LIST_>),          \
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hipLaunchKernelGGL((k_xgrad<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, pb.ptrs, xqT, ldq, pb.sq, ldx,    \
-                           n, d, hcols, Wt, ldw, pb.sW, per, out, pb.sout, m_pad, js_shift);                                 \
+        hipLaunchKernelGGL((k_xgrad<C_, DK_, VEC_, XAG_, LIST_>), grid, dim3(kXgThreads), lds, s, pb.ptrs, xqT, ldq, pb.sq,  \
+                           ldx, n, d, hcols, Wt, ldw, pb.sW, per, out, pb.sout, m_pad, js_shift, cols, ncols);              \
     }
 #define EGX_XG(C_, DK_)                                    \
     if (xag) {                                             \
-        if (vec) EGX_XG1(C_, 32, true, true)               \
-        else EGX_XG1(C_, 32, false, true)                  \
-    } else if (vec) EGX_XG1(C_, DK_, true, false)          \
-    else EGX_XG1(C_, DK_, false, false)
-    // the column-list form (cols: ncols distinct device indices in [0, d)): its own kernel, its pass width by the LIST's length
-#define EGX_XGC1(C_, DK_, VEC_, XAG_)                                                                                        \
-    {                                                                                                                        \
-        if (lds > 65536)                                                                                                     \
-            EGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xgrad_cols<C_, DK_, VEC_, XAG_>),            \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hipLaunchKernelGGL((k_xgrad_cols<C_, DK_, VEC_, XAG_>), grid, dim3(kXgThreads), lds, s, pb.ptrs, xqT, ldq, pb.sq,    \
-                           ldx, n, d, hcols, Wt, ldw, pb.sW, per, out, pb.sout, m_pad, js_shift, cols, ncols);              \
-    }
+        if (vec) EGX_XG1(C_, 32, true, true, false)        \
+        else EGX_XG1(C_, 32, false, true, false)           \
+    } else if (vec) EGX_XG1(C_, DK_, true, false, false)   \
+    else EGX_XG1(C_, DK_, false, false, false)
+    // the column-list form (cols: ncols distinct device indices in [0, d)): the LIST instances, the pass width by the LIST's length
 #define EGX_XGC(C_, DK_)                                   \
     if (xag) {                                             \
-        if (vec) EGX_XGC1(C_, DK_, true, true)             \
-        else EGX_XGC1(C_, DK_, false, true)                \
-    } else if (vec) EGX_XGC1(C_, DK_, true, false)         \
-    else EGX_XGC1(C_, DK_, false, false)
+        if (vec) EGX_XG1(C_, DK_, true, true, true)        \
+        else EGX_XG1(C_, DK_, false, true, true)           \
+    } else if (vec) EGX_XG1(C_, DK_, true, false, true)    \
+    else EGX_XG1(C_, DK_, false, false, true)
     if (cols) {
         if (ncols < 1 || ncols > d) {
             set_error("x-gradients: a column list of " + std::to_string(ncols) + " entries for " + std::to_string(d) + " inputs");
@@ -1173,7 +962,6 @@ int launch_xgrad(hipStream_t s, int corr, const PosteriorBatch &pb, const double
     }
 #undef EGX_XG1
 #undef EGX_XG
-#undef EGX_XGC1
 #undef EGX_XGC
     EGX_HIP_CHECK(hipGetLastError());
     return EGX_SUCCESS;
@@ -1364,23 +1152,14 @@ __global__ __launch_bounds__(256) void k_cov_assemble(const double *__restrict__
                                                       int64_t ldg, int m, double sigma2, double tau, double *__restrict__ S,
                                                       int64_t lds) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int t = blockIdx.x;
-    int bx = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (bx * (bx + 1) / 2 > t) bx--;
-    while ((bx + 1) * (bx + 2) / 2 <= t) bx++;
-    const int by = t - bx * (bx + 1) / 2;
+    int bx, by;
+    tri_tile(blockIdx.x, bx, by);
     const int dc = d < kCorrDC ? d : kCorrDC;
     double *xi = sm, *xj = sm + dc * 64;
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     PairAcc<CORR> acc[4][4];
-    for (int c0 = 0; c0 < d; c0 += dc) {
-        const int dn = (d - c0 < dc) ? (d - c0) : dc;
-        if (c0) __syncthreads();
-        stage_slab(xi, xqT + (int64_t)c0 * ldq, ldq, bx * 64, dn, tid, PRE ? coef + c0 : nullptr);
-        stage_slab(xj, xqT + (int64_t)c0 * ldq, ldq, by * 64, dn, tid, PRE ? coef + c0 : nullptr);
-        __syncthreads();
-        tile_pairs_acc<CORR, PRE>(xi, xj, coef + (int64_t)c0 * hcols, hcols, dn, ty, tx, acc);
-    }
+    tile_pairs_staged<CORR, PRE>(xi, xj, {xqT, ldq, bx * 64}, {xqT, ldq, by * 64}, d, dc, coef, hcols, tid, ty, tx, false, acc,
+                                 PRE ? coef : nullptr);
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll

@@ -211,15 +211,6 @@ int pending_splits(int nz) {  // a function of the model and q alone: ~512 workg
     return (slabs + per - 1) / per;
 }
 
-#define EGX_PENDING_CORR(corr, CALL)                                                                                         \
-    switch (corr) {                                                                                                          \
-        case EGX_CORR_SQUARED_EXPONENTIAL: { constexpr int C_ = EGX_CORR_SQUARED_EXPONENTIAL; CALL; } break;                 \
-        case EGX_CORR_ABSOLUTE_EXPONENTIAL: { constexpr int C_ = EGX_CORR_ABSOLUTE_EXPONENTIAL; CALL; } break;               \
-        case EGX_CORR_MATERN32: { constexpr int C_ = EGX_CORR_MATERN32; CALL; } break;                                       \
-        case EGX_CORR_MATERN52: { constexpr int C_ = EGX_CORR_MATERN52; CALL; } break;                                       \
-        default: set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;                                        \
-    }
-
 // outc: nsplit x kTile x q, outg: nsplit x kTile x q x d partial sums (outg == nullptr: values only); nz = n + q points in ZT
 int launch_pending_cross(hipStream_t s, int corr, const double *xqT, const double *ZT, int64_t ldz, int nz, int d, const double *coef,
                          int hcols, const double *W, int q, int nsplit, double *outc, double *outg) {
@@ -258,7 +249,7 @@ int launch_pending_cross(hipStream_t s, int corr, const double *xqT, const doubl
     // its bits do not depend on the width of its pass)
     for (int v0 = 0; v0 < q; v0 += kPendingQV) {
         const int cols = q - v0 < kPendingQV ? q - v0 : kPendingQV;
-        EGX_PENDING_CORR(corr, EGX_PC(C_));
+        EGX_DISPATCH_CORR(corr, EGX_PC(C_));
     }
 #undef EGX_PC1
 #undef EGX_PC2

@@ -48,52 +48,17 @@ __global__ __launch_bounds__(256) void k_sgp_grad_rect(const double *__restrict_
     for (int oo = 0; oo < DK; oo++) acc[oo] = 0.0;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int bi = t / ntc, bj = t - bi * ntc;
+        const SlabSrc si{xT, ldx, bi * 64}, sj{zT, ldz, bj * 64};
         // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
         PairAcc<CORR> pa[4][4];
-        for (int c0 = 0; c0 < d; c0 += dc) {
-            const int dn = (d - c0 < dc) ? (d - c0) : dc;
-            __syncthreads();  // the previous readers of the slabs are done
-            stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid);
-            stage_slab(xj, zT + (int64_t)c0 * ldz, ldz, bj * 64, dn, tid);
-            __syncthreads();
-            for (int k = 0; k < dn; k++) {
-                double vi[4], vj[4];
-#pragma unroll
-                for (int a = 0; a < 4; a++) vi[a] = xi[k * 64 + ty * 4 + a];
-#pragma unroll
-                for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
-                const double *ck = coef + (c0 + k);
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) pa[a][b].add(vi[a] - vj[b], ck, 1);
-            }
-        }
+        tile_pairs_staged<CORR>(xi, xj, si, sj, d, dc, coef, 1, tid, ty, tx, true, pa);
         double wp[4][4];  // T[t, i] R[t, i] inside the n x nz rectangle, else 0
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-            const int i = bi * 64 + ty * 4 + a;
-            const double *trow = T + (int64_t)i * ldt + bj * 64 + tx * 4;
-            const double2 t01 = *reinterpret_cast<const double2 *>(trow);
-            const double2 t23 = *reinterpret_cast<const double2 *>(trow + 2);
-            const double tv[4] = {t01.x, t01.y, t23.x, t23.y};
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int j = bj * 64 + tx * 4 + b;
-                wp[a][b] = (i < n && j < nz) ? pa[a][b].value() * tv[b] : 0.0;
-            }
-        }
+        rect_weights<CORR>(pa, T, ldt, bi * 64, bj * 64, n, nz, ty, tx, wp);
         // ---- pass 2: this workgroup's outputs o0 .. o0 + DK - 1: o < d <-> input dimension o, o == d the plain sum.
-        // d > dc: the chunk's dimensions are staged again, from slab row 0
+        // d > dc: the chunk's dimensions are staged again, from slab row 0 (none where the plain sum is alone in its chunk)
         int base = 0;
         if (d > dc) {
-            const int dn = (d - o0 < DK) ? (d - o0) : DK;
-            __syncthreads();
-            if (dn > 0) {
-                stage_slab(xi, xT + (int64_t)o0 * ldx, ldx, bi * 64, dn, tid);
-                stage_slab(xj, zT + (int64_t)o0 * ldz, ldz, bj * 64, dn, tid);
-            }
-            __syncthreads();
+            stage_pair(xi, xj, si.from(o0), sj.from(o0), (d - o0 < DK) ? (d - o0) : DK, tid, true);
             base = o0;
         }
 #pragma unroll
@@ -123,33 +88,15 @@ __global__ __launch_bounds__(256) void k_sgp_grad_rect(const double *__restrict_
         }
     }
     // ---- one reduction per workgroup: lanes of a wave (xor shuffles), then the four waves in a fixed order
-    __syncthreads();
-    double *red = sm;  // [4][DK]
-#pragma unroll
-    for (int oo = 0; oo < DK; oo++) {
-        double v = acc[oo];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((tid & 63) == 0) red[(tid >> 6) * DK + oo] = v;
-    }
-    __syncthreads();
-    if (tid < DK && o0 + tid < nout)
-        part[(int64_t)blockIdx.x * nout_pad + o0 + tid] = ((red[tid] + red[DK + tid]) + red[2 * DK + tid]) + red[3 * DK + tid];
+    const double v = wg_sum_dk<DK>(acc, sm, tid);
+    if (tid < DK && o0 + tid < nout) part[(int64_t)blockIdx.x * nout_pad + o0 + tid] = v;
 }
 
 // out[o] = sum over the nwg partial vectors, in a fixed order: 256 lanes take every 256th, then a tree in LDS
 __global__ __launch_bounds__(256) void k_sgp_grad_reduce(const double *__restrict__ part, int nwg, int nout_pad,
                                                          double *__restrict__ out) {
-    __shared__ double red[256];
-    const int o = blockIdx.x, tid = threadIdx.x;
-    double v = 0.0;
-    for (int b = tid; b < nwg; b += 256) v += part[(int64_t)b * nout_pad + o];
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) out[o] = red[0];
+    const double v = sum_partial_vectors(part, nwg, nout_pad, blockIdx.x, threadIdx.x);
+    if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
 // The per-point quantities, t < n_pad (zeros beyond n): alpha, beta, q, sqrt(r), p
@@ -262,13 +209,7 @@ int launch_grad_rect(hipStream_t s, int corr, const double *xT, int64_t ldx, int
     if (dk == 8) EGX_RECT(C_, 8);       \
     else if (dk == 16) EGX_RECT(C_, 16); \
     else EGX_RECT(C_, 32)
-    switch (corr) {
-        case EGX_CORR_SQUARED_EXPONENTIAL: EGX_RECT_DK(EGX_CORR_SQUARED_EXPONENTIAL); break;
-        case EGX_CORR_ABSOLUTE_EXPONENTIAL: EGX_RECT_DK(EGX_CORR_ABSOLUTE_EXPONENTIAL); break;
-        case EGX_CORR_MATERN32: EGX_RECT_DK(EGX_CORR_MATERN32); break;
-        case EGX_CORR_MATERN52: EGX_RECT_DK(EGX_CORR_MATERN52); break;
-        default: set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;
-    }
+    EGX_DISPATCH_CORR(corr, EGX_RECT_DK(C_));
 #undef EGX_RECT_DK
 #undef EGX_RECT
     hipLaunchKernelGGL(k_sgp_grad_reduce, dim3((unsigned)nout), dim3(256), 0, s, part, nwg, nout_pad, out);
@@ -318,50 +259,17 @@ __global__ __launch_bounds__(256) void k_sgp_grad_cols(const double *__restrict_
 #pragma unroll
         for (int oo = 0; oo < DK; oo++) acc[b][oo] = 0.0;
     for (int bi = r0; bi < r1; bi++) {
+        const SlabSrc si{xT, ldx, bi * 64}, sj{zT, ldz, bj * 64};
         // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
         PairAcc<CORR> pa[4][4];
-        for (int c0 = 0; c0 < d; c0 += dc) {
-            const int dn = (d - c0 < dc) ? (d - c0) : dc;
-            __syncthreads();  // the previous readers of the slabs are done
-            stage_slab(xi, xT + (int64_t)c0 * ldx, ldx, bi * 64, dn, tid);
-            stage_slab(xj, zT + (int64_t)c0 * ldz, ldz, bj * 64, dn, tid);
-            __syncthreads();
-            for (int k = 0; k < dn; k++) {
-                double vi[4], vj[4];
-#pragma unroll
-                for (int a = 0; a < 4; a++) vi[a] = xi[k * 64 + ty * 4 + a];
-#pragma unroll
-                for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
-                const double *ck = coef + (c0 + k);
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) pa[a][b].add(vi[a] - vj[b], ck, 1);
-            }
-        }
+        tile_pairs_staged<CORR>(xi, xj, si, sj, d, dc, coef, 1, tid, ty, tx, true, pa);
         double wp[4][4];  // T[i, j] R[i, j] inside the n x nz rectangle, else 0
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-            const int i = bi * 64 + ty * 4 + a;
-            const double *trow = T + (int64_t)i * ldt + bj * 64 + tx * 4;
-            const double2 t01 = *reinterpret_cast<const double2 *>(trow);
-            const double2 t23 = *reinterpret_cast<const double2 *>(trow + 2);
-            const double tv[4] = {t01.x, t01.y, t23.x, t23.y};
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int j = bj * 64 + tx * 4 + b;
-                wp[a][b] = (i < n && j < nz) ? pa[a][b].value() * tv[b] : 0.0;
-            }
-        }
+        rect_weights<CORR>(pa, T, ldt, bi * 64, bj * 64, n, nz, ty, tx, wp);
         // ---- pass 2: output dimensions o0 .. o0 + DK - 1 of this lane's four columns.  d > dc: they are staged again, from
         // slab row 0
         int base = 0;
         if (d > dc) {
-            const int dn = (d - o0 < DK) ? (d - o0) : DK;
-            __syncthreads();
-            stage_slab(xi, xT + (int64_t)o0 * ldx, ldx, bi * 64, dn, tid);
-            stage_slab(xj, zT + (int64_t)o0 * ldz, ldz, bj * 64, dn, tid);
-            __syncthreads();
+            stage_pair(xi, xj, si.from(o0), sj.from(o0), (d - o0 < DK) ? (d - o0) : DK, tid, true);
             base = o0;
         }
 #pragma unroll
@@ -451,13 +359,7 @@ int launch_grad_cols(hipStream_t s, int corr, const double *xT, int64_t ldx, int
     if (dk == 4) EGX_COLS(C_, 4);      \
     else if (dk == 8) EGX_COLS(C_, 8); \
     else EGX_COLS(C_, 16)
-    switch (corr) {
-        case EGX_CORR_SQUARED_EXPONENTIAL: EGX_COLS_DK(EGX_CORR_SQUARED_EXPONENTIAL); break;
-        case EGX_CORR_ABSOLUTE_EXPONENTIAL: EGX_COLS_DK(EGX_CORR_ABSOLUTE_EXPONENTIAL); break;
-        case EGX_CORR_MATERN32: EGX_COLS_DK(EGX_CORR_MATERN32); break;
-        case EGX_CORR_MATERN52: EGX_COLS_DK(EGX_CORR_MATERN52); break;
-        default: set_error("unknown correlation kind"); return EGX_ERR_INVALID_VALUE;
-    }
+    EGX_DISPATCH_CORR(corr, EGX_COLS_DK(C_));
 #undef EGX_COLS_DK
 #undef EGX_COLS
     const int64_t count = (int64_t)nz * d;

@@ -1036,7 +1036,7 @@ int32_t egx_infill_optimize_batch(egx_infill *h, const egx_infill_batch_config *
  * columns active[0 .. n_active) -- on every kind of handle (lone dense models, mixtures, sparse experts, typed models, pending
  * points); a non-finite value in a compact row gives +inf and a zero gradient for that point only.  Rows are expanded and
  * columns gathered on the host (csrc/infill_active.h); the experts' x-gradient contractions compute the listed columns alone
- * (k_xgrad_cols, csrc/kernels_corr.hip).  Without an activity every entry point returns the bits it returned before. */
+ * (k_xgrad<LIST>, csrc/kernels_corr.hip).  Without an activity every entry point returns the bits it returned before. */
 int32_t egx_infill_set_active(egx_infill *h, const int32_t *active /*n_active*/, int32_t n_active, const double *x_base /*d*/);
 int32_t egx_infill_clear_active(egx_infill *h);
 /* *n_active (0: no activity); optionally the indices and the base point (each d long at most, or NULL) */

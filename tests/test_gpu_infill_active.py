@@ -1,4 +1,4 @@
-"""Active coordinates on the infill handle (egx_infill_set_active; csrc/infill_active.h, k_xgrad_cols in kernels_corr.hip) and
+"""Active coordinates on the infill handle (egx_infill_set_active; csrc/infill_active.h, k_xgrad<LIST> in kernels_corr.hip) and
 CoEGO on top of them (`Egor(coego_n_coop=k)`).  The contract is bitwise: a compact call returns the full-width call's value at
 the expanded rows and that call's listed gradient columns, on every kind of handle.  One case goes against the independent
 oracles (oracle.gp_oracle on the handle's fitted state, tests/infill_oracle.py) at the expanded points."""
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 N = 130                      # three 64-row slabs, the last one partial; more than one split of the training range
 DIMS = [9, 33, 64, 65, 72]   # both pass widths of k_xgrad with more than one pass; 64 | 65: the LDS image of the queries ends
-CHUNKS = (8, 16, 32)         # k_xgrad_cols' pass widths, chosen by the LIST's length: one below, at, one above each
+CHUNKS = (8, 16, 32)         # k_xgrad<LIST>'s pass widths, chosen by the LIST's length: one below, at, one above each
 GKEYS = ("grad_mean", "grad_var")
 
 

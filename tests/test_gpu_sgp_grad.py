@@ -22,6 +22,8 @@ SHAPES = {
     "B-pinned-likelihood-shape": (700, 40, 3, T3),
     "C-z_pad-256-two-chol-blocks": (300, 130, 4, 1.5 * np.array([1.3, 0.8, 1.1, 1.3])),
     "D-second-staging-chunk": (200, 20, 65, np.full(65, 0.25)),
+    "E-sixteen-wide-output-chunk": (130, 70, 9, np.full(9, 0.8)),
+    "F-sum-output-alone-in-its-chunk": (200, 20, 96, np.full(96, 0.05)),
 }
 
 

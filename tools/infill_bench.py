@@ -55,7 +55,7 @@ profiles/infill_pending_bench.txt; no threshold is set.
 --active times ACTIVE COORDINATES (egx_infill_set_active; CoEGO) on one handle in one process: an objective and two constraint
 models, squared exponential, d = 32, 64, 128, 256 at n = 500 and n = 2000; one evaluation of 20 points with gradients, FULL
 width (d columns: what the handle launches without an activity, k_xgrad) against an ACTIVITY of a = ceil(d / 5) shuffled columns
-(compact rows, k_xgrad_cols: the pair correlation once per pass of listed columns), in both ways the optimisers evaluate: the
+(compact rows, k_xgrad<LIST>: the pair correlation once per pass of listed columns), in both ways the optimisers evaluate: the
 constraints folded into the objective (value_and_grad, six contractions per tile) and as mean constraints (constraints(x,
 grad=True), four).  Legs alternated (full, active, full again: the two full runs show the spread), 3 warm-ups, medians with
 quartiles, written to profiles/infill_active_bench.txt; no threshold is set.
