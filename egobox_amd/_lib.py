@@ -239,6 +239,8 @@ SIGNATURES = [
                                               c_double_p, c_int32_p]),
     ("egx_sgp_set_inducings", C.c_int32, [C.c_void_p, c_double_p]),
     ("egx_sgp_get_inducings", C.c_int32, [C.c_void_p, c_double_p]),
+    ("egx_sgp_set_w_star", C.c_int32, [C.c_void_p, c_double_p, C.c_int64]),
+    ("egx_sgp_get_w_star", C.c_int32, [C.c_void_p, c_double_p, c_int64_p]),
     ("egx_sgp_fit_lbfgs_z", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int32, C.c_double,
                                         C.c_int64, c_double_p, c_double_p, C.c_int64, c_int64_p]),
     ("egx_sgp_predict", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),

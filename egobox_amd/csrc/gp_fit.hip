@@ -5,6 +5,7 @@
 // driver is LOCK-STEP: multistart::run over one machine per start, a round's points in one evaluation call.  The box, the
 // budget, the machines, the reduction and the winner are fit_starts.h's; this file holds only what touches a handle.
 #include "gp_handle.h"
+#include "kpls_coef.h"
 #include "grad_runs.h"
 
 using namespace egx;
@@ -218,28 +219,8 @@ static bool grad_entry(const EvalResult &res, int hcols, const std::vector<doubl
 // dL/dtheta (h) from the kernel's sums over the coefficients (nout): the chain rule of make_coef
 static void grad_chain_rule(const egx_gp *gp, const double *gsum, int hcols, const std::vector<double> &coef,
                             const std::vector<double> &thfull, double *grad) {
-    const int d = gp->d, h = gp->h;
-    const double ln10 = std::log(10.0);
-    if (!gp->has_w || hcols > 1) {
-        for (int k = 0; k < h; k++) grad[k] = gsum[k] / ln10;  // w = I (c = theta), or KPLS + Matern (outputs are per theta)
-        return;
-    }
-    // KPLS with a collapsed per-dimension coefficient c_j (make_coef): chain rule dc_j / dtheta_l
-    //   sq-exp : c_j = sqrt(sum_l (theta_l w_jl)^2)  ->  theta_l w_jl^2 / c_j     (correlation_models.rs:97-98)
-    //   abs-exp: c_j = sum_l theta_l |w_jl|           ->  |w_jl|                   (:191)
-    const double *wm = gp->w_star.data();
-    for (int l = 0; l < h; l++) {
-        double sacc = 0.0;
-        for (int j = 0; j < d; j++) {
-            const double wjl = wm[(size_t)j * h + l], pk = gsum[j] / ln10;
-            if (gp->corr == EGX_CORR_SQUARED_EXPONENTIAL) {
-                if (coef[j] > 0.0) sacc += pk * thfull[l] * wjl * wjl / coef[j];
-            } else {
-                sacc += pk * std::fabs(wjl);
-            }
-        }
-        grad[l] = sacc;
-    }
+    kpls::chain_rule(gp->corr, gp->d, gp->h, gp->has_w ? gp->w_star.data() : nullptr, hcols, coef.data(), thfull.data(), gsum,
+                     std::log(10.0), grad);  // kpls_coef.h
 }
 
 // likelihood + gradient of the rows of thetas (k x theta_len) that `src` hands out: lkh[c], grad[c * h ..], status[c].  Caller

@@ -4,6 +4,7 @@
 // parts run in the HIP kernels of kernels_corr.hip / kernels_chol.hip.  Predictions: gp_predict.hip; optimiser drivers
 // and the theta-gradient: gp_fit.hip; sparse GP: sgp_host.hip.  There is no CPU fallback.
 #include "gp_handle.h"
+#include "kpls_coef.h"
 #include "resource_pool.h"
 
 namespace egx {
@@ -312,35 +313,7 @@ int make_coef(const egx_gp *gp, const double *theta, int64_t theta_len, std::vec
     std::vector<double> th(gp->h);
     for (int l = 0; l < gp->h; l++) th[l] = theta[theta_len == 1 ? 0 : l];
     if (theta_full) *theta_full = th;
-    const int d = gp->d, h = gp->h;
-    if (!gp->has_w) {
-        hcols = 1;
-        coef.assign(th.begin(), th.end());  // h == d
-        return EGX_SUCCESS;
-    }
-    const double *w = gp->w_star.data();
-    if (gp->corr == EGX_CORR_SQUARED_EXPONENTIAL) {
-        hcols = 1;
-        coef.assign(d, 0.0);
-        for (int j = 0; j < d; j++) {
-            double s = 0.0;
-            for (int l = 0; l < h; l++) s += (th[l] * w[j * h + l]) * (th[l] * w[j * h + l]);
-            coef[j] = std::sqrt(s);
-        }
-    } else if (gp->corr == EGX_CORR_ABSOLUTE_EXPONENTIAL) {
-        hcols = 1;
-        coef.assign(d, 0.0);
-        for (int j = 0; j < d; j++) {
-            double s = 0.0;
-            for (int l = 0; l < h; l++) s += std::fabs(w[j * h + l]) * th[l];
-            coef[j] = s;
-        }
-    } else {
-        hcols = h;
-        coef.assign((size_t)d * h, 0.0);
-        for (int j = 0; j < d; j++)
-            for (int l = 0; l < h; l++) coef[j * h + l] = th[l] * std::fabs(w[j * h + l]);
-    }
+    hcols = kpls::coef_table(gp->corr, gp->d, gp->h, gp->has_w ? gp->w_star.data() : nullptr, th.data(), coef);  // kpls_coef.h
     return EGX_SUCCESS;
 }
 

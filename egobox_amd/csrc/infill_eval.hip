@@ -105,11 +105,18 @@ int check_shapes(egx_infill *h) {
             return fail(EGX_ERR_INVALID_VALUE, "infill: " + infill_who(h, (int)e) + " lives on device " + std::to_string(h->models[e].device()) +
                 ", " + infill_who(h, 0) + " on device " + std::to_string(h->device));
     }
-    // the x-gradient contraction of a sparse expert stages d * (hcols + 5) doubles, hcols = 1 (sgp_predict.hip)
-    for (size_t e = 0; e < h->models.size(); e++)
-        if (h->models[e].sparse() && (int64_t)h->d * 6 > 20480)
+    // the x-gradient contraction of a sparse expert stages d * (hcols + 5) doubles; hcols = 1 unless it carries KPLS weights under
+    // a Matern correlation (sgp_predict.hip)
+    for (size_t e = 0; e < h->models.size(); e++) {
+        if (!h->models[e].sparse()) continue;
+        const int hc = h->models[e].sg->hcols;
+        if (hc == 1 && (int64_t)h->d * 6 > 20480)
             return fail(EGX_ERR_UNSUPPORTED, "infill: " + infill_who(h, (int)e) + ": the x-gradients of a sparse model need 6 d <= 20480 (d " +
                 std::to_string(h->d) + ")");
+        if ((int64_t)h->d * (hc + 5) > 20480)
+            return fail(EGX_ERR_UNSUPPORTED, "infill: " + infill_who(h, (int)e) + ": the x-gradients of a sparse KPLS model need d (hcols + 5) <= 20480 (d " +
+                std::to_string(h->d) + ", hcols " + std::to_string(hc) + ")");
+    }
     return EGX_SUCCESS;
 }
 
@@ -203,15 +210,15 @@ int sgp_expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, co
     const int ncols = h->use_cols ? (int)h->active.size() : 0;
     if (mean_only) flag = nullptr;
     EGX_RC(launch_infill_prepare(st, h->xraw.p + (size_t)t0 * d, mt, d, h->ident.p, h->xqT.p, flag));
-    EGX_RC(launch_predict_mean(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->vec.p, h->racc.p, msplit));
+    EGX_RC(launch_predict_mean(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, g->hcols, g->vec.p, h->racc.p, msplit));
     if (mean_only) {
         EGX_RC(launch_infill_sgp_finish(st, h->racc.p, msplit, nullptr, nullptr, g->sigma2, g->noise, 0, o.mean, nullptr));
         if (!want_g) return EGX_SUCCESS;
-        EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p, cols,
+        EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, g->vec.p, 0, 1, nsplit, h->out_y.p, cols,
                             ncols));
         return launch_infill_sgp_xgrad_finish(st, h->out_y.p, nullptr, nsplit, d, nullptr, nullptr, g->sigma2, 0, 0.0, o.gmean, nullptr);
     }
-    EGX_RC(launch_cross_corr(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, h->RT.p, z_pad));
+    EGX_RC(launch_cross_corr(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, z_pad, d, g->coef.p, g->hcols, h->RT.p, z_pad));
     EGX_RC(launch_trsm_rows(st, g->Kz.p, z_pad, z_pad, g->dinv_z.p, h->RT.p, z_pad, kTile));  // a~ = C_z^-1 r
     EGX_RC(launch_row_reduce(st, h->RT.p, z_pad, kTile, nz, nullptr, 0, 0, h->s0.p, nullptr));
     if (want_g) EGX_RC(sgp_launch_scale_copy(st, h->RT.p, vfe ? -1.0 : 1.0, (int64_t)blk, h->sE.p));  // E = -s a~: the GEMMs subtract
@@ -223,9 +230,9 @@ int sgp_expert_tile(egx_infill *h, hipStream_t st, int j, int64_t t0, int mt, co
     EGX_RC(launch_gemm_nt_sub(st, h->sE.p, z_pad, h->RT.p, z_pad, g->Wa.p, z_pad, kTile, z_pad, z_pad, 0, 0));
     EGX_HIP_CHECK(hipMemsetAsync(h->Wt.p, 0, sizeof(double) * blk, st));
     EGX_RC(launch_gemm_nt_sub(st, h->Wt.p, kTile, g->Wz.p, z_pad, h->sE.p, z_pad, z_pad, kTile, z_pad, 0, 1));
-    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit, h->out_y.p, cols,
+    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, g->vec.p, 0, 1, nsplit, h->out_y.p, cols,
                         ncols));
-    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, 1, h->Wt.p, kTile, 0, nsplit,
+    EGX_RC(launch_xgrad(st, g->corr, h->xqT.p, kTile, kTile, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, h->Wt.p, kTile, 0, nsplit,
                         h->out_v.p, cols, ncols));
     return launch_infill_sgp_xgrad_finish(st, h->out_y.p, h->out_v.p, nsplit, d, h->s0.p, h->s1.p, g->sigma2, vfe,
                                           (vfe ? -2.0 : 2.0) * g->sigma2, o.gmean, o.gvar);

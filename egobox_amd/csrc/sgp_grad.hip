@@ -22,6 +22,7 @@
 // The gradient in the inducing points (sgp_grad_tail_z, k_sgp_grad_cols) contracts the same T^T and S^ once more.
 #include "sgp_handle.h"
 #include "corr_pair.h"
+#include "kpls_coef.h"
 
 #include <algorithm>
 #include <cmath>
@@ -33,11 +34,16 @@ namespace {
 constexpr int kRectDC = 64;       // input dimensions staged per pass (2 x 64 x 64 doubles = 64 KB of LDS)
 constexpr int kRectMaxWG = 2048;  // workgroups (partial vectors) per output chunk
 
-template <int CORR, int DK>
+// MULTI (KPLS under a Matern correlation): coef is d x hcols (c_kl = theta_l |w_kl|) and the outputs are per
+// theta, not per input: output o < hcols is sum_pairs wp sum_k |w_ko| dlog_dc(c_ko, |x_ik - z_jk|), output hcols the plain sum.
+// Every theta output walks all d dimensions, so for d > kRectDC pass 2 stages the slabs again chunk by chunk.  coef and |w| are
+// read at wave-uniform addresses.  MULTI == false is the kernel as it was: hcols and wabs are not read.
+template <int CORR, int DK, bool MULTI = false>
 __global__ __launch_bounds__(256) void k_sgp_grad_rect(const double *__restrict__ xT, int64_t ldx, int n,
                                                        const double *__restrict__ zT, int64_t ldz, int nz, int d,
                                                        const double *__restrict__ coef, const double *__restrict__ T, int64_t ldt,
-                                                       int ntc, int ntiles, int nout, int nout_pad, double *__restrict__ part) {
+                                                       int ntc, int ntiles, int nout, int nout_pad, double *__restrict__ part,
+                                                       int hcols, const double *__restrict__ wabs) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int dc = d < kRectDC ? d : kRectDC;
     double *xi = sm, *xj = sm + dc * 64;
@@ -51,9 +57,55 @@ __global__ __launch_bounds__(256) void k_sgp_grad_rect(const double *__restrict_
         const SlabSrc si{xT, ldx, bi * 64}, sj{zT, ldz, bj * 64};
         // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
         PairAcc<CORR> pa[4][4];
-        tile_pairs_staged<CORR>(xi, xj, si, sj, d, dc, coef, 1, tid, ty, tx, true, pa);
+        tile_pairs_staged<CORR>(xi, xj, si, sj, d, dc, coef, MULTI ? hcols : 1, tid, ty, tx, true, pa);
         double wp[4][4];  // T[t, i] R[t, i] inside the n x nz rectangle, else 0
         rect_weights<CORR>(pa, T, ldt, bi * 64, bj * 64, n, nz, ty, tx, wp);
+        if (MULTI) {
+            // ---- pass 2, per theta: outputs o0 .. o0 + DK - 1, o < hcols <-> theta_o, o == hcols the plain sum.  d <= dc: the
+            // slabs of pass 1 hold every dimension; else each chunk is staged again (none where the plain sum is alone)
+            if (o0 < hcols) {
+                for (int c0 = 0; c0 < d; c0 += dc) {
+                    const int dn = (d - c0 < dc) ? (d - c0) : dc;
+                    if (d > dc) stage_pair(xi, xj, si.from(c0), sj.from(c0), dn, tid, true);
+                    for (int k = 0; k < dn; k++) {
+                        double vi[4], vj[4], ad[4][4];
+#pragma unroll
+                        for (int a = 0; a < 4; a++) vi[a] = xi[k * 64 + ty * 4 + a];
+#pragma unroll
+                        for (int b = 0; b < 4; b++) vj[b] = xj[k * 64 + tx * 4 + b];
+#pragma unroll
+                        for (int a = 0; a < 4; a++)
+#pragma unroll
+                            for (int b = 0; b < 4; b++) ad[a][b] = fabs(vi[a] - vj[b]);
+                        const double *ck = coef + (int64_t)(c0 + k) * hcols + o0, *wk = wabs + (int64_t)(c0 + k) * hcols + o0;
+#pragma unroll
+                        for (int oo = 0; oo < DK; oo++) {
+                            if (o0 + oo < hcols) {
+                                const double c = ck[oo], wa = wk[oo];
+                                double t = 0.0;
+#pragma unroll
+                                for (int a = 0; a < 4; a++)
+#pragma unroll
+                                    for (int b = 0; b < 4; b++) t = __builtin_fma(wp[a][b], dlog_dc<CORR>(c, ad[a][b]), t);
+                                acc[oo] = __builtin_fma(wa, t, acc[oo]);
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int oo = 0; oo < DK; oo++) {
+                if (o0 + oo == hcols) {
+                    double sacc = acc[oo];
+#pragma unroll
+                    for (int a = 0; a < 4; a++)
+#pragma unroll
+                        for (int b = 0; b < 4; b++) sacc += wp[a][b];
+                    acc[oo] = sacc;
+                }
+            }
+            continue;
+        }
         // ---- pass 2: this workgroup's outputs o0 .. o0 + DK - 1: o < d <-> input dimension o, o == d the plain sum.
         // d > dc: the chunk's dimensions are staged again, from slab row 0 (none where the plain sum is alone in its chunk)
         int base = 0;
@@ -188,9 +240,15 @@ __global__ __launch_bounds__(256) void k_sgp_form_m1(const double *__restrict__ 
 }
 
 // out (nout doubles) = the sums over the n x nz rectangle with rows xT, columns zT and weights T
+// hcols > 1 (Matern with KPLS weights; wabs = |w|, d x hcols like coef): nout = hcols + 1 sums, per theta (the MULTI form)
 int launch_grad_rect(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, const double *zT, int64_t ldz, int nz, int d,
-                     const double *coef, const double *T, int64_t ldt, double *part, double *out) {
-    const int nout = d + 1, nout_pad = (int)round_up(nout, 32);
+                     const double *coef, int hcols, const double *wabs, const double *T, int64_t ldt, double *part, double *out) {
+    const bool multi = hcols > 1;
+    if (multi && corr != EGX_CORR_MATERN32 && corr != EGX_CORR_MATERN52) {
+        set_error("sparse GP gradient: a coefficient table with hcols > 1 belongs to the Matern correlations");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const int nout = (multi ? hcols : d) + 1, nout_pad = (int)round_up(nout, 32);
     const int ntc = (nz + 63) / 64;
     const int64_t nt = (int64_t)((n + 63) / 64) * ntc;
     if (nt > 0x7fffffff) {
@@ -199,12 +257,29 @@ int launch_grad_rect(hipStream_t s, int corr, const double *xT, int64_t ldx, int
     }
     const int ntiles = (int)nt, nwg = ntiles < kRectMaxWG ? ntiles : kRectMaxWG;
     const int dc = d < kRectDC ? d : kRectDC;
-    const int dk = nout <= 8 ? 8 : (nout <= 16 ? 16 : 32);
+    // (the per-theta form walks every dimension per output: narrower chunks, so that a few thetas do not pay for 8 or 16)
+    const int dk = multi ? (nout <= 4 ? 4 : (nout <= 8 ? 8 : 16)) : (nout <= 8 ? 8 : (nout <= 16 ? 16 : 32));
     const size_t lds = sizeof(double) * (size_t)std::max(2 * dc * 64, 4 * dk);
     const dim3 grid((unsigned)nwg, (unsigned)((nout + dk - 1) / dk));
+#define EGX_RECT_M(C_, DK_)                                                                                                     \
+    hipLaunchKernelGGL((k_sgp_grad_rect<C_, DK_, true>), grid, dim3(256), lds, s, xT, ldx, n, zT, ldz, nz, d, coef, T, ldt, ntc, \
+                       ntiles, nout, nout_pad, part, hcols, wabs)
+#define EGX_RECT_M_DK(C_)                \
+    if (dk == 4) EGX_RECT_M(C_, 4);      \
+    else if (dk == 8) EGX_RECT_M(C_, 8); \
+    else EGX_RECT_M(C_, 16)
+    if (multi) {
+        if (corr == EGX_CORR_MATERN32) { EGX_RECT_M_DK(EGX_CORR_MATERN32); }
+        else { EGX_RECT_M_DK(EGX_CORR_MATERN52); }
+        hipLaunchKernelGGL(k_sgp_grad_reduce, dim3((unsigned)nout), dim3(256), 0, s, part, nwg, nout_pad, out);
+        EGX_HIP_CHECK(hipGetLastError());
+        return EGX_SUCCESS;
+    }
+#undef EGX_RECT_M_DK
+#undef EGX_RECT_M
 #define EGX_RECT(C_, DK_)                                                                                                    \
     hipLaunchKernelGGL((k_sgp_grad_rect<C_, DK_>), grid, dim3(256), lds, s, xT, ldx, n, zT, ldz, nz, d, coef, T, ldt, ntc, ntiles, \
-                       nout, nout_pad, part)
+                       nout, nout_pad, part, 1, (const double *)nullptr)
 #define EGX_RECT_DK(C_)                 \
     if (dk == 8) EGX_RECT(C_, 8);       \
     else if (dk == 16) EGX_RECT(C_, 16); \
@@ -242,11 +317,13 @@ __device__ __forceinline__ double dlog_da(double c, double dlt) {
 // rows meets in a fixed order: a lane's four rows of a tile and its tiles one after the other in registers, the four lanes of
 // a wave that share tx (xor shuffles over the ty bits 16, 32), the four waves through LDS; the partial [64 columns][d] goes to
 // part[blockIdx.x], and k_sgp_grad_cols_reduce adds the runs in order.  No atomics: the same bits on every call.
-template <int CORR, int DK>
+// MULTI (KPLS under a Matern correlation): coef is d x hcols and r is a product over (k, l), so the factor of output (j, k) is
+// sum_l dlog_da(c_kl, x_ik - z_jk); the outputs stay (column, input dimension).  MULTI == false: the kernel as it was.
+template <int CORR, int DK, bool MULTI = false>
 __global__ __launch_bounds__(256) void k_sgp_grad_cols(const double *__restrict__ xT, int64_t ldx, int n,
                                                        const double *__restrict__ zT, int64_t ldz, int nz, int d,
                                                        const double *__restrict__ coef, const double *__restrict__ T, int64_t ldt,
-                                                       int nrt, int tpc, int ncol_pad, double *__restrict__ part) {
+                                                       int nrt, int tpc, int ncol_pad, double *__restrict__ part, int hcols) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int dc = d < kRectDC ? d : kRectDC;
     double *xi = sm, *xj = sm + dc * 64;
@@ -262,7 +339,7 @@ __global__ __launch_bounds__(256) void k_sgp_grad_cols(const double *__restrict_
         const SlabSrc si{xT, ldx, bi * 64}, sj{zT, ldz, bj * 64};
         // ---- pass 1: the correlations of the tile's 16 pairs per lane (all d dimensions, staged dc at a time)
         PairAcc<CORR> pa[4][4];
-        tile_pairs_staged<CORR>(xi, xj, si, sj, d, dc, coef, 1, tid, ty, tx, true, pa);
+        tile_pairs_staged<CORR>(xi, xj, si, sj, d, dc, coef, MULTI ? hcols : 1, tid, ty, tx, true, pa);
         double wp[4][4];  // T[i, j] R[i, j] inside the n x nz rectangle, else 0
         rect_weights<CORR>(pa, T, ldt, bi * 64, bj * 64, n, nz, ty, tx, wp);
         // ---- pass 2: output dimensions o0 .. o0 + DK - 1 of this lane's four columns.  d > dc: they are staged again, from
@@ -275,7 +352,34 @@ __global__ __launch_bounds__(256) void k_sgp_grad_cols(const double *__restrict_
 #pragma unroll
         for (int oo = 0; oo < DK; oo++) {
             const int o = o0 + oo;
-            if (o < d) {
+            if (MULTI) {
+                if (o < d) {
+                    double vi[4], vj[4], fac[4][4];
+#pragma unroll
+                    for (int a = 0; a < 4; a++) vi[a] = xi[(o - base) * 64 + ty * 4 + a];
+#pragma unroll
+                    for (int b = 0; b < 4; b++) vj[b] = xj[(o - base) * 64 + tx * 4 + b];
+#pragma unroll
+                    for (int a = 0; a < 4; a++)
+#pragma unroll
+                        for (int b = 0; b < 4; b++) fac[a][b] = 0.0;
+                    const double *ck = coef + (int64_t)o * hcols;
+                    for (int l = 0; l < hcols; l++) {
+                        const double c = ck[l];
+#pragma unroll
+                        for (int a = 0; a < 4; a++)
+#pragma unroll
+                            for (int b = 0; b < 4; b++) fac[a][b] += dlog_da<CORR>(c, vi[a] - vj[b]);
+                    }
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        double sacc = acc[b][oo];
+#pragma unroll
+                        for (int a = 0; a < 4; a++) sacc = __builtin_fma(wp[a][b], fac[a][b], sacc);
+                        acc[b][oo] = sacc;
+                    }
+                }
+            } else if (o < d) {
                 const double c = coef[o];
                 double vi[4], vj[4];
 #pragma unroll
@@ -339,7 +443,12 @@ size_t cols_part_doubles(int rows, int cols, int d) {
 
 // out (nz x d) = scale * the column sums over the n x nz rectangle with rows xT, columns zT and weights T
 int launch_grad_cols(hipStream_t s, int corr, const double *xT, int64_t ldx, int n, const double *zT, int64_t ldz, int nz, int d,
-                     const double *coef, const double *T, int64_t ldt, double scale, double *part, double *out) {
+                     const double *coef, int hcols, const double *T, int64_t ldt, double scale, double *part, double *out) {
+    const bool multi = hcols > 1;  // Matern with KPLS weights: coef is d x hcols
+    if (multi && corr != EGX_CORR_MATERN32 && corr != EGX_CORR_MATERN52) {
+        set_error("sparse GP gradient in the inducing points: a coefficient table with hcols > 1 belongs to the Matern correlations");
+        return EGX_ERR_INVALID_VALUE;
+    }
     const int nrt = (n + 63) / 64, ntc = (nz + 63) / 64, ncol_pad = ntc * 64;
     int tpc, nruns;
     cols_runs(n, nz, tpc, nruns);
@@ -352,14 +461,19 @@ int launch_grad_cols(hipStream_t s, int corr, const double *xT, int64_t ldx, int
     }
     const size_t lds = sizeof(double) * (size_t)std::max(2 * dc * 64, 4 * 64 * dk);
     const dim3 grid((unsigned)nruns, (unsigned)ntc, (unsigned)nzc);
-#define EGX_COLS(C_, DK_)                                                                                                       \
-    hipLaunchKernelGGL((k_sgp_grad_cols<C_, DK_>), grid, dim3(256), lds, s, xT, ldx, n, zT, ldz, nz, d, coef, T, ldt, nrt, tpc, \
-                       ncol_pad, part)
-#define EGX_COLS_DK(C_)                \
-    if (dk == 4) EGX_COLS(C_, 4);      \
-    else if (dk == 8) EGX_COLS(C_, 8); \
-    else EGX_COLS(C_, 16)
-    EGX_DISPATCH_CORR(corr, EGX_COLS_DK(C_));
+#define EGX_COLS(C_, DK_, M_)                                                                                                       \
+    hipLaunchKernelGGL((k_sgp_grad_cols<C_, DK_, M_>), grid, dim3(256), lds, s, xT, ldx, n, zT, ldz, nz, d, coef, T, ldt, nrt, tpc, \
+                       ncol_pad, part, hcols)
+#define EGX_COLS_DK(C_, M_)                \
+    if (dk == 4) EGX_COLS(C_, 4, M_);      \
+    else if (dk == 8) EGX_COLS(C_, 8, M_); \
+    else EGX_COLS(C_, 16, M_)
+    if (multi) {
+        if (corr == EGX_CORR_MATERN32) { EGX_COLS_DK(EGX_CORR_MATERN32, true); }
+        else { EGX_COLS_DK(EGX_CORR_MATERN52, true); }
+    } else {
+        EGX_DISPATCH_CORR(corr, EGX_COLS_DK(C_, false));
+    }
 #undef EGX_COLS_DK
 #undef EGX_COLS
     const int64_t count = (int64_t)nz * d;
@@ -374,14 +488,16 @@ int launch_grad_cols(hipStream_t s, int corr, const double *xT, int64_t ldx, int
 namespace egx {
 
 // After a successful sgp_eval(theta, sigma2, noise) whose factors are resident (Kz, dinv_z, RT, s0, A with b in row z_pad,
-// dinv_a, G): grad (d + 2) = dL/dtheta_0..d-1, dL/dsigma2, dL/dnoise.  Caller holds g->mu.
+// dinv_a, G): grad (h + 2; h = d without KPLS weights) = dL/dtheta_0..h-1, dL/dsigma2, dL/dnoise.  Caller holds g->mu.
 int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad) {
     const int n = g->n, d = g->d, nz = g->nz, n_pad = g->n_pad, z_pad = g->z_pad, zext = g->zext;
     const int vfe = g->method != 0;
     const double sigma = std::sqrt(sigma2);
     hipStream_t s = g->stream;
     const size_t rect = (size_t)n_pad * z_pad, sq = (size_t)z_pad * z_pad;
-    const int nout = d + 1, nout_pad = (int)round_up(nout, 32);
+    // the kernels' sums: one per theta under KPLS with a Matern correlation (hcols > 1), else one per input dimension; + the plain sum
+    const int hcols = g->hcols, nk = hcols > 1 ? hcols : d;
+    const int nout = nk + 1, nout_pad = (int)round_up(nout, 32);
     EGX_RC(g->gr_E.alloc(rect));
     EGX_RC(g->gr_rows.alloc((size_t)7 * n_pad));
     EGX_RC(g->gr_sq.alloc(3 * sq));
@@ -430,19 +546,29 @@ int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad) {
                        (int64_t)rect, E);
     EGX_RC(launch_gemm_nt_sub(s, E, z_pad, F, z_pad, g->Wz.p, z_pad, n_pad, z_pad, z_pad, 0));
     // the two rectangles of pairs
-    EGX_RC(launch_grad_rect(s, g->corr, g->xT.p, n_pad, n, g->zT.p, z_pad, nz, d, g->coef.p, E, z_pad, g->gr_part.p, out_nz));
-    EGX_RC(launch_grad_rect(s, g->corr, g->zT.p, z_pad, nz, g->zT.p, z_pad, nz, d, g->coef.p, Sh, z_pad, g->gr_part.p, out_zz));
+    EGX_RC(launch_grad_rect(s, g->corr, g->xT.p, n_pad, n, g->zT.p, z_pad, nz, d, g->coef.p, hcols, g->d_wabs.p, E, z_pad, g->gr_part.p,
+                            out_nz));
+    EGX_RC(launch_grad_rect(s, g->corr, g->zT.p, z_pad, nz, g->zT.p, z_pad, nz, d, g->coef.p, hcols, g->d_wabs.p, Sh, z_pad,
+                            g->gr_part.p, out_zz));
     std::vector<double> h((size_t)2 * nout_pad + 32);
     EGX_HIP_CHECK(hipMemcpyAsync(h.data(), g->gr_out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
     EGX_HIP_CHECK(hipStreamSynchronize(s));
     const double *hn = h.data(), *hz = hn + nout_pad;
     const double sum_p = h[(size_t)2 * nout_pad], sum_s0 = h[(size_t)2 * nout_pad + 1];
-    for (int k = 0; k < d; k++) grad[k] = -sigma2 * hn[k] + 0.5 * hz[k];
+    const int nt = g->h;  // theta components: grad is nt + 2 long
+    if (!g->has_w) {
+        for (int k = 0; k < d; k++) grad[k] = -sigma2 * hn[k] + 0.5 * hz[k];
+    } else {  // the sums are dL/dc_j of the collapsed coefficients, or per theta already: the chain rule of the table (kpls_coef.h)
+        std::vector<double> gs(nk);
+        for (int k = 0; k < nk; k++) gs[k] = -sigma2 * hn[k] + 0.5 * hz[k];
+        kpls::chain_rule(g->corr, d, nt, g->w_ptr(), hcols, g->coef_host.data(), g->th_full.data(), gs.data(), 1.0, grad,
+                          true);
+    }
     const double nu = std::fmax(noise, g->nugget), be = 1.0 / nu;
     const double c_sigma = vfe ? (double)n * be : sum_p;
-    grad[d] = -0.5 * (2.0 * hn[d] - hz[d] / sigma2 + c_sigma);
-    if (!vfe) grad[d + 1] = -0.5 * sum_p;
-    else grad[d + 1] = (noise > g->nugget) ? -0.5 * (sum_p - be * be * ((double)n * sigma2 - sigma2 * sum_s0)) : 0.0;
+    grad[nt] = -0.5 * (2.0 * hn[nk] - hz[nk] / sigma2 + c_sigma);
+    if (!vfe) grad[nt + 1] = -0.5 * sum_p;
+    else grad[nt + 1] = (noise > g->nugget) ? -0.5 * (sum_p - be * be * ((double)n * sigma2 - sigma2 * sum_s0)) : 0.0;
     return EGX_SUCCESS;
 }
 
@@ -457,8 +583,10 @@ int sgp_grad_tail_z(egx_sgp *g, double sigma2, double *grad_z) {
     EGX_RC(g->gz_out.alloc(2 * cnt));
     const double *E = g->gr_E.p, *Sh = g->gr_sq.p + 2 * sq;
     double *out_nz = g->gz_out.p, *out_zz = out_nz + cnt;
-    EGX_RC(launch_grad_cols(s, g->corr, g->xT.p, n_pad, n, g->zT.p, z_pad, nz, d, g->coef.p, E, z_pad, sigma2, g->gz_part.p, out_nz));
-    EGX_RC(launch_grad_cols(s, g->corr, g->zT.p, z_pad, nz, g->zT.p, z_pad, nz, d, g->coef.p, Sh, z_pad, -1.0, g->gz_part.p, out_zz));
+    EGX_RC(launch_grad_cols(s, g->corr, g->xT.p, n_pad, n, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, E, z_pad, sigma2, g->gz_part.p,
+                            out_nz));
+    EGX_RC(launch_grad_cols(s, g->corr, g->zT.p, z_pad, nz, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, Sh, z_pad, -1.0, g->gz_part.p,
+                            out_zz));
     std::vector<double> h(2 * cnt);
     EGX_HIP_CHECK(hipMemcpyAsync(h.data(), g->gz_out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
     EGX_HIP_CHECK(hipStreamSynchronize(s));

@@ -34,6 +34,14 @@ struct egx_sgp {
     // the per-column range of the training inputs, the default box of egx_sgp_fit_lbfgs_z
     egx::DevBuf gz_part, gz_out;
     std::vector<double> z_host, x_lo, x_hi;
+    // KPLS (egx_sgp_set_w_star): h = the number of theta components (d without weights), w_star (d x h, row-major) and |w| on the
+    // device for the Matern gradient kernel; hcols / coef_host / th_full: the table of the last evaluation (kpls_coef.h), d x hcols
+    // in `coef`, and the theta it came from, which sgp_grad_tail's chain rule reads
+    int h = 0, hcols = 1;
+    bool has_w = false;
+    std::vector<double> w_star, coef_host, th_full;
+    egx::DevBuf d_wabs;
+    const double *w_ptr() const { return has_w ? w_star.data() : nullptr; }
 };
 
 
@@ -49,7 +57,7 @@ int sgp_launch_scale_copy(hipStream_t s, const double *RT, double sgn, int64_t c
 // W <- [scale * diag(sb) RT]^T with the row sb o y below it: the operand of the likelihood's Gram product, for any weights sb (n)
 int sgp_launch_transpose_scale(egx_sgp *g, const double *sb, double scale);
 // ---- sgp_grad.hip ----
-// grad (d + 2) = dL/dtheta, dL/dsigma2, dL/dnoise at the parameters of the evaluation whose factors are resident
+// grad (h + 2; h = d without KPLS weights) = dL/dtheta, dL/dsigma2, dL/dnoise at the parameters of the evaluation whose factors are resident
 // (a successful sgp_eval that has just returned); caller holds g->mu
 int sgp_grad_tail(egx_sgp *g, double sigma2, double noise, double *grad);
 // grad_z (nz x d, row-major) = dL/dz right after a successful sgp_grad_tail, whose pair weights T^T (gr_E) and S^ (gr_sq) it

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "sgp_handle.h"  // (gp_handle.h: fit_starts.h with the optimisers' machines and the rules of a multistart fit)
+#include "kpls_coef.h"
 
 using namespace egx;
 
@@ -81,13 +82,15 @@ struct Eval {
 int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, double noise, Eval &out, bool keep) {
     const int n = g->n, d = g->d, nz = g->nz, n_pad = g->n_pad, z_pad = g->z_pad, zext = g->zext;
     out = Eval();
-    if (theta_len != 1 && theta_len != d) {
-        set_error("theta should be either 1-dim or dim of xtrain, got " + std::to_string(theta_len));
+    const int h = g->h;  // theta components: d, or the columns of the KPLS weights
+    if (theta_len != 1 && theta_len != h) {
+        set_error(std::string("theta should be either 1-dim or dim of xtrain") + (g->has_w ? " (w_star.ncols())" : "") + ", got " +
+                  std::to_string(theta_len));
         return EGX_ERR_INVALID_VALUE;
     }
-    std::vector<double> th(d);
+    std::vector<double> th(h);
     bool bad = !(sigma2 > 0.0) || !(noise >= 0.0) || !std::isfinite(sigma2) || !std::isfinite(noise);
-    for (int k = 0; k < d; k++) {
+    for (int k = 0; k < h; k++) {
         th[k] = theta[theta_len == 1 ? 0 : k];
         if (std::isnan(th[k])) bad = true;
     }
@@ -99,16 +102,19 @@ int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, 
     const double sigma = std::sqrt(sigma2);
     g->fitted = false;  // the resident factors are about to be overwritten; set again below when `keep`
     g->winv_ok = false;  // ... and with them the cached inverse factors of the x-gradients (sgp_predict.hip)
-    EGX_HIP_CHECK(hipMemcpyAsync(g->coef.p, th.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
-    EGX_HIP_CHECK(hipStreamSynchronize(s));  // th is a local
+    // the coefficient table (kpls_coef.h): theta itself without weights, d x hcols with them
+    const int hcols = g->hcols = kpls::coef_table(g->corr, d, h, g->w_ptr(), th.data(), g->coef_host);
+    g->th_full = th;
+    EGX_HIP_CHECK(hipMemcpyAsync(g->coef.p, g->coef_host.data(), sizeof(double) * g->coef_host.size(), hipMemcpyHostToDevice, s));
+    EGX_HIP_CHECK(hipStreamSynchronize(s));
     EGX_HIP_CHECK(hipMemsetAsync(g->d_info, 0, 2 * sizeof(int), s));
     // Kmm / sigma2 = R_zz + (nugget / sigma2) I  -> C_z
-    int rc = launch_corr_sym(s, g->corr, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->nugget / sigma2, g->Kz.p, z_pad, z_pad);
+    int rc = launch_corr_sym(s, g->corr, g->zT.p, z_pad, nz, d, g->coef.p, hcols, g->nugget / sigma2, g->Kz.p, z_pad, z_pad);
     if (rc) return rc;
     rc = launch_potrf(s, g->Kz.p, z_pad, z_pad, z_pad, g->dinv_z.p, g->d_info);
     if (rc) return rc;
     // R_nz, then V~^T = R_nz C_z^-T
-    rc = launch_cross_corr(s, g->corr, g->xT.p, n_pad, n_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->RT.p, z_pad);
+    rc = launch_cross_corr(s, g->corr, g->xT.p, n_pad, n_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, hcols, g->RT.p, z_pad);
     if (rc) return rc;
     rc = launch_trsm_rows(s, g->Kz.p, z_pad, z_pad, g->dinv_z.p, g->RT.p, z_pad, n_pad);
     if (rc) return rc;
@@ -202,7 +208,7 @@ int sgp_eval(egx_sgp *g, const double *theta, int64_t theta_len, double sigma2, 
 
 // The end of a fit: the keeping evaluation at the best start's point x = log10(params); nullptr: no start ended finite
 int sgp_fit_keep(egx_sgp *g, const StartResult *best, int estimate_noise, double noise_fixed) {
-    const int d = g->d;
+    const int d = g->h;  // theta components
     if (!best) {
         set_error("sparse GP: no start point gave a finite likelihood");
         return EGX_ERR_LIKELIHOOD;
@@ -225,7 +231,7 @@ int sgp_fit_keep(egx_sgp *g, const StartResult *best, int estimate_noise, double
 // dropped when the noise is fixed.  A failed evaluation is f = +inf with a zero gradient.
 int sgp_eval_grad_x(egx_sgp *g, const std::vector<double> &xv, int estimate_noise, double noise_fixed, double &f,
                     std::vector<double> &gx) {
-    const int d = g->d, np = d + 1 + (estimate_noise ? 1 : 0);
+    const int d = g->h, np = d + 1 + (estimate_noise ? 1 : 0);  // d: theta components
     std::vector<double> prm(d + 2), grad(d + 2, 0.0);
     for (int i = 0; i <= d; i++) prm[i] = std::pow(10.0, xv[i]);
     prm[d + 1] = estimate_noise ? std::pow(10.0, xv[d + 1]) : noise_fixed;
@@ -302,20 +308,20 @@ struct ZBox {
 // gradients are evaluated.  g_u = -(hi_k - lo_k) dL/dz[j, k], 0 in a fixed column.  A failed evaluation is f = +inf.
 int sgp_eval_grad_xz(egx_sgp *g, const std::vector<double> &xv, int np, int estimate_noise, double noise_fixed, const ZBox &box,
                      double &f, std::vector<double> &gx) {
-    const int d = g->d, nz = g->nz;
+    const int d = g->d, nz = g->nz, nt = g->h;  // nt: theta components; the points keep d coordinates
     const size_t h = (size_t)np + (size_t)nz * d;
-    std::vector<double> prm(d + 2), grad(d + 2, 0.0), z, gz((size_t)nz * d, 0.0);
+    std::vector<double> prm(nt + 2), grad(nt + 2, 0.0), z, gz((size_t)nz * d, 0.0);
     box.to_z(xv.data() + np, z);
     EGX_RC(sgp_upload_z(g, z.data()));
-    for (int i = 0; i <= d; i++) prm[i] = std::pow(10.0, xv[i]);
-    prm[d + 1] = estimate_noise ? std::pow(10.0, xv[d + 1]) : noise_fixed;
+    for (int i = 0; i <= nt; i++) prm[i] = std::pow(10.0, xv[i]);
+    prm[nt + 1] = estimate_noise ? std::pow(10.0, xv[nt + 1]) : noise_fixed;
     Eval ev;
-    EGX_RC(sgp_eval(g, prm.data(), d, prm[d], prm[d + 1], ev, false));
+    EGX_RC(sgp_eval(g, prm.data(), nt, prm[nt], prm[nt + 1], ev, false));
     f = std::numeric_limits<double>::infinity();
     gx.assign(h, 0.0);
     if (ev.status != EGX_STATUS_OK) return EGX_SUCCESS;
-    EGX_RC(sgp_grad_tail(g, prm[d], prm[d + 1], grad.data()));
-    EGX_RC(sgp_grad_tail_z(g, prm[d], gz.data()));
+    EGX_RC(sgp_grad_tail(g, prm[nt], prm[nt + 1], grad.data()));
+    EGX_RC(sgp_grad_tail_z(g, prm[nt], gz.data()));
     f = -ev.lkh;
     const double ln10 = std::log(10.0);
     for (int i = 0; i < np; i++) gx[i] = -prm[i] * ln10 * grad[i];
@@ -412,6 +418,7 @@ int32_t egx_sgp_create(const egx_sgp_config *cfg_in, const double *x, const doub
     g->nugget = cfg.nugget;
     g->n = (int)n;
     g->d = (int)d;
+    g->h = (int)d;
     g->nz = (int)nz;
     g->n_pad = (int)round_up(n, kTile);
     g->z_pad = (int)round_up(nz, kTile);
@@ -522,7 +529,7 @@ int32_t egx_sgp_likelihood_grad(egx_sgp *g, const double *theta, int64_t theta_l
     EGX_HIP_CHECK(hipSetDevice(g->device));
     Eval ev;
     EGX_RC(sgp_eval(g, theta, theta_len, sigma2, noise, ev, false));
-    for (int i = 0; i < g->d + 2; i++) grad[i] = 0.0;
+    for (int i = 0; i < g->h + 2; i++) grad[i] = 0.0;
     if (ev.status == EGX_STATUS_OK) EGX_RC(sgp_grad_tail(g, sigma2, noise, grad));
     *lkh = ev.lkh;
     *status = ev.status;
@@ -559,7 +566,7 @@ int32_t egx_sgp_fit(egx_sgp *g, const double *params0s, int64_t n_starts, const 
     }
     std::lock_guard<std::mutex> lock(g->mu);
     EGX_HIP_CHECK(hipSetDevice(g->device));
-    const int d = g->d, np = d + 1 + (estimate_noise ? 1 : 0);
+    const int d = g->h, np = d + 1 + (estimate_noise ? 1 : 0);  // d: theta components
     fit::Log10Box box;
     EGX_RC(fit_box(lo, hi, np, np, params0s, n_starts * np, fit::Sparse, box));
     // the budget counts the theta dimensions, not np (sparse_algorithm.rs:601-603)
@@ -605,7 +612,7 @@ int32_t egx_sgp_likelihood_grad_z(egx_sgp *g, const double *theta, int64_t theta
     EGX_HIP_CHECK(hipSetDevice(g->device));
     Eval ev;
     EGX_RC(sgp_eval(g, theta, theta_len, sigma2, noise, ev, false));
-    for (int i = 0; i < g->d + 2; i++) grad[i] = 0.0;
+    for (int i = 0; i < g->h + 2; i++) grad[i] = 0.0;
     for (size_t e = 0; e < (size_t)g->nz * g->d; e++) grad_z[e] = 0.0;
     if (ev.status == EGX_STATUS_OK) {
         EGX_RC(sgp_grad_tail(g, sigma2, noise, grad));
@@ -641,6 +648,70 @@ int32_t egx_sgp_get_inducings(egx_sgp *g, double *z) {
     return EGX_SUCCESS;
 }
 
+// The KPLS weights (header).  They are checked before anything changes; the coefficient buffer grows to d x h and |w| goes to the
+// device once, for the Matern form of the gradient kernel (sgp_grad.hip), as the dense model's d_wabs does.
+int32_t egx_sgp_set_w_star(egx_sgp *g, const double *w, int64_t h) {
+    if (w && h == 0) {  // sparse_parameters.rs:306-311 (needs no handle: refused first)
+        set_error("`kpls_dim` canot be 0!");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (!g) {
+        set_error("NULL handle");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    const int d = g->d;
+    if (!w && h == 0) {  // back to w = I
+        g->has_w = false;
+        g->w_star.clear();
+        g->h = d;
+        g->hcols = 1;
+        g->fitted = false;
+        g->winv_ok = false;
+        return EGX_SUCCESS;
+    }
+    if (h < 0 || h > d) {  // sparse_algorithm.rs:430-438
+        set_error("Dimension reduction " + std::to_string(h) + " should be smaller than actual training input dimensions " +
+                  std::to_string(d));
+        return EGX_ERR_INVALID_VALUE;
+    }
+    if (!w) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    const size_t cnt = (size_t)d * (size_t)h;
+    for (size_t e = 0; e < cnt; e++)
+        if (!std::isfinite(w[e])) {
+            set_error("w_star contains non-finite values");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    std::vector<double> wabs(cnt);
+    for (size_t e = 0; e < cnt; e++) wabs[e] = std::fabs(w[e]);
+    EGX_RC(g->coef.alloc(cnt));
+    EGX_RC(g->d_wabs.alloc(cnt));
+    EGX_HIP_CHECK(hipMemcpyAsync(g->d_wabs.p, wabs.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
+    EGX_HIP_CHECK(hipStreamSynchronize(g->stream));  // wabs is a local
+    g->w_star.assign(w, w + cnt);
+    g->has_w = true;
+    g->h = (int)h;
+    g->hcols = (g->corr == EGX_CORR_MATERN32 || g->corr == EGX_CORR_MATERN52) ? (int)h : 1;
+    g->fitted = false;
+    g->winv_ok = false;
+    return EGX_SUCCESS;
+}
+
+int32_t egx_sgp_get_w_star(egx_sgp *g, double *w, int64_t *h) {
+    if (!g || !h) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    *h = g->h;
+    if (w && g->has_w) std::memcpy(w, g->w_star.data(), sizeof(double) * g->w_star.size());
+    return EGX_SUCCESS;
+}
+
 // egx_sgp_fit_lbfgs, then one more L-BFGS from its winner in which the inducing points move too (header: phase 2).  The phase-2
 // point is kept only where its likelihood is strictly higher; otherwise the points go back, bit for bit, to where they were.
 int32_t egx_sgp_fit_lbfgs_z(egx_sgp *g, const double *params0s, int64_t n_starts, const double *lo, const double *hi,
@@ -656,7 +727,7 @@ int32_t egx_sgp_fit_lbfgs_z(egx_sgp *g, const double *params0s, int64_t n_starts
     }
     std::lock_guard<std::mutex> lock(g->mu);
     EGX_HIP_CHECK(hipSetDevice(g->device));
-    const int d = g->d, nz = g->nz, np = d + 1 + (estimate_noise ? 1 : 0);
+    const int d = g->d, nz = g->nz, np = g->h + 1 + (estimate_noise ? 1 : 0);
     fit::Log10Box pbox;
     EGX_RC(fit_box(lo, hi, np, np, params0s, n_starts * np, fit::Sparse, pbox));
     ZBox box;
@@ -722,7 +793,7 @@ int32_t egx_sgp_get_state(egx_sgp *g, double *theta, double *sigma2, double *noi
     }
     EGX_HIP_CHECK(hipSetDevice(g->device));
     const int nz = g->nz, z_pad = g->z_pad;
-    if (theta) std::memcpy(theta, g->theta.data(), sizeof(double) * g->d);
+    if (theta) std::memcpy(theta, g->theta.data(), sizeof(double) * g->h);
     if (sigma2) *sigma2 = g->sigma2;
     if (noise) *noise = g->noise;
     if (likelihood) *likelihood = g->likelihood;

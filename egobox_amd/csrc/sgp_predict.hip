@@ -112,13 +112,16 @@ int sgp_ensure_inverse_factors(egx_sgp *g) {
 }
 
 int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vout, double *gyout, double *gvout) {
-    EGX_RC(check_sgp_query(g, xq, m));
     const int d = g->d, nz = g->nz, z_pad = g->z_pad;
     const bool grad = gyout || gvout, solves = vout || gvout;
-    if (grad && (int64_t)d * (1 + 5) > 20480) {
-        set_error("x-gradients: " + std::to_string(d) + " inputs do not fit the 160 KB of LDS (d * (hcols + 5) <= 20480, hcols = 1)");
+    // (with KPLS weights the bound is known from egx_sgp_set_w_star on and is reported before anything else: no fit can lift it)
+    if (!g->has_w) EGX_RC(check_sgp_query(g, xq, m));
+    if (grad && (int64_t)d * (g->hcols + 5) > 20480) {
+        set_error("x-gradients: " + std::to_string(d) + " inputs do not fit the 160 KB of LDS (d * (hcols + 5) <= 20480, hcols = " +
+                  std::to_string(g->hcols) + ")");
         return EGX_ERR_UNSUPPORTED;
     }
+    if (g->has_w) EGX_RC(check_sgp_query(g, xq, m));
     if (m == 0) return EGX_SUCCESS;
     hipStream_t s = g->stream;
     if (gvout) EGX_RC(sgp_ensure_inverse_factors(g));
@@ -140,12 +143,12 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
         EGX_RC(g->q_out.alloc(out_sz));
         double *dout = g->q_out.p;
         if (yout)  // Kx . vec  (:237-241), R never materialised; g->vec carries the factor sigma2
-            EGX_RC(launch_predict_mean(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->vec.p,
+            EGX_RC(launch_predict_mean(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, g->hcols, g->vec.p,
                                        dout + o_y));
         if (solves) {  // sigma2 - kx^T inv kx  (:245-257)
             const size_t blk = (size_t)m_pad * z_pad;
             EGX_RC(g->q_RT.alloc(blk));
-            EGX_RC(launch_cross_corr(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, 1, g->q_RT.p, z_pad));
+            EGX_RC(launch_cross_corr(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, z_pad, d, g->coef.p, g->hcols, g->q_RT.p, z_pad));
             EGX_RC(launch_trsm_rows(s, g->Kz.p, z_pad, z_pad, g->dinv_z.p, g->q_RT.p, z_pad, m_pad));  // a~ = C_z^-1 r
             EGX_RC(launch_row_reduce(s, g->q_RT.p, z_pad, m_pad, nz, nullptr, 0, 0, dout + o_p, nullptr));
             if (gvout) {  // E = sgn a~, sgn = -s: the GEMMs below subtract
@@ -168,7 +171,7 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
             const int nblk = (nz + 255) / 256;
             EGX_RC(g->q_part.alloc((size_t)nblk * mc * d));
             if (gyout) {
-                EGX_RC(launch_xgrad_point(s, g->corr, g->q_x.p, m_pad, mc, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p,
+                EGX_RC(launch_xgrad_point(s, g->corr, g->q_x.p, m_pad, mc, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, g->vec.p,
                                           g->q_part.p));
                 hipLaunchKernelGGL(k_sgp_grad_finish, dim3(fin_blocks), dim3(256), 0, s, (const double *)g->q_part.p, nblk,
                                    (int64_t)mc * d, (int64_t)d, d, mc, (const double *)nullptr, (const double *)nullptr, g->sigma2,
@@ -182,7 +185,7 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
                                               mc));  // E = a~ + s L^-T b~
                 EGX_RC(launch_uptri_gemv_rows(s, g->Wz.p, z_pad, nz, g->q_E.p, nullptr, 1.0, g->q_Ct.p, z_pad, mc));  // c
                 for (int a = 0; a < mc; a++)
-                    EGX_RC(launch_xgrad_point(s, g->corr, g->q_x.p + a, m_pad, 1, g->zT.p, z_pad, nz, d, g->coef.p, 1,
+                    EGX_RC(launch_xgrad_point(s, g->corr, g->q_x.p + a, m_pad, 1, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols,
                                               g->q_Ct.p + (size_t)a * z_pad, g->q_part.p + (size_t)a * nblk * d));
                 hipLaunchKernelGGL(k_sgp_grad_finish, dim3(fin_blocks), dim3(256), 0, s, (const double *)g->q_part.p, nblk,
                                    (int64_t)d, (int64_t)nblk * d, d, mc, (const double *)(dout + o_p), (const double *)(dout + o_q),
@@ -194,7 +197,7 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
             const int nsplit = xgrad_splits(nz, m_pad);
             EGX_RC(g->q_part.alloc((size_t)nsplit * m_pad * d));
             if (gyout) {
-                EGX_RC(launch_xgrad(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->vec.p, 0, 1, nsplit,
+                EGX_RC(launch_xgrad(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, g->vec.p, 0, 1, nsplit,
                                     g->q_part.p));
                 hipLaunchKernelGGL(k_sgp_grad_finish, dim3(fin_blocks), dim3(256), 0, s, (const double *)g->q_part.p, nsplit,
                                    (int64_t)m_pad * d, (int64_t)d, d, mc, (const double *)nullptr, (const double *)nullptr,
@@ -207,7 +210,7 @@ int sgp_query(egx_sgp *g, const double *xq, int64_t m, double *yout, double *vou
                 // Ct = 0 - C_z^-T E^T = -sgn c, (z_pad x m_pad): W upper triangular, the K range starts at the row tile
                 EGX_HIP_CHECK(hipMemsetAsync(g->q_Ct.p, 0, sizeof(double) * blk, s));
                 EGX_RC(launch_gemm_nt_sub(s, g->q_Ct.p, m_pad, g->Wz.p, z_pad, g->q_E.p, z_pad, z_pad, m_pad, z_pad, 0, 1));
-                EGX_RC(launch_xgrad(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, nz, d, g->coef.p, 1, g->q_Ct.p, m_pad, 0,
+                EGX_RC(launch_xgrad(s, g->corr, g->q_x.p, m_pad, m_pad, g->zT.p, z_pad, nz, d, g->coef.p, g->hcols, g->q_Ct.p, m_pad, 0,
                                     nsplit, g->q_part.p));
                 hipLaunchKernelGGL(k_sgp_grad_finish, dim3(fin_blocks), dim3(256), 0, s, (const double *)g->q_part.p, nsplit,
                                    (int64_t)m_pad * d, (int64_t)d, d, mc, (const double *)(dout + o_p), (const double *)(dout + o_q),
@@ -280,7 +283,7 @@ int sgp_sample(egx_sgp *g, const double *xq, int64_t m, int64_t n_traj, int meth
         for (int k = 0; k < d; k++) g->h_x[(size_t)k * m_pad + a] = xq[(size_t)a * d + k];
     EGX_RC(g->q_x.alloc(g->h_x.size()));
     EGX_HIP_CHECK(hipMemcpyAsync(g->q_x.p, g->h_x.data(), sizeof(double) * g->h_x.size(), hipMemcpyHostToDevice, g->stream));
-    const SampleCov c{g->corr, g->q_x.p, d, g->coef.p, 1, nullptr, g->sigma2, g->sigma2, "prior"};
+    const SampleCov c{g->corr, g->q_x.p, d, g->coef.p, g->hcols, nullptr, g->sigma2, g->sigma2, "prior"};
     return sample_draw(g->stream, c, (int)m, (int)n_traj, method, seed, z, mean.data(), traj, tau_out);
 }
 

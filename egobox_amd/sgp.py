@@ -58,7 +58,7 @@ class ParamTuning:
 class SgpHandle:
     """Thin owner of an `egx_sgp*`."""
 
-    def __init__(self, x, y, z, corr=0, method=FITC, nugget=G.DEFAULT_NUGGET, device=-1):
+    def __init__(self, x, y, z, corr=0, method=FITC, nugget=G.DEFAULT_NUGGET, device=-1, w_star=None):
         self._lib = L.load()
         x = L.as_f64(x)
         if x.ndim == 1:
@@ -77,7 +77,35 @@ class SgpHandle:
                                          z.shape[0], C.byref(h)))
         self._h = h
         self.n, self.d, self.nz = x.shape[0], x.shape[1], z.shape[0]
+        self.h = self.d  # theta components: the columns of the KPLS weights once `set_w_star` has set some
         self.z = z.copy()
+        if w_star is not None:
+            try:
+                self.set_w_star(w_star)
+            except Exception:
+                self.close()
+                raise
+
+    def set_w_star(self, w):
+        """KPLS weights (d, h), 1 <= h <= d, finite; None clears them (egx_sgp_set_w_star).  Un-fits the handle; theta then has
+        h components everywhere, gradients are h + 2 long; `grad_z` and the inducing points stay (nz, d)."""
+        if w is None:
+            L.check(self._lib.egx_sgp_set_w_star(self._h, None, 0))
+            self.h = self.d
+            return
+        w = np.ascontiguousarray(L.as_f64(w))
+        if w.ndim != 2 or w.shape[0] != self.d:
+            raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"w_star must be ({self.d}, h), got {w.shape}")
+        L.check(self._lib.egx_sgp_set_w_star(self._h, L.dptr(w), w.shape[1]))
+        self.h = w.shape[1]
+
+    def w_star(self):
+        """The KPLS weights (d, h), or None when none are set (egx_sgp_get_w_star)."""
+        h = C.c_int64()
+        L.check(self._lib.egx_sgp_get_w_star(self._h, None, C.byref(h)))
+        w = np.full((self.d, h.value), np.nan)
+        L.check(self._lib.egx_sgp_get_w_star(self._h, L.dptr(w), C.byref(h)))
+        return None if np.isnan(w[0, 0]) else w
 
     def close(self):
         if getattr(self, "_h", None):
@@ -101,11 +129,11 @@ class SgpHandle:
 
     def likelihood_grad(self, theta, sigma2, noise):
         """(likelihood, gradient, status): the likelihood of `likelihood` (same bits) and its closed-form gradient
-        (d + 2: dL/dtheta_0..d-1 -- of the broadcast theta when one value is given --, dL/dsigma2, dL/dnoise), zeros
-        whenever status != 0 (egx_sgp_likelihood_grad)."""
+        (h + 2, h = d without KPLS weights: dL/dtheta_0..h-1 -- of the broadcast theta when one value is given --, dL/dsigma2,
+        dL/dnoise), zeros whenever status != 0 (egx_sgp_likelihood_grad)."""
         th = L.as_f64(np.atleast_1d(theta), 1)
         lk, st = C.c_double(), C.c_int32()
-        grad = np.zeros(self.d + 2)
+        grad = np.zeros(self.h + 2)
         L.check(self._lib.egx_sgp_likelihood_grad(self._h, L.dptr(th), th.size, float(sigma2), float(noise), C.byref(lk),
                                                   L.dptr(grad), C.byref(st)))
         return lk.value, grad, st.value
@@ -137,7 +165,7 @@ class SgpHandle:
         the inducing points; zeros whenever status != 0 (egx_sgp_likelihood_grad_z)."""
         th = L.as_f64(np.atleast_1d(theta), 1)
         lk, st = C.c_double(), C.c_int32()
-        grad, grad_z = np.zeros(self.d + 2), np.zeros((self.nz, self.d))
+        grad, grad_z = np.zeros(self.h + 2), np.zeros((self.nz, self.d))
         L.check(self._lib.egx_sgp_likelihood_grad_z(self._h, L.dptr(th), th.size, float(sigma2), float(noise), C.byref(lk),
                                                     L.dptr(grad), L.dptr(grad_z), C.byref(st)))
         return lk.value, grad, grad_z, st.value
@@ -250,7 +278,7 @@ class SgpHandle:
         return (out, tau.value) if return_tau else out
 
     def state(self, with_inv=False):
-        th, vec = np.empty(self.d), np.empty(self.nz)
+        th, vec = np.empty(self.h), np.empty(self.nz)
         s2, nv, lk = C.c_double(), C.c_double(), C.c_double()
         inv = np.empty((self.nz, self.nz)) if with_inv else None
         L.check(self._lib.egx_sgp_get_state(self._h, L.dptr(th), C.byref(s2), C.byref(nv), C.byref(lk), L.dptr(vec),
@@ -274,6 +302,25 @@ class SgpParams:
         self._nugget, self._seed, self._device = G.DEFAULT_NUGGET, None, -1
         self._optimizer = "cobyla"  # the reference's optimiser; "lbfgs" uses the closed-form likelihood gradient
         self._opt_z = None          # optimize_inducings: (max_iter, (z_lo, z_hi) or None)
+        self._kpls_dim = None
+
+    def kpls_dim(self, k):
+        """SgpParams::kpls_dim (sparse_parameters.rs:216-220, checked as :304-322): fit on k PLS components of the inputs.  The
+        rotations w_star (d, k) are those of a PLS regression of the raw y on the raw x (`kpls.pls_rotations`, on the host, as
+        sparse_algorithm.rs:429-455 takes them from linfa-pls); theta, its initial guess and its bounds then have k components,
+        with every optimiser.  None switches it off."""
+        if k is not None:
+            k = int(k)
+            if k == 0:
+                raise L.InvalidValueError(L.ERR_INVALID_VALUE, "`kpls_dim` canot be 0!")
+            th = np.asarray(self._theta_tuning.init, dtype=np.float64).reshape(-1)
+            if th.size > 1 and k > th.size:
+                raise L.InvalidValueError(
+                    L.ERR_INVALID_VALUE,
+                    f"Dimension reduction ({k}) should be smaller than expected training input size "
+                    f"infered from given initial theta length ({th.size})")
+        self._kpls_dim = k
+        return self
 
     def sparse_method(self, m):
         self._method = {"fitc": FITC, "vfe": VFE}[m.lower()] if isinstance(m, str) else int(m)
@@ -349,14 +396,24 @@ class SgpParams:
         else:  # make_inducings :833-848 (numpy shuffle instead of Xoshiro256Plus)
             rng = np.random.default_rng(self._seed)
             z = x[rng.permutation(x.shape[0])[:min(self._inducings.value, x.shape[0])]].copy()
-        h = SgpHandle(x, y, z, corr=self._corr.code, method=self._method, nugget=self._nugget, device=self._device)
-        d = h.d
+        w_star = None
+        if self._kpls_dim is not None:
+            if self._kpls_dim > x.shape[1]:  # sparse_algorithm.rs:430-438
+                raise L.InvalidValueError(
+                    L.ERR_INVALID_VALUE,
+                    f"Dimension reduction {self._kpls_dim} should be smaller than actual training input dimensions {x.shape[1]}")
+            from .kpls import pls_rotations
+            w_star = pls_rotations(x, y, self._kpls_dim)  # on the raw data, as the reference does (:440-455)
+        h = SgpHandle(x, y, z, corr=self._corr.code, method=self._method, nugget=self._nugget, device=self._device,
+                      w_star=w_star)
+        d = h.h  # theta components: kpls_dim with KPLS, else the number of inputs
         t = self._theta_tuning
         init = np.asarray(t.init, dtype=np.float64).reshape(-1)
         if init.size not in (1, d):
             h.close()
             raise L.InvalidValueError(L.ERR_INVALID_VALUE,
-                                      f"Initial guess for theta should be either 1-dim or dim of xtrain, got {init.size}")
+                                      "Initial guess for theta should be either 1-dim or dim of xtrain" +
+                                      (" (w_star.ncols())" if w_star is not None else "") + f", got {init.size}")
         theta0 = np.full(d, init[0]) if init.size == 1 else init
         sigma2_0 = float(np.std(y, ddof=1) ** 2)                      # :503-505
         est = self._noise.kind == "Optimized"
@@ -364,6 +421,9 @@ class SgpParams:
             tb = [(v, v) for v in theta0]
         else:
             tb = list(t.bounds) * d if len(t.bounds) == 1 else list(t.bounds)
+            if w_star is not None and len(tb) != d:
+                h.close()
+                raise L.InvalidValueError(L.ERR_INVALID_VALUE, f"theta bounds: one pair or {d} pairs expected, got {len(tb)}")
         params0 = np.concatenate([theta0, [sigma2_0], [self._noise.init] if est else []])
         bounds = tb + [(1e-12, 9.0 * sigma2_0)] + ([tuple(self._noise.bounds)] if est else [])  # :580-592
         for i, (lo, hi) in enumerate(bounds):   # keep every start inside its box
@@ -472,7 +532,13 @@ class SparseGaussianProcess:
         return self._h.z
 
     def dims(self):
-        return self._h.d, 1
+        """(the number of theta components -- kpls_dim under KPLS, else the inputs --, 1), sparse_algorithm.rs:283-285"""
+        return self._h.h, 1
+
+    def w_star(self):
+        """The KPLS weights (d, h) the model was fitted with; the identity without KPLS, as the reference stores it."""
+        w = self._h.w_star()
+        return np.eye(self._h.d) if w is None else w
 
     def woodbury(self):
         s = self._h.state(with_inv=True)
@@ -500,7 +566,9 @@ class SparseGpMix:
     sparse expert per cluster -- Located(z): every expert the same z; Randomized(nz): nz rows of the expert's own cluster, drawn
     with the seed --, and `recombination` "hard" or "smooth"; smooth with heaviside_factor=None (the reference's Smooth(None))
     chooses the factor on one row out of five (`optimize_heaviside_factor`) and retrains on all rows.  n_clusters = 0 (automatic)
-    and kpls_dim are not implemented.  optimize_inducings (an extension, with optimizer="lbfgs"): every expert moves its
+    and kpls_dim are not implemented HERE: a single sparse model takes KPLS through `SgpParams.kpls_dim` (the Rust-shaped
+    builder), and this builder keeps refusing kpls_dim with NotImplementedError("KPLS ...") -- lifting that is a follow-up, which
+    has to edit the test that pins the refusal (tests/test_infill_sparse_cpu.py).  optimize_inducings (an extension, with optimizer="lbfgs"): every expert moves its
     inducing points by the likelihood gradient after its fit (`SgpParams.optimize_inducings`)."""
 
     def __init__(self, corr_spec=1, theta_init=None, theta_bounds=None, kpls_dim=None, n_start=G.GP_OPTIM_N_START, nz=None,
@@ -664,7 +732,7 @@ class SparseGpx:
         corr = str(g.params_._corr)
         expert = {"type_sgp": f"Sgp{corr}Surrogate", "corr": corr, "method": "Fitc" if g.params_._method == FITC else "Vfe",
                   "theta": nd(st["theta"]), "sigma2": st["sigma2"], "noise": st["noise"], "likelihood": st["likelihood"],
-                  "w_star": nd(np.eye(h.d)), "inducings": nd(h.z),
+                  "w_star": nd(g.w_star()), "inducings": nd(h.z),
                   "w_data": {"vec": nd(st["w_vec"].reshape(-1, 1)), "inv": nd(st["w_inv"])},
                   "training_data": [nd(g._xy[0]), nd(g._xy[1])], "nugget": g.params_._nugget}
         return {"recombination": {"Smooth": 1.0}, "experts": [expert], "gp_type": "SparseGp"}
@@ -694,6 +762,14 @@ class SparseGpx:
         method = FITC if e["method"] == "Fitc" else VFE
         params = SgpParams(corr, Inducings.Located(z)).sparse_method(method).nugget(e.get("nugget", G.DEFAULT_NUGGET))
         h = SgpHandle(x, y, z, corr=corr.code, method=method, nugget=params._nugget)
+        w = arr(e["w_star"]) if "w_star" in e else None
+        if w is not None and not (w.shape[0] == w.shape[1] and np.array_equal(w, np.eye(w.shape[0]))):
+            try:  # real KPLS weights: restored before the state goes in (a file with eye(d) loads exactly as it always did)
+                h.set_w_star(w)
+                params.kpls_dim(w.shape[1])
+            except Exception:
+                h.close()
+                raise
         h.finalize(theta, e["sigma2"], e["noise"])
         lk = h.state()["likelihood"]
         if not np.isclose(lk, e["likelihood"], rtol=1e-6, atol=1e-9):

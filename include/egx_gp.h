@@ -693,6 +693,23 @@ int32_t egx_sgp_likelihood_grad_z(egx_sgp *sgp, const double *theta, int64_t the
  * Un-fits the handle: finalize or fit again before predicting.  egx_sgp_get_inducings returns the current points. */
 int32_t egx_sgp_set_inducings(egx_sgp *sgp, const double *z /*nz*d*/);
 int32_t egx_sgp_get_inducings(egx_sgp *sgp, double *z /*nz*d*/);
+/* KPLS dimension reduction of the sparse model (SgpValidParams::fit computes the PLS rotations on the raw (x, y) and carries
+ * w_star through compute_k, fitc, vfe, predict* and sample: sparse_algorithm.rs:429-455, 222-229, 659-687).  w is d x h row-major,
+ * 1 <= h <= d, finite values; otherwise EGX_ERR_INVALID_VALUE ("`kpls_dim` canot be 0!", "Dimension reduction ... should be
+ * smaller than actual training input dimensions ...") and the handle stays as it was.  An all-zero w is accepted (the reference
+ * passes it on a constant PLS residual); evaluations then report their status as values.  Un-fits the handle.  w == NULL with
+ * h == 0 clears the weights: every output is again bit for bit that of a handle that never had any.  While weights are set
+ *   - theta has h components: theta_len is 1 or h in egx_sgp_likelihood / _finalize / _likelihood_grad / _likelihood_grad_z
+ *     ("theta should be either 1-dim or dim of xtrain (w_star.ncols()), got ..."), egx_sgp_get_state writes h thetas;
+ *   - grad of egx_sgp_likelihood_grad / _grad_z is h + 2 long: dL/dtheta_0..h-1, dL/dsigma2, dL/dnoise;
+ *   - egx_sgp_fit / _fit_lbfgs / _fit_lbfgs_z take np = h + 1 + (estimate_noise != 0), and the evaluation budget of egx_sgp_fit
+ *     is clamp(10 h, 25, max_eval);
+ *   - grad_z, the inducing points and their box stay nz x d / d: the points live in the input space;
+ *   - the x-gradients need d * (hcols + 5) <= 20480 with hcols = h for the Matern correlations and 1 otherwise
+ *     (the squared and the absolute exponential collapse theta and w into one coefficient per input).
+ * egx_sgp_get_w_star writes *h (d when no weights are set) and, where w != NULL and weights are set, the d x h weights. */
+int32_t egx_sgp_set_w_star(egx_sgp *sgp, const double *w /*d*h row-major, or NULL*/, int64_t h);
+int32_t egx_sgp_get_w_star(egx_sgp *sgp, double *w /*d*h or NULL*/, int64_t *h);
 /* egx_sgp_fit_lbfgs (phase 1, exactly), then ONE more projected L-BFGS from its winner over [log10 params (np), u (nz*d)],
  * u = (z - z_lo) / (z_hi - z_lo) in [0, 1]: the inducing points move with the parameters, driven by egx_sgp_likelihood_grad_z.
  * z_lo / z_hi (d each) box every inducing point; NULL: the per-column min / max of the training x.  A column with z_hi == z_lo
@@ -717,7 +734,8 @@ int32_t egx_sgp_predict_valvar(egx_sgp *sgp, const double *xq, int64_t m, double
  *   d mean / d x_k = sigma2 sum_j vec_j d r(x, z_j) / d x_k
  *   d var  / d x_k = -2 sigma2 sum_j (W kx)_j d r(x, z_j) / d x_k  where sigma2 - kx^T W kx >= 1e-15, and exactly 0 where
  *                    predict_var clamps (the derivative of the clamped function, as the central difference gives there).
- * xq (m x d) in the units of the training inputs; m = 0 succeeds and does nothing; EGX_ERR_UNSUPPORTED when 6 d > 20480. */
+ * xq (m x d) in the units of the training inputs; m = 0 succeeds and does nothing; EGX_ERR_UNSUPPORTED when 6 d > 20480
+ * (d * (hcols + 5) > 20480 with KPLS weights, egx_sgp_set_w_star). */
 int32_t egx_sgp_predict_gradients(egx_sgp *sgp, const double *xq, int64_t m, double *grad /*m*d*/);
 int32_t egx_sgp_predict_var_gradients(egx_sgp *sgp, const double *xq, int64_t m, double *grad /*m*d*/);
 int32_t egx_sgp_predict_valvar_gradients(egx_sgp *sgp, const double *xq, int64_t m, double *grad_y /*m*d*/,

@@ -318,14 +318,31 @@ class SparseGaussianProcess {
     void finalize(const double *theta, int64_t theta_len, double sigma2, double noise) {
         check(egx_sgp_finalize(h_.get(), theta, theta_len, sigma2, noise));
     }
-    // the likelihood and its closed-form gradient (d + 2: theta.., sigma2, noise; zeros when status != 0): egx_sgp_likelihood_grad
+    // KPLS weights (d x h row-major, 1 <= h <= d; nullptr with h = 0 clears them): egx_sgp_set_w_star.  Un-fits the model; theta
+    // then has h components.  w_star(): (the weights, h); no weights and h = d when none are set.
+    void set_w_star(const double *w, int64_t h) { check(egx_sgp_set_w_star(h_.get(), w, h)); }
+    std::pair<std::vector<double>, int64_t> w_star() const {
+        int64_t h = 0;
+        check(egx_sgp_get_w_star(h_.get(), nullptr, &h));
+        std::vector<double> w((size_t)(d_ * h), std::nan(""));  // (weights are finite: NaN left behind means none are set)
+        check(egx_sgp_get_w_star(h_.get(), w.data(), &h));
+        if (std::isnan(w[0])) w.clear();
+        return {std::move(w), h};
+    }
+    // the number of theta components: h with KPLS weights, else d
+    int64_t n_theta() const {
+        int64_t h = 0;
+        check(egx_sgp_get_w_star(h_.get(), nullptr, &h));
+        return h;
+    }
+    // the likelihood and its closed-form gradient (h + 2: theta.., sigma2, noise; zeros when status != 0): egx_sgp_likelihood_grad
     struct LikelihoodGrad {
         double likelihood;
         std::vector<double> grad;
         int32_t status;
     };
     LikelihoodGrad likelihood_grad(const double *theta, int64_t theta_len, double sigma2, double noise) {
-        LikelihoodGrad r{0.0, std::vector<double>((size_t)(d_ + 2)), 0};
+        LikelihoodGrad r{0.0, std::vector<double>((size_t)(w_star().second + 2)), 0};
         check(egx_sgp_likelihood_grad(h_.get(), theta, theta_len, sigma2, noise, &r.likelihood, r.grad.data(), &r.status));
         return r;
     }
@@ -343,7 +360,7 @@ class SparseGaussianProcess {
         int32_t status;
     };
     LikelihoodGradZ likelihood_grad_z(const double *theta, int64_t theta_len, double sigma2, double noise) {
-        LikelihoodGradZ r{0.0, std::vector<double>((size_t)(d_ + 2)), std::vector<double>((size_t)(nz() * d_)), 0};
+        LikelihoodGradZ r{0.0, std::vector<double>((size_t)(w_star().second + 2)), std::vector<double>((size_t)(nz() * d_)), 0};
         check(egx_sgp_likelihood_grad_z(h_.get(), theta, theta_len, sigma2, noise, &r.likelihood, r.grad.data(), r.grad_z.data(),
                                         &r.status));
         return r;
