@@ -13,6 +13,8 @@
 //                       16x16 inverses A left behind (+ one refinement step for ill-conditioned tiles); the solves after
 //                       the factorisation (launch_trsm_rows) use it too, with the 16x16 diagonal blocks of the 64x64 tile
 //                       inverses.
+//      k_panel_trsm_rows: the same solve for the factorisation's TALL panels (>= "trsm_rows_min" rows): a wave owns a
+//                       16-row tile across all strips, X stays in registers, the block goes through LDS once per 64 rows.
 //   C  k_gemm_stream  : chip-filling trailing updates  C -= P P^T  (lower tiles only) -- the n^3/3 flops -- 128x256
 //      k_gemm_nt_sub    tiles, LDS-DMA ring; smaller launches by the register-staged 128x128 / 64x64 kernel:
 //                       v_mfma_f64_16x16x4_f64, A/B staged through LDS in 16-deep K chunks.
@@ -592,7 +594,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_potf2_reg(double *__restrict__ D
 // blocks on its block diagonal, so strip C reads the 16x16 block (C % 4, C % 4) of tile C / 4 (row stride 64) and takes
 // that tile's refinement flag (`tflags`, one per 64x64 tile, from k_diag_tile_inverses).
 template <int RT, bool POST = false>  // RT: 16-row tiles per workgroup: 1 (panels of small matrices: n / 16 workgroups) or 2
-                                      // (tall panels: the L fragments and the barrier serve two tiles, half the workgroups)
+                                      // (POST solves of >= 4096 rows: the L fragments and the barrier serve two tiles, half the
+                                      //  workgroups; the factorisation's tall panels take k_panel_trsm_rows, below)
 __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, int64_t ldp, const double *__restrict__ L, int64_t ldl,
                                                       const double *__restrict__ lin, int nbk, const int *__restrict__ info,
                                                       int64_t bsP, int64_t bsM, int64_t bsL, int bsI,
@@ -715,6 +718,131 @@ __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, in
             if (k + 1 < nb16) {
                 if (k + 2 < nb16) fetch_l(k + 2);  // into the set strip k just finished with
                 __syncthreads();
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// B'' : the same solve for TALL panels inside a factorisation, with the ownership turned round: a WAVE owns one 16-row
+// tile across all (<= 16) column strips (64 accumulator doubles per lane, the lane layout of k_panel_trsm16's strip tiles),
+// a workgroup is four such waves = 64 rows.  The lane that holds X_k[frow][4 fk ..] after the solve is the lane that needs
+// exactly those four doubles as the B operand of the updates, so X_k goes from the solve into the updates in registers:
+// no X exchange through LDS, no barrier between the waves' arithmetic.  What the waves share is the factored block: per
+// step k the workgroup stages, one step ahead and through registers, the tiles the step reads -- L(C, k) for C > k, and
+// for the solve of tile k + 1 the inverse Linv_{k+1} and the diagonal tile L(k+1, k+1) -- into one of two LDS buffers
+// (rows padded to RB_LD doubles); the barrier that hands a buffer over is the only one left, and the block is read from
+// L2 once per 64 rows instead of once per 32.  Per element the instructions and their order are k_panel_trsm16's:
+// T_C -= X_k L(C, k)^T for k ascending (one RB_MFMA4 chain each, same operand roles), then X = T Linv^T with the
+// refinement step under the same flag -- hence the same bits, and "trsm_rows_min" may move a panel between the two kernels
+// at launch time.  Inside a wave: tile k + 1 is updated first and solved at once, then the other 14 - k update chains.
+// gfx950 (tools/kres.sh): 202 VGPRs + 0 AGPRs = two waves per SIMD, ScratchSize 0, LDS 78336 B dynamic + 16 B static per
+// workgroup = two workgroups per CU.
+// ---------------------------------------------------------------------------------------------
+constexpr int PR_SLOTS = 17;           // staged tiles of a step: Linv_{k+1}, L(k+1, k+1), L(C, k) for C = k + 1 .. 15
+constexpr int PR_TILE = 16 * RB_LD;    // doubles of a staged 16x16 tile
+constexpr int PR_PASSES = (PR_SLOTS + 1) / 2;  // 256 threads stage two tiles per pass, 16 bytes each
+constexpr int PR_LDS_BYTES = 2 * PR_SLOTS * PR_TILE * 8;
+__global__ __launch_bounds__(256, 2) void k_panel_trsm_rows(double *__restrict__ P, int64_t ldp, const double *__restrict__ L,
+                                                            int64_t ldl, const double *__restrict__ lin, int nbk,
+                                                            const int *__restrict__ info, int64_t bsP, int64_t bsM, int64_t bsL,
+                                                            int bsI) {
+    extern __shared__ __attribute__((aligned(16))) double pr_sm[];
+    {   // lock-step batch: matrix blockIdx.z (strides as in k_panel_trsm16)
+        const int64_t z = blockIdx.z;
+        P += z * bsP;
+        L += z * bsM;
+        lin += z * bsL;
+        if (info != nullptr) info += z * bsI;
+    }
+    if (wg_failed_before(info)) return;  // failed pivot earlier: early exit (see k_gemm_nt_sub)
+    __builtin_amdgcn_s_setprio(2);
+    const int tid = threadIdx.x, lane = tid & 63, frow = lane & 15, fk = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nb16 = nbk >> 4;
+    const int prow = ((frow & 3) << 2) | (frow >> 2);  // pi(frow), see k_potf2_reg
+    double *Pw = P + (int64_t)(blockIdx.x * 64 + wave * 16 + frow) * ldp + 4 * fk;  // + 16 C: strip C of this wave's row tile
+    // staging role of this thread: row sr, doubles [sc, sc + 2) of tile 2 p + sh in pass p
+    const int sh = wave >> 1, sr = (tid & 127) >> 3, sc = 2 * (tid & 7);
+    const double *Ls = L + (int64_t)sr * ldl + sc;  // + (16 R) ldl + 16 C: tile (R, C) of the factored block
+    const double *lins = lin + sr * 16 + sc;        // + the strip's 16x16 inverse in the tile-inverse slots (see store_diag)
+    double *sdst = pr_sm + sr * RB_LD + sc;
+    auto stage_src = [&](int k, int s) -> const double * {  // slot s of step k
+        if (s == 0) return lins + (int64_t)((k + 1) >> 2) * 4096 + ((k + 1) & 3) * 256;
+        if (s == 1) return Ls + (int64_t)(16 * (k + 1)) * ldl + 16 * (k + 1);
+        return Ls + (int64_t)(16 * (k + s - 1)) * ldl + 16 * k;
+    };
+    d2_t st[PR_PASSES];
+    auto stage_load = [&](int k) {  // step k reads nb16 + 1 - k slots
+#pragma unroll
+        for (int p = 0; p < PR_PASSES; p++)
+            if (2 * p < PR_SLOTS - k && 2 * p + sh < nb16 + 1 - k) st[p] = *reinterpret_cast<const d2_t *>(stage_src(k, 2 * p + sh));
+    };
+    auto stage_store = [&](int k) {
+#pragma unroll
+        for (int p = 0; p < PR_PASSES; p++)
+            if (2 * p < PR_SLOTS - k && 2 * p + sh < nb16 + 1 - k)
+                *reinterpret_cast<d2_t *>(sdst + ((k & 1) * PR_SLOTS + 2 * p + sh) * PR_TILE) = st[p];
+    };
+    if (nb16 > 1) stage_load(0);  // (in front of the row tile: these come from L2, the tile from HBM, and loads return in order)
+    double4_t acc[16];  // strip C of the row tile: lane (frow, fk), register q <-> T[frow][16 C + 4 fk + q]
+#pragma unroll
+    for (int C = 0; C < 16; C++)
+        if (C < nb16) {
+            const d2_t v0 = *reinterpret_cast<const d2_t *>(Pw + 16 * C), v1 = *reinterpret_cast<const d2_t *>(Pw + 16 * C + 2);
+            acc[C] = double4_t{v0[0], v0[1], v1[0], v1[1]};
+        }
+    // the strips' refinement flags (k_potf2_reg left them beside the 16x16 inverses), bit C of a wave-uniform mask
+    const double rflag = (lane < nb16) ? lin[(int64_t)(lane >> 2) * 4096 + 1024 + (lane & 3)] : 0.0;
+    const unsigned int refine = (unsigned int)__builtin_amdgcn_ballot_w64(rflag != 0.0);
+    // solve strip k: X_k = T_k Linv_k^T (+ one refinement step, see k_potf2_reg) -> global; n: Linv_k, r: L(k, k), rows pi(frow)
+    auto solve = [&](int k, d2_t n01, d2_t n23, d2_t r01, d2_t r23) -> double4_t {
+        double4_t x = double4_t{0.0, 0.0, 0.0, 0.0};
+        RB_MFMA4(x, 0, n01, n23, acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+        if ((refine >> k) & 1u) {
+            const d2_t l01 = d2_t{(4 * fk <= prow) ? r01[0] : 0.0, (4 * fk + 1 <= prow) ? r01[1] : 0.0};
+            const d2_t l23 = d2_t{(4 * fk + 2 <= prow) ? r23[0] : 0.0, (4 * fk + 3 <= prow) ? r23[1] : 0.0};
+            double4_t rs = acc[k];
+            RB_MFMA4(rs, 1, l01, l23, x[0], x[1], x[2], x[3]);
+            RB_MFMA4(x, 0, n01, n23, rs[0], rs[1], rs[2], rs[3]);
+        }
+        double *dst = Pw + 16 * k;
+        *reinterpret_cast<d2_t *>(dst) = d2_t{x[0], x[1]};
+        *reinterpret_cast<d2_t *>(dst + 2) = d2_t{x[2], x[3]};
+        return x;
+    };
+    double4_t x;
+    {   // strip 0 needs nothing but its own inverse and diagonal tile: straight from L2
+        const double *n0 = lin + prow * 16 + 4 * fk, *l0 = L + (int64_t)prow * ldl + 4 * fk;
+        x = solve(0, *reinterpret_cast<const d2_t *>(n0), *reinterpret_cast<const d2_t *>(n0 + 2),
+                  *reinterpret_cast<const d2_t *>(l0), *reinterpret_cast<const d2_t *>(l0 + 2));
+    }
+    if (nb16 > 1) stage_store(0);
+    __syncthreads();
+    // Step k: every tile right of strip k receives X_k (in registers); tile k + 1 first, solved at once, so that its
+    // dependent chain is behind the independent updates.  The next step's tiles travel global -> registers -> LDS meanwhile.
+#pragma unroll
+    for (int k = 0; k < 15; k++) {
+        if (k + 1 < nb16) {
+            const double *buf = pr_sm + (k & 1) * (PR_SLOTS * PR_TILE) + prow * RB_LD + 4 * fk;
+            if (k + 2 < nb16) stage_load(k + 1);
+            {
+                const d2_t a01 = *reinterpret_cast<const d2_t *>(buf + 2 * PR_TILE), a23 = *reinterpret_cast<const d2_t *>(buf + 2 * PR_TILE + 2);
+                RB_MFMA4(acc[k + 1], 1, a01, a23, x[0], x[1], x[2], x[3]);
+            }
+            const double4_t xn = solve(k + 1, *reinterpret_cast<const d2_t *>(buf), *reinterpret_cast<const d2_t *>(buf + 2),
+                                       *reinterpret_cast<const d2_t *>(buf + PR_TILE), *reinterpret_cast<const d2_t *>(buf + PR_TILE + 2));
+#pragma unroll
+            for (int C = k + 2; C < 16; C++)
+                if (C < nb16) {
+                    const double *a = buf + (C - k + 1) * PR_TILE;
+                    const d2_t a01 = *reinterpret_cast<const d2_t *>(a), a23 = *reinterpret_cast<const d2_t *>(a + 2);
+                    RB_MFMA4(acc[C], 1, a01, a23, x[0], x[1], x[2], x[3]);
+                }
+            x = xn;
+            if (k + 2 < nb16) {
+                stage_store(k + 1);
+                __syncthreads();  // buffer (k + 1) & 1 is complete; everybody has finished reading it in step k - 1
             }
         }
     }
@@ -1060,6 +1188,7 @@ static std::atomic<int> g_trsv_stall{0};  // egx_set_tuning "trsv_stall" (test b
 #define EGX_TRSV_STALL 0
 #endif
 static std::atomic<int> g_trsv_fused{1};          // EGX_TRSV_FUSED=0: the back-substitution gamma = C^-T rho as one launch PER BLOCK (rounds 1-5) instead of one launch
+static std::atomic<int> g_trsm_rows_min{4096};    // EGX_TRSM_ROWS_MIN: rows (of ONE matrix) from which a panel of the factorisation takes k_panel_trsm_rows (same bits)
 static std::atomic<int> g_potrf_left{1};          // EGX_POTRF_LEFT: left-looking group updates (factor and C^-T rider) 0 never, 1 by schedule.h, 2 always
 constexpr int kTrsmGroupPanels = 4;   // panels per update in the solves after the factorisation
 static_assert(kPlanPanel == kNB, "potrf_plan.h plans in panels of kNB columns");
@@ -1078,6 +1207,7 @@ int chol_init() {
         if (const char *e = std::getenv("EGX_LUR_SIDE")) g_lur_side = std::atoi(e);
         if (const char *e = std::getenv("EGX_TRSV_FUSED")) g_trsv_fused = std::atoi(e);
         if (const char *e = std::getenv("EGX_POTRF_LEFT")) g_potrf_left = std::atoi(e);
+        if (const char *e = std::getenv("EGX_TRSM_ROWS_MIN")) g_trsm_rows_min = std::atoi(e);
         auto set = [](const void *fn, int bytes) {
             hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             if (e != hipSuccess && rc_once == EGX_SUCCESS) {
@@ -1093,6 +1223,7 @@ int chol_init() {
         set(reinterpret_cast<const void *>(&k_gemm_stream<false, true>), ST_LDS_BYTES);
         set(reinterpret_cast<const void *>(&k_gemm_stream<true, false, 1>), ST_LDS_BYTES);
         set(reinterpret_cast<const void *>(&k_gemm_stream<true, false, 2>), ST_LDS_BYTES);
+        set(reinterpret_cast<const void *>(&k_panel_trsm_rows), PR_LDS_BYTES);
     });
     return rc_once;
 }
@@ -1121,7 +1252,7 @@ int set_knob(const char *name, int value) {
     struct { const char *n; std::atomic<int> *v; } tab[] = {{"potrf_group", &g_potrf_group}, {"stream_min", &g_stream_min_tiles},
                                                            {"gemm_small", &g_gemm_small_max}, {"look_min", &g_look_min_cols},
                                                            {"lur_side", &g_lur_side},         {"potrf_left", &g_potrf_left},
-                                                           {"trsv_fused", &g_trsv_fused}};
+                                                           {"trsv_fused", &g_trsv_fused},     {"trsm_rows_min", &g_trsm_rows_min}};
     for (auto &e : tab)
         if (std::string(name) == e.n) return e.v->exchange(value);
 #ifdef EGX_TEST_HOOKS
@@ -1343,10 +1474,11 @@ int launch_potrf(hipStream_t s, double *M, int64_t ld, int n_pad, int m_tot, dou
             const int64_t ldp = fac ? ld : inv->ldw, sP = fac ? pb.sM : inv->sW;
             const double *L = M + (int64_t)p.k0 * ld + p.k0;
             const double *lin = dinv + (int64_t)(p.k0 / 64) * 4096;
-            if (rows >= 4096)  // tall panels: two 16-row tiles per workgroup (+1 %, profiles/r02_run34_*)
-                hipLaunchKernelGGL((k_panel_trsm16<2, false>), dim3(rows / 32, 1, nz), dim3(256), 0, st, P, ldp, L, ld, lin, p.K,
-                                   (const int *)info, sP, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
-            else
+            // (by the rows of ONE matrix, never by the batch count; the kernels give the same bits, so the knob is a launch-time one)
+            if (rows >= g_trsm_rows_min && rows % 64 == 0)  // tall panels: a wave per 16-row tile, the block through LDS
+                hipLaunchKernelGGL(k_panel_trsm_rows, dim3(rows / 64, 1, nz), dim3(256), PR_LDS_BYTES, st, P, ldp, L, ld, lin, p.K,
+                                   (const int *)info, sP, pb.sM, pb.sD, pb.sI);
+            else  // (the two-tile form <2> that tall panels took before serves the solves after the factorisation only)
                 hipLaunchKernelGGL((k_panel_trsm16<1, false>), dim3(rows / 16, 1, nz), dim3(256), 0, st, P, ldp, L, ld, lin, p.K,
                                    (const int *)info, sP, pb.sM, pb.sD, pb.sI, (const double *)nullptr);
             break;

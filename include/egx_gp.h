@@ -129,6 +129,9 @@ void egx_chain_stats(int64_t *aborted, int64_t *retried);
  *                      wait that ran out the launch-per-block form is run once, counted by egx_chain_stats; EGX_ERR_HIP only if that
  *                      fails too or with "pipe_retry" = 0 -- never a wrong gamma); 0: one launch per 256-column block (rounds 1-5).
  *                      The same sums in the same order either way: the same bits
+ *   "trsm_rows_min"    panels of a factorisation with at least this many rows (of ONE matrix; default 4096) are solved by the
+ *                      row-owning kernel k_panel_trsm_rows, shorter ones by k_panel_trsm16; a value beyond any n switches the
+ *                      kernel off.  The same instructions on the same values either way: the same bits, at launch time
  * (the test hook "pipe_stall" exists only in the test build of the library, -DEGX_TEST_HOOKS).  They move launches between streams and kernels between tile shapes, never the
  * arithmetic inside a kernel; "potrf_group" / "stream_min" / "gemm_small" / "potrf_left" / "pipe" change which kernel
  * updates a block, or the order in which updates are summed, hence the rounding -- and "potrf_left" / "pipe" /
