@@ -15,6 +15,8 @@
 //                       inverses.
 //      k_panel_trsm_rows: the same solve for the factorisation's TALL panels (>= "trsm_rows_min" rows): a wave owns a
 //                       16-row tile across all strips, X stays in registers, the block goes through LDS once per 64 rows.
+//                       (Both, the TRSM slots of A and the chain launches' TRSM task call ONE strip solve / update body,
+//                       panel_strip.h: a tile gets the same bits whichever kernel owns it.)
 //   C  k_gemm_stream  : chip-filling trailing updates  C -= P P^T  (lower tiles only) -- the n^3/3 flops -- 128x256
 //      k_gemm_nt_sub    tiles, LDS-DMA ring; smaller launches by the register-staged 128x128 / 64x64 kernel:
 //                       v_mfma_f64_16x16x4_f64, A/B staged through LDS in 16-deep K chunks.
@@ -580,8 +582,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_potf2_reg(double *__restrict__ D
 // B' (round 2): panel solve  X = P L^-T  below a diagonal block factored by k_potf2_reg, with the same 16x16 machinery:
 // one workgroup = ONE 16-row tile of the panel x all (<= 16) column strips, as FP64-MFMA accumulators of its four waves
 // (wave w owns the strips C = w mod 4: four tiles, 32 registers).  Per strip k: the wave that owns it turns its tile
-// into X_k = T_k Linv_k^T (Linv_k and the refinement flag were left by k_potf2_reg in the tile-inverse slots; the
-// refinement step is the diagonal-block kernel's), puts it into LDS (two buffers, one barrier per strip) and global;
+// into X_k = T_k Linv_k^T (Linv_k and the refinement flag were left by k_potf2_reg in the tile-inverse slots; solve,
+// refinement step and update are panel_strip.h's), puts it into LDS (two buffers, one barrier per strip) and global;
 // every wave then applies  T_C -= X_k L(C,k)^T  to its strips right of k, the L(C,k) fragments (rows pi(frow), 32
 // contiguous bytes per lane) straight from the factored block in L2 and already in flight when the barrier opens.
 // No global round trip between the strips (the round-1 kernel re-read its 64-row slab from global four times per block:
@@ -615,24 +617,17 @@ __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, in
     const int tid = threadIdx.x, lane = tid & 63, frow = lane & 15, fk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nb16 = nbk >> 4;
-    const int prow = ((frow & 3) << 2) | (frow >> 2);  // pi(frow), see k_potf2_reg
+    const int prow = rb_prow(frow);
     double *Pw = P + (int64_t)(blockIdx.x * 16 * RT + frow) * ldp + 4 * fk;  // + 16 r ldp + 16 C: row tile r, strip C
     const double *Lp = L + (int64_t)prow * ldl + 4 * fk;                     // + (16 C) ldl + 16 k: row pi(frow) of tile (C, k)
-    double acc[RT][16];                   // row tile r, slot t <-> strip C = 4 t + wave
+    double4_t acc[RT][4];                 // row tile r, slot t <-> strip C = 4 t + wave
     d2_t n01[4], n23[4], l01[4], l23[4];  // for the strips this wave solves: Linv fragments, masked fragments of L(C, C)
     bool refine[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) {
         const int C = 4 * t + wave, Cc = C < nb16 ? C : 0;
 #pragma unroll
-        for (int r = 0; r < RT; r++) {
-            const double *src = Pw + (int64_t)(16 * r) * ldp + 16 * Cc;
-            const d2_t v0 = *reinterpret_cast<const d2_t *>(src), v1 = *reinterpret_cast<const d2_t *>(src + 2);
-            acc[r][4 * t] = v0[0];
-            acc[r][4 * t + 1] = v0[1];
-            acc[r][4 * t + 2] = v1[0];
-            acc[r][4 * t + 3] = v1[1];
-        }
+        for (int r = 0; r < RT; r++) acc[r][t] = rb_load4(Pw + (int64_t)(16 * r) * ldp + 16 * Cc);
         // everything a solve needs besides its tile comes from L2 (~1 us): fetched here, not when the strip comes up
         constexpr int LS = POST ? 64 : 16;  // row stride of the 16x16 inverse
         const double *lk = lin + (int64_t)(Cc >> 2) * 4096 + (Cc & 3) * (POST ? 16 * 64 + 16 : 256);
@@ -640,27 +635,17 @@ __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, in
         n23[t] = *reinterpret_cast<const d2_t *>(lk + prow * LS + 4 * fk + 2);
         refine[t] = POST ? (tflags != nullptr && tflags[Cc >> 2] != 0.0) : (lin[(int64_t)(Cc >> 2) * 4096 + 1024 + (Cc & 3)] != 0.0);
         const double *ld16 = Lp + (int64_t)(16 * Cc) * ldl + 16 * Cc;
-        const d2_t r01 = *reinterpret_cast<const d2_t *>(ld16), r23 = *reinterpret_cast<const d2_t *>(ld16 + 2);
-        l01[t] = d2_t{(4 * fk <= prow) ? r01[0] : 0.0, (4 * fk + 1 <= prow) ? r01[1] : 0.0};
-        l23[t] = d2_t{(4 * fk + 2 <= prow) ? r23[0] : 0.0, (4 * fk + 3 <= prow) ? r23[1] : 0.0};
+        l01[t] = *reinterpret_cast<const d2_t *>(ld16);
+        l23[t] = *reinterpret_cast<const d2_t *>(ld16 + 2);
+        rb_mask_lower(l01[t], l23[t], prow, 4 * fk);
     }
-    // solve strip k = 4 t + wave: X_k = T_k Linv_k^T (+ one refinement step, see k_potf2_reg) -> LDS buffer k & 1, global
+    // solve strip k = 4 t + wave (panel_strip.h) -> LDS buffer k & 1, global
     auto solve = [&](int t, int k) {
 #pragma unroll
         for (int r = 0; r < RT; r++) {
-            double4_t x = double4_t{0.0, 0.0, 0.0, 0.0};
-            RB_MFMA4(x, 0, n01[t], n23[t], acc[r][4 * t], acc[r][4 * t + 1], acc[r][4 * t + 2], acc[r][4 * t + 3]);
-            if (refine[t]) {
-                double4_t rs = double4_t{acc[r][4 * t], acc[r][4 * t + 1], acc[r][4 * t + 2], acc[r][4 * t + 3]};
-                RB_MFMA4(rs, 1, l01[t], l23[t], x[0], x[1], x[2], x[3]);
-                RB_MFMA4(x, 0, n01[t], n23[t], rs[0], rs[1], rs[2], rs[3]);
-            }
-            double *xs = X[k & 1][r] + frow * RB_LD + 4 * fk;
-            *reinterpret_cast<d2_t *>(xs) = d2_t{x[0], x[1]};
-            *reinterpret_cast<d2_t *>(xs + 2) = d2_t{x[2], x[3]};
-            double *dst = Pw + (int64_t)(16 * r) * ldp + 16 * k;
-            *reinterpret_cast<d2_t *>(dst) = d2_t{x[0], x[1]};
-            *reinterpret_cast<d2_t *>(dst + 2) = d2_t{x[2], x[3]};
+            const double4_t x = rb_strip_solve(acc[r][t], n01[t], n23[t], l01[t], l23[t], refine[t]);
+            rb_store4(X[k & 1][r] + frow * RB_LD + 4 * fk, x);
+            rb_store4(Pw + (int64_t)(16 * r) * ldp + 16 * k, x);
         }
     };
     // The L(C, k) fragments (A' operands) of strip k for the four slots, in two sets (k & 1): fetched TWO strips ahead of
@@ -677,16 +662,9 @@ __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, in
         }
     };
     // T_C -= X_k L(C, k)^T for slot t (strip C = 4 t + wave), all row tiles
-    auto update = [&](int t, int k, const d2_t (&b01)[RT], const d2_t (&b23)[RT]) {
+    auto update = [&](int t, int k, const double4_t (&xk)[RT]) {
 #pragma unroll
-        for (int r = 0; r < RT; r++) {
-            double4_t c4 = double4_t{acc[r][4 * t], acc[r][4 * t + 1], acc[r][4 * t + 2], acc[r][4 * t + 3]};
-            RB_MFMA4(c4, 1, a01[k & 1][t], a23[k & 1][t], b01[r][0], b01[r][1], b23[r][0], b23[r][1]);
-            acc[r][4 * t] = c4[0];
-            acc[r][4 * t + 1] = c4[1];
-            acc[r][4 * t + 2] = c4[2];
-            acc[r][4 * t + 3] = c4[3];
-        }
+        for (int r = 0; r < RT; r++) rb_strip_update(acc[r][t], a01[k & 1][t], a23[k & 1][t], xk[r]);
     };
     fetch_l(0);
     if (nb16 > 1) fetch_l(1);
@@ -697,23 +675,19 @@ __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, in
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         if (k < nb16) {
-            d2_t b01[RT], b23[RT];
+            double4_t xk[RT];
 #pragma unroll
-            for (int r = 0; r < RT; r++) {
-                const double *xs = X[k & 1][r] + frow * RB_LD + 4 * fk;
-                b01[r] = *reinterpret_cast<const d2_t *>(xs);
-                b23[r] = *reinterpret_cast<const d2_t *>(xs + 2);
-            }
+            for (int r = 0; r < RT; r++) xk[r] = rb_load4(X[k & 1][r] + frow * RB_LD + 4 * fk);
             const int tn = (k + 1) >> 2;  // slot of strip k + 1 in the wave that owns it
             const bool next_owner = wave == ((k + 1) & 3) && k + 1 < nb16;
             if (next_owner) {
-                update(tn, k, b01, b23);
+                update(tn, k, xk);
                 solve(tn, k + 1);
             }
 #pragma unroll
             for (int t = 0; t < 4; t++) {
                 const int C = 4 * t + wave;
-                if (C > k && C < nb16 && !(next_owner && t == tn)) update(t, k, b01, b23);
+                if (C > k && C < nb16 && !(next_owner && t == tn)) update(t, k, xk);
             }
             if (k + 1 < nb16) {
                 if (k + 2 < nb16) fetch_l(k + 2);  // into the set strip k just finished with
@@ -732,10 +706,10 @@ __global__ __launch_bounds__(256) void k_panel_trsm16(double *__restrict__ P, in
 // step k the workgroup stages, one step ahead and through registers, the tiles the step reads -- L(C, k) for C > k, and
 // for the solve of tile k + 1 the inverse Linv_{k+1} and the diagonal tile L(k+1, k+1) -- into one of two LDS buffers
 // (rows padded to RB_LD doubles); the barrier that hands a buffer over is the only one left, and the block is read from
-// L2 once per 64 rows instead of once per 32.  Per element the instructions and their order are k_panel_trsm16's:
-// T_C -= X_k L(C, k)^T for k ascending (one RB_MFMA4 chain each, same operand roles), then X = T Linv^T with the
-// refinement step under the same flag -- hence the same bits, and "trsm_rows_min" may move a panel between the two kernels
-// at launch time.  Inside a wave: tile k + 1 is updated first and solved at once, then the other 14 - k update chains.
+// L2 once per 64 rows instead of once per 32.  The arithmetic is panel_strip.h's, as in k_panel_trsm16 -- rb_strip_update
+// for k ascending, then the solve with the refinement step under the same flag -- hence the same bits, and "trsm_rows_min"
+// may move a panel between the two kernels at launch time.  Inside a wave: tile k + 1 is updated first and solved at once,
+// then the other 14 - k update chains.
 // gfx950 (tools/kres.sh): 202 VGPRs + 0 AGPRs = two waves per SIMD, ScratchSize 0, LDS 78336 B dynamic + 16 B static per
 // workgroup = two workgroups per CU.
 // ---------------------------------------------------------------------------------------------
@@ -760,7 +734,7 @@ __global__ __launch_bounds__(256, 2) void k_panel_trsm_rows(double *__restrict__
     const int tid = threadIdx.x, lane = tid & 63, frow = lane & 15, fk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nb16 = nbk >> 4;
-    const int prow = ((frow & 3) << 2) | (frow >> 2);  // pi(frow), see k_potf2_reg
+    const int prow = rb_prow(frow);
     double *Pw = P + (int64_t)(blockIdx.x * 64 + wave * 16 + frow) * ldp + 4 * fk;  // + 16 C: strip C of this wave's row tile
     // staging role of this thread: row sr, doubles [sc, sc + 2) of tile 2 p + sh in pass p
     const int sh = wave >> 1, sr = (tid & 127) >> 3, sc = 2 * (tid & 7);
@@ -788,27 +762,18 @@ __global__ __launch_bounds__(256, 2) void k_panel_trsm_rows(double *__restrict__
     double4_t acc[16];  // strip C of the row tile: lane (frow, fk), register q <-> T[frow][16 C + 4 fk + q]
 #pragma unroll
     for (int C = 0; C < 16; C++)
-        if (C < nb16) {
-            const d2_t v0 = *reinterpret_cast<const d2_t *>(Pw + 16 * C), v1 = *reinterpret_cast<const d2_t *>(Pw + 16 * C + 2);
-            acc[C] = double4_t{v0[0], v0[1], v1[0], v1[1]};
-        }
+        if (C < nb16) acc[C] = rb_load4(Pw + 16 * C);
     // the strips' refinement flags (k_potf2_reg left them beside the 16x16 inverses), bit C of a wave-uniform mask
     const double rflag = (lane < nb16) ? lin[(int64_t)(lane >> 2) * 4096 + 1024 + (lane & 3)] : 0.0;
     const unsigned int refine = (unsigned int)__builtin_amdgcn_ballot_w64(rflag != 0.0);
-    // solve strip k: X_k = T_k Linv_k^T (+ one refinement step, see k_potf2_reg) -> global; n: Linv_k, r: L(k, k), rows pi(frow)
-    auto solve = [&](int k, d2_t n01, d2_t n23, d2_t r01, d2_t r23) -> double4_t {
-        double4_t x = double4_t{0.0, 0.0, 0.0, 0.0};
-        RB_MFMA4(x, 0, n01, n23, acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+    // solve strip k (panel_strip.h) -> global; n: Linv_k, l: L(k, k), rows pi(frow)
+    auto solve = [&](int k, d2_t n01, d2_t n23, d2_t l01, d2_t l23) -> double4_t {
+        double4_t x = rb_strip_solve(acc[k], n01, n23);
         if ((refine >> k) & 1u) {
-            const d2_t l01 = d2_t{(4 * fk <= prow) ? r01[0] : 0.0, (4 * fk + 1 <= prow) ? r01[1] : 0.0};
-            const d2_t l23 = d2_t{(4 * fk + 2 <= prow) ? r23[0] : 0.0, (4 * fk + 3 <= prow) ? r23[1] : 0.0};
-            double4_t rs = acc[k];
-            RB_MFMA4(rs, 1, l01, l23, x[0], x[1], x[2], x[3]);
-            RB_MFMA4(x, 0, n01, n23, rs[0], rs[1], rs[2], rs[3]);
+            rb_mask_lower(l01, l23, prow, 4 * fk);
+            rb_strip_refine(x, acc[k], n01, n23, l01, l23);
         }
-        double *dst = Pw + 16 * k;
-        *reinterpret_cast<d2_t *>(dst) = d2_t{x[0], x[1]};
-        *reinterpret_cast<d2_t *>(dst + 2) = d2_t{x[2], x[3]};
+        rb_store4(Pw + 16 * k, x);
         return x;
     };
     double4_t x;
@@ -826,18 +791,13 @@ __global__ __launch_bounds__(256, 2) void k_panel_trsm_rows(double *__restrict__
         if (k + 1 < nb16) {
             const double *buf = pr_sm + (k & 1) * (PR_SLOTS * PR_TILE) + prow * RB_LD + 4 * fk;
             if (k + 2 < nb16) stage_load(k + 1);
-            {
-                const d2_t a01 = *reinterpret_cast<const d2_t *>(buf + 2 * PR_TILE), a23 = *reinterpret_cast<const d2_t *>(buf + 2 * PR_TILE + 2);
-                RB_MFMA4(acc[k + 1], 1, a01, a23, x[0], x[1], x[2], x[3]);
-            }
+            rb_strip_update(acc[k + 1], buf + 2 * PR_TILE, x);
             const double4_t xn = solve(k + 1, *reinterpret_cast<const d2_t *>(buf), *reinterpret_cast<const d2_t *>(buf + 2),
                                        *reinterpret_cast<const d2_t *>(buf + PR_TILE), *reinterpret_cast<const d2_t *>(buf + PR_TILE + 2));
 #pragma unroll
             for (int C = k + 2; C < 16; C++)
                 if (C < nb16) {
-                    const double *a = buf + (C - k + 1) * PR_TILE;
-                    const d2_t a01 = *reinterpret_cast<const d2_t *>(a), a23 = *reinterpret_cast<const d2_t *>(a + 2);
-                    RB_MFMA4(acc[C], 1, a01, a23, x[0], x[1], x[2], x[3]);
+                    rb_strip_update(acc[C], buf + (C - k + 1) * PR_TILE, x);
                 }
             x = xn;
             if (k + 2 < nb16) {

@@ -16,7 +16,7 @@
 //                          resident, so launches that share the chip cannot starve each other's diagonal blocks
 //   everybody (the DIAG    workers: TASK ticket -> (task, matrix) from a host-built list in an order in which every task
 //   workgroups afterwards) depends on EARLIER tasks only; a worker that finishes takes the next ticket
-//     TRSM(p, rows)        64 * RT rows of the panel below diagonal block p: the register-resident 16-row-tile solve of
+//     TRSM(p, rows)        64 rows of the panel below diagonal block p: the register-resident 16-row-tile solve of
 //                          k_panel_trsm16, driven by the strips as they are published (two workgroup barriers per strip,
 //                          the fragments of the next strip prefetched whenever that strip is already there)
 //     FINE(p, i, j)        64 x 64 tile of block column p + 1 (the NEXT panel: on the chain) -= P_p P_p^T, QUARTER BY QUARTER of the
@@ -41,8 +41,9 @@
 // A task first waits (ONE lane polls, relaxed loads + s_sleep), then ONE agent-scope acquire drops the stale lines of its
 // CU's L1, a workgroup barrier, then plain loads.
 //
-// ARITHMETIC.  DIAG and TRSM do exactly what k_potf2_reg / k_panel_trsm16 do (same instructions on the same values: a
-// group of ONE panel gives the same bits as the separate launches, tools/pipe_check.hip); FINE / COARSE add their K = 256
+// ARITHMETIC.  DIAG and TRSM do exactly what k_potf2_reg / k_panel_trsm16 do (DIAG is the same rb_factor_block, TRSM calls
+// the strip solve / update body of panel_strip.h that every panel solve calls: a group of ONE panel gives the same bits as
+// the separate launches, tools/pipe_check.hip); FINE / COARSE add their K = 256
 // products in an order of their own (fixed: a matrix gets the same bits alone and in a lock-step batch, on any grid size).
 #include "egx_internal.h"
 #include "dev_mem.h"
@@ -194,17 +195,18 @@ __device__ __forceinline__ int pipe_wg_wait(int *s_ctl, F &&waits) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// TRSM: 64 RT rows of the panel below diagonal block p.  Wave w: row-tile group w / 4 (RT tiles of 16 rows), strips
-// C = w % 4 (mod 4) of those tiles as FP64-MFMA accumulators (k_panel_trsm16's layout and arithmetic).  What a strip
+// TRSM: 64 rows of the panel below diagonal block p.  Wave w: row tile w / 4 (16 rows), strips C = w % 4 (mod 4) of that
+// tile as FP64-MFMA accumulators (k_panel_trsm16's layout; the arithmetic is panel_strip.h's).  What a strip
 // needs from the DIAG role -- its column of the factor below and including the diagonal tile, the tile's inverse and
 // refinement flag -- is STAGED through LDS by the whole workgroup (one agent-scope 32-byte piece per thread; two buffers:
 // strip k + 1 is fetched, whenever it is already published, while strip k is being applied).
 // ---------------------------------------------------------------------------------------------
-constexpr int kTrsmXDoubles = 2 * 4 * 2 * 16 * RB_LD;  // X_k of 4 row-tile groups x (up to) 2 tiles, two buffers
+// X_k of the 4 row tiles, two buffers.  (A tile takes every other 16-row slot: packing them moves nothing but addresses, yet
+// the role then saves three more registers on entry -- 12 bytes of scratch in both chain kernels.)
+constexpr int kTrsmXDoubles = 2 * 4 * 2 * 16 * RB_LD;
 constexpr int kTrsmLBuf = 256 * RB_LD + 16 * RB_LD + 8;  // strip column (row r of the block at r * RB_LD), Linv_k, flag
 static_assert(kTrsmXDoubles + 2 * kTrsmLBuf <= kFineStage2 * 4, "LDS of the TRSM role");
 
-template <int RT>
 __device__ __noinline__ int pipe_role_trsm(pipe_kargs_t ka, pipe_lds_t sm3, long long *tr, int z, int p, int c0) {
     const PipeArgs a = pipe_kargs(ka);
     z = pipe_uniform(z), p = pipe_uniform(p), c0 = pipe_uniform(c0);
@@ -224,14 +226,13 @@ __device__ __noinline__ int pipe_role_trsm(pipe_kargs_t ka, pipe_lds_t sm3, long
     const int tid = threadIdx.x, lane = tid & 63, frow = lane & 15, fk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, sw = wave & 3;
-    const int prow = ((frow & 3) << 2) | (frow >> 2);  // pi(frow), see rb_factor_block
+    const int prow = rb_prow(frow);
     // the rows' columns of this panel have received the previous panel (fine tiles), and strip 0 is there
     if (tid == 0) {
         int r = load_flag(info) != 0 ? 1 : 0;
         if (p == 0 && a.ext_need && r == 0) r = pipe_wait_ge(a.sync + 3, a.ext_need, a.sync, info, a.timeout, (9 << 28) | (c0 & 0xfffff));
-        if (p > 0)
-            for (int c = 0; c < RT && r == 0; c++)
-                r = pipe_wait_ge(S + a.off_fcnt + P * a.NC + c0 + c, nbk / 64, a.sync, info, a.timeout, (1 << 28) | ((p) << 20) | ((c0) & 0xfffff));
+        if (p > 0 && r == 0)
+            r = pipe_wait_ge(S + a.off_fcnt + P * a.NC + c0, nbk / 64, a.sync, info, a.timeout, (1 << 28) | ((p) << 20) | ((c0) & 0xfffff));
         if (r == 0) r = pipe_wait_ge(S + 1, base + 1, a.sync, info, a.timeout, (2 << 28) | ((p) << 20) | ((c0) & 0xfffff));
         if (r == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         s_ctl[0] = r;
@@ -247,20 +248,12 @@ __device__ __noinline__ int pipe_role_trsm(pipe_kargs_t ka, pipe_lds_t sm3, long
     }
     int avail = s_ctl[1];  // strips published when thread 0 last looked (>= base + 1)
     if (tr && threadIdx.x == 0) tr[3] = wall_clock64();
-    double *Pw = Mz + (int64_t)(64 * c0 + grp * RT * 16 + frow) * a.ld + k0 + 4 * fk;  // + 16 r ld + 16 C: row tile r, strip C
-    double acc[RT][16];  // row tile r, slot t <-> strip C = 4 t + sw
+    double *Pw = Mz + (int64_t)(64 * c0 + grp * 16 + frow) * a.ld + k0 + 4 * fk;  // + 16 C: strip C of the row tile
+    double4_t acc[4];  // slot t <-> strip C = 4 t + sw
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-        const int C = 4 * t + sw, Cc = C < nb16 ? C : 0;
-#pragma unroll
-        for (int r = 0; r < RT; r++) {
-            const double *src = Pw + (int64_t)(16 * r) * a.ld + 16 * Cc;
-            const d2_t v0 = *reinterpret_cast<const d2_t *>(src), v1 = *reinterpret_cast<const d2_t *>(src + 2);
-            acc[r][4 * t] = v0[0];
-            acc[r][4 * t + 1] = v0[1];
-            acc[r][4 * t + 2] = v1[0];
-            acc[r][4 * t + 3] = v1[1];
-        }
+        const int C = 4 * t + sw;
+        acc[t] = rb_load4(Pw + 16 * (C < nb16 ? C : 0));
     }
     double *Xs = sm, *Ls = sm + kTrsmXDoubles;
     // staging of strip k: thread -> row tid / 4 of the diagonal block, doubles [4 (tid % 4), + 4) of the strip's 16 columns
@@ -294,10 +287,9 @@ __device__ __noinline__ int pipe_role_trsm(pipe_kargs_t ka, pipe_lds_t sm3, long
         }
         if (tid == 64) Lb[256 * RB_LD + 16 * RB_LD] = sflag;
     };
-    auto xbuf = [&](int k, int r) { return Xs + ((size_t)((k & 1) * 4 + grp) * 2 + r) * (16 * RB_LD); };
-    // solve strip k (slot k / 4 of the waves with sw == k % 4): X_k = T_k Linv_k^T (+ one refinement step) -> LDS, global
+    auto xbuf = [&](int k) { return Xs + (size_t)((k & 1) * 4 + grp) * (2 * 16 * RB_LD) + frow * RB_LD + 4 * fk; };
+    // solve strip k (slot k / 4 of the waves with sw == k % 4; panel_strip.h) -> LDS, global
     auto solve = [&](int k) {
-        const int t = k >> 2;
         const double *Lb = Ls + (k & 1) * kTrsmLBuf;
         const double *li = Lb + 256 * RB_LD + prow * RB_LD + 4 * fk;
         const d2_t n01 = *reinterpret_cast<const d2_t *>(li), n23 = *reinterpret_cast<const d2_t *>(li + 2);
@@ -305,26 +297,12 @@ __device__ __noinline__ int pipe_role_trsm(pipe_kargs_t ka, pipe_lds_t sm3, long
         d2_t l01 = d2_t{0.0, 0.0}, l23 = d2_t{0.0, 0.0};
         if (refine) {  // rows pi(frow) of the raw diagonal tile, zero right of the diagonal
             const double *lr = Lb + (16 * k + prow) * RB_LD + 4 * fk;
-            const d2_t r01 = *reinterpret_cast<const d2_t *>(lr), r23 = *reinterpret_cast<const d2_t *>(lr + 2);
-            l01 = d2_t{(4 * fk <= prow) ? r01[0] : 0.0, (4 * fk + 1 <= prow) ? r01[1] : 0.0};
-            l23 = d2_t{(4 * fk + 2 <= prow) ? r23[0] : 0.0, (4 * fk + 3 <= prow) ? r23[1] : 0.0};
+            l01 = *reinterpret_cast<const d2_t *>(lr), l23 = *reinterpret_cast<const d2_t *>(lr + 2);
+            rb_mask_lower(l01, l23, prow, 4 * fk);
         }
-#pragma unroll
-        for (int r = 0; r < RT; r++) {
-            double4_t x = double4_t{0.0, 0.0, 0.0, 0.0};
-            RB_MFMA4(x, 0, n01, n23, acc[r][4 * t], acc[r][4 * t + 1], acc[r][4 * t + 2], acc[r][4 * t + 3]);
-            if (refine) {
-                double4_t rs = double4_t{acc[r][4 * t], acc[r][4 * t + 1], acc[r][4 * t + 2], acc[r][4 * t + 3]};
-                RB_MFMA4(rs, 1, l01, l23, x[0], x[1], x[2], x[3]);
-                RB_MFMA4(x, 0, n01, n23, rs[0], rs[1], rs[2], rs[3]);
-            }
-            double *xs = xbuf(k, r) + frow * RB_LD + 4 * fk;
-            *reinterpret_cast<d2_t *>(xs) = d2_t{x[0], x[1]};
-            *reinterpret_cast<d2_t *>(xs + 2) = d2_t{x[2], x[3]};
-            double *dst = Pw + (int64_t)(16 * r) * a.ld + 16 * k;
-            store_d2_sc1(dst, d2_t{x[0], x[1]});
-            store_d2_sc1(dst + 2, d2_t{x[2], x[3]});
-        }
+        const double4_t x = rb_strip_solve(acc[k >> 2], n01, n23, l01, l23, refine);
+        rb_store4(xbuf(k), x);
+        rb_store4<true>(Pw + 16 * k, x);
     };
     stage_load(0);
     stage_store(0);
@@ -345,32 +323,16 @@ __device__ __noinline__ int pipe_role_trsm(pipe_kargs_t ka, pipe_lds_t sm3, long
                 if (have) stage_load(k + 1);
             }
             __syncthreads();  // X_k is in LDS
-            if (qend && tid == 0)
-                for (int c = 0; c < RT; c++) store_flag(S + a.off_rowT + P * a.NC + c0 + c, (k >> 2) + 1);
+            if (qend && tid == 0) store_flag(S + a.off_rowT + P * a.NC + c0, (k >> 2) + 1);
             {
                 const double *Lb = Ls + (k & 1) * kTrsmLBuf;
-                d2_t b01[RT], b23[RT];
-#pragma unroll
-                for (int r = 0; r < RT; r++) {
-                    const double *xs = xbuf(k, r) + frow * RB_LD + 4 * fk;
-                    b01[r] = *reinterpret_cast<const d2_t *>(xs);
-                    b23[r] = *reinterpret_cast<const d2_t *>(xs + 2);
-                }
+                const double4_t xk = rb_load4(xbuf(k));
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
                     const int C = 4 * t + sw;
                     if (C > k && C < nb16) {  // T_C -= X_k L(C, k)^T
                         const double *lf = Lb + (16 * C + prow) * RB_LD + 4 * fk;
-                        const d2_t a01 = *reinterpret_cast<const d2_t *>(lf), a23 = *reinterpret_cast<const d2_t *>(lf + 2);
-#pragma unroll
-                        for (int r = 0; r < RT; r++) {
-                            double4_t c4 = double4_t{acc[r][4 * t], acc[r][4 * t + 1], acc[r][4 * t + 2], acc[r][4 * t + 3]};
-                            RB_MFMA4(c4, 1, a01, a23, b01[r][0], b01[r][1], b23[r][0], b23[r][1]);
-                            acc[r][4 * t] = c4[0];
-                            acc[r][4 * t + 1] = c4[1];
-                            acc[r][4 * t + 2] = c4[2];
-                            acc[r][4 * t + 3] = c4[3];
-                        }
+                        rb_strip_update(acc[t], lf, xk);
                     }
                 }
             }
@@ -426,7 +388,7 @@ __device__ __noinline__ int pipe_role_fine(pipe_kargs_t ka, pipe_lds_t sm3, long
     int *S = a.sync + (int64_t)z * a.sS;
     const int tid = threadIdx.x, lane = tid & 63, frow = lane & 15, fk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int prow = ((frow & 3) << 2) | (frow >> 2);  // pi(frow), see rb_factor_block
+    const int prow = rb_prow(frow);
     // staging: thread -> row tid / 16 of the 64, doubles [4 (tid % 16), + 4) of the quarter's 64 columns
     const int srow = tid >> 4, spart = (tid & 15) * 4;
     const double *Ag = Mz + (int64_t)(R0 + srow) * a.ld + k0 + spart;
@@ -590,7 +552,7 @@ __device__ __noinline__ void pipe_worker_loop(pipe_kargs_t ka, pipe_lds_t sm3) {
             tr[5] = __builtin_amdgcn_s_getreg((3 << 11) | 20) | ((long long)blockIdx.x << 8);  // XCC_ID, workgroup
         }
         int r;
-        if (task.type == PT_TRSM) r = pipe_role_trsm<1>(ka, (pipe_lds_t)sm, tr, z, task.p, task.a);
+        if (task.type == PT_TRSM) r = pipe_role_trsm(ka, (pipe_lds_t)sm, tr, z, task.p, task.a);
         else if (task.type == PT_FINE) r = pipe_role_fine(ka, (pipe_lds_t)sm, tr, z, task.p, task.a, task.b);
         else r = pipe_role_coarse(ka, (pipe_lds_t)sm, tr, z, task.p, task.a, task.b);
         if (tr && threadIdx.x == 0) tr[4] = wall_clock64();
@@ -1101,7 +1063,7 @@ __device__ __noinline__ int flow_worker_loop(flow_kargs_t kf, pipe_lds_t sm3, in
                     tr[2] = wall_clock64();
                     tr[5] = __builtin_amdgcn_s_getreg((3 << 11) | 20) | ((long long)blockIdx.x << 8);
                 }
-                if (task.type == PT_TRSM) r = pipe_role_trsm<1>(ka, (pipe_lds_t)sm, tr, z, task.p, task.a);
+                if (task.type == PT_TRSM) r = pipe_role_trsm(ka, (pipe_lds_t)sm, tr, z, task.p, task.a);
                 else if (task.type == PT_FINE) r = pipe_role_fine(ka, (pipe_lds_t)sm, tr, z, task.p, task.a, task.b);
                 else r = pipe_role_coarse(ka, (pipe_lds_t)sm, tr, z, task.p, task.a, task.b, task.type == PT_COARSE_LAST ? 1 : 0);
             } else {

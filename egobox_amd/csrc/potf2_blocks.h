@@ -8,26 +8,14 @@
 #include <stdint.h>
 #include <utility>
 
-namespace egx {
+#include "panel_strip.h"  // d2_t, double4_t, RB_LD, RB_MFMA4, store_d2 and the strip solve / update of the TRSM slots
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
+namespace egx {
 
 // ---- in-launch hand-offs (k_potrf_pipe; MI355X guide, "agent-scope release/acquire"): payload stores are WRITE-THROUGH
 // (sc1), every storing wave drains them (s_waitcnt vmcnt(0)) in front of a workgroup barrier, then ONE lane stores the flag
-// (relaxed, agent scope).  Consumers poll that one word relaxed and read the payload with agent-scope (sc1) loads, or
-// after one agent-scope acquire with plain loads.
-__device__ __forceinline__ void store_d2_sc1(double *p, d2_t v) {
-    // (inline asm is invisible to the hazard recogniser: the TWO wait states gfx940+ needs between a store of more than 64
-    //  bits and a VALU write of its data registers are part of the statement -- with one, a v_and that followed the asm
-    //  replaced the low word of a stored double in lanes 0..15)
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-}
-template <bool SC1>
-__device__ __forceinline__ void store_d2(double *p, d2_t v) {
-    if constexpr (SC1) store_d2_sc1(p, v);
-    else *reinterpret_cast<d2_t *>(p) = v;
-}
+// (relaxed, agent scope; the stores themselves: store_d2_sc1, panel_strip.h).  Consumers poll that one word relaxed and
+// read the payload with agent-scope (sc1) loads, or after one agent-scope acquire with plain loads.
 __device__ __forceinline__ double load_sc1(const double *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -71,7 +59,6 @@ __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0
 #ifndef RB_REFINE_LOG2
 #define RB_REFINE_LOG2 5  // refine the strip's TRSM when log2(max |Linv| max L_ii) reaches this (-100: always, 100: never)
 #endif
-constexpr int RB_LD = 18;                 // LDS row stride (doubles): b128 reads of 16 rows hit 16 distinct 4-bank groups
 constexpr int RB_P_DOUBLES = 256 * RB_LD;
 constexpr int RB_RD_DOUBLES = 16 + 64 + 16;  // 1 / L_jj of the current strip + a dump area (see rb_chain_run)
 constexpr int RB_LDS_BYTES = (RB_P_DOUBLES + 3 * 16 * RB_LD + RB_RD_DOUBLES) * 8 + 16;
@@ -323,14 +310,6 @@ __device__ __forceinline__ void rb_chain_run(RbChain &ch, double *NL, double *LR
     }
 }
 
-// one 16x16x16 product on the matrix cores: c +-= A' B' with both operands as 4 consecutive doubles per lane.  NEG = 1
-// negates A' in the instruction (the FP64 MFMAs of gfx940+ read their BLGP field as neg:[a,b,c]).
-#define RB_MFMA4(c, NEG, a01, a23, b0, b1, b2, b3)                               \
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[0], b0, c, 0, 0, NEG);           \
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[1], b1, c, 0, 0, NEG);           \
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[0], b2, c, 0, 0, NEG);           \
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[1], b3, c, 0, 0, NEG)
-
 // Where the diagonal role of k_potrf_pipe publishes its finished strips: `strips` is the matrix' monotonic count of
 // published 16-column strips of the whole factorisation (block at column col0: base = col0 / 16), kernels_pipe.hip.
 struct RbPublish {
@@ -366,7 +345,7 @@ __device__ __forceinline__ bool rb_factor_block(double *__restrict__ D, int64_t 
     const int tid = threadIdx.x, lane = tid & 63, frow = lane & 15, fk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nb16 = nbk >> 4;
-    const int prow = ((frow & 3) << 2) | (frow >> 2);  // pi(frow)
+    const int prow = rb_prow(frow);
     if (tid == 0) *flag = 0;
     if (wave == 0) {
         // ================= chain wave: no tiles, no MFMA; two barriers per strip like the update waves
@@ -400,7 +379,7 @@ __device__ __forceinline__ bool rb_factor_block(double *__restrict__ D, int64_t 
     }
     // ===================== update waves 1..NU
     const RbTab<NU> &tab = c_rb_tab<NU>;
-    double acc[RB_NS * 4];  // slot s, register q: acc[4 s + q]
+    double4_t acc[RB_NS];   // the tile of slot s
     int rc[RB_NS];          // (wave-uniform) tile of slot s: R * 16 + C
     unsigned int valid = 0;  // slots whose tile exists in an nbk x nbk block
 #pragma unroll
@@ -416,11 +395,7 @@ __device__ __forceinline__ bool rb_factor_block(double *__restrict__ D, int64_t 
         if (have) valid |= 1u << s;
         const int tt = have ? t : 0;
         const double *src = D + (int64_t)((tt >> 4) * 16 + frow) * ld + (tt & 15) * 16 + 4 * fk;
-        const d2_t v0 = *reinterpret_cast<const d2_t *>(src), v1 = *reinterpret_cast<const d2_t *>(src + 2);
-        acc[4 * s] = v0[0];
-        acc[4 * s + 1] = v0[1];
-        acc[4 * s + 2] = v1[0];
-        acc[4 * s + 3] = v1[1];
+        acc[s] = rb_load4(src);
     }
     if (failed_before != 0) return false;  // a previous block of this factorisation already failed: early exit
     // the strictly upper 16x16 tiles of the 64x64 diagonal tiles are part of the factor's contract: zeros
@@ -483,39 +458,24 @@ __device__ __forceinline__ bool rb_factor_block(double *__restrict__ D, int64_t 
             for (int s = 0; s < RB_NS; s++) {
                 if (m_trsm & (1u << s)) {
                     const int R = rc[s] >> 4;
-                    double4_t x = double4_t{0.0, 0.0, 0.0, 0.0};
-                    RB_MFMA4(x, 0, n01, n23, acc[4 * s], acc[4 * s + 1], acc[4 * s + 2], acc[4 * s + 3]);
+                    double4_t x = rb_strip_solve(acc[s], n01, n23);
                     if (refine) {
-                        // A' operand of X L^T: rows pi(frow) of the raw factor, zero right of the diagonal (read per tile:
-                        // held across the slots it costs eight registers the pipelined form of this block does not have)
-                        const d2_t r01 = *reinterpret_cast<const d2_t *>(LR + pr * RB_LD + f4);
-                        const d2_t r23 = *reinterpret_cast<const d2_t *>(LR + pr * RB_LD + f4 + 2);
-                        const d2_t l01 = d2_t{(f4 <= pr) ? r01[0] : 0.0, (f4 + 1 <= pr) ? r01[1] : 0.0};
-                        const d2_t l23 = d2_t{(f4 + 2 <= pr) ? r23[0] : 0.0, (f4 + 3 <= pr) ? r23[1] : 0.0};
-                        // (the residual is formed IN the tile's own registers: the tile is dead once it has become X, and a copy
+                        // A' operand of X L^T: rows pi(frow) of the raw factor (read per tile: held across the slots it costs
+                        // eight registers the pipelined form of this block does not have)
+                        d2_t l01 = *reinterpret_cast<const d2_t *>(LR + pr * RB_LD + f4);
+                        d2_t l23 = *reinterpret_cast<const d2_t *>(LR + pr * RB_LD + f4 + 2);
+                        rb_mask_lower(l01, l23, pr, f4);
+                        // (the residual is formed IN the slot's own registers: the tile is dead once it has become X, and a copy
                         //  would cost eight registers at the point where the block has none to spare)
-                        double4_t r = double4_t{acc[4 * s], acc[4 * s + 1], acc[4 * s + 2], acc[4 * s + 3]};  // A
-                        RB_MFMA4(r, 1, l01, l23, x[0], x[1], x[2], x[3]);                                      // A - X L^T
-                        acc[4 * s] = r[0], acc[4 * s + 1] = r[1], acc[4 * s + 2] = r[2], acc[4 * s + 3] = r[3];
-                        RB_MFMA4(x, 0, n01, n23, acc[4 * s], acc[4 * s + 1], acc[4 * s + 2], acc[4 * s + 3]);  // X + (A - X L^T) Linv^T
+                        rb_strip_refine(x, acc[s], n01, n23, l01, l23);
                     }
-                    double *px = P + (R * 16 + fr) * RB_LD + f4;
-                    *reinterpret_cast<d2_t *>(px) = d2_t{x[0], x[1]};
-                    *reinterpret_cast<d2_t *>(px + 2) = d2_t{x[2], x[3]};
-                    if constexpr (!PIPE) {  // (PIPE: the strip's column goes to global memory from the LDS panel, in phase B)
-                        double *dst = D + (int64_t)(R * 16 + fr) * ld + k * 16 + f4;
-                        *reinterpret_cast<d2_t *>(dst) = d2_t{x[0], x[1]};
-                        *reinterpret_cast<d2_t *>(dst + 2) = d2_t{x[2], x[3]};
-                    }
+                    rb_store4(P + (R * 16 + fr) * RB_LD + f4, x);
+                    if constexpr (!PIPE)  // (PIPE: the strip's column goes to global memory from the LDS panel, in phase B)
+                        rb_store4(D + (int64_t)(R * 16 + fr) * ld + k * 16 + f4, x);
                     if (s + 1 < RB_NS && (m_pair & (1u << s))) {  // slot s + 1 is tile (k+1, k+1): T -= X X^T, A' = own LDS rows
                         const double *pa = P + (R * 16 + pr) * RB_LD + f4;
-                        const d2_t a01 = *reinterpret_cast<const d2_t *>(pa), a23 = *reinterpret_cast<const d2_t *>(pa + 2);
-                        double4_t c4 = double4_t{acc[4 * s + 4], acc[4 * s + 5], acc[4 * s + 6], acc[4 * s + 7]};
-                        RB_MFMA4(c4, 1, a01, a23, x[0], x[1], x[2], x[3]);
-                        acc[4 * s + 4] = c4[0], acc[4 * s + 5] = c4[1], acc[4 * s + 6] = c4[2], acc[4 * s + 7] = c4[3];  // (in place: dead after the hand-off)
-                        double *dg = Dg + fr * RB_LD + f4;
-                        *reinterpret_cast<d2_t *>(dg) = d2_t{c4[0], c4[1]};
-                        *reinterpret_cast<d2_t *>(dg + 2) = d2_t{c4[2], c4[3]};
+                        rb_strip_update(acc[s + 1], pa, x);
+                        rb_store4(Dg + fr * RB_LD + f4, acc[s + 1]);
                     }
                 }
             }
@@ -539,14 +499,7 @@ __device__ __forceinline__ bool rb_factor_block(double *__restrict__ D, int64_t 
                 const int R = rc[s] >> 4, C = rc[s] & 15;
                 const double *pa = P + (C * 16 + pr) * RB_LD + f4;
                 const double *pb = P + (R * 16 + fr) * RB_LD + f4;
-                const d2_t a01 = *reinterpret_cast<const d2_t *>(pa), a23 = *reinterpret_cast<const d2_t *>(pa + 2);
-                const d2_t b01 = *reinterpret_cast<const d2_t *>(pb), b23 = *reinterpret_cast<const d2_t *>(pb + 2);
-                double4_t c4 = double4_t{acc[4 * s], acc[4 * s + 1], acc[4 * s + 2], acc[4 * s + 3]};
-                RB_MFMA4(c4, 1, a01, a23, b01[0], b01[1], b23[0], b23[1]);
-                acc[4 * s] = c4[0];
-                acc[4 * s + 1] = c4[1];
-                acc[4 * s + 2] = c4[2];
-                acc[4 * s + 3] = c4[3];
+                rb_strip_update(acc[s], pa, rb_load4(pb));
             }
         }
         if (PIPE) drain_stores();  // strip k's column, diagonal tile and inverse: issued a phase ago

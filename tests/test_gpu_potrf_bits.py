@@ -4,7 +4,8 @@ SHA-256 of the fitted factor, on every branch of the launch order -- separate la
 group of panels (waiting on the device and on the stream), the whole chain launch, left-looking updates, each with and without
 the theta-gradient's C^-T rider and alone and in lock-step, forced at the smallest sizes that have one, two and three groups
 of panels; and at n = 14336, the first size with the look-ahead columns' update on the side stream, the default left-looking
-schedule and the flow tail.  The other tests pin these forms to EACH OTHER and to LAPACK to rounding; a change of the order
+schedule and the flow tail; and, in the group refine/..., an ill-conditioned matrix whose strips take the refinement step of
+the strip solve (csrc/panel_strip.h) through every kernel that solves a panel.  The other tests pin these forms to EACH OTHER and to LAPACK to rounding; a change of the order
 that moved a form's bits, or all forms alike, would pass those.  The file was recorded at the commit its "recorded_at" names,
 not by the code under test.
 
@@ -144,6 +145,48 @@ def run_big(egx, which):
 
 BIG = ("lone", "width4", "width8")
 
+# ---- refine/...: the refinement step X += (T - X L_kk^T) Linv_k^T of the strip solve, on every kernel that solves a panel.
+# The matrix of test_gpu_panel_rows.py::test_ill_conditioned_kernel_matrix_takes_the_refinement_step (cond(L) ~ 1e6, padded
+# 1024: four panels with 768 / 512 / 256 rows below the blocks) through egx.potrf by separate launches -- the row-owning
+# kernel and the column-strip kernel under the diagonal-block kernel -- and by the two chain launches (the chain role's TRSM
+# task under the chain's diagonal role).  That every case takes the branch was confirmed with ONE scratch build in which the
+# refinement step of panel_strip.h did nothing: all six cases then failed.
+# (knobs, what schedule() says of a one-workspace handle of this size: egx.potrf factors by that handle's schedule)
+REFINE_POTRF = {
+    "separate/rows": ({"pipe": 0, "trsm_rows_min": 64}, {"pipelined_chain": 0, "left_looking": 0}),
+    "separate/strips": ({"pipe": 0, "trsm_rows_min": 1 << 30}, {"pipelined_chain": 0, "left_looking": 0}),
+    "chain-per-group": ({"pipe": 2}, {"pipelined_chain": 1, "whole_factorisation_launch": 0, "left_looking": 0}),
+    "whole-chain": ({"pipe": 1}, {"pipelined_chain": 1, "whole_factorisation_launch": 1, "left_looking": 0}),
+}
+# ... and on the solves after the factorisation: a one-dimensional training set of 300 points of [0, 3] at theta = 3.2 on the
+# standardised inputs with the same nugget (cond(L) ~ 9e5 by numpy, as above), predict_var at 128 queries (k_panel_trsm16<1, true>)
+# and at 4096, the first size launch_trsm_rows gives to k_panel_trsm16<2, true>
+REFINE_QUERIES = (128, 4096)
+
+
+def _ill_conditioned_matrix():
+    n = 1024
+    t = np.random.default_rng(5).uniform(0.0, 3.0, n)
+    return np.exp(-((t[:, None] - t[None, :]) ** 2) / 0.02) + 1e-10 * np.eye(n)
+
+
+def run_refine_potrf(egx, form):
+    settings, want = REFINE_POTRF[form]
+    with _knobs(egx, settings):
+        with egx.GpHandle(np.linspace(0.0, 1.0, 1024)[:, None], np.linspace(0.0, 1.0, 1024)) as h:
+            s = h.schedule()
+            assert {k: s[k] for k in want} == want, (form, s)
+        fac, info = egx.potrf(_ill_conditioned_matrix())
+    return {f"refine/potrf/{form}": {"info": int(info), "sha256": hashlib.sha256(np.ascontiguousarray(fac).tobytes()).hexdigest()}}
+
+
+def run_refine_predict(egx):
+    x = np.random.default_rng(5).uniform(0.0, 3.0, 300)
+    xq = np.random.default_rng(6).uniform(-0.3, 3.3, max(REFINE_QUERIES))
+    with egx.GpHandle(x[:, None], np.sin(3.0 * x), nugget=1e-10) as h:
+        h.finalize(np.array([3.2]))
+        return {f"refine/predict_var/m={m}": {"predict_var": _hex(h.predict_var(xq[:m, None]))} for m in REFINE_QUERIES}
+
 
 def run_cases(egx):
     out = {}
@@ -151,6 +194,9 @@ def run_cases(egx):
         out.update(run_form(egx, form))
     for which in BIG:
         out.update(run_big(egx, which))
+    for form in REFINE_POTRF:
+        out.update(run_refine_potrf(egx, form))
+    out.update(run_refine_predict(egx))
     return out
 
 
@@ -175,9 +221,17 @@ def _compare(golden, got):
 
 def test_the_golden_file_names_the_cases(golden):
     names = [f"{form}/n={n}" for form in FORMS for n in SMALL_N] + [f"n=14336/{w}" for w in BIG]
-    assert sorted(golden["cases"]) == sorted(names)
+    refine = [f"refine/potrf/{form}" for form in REFINE_POTRF] + [f"refine/predict_var/m={m}" for m in REFINE_QUERIES]
+    assert sorted(golden["cases"]) == sorted(names + refine)
     assert len(golden["recorded_at"]) == 40 and golden["how"]
     for name, rec in golden["cases"].items():  # a recording of lost pivots would pin nothing
+        if name.startswith("refine/potrf/"):
+            assert rec["info"] == 0 and len(rec["sha256"]) == 64, name
+            continue
+        if name.startswith("refine/predict_var/"):
+            var = np.array([float.fromhex(v) for v in rec["predict_var"]])
+            assert var.size == int(name.split("=")[1]) and np.all(np.isfinite(var)) and np.unique(var).size > var.size // 2, name
+            continue
         for key, val in rec.items():
             if key != "r_chol_sha256":
                 assert not np.any(np.asarray(val[-1])), (name, key)
@@ -191,6 +245,24 @@ def test_forced_forms_give_the_recorded_bits(egx, golden, form):
 @pytest.mark.parametrize("which", BIG)
 def test_n_14336_gives_the_recorded_bits(egx, golden, which):
     _compare(golden, run_big(egx, which))
+
+
+@pytest.mark.parametrize("form", sorted(REFINE_POTRF))
+def test_refinement_step_in_the_factorisation_gives_the_recorded_bits(egx, golden, form):
+    _compare(golden, run_refine_potrf(egx, form))
+
+
+def test_refinement_step_moves_between_the_panel_kernels_without_a_bit(egx, golden):
+    """ "trsm_rows_min" is a launch-time knob: the recorded factors of the two separate-launch forms are one factor"""
+    assert golden["cases"]["refine/potrf/separate/rows"] == golden["cases"]["refine/potrf/separate/strips"]
+    rows, strips = (list(run_refine_potrf(egx, form).values())[0] for form in ("separate/rows", "separate/strips"))
+    assert rows["info"] == 0 and rows == strips
+
+
+@pytest.mark.parametrize("m", REFINE_QUERIES)
+def test_refinement_step_after_the_factorisation_gives_the_recorded_bits(egx, golden, m):
+    name = f"refine/predict_var/m={m}"
+    _compare(golden, {name: run_refine_predict(egx)[name]})
 
 
 if __name__ == "__main__":  # record: see the module docstring
