@@ -27,6 +27,11 @@ def problem(n, nz, d, seed=0, noise=0.05):
     return x, y, z
 
 
+def weights(d, h):
+    """The (d, h) KPLS weights of every case here (and of the `kpls` row of tests/sgp_edge_cases.py)."""
+    return np.random.default_rng(2).standard_normal((d, h)) / np.sqrt(d)
+
+
 _data, _theta = {}, {}
 
 
@@ -34,7 +39,7 @@ def data(cid):
     """(x, y, z, w) of a case, computed once."""
     if cid not in _data:
         n, nz, d, h = CASES[cid]
-        _data[cid] = problem(n, nz, d, seed=n) + (np.random.default_rng(2).standard_normal((d, h)) / np.sqrt(d),)
+        _data[cid] = problem(n, nz, d, seed=n) + (weights(d, h),)
     return _data[cid]
 
 

@@ -59,10 +59,13 @@ def _check_grad(egx, corr, method, x, y, z, theta, sigma2, noise):
     with egx.SgpHandle(x, y, z, corr=corr, method=method) as h:
         lk0, st0 = h.likelihood(theta, sigma2, noise)
         lk, got, st = h.likelihood_grad(theta, sigma2, noise)
+    from oracle import sgp_oracle as S
+    lk_ref = S.SparseGpOracle(x, y, z, theta, sigma2, noise, corr=GO.KINDS[corr], method=[S.FITC, S.VFE][method], nugget=nugget).likelihood
     dev = np.abs(got - want).max() / np.abs(want).max()
     print(f"corr {corr} method {method} n {x.shape[0]} nz {z.shape[0]} d {x.shape[1]}: cond {cond:.2e}, "
-          f"max |got - want| / max |want| = {dev:.3e}")
+          f"max |got - want| / max |want| = {dev:.3e}, likelihood off the oracle by {abs(lk0 - lk_ref) / abs(lk_ref):.3e}")
     assert st0 == 0 and st == 0 and lk == lk0  # bit for bit
+    assert lk0 == pytest.approx(lk_ref, rel=1e-8)  # ... and the value itself, not only the two calls' agreement
     assert got.shape == (x.shape[1] + 2,)
     np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6 * np.abs(want).max())
 

@@ -223,16 +223,25 @@ def test_gradients_on_an_ill_conditioned_kmm(egx, S, method):
 
 # ------------------------------------------------------------------ 7. predict_valvar = predict, predict_var
 @pytest.mark.parametrize("method", [0, 1])
-def test_valvar_bit_equals_the_two_calls(egx, method):
+def test_valvar_bit_equals_the_two_calls(egx, S, method):
     x, y, z = problem(700, 40, 3, seed=3)
     rng = np.random.default_rng(11)
+    theta, sigma2, noise = np.array([1.3, 0.8, 1.1]), 0.9, 0.02
     with egx.SgpHandle(x, y, z, corr=3, method=method) as h:
-        h.finalize(np.array([1.3, 0.8, 1.1]), 0.9, 0.02)
+        h.finalize(theta, sigma2, noise)
         for m in (1, 7, 333, 70000):
             xq = rng.random((m, 3)) * 2 - 1
             yv, vv = h.predict_valvar(xq)
             np.testing.assert_array_equal(yv, h.predict(xq))
             np.testing.assert_array_equal(vv, h.predict_var(xq))
+    # the three calls share the chunk loop of 65536 queries: the rows on both sides of its edge against the oracle as well
+    # (the bars of test_sgp_gpu.py; none of these rows is within 1e-7 sigma2 of the variance clamp, on the oracle alone)
+    rows = slice(65530, 65546)
+    ref = S.SparseGpOracle(x, y, z, theta, sigma2, noise, corr=KINDS[3], method=[S.FITC, S.VFE][method])
+    _, _, var_raw = analytic_gradients(ref, xq[rows])
+    assert np.all(np.abs(var_raw - 1e-15) >= 1e-7 * sigma2)
+    np.testing.assert_allclose(yv[rows], ref.predict(xq[rows]), rtol=1e-6, atol=1e-8)
+    np.testing.assert_allclose(vv[rows], ref.predict_var(xq[rows]), rtol=1e-6, atol=1e-9)
 
 
 # ------------------------------------------------------------------ 8. against the reference's own definition
