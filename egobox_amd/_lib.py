@@ -49,6 +49,11 @@ class SgpConfig(C.Structure):
     _fields_ = [("corr", C.c_int32), ("method", C.c_int32), ("nugget", C.c_double), ("device", C.c_int32)]
 
 
+class PlsPlan(C.Structure):
+    """egx_pls_plan"""
+    _fields_ = [(k, C.c_int64) for k in ("n", "d", "chunk_rows", "n_chunks", "tiles", "out_tiles", "block_side", "blocks")]
+
+
 class InfillConfig(C.Structure):
     _fields_ = [("criterion", C.c_int32), ("feasibility", C.c_int32), ("fmin", C.c_double), ("sigma_weight", C.c_double),
                 ("scale_ic", C.c_double), ("scale", C.c_double)]
@@ -241,6 +246,10 @@ SIGNATURES = [
     ("egx_sgp_get_inducings", C.c_int32, [C.c_void_p, c_double_p]),
     ("egx_sgp_set_w_star", C.c_int32, [C.c_void_p, c_double_p, C.c_int64]),
     ("egx_sgp_get_w_star", C.c_int32, [C.c_void_p, c_double_p, c_int64_p]),
+    ("egx_pls_rotations", C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_int32_p]),
+    ("egx_sgp_compute_w_star", C.c_int32, [C.c_void_p, C.c_int64]),
+    ("egx_sgp_pls_launch_ms", C.c_int32, [C.c_void_p, c_double_p]),
+    ("egx_pls_get_plan", C.c_int32, [C.c_int64, C.c_int64, C.POINTER(PlsPlan)]),
     ("egx_sgp_fit_lbfgs_z", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int32, C.c_double,
                                         C.c_int64, c_double_p, c_double_p, C.c_int64, c_int64_p]),
     ("egx_sgp_predict", C.c_int32, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),

@@ -566,6 +566,15 @@ void pipe_set_trace_cap(int slots);          // slots of the trace buffer (flow 
 void flow_test_set_leads(int lead_short, int lead_long);  // FlowArgs::lead_* of the next flow launches (-1: the product's)
 #endif
 int chol_init();  // one-time function attribute setup (dynamic LDS sizes)
+
+// ---- kernels_pls.hip --------------------------------------------------------
+// PLS1 rotations w (d x k, row-major) of the n rows of xT (d x ld, k-major; ld even and >= n) and y (n, readable up to an even
+// count) on the device: column means, centred Gram matrix on the matrix unit (split-K, summed in chunk order), the O(d^2 k)
+// deflation on the host (pls_host.h).  *status: 0, or 1 with zeros on a constant response.  Synchronises s.
+int pls_device_rotations(hipStream_t s, const double *xT, int64_t ld, const double *y, int64_t n, int d, int k, double *w, int *status);
+// the three launches alone between two events (a measurement aid: tools/pls_bench.py)
+int pls_device_launch_ms(hipStream_t s, const double *xT, int64_t ld, const double *y, int64_t n, int d, double *ms);
+int pls_check_k(int64_t k, int64_t d);  // the reference's two messages for k < 1 and k > d
 int set_knob(const char *name, int value);  // kernels_chol.hip tuning knobs by name; INT_MIN = unknown
 
 }  // namespace egx

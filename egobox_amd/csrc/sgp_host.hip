@@ -650,6 +650,32 @@ int32_t egx_sgp_get_inducings(egx_sgp *g, double *z) {
 
 // The KPLS weights (header).  They are checked before anything changes; the coefficient buffer grows to d x h and |w| goes to the
 // device once, for the Matern form of the gradient kernel (sgp_grad.hip), as the dense model's d_wabs does.
+namespace {
+// caller holds g->mu; g, w and 1 <= h <= d are checked
+int sgp_install_w_star(egx_sgp *g, const double *w, int64_t h) {
+    const size_t cnt = (size_t)g->d * (size_t)h;
+    for (size_t e = 0; e < cnt; e++)
+        if (!std::isfinite(w[e])) {
+            set_error("w_star contains non-finite values");
+            return EGX_ERR_INVALID_VALUE;
+        }
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    std::vector<double> wabs(cnt);
+    for (size_t e = 0; e < cnt; e++) wabs[e] = std::fabs(w[e]);
+    EGX_RC(g->coef.alloc(cnt));
+    EGX_RC(g->d_wabs.alloc(cnt));
+    EGX_HIP_CHECK(hipMemcpyAsync(g->d_wabs.p, wabs.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
+    EGX_HIP_CHECK(hipStreamSynchronize(g->stream));  // wabs is a local
+    g->w_star.assign(w, w + cnt);
+    g->has_w = true;
+    g->h = (int)h;
+    g->hcols = (g->corr == EGX_CORR_MATERN32 || g->corr == EGX_CORR_MATERN52) ? (int)h : 1;
+    g->fitted = false;
+    g->winv_ok = false;
+    return EGX_SUCCESS;
+}
+}  // namespace
+
 int32_t egx_sgp_set_w_star(egx_sgp *g, const double *w, int64_t h) {
     if (w && h == 0) {  // sparse_parameters.rs:306-311 (needs no handle: refused first)
         set_error("`kpls_dim` canot be 0!");
@@ -679,26 +705,33 @@ int32_t egx_sgp_set_w_star(egx_sgp *g, const double *w, int64_t h) {
         set_error("NULL argument");
         return EGX_ERR_INVALID_VALUE;
     }
-    const size_t cnt = (size_t)d * (size_t)h;
-    for (size_t e = 0; e < cnt; e++)
-        if (!std::isfinite(w[e])) {
-            set_error("w_star contains non-finite values");
-            return EGX_ERR_INVALID_VALUE;
-        }
+    return sgp_install_w_star(g, w, h);
+}
+
+// The PLS rotations of the resident training set (kernels_pls.hip), installed as egx_sgp_set_w_star installs a caller's
+int32_t egx_sgp_compute_w_star(egx_sgp *g, int64_t k) {
+    if (k < 1) return pls_check_k(k, 1);  // needs no handle: refused first, as in egx_sgp_set_w_star
+    if (!g) {
+        set_error("NULL handle");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    EGX_RC(pls_check_k(k, g->d));
     EGX_HIP_CHECK(hipSetDevice(g->device));
-    std::vector<double> wabs(cnt);
-    for (size_t e = 0; e < cnt; e++) wabs[e] = std::fabs(w[e]);
-    EGX_RC(g->coef.alloc(cnt));
-    EGX_RC(g->d_wabs.alloc(cnt));
-    EGX_HIP_CHECK(hipMemcpyAsync(g->d_wabs.p, wabs.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
-    EGX_HIP_CHECK(hipStreamSynchronize(g->stream));  // wabs is a local
-    g->w_star.assign(w, w + cnt);
-    g->has_w = true;
-    g->h = (int)h;
-    g->hcols = (g->corr == EGX_CORR_MATERN32 || g->corr == EGX_CORR_MATERN52) ? (int)h : 1;
-    g->fitted = false;
-    g->winv_ok = false;
-    return EGX_SUCCESS;
+    std::vector<double> w((size_t)g->d * (size_t)k);
+    int st = 0;
+    EGX_RC(pls_device_rotations(g->stream, g->xT.p, g->n_pad, g->y.p, g->n, g->d, (int)k, w.data(), &st));
+    return sgp_install_w_star(g, w.data(), k);
+}
+
+int32_t egx_sgp_pls_launch_ms(egx_sgp *g, double *ms) {
+    if (!g || !ms) {
+        set_error("NULL argument");
+        return EGX_ERR_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(g->mu);
+    EGX_HIP_CHECK(hipSetDevice(g->device));
+    return pls_device_launch_ms(g->stream, g->xT.p, g->n_pad, g->y.p, g->n, g->d, ms);
 }
 
 int32_t egx_sgp_get_w_star(egx_sgp *g, double *w, int64_t *h) {

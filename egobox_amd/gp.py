@@ -678,6 +678,7 @@ class GpParams:
         self._theta_tuning = ThetaTuning.default()
         self._kpls_dim = None
         self._kpls_weights = None
+        self._pls = "host"
         self._n_start = GP_OPTIM_N_START
         self._max_eval = GP_COBYLA_MAX_EVAL
         self._nugget = DEFAULT_NUGGET
@@ -697,6 +698,14 @@ class GpParams:
 
     def kpls_dim(self, kpls_dim):
         self._kpls_dim = kpls_dim
+        return self
+
+    def pls(self, where):
+        """Where `kpls_dim` computes its rotations: "host" (default: `kpls.pls_rotations`, the oracle) or "device"
+        (`kpls.pls_rotations_device`: means and centred Gram matrix on the GPU)."""
+        if where not in ("host", "device"):
+            raise ValueError("pls must be 'host' or 'device'")
+        self._pls = where
         return self
 
     def kpls_weights(self, w_star):
@@ -782,8 +791,11 @@ class GpParams:
                     L.ERR_INVALID_VALUE,
                     f"Dimension reduction {self._kpls_dim} should be smaller than actual training input dimensions {nx}")
             if self._kpls_weights is None:  # algorithm.rs:843-855: rotations of a PLS regression of y on x
-                from .kpls import pls_rotations
-                w = pls_rotations(x, y, self._kpls_dim)
+                from .kpls import pls_rotations, pls_rotations_device
+                if self._pls == "device":
+                    w = pls_rotations_device(x, y, self._kpls_dim, device=self._device)
+                else:
+                    w = pls_rotations(x, y, self._kpls_dim)
             else:
                 w = self._kpls_weights
         if self._theta_tuning.kind == "Fixed":

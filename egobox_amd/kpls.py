@@ -42,3 +42,33 @@ def pls_rotations(x, y, n_components):
         yk = yk - qa * t
         w[:, a], p[:, a] = wa, pa
     return w @ np.linalg.pinv(p.T @ w)
+
+
+def pls_rotations_device(x, y, n_components, device=-1, return_status=False):
+    """`pls_rotations` on the GPU (egx_pls_rotations): column means and the centred Gram matrix of [x | y] on the device, the
+    O(d^2 k) deflation on the host from that matrix.  Same contract: (d, k), zeros on a constant response (status 1)."""
+    import ctypes as C
+
+    from . import _lib as L
+    x = L.as_f64(x)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    y = L.as_f64(np.asarray(y, dtype=np.float64).reshape(-1))
+    if x.ndim != 2 or y.shape[0] != x.shape[0]:
+        raise L.InvalidValueError(L.ERR_INVALID_VALUE, "x (n, d) and y (n) expected")
+    n, d = x.shape
+    k = int(n_components)
+    w = np.zeros((d, max(k, 1)))
+    status = C.c_int32(0)
+    L.check(L.load().egx_pls_rotations(int(device), L.dptr(x), L.dptr(y), n, d, k, L.dptr(w), C.byref(status)))
+    return (w, status.value) if return_status else w
+
+
+def pls_plan(n, d):
+    """egx_pls_get_plan as a dict: how the device path cuts an (n, d) training set (host only)."""
+    import ctypes as C
+
+    from . import _lib as L
+    p = L.PlsPlan()
+    L.check(L.load().egx_pls_get_plan(int(n), int(d), C.byref(p)))
+    return {k: int(getattr(p, k)) for k, _ in L.PlsPlan._fields_}

@@ -99,6 +99,13 @@ class SgpHandle:
         L.check(self._lib.egx_sgp_set_w_star(self._h, L.dptr(w), w.shape[1]))
         self.h = w.shape[1]
 
+    def compute_w_star(self, k):
+        """The PLS rotations (d, k) of the training set the handle holds, computed on the device (egx_sgp_compute_w_star: no
+        upload) and installed as `set_w_star` installs them.  A constant response installs zeros.  Returns the weights."""
+        L.check(self._lib.egx_sgp_compute_w_star(self._h, int(k)))
+        self.h = int(k)
+        return self.w_star()
+
     def w_star(self):
         """The KPLS weights (d, h), or None when none are set (egx_sgp_get_w_star)."""
         h = C.c_int64()
@@ -303,12 +310,13 @@ class SgpParams:
         self._optimizer = "cobyla"  # the reference's optimiser; "lbfgs" uses the closed-form likelihood gradient
         self._opt_z = None          # optimize_inducings: (max_iter, (z_lo, z_hi) or None)
         self._kpls_dim = None
+        self._pls = "host"
 
     def kpls_dim(self, k):
         """SgpParams::kpls_dim (sparse_parameters.rs:216-220, checked as :304-322): fit on k PLS components of the inputs.  The
         rotations w_star (d, k) are those of a PLS regression of the raw y on the raw x (`kpls.pls_rotations`, on the host, as
-        sparse_algorithm.rs:429-455 takes them from linfa-pls); theta, its initial guess and its bounds then have k components,
-        with every optimiser.  None switches it off."""
+        sparse_algorithm.rs:429-455 takes them from linfa-pls; `pls("device")`: computed by the handle on the GPU); theta, its
+        initial guess and its bounds then have k components, with every optimiser.  None switches it off."""
         if k is not None:
             k = int(k)
             if k == 0:
@@ -320,6 +328,14 @@ class SgpParams:
                     f"Dimension reduction ({k}) should be smaller than expected training input size "
                     f"infered from given initial theta length ({th.size})")
         self._kpls_dim = k
+        return self
+
+    def pls(self, where):
+        """Where `kpls_dim` computes its rotations: "host" (default: `kpls.pls_rotations`, the oracle) or "device" (the handle is
+        created without weights and computes them from its resident training set, `SgpHandle.compute_w_star`)."""
+        if where not in ("host", "device"):
+            raise ValueError("pls must be 'host' or 'device'")
+        self._pls = where
         return self
 
     def sparse_method(self, m):
@@ -402,10 +418,17 @@ class SgpParams:
                 raise L.InvalidValueError(
                     L.ERR_INVALID_VALUE,
                     f"Dimension reduction {self._kpls_dim} should be smaller than actual training input dimensions {x.shape[1]}")
-            from .kpls import pls_rotations
-            w_star = pls_rotations(x, y, self._kpls_dim)  # on the raw data, as the reference does (:440-455)
+            if self._pls == "host":
+                from .kpls import pls_rotations
+                w_star = pls_rotations(x, y, self._kpls_dim)  # on the raw data, as the reference does (:440-455)
         h = SgpHandle(x, y, z, corr=self._corr.code, method=self._method, nugget=self._nugget, device=self._device,
                       w_star=w_star)
+        if self._kpls_dim is not None and w_star is None:  # pls("device"): from the training set the handle just uploaded
+            try:
+                w_star = h.compute_w_star(self._kpls_dim)
+            except Exception:
+                h.close()
+                raise
         d = h.h  # theta components: kpls_dim with KPLS, else the number of inputs
         t = self._theta_tuning
         init = np.asarray(t.init, dtype=np.float64).reshape(-1)

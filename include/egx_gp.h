@@ -713,6 +713,47 @@ int32_t egx_sgp_get_inducings(egx_sgp *sgp, double *z /*nz*d*/);
  * egx_sgp_get_w_star writes *h (d when no weights are set) and, where w != NULL and weights are set, the d x h weights. */
 int32_t egx_sgp_set_w_star(egx_sgp *sgp, const double *w /*d*h row-major, or NULL*/, int64_t h);
 int32_t egx_sgp_get_w_star(egx_sgp *sgp, double *w /*d*h or NULL*/, int64_t *h);
+
+/* ---- PLS rotations on the device (the weights w_star of KPLS) ------------------------------------------------------------------
+ * The x rotations W (P^T W)^-1 (d x k, row-major) of a PLS1 regression of y on x, both centred and scaled to unit variance
+ * (ddof = 1; a column of zero spread is scaled by 1 and gets a zero row): what linfa-pls' PlsRegression::params(k).fit(..)
+ * .rotations().0 gives the reference (algorithm.rs:843-855) and egobox_amd/kpls.py restates on the host.  The signs of the columns
+ * are those of the NIPALS recursion; every consumer reads |w| or w^2.
+ *
+ * Two launches read the data: the column means, then the centred Gram matrix of [x | y] on the FP64 matrix unit, the rows split
+ * into chunks whose partial sums are added in chunk order (a third, tiny launch).  The O(d^2 k) deflation runs on the host from
+ * that matrix.  No atomics: the result depends on (x, y, n, d, k) alone -- the same bits on every call, for every leading
+ * dimension of the device copy, from egx_pls_rotations and from egx_sgp_compute_w_star.
+ *
+ * *status = 0, or 1 with w all zeros where the response (or the residual left by an earlier component) is constant up to
+ * rounding -- where the reference hands zeros on after PowerMethodConstantResidualError.  status may be NULL.
+ *
+ * Checked before a device is touched, EGX_ERR_INVALID_VALUE: NULL x / y / w; k < 1 ("`kpls_dim` canot be 0!"); k > d ("Dimension
+ * reduction k should be smaller than actual training input dimensions d"); n < 2; d < 1; a non-finite entry of x or y.
+ * Then EGX_ERR_NO_DEVICE without a device, EGX_ERR_INVALID_VALUE for a device ordinal out of range (device < 0: the current one). */
+int32_t egx_pls_rotations(int32_t device, const double *x /*n*d row-major*/, const double *y /*n*/, int64_t n, int64_t d, int64_t k,
+                          double *w /*d*k row-major*/, int32_t *status);
+/* The same rotations from the training set the handle holds on the device (no upload), installed exactly as
+ * egx_sgp_set_w_star(sgp, w, k) installs them: the handle is un-fitted, theta has k components, egx_sgp_get_w_star returns the
+ * weights.  A constant response installs zeros (accepted as from egx_sgp_set_w_star; evaluations then report their status as
+ * values); egx_sgp_get_w_star shows them.  k < 1 / k > d: EGX_ERR_INVALID_VALUE with the messages above, and the handle stays
+ * as it was (a NULL handle is refused after k < 1, as egx_sgp_set_w_star does). */
+int32_t egx_sgp_compute_w_star(egx_sgp *sgp, int64_t k);
+/* A measurement aid (tools/pls_bench.py): the launches of egx_sgp_compute_w_star on the handle's data, once, between two HIP
+ * events; *ms their elapsed time.  The handle is left as it was. */
+int32_t egx_sgp_pls_launch_ms(egx_sgp *sgp, double *ms);
+/* How the two launches above cut an (n x d) training set (host only, no device; csrc/pls_host.h is the one place that decides):
+ * chunk c < n_chunks owns the rows [c chunk_rows, min(n, (c + 1) chunk_rows)) -- every row once, no chunk empty; chunk_rows is a
+ * multiple of 64 and does not shrink as n grows.  [x | y] has d + 1 columns in `tiles` tiles of 16; out_tiles = the 16 x 16
+ * tiles of the lower triangle, the only ones computed; a workgroup owns one of `blocks` 64 x 64 blocks (block_side per side) of
+ * one chunk.  None of them shrinks as d grows.  n < 1, d < 1 or out == NULL: EGX_ERR_INVALID_VALUE. */
+typedef struct {
+    int64_t n, d;
+    int64_t chunk_rows, n_chunks;
+    int64_t tiles, out_tiles;
+    int64_t block_side, blocks;
+} egx_pls_plan;
+int32_t egx_pls_get_plan(int64_t n, int64_t d, egx_pls_plan *out);
 /* egx_sgp_fit_lbfgs (phase 1, exactly), then ONE more projected L-BFGS from its winner over [log10 params (np), u (nz*d)],
  * u = (z - z_lo) / (z_hi - z_lo) in [0, 1]: the inducing points move with the parameters, driven by egx_sgp_likelihood_grad_z.
  * z_lo / z_hi (d each) box every inducing point; NULL: the per-column min / max of the training x.  A column with z_hi == z_lo

@@ -138,6 +138,15 @@ inline std::vector<double> to_discrete_space(const std::vector<XType> &xt, const
 }
 }  // namespace mixint
 
+// The x rotations (d x k, row-major) of a PLS1 regression of y on x (n x d row-major), centred and scaled to unit variance, computed
+// on the device (egx_pls_rotations): the KPLS weights w_star.  status (optional): 1 with all zeros on a constant response.
+inline std::vector<double> pls_rotations(const double *x, const double *y, int64_t n, int64_t d, int64_t k, int device = -1,
+                                         int32_t *status = nullptr) {
+    std::vector<double> w((size_t)(d > 0 ? d : 0) * (size_t)(k > 0 ? k : 0));
+    check(egx_pls_rotations(device, x, y, n, d, k, w.empty() ? nullptr : w.data(), status));
+    return w;
+}
+
 class GaussianProcess;
 
 // GpParams / GpValidParams, parameters.rs:80-313
@@ -147,6 +156,13 @@ class GpParams {
     GpParams &theta_tuning(ThetaTuning t) { tuning_ = std::move(t); return *this; }
     GpParams &theta_init(std::vector<double> v) { tuning_.init = std::move(v); return *this; }
     GpParams &theta_bounds(std::vector<std::pair<double, double>> b) { tuning_.bounds = std::move(b); return *this; }
+    // KPLS (parameters.rs:214-218, algorithm.rs:798-855): fit on k PLS components of the inputs.  `fit` computes the rotations on
+    // the device (pls_rotations) and hands them to the model as w_star / kpls_dim of egx_gp_config; theta, its initial guess and
+    // its bounds then have k components (a single value is broadcast).  k = 0 is refused by `fit` ("`kpls_dim` canot be 0!"), as
+    // is k > d.  w_star(w, k): the caller's own rotations (d x k, row-major) instead.  fit_group refuses both: the members of a
+    // lock-step group share no rotations (InvalidValueError).
+    GpParams &kpls_dim(int64_t k) { kpls_dim_ = k; has_kpls_ = true; w_star_.clear(); return *this; }
+    GpParams &w_star(std::vector<double> w, int64_t k) { w_star_ = std::move(w); kpls_dim_ = k; has_kpls_ = true; return *this; }
     GpParams &n_start(int n) { n_start_ = n; return *this; }
     GpParams &max_eval(int n) { max_eval_ = n; return *this; }
     GpParams &nugget(double v) { nugget_ = v; return *this; }
@@ -168,6 +184,9 @@ class GpParams {
     double nugget_ = 100.0 * 2.220446049250313e-16;
     uint64_t seed_ = 42;
     int device_ = -1, n_workspaces_ = 1;
+    bool has_kpls_ = false;
+    int64_t kpls_dim_ = 0;
+    std::vector<double> w_star_;
 };
 
 // GaussianProcess, algorithm.rs:174-440
@@ -279,6 +298,7 @@ class GaussianProcess {
     double likelihood() const { return likelihood_; }             // :428-431
     std::pair<int64_t, int64_t> dims() const { return {d_, 1}; }  // :436-439
     int64_t n_evals() const { return n_evals_; }
+    int64_t kpls_dim() const { return kpls_dim_; }  // the PLS components the model was fitted on; 0: none
     egx_gp *handle() const { return h_.get(); }
     // theta() / variance() / likelihood() read again from the handle after a fit that ran on it from outside (fit_lbfgs_group)
     void adopt_fit(int64_t n_evals) {
@@ -301,7 +321,7 @@ class GaussianProcess {
     std::unique_ptr<egx_gp, Deleter> h_;
     std::vector<double> theta_;
     double sigma2_ = 0.0, likelihood_ = 0.0;
-    int64_t d_ = 0, n_evals_ = 0;
+    int64_t d_ = 0, n_evals_ = 0, kpls_dim_ = 0;
 };
 
 // SparseGaussianProcess at given parameters, sparse_algorithm.rs:145-362 (the predict side; the multistart fit is egx_sgp_fit):
@@ -321,6 +341,12 @@ class SparseGaussianProcess {
     // KPLS weights (d x h row-major, 1 <= h <= d; nullptr with h = 0 clears them): egx_sgp_set_w_star.  Un-fits the model; theta
     // then has h components.  w_star(): (the weights, h); no weights and h = d when none are set.
     void set_w_star(const double *w, int64_t h) { check(egx_sgp_set_w_star(h_.get(), w, h)); }
+    // ... computed on the device from the training set the handle holds (egx_sgp_compute_w_star: no upload) and installed as
+    // set_w_star installs them; zeros on a constant response.  Returns the weights (d x k).
+    std::vector<double> compute_w_star(int64_t k) {
+        check(egx_sgp_compute_w_star(h_.get(), k));
+        return w_star().first;
+    }
     std::pair<std::vector<double>, int64_t> w_star() const {
         int64_t h = 0;
         check(egx_sgp_get_w_star(h_.get(), nullptr, &h));
@@ -442,6 +468,7 @@ class SparseGaussianProcess {
 inline std::vector<GaussianProcess> GpParams::fit_group(const double *x, const double *y, int64_t n, int64_t d, int32_t k) const {
     if (tuning_.kind == ThetaTuning::Kind::Partial)
         throw InvalidValueError(EGX_ERR_INVALID_VALUE, "fit_group: ThetaTuning::Fixed or ::Full");
+    if (has_kpls_) throw InvalidValueError(EGX_ERR_INVALID_VALUE, "fit_group: kpls_dim / w_star are not supported, fit the members one by one");
     egx_gp_config cfg;
     egx_gp_config_default(&cfg);
     cfg.corr = (int32_t)corr_;
@@ -519,11 +546,24 @@ inline GaussianProcess GpParams::fit(const double *x, int64_t n, int64_t d, cons
     cfg.device = device_;
     const bool tuned = tuning_.kind != ThetaTuning::Kind::Fixed;
     cfg.n_workspaces = tuned ? std::max(1, std::min(n_workspaces_, n_start_ + 1)) : std::max(1, n_workspaces_);
+    std::vector<double> w;  // outlives egx_gp_create, which copies it
+    if (has_kpls_) {
+        if (w_star_.empty()) {
+            w = pls_rotations(x, y, n, d, kpls_dim_, device_);
+        } else {
+            if (kpls_dim_ < 1 || kpls_dim_ > d || w_star_.size() != (size_t)(d * kpls_dim_))
+                throw InvalidValueError(EGX_ERR_INVALID_VALUE, "w_star must hold d x kpls_dim values, 1 <= kpls_dim <= d");
+            w = w_star_;
+        }
+        cfg.w_star = w.data();
+        cfg.kpls_dim = kpls_dim_;
+    }
     egx_gp *raw = nullptr;
     check(egx_gp_create(&cfg, x, y, n, d, &raw));
     GaussianProcess gp;
     gp.h_.reset(raw);
     gp.d_ = d;
+    gp.kpls_dim_ = has_kpls_ ? kpls_dim_ : 0;
     int64_t hh = 0;
     check(egx_gp_dims(raw, nullptr, nullptr, nullptr, &hh));
     const size_t h = (size_t)hh;
